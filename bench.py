@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- hybrid BM25 + cosine + RRF top-100 queries/sec on MI355X (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[2]): 10M posts x 768-d f32 synthetic corpus,
@@ -15,7 +15,11 @@ their number, shape and statistics do not) and the per-shard lists are exchanged
 `python -m torch.distributed.run --nproc-per-node N ... bench.py ...`) BEFORE anything touches the GPU, relays
 rank 0's JSON line and exits with the child's code; under torch.distributed.run it is a rank.
 
-Prints ONE JSON line on rank 0 (see README/DESIGN.md for every field).
+Prints ONE JSON line on rank 0 (see README/DESIGN.md for every field).  A plain run sets up, warms up, times the K steps and
+prints the headline (value, ms_per_step, the roofline from the timed region's own kernel events); --full adds everything
+else the line can carry (other scorers, latency loops, isolated kernel times, CPU baselines, text paths, other configs).
+--dump-outputs DIR writes the last timed step's results (scores, docs, counts) as DIR/<name>.npy; the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -311,7 +315,7 @@ def other_configs():
             any(k.startswith("ROCPROF") for k in os.environ):
         return {"skipped": "running under rocprofv3: the children would be profiled into this run's statistics"}
     here = os.path.abspath(__file__)
-    common = ["--no-cpu-baseline", "--no-text-paths", "--no-other-configs", "--no-pipelined-side"]
+    common = ["--full", "--no-cpu-baseline", "--no-text-paths", "--no-other-configs", "--no-pipelined-side"]
     runs = {
         "config1_single_query": (["--docs", "1000000", "--batch", "1", "--depth", "100", "--steps", "300", "--warmup", "20"],
                                  "BASELINE configs[1]: 1M posts x 768-d f32, ONE query, hybrid top-100 (per-list depth 100)"),
@@ -403,7 +407,16 @@ def main():
     ap.add_argument("--cpu-sample-queries", type=int, default=64)
     ap.add_argument("--latency-batches", type=int, default=200, help="timed batches of the latency loops (SURVEY 8d: >= 200)")
     ap.add_argument("--latency-warmup", type=int, default=20, help="untimed batches before each latency loop (SURVEY 8d: 20)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline: isolated kernel times, the exact / "
+                         "f32-stream / pipelined scorers, the latency loops, the CPU baseline, the text paths and the other "
+                         "configurations (the --no-* switches above and the --latency-* / --cpu-* / --text-* sizes act on these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/scores.npy (f32 [B, k]), DIR/docs.npy and DIR/counts.npy "
+                         "(f64 [B, k] and [B]: global doc ids and valid entries per row, exact in f64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.lanes is None:
         args.lanes = 3 if args.exchange == "native" else 2
 
@@ -614,16 +627,19 @@ def main():
         lane_ctxs = [index.ctx for index, _ in pipe.lanes]   # every lane scores on a context of its own (lane 0 too)
 
     def step():
+        """One batch through the hot path; returns its (scores, docs, counts) on the device (final once fence() has run)."""
         qv, qt, qo = batches[step_no[0] % NB]
         step_no[0] += 1
         if world == 1 and not force_dist and not (pipe is not None and pipelined[0]):
             idx.search(qv, qt, qo, k=args.k, depth=args.depth, out=out)   # one C-ABI call: the whole query
-            return out.docs
+            return out.scores, out.docs, out.counts
         if pipe is not None and pipelined[0]:
-            return pipe.results[pipe.submit(qv, qt, qo)].docs
+            r = pipe.results[pipe.submit(qv, qt, qo)]
+            return r.scores, r.docs, r.counts
         if native_comm is not None:
-            return idx.search_sharded(native_comm, qv, qt, qo, k=args.k, depth=args.depth, out=out).docs   # one C-ABI call, RCCL inside
-        return sr.search(qv, qt, qo, args.k, args.depth, check=False)[1]  # overflow flag checked after the loops
+            r = idx.search_sharded(native_comm, qv, qt, qo, k=args.k, depth=args.depth, out=out)   # one C-ABI call, RCCL inside
+            return r.scores, r.docs, r.counts
+        return sr.search(qv, qt, qo, args.k, args.depth, check=False)  # overflow flag checked after the loops
 
     pipelined = [False]
 
@@ -662,7 +678,7 @@ def main():
     step_host, step_at = [], []
     for _ in range(args.steps):
         ts = time.perf_counter()
-        step()
+        last = step()
         step_host.append(time.perf_counter() - ts)
         step_at.append(ts - t0)
     t_enqueued = time.perf_counter() - t0    # (host time of the K calls alone: shows a host-bound loop)
@@ -672,6 +688,15 @@ def main():
         sys.stderr.write("[bench] step() entered at us: " + " ".join("%d" % (x * 1e6) for x in step_at) + "\n")
     fence()
     elapsed = time.perf_counter() - t0
+    # what the last timed step returned to its caller, copied out before any later step can overwrite it
+    last_scores, last_docs, last_counts = (x.cpu().numpy() for x in last)
+    # a result sanity check outside the timed region: every row full, ids in range
+    assert last_docs.shape == (args.batch, args.k) and last_docs.min() >= 0 and last_docs.max() < args.docs
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("scores", last_scores.astype(np.float32)), ("docs", last_docs.astype(np.float64)),
+                        ("counts", last_counts.astype(np.float64))):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     tm_own = elapsed
     tm = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
@@ -704,23 +729,24 @@ def main():
     # the CUs it lends to BM25 workgroups.  A few untimed steps with the legs one after the other give the
     # kernel's own duration as well (reported next to the live figure, never instead of it).
     iso_steps = max(1, min(5, args.steps))
-    ctx.set_overlap(False)
-    step()
-    fence()
-    ctx.profile_reset(True)
-    for _ in range(iso_steps):
+    if args.full:
+        ctx.set_overlap(False)
         step()
-    fence()
-    iso_ms, iso_launches = ctx.profile_read("cosine")
-    other = {t: ctx.profile_read(t) for t in ("bm25", "select", "rrf")}
-    ctx.profile_reset(False)
-    ctx.set_overlap(True)
+        fence()
+        ctx.profile_reset(True)
+        for _ in range(iso_steps):
+            step()
+        fence()
+        iso_ms, iso_launches = ctx.profile_read("cosine")
+        other = {t: ctx.profile_read(t) for t in ("bm25", "select", "rrf")}
+        ctx.profile_reset(False)
+        ctx.set_overlap(True)
 
     # The default scorer screens in bf16 and rescores exactly; the same batch through the exact f32 MFMA kernel for
     # every row is measured beside it (untimed steps), so that the line carries both scorers.
     exact_side = None
     stream_side = None
-    if args.cosine == "screen" and args.corpus == "f32" and args.batch > 8:
+    if args.full and args.cosine == "screen" and args.corpus == "f32" and args.batch > 8:
         gate_opened = ctx.profile_read("screen_gate")[0]
         ctx.set_cosine_mode(MODES["exact"])
         step()
@@ -744,7 +770,7 @@ def main():
     # rounds 1-4's default beside it: the same screen converting the f32 rows on the fly (4 d bytes per row instead of 2 d)
     # (batches of <= 8 queries too: there the f32 path is the exact GEMV)
     ex_steps = max(1, args.steps)
-    if copy_streamed and not args.no_stream_side and args.cosine == "screen" and args.corpus == "f32":
+    if args.full and copy_streamed and not args.no_stream_side and args.cosine == "screen" and args.corpus == "f32":
         ctx.set_cosine_mode(MODES["screen-stream"])
         step(); step()
         fence()
@@ -771,7 +797,7 @@ def main():
     # run for throughput) -- batch i+1's corpus stream beside the selects / rescoring / fusion of batch i.  A side number: the
     # headline stays one oi_search call per batch, one batch in flight, as in every earlier round.
     pipelined_side = None
-    if world == 1 and not force_dist and not args.no_pipelined_side and args.batch > 8:
+    if args.full and world == 1 and not force_dist and not args.no_pipelined_side and args.batch > 8:
         npipe = oi.NativePipeline(idx, lanes=2, max_queries=args.batch, max_query_terms=4, depth=args.depth, k=args.k)
         outs = [oi.SearchResult(torch.zeros((args.batch, args.k), dtype=torch.float32, device=dev),
                                 torch.zeros((args.batch, args.k), dtype=torch.int32, device=dev),
@@ -799,62 +825,58 @@ def main():
                                   "through lanes the library owns; NOT the headline (value = one oi_search call per batch, one batch in flight)"}
         npipe.close()
 
-    # ---------------------------------------------------------------- latency (SURVEY 8d): >= 200 timed batches after 20 warm-ups,
-    # whatever --steps says.  (a) device-resident: HIP events on the launch stream around ONE batch at a time (queries and
-    # results in HBM), plus the host's wall clock around the same batch (call + sync); (b) host-inclusive: the OI_HOST entry
-    # point -- H2D of the queries (196 KB of vectors + terms at B=64), the whole query, D2H of the top-k -- wall clock.
-    NL, NW = max(1, args.latency_batches), max(0, args.latency_warmup)
-
     def pct(v, p):
         v = sorted(v)
         return v[min(len(v) - 1, max(0, int(round(p * (len(v) - 1)))))]
 
-    for _ in range(NW):
-        step()
-    fence()
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(NL)]
-    lat_wall = []
-    for a, b in ev:
-        if world > 1:
-            dist.barrier()          # ranks enter every batch together (a collective inside would wait for the slowest anyway)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        a.record()
-        step()
-        b.record()
-        torch.cuda.synchronize()
-        lat_wall.append((time.perf_counter() - t1) * 1e3)
-    lat = [a.elapsed_time(b) for a, b in ev]
+    # ---------------------------------------------------------------- latency (SURVEY 8d): >= 200 timed batches after 20 warm-ups,
+    # whatever --steps says.  (a) device-resident: HIP events on the launch stream around ONE batch at a time (queries and
+    # results in HBM), plus the host's wall clock around the same batch (call + sync); (b) host-inclusive: the OI_HOST entry
+    # point -- H2D of the queries (196 KB of vectors + terms at B=64), the whole query, D2H of the top-k -- wall clock.
+    if args.full:
+        NL, NW = max(1, args.latency_batches), max(0, args.latency_warmup)
+        for _ in range(NW):
+            step()
+        fence()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(NL)]
+        lat_wall = []
+        for a, b in ev:
+            if world > 1:
+                dist.barrier()          # ranks enter every batch together (a collective inside would wait for the slowest anyway)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            a.record()
+            step()
+            b.record()
+            torch.cuda.synchronize()
+            lat_wall.append((time.perf_counter() - t1) * 1e3)
+        lat = [a.elapsed_time(b) for a, b in ev]
 
-    host_batches = [tuple(x.cpu().numpy() for x in b) for b in batches]
-    host_batches = [(qv, qt.view(np.uint32) if qt.dtype != np.uint32 else qt, qo.view(np.uint32) if qo.dtype != np.uint32 else qo)
-                    for qv, qt, qo in host_batches]
+        host_batches = [tuple(x.cpu().numpy() for x in b) for b in batches]
+        host_batches = [(qv, qt.view(np.uint32) if qt.dtype != np.uint32 else qt, qo.view(np.uint32) if qo.dtype != np.uint32 else qo)
+                        for qv, qt, qo in host_batches]
 
-    def host_step(i):
-        qv, qt, qo = host_batches[i % NB]
-        if world == 1 and not force_dist:
-            return idx.search(qv, qt, qo, k=args.k, depth=args.depth).docs     # OI_HOST: numpy in, numpy out, synchronous
-        if native_comm is not None:
-            return idx.search_sharded(native_comm, qv, qt, qo, k=args.k, depth=args.depth).docs       # OI_HOST through the library
-        d = [torch.from_numpy(x.view(np.int32) if x.dtype == np.uint32 else x).to(dev) for x in (qv, qt, qo)]
-        return sr.search(d[0], d[1], d[2], args.k, args.depth, check=False)[1].cpu().numpy()
+        def host_step(i):
+            qv, qt, qo = host_batches[i % NB]
+            if world == 1 and not force_dist:
+                return idx.search(qv, qt, qo, k=args.k, depth=args.depth).docs     # OI_HOST: numpy in, numpy out, synchronous
+            if native_comm is not None:
+                return idx.search_sharded(native_comm, qv, qt, qo, k=args.k, depth=args.depth).docs       # OI_HOST through the library
+            d = [torch.from_numpy(x.view(np.int32) if x.dtype == np.uint32 else x).to(dev) for x in (qv, qt, qo)]
+            return sr.search(d[0], d[1], d[2], args.k, args.depth, check=False)[1].cpu().numpy()
 
-    for i in range(NW):
-        host_step(i)
-    fence()
-    lat_host = []
-    for i in range(NL):
-        if world > 1:
-            dist.barrier()
-        t1 = time.perf_counter()
-        host_step(i)
-        lat_host.append((time.perf_counter() - t1) * 1e3)
-    fence()
-    ctx.synchronize()
-
-    # a result sanity check outside the timed region: every row full, ids in range
-    docs = step().cpu().numpy()
-    assert docs.shape == (args.batch, args.k) and docs.min() >= 0 and docs.max() < args.docs
+        for i in range(NW):
+            host_step(i)
+        fence()
+        lat_host = []
+        for i in range(NL):
+            if world > 1:
+                dist.barrier()
+            t1 = time.perf_counter()
+            host_step(i)
+            lat_host.append((time.perf_counter() - t1) * 1e3)
+        fence()
+        ctx.synchronize()
 
     if rank == 0:
         qps = args.batch * args.steps / elapsed
@@ -926,10 +948,11 @@ def main():
             # so the per-launch figure above understates the rate the corpus is streamed at; the step-level figure does not
             roof["overlapped_launches"] = ("%d batches in flight per rank: launch durations overlap and are summed as measured "
                                            "(frac understates the kernel); see step_level and isolated" % len(pipe.lanes))
-        roof["isolated"] = {"avg_launch_ms": iso_ms / max(1, iso_launches),
-                            "frac": (flops_step if roof["bound"] == "mfma" else bytes_step) * iso_steps / (iso_ms / 1e3)
-                            / (1e12 if roof["bound"] == "mfma" else 1e9) / roof["peak"],
-                            "note": "%d extra untimed steps with the legs serialised" % iso_steps}
+        if args.full:
+            roof["isolated"] = {"avg_launch_ms": iso_ms / max(1, iso_launches),
+                                "frac": (flops_step if roof["bound"] == "mfma" else bytes_step) * iso_steps / (iso_ms / 1e3)
+                                / (1e12 if roof["bound"] == "mfma" else 1e9) / roof["peak"],
+                                "note": "%d extra untimed steps with the legs serialised" % iso_steps}
         line = {
             "metric": "queries/sec + p50 latency, 10M-post/768-d hybrid BM25+cosine+RRF top-100",
             "value": qps, "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -971,25 +994,28 @@ def main():
                        "backend": (backend if (world > 1 or force_dist) else None),
                        "forced_process_group_of_one": force_dist,
                        "per_rank": per_rank},
-            "p50_ms": pct(lat, 0.5), "p95_ms": pct(lat, 0.95),
-            "p50_host_ms": pct(lat_host, 0.5), "p95_host_ms": pct(lat_host, 0.95),
-            "latency": {"batches": NL, "warmup": NW,
-                        "device": {"p50_ms": pct(lat, 0.5), "p95_ms": pct(lat, 0.95), "min_ms": min(lat), "max_ms": max(lat),
-                                   "clock": "HIP events on the launch stream around one batch; queries and results resident in HBM"},
-                        "device_wall": {"p50_ms": pct(lat_wall, 0.5), "p95_ms": pct(lat_wall, 0.95),
-                                        "clock": "host perf_counter around the same batch: call + stream sync"},
-                        "host_inclusive": {"p50_ms": pct(lat_host, 0.5), "p95_ms": pct(lat_host, 0.95), "min_ms": min(lat_host), "max_ms": max(lat_host),
-                                           "clock": "host perf_counter around the OI_HOST entry point: H2D of %d query bytes, the query, D2H of %d result bytes"
-                                                    % (sum(int(x.nbytes) for x in host_batches[0]), args.batch * args.k * 8 + args.batch * 4)},
-                        "note": "rank 0's clocks; one batch in flight at a time (the timed throughput region above pipelines batches when N > 1)"},
             "roofline": roof,
-            "other_kernels_ms_per_step": dict({t: v[0] / iso_steps for t, v in other.items()},
-                                              note="from the %d serialised steps, not the timed region" % iso_steps),
             "build_s": t_build,
         }
+        if args.full:
+            line.update({
+                "p50_ms": pct(lat, 0.5), "p95_ms": pct(lat, 0.95),
+                "p50_host_ms": pct(lat_host, 0.5), "p95_host_ms": pct(lat_host, 0.95),
+                "latency": {"batches": NL, "warmup": NW,
+                            "device": {"p50_ms": pct(lat, 0.5), "p95_ms": pct(lat, 0.95), "min_ms": min(lat), "max_ms": max(lat),
+                                       "clock": "HIP events on the launch stream around one batch; queries and results resident in HBM"},
+                            "device_wall": {"p50_ms": pct(lat_wall, 0.5), "p95_ms": pct(lat_wall, 0.95),
+                                            "clock": "host perf_counter around the same batch: call + stream sync"},
+                            "host_inclusive": {"p50_ms": pct(lat_host, 0.5), "p95_ms": pct(lat_host, 0.95), "min_ms": min(lat_host), "max_ms": max(lat_host),
+                                               "clock": "host perf_counter around the OI_HOST entry point: H2D of %d query bytes, the query, D2H of %d result bytes"
+                                                        % (sum(int(x.nbytes) for x in host_batches[0]), args.batch * args.k * 8 + args.batch * 4)},
+                            "note": "rank 0's clocks; one batch in flight at a time (the timed throughput region above pipelines batches when N > 1)"},
+                "other_kernels_ms_per_step": dict({t: v[0] / iso_steps for t, v in other.items()},
+                                                  note="from the %d serialised steps, not the timed region" % iso_steps),
+            })
         # BM25 leg: term-at-a-time reads 8 B per posting of the batch's terms + 8 B per (doc block, term) bounds
         # lookup; its kernels' time comes from the serialised steps above (the leg runs beside the cosine leg otherwise).
-        if bm25_bytes is not None and other["bm25"][0] > 0:
+        if args.full and bm25_bytes is not None and other["bm25"][0] > 0:
             bm_ms = other["bm25"][0] / iso_steps
             line["bm25_roofline"] = {"bound": "hbm", "achieved": bm25_bytes / (bm_ms / 1e3) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
                                      "frac": bm25_bytes / (bm_ms / 1e3) / 1e9 / PEAK_HBM_GBS, "kernel_ms_per_step": bm_ms,
@@ -1018,12 +1044,12 @@ def main():
             line["f32_stream_scorer"] = stream_side
         if pipelined_side is not None:
             line["pipelined_native"] = pipelined_side
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg is timed on rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg is timed on rank 0 at N=1 only
             line["cpu_baseline"] = cpu_baseline(args.docs, args.dim, args.vocab, args.depth, args.k,
                                                 args.cpu_sample_docs, args.cpu_sample_queries)
-        if not args.no_text_paths and world == 1:    # the reference-pinned paths, on rank 0 at N=1 (their own inputs; outside the timed region)
+        if args.full and not args.no_text_paths and world == 1:    # the reference-pinned paths, on rank 0 at N=1 (their own inputs; outside the timed region)
             line.update(text_paths(oi, ctx, dev, args.text_items, 10, args.text_cpu_sample))
-        if (not args.no_other_configs and world == 1 and not force_dist and
+        if (args.full and not args.no_other_configs and world == 1 and not force_dist and
                 (args.docs, args.dim, args.batch, args.corpus, args.cosine) == (10_000_000, 768, 64, "f32", "screen")):
             line["other_configs"] = other_configs()
         line["library"] = os.path.relpath(_oil.LIB_PATH, ROOT)   # what was measured (the package loader has no override)

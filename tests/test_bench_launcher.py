@@ -94,7 +94,7 @@ def test_other_configs_keeps_the_childs_headline_fields_and_never_raises(monkeyp
 
     def fake_run(cmd, capture_output=True, text=True, timeout=None):
         calls.append(cmd)
-        assert "--no-other-configs" in cmd and "--no-cpu-baseline" in cmd and cmd[1].endswith("bench.py")
+        assert "--full" in cmd and "--no-other-configs" in cmd and "--no-cpu-baseline" in cmd and cmd[1].endswith("bench.py")
         if "--corpus" in cmd:            # the configs[4] shard: a child that dies
             return sp.CompletedProcess(cmd, 3, stdout="", stderr="boom")
         line = {"value": 2900.0, "ms_per_step": 0.34, "p50_ms": 0.33, "p95_ms": 0.35, "steps": 300, "dtype": "f32",

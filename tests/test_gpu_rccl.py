@@ -123,7 +123,7 @@ def _run_bench(extra_env, argv):
     return json.loads(lines[0])
 
 
-SMALL = ["--docs", "200000", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-screen-copy", "--latency-batches", "20",
+SMALL = ["--full", "--docs", "200000", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-screen-copy", "--latency-batches", "20",
          "--latency-warmup", "3", "--vocab", "4096"]
 
 

@@ -9,9 +9,9 @@ mkdir -p $OUT
 for cfg in "8 1" "16 1" "32 1" "64 1" "16 2" "8 1"; do
   set -- $cfg
   export OI_CHUNK_GROWTH=$1 OI_FIRST_CHUNK_MULT=$2
-  timeout -k 10 200 python3 $R/bench.py --no-cpu-baseline --steps 30 > $OUT/full_$1_$2.json || exit 1
+  timeout -k 10 200 python3 $R/bench.py --full --no-cpu-baseline --steps 30 > $OUT/full_$1_$2.json || exit 1
   timeout -k 10 100 python3 $R/tools/shard_step_bench.py 1250000 50 > $OUT/shard_$1_$2.json || exit 1
-  timeout -k 10 100 python3 $R/bench.py --docs 1000000 --batch 1 --depth 100 --steps 300 --no-cpu-baseline > $OUT/b1_$1_$2.json || exit 1
+  timeout -k 10 100 python3 $R/bench.py --full --docs 1000000 --batch 1 --depth 100 --steps 300 --no-cpu-baseline > $OUT/b1_$1_$2.json || exit 1
   python3 - <<P
 import json
 f=json.load(open("$OUT/full_$1_$2.json")); s=json.load(open("$OUT/shard_$1_$2.json")); b=json.load(open("$OUT/b1_$1_$2.json"))

@@ -14,7 +14,7 @@ modes = [int(m) for m in sys.argv[1].split(",")] if len(sys.argv) > 1 else [0, 4
 extra = sys.argv[2:]
 for m in modes:
     env = dict(os.environ, OI_KS_DEBUG=str(m))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "6", "--warmup", "2",
                         "--no-cpu-baseline", *extra], env=env, capture_output=True, text=True)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if not line:

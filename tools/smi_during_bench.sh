@@ -4,7 +4,7 @@
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/smi
 mkdir -p $OUT
-python3 $R/bench.py --steps 400 --warmup 20 --no-cpu-baseline --latency-batches 200 > $OUT/bench.json 2> $OUT/bench.err &
+python3 $R/bench.py --full --steps 400 --warmup 20 --no-cpu-baseline --latency-batches 200 > $OUT/bench.json 2> $OUT/bench.err &
 BP=$!
 for i in $(seq 1 60); do
   if ! kill -0 $BP 2>/dev/null; then break; fi
