@@ -9,10 +9,13 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _case(n=60_001, dim=384, vocab=300, B=64, seed=21, n_batches=9):
+def _case(n=60_001, dim=384, vocab=300, B=64, seed=21, n_batches=9, bf16=False):
     rng = np.random.default_rng(seed)
     from openintel_amd import synth
     rows = synth.embeddings_np(n, dim, seed=seed)
+    if bf16:                                            # bfloat16 bit patterns (round to nearest even) of the same rows
+        u = rows.view(np.uint32).astype(np.uint64)
+        rows = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
     lens = rng.integers(1, 12, size=n)
     offs = np.zeros(n + 1, np.uint64)
     offs[1:] = np.cumsum(lens)
@@ -30,7 +33,10 @@ def _case(n=60_001, dim=384, vocab=300, B=64, seed=21, n_batches=9):
 def _index(ctx, rows, terms, offs, vocab=300, base=700):
     import openintel_amd as oi
     idx = oi.HybridIndex(ctx, rows.shape[0], rows.shape[1], vocab, doc_id_base=base)
-    idx.set_embeddings(rows.copy(), normalize=False)
+    if rows.dtype == np.uint16:
+        idx.set_embeddings_bf16(rows)                   # a bf16 corpus (csrc/cosine_bf16.hip)
+    else:
+        idx.set_embeddings(rows.copy(), normalize=False)
     idx.set_forward(terms, offs)
     idx.finalize()
     return idx
@@ -43,16 +49,19 @@ def _same(got, want):
             and np.array_equal(g[0].view(np.uint32), w[0].view(np.uint32)))
 
 
-@pytest.mark.parametrize("lanes", [1, 2, 3])
-def test_pipeline_equals_oi_search_bit_for_bit_host_and_device(lanes):
+@pytest.mark.parametrize("lanes,corpus", [(1, "f32"), (2, "f32"), (3, "f32"), (2, "bf16")], ids=["1", "2", "3", "2-bf16"])
+def test_pipeline_equals_oi_search_bit_for_bit_host_and_device(lanes, corpus):
+    """(bf16: a d = 1024 bf16 corpus of 60001 rows, batches of up to 256 queries -- the sibling kernel on both chunks of the
+    full batches, the 128-query kernels on the ragged ones.)"""
     import torch
     import openintel_amd as oi
     K, DEPTH = 50, 200
-    rows, terms, offs, batches = _case()
+    MAXQ = 256 if corpus == "bf16" else 64
+    rows, terms, offs, batches = _case(dim=1024, B=256, bf16=True) if corpus == "bf16" else _case()
     ctx = oi.HipContext(0)
     idx = _index(ctx, rows, terms, offs)
     want = [idx.search(q, qt, qo, k=K, depth=DEPTH) for q, qt, qo in batches]
-    pipe = oi.NativePipeline(idx, lanes=lanes, max_queries=64, max_query_terms=4, depth=DEPTH, k=K)
+    pipe = oi.NativePipeline(idx, lanes=lanes, max_queries=MAXQ, max_query_terms=4, depth=DEPTH, k=K)
     assert pipe.workspace_bytes()[0] > 0
     conc, total = pipe.concurrent_streams()
     assert total == lanes + 1 and 1 <= conc <= total
@@ -83,7 +92,8 @@ def test_pipeline_equals_oi_search_bit_for_bit_host_and_device(lanes):
     # errors are loud
     from openintel_amd._lib import OiError
     with pytest.raises(OiError):
-        pipe.submit(np.zeros((65, rows.shape[1]), np.float32), np.zeros(260, np.uint32), (np.arange(66) * 4).astype(np.uint32))
+        pipe.submit(np.zeros((MAXQ + 1, rows.shape[1]), np.float32), np.zeros(4 * MAXQ + 4, np.uint32),
+                    (np.arange(MAXQ + 2) * 4).astype(np.uint32))
     with pytest.raises(OiError):
         pipe.wait(10_000)
     pipe.close()
@@ -134,21 +144,26 @@ def test_pipeline_survives_any_destruction_order():
     idx.close()
 
 
-@pytest.mark.parametrize("mode", ["copy", "stream"])
+@pytest.mark.parametrize("mode", ["copy", "stream", "bf16"])
 def test_concurrent_lanes_return_the_serial_lists_bit_for_bit(mode):
     """Round 5's co-residency finding (csrc/oi_device.h; profiles/r05_coresidency_probe.txt): with lanes that REALLY run at the same
     time (eight hardware queues), a pf_rescore_kernel wave scheduled on a CU beside a d = 384 screen workgroup of another lane lost
     one product of its packed fma chain -- one wrong exact cosine score in 2-11 % of the batches.  The MFMA kernels now take their
     CUs whole and the rescoring chain is single v_fma_f32.  Three lanes, their own streams, views of one index, rotating ragged
     batches, 40 rounds (360 batches; the unfixed library failed 10-40 of them): every packed pair of lists must be the serial
-    call's, word for word."""
+    call's, word for word.  mode "bf16": the same with a d = 1024 bf16 corpus and batches of up to 256 queries (the MFMA kernels
+    of csrc/cosine_bf16.hip, siblings among them, beside each other on concurrent lanes)."""
     import torch
     import openintel_amd as oi
     from openintel_amd import _lib
     DEPTH, LANES, ROUNDS = 200, 3, 40
-    rows, terms, offs, batches = _case()                       # d = 384: the screen wave leaves room on its SIMD unless it claims it
+    if mode == "bf16":
+        rows, terms, offs, batches = _case(dim=1024, B=256, bf16=True)
+    else:
+        rows, terms, offs, batches = _case()                   # d = 384: the screen wave leaves room on its SIMD unless it claims it
     ctx = oi.HipContext(0)
-    ctx.set_cosine_mode(_lib.OI_COSINE_SCREEN if mode == "copy" else _lib.OI_COSINE_SCREEN_STREAM)
+    if mode != "bf16":
+        ctx.set_cosine_mode(_lib.OI_COSINE_SCREEN if mode == "copy" else _lib.OI_COSINE_SCREEN_STREAM)
     idx = _index(ctx, rows, terms, offs)
     if mode == "copy":
         assert idx.index_bytes()[1] > 0                        # (made by default at this size)
