@@ -812,7 +812,7 @@ extern "C" int oi_index_view(oi_index *src, oi_ctx *ctx, oi_index **out) {
     v->total_tokens = src->total_tokens; v->n_postings = src->n_postings; v->n_blocks = src->n_blocks; v->n_win = src->n_win;
     v->avgdl = src->avgdl; v->max_query_terms = src->max_query_terms; v->bm25_mode = src->bm25_mode;
     auto alias = [](DevBuf &dst, const DevBuf &from) { dst.p = from.p; dst.cap = from.cap; dst.borrowed = from.p != nullptr; };
-    alias(v->max_row_norm, src->max_row_norm); alias(v->screen_copy, src->screen_copy);
+    alias(v->max_row_norm, src->max_row_norm); alias(v->screen_copy, src->screen_copy); alias(v->screen_i8, src->screen_i8);
     alias(v->uniq_keys, src->uniq_keys); alias(v->tf, src->tf); alias(v->doc_len, src->doc_len); alias(v->df_local, src->df_local);
     alias(v->postings, src->postings); alias(v->cell_start, src->cell_start); alias(v->idf, src->idf);
     alias(v->impact_floor, src->impact_floor);
@@ -838,6 +838,7 @@ static void index_release(oi_index *idx) {
         idx->uniq_keys.release(); idx->tf.release(); idx->doc_len.release(); idx->df_local.release();
         idx->postings.release(); idx->cell_start.release(); idx->idf.release();
         idx->fwd_terms.release(); idx->fwd_offsets.release(); idx->max_row_norm.release(); idx->screen_copy.release();
+        idx->screen_i8.release();
     }
     delete idx;
     if (src) index_release(src);
@@ -872,11 +873,19 @@ static int apply_screen_copy_policy(oi_index *idx) {
     const int policy = idx->screen_copy_policy < 0 ? default_screen_copy_policy() : idx->screen_copy_policy;
     const bool possible = idx->rows && !idx->rows_bf16 && idx->screen_ok && oi_cosine_screen_supported(idx->dim);
     if (policy == OI_SCREEN_COPY_NEVER || !possible) {
-        if (idx->screen_copy.p) { OI_HIP_CHECK(hipStreamSynchronize(ctx->stream)); idx->screen_copy.release(); }
+        if (idx->screen_copy.p || idx->screen_i8.p) {
+            OI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            idx->screen_copy.release();
+            idx->screen_i8.release();
+        }
         return OI_OK;
     }
-    if (idx->screen_copy.p) return OI_OK; // (set_embeddings releases a copy of the previous rows)
+    if (idx->screen_copy.p) return OI_OK; // (set_embeddings releases the copies of the previous rows)
+    // The bf16 copy and, in front of it, the int8 copy of the first screening tier (cosine_screen_i8.hip): AUTO makes both when
+    // both fit the budget, the bf16 one alone when only it does
     const size_t bytes = sizeof(uint16_t) * (size_t)idx->n_docs * idx->dim + 64;
+    const size_t bytes_i8 = oi_screen_i8_bytes(idx->n_docs, idx->dim);
+    bool with_i8 = true;
     if (policy == OI_SCREEN_COPY_AUTO) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return OI_OK; // no figure, no copy
@@ -886,9 +895,15 @@ static int apply_screen_copy_policy(oi_index *idx) {
             return f > 0.0 && f <= 1.0 ? f : 0.25;
         }();
         if ((double)bytes > frac * (double)free_b) return OI_OK;
+        with_i8 = (double)(bytes + bytes_i8) <= frac * (double)free_b;
     }
     OI_CHECK(idx->screen_copy.ensure(bytes));
     OI_CHECK(oi_launch_make_screen_copy(ctx, idx->rows, idx->n_docs, idx->dim, idx->screen_copy.as<uint16_t>()));
+    if (with_i8) {
+        OI_CHECK(idx->screen_i8.ensure(bytes_i8));
+        OI_CHECK(oi_launch_make_screen_i8(ctx, idx->rows, idx->n_docs, idx->dim, idx->n_long ? idx->long_bitmap.as<uint32_t>() : nullptr,
+                                          idx->screen_i8.as<uint8_t>()));
+    }
     OI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return OI_OK;
 }
@@ -913,7 +928,9 @@ extern "C" int oi_index_bytes(oi_index *idx, uint64_t *rows_owned, uint64_t *scr
     if (rows_owned)
         *rows_owned = (idx->rows_owned ? sizeof(float) * (uint64_t)idx->n_docs * idx->dim : 0) +
                       (idx->rows_bf16_owned ? sizeof(uint16_t) * (uint64_t)idx->n_docs * idx->dim : 0);
-    if (screen_copy) *screen_copy = idx->screen_copy.p && !idx->screen_copy.borrowed ? (uint64_t)idx->screen_copy.cap : 0;
+    if (screen_copy)
+        *screen_copy = (idx->screen_copy.p && !idx->screen_copy.borrowed ? (uint64_t)idx->screen_copy.cap : 0) +
+                       (idx->screen_i8.p && !idx->screen_i8.borrowed ? (uint64_t)idx->screen_i8.cap : 0);
     if (bm25) {
         uint64_t b = 0;
         for (const DevBuf *d : {&idx->uniq_keys, &idx->tf, &idx->doc_len, &idx->df_local, &idx->postings, &idx->cell_start, &idx->idf,
@@ -937,6 +954,7 @@ extern "C" int oi_index_set_embeddings(oi_index *idx, float *rows, int location,
     if (idx->rows_bf16_owned && idx->rows_bf16) (void)hipFree(idx->rows_bf16);
     idx->rows_bf16 = nullptr; idx->rows_bf16_owned = false;
     idx->screen_copy.release(); // a copy of the previous rows
+    idx->screen_i8.release();
     const size_t bytes = (size_t)idx->n_docs * idx->dim * sizeof(float);
     if (location == OI_DEVICE) {
         OI_REQUIRE(((uintptr_t)rows & 15u) == 0, "index: embedding matrix must be 16-byte aligned");
@@ -1002,6 +1020,7 @@ extern "C" int oi_index_set_embeddings_bf16(oi_index *idx, const uint16_t *rows,
     if (idx->rows_owned && idx->rows) (void)hipFree(idx->rows);
     idx->rows = nullptr; idx->rows_owned = false;
     idx->screen_copy.release(); // (a copy of f32 rows that are gone)
+    idx->screen_i8.release();
     if (idx->rows_bf16_owned && idx->rows_bf16) (void)hipFree(idx->rows_bf16);
     idx->rows_bf16 = nullptr; idx->rows_bf16_owned = false;
     const size_t bytes = (size_t)idx->n_docs * idx->dim * sizeof(uint16_t);
@@ -1202,8 +1221,12 @@ int search_lists_device(oi_index *idx, const float *d_qv, const uint32_t *d_qt, 
     if (cos_stride > budget) cos_stride = budget;
     if (cos_stride < carry_cap + 4 * slack) cos_stride = carry_cap + 4 * slack;
     if (cos_stride > carry_cap + n + slack) cos_stride = carry_cap + n + slack;
-    // the screen's view of the same buffer keeps up to 4096 keys per query between chunks and rounds its segments to 4 tiles
-    const uint32_t pf_carry = 4096;
+    // the screen's view of the same buffer keeps up to 4096 keys per query between chunks and rounds its segments to 4 tiles; with
+    // the int8 first tier (cosine_screen_i8.hip: the index holds both screening copies, B > 8) up to OI_I8_CARRY
+    const bool i8_tier = cos_s && idx->rows && !idx->rows_bf16 && idx->screen_copy.p && idx->screen_i8.p && B > 8 && idx->screen_ok &&
+                         oi_cosine_screen_supported(idx->dim) &&
+                         (ctx->cosine_mode == OI_COSINE_SCREEN || ctx->cosine_mode == OI_COSINE_SCREEN_COPY);
+    const uint32_t pf_carry = i8_tier ? OI_I8_CARRY : 4096;
     const uint64_t pf_slack = 128ull * ((uint64_t)ctx->num_cus + 1);
     uint64_t pf_stride = 1ull << 24;
     if (pf_stride > budget) pf_stride = budget;
@@ -1565,6 +1588,32 @@ int search_lists_device(oi_index *idx, const float *d_qv, const uint32_t *d_qt, 
                 OI_CHECK(idx->screen_copy.ensure(sizeof(uint16_t) * (size_t)n * idx->dim + 64));
                 OI_CHECK(oi_launch_make_screen_copy(ctx, idx->rows, n, idx->dim, idx->screen_copy.as<uint16_t>()));
             }
+            // The int8 first tier (cosine_screen_i8.hip): the chunks stream the int8 copy against per-row bounds, the
+            // margin selects keep up to OI_I8_CARRY lower-bound keys per query (an overflow opens the gate), the speculation works on
+            // those keys; after the last chunk the survivors get their bf16 screen keys from the bf16 copy and the bf16 screen's
+            // final margin select, rescoring and gate follow unchanged.
+            const bool i8 = i8_tier && want_copy;
+            OI_REQUIRE(!i8 || pf_carry == OI_I8_CARRY, "search: int8 tier without its carry");
+            int8_t *qi8 = nullptr;
+            float *qf8 = nullptr;
+            SelectExtra m8 = mx;
+            if (i8) {
+                DevBuf &qs = ctx->buf("screen_q_i8"), &cb = ctx->buf("screen_i8_cand");
+                const size_t qi8_bytes = ((2 * (size_t)n_padded * idx->dim) + 255) & ~(size_t)255;
+                OI_CHECK(qs.ensure(qi8_bytes + sizeof(float) * 4 * (size_t)n_padded));
+                OI_CHECK(cb.ensure(sizeof(uint64_t) * (size_t)B * OI_I8_CARRY));
+                qi8 = reinterpret_cast<int8_t *>(qs.p);
+                qf8 = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(qs.p) + qi8_bytes);
+                OI_CHECK(oi_launch_screen_stage_i8(ctx, d_qv, B, idx->dim, idx->max_row_norm.as<uint32_t>(), idx->screen_i8.as<uint8_t>(), n,
+                                                   qi8, qf8, gate));
+                m8.eps2 = qf8 + 3 * (size_t)n_padded;
+                m8.cand = cb.as<uint64_t>();
+                m8.cand_cap = OI_I8_CARRY;
+                m8.row_meta = reinterpret_cast<const float *>(idx->screen_i8.as<uint8_t>() + oi_screen_i8_meta_offset(n, idx->dim));
+                m8.meta_base = idx->doc_id_base;
+                m8.row_qn = qf8 + (size_t)n_padded;
+                m8.row_cq = qf8 + 2 * (size_t)n_padded;
+            }
             // Speculative thresholds (decided above: spec_on, screen_growth): the next chunk is screened against the larger of
             // the proven threshold and a prediction from the rows seen so far, checked at the end (a failed check opens the gate).
             const bool spec = spec_on;
@@ -1579,12 +1628,13 @@ int search_lists_device(oi_index *idx, const float *d_qv, const uint32_t *d_qt, 
                 if (late_pending && e == n) OI_HIP_CHECK(hipEventRecord(ctx->ev_fork, st)); // (before the last chunk's launch)
                 uint32_t *const proven_tau = PF.tau_keys;
                 if (spec_next) PF.tau_keys = spec_tau; // (this launch only: the selects keep the proven thresholds)
-                const int rc_screen = want_copy ? oi_launch_cosine_screen_copy_chunk(ctx, idx->screen_copy.as<uint16_t>(), r, e, idx->dim, qb.as<uint16_t>(), B, idx->doc_id_base, PF)
-                                                : oi_launch_cosine_screen_chunk(ctx, idx->rows, r, e, idx->dim, qb.as<uint16_t>(), B, idx->doc_id_base, PF);
+                const int rc_screen = i8 ? oi_launch_cosine_screen_i8_chunk(ctx, idx->screen_i8.as<uint8_t>(), n, r, e, idx->dim, qi8, qf8, B, idx->doc_id_base, PF)
+                                      : want_copy ? oi_launch_cosine_screen_copy_chunk(ctx, idx->screen_copy.as<uint16_t>(), r, e, idx->dim, qb.as<uint16_t>(), B, idx->doc_id_base, PF)
+                                                  : oi_launch_cosine_screen_chunk(ctx, idx->rows, r, e, idx->dim, qb.as<uint16_t>(), B, idx->doc_id_base, PF);
                 PF.tau_keys = proven_tau;
                 OI_CHECK(rc_screen);
                 if (late_pending && e == n) { late_pending = false; OI_CHECK(fork_bm25()); } // ... enqueued after it: the screen's workgroups get their CUs first
-                OI_CHECK(oi_launch_select(ctx, PF, B, depth, /*compact=*/true, nullptr, nullptr, nullptr, depth, &mx));
+                OI_CHECK(oi_launch_select(ctx, PF, B, depth, /*compact=*/true, nullptr, nullptr, nullptr, depth, i8 ? &m8 : &mx));
                 r = e;
                 chunk *= screen_growth;
                 spec_next = false;
@@ -1592,15 +1642,26 @@ int search_lists_device(oi_index *idx, const float *d_qv, const uint32_t *d_qt, 
                     // expected rank of the final k'-th among the r rows seen: depth r / n; three times that plus twelve
                     const uint64_t rank = (3ull * depth * r + n - 1) / n + 12;
                     if (2 * rank <= depth) {
-                        OI_CHECK(oi_launch_spec_threshold(ctx, PF, B, (uint32_t)rank, eps2, spec_tau, spec_max));
+                        OI_CHECK(oi_launch_spec_threshold(ctx, PF, B, (uint32_t)rank, i8 ? m8.eps2 : eps2, spec_tau, spec_max));
                         spec_next = spec_any = true;
                     }
                 }
             }
             if (spec_any) ++ctx->spec_searches;
+            PoolView PR = PF; // what the rescoring reads: the bf16 screen's final survivors (<= 4096 per query)
+            if (i8) {
+                // the int8 survivors' bf16 keys (in place), then the bf16 screen's final margin select over them; the int8 tier's
+                // proven thresholds stay (the speculation check and the gated exact pipeline read them)
+                OI_CHECK(oi_launch_rescreen_bf16(ctx, idx->screen_copy.as<uint16_t>(), n, idx->dim, idx->doc_id_base, qb.as<uint16_t>(), B, PF));
+                PoolView PB = PF;
+                PB.tau_keys = nullptr;
+                PB.n_segs = 0;
+                OI_CHECK(oi_launch_select(ctx, PB, B, depth, /*compact=*/true, nullptr, nullptr, nullptr, depth, &mx));
+                PR.carry_cap = 4096;
+            }
             // (the check of the speculative thresholds against the proven final ones rides in the rescoring launch; the gated exact
             // pipeline is enqueued after it)
-            OI_CHECK(oi_launch_rescore(ctx, idx->rows, n, idx->dim, idx->doc_id_base, d_qv, B, PF, RS,
+            OI_CHECK(oi_launch_rescore(ctx, idx->rows, n, idx->dim, idx->doc_id_base, d_qv, B, PR, RS,
                                        idx->n_long ? idx->long_list.as<uint32_t>() : nullptr, idx->n_long,
                                        spec_any ? spec_max : nullptr, pf_tau, gate, ctx->spec_fail_host));
             RS.n_segs = 0;

@@ -1,0 +1,649 @@
+// cosine_screen_i8.hip -- the FIRST screening tier of an f32 corpus: an int8 copy of the rows (one byte per coordinate, a
+// per-row absmax scale) streamed in front of the bf16 screen, with a PER-ROW error bound.  DESIGN.md section 4.1a.
+//
+// Builder-defined like the rest of the retrieval path (the reference has none).
+//
+// Why.  The bf16 copy screen (cosine_screen_copy.hip) streams 2 d bytes per row and batch at the HBM rate: tuning it cannot make
+// it faster, reading fewer bytes can.  This tier reads d + 8 bytes per row (the i8 values, the row's f32 scale and its f32
+// error norm) and keeps every row that can still reach the list; its survivors (a few k' per query) are then given their bf16
+// screen keys from the bf16 copy (pf_rescreen_kernel, 2 d bytes per SURVIVOR) and the bf16 pipeline goes on unchanged: final
+// margin select, exact f32 rescoring, gate.
+//
+// The bound.  Row r: x^ = s_r i_r (i_r in [-127, 127], s_r = max |x_r| / 127), e_r >= |x^ - x_r| measured in f64 when the copy
+// is made and rounded up.  Query: q^ = a (h + l / 128), h, l in [-127, 127] (a = max |q| / 127, l the rounded remainder); the
+// products are two exact integer dot products, S_h = sum i h and S_l = sum i l (|S| <= d 127^2 < 2^24), and
+// S = 128 S_h + S_l (< 2^31) is exact in i32.  The screen score is s~ = f32(S) * f32(s_r a / 128) -- three roundings of 2^-24.
+//   x^ . q^ - x . q = (x^ - x) . q^ + x . (q^ - q), so |x^ . q^ - x . q| <= e_r |q^| + X |e_q|   (Cauchy-Schwarz)
+// with X = max |x_r| over the rows that are not long (the bf16 screen's X) and |e_q| = |q^ - q|, |q^| measured per query in f64.
+// The rescoring (an f32 chain) is off the exact dot by <= d 2^-22 |x| |q|, the three roundings of s~ and the few of the test by
+// far less than 2^-18 (|x^| |q^|).  So with
+//   m_r = e_r |q^| + c_q,   c_q = X |e_q| + (2^-18 + d 2^-22) (X + e_max) (|q^| + |e_q|)  (+ 1e-27 for flushed denormals)
+// the rescored f32 score s^ of every row that is not long lies in [l_r, u_r] = [s~ - m_r, s~ + m_r].  Hence:
+//   * keys are LOWER bounds l_r: the k'-th largest l so far, tau_l, is <= the k'-th largest s^ of the whole corpus, so every
+//     row of the exact list has u_r >= s^ >= tau_l: the kernel keeps (q, r) when u_r >= T, T <= tau_l (per row: the row's own e_r);
+//   * the margin select (select.hip, margin mode with eps2 = m2 = 2 max_r m_r) keeps every key with l >= tau_l - m2, a
+//     superset of the keys with u >= tau_l (l_r = u_r - 2 m_r >= u_r - m2), and stores tau_l - m2 as the threshold key;
+//   * the kernel adds m2 back: T = tau_stored + m2 - 2^-20 (|tau_stored| + m2) <= tau_l whatever the f32 rounding.
+// Every row of the exact list survives every chunk; the survivors' bf16 keys then go through the bf16 screen's final margin select,
+// which keeps every row whose bf16 score can reach the list (its threshold over a subset of the rows is only lower): the lists are
+// the exact rescoring of a superset of the exact list, the same lists as the bf16 screen's.  Long rows are skipped by the selects and
+// rescored whatever happens, as before.  A query without a bound (staging) has m2 = inf: it never gets a threshold, overflows and
+// opens the gate like the bf16 screen's.
+//
+// Kernel shape: cosine_copy_screen's.  One persistent workgroup on 7/8 of the CUs, 4 waves, a wave holds all 64 queries over the
+// whole K as i8 hi / lo B operands (384 VGPRs at d = 768, as the bf16 screen), owns whole 32-row tiles and streams them through its
+// own LDS ring of 4 KiB slots (32 rows x 128 i8) with buffer_load ... lds, ordered by counted s_waitcnt vmcnt.  Per 32 k of a tile:
+// one ds_read_b128, 2 NQT v_mfma_i32_32x32x32_i8 (the cycles of the bf16 32x32x16: the matrix time per tile is the bf16 screen's,
+// the bytes are half).  The tile's 32 {scale, e_r} pairs (256 B) ride one more LDS-DMA load, issued a tile ahead.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <type_traits>
+
+#include "oi_device.h"
+#include "oi_internal.h"
+
+typedef int i8s_i32x4 __attribute__((ext_vector_type(4)));
+typedef int i8s_i32x16 __attribute__((ext_vector_type(16)));
+typedef uint32_t i8s_u32x4 __attribute__((ext_vector_type(4)));
+typedef float i8s_f32x4 __attribute__((ext_vector_type(4)));
+
+#define I8S_TILE_ROWS 32
+#define I8S_SLOT_BYTES (I8S_TILE_ROWS * 128) // 32 rows x 128 i8 of K
+#define I8S_META_BYTES 256                   // 32 rows x {scale, e_r}
+#define I8S_STAGE 256
+#define I8S_STAGE_FLUSH 64u
+#define I8S_STAGE_LDS (4 * I8S_STAGE * 12)
+#define I8S_PAD_ROWS 64
+
+// ------------------------------------------------------------------ the copy
+size_t oi_screen_i8_meta_offset(uint64_t n, uint32_t dim) { return ((size_t)n * dim + 255) & ~(size_t)255; }
+size_t oi_screen_i8_bytes(uint64_t n, uint32_t dim) {
+    return oi_screen_i8_meta_offset(n, dim) + 8 * ((size_t)n + I8S_PAD_ROWS) + 256;
+}
+
+// One wave per row: absmax scale, i = rint(x / s) clamped to [-127, 127], e_r = |s i - x| in f64, rounded up to f32.  e_max over the
+// rows that are not long (long_bitmap, may be null) goes to the word after the metadata.
+__global__ __launch_bounds__(256) void i8s_make_kernel(const float *__restrict__ rows, uint64_t n, uint32_t dim,
+                                                       const uint32_t *__restrict__ long_bitmap, uint32_t *__restrict__ out_i8,
+                                                       float *__restrict__ meta, uint32_t *__restrict__ emax_bits) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    const uint32_t nv = dim >> 2; // float4 per row (96 / 192)
+    float best = 0.f;
+    for (uint64_t r = wave; r < n; r += n_waves) {
+        const float4 *x = reinterpret_cast<const float4 *>(rows + r * dim);
+        float4 v[3];
+        float amax = 0.f;
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const uint32_t j = lane + 64u * u;
+            v[u] = j < nv ? x[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+            amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)), fmaxf(fabsf(v[u].z), fabsf(v[u].w))));
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, OI_WAVE));
+        const float s = amax / 127.f;
+        double e2 = 0.0;
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const uint32_t j = lane + 64u * u;
+            const float xs[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+            uint32_t packed = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float t = s > 0.f ? rintf(xs[c] / s) : 0.f;
+                t = fminf(127.f, fmaxf(-127.f, t));
+                const int iv = (int)t;
+                const double e = (double)s * (double)iv - (double)xs[c]; // s * iv is exact in f64
+                e2 += j < nv ? e * e : 0.0;
+                packed |= ((uint32_t)iv & 0xFFu) << (8 * c);
+            }
+            if (j < nv) out_i8[r * nv + j] = packed;
+        }
+        e2 = oi_wave_sum(e2);
+        const float er = (float)sqrt(e2) * 1.00000095367431640625f; // (1 + 2^-20): rounded up past both roundings
+        if (lane == 0) {
+            meta[2 * r] = s;
+            meta[2 * r + 1] = er;
+        }
+        const bool is_long = long_bitmap && ((long_bitmap[r >> 5] >> (r & 31)) & 1u);
+        if (!is_long) best = fmaxf(best, er);
+    }
+    if (lane == 0) atomicMax(emax_bits, __float_as_uint(best));
+}
+
+int oi_launch_make_screen_i8(oi_ctx *ctx, const float *rows, uint64_t n, uint32_t dim, const uint32_t *long_bitmap, uint8_t *out) {
+    OI_REQUIRE(oi_cosine_screen_supported(dim), "int8 screening copy: dim %u not instantiated (384, 768)", dim);
+    const size_t mo = oi_screen_i8_meta_offset(n, dim);
+    // the padding rows' metadata (read by the last tile's DMA) and e_max start at zero
+    OI_HIP_CHECK(hipMemsetAsync(out + mo, 0, 8 * ((size_t)n + I8S_PAD_ROWS) + 256, ctx->stream));
+    if (n == 0) return OI_OK;
+    uint64_t blocks = (n + 3) / 4;
+    const uint64_t cap = (uint64_t)ctx->num_cus * 8;
+    if (blocks > cap) blocks = cap;
+    float *meta = reinterpret_cast<float *>(out + mo);
+    hipLaunchKernelGGL(i8s_make_kernel, dim3((uint32_t)blocks), dim3(256), 0, ctx->stream, rows, n, dim, long_bitmap,
+                       reinterpret_cast<uint32_t *>(out), meta, reinterpret_cast<uint32_t *>(meta + 2 * (n + I8S_PAD_ROWS)));
+    OI_HIP_CHECK(hipGetLastError());
+    return OI_OK;
+}
+
+// ------------------------------------------------------------------ the queries
+// One wave per (padded) query: h, l and the four per-query floats at qf[0 np + q] = a, qf[1 np + q] = |q^| (rounded up),
+// qf[2 np + q] = c_q, qf[3 np + q] = m2 = 2 (e_max |q^| + c_q), the tier's select margin.  Padding rows: zeros.  A query the bound
+// does not hold for (not finite, norm out of the bf16 screen's range) gets m2 = inf and opens the gate.
+#define I8S_NORM_LIMIT 1.0e15f
+#define I8S_QNORM_MIN 1.0e-12f
+__global__ __launch_bounds__(256) void i8s_stage_kernel(const float *__restrict__ q, uint32_t n_queries, uint32_t n_padded, uint32_t dim,
+                                                        const uint32_t *__restrict__ max_norm_bits, const uint32_t *__restrict__ emax_bits,
+                                                        int8_t *__restrict__ qi8, float *__restrict__ qf, uint32_t *gate) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t row = wave; row < n_padded; row += n_waves) {
+        const bool real = row < n_queries;
+        float amax = 0.f;
+        bool fin = true;
+        for (uint32_t k = lane; k < dim; k += 64) {
+            const float f = real ? q[(uint64_t)row * dim + k] : 0.f;
+            fin = fin && (f - f == 0.f);
+            amax = fmaxf(amax, fabsf(f));
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, OI_WAVE));
+        fin = __builtin_amdgcn_ballot_w64(!fin) == 0ull;
+        const float a = fin ? amax / 127.f : 0.f;
+        double qn2 = 0.0, en2 = 0.0;
+        for (uint32_t k = lane; k < dim; k += 64) {
+            const float f = real ? q[(uint64_t)row * dim + k] : 0.f;
+            float h = 0.f, l = 0.f;
+            if (a > 0.f) {
+                const float t = f / a;
+                h = fminf(127.f, fmaxf(-127.f, rintf(t)));
+                l = fminf(127.f, fmaxf(-127.f, rintf((t - h) * 128.f)));
+            }
+            const double qh = (double)a * ((double)h + (double)l * 0.0078125); // exact in f64
+            qn2 += qh * qh;
+            en2 += (qh - (double)f) * (qh - (double)f);
+            qi8[(uint64_t)row * dim + k] = (int8_t)(int)h;
+            qi8[((uint64_t)n_padded + row) * dim + k] = (int8_t)(int)l;
+        }
+        qn2 = oi_wave_sum(qn2);
+        en2 = oi_wave_sum(en2);
+        if (lane == 0) {
+            const float up = 1.00000095367431640625f; // 1 + 2^-20
+            const float qn = (float)sqrt(qn2) * up, en = (float)sqrt(en2) * up;
+            const float X = __uint_as_float(max_norm_bits[0]), em = __uint_as_float(*emax_bits);
+            const bool ok = fin && amax > 0.f && qn < I8S_NORM_LIMIT && qn >= I8S_QNORM_MIN && X < I8S_NORM_LIMIT && em < I8S_NORM_LIMIT;
+            const float rnd = 3.814697265625e-06f + (float)dim * 2.384185791015625e-07f; // 2^-18 + d 2^-22
+            const float cq = 1.001f * (X * en + rnd * (X + em) * (qn + en)) + 1.0e-27f;
+            const float m2 = 2.002f * (em * qn + cq);
+            qf[row] = ok ? a : 0.f;
+            qf[n_padded + row] = ok ? qn : 0.f;
+            qf[2 * n_padded + row] = ok ? cq : 0.f;
+            qf[3 * n_padded + row] = ok || !real ? m2 : __builtin_inff();
+            if (real && !ok) *gate = 1u;
+        }
+    }
+}
+
+int oi_launch_screen_stage_i8(oi_ctx *ctx, const float *d_queries, uint32_t n_queries, uint32_t dim, const uint32_t *max_norm_bits,
+                              const uint8_t *i8_copy, uint64_t n_rows, int8_t *qi8, float *qf, uint32_t *gate) {
+    const uint32_t n_padded = (n_queries + 31u) & ~31u;
+    if (n_padded == 0) return OI_OK;
+    const uint32_t *emax = reinterpret_cast<const uint32_t *>(i8_copy + oi_screen_i8_meta_offset(n_rows, dim)) + 2 * (n_rows + I8S_PAD_ROWS);
+    hipLaunchKernelGGL(i8s_stage_kernel, dim3((n_padded + 3) / 4), dim3(256), 0, ctx->stream, d_queries, n_queries, n_padded, dim,
+                       max_norm_bits, emax, qi8, qf, gate);
+    OI_HIP_CHECK(hipGetLastError());
+    return OI_OK;
+}
+
+// ------------------------------------------------------------------ the screen
+__device__ __forceinline__ uint32_t i8s_lds_addr(const void *p) {
+    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)p;
+}
+__device__ __forceinline__ i8s_u32x4 i8s_make_srd(const void *base, uint64_t bytes) {
+    const uint64_t b = (uint64_t)base;
+    i8s_u32x4 r;
+    r[0] = __builtin_amdgcn_readfirstlane((uint32_t)b);
+    r[1] = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32) & 0xFFFFu); // stride 0
+    r[2] = __builtin_amdgcn_readfirstlane((uint32_t)(bytes > 0xFFFFFFFFull ? 0xFFFFFFFFull : bytes));
+    r[3] = 0x00020000u;
+    return r;
+}
+// One 1-KiB LDS-DMA piece (8 rows x 128 B); lanes past the descriptor's end read as zero (cosine_screen_copy.hip: sc_issue_piece).
+__device__ __forceinline__ void i8s_issue_piece(const i8s_u32x4 &srd, uint32_t voff, uint32_t soff, uint32_t lds_dst) {
+#ifdef I8S_NO_DMA
+    (void)srd; (void)voff; (void)soff; (void)lds_dst; // (ablation builds: no loads at all; results WRONG)
+#else
+    uint32_t keep;
+    const uint32_t d = __builtin_amdgcn_readfirstlane(lds_dst);
+    const uint32_t so = __builtin_amdgcn_readfirstlane(soff);
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %4\n\t"
+        "s_nop 0\n\t"
+        "buffer_load_dwordx4 %1, %2, %3 offen " OI_DMA_NT "lds\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(voff), "s"(srd), "s"(so), "s"(d)
+        : "memory");
+#endif
+}
+// The tile's metadata: 64 lanes x 4 B = 32 rows x {scale, e_r} into the wave's meta slot.
+__device__ __forceinline__ void i8s_issue_meta(const i8s_u32x4 &srd, uint32_t voff, uint32_t lds_dst) {
+#ifdef I8S_NO_DMA
+    (void)srd; (void)voff; (void)lds_dst;
+#else
+    uint32_t keep;
+    const uint32_t d = __builtin_amdgcn_readfirstlane(lds_dst);
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %3\n\t"
+        "s_nop 0\n\t"
+        "buffer_load_dword %1, %2, 0 offen " OI_DMA_NT "lds\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(voff), "s"(srd), "s"(d)
+        : "memory");
+#endif
+}
+template <int I, int N, class F>
+__device__ __forceinline__ void i8s_static_for(F &&f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        i8s_static_for<I + 1, N>(f);
+    }
+}
+template <int N>
+__device__ __forceinline__ void i8s_wait() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+__device__ __forceinline__ uint32_t i8s_incl_scan(uint32_t v) { // wave-wide inclusive prefix sum (DPP, no LDS)
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
+    return v;
+}
+// cosine_screen_copy.hip: SC_FLUSH (the same contract)
+#define I8S_FLUSH(NF)                                                                                                  \
+    do {                                                                                                               \
+        const uint32_t nf_ = (NF);                                                                                     \
+        asm volatile("" ::: "memory");                                                                                 \
+        if (lane < nf_) {                                                                                              \
+            const uint32_t i_ = (st_head + lane) & (I8S_STAGE - 1);                                                    \
+            const uint64_t key_ = stage_keys[i_];                                                                      \
+            const uint32_t q_ = stage_q[i_];                                                                           \
+            const uint32_t pos_ = atomicAdd(&seg_fill[q_], 1u);                                                        \
+            if (pos_ < seg_cap) my_seg[(uint64_t)q_ * pool_stride + pos_] = key_;                                      \
+            else *overflow = 1u;                                                                                       \
+        }                                                                                                              \
+        asm volatile("" ::: "memory");                                                                                 \
+        st_head = (st_head + nf_) & (I8S_STAGE - 1);                                                                   \
+        st_n -= nf_;                                                                                                   \
+    } while (0)
+
+template <int D, int NQT, int NBUF>
+__global__ __launch_bounds__(256, 1) void cosine_i8_screen(
+    const uint8_t *__restrict__ rows, const float *__restrict__ meta, uint64_t row_begin, uint64_t row_end,
+    const int8_t *__restrict__ qhi, const int8_t *__restrict__ qlo, // [32*NQT][D] each (i8s_stage_kernel)
+    const float *__restrict__ qf, uint32_t qf_stride, uint32_t n_queries, uint32_t doc_id_base, uint64_t *pools, uint32_t *seg_cnt,
+    uint32_t seg_cnt_stride, const uint32_t *tau_keys, uint64_t pool_stride, uint32_t carry_cap, uint32_t seg_cap, uint32_t *overflow) {
+    constexpr int NKC = D / 128;          // ring slots per tile
+    constexpr int P = NBUF - 1;           // slots in flight ahead of the one being consumed
+    constexpr int KSTEPS = D / 32;        // MFMA groups per tile: four per slot
+    constexpr uint32_t RING = NBUF * I8S_SLOT_BYTES;
+    static_assert(D % 128 == 0 && P >= 1 && P <= 2 * NKC, "unsupported ring depth for this D");
+    constexpr uint32_t QLO_LDS = NQT * KSTEPS * 64 * 16; // the lo parts, fragment-major (one conflict-free ds_read_b128 each)
+    static_assert(NQT * KSTEPS * 4 <= 200, "the hi query block must fit the register file");
+    static_assert(4 * RING + 4 * 2 * I8S_META_BYTES + 256 + I8S_STAGE_LDS + QLO_LDS <= 160 * 1024, "LDS");
+
+    extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
+    unsigned char *ring = smem;                                                          // [4][NBUF][4 KiB]
+    unsigned char *meta_lds = smem + 4 * RING;                                           // [4][2][256 B]
+    uint32_t *seg_fill = reinterpret_cast<uint32_t *>(smem + 4 * RING + 8 * I8S_META_BYTES); // [64]
+    unsigned char *stage_base = smem + 4 * RING + 8 * I8S_META_BYTES + 256;
+    unsigned char *qlo_lds = stage_base + I8S_STAGE_LDS; // [NQT][KSTEPS][64 lanes][16 B], shared by the four waves
+
+    OI_CLAIM_WHOLE_SIMD(); // (MFMA kernel: nothing else may run on this CU -- oi_device.h)
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t li = lane & 31, lh = lane >> 5;
+    uint64_t *stage_keys = reinterpret_cast<uint64_t *>(stage_base) + w * I8S_STAGE;
+    uint32_t *stage_q = reinterpret_cast<uint32_t *>(stage_base + 4 * I8S_STAGE * 8) + w * I8S_STAGE;
+    uint32_t st_head = 0, st_n = 0;
+
+    // ---- every query over the whole K: B[k = 32 s + 16 lh + 0..15][n = li].  The hi parts in registers for the whole launch (192
+    // VGPRs at d = 768); the lo parts in LDS, read per MFMA (with both in registers beside the two accumulator sets the query block
+    // spilled into the tile loop)
+    i8s_i32x4 qh[NQT][KSTEPS];
+#pragma unroll
+    for (int t = 0; t < NQT; ++t)
+#pragma unroll
+        for (int s = 0; s < KSTEPS; ++s)
+            qh[t][s] = *reinterpret_cast<const i8s_i32x4 *>(qhi + (uint64_t)(32 * t + li) * D + 32 * s + 16 * lh);
+    for (uint32_t c = tid; c < (uint32_t)(NQT * KSTEPS * 64); c += 256) {
+        const uint32_t t = c / (KSTEPS * 64), s = (c / 64) % KSTEPS, l = c % 64;
+        *reinterpret_cast<i8s_i32x4 *>(qlo_lds + c * 16) =
+            *reinterpret_cast<const i8s_i32x4 *>(qlo + (uint64_t)(32 * t + (l & 31)) * D + 32 * s + 16 * (l >> 5));
+    }
+    // per query of this lane: a, |q^|, c_q and the test's right-hand side T - c_q, T = tau + m2 - 2^-20 (|tau| + m2) <= tau_l
+    // (no query in the slot: NaN, nothing passes; a threshold key at or below key(-inf): -inf, everything passes)
+    float qa[NQT], qn[NQT], cq[NQT], tc[NQT];
+#pragma unroll
+    for (int t = 0; t < NQT; ++t) {
+        const uint32_t q = 32u * t + li;
+        const bool real = q < n_queries;
+        const uint32_t k = real ? tau_keys[q] : 0xFFFFFFFFu;
+        const float tau = k <= 0x007FFFFFu ? -__builtin_inff() : oi_key_f32(k);
+        qa[t] = real ? qf[q] * 0.0078125f : 0.f; // a / 128: S = 128 S_h + S_l counts q^ / a in units of 1/128 (exact)
+        qn[t] = real ? qf[qf_stride + q] : 0.f;
+        cq[t] = real ? qf[2 * qf_stride + q] : 0.f;
+        const float m2 = real ? qf[3 * qf_stride + q] : 0.f;
+        const float T = m2 < __builtin_inff() ? (tau + m2) - (fabsf(tau) + m2) * 9.5367431640625e-07f : -__builtin_inff();
+        tc[t] = T - cq[t];
+    }
+    if (tid < 32 * NQT) seg_fill[tid] = 0;
+#ifdef I8S_NO_DMA
+    for (uint32_t i = tid; i < (4 * RING + 8 * I8S_META_BYTES) / 4; i += 256) reinterpret_cast<uint32_t *>(smem)[i] = 0u; // (ring, meta)
+#endif
+    __syncthreads(); // the only barrier before the end: seg_fill is zero before any wave appends
+
+    const uint64_t n_rows = row_end - row_begin;
+    const uint64_t n_tiles = (n_rows + I8S_TILE_ROWS - 1) / I8S_TILE_ROWS;
+    const uint64_t first = (uint64_t)blockIdx.x * 4 + w, stride = (uint64_t)gridDim.x * 4;
+    const uint64_t my_nt = first < n_tiles ? (n_tiles - first + stride - 1) / stride : 0;
+    uint64_t *my_seg = pools + carry_cap + (uint64_t)blockIdx.x * seg_cap;
+
+    if (my_nt) {
+        // the copy screen's piece geometry with D-byte rows: piece m covers tile rows 8m..8m+7; lane l -> row 8m + (l>>3),
+        // physical 16-B column l&7 holding LOGICAL column (l&7) ^ ((row>>1)&7)
+        uint32_t voff[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const uint32_t prow = 8 * m + (lane >> 3);
+            voff[m] = prow * (uint32_t)D + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
+        }
+        const uint32_t ring_w = i8s_lds_addr(ring) + w * RING;
+        const unsigned char *ring_rd = ring + w * RING;
+        const uint32_t meta_w = i8s_lds_addr(meta_lds) + w * 2 * I8S_META_BYTES;
+        const unsigned char *meta_rd = meta_lds + w * 2 * I8S_META_BYTES;
+        // fragment of MFMA group g of a slot: row li, i8 32 g + 16 lh + 0..15 = logical 16-B column 2g + lh
+        uint32_t frag_off[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) frag_off[g] = li * 128 + (((2 * g + lh) ^ ((li >> 1) & 7)) << 4);
+
+        auto tile_row0 = [&](uint64_t ti) { return row_begin + (first + ti * stride) * (uint64_t)I8S_TILE_ROWS; };
+        auto tile_srd = [&](uint64_t ti) { // past this wave's last tile: an EMPTY descriptor (loads return zeros)
+            const uint64_t r0 = tile_row0(ti < my_nt ? ti : 0);
+            return i8s_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)D : 0ull);
+        };
+        auto issue_meta = [&](uint64_t ti) { // rows past the end read as zeros (scale 0); called for ti < my_nt only
+            const uint64_t r0 = tile_row0(ti);
+            i8s_issue_meta(i8s_make_srd(meta + 2 * r0, (row_end - r0) * 8ull), lane * 4u, meta_w + (uint32_t)(ti & 1) * I8S_META_BYTES);
+        };
+        i8s_u32x4 s0 = tile_srd(0), s1 = tile_srd(1), s2 = tile_srd(2);
+        __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): every load hipcc knows about is retired here (cosine_screen_copy.hip)
+        i8s_static_for<0, P>([&](auto j_) {
+            constexpr int j = decltype(j_)::value;
+            constexpr int tj = j / NKC, kj = j % NKC;
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+                i8s_issue_piece(tj == 0 ? s0 : (tj == 1 ? s1 : s2), voff[m], kj * 128, ring_w + j * I8S_SLOT_BYTES + m * 1024);
+        });
+        issue_meta(0); // (4 NKC pieces younger than it when tile 0's epilogue waits for it)
+        uint32_t rd_off = 0, wr_off = (NBUF - 1) * I8S_SLOT_BYTES;
+
+        for (uint64_t ti = 0; ti < my_nt; ++ti) {
+            i8s_i32x16 ah[NQT], al[NQT];
+#pragma unroll
+            for (int t = 0; t < NQT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { ah[t][r] = 0; al[t][r] = 0; }
+
+            i8s_wait<4 * (P - 1)>(); // (the meta load between the pieces only makes a counted wait wait for one piece more)
+            i8s_i32x4 a_cur = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + rd_off + frag_off[0]);
+            i8s_static_for<0, NKC * 4>([&](auto gi_) {
+                constexpr int gi = decltype(gi_)::value;
+                constexpr int kc = gi / 4, g = gi % 4;
+                constexpr int sn = kc + P;
+                constexpr int tn = sn / NKC, kn = sn % NKC;
+                i8s_i32x4 a_nxt = a_cur;
+                if constexpr (g < 3) a_nxt = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + rd_off + frag_off[g + 1]);
+#ifndef I8S_NO_MFMA // (ablation builds: the stream without the matrix instructions; every score 0, results WRONG)
+#pragma unroll
+                for (int t = 0; t < NQT; ++t) {
+                    const i8s_i32x4 b_lo = *reinterpret_cast<const i8s_i32x4 *>(qlo_lds + ((t * KSTEPS + gi) * 64 + lane) * 16);
+                    ah[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_cur, qh[t][gi], ah[t], 0, 0, 0);
+                    al[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_cur, b_lo, al[t], 0, 0, 0);
+                }
+#else
+                asm volatile("" : : "v"(a_cur));
+#endif
+                i8s_issue_piece(tn == 0 ? s0 : (tn == 1 ? s1 : s2), voff[g], kn * 128, ring_w + wr_off + g * 1024);
+                if constexpr (g == 3) {
+                    wr_off = rd_off;
+                    rd_off = rd_off + I8S_SLOT_BYTES == RING ? 0u : rd_off + I8S_SLOT_BYTES;
+                    if constexpr (kc + 1 < NKC) {
+                        i8s_wait<4 * (P - 1)>();
+                        a_nxt = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + rd_off + frag_off[0]);
+                    }
+                }
+                a_cur = a_nxt;
+            });
+
+            // ---- this tile's metadata: issued before the 4 NKC pieces of this tile's refills, so vmcnt(4 NKC) retires it.
+            // Register r of query tile t holds D[row (r&3) + 8 (r>>2) + 4 lh][query 32 t + li]: rows 8 j + 4 lh + 0..3, 32 B of
+            // {scale, e_r}, read four rows at a time (the query block leaves ~60 registers for everything else)
+            i8s_wait<4 * NKC>();
+            const unsigned char *mt = meta_rd + (uint32_t)(ti & 1) * I8S_META_BYTES;
+            auto meta4 = [&](int j, float (&sr)[4], float (&er)[4]) {
+                const i8s_f32x4 u0 = *reinterpret_cast<const i8s_f32x4 *>(mt + (8 * j + 4 * lh) * 8);
+                const i8s_f32x4 u1 = *reinterpret_cast<const i8s_f32x4 *>(mt + (8 * j + 4 * lh) * 8 + 16);
+                sr[0] = u0[0]; er[0] = u0[1]; sr[1] = u0[2]; er[1] = u0[3];
+                sr[2] = u1[0]; er[2] = u1[1]; sr[3] = u1[2]; er[3] = u1[3];
+            };
+            auto score = [&](int t, int r, float sr) -> float {
+                const int S = ah[t][r] * 128 + al[t][r];
+                return (float)S * (sr * qa[t]);
+            };
+
+            // ---- filter + append: keep (q, r) when s~ + e_r |q^| + c_q >= T; the key is the lower bound s~ - e_r |q^| - c_q
+            const uint64_t row0 = tile_row0(ti);
+            uint32_t m = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float sr[4], er[4];
+                meta4(j, sr, er);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int t = 0; t < NQT; ++t)
+                        m |= score(t, 4 * j + i, sr[i]) >= fmaf(-er[i], qn[t], tc[t]) ? 1u << (16 * t + 4 * j + i) : 0u;
+                asm volatile("" ::: "memory"); // (one group of metadata live at a time)
+            }
+            if (row_end - row0 < (uint64_t)I8S_TILE_ROWS) { // the ragged last tile: rows past the end read as zeros
+                const uint32_t left = (uint32_t)(row_end - row0);
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if ((uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * lh >= left) m &= ~(0x00010001u << r);
+            }
+            auto lower_key = [&](int t, int r, uint32_t row) -> uint64_t { // (survivors only: the metadata read again)
+                float sr[4], er[4];
+                meta4(r >> 2, sr, er);
+                return oi_rank_key(score(t, r, sr[r & 3]) - fmaf(er[r & 3], qn[t], cq[t]), doc_id_base + row);
+            };
+            if (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull) {
+                const uint32_t cnt = (uint32_t)__builtin_popcount(m);
+                const uint32_t incl = i8s_incl_scan(cnt);
+                const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+                if (total <= I8S_STAGE - I8S_STAGE_FLUSH) {
+                    uint32_t idx = st_head + st_n + incl - cnt;
+#pragma unroll
+                    for (int t = 0; t < NQT; ++t)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            if (m & (1u << (16 * t + r))) {
+                                const uint32_t row = (uint32_t)row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                                stage_keys[idx & (I8S_STAGE - 1)] = lower_key(t, r, row);
+                                stage_q[idx & (I8S_STAGE - 1)] = 32u * t + li;
+                                ++idx;
+                            }
+                    st_n += total;
+                    while (st_n >= I8S_STAGE_FLUSH) {
+                        I8S_FLUSH(I8S_STAGE_FLUSH);
+                    }
+                } else {
+                    uint32_t pos[NQT];
+#pragma unroll
+                    for (int t = 0; t < NQT; ++t)
+                        pos[t] = atomicAdd(&seg_fill[32u * t + li], (uint32_t)__builtin_popcount((m >> (16 * t)) & 0xFFFFu));
+#pragma unroll
+                    for (int t = 0; t < NQT; ++t) {
+                        uint64_t *dst = my_seg + (uint64_t)(32u * t + li) * pool_stride;
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            if (m & (1u << (16 * t + r))) {
+                                const uint32_t row = (uint32_t)row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                                if (pos[t] < seg_cap) dst[pos[t]] = lower_key(t, r, row);
+                                else *overflow = 1u;
+                                ++pos[t];
+                            }
+                        }
+                    }
+                }
+            }
+            // the next tile's metadata into the other meta slot (this tile's reads have all returned: their values were used)
+            if (ti + 1 < my_nt) issue_meta(ti + 1);
+            s0 = s1;
+            s1 = s2;
+            s2 = tile_srd(ti + 3);
+        }
+        if (st_n) {
+            I8S_FLUSH(st_n);
+        }
+        i8s_wait<0>(); // the zero-filling refills issued past the last tile have landed before the LDS goes back
+    }
+    __syncthreads();
+    if (tid < 32 * NQT && tid < n_queries) {
+        const uint32_t c = seg_fill[tid];
+        seg_cnt[(uint64_t)tid * seg_cnt_stride + blockIdx.x] = c < seg_cap ? c : seg_cap;
+    }
+}
+
+template <int D, int NQT, int NBUF>
+static int launch_i8_screen(oi_ctx *ctx, const uint8_t *rows, const float *meta, uint64_t row_begin, uint64_t row_end, const int8_t *qhi,
+                            const int8_t *qlo, const float *qf, uint32_t qf_stride, uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
+    constexpr size_t smem = 4 * NBUF * I8S_SLOT_BYTES + 8 * I8S_META_BYTES + 256 + I8S_STAGE_LDS + NQT * (D / 32) * 64 * 16;
+    OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(cosine_i8_screen<D, NQT, NBUF>), (size_t)(smem)));
+    hipLaunchKernelGGL((cosine_i8_screen<D, NQT, NBUF>), dim3(p.n_segs), dim3(256), smem, ctx->stream, rows, meta, row_begin, row_end,
+                       qhi, qlo, qf, qf_stride, nq, doc_id_base, p.keys, p.seg_cnt, p.seg_cnt_stride, p.tau_keys, p.stride, p.carry_cap,
+                       p.seg_cap, p.overflow);
+    OI_HIP_CHECK(hipGetLastError());
+    return OI_OK;
+}
+
+// All queries of a batch over rows [row_begin, row_end) of the index's int8 copy (n_rows_total rows).  qi8 / qf: staged by
+// oi_launch_screen_stage_i8.  Pool geometry: the bf16 screens' (oi_cosine_screen_geometry).
+int oi_launch_cosine_screen_i8_chunk(oi_ctx *ctx, const uint8_t *i8_copy, uint64_t n_rows_total, uint64_t row_begin, uint64_t row_end,
+                                     uint32_t dim, const int8_t *qi8, const float *qf, uint32_t n_queries, uint32_t doc_id_base,
+                                     PoolView &pool) {
+    OI_REQUIRE(oi_cosine_screen_supported(dim), "cosine screen (int8): dim %u not instantiated (384, 768)", dim);
+    OI_REQUIRE(row_end <= n_rows_total, "cosine screen (int8): rows past the copy");
+    oi_cosine_screen_geometry(ctx, row_end > row_begin ? row_end - row_begin : 0, &pool.n_segs, &pool.seg_cap);
+    OI_REQUIRE(pool.n_segs <= pool.seg_cnt_stride && pool.carry_cap + (uint64_t)pool.n_segs * pool.seg_cap <= pool.stride,
+               "cosine screen (int8): chunk does not fit the candidate pool");
+    if (row_end <= row_begin || n_queries == 0) return OI_OK;
+    const float *meta = reinterpret_cast<const float *>(i8_copy + oi_screen_i8_meta_offset(n_rows_total, dim));
+    const uint32_t np = (n_queries + 31u) & ~31u;
+    ProfScope ps(ctx, "cosine");
+    for (uint32_t q0 = 0; q0 < n_queries; q0 += 64) {
+        const uint32_t nq_here = std::min(64u, n_queries - q0);
+        PoolView p = pool;
+        p.keys += (uint64_t)q0 * pool.stride;
+        p.carry_cnt += q0;
+        p.seg_cnt += (uint64_t)q0 * pool.seg_cnt_stride;
+        p.tau_keys += q0;
+        const int8_t *qhi = qi8 + (uint64_t)q0 * dim, *qlo = qi8 + ((uint64_t)np + q0) * dim;
+        const float *qfp = qf + q0;
+        const bool two = nq_here > 32;
+        if (dim == 768) {
+            if (two) OI_CHECK((launch_i8_screen<768, 2, 6>(ctx, i8_copy, meta, row_begin, row_end, qhi, qlo, qfp, np, nq_here, doc_id_base, p)));
+            else OI_CHECK((launch_i8_screen<768, 1, 6>(ctx, i8_copy, meta, row_begin, row_end, qhi, qlo, qfp, np, nq_here, doc_id_base, p)));
+        } else {
+            if (two) OI_CHECK((launch_i8_screen<384, 2, 6>(ctx, i8_copy, meta, row_begin, row_end, qhi, qlo, qfp, np, nq_here, doc_id_base, p)));
+            else OI_CHECK((launch_i8_screen<384, 1, 6>(ctx, i8_copy, meta, row_begin, row_end, qhi, qlo, qfp, np, nq_here, doc_id_base, p)));
+        }
+    }
+    return OI_OK;
+}
+
+// ------------------------------------------------------------------ the bf16 rescreen
+// One wave per (query, survivor), four survivors per trip: s~ = sum_k bf16(x_k) bf16(q_k) from the bf16 copy (products exact in
+// f32, summed in f32 in any order: the bf16 bound allows it), written as the row's bf16 screen key over its int8 key, in place.
+// Single v_fma_f32 (oi_fma_unpacked), no packed-f32 forms.
+__device__ __forceinline__ float i8s_bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float i8s_bf16_hi(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
+__global__ __launch_bounds__(256) void pf_rescreen_kernel(const uint16_t *__restrict__ copy, uint64_t n_rows, uint32_t dim,
+                                                          uint32_t doc_id_base, const uint16_t *__restrict__ qb, uint64_t *pools,
+                                                          const uint32_t *__restrict__ cnt, uint64_t stride, uint32_t cap) {
+    const uint32_t q = blockIdx.y, lane = threadIdx.x & 63;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    uint32_t c = cnt[q];
+    c = c < cap ? c : cap;
+    uint64_t *keys = pools + (uint64_t)q * stride;
+    const uint32_t nvec = dim >> 3; // 8 bf16 per uint4
+    const uint4 *qv = reinterpret_cast<const uint4 *>(qb + (uint64_t)q * dim);
+    for (uint32_t i0 = wave * 4u; i0 < c; i0 += n_waves * 4u) {
+        uint32_t doc[4];
+        const uint4 *x[4];
+        float a[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint32_t i = i0 + u < c ? i0 + u : c - 1u;
+            doc[u] = oi_rank_key_doc(keys[i]);
+            const uint64_t r = (uint64_t)(doc[u] - doc_id_base);
+            x[u] = reinterpret_cast<const uint4 *>(copy + (r < n_rows ? r : 0) * dim);
+            a[u] = 0.f;
+        }
+        for (uint32_t v = lane; v < nvec; v += 64) {
+            const uint4 yv = qv[v];
+            uint4 xv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) xv[u] = oi_load_stream(x[u] + v);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t xw[4] = {xv[u].x, xv[u].y, xv[u].z, xv[u].w}, yw[4] = {yv.x, yv.y, yv.z, yv.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    a[u] = oi_fma_unpacked(i8s_bf16_lo(xw[e]), i8s_bf16_lo(yw[e]), a[u]);
+                    a[u] = oi_fma_unpacked(i8s_bf16_hi(xw[e]), i8s_bf16_hi(yw[e]), a[u]);
+                }
+            }
+        }
+        float s[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) s[u] = oi_wave_sum(a[u]);
+        // (every lane has read its keys: the four writes go over them)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint64_t r = (uint64_t)(doc[u] - doc_id_base);
+            const float sc = r < n_rows ? s[u] : 0.f;
+            if (lane == 0 && i0 + u < c) keys[i0 + u] = oi_rank_key(sc, doc[u]);
+        }
+    }
+}
+
+int oi_launch_rescreen_bf16(oi_ctx *ctx, const uint16_t *copy_rows, uint64_t n_rows, uint32_t dim, uint32_t doc_id_base,
+                            const uint16_t *q_bf16, uint32_t n_queries, const PoolView &pool) {
+    if (n_queries == 0) return OI_OK;
+    ProfScope ps(ctx, "rescreen");
+    hipLaunchKernelGGL(pf_rescreen_kernel, dim3(32, n_queries), dim3(256), 0, ctx->stream, copy_rows, n_rows, dim, doc_id_base, q_bf16,
+                       pool.keys, pool.carry_cnt, pool.stride, pool.carry_cap);
+    OI_HIP_CHECK(hipGetLastError());
+    return OI_OK;
+}

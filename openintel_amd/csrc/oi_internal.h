@@ -187,6 +187,10 @@ struct oi_index {
     DevBuf long_list, long_bitmap;
     DevBuf screen_copy;     // the bf16 screening copy: bf16(rows), n_docs x dim x 2 B, made at finalize when the policy allows
     int screen_copy_policy = -1; // oi_index_set_screen_copy; -1 = the process default (OI_SCREEN_COPY, else AUTO)
+    // the int8 screening copy (cosine_screen_i8.hip), made and dropped together with the bf16 one: i8 rows (n_docs x dim B,
+    // per-row absmax scale) then, 256-B aligned, f32 {scale, e_r} per row (+ 64 rows of zero padding) and bits of max e_r over
+    // the rows that are not long
+    DevBuf screen_i8;
 
     // staged forward index (between set_forward and finalize)
     bool forward_set = false, finalized = false;
@@ -267,6 +271,12 @@ struct SelectExtra {
     const uint32_t *run_gate = nullptr;
     const uint32_t *skip_bitmap = nullptr; // margin mode: keys of docs whose bit (doc - skip_base) is set are left out of the selection
     uint32_t skip_base = 0;
+    uint64_t *cand = nullptr; // margin mode: candidates staged here ([n_queries][cand_cap], global) instead of in LDS (4096 keys)
+    uint32_t cand_cap = 0;
+    // margin mode with per-row margins (the int8 tier): {scale, e_r} per row (row = doc - meta_base), |q^| and c_q per query
+    const float *row_meta = nullptr;
+    uint32_t meta_base = 0;
+    const float *row_qn = nullptr, *row_cq = nullptr;
 };
 int oi_launch_select(oi_ctx *ctx, const PoolView &pool, uint32_t n_queries, uint32_t k, bool compact,
                      float *out_scores, uint32_t *out_docs, uint32_t *out_counts, uint32_t out_stride,
@@ -308,6 +318,20 @@ int oi_launch_screen_stage(oi_ctx *ctx, const float *d_queries, uint32_t n_queri
 int oi_launch_cosine_screen_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end, uint32_t dim,
                                   const uint16_t *q_bf16, uint32_t n_queries, uint32_t doc_id_base, PoolView &pool);
 int oi_launch_make_screen_copy(oi_ctx *ctx, const float *rows, uint64_t n, uint32_t dim, uint16_t *out);
+// cosine_screen_i8.hip: the int8 first tier in front of the bf16 screen
+#define OI_I8_CARRY 16384u // keys per query the int8 tier carries between chunks (its margin selects' candidate room)
+size_t oi_screen_i8_bytes(uint64_t n, uint32_t dim);
+size_t oi_screen_i8_meta_offset(uint64_t n, uint32_t dim);
+int oi_launch_make_screen_i8(oi_ctx *ctx, const float *rows, uint64_t n, uint32_t dim, const uint32_t *long_bitmap, uint8_t *out);
+// per search: i8 hi / lo query blocks (qi8: [2][n_padded][dim]) and four floats per query in qf: qa, qn, cq, eps2 (the tier's margin)
+int oi_launch_screen_stage_i8(oi_ctx *ctx, const float *d_queries, uint32_t n_queries, uint32_t dim, const uint32_t *max_norm_bits,
+                              const uint8_t *i8_copy, uint64_t n_rows, int8_t *qi8, float *qf, uint32_t *gate);
+int oi_launch_cosine_screen_i8_chunk(oi_ctx *ctx, const uint8_t *i8_copy, uint64_t n_rows_total, uint64_t row_begin, uint64_t row_end,
+                                     uint32_t dim, const int8_t *qi8, const float *qf, uint32_t n_queries, uint32_t doc_id_base,
+                                     PoolView &pool);
+// the bf16 rescreen: every key of pool's carry (an int8 survivor) becomes its bf16 screen key, in place
+int oi_launch_rescreen_bf16(oi_ctx *ctx, const uint16_t *copy_rows, uint64_t n_rows, uint32_t dim, uint32_t doc_id_base,
+                            const uint16_t *q_bf16, uint32_t n_queries, const PoolView &pool);
 // cosine_screen_copy.hip
 int oi_launch_cosine_screen_copy_chunk(oi_ctx *ctx, const uint16_t *copy_rows, uint64_t row_begin, uint64_t row_end, uint32_t dim,
                                        const uint16_t *q_bf16, uint32_t n_queries, uint32_t doc_id_base, PoolView &pool);

@@ -229,6 +229,21 @@ __device__ unsigned long long sel_dbg_t[16];
 #endif
 #define SEL_CAND 4096
 
+// Per-row margins of a margin select (the int8 screening tier, cosine_screen_i8.hip): keys are LOWER bounds l_r of rows whose upper
+// bound is l_r + 2 (e_r qn + cq); a key passing the global margin (eps2 = the largest such width) is kept only when its own upper
+// bound reaches the k-th key, less a guard for the f32 rounding of the test.  meta: {scale, e_r} per row (row = doc - base).
+struct SelRowMargin {
+    const float *meta;
+    uint32_t base;
+    float qn, cq;
+};
+__device__ __forceinline__ bool sel_row_keep(const SelRowMargin *rm, uint64_t kv, float edge, float eps2) {
+    if (!rm) return true;
+    const float e = rm->meta[2 * (uint64_t)(oi_rank_key_doc(kv) - rm->base) + 1];
+    const float u = oi_rank_key_score(kv) + 2.002f * (e * rm->qn + rm->cq);
+    return u >= edge - 9.5367431640625e-07f * (fabsf(edge) + eps2);
+}
+
 struct SelShared {
     uint32_t hist[256];
     uint32_t hist2k[2048]; // the margin selects' 11-bit digits (sel_flat_select, fast margin path)
@@ -389,7 +404,8 @@ __device__ __forceinline__ void sel_threshold(FE &&for_each, uint32_t kk_in, Sel
 template <int KPT>
 __device__ __forceinline__ uint32_t sel_flat_select(const SelFlat &K, uint32_t k, SelShared &sh, uint64_t *sel,
                                                     uint64_t *cand, float eps2, bool *in_cand, uint32_t *margin_tau,
-                                                    bool *margin_overflow, const uint32_t *skip, uint32_t skip_base) {
+                                                    bool *margin_overflow, const uint32_t *skip, uint32_t skip_base,
+                                                    uint64_t *mc, uint32_t mcap, const SelRowMargin *rm) {
     // skip (the screen's two-class margin): keys of docs marked in this bitmap do not take part -- they are scored exactly
     // whatever happens here, and their screen scores must not move the threshold (cosine_prefilter.hip)
     auto skipped = [&](uint64_t kv) -> bool {
@@ -541,15 +557,17 @@ __device__ __forceinline__ uint32_t sel_flat_select(const SelFlat &K, uint32_t k
             const uint32_t t32 = eps2 < __builtin_inff() ? oi_f32_key(oi_key_f32(tkey) - eps2) : 0u;
             // the filter: a thread counts its survivors, the wave takes ONE slot range for all of them
             uint32_t mine = 0;
-            for_each([&](bool valid, uint64_t kv) { mine += valid && (uint32_t)(kv >> 32) >= t32 ? 1u : 0u; });
+            const float edge = oi_key_f32(tkey);
+            auto keep = [&](bool valid, uint64_t kv) { return valid && (uint32_t)(kv >> 32) >= t32 && sel_row_keep(rm, kv, edge, eps2); };
+            for_each([&](bool valid, uint64_t kv) { mine += keep(valid, kv) ? 1u : 0u; });
             const uint32_t incl = sel_incl_scan(mine);
             const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             uint32_t base = 0;
             if (lane == 0 && tot) base = atomicAdd(&sh.cnt, tot);
             uint32_t pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)base) + incl - mine;
             for_each([&](bool valid, uint64_t kv) {
-                if (valid && (uint32_t)(kv >> 32) >= t32) {
-                    if (pos < SEL_CAND) cand[pos] = kv;
+                if (keep(valid, kv)) {
+                    if (pos < mcap) mc[pos] = kv;
                     ++pos;
                 }
             });
@@ -557,9 +575,9 @@ __device__ __forceinline__ uint32_t sel_flat_select(const SelFlat &K, uint32_t k
             const uint32_t c = sh.cnt;
             *in_cand = true;
             *margin_tau = t32;
-            *margin_overflow = c > SEL_CAND;
+            *margin_overflow = c > mcap;
             SEL_STAMP(5);
-            return c > SEL_CAND ? SEL_CAND : c;
+            return c > mcap ? mcap : c;
         }
     }
     int shift;
@@ -642,20 +660,24 @@ __device__ __forceinline__ uint32_t sel_flat_select(const SelFlat &K, uint32_t k
     __syncthreads();
     // an infinite margin (a query without a bound, cosine_prefilter.hip) keeps everything and never raises the threshold
     const uint32_t t32 = eps2 < __builtin_inff() ? oi_f32_key(oi_key_f32((uint32_t)(sh.min_key >> 32)) - eps2) : 0u;
-    for_each([&](bool valid, uint64_t kv) { sel_append(cand, &sh.cnt, SEL_CAND, valid && (uint32_t)(kv >> 32) >= t32, kv); });
+    const float edge = oi_key_f32((uint32_t)(sh.min_key >> 32));
+    for_each([&](bool valid, uint64_t kv) {
+        sel_append(mc, &sh.cnt, mcap, valid && (uint32_t)(kv >> 32) >= t32 && sel_row_keep(rm, kv, edge, eps2), kv);
+    });
     __syncthreads();
     const uint32_t c = sh.cnt;
     *in_cand = true;
     *margin_tau = t32;
-    *margin_overflow = c > SEL_CAND;
-    return c > SEL_CAND ? SEL_CAND : c;
+    *margin_overflow = c > mcap;
+    return c > mcap ? mcap : c;
 }
 
 __global__ __launch_bounds__(SEL_THREADS) void select_flat_kernel(
     uint64_t *pools, uint32_t *carry_cnt, uint32_t *seg_cnt, uint32_t *tau_keys, uint64_t pool_stride,
     uint32_t carry_cap, uint32_t seg_cap, uint32_t n_segs, uint32_t seg_cnt_stride, uint32_t *overflow,
     uint32_t k, int compact, float *out_scores, uint32_t *out_docs, uint32_t *out_counts, uint32_t out_stride,
-    const float *eps2, uint32_t *margin_gate, const uint32_t *run_gate, const uint32_t *skip, uint32_t skip_base) {
+    const float *eps2, uint32_t *margin_gate, const uint32_t *run_gate, const uint32_t *skip, uint32_t skip_base,
+    uint64_t *cand_g, uint32_t cand_cap, const float *row_meta, uint32_t meta_base, const float *row_qn, const float *row_cq) {
     // run_gate: this launch belongs to the gated exact pipeline (cosine_prefilter.hip) and only runs when the
     // screen gave up.  eps2: margin mode (see sel_flat_select); its overflow opens that gate.
     if (run_gate && *run_gate == 0u) return;
@@ -668,6 +690,13 @@ __global__ __launch_bounds__(SEL_THREADS) void select_flat_kernel(
     SEL_STAMP(0);
     const uint32_t c0_raw = carry_cnt[q];    // (issued beside the segment counts: not a second round trip after the scan)
     const float e2 = eps2 ? eps2[q] : -1.f;
+    // margin candidates: LDS (4096 keys), or a global buffer of the caller's (the int8 tier: OI_I8_CARRY keys), copied into the
+    // carry region after the pass that reads the pool
+    uint64_t *const mc = cand_g ? cand_g + (uint64_t)q * cand_cap : cand;
+    const uint32_t mcap = cand_g ? cand_cap : SEL_CAND;
+    SelRowMargin rm_v;
+    if (row_meta) rm_v = SelRowMargin{row_meta, meta_base, row_qn[q], row_cq[q]};
+    const SelRowMargin *rm = row_meta && e2 < __builtin_inff() ? &rm_v : nullptr;
 
     // exclusive scan of the (clamped) segment counts -> sh.seg_off; SEL_MAX_SEGS / SEL_THREADS = 4 per thread
     constexpr int SPT = SEL_MAX_SEGS / SEL_THREADS;
@@ -712,14 +741,14 @@ __global__ __launch_bounds__(SEL_THREADS) void select_flat_kernel(
 
     uint32_t m, m_tau = 0;
     bool in_cand = false, m_over = false;
-    if (K.n <= 4 * SEL_THREADS) m = sel_flat_select<4>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base);
-    else if (K.n <= 8 * SEL_THREADS) m = sel_flat_select<8>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base);
-    else if (K.n <= 16 * SEL_THREADS) m = sel_flat_select<16>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base);
-    else if (K.n <= SEL_KPT_MAX * SEL_THREADS) m = sel_flat_select<SEL_KPT_MAX>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base);
-    else m = sel_flat_select<0>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base);
+    if (K.n <= 4 * SEL_THREADS) m = sel_flat_select<4>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm);
+    else if (K.n <= 8 * SEL_THREADS) m = sel_flat_select<8>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm);
+    else if (K.n <= 16 * SEL_THREADS) m = sel_flat_select<16>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm);
+    else if (K.n <= SEL_KPT_MAX * SEL_THREADS) m = sel_flat_select<SEL_KPT_MAX>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm);
+    else m = sel_flat_select<0>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm);
     if (in_cand) { // margin mode: an unsorted superset of the top k in cand[]; only ever compacted
         if (m_over && tid == 0 && margin_gate) *margin_gate = 1u;
-        for (uint32_t i = tid; i < m; i += SEL_THREADS) pool[i] = cand[i];
+        for (uint32_t i = tid; i < m; i += SEL_THREADS) pool[i] = mc[i];
         for (uint32_t sg = tid; sg < n_segs; sg += SEL_THREADS) segc[sg] = 0;
         if (tid == 0) {
             carry_cnt[q] = m;
@@ -793,8 +822,9 @@ int oi_launch_select(oi_ctx *ctx, const PoolView &pool, uint32_t n_queries, uint
     const bool special = extra && (extra->eps2 || extra->run_gate);
     if (special) {
         OI_REQUIRE(pool.n_segs <= SEL_MAX_SEGS, "select: %u segments (margin / gated selects take <= %u)", pool.n_segs, SEL_MAX_SEGS);
-        OI_REQUIRE(!extra->eps2 || (compact && !out_scores && pool.carry_cap >= SEL_CAND),
-                   "select: margin mode compacts into a carry region of >= %u keys", SEL_CAND);
+        const uint32_t mcap = extra->cand ? extra->cand_cap : SEL_CAND;
+        OI_REQUIRE(!extra->eps2 || (compact && !out_scores && pool.carry_cap >= mcap),
+                   "select: margin mode compacts into a carry region of >= %u keys", mcap);
     }
     if ((!v1 || special) && pool.n_segs <= SEL_MAX_SEGS) {
         hipLaunchKernelGGL(select_flat_kernel, dim3(n_queries), dim3(SEL_THREADS), 0, ctx->stream, pool.keys,
@@ -802,7 +832,9 @@ int oi_launch_select(oi_ctx *ctx, const PoolView &pool, uint32_t n_queries, uint
                            pool.n_segs, pool.seg_cnt_stride, pool.overflow, k, compact ? 1 : 0, out_scores, out_docs,
                            out_counts, out_stride, extra ? extra->eps2 : nullptr, extra ? extra->margin_gate : nullptr,
                            extra ? extra->run_gate : nullptr, extra && extra->eps2 ? extra->skip_bitmap : nullptr,
-                           extra ? extra->skip_base : 0u);
+                           extra ? extra->skip_base : 0u, extra && extra->eps2 ? extra->cand : nullptr,
+                           extra && extra->eps2 ? extra->cand_cap : 0u, extra && extra->eps2 ? extra->row_meta : nullptr,
+                           extra ? extra->meta_base : 0u, extra ? extra->row_qn : nullptr, extra ? extra->row_cq : nullptr);
         OI_HIP_CHECK(hipGetLastError());
         return OI_OK;
     }
