@@ -136,7 +136,7 @@ extern "C" int oi_profile_read(oi_ctx *ctx, const char *kernel_tag, double *tota
         return OI_OK;
     }
     if (strcmp(kernel_tag, "spec_state") == 0) { // diagnostics of the speculative screen thresholds: failed checks seen so far, searches that speculated
-        if (ctx->spec_fail_host && *ctx->spec_fail_host) { *ctx->spec_fail_host = 0; ++ctx->spec_failures; ctx->spec_backoff = ctx->spec_backoff ? std::min(1024u, 2 * ctx->spec_backoff) : 16u; ctx->spec_skip = ctx->spec_backoff; }
+        oi_spec_take_failure(ctx);
         if (total_ms_out) *total_ms_out = (double)ctx->spec_failures;
         if (launches_out) *launches_out = ctx->spec_searches;
         return OI_OK;
@@ -871,8 +871,7 @@ static int apply_screen_copy_policy(oi_index *idx) {
     oi_ctx *ctx = idx->ctx;
     if (idx->is_view) return OI_OK;
     const int policy = idx->screen_copy_policy < 0 ? default_screen_copy_policy() : idx->screen_copy_policy;
-    const bool possible = idx->rows && !idx->rows_bf16 && idx->screen_ok && oi_cosine_screen_supported(idx->dim);
-    if (policy == OI_SCREEN_COPY_NEVER || !possible) {
+    if (policy == OI_SCREEN_COPY_NEVER || !oi_index_screenable(idx)) {
         if (idx->screen_copy.p || idx->screen_i8.p) {
             OI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
             idx->screen_copy.release();
@@ -1111,584 +1110,8 @@ extern "C" int oi_index_finalize(oi_index *idx, uint64_t global_n_docs, uint64_t
     return apply_screen_copy_policy(idx); // the derived structure of the cosine leg, beside the BM25 leg's postings
 }
 
-// ---------------------------------------------------------------- search
+// ---------------------------------------------------------------- search (search.hip: search_lists_device)
 namespace {
-
-struct Pools {
-    PoolView cos, bm;
-};
-
-// 1 term-at-a-time per workgroup (bm25.hip), 2 scan of the forward index, 3 one wave per task (bm25_wave.hip), 4 the stream
-// kernel (bm25_stream.hip: the default).  The index's own setting wins over the process-wide OI_BM25_MODE.
-int bm25_mode_of(const oi_index *idx) {
-    static const char *mode_env = getenv("OI_BM25_MODE");
-    int mode = idx->bm25_mode;
-    if (mode == 0 && mode_env)
-        mode = strcmp(mode_env, "scan") == 0 ? 2 : strcmp(mode_env, "taat") == 0 ? 1 : strcmp(mode_env, "wave") == 0 ? 3 : 4;
-    return mode == 0 ? 4 : mode;
-}
-
-// State of both pools in one block, zeroed with ONE memset per search:
-//   cosine: carry_cnt[B] tau[B] seg_cnt[B][CUs]      BM25: carry_cnt[B] seg_cnt[B][n_blocks]
-// `extra_words` more zeroed words follow them (*extra): the bf16 screen's state, so that one memset kernel does both.
-int prepare_pools(oi_ctx *ctx, uint32_t B, uint64_t cos_alloc_stride, uint64_t cos_stride, uint32_t carry_cap, uint32_t bm_blocks,
-                  uint32_t depth, Pools *out, size_t extra_words = 0, uint32_t **extra = nullptr) {
-    DevBuf &flag = ctx->buf("state_flag");
-    if (!flag.p) {
-        OI_CHECK(flag.ensure(16));
-        OI_HIP_CHECK(hipMemsetAsync(flag.p, 0, 16, ctx->stream));
-    }
-    const uint32_t cos_segs = (uint32_t)ctx->num_cus * (B <= 8 ? 8u : 1u); // one per workgroup: GEMV grids are 8 per CU
-    const uint32_t bm_segs = bm_blocks ? bm_blocks : 1;
-    const size_t words = (size_t)B * (2 + cos_segs + 2 + bm_segs);
-    DevBuf &st = ctx->buf("pool_state");
-    OI_CHECK(st.ensure(sizeof(uint32_t) * (words + extra_words)));
-    OI_HIP_CHECK(hipMemsetAsync(st.p, 0, sizeof(uint32_t) * (words + extra_words), ctx->stream));
-    if (extra) *extra = st.as<uint32_t>() + words;
-    const uint64_t bm_stride = (uint64_t)carry_cap + (uint64_t)bm_segs * depth;
-    DevBuf &pc = ctx->buf("pool_cos"), &pb = ctx->buf("pool_bm");
-    OI_CHECK(pc.ensure(sizeof(uint64_t) * (size_t)B * cos_alloc_stride)); // (room for the widest view of it: the screen's)
-    OI_CHECK(pb.ensure(sizeof(uint64_t) * (size_t)B * bm_stride));
-    uint32_t *s = st.as<uint32_t>();
-    uint32_t *cos_carry = s, *cos_tau = s + B, *cos_seg = s + 2 * (size_t)B;
-    uint32_t *bm_carry = cos_seg + (size_t)B * cos_segs, *bm_tau = bm_carry + B, *bm_seg = bm_tau + B;
-    out->cos = PoolView{pc.as<uint64_t>(), cos_carry, cos_seg, cos_tau, cos_stride, carry_cap, 0, 0, cos_segs,
-                        flag.as<uint32_t>()};
-    out->bm = PoolView{pb.as<uint64_t>(), bm_carry, bm_seg, bm_tau, bm_stride, carry_cap, depth, bm_segs, bm_segs,
-                       flag.as<uint32_t>()};
-    return OI_OK;
-}
-
-// Rows of the first corpus chunk (scored with no threshold yet: every row lands in the pool, so it is kept
-// small); each later chunk is 8x the one before.  OI_FIRST_CHUNK_MULT scales it (A/B runs).
-static uint64_t oi_first_chunk_rows(uint32_t depth) {
-    static const uint64_t mult = oi_ablation_env("OI_FIRST_CHUNK_MULT") ? std::max(1, atoi(oi_ablation_env("OI_FIRST_CHUNK_MULT"))) : 1;
-    static const uint64_t div = oi_ablation_env("OI_FIRST_CHUNK_DIV") ? std::max(1, atoi(oi_ablation_env("OI_FIRST_CHUNK_DIV"))) : 1; // (A/B)
-    return std::max<uint64_t>(std::max<uint64_t>(8192, 32ull * depth) * mult / div, 2ull * depth);
-}
-// The screen's first chunk (round 4): a whole number of ROUNDS of the persistent grid -- 7/8 of the CUs x 4 waves x 32-row tiles
-// (cosine_prefilter.hip: oi_cosine_screen_geometry) -- so that no wave of the two short first launches runs one tile more than
-// the others (32000 rows = 1000 tiles on 896 waves: 104 waves with two tiles; 256000 rows: 9.1 per wave, i.e. 10 rounds).
-// Chunk k is 8^k times the first and keeps the property.  OI_SCREEN_NO_ROUND=1 (A/B): as before.
-static uint64_t oi_screen_first_chunk_rows(const oi_ctx *ctx, uint32_t depth) {
-    static const bool no_round = oi_ablation_env("OI_SCREEN_NO_ROUND") != nullptr;
-    uint64_t rows = oi_first_chunk_rows(depth);
-    const uint64_t round = 32ull * 4 * std::max<uint64_t>(1, (uint64_t)ctx->num_cus * 7 / 8);
-    if (!no_round && rows >= round) rows -= rows % round;
-    return rows;
-}
-// Measured (tools/growth_ab.sh): 8 is best for the MFMA batch path at 10M and 1.25M rows (more survivors per
-// chunk cost more in the epilogue and the select than the launch they save); the GEMV path (B <= 8) gains
-// 3 % from 16 (1M rows: 3 launches instead of 4).
-static uint64_t oi_chunk_growth(uint32_t B) {
-    static const uint64_t g = oi_ablation_env("OI_CHUNK_GROWTH") ? std::max(2, atoi(oi_ablation_env("OI_CHUNK_GROWTH"))) : 0;
-    return g ? g : (B <= 8 ? 16 : 8);
-}
-
-// End of the corpus chunk that starts at row r: `chunk` rows, but a tail shorter than a quarter of the chunk is taken along
-// (a 2.5M-row shard: 32K, 256K, 2.2M rows instead of 32K, 256K, 2M and a fourth launch + select for 0.2M).
-// And when what is left after this chunk would not fit ONE more chunk but fits two, this chunk grows so that the last one is
-// exactly the largest the pool takes (10M rows, 6.8M-row pool: 32K, 256K, 2.9M, 6.8M instead of 32K, 256K, 2M, 6.8M, 0.9M).
-// (only where the chunk AFTER this one would be cut by the pool anyway -- `next_chunk`, its planned size, reaches max_chunk --
-// never for the small first chunks, which run without a threshold).
-static uint64_t oi_chunk_end(uint64_t r, uint64_t chunk, uint64_t n, uint64_t max_chunk, uint64_t next_chunk) {
-    uint64_t e = std::min(n, r + chunk);
-    if (e < n && (n - e) * 4 <= (e - r) && n - r <= max_chunk) e = n;
-    if (e < n && next_chunk >= max_chunk && n - e > max_chunk && n - r <= 2 * max_chunk) e = n - max_chunk;
-    return e;
-}
-
-// Device-side ranked lists for a batch; all pointers device.
-int search_lists_device(oi_index *idx, const float *d_qv, const uint32_t *d_qt, const uint32_t *d_qo, uint32_t B,
-                        uint32_t depth, float *cos_s, uint32_t *cos_d, uint32_t *cos_c, float *bm_s,
-                        uint32_t *bm_d, uint32_t *bm_c) {
-    oi_ctx *ctx = idx->ctx;
-    hipStream_t st = ctx->stream;
-    const uint64_t n = idx->n_docs;
-    // ---- pool capacities
-    // cosine: the corpus is scored in chunks; a chunk can append at most one entry per row and
-    // query, so a chunk sized from the pool's free room can never overflow it (no overflow path
-    // to handle, no data-dependent sizing).  BM25: every doc block contributes <= depth entries.
-    const uint32_t carry_cap = OI_MAX_DEPTH;
-    const uint64_t slack = (idx->rows_bf16 ? 128ull : 32ull) * ((uint64_t)ctx->num_cus + 1);
-    // Large pools = few launches: at 10M rows the schedule is 32K, 256K, 3.2M, 6.5M rows (4 launches).  The room is worst
-    // case (every row of a chunk passes the threshold), only entries that pass are written.  Round 4: an f32 corpus gets
-    // 3.25 GiB of pool instead of 8 (the last two chunks are balanced so that the launch count stays), and the screen's pool
-    // and the exact fallback's pool are ONE buffer (they are never live together: the gated exact pipeline starts after the
-    // rescoring has consumed the screen's survivors).  A bf16 corpus (configs[4]: 256 queries) keeps 8 GiB.
-    uint64_t cos_stride = 1ull << 24;
-    const uint64_t budget = (idx->rows_bf16 ? (8ull << 30) : (13ull << 28)) / 8 / B;
-    if (cos_stride > budget) cos_stride = budget;
-    if (cos_stride < carry_cap + 4 * slack) cos_stride = carry_cap + 4 * slack;
-    if (cos_stride > carry_cap + n + slack) cos_stride = carry_cap + n + slack;
-    // the screen's view of the same buffer keeps up to 4096 keys per query between chunks and rounds its segments to 4 tiles; with
-    // the int8 first tier (cosine_screen_i8.hip: the index holds both screening copies, B > 8) up to OI_I8_CARRY
-    const bool i8_tier = cos_s && idx->rows && !idx->rows_bf16 && idx->screen_copy.p && idx->screen_i8.p && B > 8 && idx->screen_ok &&
-                         oi_cosine_screen_supported(idx->dim) &&
-                         (ctx->cosine_mode == OI_COSINE_SCREEN || ctx->cosine_mode == OI_COSINE_SCREEN_COPY);
-    const uint32_t pf_carry = i8_tier ? OI_I8_CARRY : 4096;
-    const uint64_t pf_slack = 128ull * ((uint64_t)ctx->num_cus + 1);
-    uint64_t pf_stride = 1ull << 24;
-    if (pf_stride > budget) pf_stride = budget;
-    if (pf_stride < pf_carry + 4 * pf_slack) pf_stride = pf_carry + 4 * pf_slack;
-    if (pf_stride > pf_carry + n + pf_slack) pf_stride = pf_carry + n + pf_slack;
-    Pools P;
-    // the bf16 screen's state words (carry_cnt[B] tau[B] rs_cnt[B] eps2[B] gate[4] seg_cnt[B][CUs]) ride in the same memset
-    const size_t screen_words = (size_t)B * (6 + (size_t)ctx->num_cus) + 4; // (+ spec_tau[B] spec_max[B]: speculative thresholds)
-    uint32_t *screen_state = nullptr;
-    // (the depth-sized segments of P.bm belong to the workgroup-per-block kernel: no room is set aside for them otherwise)
-    OI_CHECK(prepare_pools(ctx, B, std::max<uint64_t>(cos_stride, idx->rows_bf16 ? 0ull : pf_stride), cos_stride, carry_cap,
-                           bm25_mode_of(idx) == 1 ? idx->n_blocks : 0, depth, &P, screen_words, &screen_state));
-
-    // Speculative thresholds of the screen (cosine_prefilter.hip, pf_spec_kernel; oi_set_screen_speculation).  Decided here because
-    // the chunk schedule depends on it: with a predicted threshold after the first chunk the second can be as large as the pool takes
-    // (10M rows 2.64 -> 2.54 ms, a 1.25M-row shard 0.574 -> 0.540 -> 0.523 with the short first chunk; tools/r05_spec_sched.sh), with
-    // proven thresholds it must grow slowly (x 8).  Off: oi_set_screen_speculation(ctx, 0); with graph replay (the host
-    // decides per call); for batches of <= 8 queries (their survivors cost next to nothing, the extra launches 11 us of 0.34 ms);
-    // for spec_skip searches after a failed check.  OI_NO_SPEC=1, OI_SPEC_GROWTH (ablation builds): A/B.
-    bool spec_on = false;
-    uint64_t screen_growth = oi_chunk_growth(B), screen_first = oi_screen_first_chunk_rows(ctx, depth);
-    if (cos_s && idx->rows && !idx->rows_bf16 && B > 8 && idx->screen_ok && oi_cosine_screen_supported(idx->dim) &&
-        (ctx->cosine_mode == OI_COSINE_SCREEN || ctx->cosine_mode == OI_COSINE_SCREEN_COPY || ctx->cosine_mode == OI_COSINE_SCREEN_STREAM)) {
-        static const bool spec_env_off = oi_ablation_env("OI_NO_SPEC") != nullptr;
-        static const uint64_t spec_growth = oi_ablation_env("OI_SPEC_GROWTH") ? std::max(2, atoi(oi_ablation_env("OI_SPEC_GROWTH"))) : 128;
-        static const uint64_t spec_first_div = oi_ablation_env("OI_SPEC_FIRST_DIV") ? std::max(1, atoi(oi_ablation_env("OI_SPEC_FIRST_DIV"))) : 4;
-        if (ctx->spec_fail_host && *ctx->spec_fail_host) { // a batch since the last look failed its check: back off
-            *ctx->spec_fail_host = 0;
-            ++ctx->spec_failures;
-            ctx->spec_backoff = ctx->spec_backoff ? std::min(1024u, 2 * ctx->spec_backoff) : 16u;
-            ctx->spec_skip = ctx->spec_backoff;
-        }
-        spec_on = ctx->speculate && !spec_env_off && !ctx->use_graphs;
-        if (spec_on && ctx->spec_skip) { --ctx->spec_skip; spec_on = false; }
-        if (spec_on && !ctx->spec_fail_host) {
-            if (hipHostMalloc(reinterpret_cast<void **>(&ctx->spec_fail_host), 64, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                ctx->spec_fail_host = nullptr;
-                spec_on = false; // (no way to hear of a failed check: no speculation)
-            } else *ctx->spec_fail_host = 0;
-        }
-        if (spec_on && n) { // does the rank after the FIRST chunk qualify (pf_spec_kernel is launched when 2 r <= k')?
-            const uint64_t pool_max = pf_stride > pf_carry + pf_slack ? pf_stride - pf_carry - pf_slack : 0; // rows one launch may take
-            // a SHORT first chunk (a quarter of the proven schedule's, >= 8192 rows, >= 8 k': its only job is the sample the
-            // prediction is read from) when everything after it fits ONE launch -- a shard: 8 192 rows, then the rest
-            // (1.25M rows: 0.540 -> 0.523 ms against 28 672 + the rest); a corpus that needs three launches anyway keeps the
-            // regular first chunk and grows x 128 (10M: 28 672, 3.67M, 6.3M rows; a short first chunk measured the same there)
-            const uint64_t first_short = std::min<uint64_t>(n, std::max<uint64_t>(std::max<uint64_t>(8192, 8ull * depth), screen_first / spec_first_div));
-            if (n - first_short <= pool_max && 2 * ((3ull * depth * first_short + n - 1) / n + 12) <= depth) {
-                screen_growth = spec_growth;
-                screen_first = first_short;
-            } else if (2 * ((3ull * depth * std::min<uint64_t>(n, screen_first) + n - 1) / n + 12) <= depth) screen_growth = spec_growth;
-        }
-    }
-
-    // The two legs of a hybrid query are independent until fusion: the BM25 leg (latency-bound, 128 KB of
-    // LDS per workgroup) is issued on a side stream and fills the issue slots the MFMA-bound cosine leg
-    // leaves, instead of running after it.  OI_NO_OVERLAP=1 serialises them (A/B runs).
-    static const bool no_overlap = oi_ablation_env("OI_NO_OVERLAP") != nullptr;
-    if (cos_s && bm_s && !ctx->side_stream && !ctx->side_stream_failed && ctx->overlap_legs && !no_overlap) {
-        // (default priority: at the lowest one the BM25 leg stretched over the whole cosine leg and the step was no shorter)
-        if (hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking) != hipSuccess) { ctx->side_stream = nullptr; ctx->side_stream_failed = true; }
-    }
-    const bool overlap = cos_s && bm_s && ctx->side_stream && ctx->ev_fork && ctx->ev_join && ctx->overlap_legs && !no_overlap;
-    // ---- BM25 list
-    auto bm25_leg = [&]() -> int {
-        hipStream_t st = ctx->stream; // (the side stream when the legs overlap)
-        (void)st;
-        OI_REQUIRE(idx->finalized, "search: index not finalized");
-        // Which BM25 kernel.  Default: the stream kernel (bm25_stream.hip).  The wave-per-task kernel (bm25_wave.hip), the
-        // first-generation workgroup-per-block kernel (bm25.hip) and the batch scan of the forward index
-        // (bm25_scan.hip) stay selectable per index (oi_index_set_bm25_mode) or process-wide with
-        // OI_BM25_MODE=stream|wave|taat|scan; all four return bit-identical lists.
-        const int mode = bm25_mode_of(idx);
-        const bool have_fwd = idx->fwd_terms.p && idx->total_tokens > 0;
-        const bool scan = have_fwd && mode == 2;
-        if (!scan && mode != 1 && mode != 3) {
-            // The STREAM kernel (bm25_stream.hip, the default).  Two phases like the cosine chunks: the first eighth of the doc
-            // blocks is scored with no threshold and fixes tau_q = the depth-th score so far, a lower bound of the final
-            // one; the remaining blocks emit only scores >= tau_q.  A task's pool segment is SMALL and fixed (4096 keys
-            // in the first phase, depth + 256 in the second): a segment that would overflow is pruned in place to its
-            // top `depth` keys, so nothing can overflow whatever the data, and the pool is ~3 MB per query at 10M docs.
-            const uint32_t nb = idx->n_blocks;
-            if (nb == 0 || idx->n_postings == 0) {
-                OI_HIP_CHECK(hipMemsetAsync(bm_c, 0, sizeof(uint32_t) * B, st));
-                return OI_OK;
-            }
-            // (the share of the blocks scored without a threshold: 1/8 and 1/16 measure the same, 1/32 is 5 % slower)
-            static const uint32_t first_div = oi_ablation_env("OI_BM25_FIRST_DIV") ? std::max(1, atoi(oi_ablation_env("OI_BM25_FIRST_DIV"))) : 8;
-            // Up to 48 blocks (1.5M docs: a shard of configs[3]) ONE phase: every touched doc is a candidate (~30K keys per query,
-            // the select's register path), one launch and one select fewer -- 0.052 vs 0.081 ms of kernels at 1.25M docs.
-            // Round 4, second half: NO threshold-less phase at all when the index has its per-term impact floors (bm25.hip): the
-            // plan kernel starts every query at max_t fl(idf_t * floor_t) -- at least `depth` docs score that much, so it is a valid
-            // lower bound of the depth-th best score before a posting is read -- and ONE launch scores every block against it, with the
-            // small pruned segments of the former second phase.  At 10M docs that bound is HIGHER than the first phase's (the 1024th
-            // impact of one term over all docs vs the 1000th score over an eighth of them), and a launch, a select and the first
-            // phase's 30 K candidates per query go away.  OI_BM25_TWO_PHASE=1 (A/B): the phases as before.
-            static const bool two_phase_env = oi_ablation_env("OI_BM25_TWO_PHASE") != nullptr;
-            const bool floors = idx->impact_floor.p != nullptr && !two_phase_env;
-            const uint32_t first = floors ? nb : nb > 48 ? std::max<uint32_t>(8, nb / first_div) : nb;
-            const uint32_t cap1 = oi_bm25_stream_seg_cap(depth, !floors), cap2 = oi_bm25_stream_seg_cap(depth, false);
-            const uint64_t sstride = (uint64_t)carry_cap + std::max<uint64_t>((uint64_t)first * cap1, (uint64_t)nb * cap2);
-            uint64_t pass = (2ull << 30) / 8 / sstride; // <= 2 GiB of pool (0.2 GB for 64 queries over 10M docs)
-            pass = std::max<uint64_t>(1, std::min<uint64_t>(pass, std::min<uint32_t>(B, oi_bm25_stream_pass_queries())));
-            DevBuf &sp = ctx->buf("pool_bm_stream"), &sc = ctx->buf("pool_bm_stream_state");
-            OI_CHECK(sp.ensure(sizeof(uint64_t) * (size_t)pass * sstride));
-            const size_t swords = (size_t)pass * (2 + nb);
-            OI_CHECK(sc.ensure(sizeof(uint32_t) * swords));
-            for (uint32_t q0 = 0; q0 < B; q0 += (uint32_t)pass) {
-                const uint32_t nq = std::min<uint32_t>((uint32_t)pass, B - q0);
-                uint32_t *w = sc.as<uint32_t>();
-                // (the plan launch also zeroes the pass's pool state: carry_cnt[pass] tau[pass] seg_cnt[pass][nb])
-                OI_CHECK(oi_launch_bm25_plan(idx, d_qt, d_qo, q0, nq, w, swords, depth, (uint32_t)pass, (uint32_t)pass, floors));
-                PoolView W1{sp.as<uint64_t>(), w, w + 2 * (size_t)pass, w + pass, sstride, carry_cap, cap1, first, nb, P.bm.overflow};
-                OI_CHECK(oi_launch_bm25_stream(idx, d_qt, d_qo, q0, nq, depth, W1, 0, first));
-                if (first < nb) {
-                    OI_CHECK(oi_launch_select(ctx, W1, nq, depth, /*compact=*/true, nullptr, nullptr, nullptr, depth));
-                    PoolView W2 = W1;
-                    W2.seg_cap = cap2; W2.n_segs = nb; // the first phase's segments are empty again: the same memory, cut anew
-                    OI_CHECK(oi_launch_bm25_stream(idx, d_qt, d_qo, q0, nq, depth, W2, first, nb));
-                    OI_CHECK(oi_launch_select(ctx, W2, nq, depth, false, bm_s + (size_t)q0 * depth, bm_d + (size_t)q0 * depth, bm_c + q0, depth));
-                } else
-                    OI_CHECK(oi_launch_select(ctx, W1, nq, depth, false, bm_s + (size_t)q0 * depth, bm_d + (size_t)q0 * depth, bm_c + q0, depth));
-            }
-            return OI_OK;
-        }
-        if (!scan && mode == 3) {
-            // The wave-per-task kernel.  Two phases like the cosine chunks: the first eighth of the doc blocks is scored with no threshold
-            // (every touched doc is a candidate) and fixes tau_q = the depth-th score so far, a lower bound of
-            // the final one; the remaining blocks emit only scores >= tau_q.  A task's pool segment holds a whole
-            // block, so nothing can overflow; the room is address space, not traffic (only emitted keys are
-            // written).  Queries go in passes sized from a 6 GiB pool budget.
-            const uint32_t nb = idx->n_blocks;
-            if (nb == 0 || idx->n_postings == 0) {
-                OI_HIP_CHECK(hipMemsetAsync(bm_c, 0, sizeof(uint32_t) * B, st));
-                return OI_OK;
-            }
-            const uint64_t wstride = (uint64_t)carry_cap + (uint64_t)nb * OI_BM25_BLOCK_DOCS;
-            uint64_t pass = (6ull << 30) / 8 / wstride;
-            pass = std::max<uint64_t>(1, std::min<uint64_t>(pass, std::min<uint32_t>(B, oi_bm25_wave_pass_queries())));
-            DevBuf &wp = ctx->buf("pool_bm_wave"), &wc = ctx->buf("pool_bm_wave_state");
-            OI_CHECK(wp.ensure(sizeof(uint64_t) * (size_t)pass * wstride));
-            const size_t wwords = (size_t)pass * (2 + nb);
-            OI_CHECK(wc.ensure(sizeof(uint32_t) * wwords));
-            const uint32_t first = nb > 16 ? std::max<uint32_t>(8, nb / 8) : nb;
-            for (uint32_t q0 = 0; q0 < B; q0 += (uint32_t)pass) {
-                const uint32_t nq = std::min<uint32_t>((uint32_t)pass, B - q0);
-                OI_HIP_CHECK(hipMemsetAsync(wc.p, 0, sizeof(uint32_t) * wwords, st));
-                uint32_t *w = wc.as<uint32_t>();
-                PoolView W{wp.as<uint64_t>(), w, w + 2 * (size_t)pass, w + pass, wstride, carry_cap, OI_BM25_BLOCK_DOCS, nb, nb, P.bm.overflow};
-                OI_CHECK(oi_launch_bm25_wave(idx, d_qt, d_qo, q0, nq, W, 0, first));
-                if (first < nb) {
-                    OI_CHECK(oi_launch_select(ctx, W, nq, depth, /*compact=*/true, nullptr, nullptr, nullptr, depth));
-                    OI_CHECK(oi_launch_bm25_wave(idx, d_qt, d_qo, q0, nq, W, first, nb));
-                }
-                OI_CHECK(oi_launch_select(ctx, W, nq, depth, false, bm_s + (size_t)q0 * depth, bm_d + (size_t)q0 * depth, bm_c + q0, depth));
-            }
-            return OI_OK;
-        }
-        if (!scan) {
-            // Term-at-a-time, one WORKGROUP per doc block (the first-generation kernel).  Two phases, like the cosine chunks: the
-            // first eighth of the doc blocks fixes a per-query threshold (the depth-th score seen so far
-            // is a lower bound of the final one); the remaining blocks then emit only candidates at or
-            // above it, so the final selection scans little.
-            const uint32_t nb = idx->n_blocks;
-            const uint32_t first = nb > 16 ? std::max<uint32_t>(8, nb / 8) : nb;
-            OI_CHECK(oi_launch_bm25(idx, d_qt, d_qo, B, depth, P.bm, 0, first));
-            if (first < nb) {
-                OI_CHECK(oi_launch_select(ctx, P.bm, B, depth, /*compact=*/true, nullptr, nullptr, nullptr, depth));
-                OI_CHECK(oi_launch_bm25(idx, d_qt, d_qo, B, depth, P.bm, first, nb));
-            }
-            OI_CHECK(oi_launch_select(ctx, P.bm, B, depth, false, bm_s, bm_d, bm_c, depth));
-        } else {
-            // Batch scan of the forward index (bm25_scan.hip): the whole batch in passes of up to
-            // 1024 / max_query_terms queries; docs in chunks sized from the pool's free room, the first
-            // chunk (1/8 of the docs) fixing the thresholds.  Same worst-case rule as the cosine pools:
-            // a chunk can append at most one entry per doc and query.
-            const uint32_t segs = 2u * (uint32_t)ctx->num_cus;
-            const uint64_t sslack = 1024ull * (segs + 1); // oi_bm25_scan_geometry: a workgroup's docs, rounded up by two tiles
-            uint64_t sstride = carry_cap + std::min<uint64_t>(n, 1ull << 23) + sslack;
-            const uint64_t sbudget = (4ull << 30) / 8 / B;
-            if (sstride > sbudget) sstride = std::max<uint64_t>(sbudget, carry_cap + 4 * sslack);
-            DevBuf &sp = ctx->buf("pool_bm_scan"), &sc = ctx->buf("pool_bm_scan_state");
-            OI_CHECK(sp.ensure(sizeof(uint64_t) * (size_t)B * sstride));
-            const size_t swords = (size_t)B * (2 + segs);
-            OI_CHECK(sc.ensure(sizeof(uint32_t) * swords));
-            OI_HIP_CHECK(hipMemsetAsync(sc.p, 0, sizeof(uint32_t) * swords, st));
-            uint32_t *w = sc.as<uint32_t>();
-            PoolView SP{sp.as<uint64_t>(), w, w + 2 * (size_t)B, w + B, sstride, carry_cap, 0, 0, segs, P.bm.overflow};
-            const uint64_t max_chunk = sstride - carry_cap - sslack;
-            const uint32_t pass = oi_bm25_scan_pass_queries(idx->max_query_terms);
-            for (uint32_t q0 = 0; q0 < B; q0 += pass) {
-                const uint32_t nq = std::min(pass, B - q0);
-                PoolView V = SP;
-                V.carry_cnt += q0; V.tau_keys += q0; // keys / seg_cnt are offset inside the kernel by q_begin
-                uint64_t r = 0, chunk = std::max<uint64_t>(n / 8, 65536);
-                bool first_chunk = true;
-                while (r < n) {
-                    if (chunk > max_chunk) chunk = max_chunk;
-                    const uint64_t e = std::min(n, r + chunk);
-                    oi_bm25_scan_geometry(ctx, e - r, &V.n_segs, &V.seg_cap);
-                    SP.n_segs = V.n_segs; SP.seg_cap = V.seg_cap;
-                    OI_CHECK(oi_launch_bm25_scan(idx, d_qt, d_qo, q0, nq, r, e, idx->avgdl, first_chunk, SP));
-                    const bool last = e == n;
-                    PoolView S2 = SP; // select works on this pass's queries only
-                    S2.keys += (uint64_t)q0 * sstride; S2.carry_cnt += q0; S2.tau_keys += q0;
-                    S2.seg_cnt += (uint64_t)q0 * segs;
-                    OI_CHECK(oi_launch_select(ctx, S2, nq, depth, /*compact=*/!last, last ? bm_s + (size_t)q0 * depth : nullptr,
-                                              last ? bm_d + (size_t)q0 * depth : nullptr, last ? bm_c + q0 : nullptr, depth));
-                    r = e;
-                    chunk = n; // everything that is left, as far as the pool allows
-                    first_chunk = false;
-                }
-            }
-        }
-        return OI_OK;
-    };
-    auto fork_bm25 = [&]() -> int {
-        OI_HIP_CHECK(hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
-        ctx->stream = ctx->side_stream;
-        const int rc = bm25_leg();
-        ctx->stream = st;
-        if (rc != OI_OK) { (void)hipStreamSynchronize(ctx->side_stream); return rc; } // nothing of this call stays in flight
-        OI_HIP_CHECK(hipEventRecord(ctx->ev_join, ctx->side_stream));
-        return OI_OK;
-    };
-    // Round 4: beside the screen the BM25 leg starts with the LAST corpus chunk, not the first.  The screen's persistent
-    // workgroups leave 1/8 of the CUs free; the BM25 kernels (enqueued AFTER the last chunk's launch, so that the screen's
-    // workgroups are resident first) run there while the long chunk streams -- instead of sharing the CUs with the two short
-    // first chunks, whose launches they stretched (10M rows: step 4.998 -> 4.940 ms on one box, -44 .. -58 us on three;
-    // tools/r04_epilogue_probe.sh, r04_old_new_ab.sh).  Only when the last chunk is long enough to cover the leg: >= 512K rows.
-    // OI_BM25_EARLY=1 (A/B): the round-3 placement.
-    static const bool early_env = oi_ablation_env("OI_BM25_EARLY") != nullptr;
-    bool late_pending = false;
-    if (overlap) {
-        bool late = false;
-        if (!early_env && !idx->rows_bf16 && idx->rows &&
-            (ctx->cosine_mode == OI_COSINE_SCREEN || ctx->cosine_mode == OI_COSINE_SCREEN_COPY || ctx->cosine_mode == OI_COSINE_SCREEN_STREAM) && B > 8 && idx->screen_ok &&
-            oi_cosine_screen_supported(idx->dim) && pf_stride > pf_carry + pf_slack) {
-            const uint64_t mc = pf_stride - pf_carry - pf_slack; // the screen's own schedule (cosine_leg below), dry
-            uint64_t chunk = screen_first, r = 0, last = 0;
-            while (r < n) {
-                if (chunk > mc) chunk = mc;
-                const uint64_t e = oi_chunk_end(r, chunk, n, mc, r == 0 ? 0 : chunk * screen_growth);
-                last = e - r;
-                r = e;
-                chunk *= screen_growth;
-            }
-            late = last >= (512u << 10);
-        }
-        if (late) late_pending = true;
-        else {
-            OI_HIP_CHECK(hipEventRecord(ctx->ev_fork, st)); // pools are reset, queries staged
-            OI_CHECK(fork_bm25());
-        }
-    }
-    // ---- cosine list
-    auto cosine_leg = [&]() -> int {
-        if (cos_s && idx->rows_bf16) {
-            // bf16 corpus: same chunk schedule; a workgroup's segment is rounded up to four tiles per wave round
-            const uint64_t bslack = 128ull * ((uint64_t)ctx->num_cus + 1);
-            const uint64_t room = cos_stride - carry_cap;
-            const uint64_t max_chunk = room > bslack ? room - bslack : 0;
-            if (max_chunk == 0) { oi_set_error("search: cosine pool too small"); return OI_ERR_STATE; }
-            uint64_t chunk = oi_first_chunk_rows(depth);
-            uint64_t r = 0;
-            while (r < n) {
-                if (chunk > max_chunk) chunk = max_chunk;
-                const uint64_t e = oi_chunk_end(r, chunk, n, max_chunk, chunk * oi_chunk_growth(B));
-                OI_CHECK(oi_launch_cosine_bf16_chunk(ctx, idx->rows_bf16, r, e, idx->dim, d_qv, B, idx->doc_id_base, P.cos));
-                const bool last = e == n;
-                OI_CHECK(oi_launch_select(ctx, P.cos, B, depth, /*compact=*/!last, last ? cos_s : nullptr,
-                                          last ? cos_d : nullptr, last ? cos_c : nullptr, depth));
-                r = e;
-                chunk *= oi_chunk_growth(B);
-            }
-        } else if (cos_s) {
-            OI_REQUIRE(idx->rows, "search: embeddings not set");
-            const uint32_t Bp = oi_cosine_query_padding(B);
-            const float *q = d_qv;
-            if (Bp != B) {
-                DevBuf &qp = ctx->buf("q_padded");
-                OI_CHECK(qp.ensure(sizeof(float) * (size_t)Bp * idx->dim));
-                OI_HIP_CHECK(hipMemsetAsync(qp.p, 0, sizeof(float) * (size_t)Bp * idx->dim, st));
-                OI_HIP_CHECK(hipMemcpyAsync(qp.p, d_qv, sizeof(float) * (size_t)B * idx->dim, hipMemcpyDeviceToDevice, st));
-                q = qp.as<float>();
-            }
-            const uint64_t max_chunk = oi_cosine_max_chunk_rows(ctx, idx->dim, B, cos_stride, carry_cap);
-            if (max_chunk == 0) { oi_set_error("search: cosine pool too small"); return OI_ERR_STATE; }
-            // the exact pipeline; with a gate it is the fallback behind the bf16 screen and every launch exits at
-            // once unless the screen opened the gate
-            // With a gate and the screen's thresholds it is the fallback behind the bf16 screen: tau~ - 2 eps is a valid
-            // lower bound of the exact k'-th score even when the survivors did not fit, so the exact kernel takes all
-            // rows in ONE launch (as many as the pool holds) -- two launches that exit at once when the gate is shut.
-            auto exact_pipeline = [&](const uint32_t *gate, uint32_t *screen_tau) -> int {
-                SelectExtra ex;
-                ex.run_gate = gate;
-                PoolView X = P.cos;
-                if (screen_tau) X.tau_keys = screen_tau;
-                uint64_t chunk = gate ? max_chunk : oi_first_chunk_rows(depth);
-                uint64_t r = 0;
-                while (r < n) {
-                    if (chunk > max_chunk) chunk = max_chunk;
-                    const uint64_t e = oi_chunk_end(r, chunk, n, max_chunk, chunk * oi_chunk_growth(B));
-                    OI_CHECK(oi_launch_cosine_chunk(ctx, idx->rows, r, e, idx->dim, q, B, Bp, idx->doc_id_base, X));
-                    const bool last = e == n;
-                    OI_CHECK(oi_launch_select(ctx, X, B, depth, /*compact=*/!last, last ? cos_s : nullptr,
-                                              last ? cos_d : nullptr, last ? cos_c : nullptr, depth, gate ? &ex : nullptr));
-                    r = e;
-                    chunk *= oi_chunk_growth(B);
-                }
-                return OI_OK;
-            };
-            static const bool shape16 = !(oi_ablation_env("OI_KS_SHAPE") && atoi(oi_ablation_env("OI_KS_SHAPE")) == 32);
-            static const bool cos_v1 = oi_ablation_env("OI_COSINE_V1") != nullptr || oi_ablation_env("OI_SELECT_V1") != nullptr;
-            // (a view never makes a copy of its own: it streams the source's if that exists, the f32 rows otherwise)
-            // OI_COSINE_SCREEN streams the index's bf16 screening copy when there is one (made at finalize, budget permitting);
-            // _COPY also makes a missing one now; _STREAM converts the f32 rows on the fly whatever the index holds
-            const bool want_copy = ctx->cosine_mode != OI_COSINE_SCREEN_STREAM &&
-                                   (idx->screen_copy.p != nullptr || (ctx->cosine_mode == OI_COSINE_SCREEN_COPY && !idx->is_view));
-            // B <= 8 (configs[1]: one query): screened only when there is a copy to stream -- half the bytes of the f32 GEMV, which
-            // is HBM-bound; the f32-stream screen would read what the GEMV reads.  OI_SMALL_BATCH_GEMV=1 (A/B): as before round 5.
-            static const bool small_gemv = oi_ablation_env("OI_SMALL_BATCH_GEMV") != nullptr;
-            const bool screen = (ctx->cosine_mode == OI_COSINE_SCREEN || ctx->cosine_mode == OI_COSINE_SCREEN_COPY ||
-                                 ctx->cosine_mode == OI_COSINE_SCREEN_STREAM) && (B > 8 || (want_copy && !small_gemv)) &&
-                                oi_cosine_screen_supported(idx->dim) && idx->screen_ok && shape16 && !cos_v1;
-            if (!screen) {
-                ctx->last_screen_gate = nullptr; // (profile "screen_gate": -1 = this search was not screened)
-                return exact_pipeline(nullptr, nullptr);
-            }
-
-            // ---- bf16 screen -> margin selects -> exact rescoring -> sorted selection; then the gated exact pipeline
-            // (cosine_prefilter.hip).  Its pool keeps up to 4096 keys per query between chunks.
-            const uint32_t segs = (uint32_t)ctx->num_cus;
-            // state, zeroed with one memset: carry_cnt[B] tau[B] rs_cnt[B] eps2[B] gate[4] seg_cnt[B][segs] spec_tau[B] spec_max[B]
-            const size_t words = (size_t)B * (6 + segs) + 4;
-            DevBuf &pk = ctx->buf("pool_cos"), &rk = ctx->buf("screen_rescored"), &qb = ctx->buf("screen_q_bf16");
-            OI_REQUIRE(words <= screen_words, "search: screen state does not fit its reservation");
-            OI_REQUIRE(pk.cap >= sizeof(uint64_t) * (size_t)B * pf_stride, "search: the shared cosine pool is too small for the screen's view");
-            const uint32_t rs_cap = pf_carry + OI_LONG_ROWS_MAX; // the survivors and the index's long rows (two-class margin)
-            OI_CHECK(rk.ensure(sizeof(uint64_t) * (size_t)B * rs_cap));
-            const uint32_t n_padded = (B + 31u) & ~31u;
-            OI_CHECK(qb.ensure(sizeof(uint16_t) * (size_t)(n_padded + 64) * idx->dim));
-            uint32_t *w = screen_state; // zeroed with the pool state (prepare_pools)
-            uint32_t *pf_cnt = w, *pf_tau = w + B, *rs_cnt = w + 2 * (size_t)B;
-            float *eps2 = reinterpret_cast<float *>(w + 3 * (size_t)B);
-            uint32_t *gate = w + 4 * (size_t)B, *pf_seg = gate + 4;
-            uint32_t *spec_tau = pf_seg + (size_t)B * segs, *spec_max = spec_tau + B;
-            PoolView PF{pk.as<uint64_t>(), pf_cnt, pf_seg, pf_tau, pf_stride, pf_carry, 0, 0, segs, P.cos.overflow};
-            PoolView RS{rk.as<uint64_t>(), rs_cnt, pf_seg, nullptr, rs_cap, rs_cap, 0, 0, segs, P.cos.overflow};
-            OI_CHECK(oi_launch_screen_stage(ctx, d_qv, B, idx->dim, idx->max_row_norm.as<uint32_t>(), qb.as<uint16_t>(),
-                                            eps2, gate));
-            const uint64_t pf_max_chunk = pf_stride - pf_carry - pf_slack;
-            SelectExtra mx;
-            mx.eps2 = eps2;
-            mx.margin_gate = gate;
-            if (idx->n_long) { mx.skip_bitmap = idx->long_bitmap.as<uint32_t>(); mx.skip_base = idx->doc_id_base; }
-            if (want_copy && !idx->screen_copy.p) { // made once, on the first search that asks for it (n x d x 2 B of HBM)
-                OI_CHECK(idx->screen_copy.ensure(sizeof(uint16_t) * (size_t)n * idx->dim + 64));
-                OI_CHECK(oi_launch_make_screen_copy(ctx, idx->rows, n, idx->dim, idx->screen_copy.as<uint16_t>()));
-            }
-            // The int8 first tier (cosine_screen_i8.hip): the chunks stream the int8 copy against per-row bounds, the
-            // margin selects keep up to OI_I8_CARRY lower-bound keys per query (an overflow opens the gate), the speculation works on
-            // those keys; after the last chunk the survivors get their bf16 screen keys from the bf16 copy and the bf16 screen's
-            // final margin select, rescoring and gate follow unchanged.
-            const bool i8 = i8_tier && want_copy;
-            OI_REQUIRE(!i8 || pf_carry == OI_I8_CARRY, "search: int8 tier without its carry");
-            int8_t *qi8 = nullptr;
-            float *qf8 = nullptr;
-            SelectExtra m8 = mx;
-            if (i8) {
-                DevBuf &qs = ctx->buf("screen_q_i8"), &cb = ctx->buf("screen_i8_cand");
-                const size_t qi8_bytes = ((2 * (size_t)n_padded * idx->dim) + 255) & ~(size_t)255;
-                OI_CHECK(qs.ensure(qi8_bytes + sizeof(float) * 4 * (size_t)n_padded));
-                OI_CHECK(cb.ensure(sizeof(uint64_t) * (size_t)B * OI_I8_CARRY));
-                qi8 = reinterpret_cast<int8_t *>(qs.p);
-                qf8 = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(qs.p) + qi8_bytes);
-                OI_CHECK(oi_launch_screen_stage_i8(ctx, d_qv, B, idx->dim, idx->max_row_norm.as<uint32_t>(), idx->screen_i8.as<uint8_t>(), n,
-                                                   qi8, qf8, gate));
-                m8.eps2 = qf8 + 3 * (size_t)n_padded;
-                m8.cand = cb.as<uint64_t>();
-                m8.cand_cap = OI_I8_CARRY;
-                m8.row_meta = reinterpret_cast<const float *>(idx->screen_i8.as<uint8_t>() + oi_screen_i8_meta_offset(n, idx->dim));
-                m8.meta_base = idx->doc_id_base;
-                m8.row_qn = qf8 + (size_t)n_padded;
-                m8.row_cq = qf8 + 2 * (size_t)n_padded;
-            }
-            // Speculative thresholds (decided above: spec_on, screen_growth): the next chunk is screened against the larger of
-            // the proven threshold and a prediction from the rows seen so far, checked at the end (a failed check opens the gate).
-            const bool spec = spec_on;
-            bool spec_next = false, spec_any = false;
-            uint64_t chunk = screen_first;
-            uint64_t r = 0;
-            while (r < n) {
-                if (chunk > pf_max_chunk) chunk = pf_max_chunk;
-                const uint64_t e = oi_chunk_end(r, chunk, n, pf_max_chunk, r == 0 ? 0 : chunk * screen_growth); // (r == 0: the threshold-less first chunk is never stretched)
-                // the same products, the same bound: only where bf16(x) comes from differs (converted on the fly from the
-                // f32 rows, 4 d bytes per row -- or read from the copy, 2 d bytes per row)
-                if (late_pending && e == n) OI_HIP_CHECK(hipEventRecord(ctx->ev_fork, st)); // (before the last chunk's launch)
-                uint32_t *const proven_tau = PF.tau_keys;
-                if (spec_next) PF.tau_keys = spec_tau; // (this launch only: the selects keep the proven thresholds)
-                const int rc_screen = i8 ? oi_launch_cosine_screen_i8_chunk(ctx, idx->screen_i8.as<uint8_t>(), n, r, e, idx->dim, qi8, qf8, B, idx->doc_id_base, PF)
-                                      : want_copy ? oi_launch_cosine_screen_copy_chunk(ctx, idx->screen_copy.as<uint16_t>(), r, e, idx->dim, qb.as<uint16_t>(), B, idx->doc_id_base, PF)
-                                                  : oi_launch_cosine_screen_chunk(ctx, idx->rows, r, e, idx->dim, qb.as<uint16_t>(), B, idx->doc_id_base, PF);
-                PF.tau_keys = proven_tau;
-                OI_CHECK(rc_screen);
-                if (late_pending && e == n) { late_pending = false; OI_CHECK(fork_bm25()); } // ... enqueued after it: the screen's workgroups get their CUs first
-                OI_CHECK(oi_launch_select(ctx, PF, B, depth, /*compact=*/true, nullptr, nullptr, nullptr, depth, i8 ? &m8 : &mx));
-                r = e;
-                chunk *= screen_growth;
-                spec_next = false;
-                if (spec && r < n) {
-                    // expected rank of the final k'-th among the r rows seen: depth r / n; three times that plus twelve
-                    const uint64_t rank = (3ull * depth * r + n - 1) / n + 12;
-                    if (2 * rank <= depth) {
-                        OI_CHECK(oi_launch_spec_threshold(ctx, PF, B, (uint32_t)rank, i8 ? m8.eps2 : eps2, spec_tau, spec_max));
-                        spec_next = spec_any = true;
-                    }
-                }
-            }
-            if (spec_any) ++ctx->spec_searches;
-            PoolView PR = PF; // what the rescoring reads: the bf16 screen's final survivors (<= 4096 per query)
-            if (i8) {
-                // the int8 survivors' bf16 keys (in place), then the bf16 screen's final margin select over them; the int8 tier's
-                // proven thresholds stay (the speculation check and the gated exact pipeline read them)
-                OI_CHECK(oi_launch_rescreen_bf16(ctx, idx->screen_copy.as<uint16_t>(), n, idx->dim, idx->doc_id_base, qb.as<uint16_t>(), B, PF));
-                PoolView PB = PF;
-                PB.tau_keys = nullptr;
-                PB.n_segs = 0;
-                OI_CHECK(oi_launch_select(ctx, PB, B, depth, /*compact=*/true, nullptr, nullptr, nullptr, depth, &mx));
-                PR.carry_cap = 4096;
-            }
-            // (the check of the speculative thresholds against the proven final ones rides in the rescoring launch; the gated exact
-            // pipeline is enqueued after it)
-            OI_CHECK(oi_launch_rescore(ctx, idx->rows, n, idx->dim, idx->doc_id_base, d_qv, B, PR, RS,
-                                       idx->n_long ? idx->long_list.as<uint32_t>() : nullptr, idx->n_long,
-                                       spec_any ? spec_max : nullptr, pf_tau, gate, ctx->spec_fail_host));
-            RS.n_segs = 0;
-            OI_CHECK(oi_launch_select(ctx, RS, B, depth, false, cos_s, cos_d, cos_c, depth));
-            ctx->run_gate = gate;
-            ctx->last_screen_gate = gate;
-            const int rc = exact_pipeline(gate, pf_tau);
-            ctx->run_gate = nullptr;
-            return rc;
-        }
-        return OI_OK;
-    };
-    {
-        const int rc = cosine_leg();
-        if (rc != OI_OK) { // nothing of this call stays in flight behind an error return
-            if (overlap) (void)hipStreamSynchronize(ctx->side_stream);
-            return rc;
-        }
-    }
-    if (late_pending) { // (the screen was not taken after all)
-        OI_HIP_CHECK(hipEventRecord(ctx->ev_fork, st));
-        OI_CHECK(fork_bm25());
-    }
-    if (overlap) OI_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_join, 0));
-    else if (bm_s) OI_CHECK(bm25_leg());
-    return OI_OK;
-}
 
 struct QueryStage {
     const float *qv;

@@ -223,7 +223,7 @@ uint64_t oi_cosine_max_chunk_rows(const oi_ctx *ctx, uint32_t dim, uint32_t n_qu
     // K-split: segments are rounded up to whole tiles per workgroup -> up to 32 * (CUs + 1) slack
     const uint64_t slack = 32ull * ((uint64_t)ctx->num_cus + 1);
     const uint64_t room = stride - carry_cap;
-    return room > slack ? room - slack : 0; // api.hip sizes the pool so that room >= min(n, 3*slack) + slack
+    return room > slack ? room - slack : 0; // search.hip sizes the pool so that room >= min(n, 3*slack) + slack
 }
 
 uint32_t oi_cosine_query_padding(uint32_t n_queries) {

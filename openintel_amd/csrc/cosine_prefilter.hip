@@ -620,7 +620,7 @@ __global__ __launch_bounds__(256) void pf_rescore_kernel(const float *__restrict
 // the speculation dropped (s~ < T_spec) would have been dropped by the final proven threshold as well: the survivor set still
 // holds every row of the exact list, the lists are the proven screen's.  Otherwise (a corpus whose first rows are not a fair
 // sample: sorted by time or topic) the gate opens and the exact pipeline rescores the batch in the same call, and the host,
-// told through a pinned flag, stops speculating for a while (api.hip: spec_backoff).
+// told through a pinned flag, stops speculating for a while (search.hip: oi_spec_take_failure).
 __global__ __launch_bounds__(256) void pf_spec_kernel(const uint64_t *__restrict__ pools, const uint32_t *__restrict__ carry_cnt,
                                                       uint64_t stride, uint32_t cap, uint32_t r, const float *__restrict__ eps2,
                                                       const uint32_t *__restrict__ tau_keys, uint32_t *spec_tau, uint32_t *spec_max) {

@@ -133,7 +133,7 @@ struct oi_ctx {
     std::mutex mu;
     std::map<std::string, DevBuf> ws; // named workspaces
     int prof_enabled = 0; // 0 off, 1 every tagged launch, 2 the cosine scorer only
-    // set by api.hip around the gated exact pipeline that follows a bf16 screen (cosine_prefilter.hip): the exact
+    // set by search.hip around the gated exact pipeline that follows a bf16 screen (cosine_prefilter.hip): the exact
     // cosine kernel and the selects launched meanwhile exit at once unless *run_gate is nonzero
     const uint32_t *run_gate = nullptr;
     const uint32_t *last_screen_gate = nullptr; // the gate word of the last screened search (diagnostics)
@@ -220,6 +220,11 @@ struct oi_index {
                                    // 4 the stream kernel (bm25_stream.hip)
     bool is_view = false;          // oi_index_view: the data belongs to another index; this handle only searches
 };
+
+// search.hip: one hybrid search on the device (the entry points in api.hip stage the queries and copy the results)
+int search_lists_device(oi_index *idx, const float *d_qv, const uint32_t *d_qt, const uint32_t *d_qo, uint32_t B, uint32_t depth,
+                        float *cos_s, uint32_t *cos_d, uint32_t *cos_c, float *bm_s, uint32_t *bm_d, uint32_t *bm_c);
+void oi_spec_take_failure(oi_ctx *ctx); // a failed speculation check seen since the last look: back off
 
 // ---------------------------------------------------------------- kernels (host launchers)
 // lexicon.hip
@@ -311,6 +316,11 @@ bool oi_cosine_ksplit_supported(uint32_t dim);
 void oi_cosine_ksplit_geometry(const oi_ctx *ctx, uint64_t n_rows, uint32_t *n_segs, uint32_t *seg_cap);
 // cosine_prefilter.hip: the bf16 screen + exact rescoring of an f32 corpus
 bool oi_cosine_screen_supported(uint32_t dim);
+// The bf16 screen (and the screening copies behind it) applies to this index's corpus: f32 rows of a dim the screen kernels are
+// built for, with norms finite and small enough for its bound.
+inline bool oi_index_screenable(const oi_index *idx) {
+    return idx->rows && !idx->rows_bf16 && idx->screen_ok && oi_cosine_screen_supported(idx->dim);
+}
 void oi_cosine_screen_geometry(const oi_ctx *ctx, uint64_t n_rows, uint32_t *n_segs, uint32_t *seg_cap);
 int oi_launch_row_norm_max(oi_ctx *ctx, const float *rows, uint64_t n, uint32_t dim, uint32_t *max_bits);
 int oi_launch_screen_stage(oi_ctx *ctx, const float *d_queries, uint32_t n_queries, uint32_t dim,

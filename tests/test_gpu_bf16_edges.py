@@ -4,7 +4,7 @@ One search over a bf16 corpus can run four kernels, chosen per corpus chunk and 
 the solo kernel (cosine_bf16_filter<D, 1 | 2>), the pair kernel (cosine_bf16_pair<D, 2 | 3>), the query-split kernel
 (cosine_bf16_qsplit<0>: 97-128 queries at d = 1024) and its sibling form (cosine_bf16_qsplit<2>: 256 queries at d = 1024 as two
 workgroups per tile, only when B % 256 == 0 and the chunk has >= 32 x num_cus rows).  The search cuts the corpus into chunks
-(api.hip: oi_first_chunk_rows, oi_chunk_growth, oi_chunk_end, the pool budget of search_lists_device), so one search can run
+(search.hip: oi_first_chunk_rows, oi_chunk_growth, chunk_schedule, the pool budget of plan_search), so one search can run
 siblings on one chunk and qsplit<0> on the next, both carrying into the same pools.
 
 CASES below is the table of what this module runs.  A pure-Python mirror of the dispatch rules (`schedule`) computes each case's
@@ -41,17 +41,17 @@ def cb_group(dim: int, left: int) -> int:
 
 
 def first_chunk_rows(depth: int) -> int:
-    """api.hip: oi_first_chunk_rows."""
+    """search.hip: oi_first_chunk_rows."""
     return max(max(8192, 32 * depth), 2 * depth)
 
 
 def chunk_growth(B: int) -> int:
-    """api.hip: oi_chunk_growth."""
+    """search.hip: oi_chunk_growth."""
     return 16 if B <= 8 else 8
 
 
 def chunk_end(r: int, chunk: int, n: int, max_chunk: int, next_chunk: int) -> int:
-    """api.hip: oi_chunk_end."""
+    """search.hip: oi_chunk_end."""
     e = min(n, r + chunk)
     if e < n and (n - e) * 4 <= (e - r) and n - r <= max_chunk:
         e = n
@@ -61,7 +61,7 @@ def chunk_end(r: int, chunk: int, n: int, max_chunk: int, next_chunk: int) -> in
 
 
 def bf16_pool(n: int, B: int, num_cus: int) -> Tuple[int, int]:
-    """api.hip, search_lists_device: (cos_stride, max_chunk) of a bf16 corpus."""
+    """search.hip, plan_search and cosine_bf16: (cos_stride, max_chunk) of a bf16 corpus."""
     carry_cap = OI_MAX_DEPTH
     slack = 128 * (num_cus + 1)
     cos_stride = 1 << 24
@@ -124,7 +124,7 @@ class Chunk(NamedTuple):
 
 
 def schedule(n: int, dim: int, B: int, depth: int, num_cus: int):
-    """The chunks of one search over an n-row bf16 corpus (api.hip: cosine_leg of search_lists_device)."""
+    """The chunks of one search over an n-row bf16 corpus (search.hip: cosine_bf16, through chunk_schedule)."""
     _, max_chunk = bf16_pool(n, B, num_cus)
     assert max_chunk > 0
     chunks, chunk, r = [], first_chunk_rows(depth), 0
