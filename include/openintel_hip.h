@@ -440,6 +440,52 @@ int oi_search_sharded(oi_index *idx, oi_comm *comm, const float *query_vecs, con
                       float *scores_out, uint32_t *docs_out, uint32_t *counts_out);
 
 /* ------------------------------------------------------------------------- */
+/* Filtered search: the best rows among the documents that match a predicate    */
+/* ------------------------------------------------------------------------- */
+/*
+ * A document has two caller-defined 32-bit attributes, `group` and `stamp` (e.g. a ticker id and source bits; minutes
+ * since an epoch).  A query carries one filter; document d passes when
+ *     (group[d] & group_mask) == group_value  &&  stamp_lo <= stamp[d] && stamp[d] <= stamp_hi      (bounds inclusive)
+ * {0, 0, 0, 0xFFFFFFFF} passes every document.
+ *
+ * A filter selects documents; it changes no score.  BM25 idf and average length stay the whole collection's (finalize /
+ * finalize_sharded), cosine scores are the f32 values the unfiltered search returns for those rows.  A filtered list is the
+ * unfiltered full ranking restricted to the passing documents and cut at `depth`: same order (score desc, doc id asc),
+ * the BM25 list holds scores > 0 only, counts[q] is anything from 0 to depth.  RRF fuses the two filtered lists as usual.
+ *
+ * oi_index_set_doc_attrs: `n_docs` entries each, indexed by LOCAL row; either array may be NULL (zeros).  Allowed before or
+ * after finalize.  The index holds one interleaved {group, stamp} pair per row (8 B), allocated by the first call and never
+ * reallocated: a later call overwrites it in place, stream-ordered on the index's ctx (retag or "soft-delete" documents
+ * without a rebuild).  Views alias it like every other index buffer and see later updates; a view made before any
+ * attributes existed has none.  On a view: OI_ERR_STATE.
+ *
+ * The *_filtered calls take the arguments of their unfiltered twin plus `filters` (n_queries entries, where `location`
+ * says).  filters == NULL: exactly the unfiltered call (same kernels, same bytes).  A filtered search on an index without
+ * attributes returns OI_ERR_STATE.  oi_search_sharded_filtered: each rank filters its own shard; merge and fusion
+ * are unchanged.  Graph replay (oi_set_graph_replay): the capture key includes the filters pointer; a replay reads the
+ * filter and attribute CONTENTS at replay time, so changing either between replays is seen by the next one.
+ */
+typedef struct oi_doc_filter {
+    uint32_t group_mask, group_value, stamp_lo, stamp_hi;
+} oi_doc_filter;
+int oi_index_set_doc_attrs(oi_index *idx, const uint32_t *group, const uint32_t *stamp, int location);
+int oi_search_lists_filtered(oi_index *idx, const float *query_vecs, const uint32_t *query_terms,
+                             const uint32_t *q_term_offsets, uint32_t n_queries, uint32_t depth,
+                             const oi_doc_filter *filters, int location, float *cos_scores, uint32_t *cos_docs,
+                             uint32_t *cos_counts, float *bm25_scores, uint32_t *bm25_docs, uint32_t *bm25_counts);
+int oi_search_lists_packed_filtered(oi_index *idx, const float *query_vecs, const uint32_t *query_terms,
+                                    const uint32_t *q_term_offsets, uint32_t n_queries, uint32_t depth,
+                                    const oi_doc_filter *filters, int location, uint32_t *packed_out);
+int oi_search_filtered(oi_index *idx, const float *query_vecs, const uint32_t *query_terms,
+                       const uint32_t *q_term_offsets, uint32_t n_queries, uint32_t depth, uint32_t k,
+                       const oi_doc_filter *filters, int location, float *scores_out, uint32_t *docs_out,
+                       uint32_t *counts_out);
+int oi_search_sharded_filtered(oi_index *idx, oi_comm *comm, const float *query_vecs, const uint32_t *query_terms,
+                               const uint32_t *q_term_offsets, uint32_t n_queries, uint32_t depth, uint32_t k,
+                               const oi_doc_filter *filters, int location, float *scores_out, uint32_t *docs_out,
+                               uint32_t *counts_out);
+
+/* ------------------------------------------------------------------------- */
 /* The pipelined query behind the C ABI: several batches in flight             */
 /* ------------------------------------------------------------------------- */
 /*

@@ -34,6 +34,17 @@ pub struct OiSocialCounters {
     pub polarity_sum: f64,
 }
 
+/// `oi_doc_filter`: document d passes when (group[d] & group_mask) == group_value && stamp_lo <= stamp[d] <= stamp_hi.
+/// `{0, 0, 0, u32::MAX}` passes every document.
+#[repr(C)]
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub struct OiDocFilter {
+    pub group_mask: u32,
+    pub group_value: u32,
+    pub stamp_lo: u32,
+    pub stamp_hi: u32,
+}
+
 pub const OI_OK: c_int = 0;
 pub const OI_ERR_ANALYZER_MISMATCH: c_int = -3;
 pub const OI_ERR_OVERFLOW: c_int = -8;
@@ -141,6 +152,23 @@ extern "C" {
     pub fn oi_search_sharded(idx: *mut OiIndex, comm: *mut OiComm, query_vecs: *const f32, query_terms: *const u32,
                              q_term_offsets: *const u32, n_queries: u32, depth: u32, k: u32, location: c_int,
                              scores_out: *mut f32, docs_out: *mut u32, counts_out: *mut u32) -> c_int;
+
+    // filtered search (per-document group / stamp attributes, one oi_doc_filter per query)
+    pub fn oi_index_set_doc_attrs(idx: *mut OiIndex, group: *const u32, stamp: *const u32, location: c_int) -> c_int;
+    pub fn oi_search_lists_filtered(idx: *mut OiIndex, query_vecs: *const f32, query_terms: *const u32, q_term_offsets: *const u32,
+                                    n_queries: u32, depth: u32, filters: *const OiDocFilter, location: c_int,
+                                    cos_scores: *mut f32, cos_docs: *mut u32, cos_counts: *mut u32, bm25_scores: *mut f32,
+                                    bm25_docs: *mut u32, bm25_counts: *mut u32) -> c_int;
+    pub fn oi_search_lists_packed_filtered(idx: *mut OiIndex, query_vecs: *const f32, query_terms: *const u32,
+                                           q_term_offsets: *const u32, n_queries: u32, depth: u32, filters: *const OiDocFilter,
+                                           location: c_int, packed_out: *mut u32) -> c_int;
+    pub fn oi_search_filtered(idx: *mut OiIndex, query_vecs: *const f32, query_terms: *const u32, q_term_offsets: *const u32,
+                              n_queries: u32, depth: u32, k: u32, filters: *const OiDocFilter, location: c_int,
+                              scores_out: *mut f32, docs_out: *mut u32, counts_out: *mut u32) -> c_int;
+    pub fn oi_search_sharded_filtered(idx: *mut OiIndex, comm: *mut OiComm, query_vecs: *const f32, query_terms: *const u32,
+                                      q_term_offsets: *const u32, n_queries: u32, depth: u32, k: u32,
+                                      filters: *const OiDocFilter, location: c_int, scores_out: *mut f32, docs_out: *mut u32,
+                                      counts_out: *mut u32) -> c_int;
 
     pub fn oi_pipeline_create(idx: *mut OiIndex, comm: *mut OiComm, lanes: u32, max_queries: u32, max_query_terms: u32,
                               depth: u32, k: u32, out: *mut *mut OiPipeline) -> c_int;

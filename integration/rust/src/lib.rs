@@ -172,6 +172,7 @@ pub struct HipIndex {
     ctx: Arc<HipCtx>,
     idx: *mut ffi::OiIndex,
     dim: usize,
+    n_docs: usize, // rows of this shard (the length of every per-document array)
     source: Option<Arc<HipIndex>>, // a view keeps the index it borrows from alive (oi_index_view)
 }
 unsafe impl Send for HipIndex {}
@@ -185,13 +186,32 @@ pub struct RankedPost {
     pub doc_id: u32,
     pub score: f32,
 }
+/// Concatenated query terms and their offsets (a never-empty term buffer).
+fn flatten_terms(query_terms: &[Vec<u32>]) -> (Vec<u32>, Vec<u32>) {
+    let mut flat = Vec::new();
+    let mut offs = vec![0u32];
+    for t in query_terms {
+        flat.extend_from_slice(t);
+        offs.push(flat.len() as u32);
+    }
+    if flat.is_empty() {
+        flat.push(0);
+    }
+    (flat, offs)
+}
+/// The first counts[q] entries of each query's row of stride k.
+fn ranked(s: &[f32], d: &[u32], c: &[u32], k: usize) -> Vec<Vec<RankedPost>> {
+    (0..c.len())
+        .map(|q| (0..c[q] as usize).map(|i| RankedPost { doc_id: d[q * k + i], score: s[q * k + i] }).collect())
+        .collect()
+}
 impl HipIndex {
     /// rows: n_docs x dim f32 (copied to HBM, L2-normalised); forward index: doc d owns terms[offsets[d]..offsets[d+1]].
     pub fn build(ctx: Arc<HipCtx>, rows: &mut [f32], dim: usize, vocab: u32, terms: &[u32], offsets: &[u64]) -> Result<Self, HipError> {
         let n_docs = (rows.len() / dim) as u64;
         let mut idx = std::ptr::null_mut();
         check(unsafe { ffi::oi_index_create(ctx.raw(), n_docs, dim as u32, vocab, 0, &mut idx) })?;
-        let me = HipIndex { ctx, idx, dim, source: None };
+        let me = HipIndex { ctx, idx, dim, n_docs: n_docs as usize, source: None };
         check(unsafe { ffi::oi_index_set_embeddings(me.idx, rows.as_mut_ptr(), ffi::OI_HOST, 1) })?;
         check(unsafe { ffi::oi_index_set_forward(me.idx, terms.as_ptr(), offsets.as_ptr(), ffi::OI_HOST) })?;
         let mut tokens = 0u64;
@@ -204,7 +224,30 @@ impl HipIndex {
     pub fn view(self: &Arc<Self>, ctx: Arc<HipCtx>) -> Result<HipIndex, HipError> {
         let mut idx = std::ptr::null_mut();
         check(unsafe { ffi::oi_index_view(self.idx, ctx.raw(), &mut idx) })?;
-        Ok(HipIndex { ctx, idx, dim: self.dim, source: Some(Arc::clone(self)) })
+        Ok(HipIndex { ctx, idx, dim: self.dim, n_docs: self.n_docs, source: Some(Arc::clone(self)) })
+    }
+    /// Per-document attributes of filtered searches (`oi_index_set_doc_attrs`): n_docs entries each, local rows; None = zeros.
+    /// A later call overwrites them in place (retag or soft-delete posts without a rebuild).
+    pub fn set_doc_attrs(&self, group: Option<&[u32]>, stamp: Option<&[u32]>) -> Result<(), HipError> {
+        for a in [group, stamp].into_iter().flatten() {
+            assert_eq!(a.len(), self.n_docs, "one attribute per document of the shard"); // (the C call reads n_docs of each)
+        }
+        let p = |a: Option<&[u32]>| a.map_or(std::ptr::null(), |v| v.as_ptr());
+        check(unsafe { ffi::oi_index_set_doc_attrs(self.idx, p(group), p(stamp), ffi::OI_HOST) })
+    }
+    /// `search` restricted to the documents that pass each query's filter (one per query): scores unchanged.
+    pub fn search_filtered(&self, query_vecs: &[f32], query_terms: &[Vec<u32>], filters: &[ffi::OiDocFilter], k: usize,
+                           depth: usize) -> Result<Vec<Vec<RankedPost>>, HipError> {
+        let b = query_terms.len();
+        assert_eq!(query_vecs.len(), b * self.dim);
+        assert_eq!(filters.len(), b);
+        let (flat, offs) = flatten_terms(query_terms);
+        let (mut s, mut d, mut c) = (vec![0f32; b * k], vec![0u32; b * k], vec![0u32; b]);
+        check(unsafe {
+            ffi::oi_search_filtered(self.idx, query_vecs.as_ptr(), flat.as_ptr(), offs.as_ptr(), b as u32, depth as u32,
+                                    k as u32, filters.as_ptr(), ffi::OI_HOST, s.as_mut_ptr(), d.as_mut_ptr(), c.as_mut_ptr())
+        })?;
+        Ok(ranked(&s, &d, &c, k))
     }
     /// Hybrid BM25 + cosine + RRF: one ranked list (<= k) per query, in query order.
     pub fn search(&self, query_vecs: &[f32], query_terms: &[Vec<u32>], k: usize, depth: usize) -> Result<Vec<Vec<RankedPost>>, HipError> {
@@ -269,11 +312,26 @@ impl HipIndex {
         let n_docs = (rows.len() / dim) as u64;
         let mut idx = std::ptr::null_mut();
         check(unsafe { ffi::oi_index_create(comm.ctx.raw(), n_docs, dim as u32, vocab, doc_id_base, &mut idx) })?;
-        let me = HipIndex { ctx: comm.ctx.clone(), idx, dim, source: None };
+        let me = HipIndex { ctx: comm.ctx.clone(), idx, dim, n_docs: n_docs as usize, source: None };
         check(unsafe { ffi::oi_index_set_embeddings(me.idx, rows.as_mut_ptr(), ffi::OI_HOST, 1) })?;
         check(unsafe { ffi::oi_index_set_forward(me.idx, terms.as_ptr(), offsets.as_ptr(), ffi::OI_HOST) })?;
         check(unsafe { ffi::oi_index_finalize_sharded(me.idx, comm.comm) })?;
         Ok(me)
+    }
+    /// `search_sharded` with one doc filter per query: each rank filters its own shard; merge and fusion unchanged.
+    pub fn search_sharded_filtered(&self, comm: &HipComm, query_vecs: &[f32], query_terms: &[Vec<u32>],
+                                   filters: &[ffi::OiDocFilter], k: usize, depth: usize) -> Result<Vec<Vec<RankedPost>>, HipError> {
+        let b = query_terms.len();
+        assert_eq!(query_vecs.len(), b * self.dim);
+        assert_eq!(filters.len(), b);
+        let (flat, offs) = flatten_terms(query_terms);
+        let (mut s, mut d, mut c) = (vec![0f32; b * k], vec![0u32; b * k], vec![0u32; b]);
+        check(unsafe {
+            ffi::oi_search_sharded_filtered(self.idx, comm.comm, query_vecs.as_ptr(), flat.as_ptr(), offs.as_ptr(), b as u32,
+                                            depth as u32, k as u32, filters.as_ptr(), ffi::OI_HOST, s.as_mut_ptr(),
+                                            d.as_mut_ptr(), c.as_mut_ptr())
+        })?;
+        Ok(ranked(&s, &d, &c, k))
     }
     /// The hybrid query over ALL shards (collective, same queries on every rank, one ncclAllGather per batch inside):
     /// identical lists on every rank, global doc ids.

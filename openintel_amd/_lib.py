@@ -51,6 +51,16 @@ class SocialCounters(C.Structure):
     ]
 
 
+class DocFilter(C.Structure):
+    """oi_doc_filter: a document passes when (group & group_mask) == group_value and stamp_lo <= stamp <= stamp_hi."""
+    _fields_ = [
+        ("group_mask", C.c_uint32),
+        ("group_value", C.c_uint32),
+        ("stamp_lo", C.c_uint32),
+        ("stamp_hi", C.c_uint32),
+    ]
+
+
 _P = C.c_void_p
 _U32, _U64, _I = C.c_uint32, C.c_uint64, C.c_int
 
@@ -102,6 +112,11 @@ SIGNATURES = {
     "oi_comm_destroy": (None, [_P]),
     "oi_index_finalize_sharded": (_I, [_P, _P]),
     "oi_search_sharded": (_I, [_P, _P, _P, _P, _P, _U32, _U32, _U32, _I, _P, _P, _P]),
+    "oi_index_set_doc_attrs": (_I, [_P, _P, _P, _I]),
+    "oi_search_lists_filtered": (_I, [_P, _P, _P, _P, _U32, _U32, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "oi_search_lists_packed_filtered": (_I, [_P, _P, _P, _P, _U32, _U32, _P, _I, _P]),
+    "oi_search_filtered": (_I, [_P, _P, _P, _P, _U32, _U32, _U32, _P, _I, _P, _P, _P]),
+    "oi_search_sharded_filtered": (_I, [_P, _P, _P, _P, _P, _U32, _U32, _U32, _P, _I, _P, _P, _P]),
     "oi_pipeline_create": (_I, [_P, _P, _U32, _U32, _U32, _U32, _U32, C.POINTER(_P)]),
     "oi_pipeline_destroy": (None, [_P]),
     "oi_pipeline_submit": (_I, [_P, _P, _P, _P, _U32, _I, _P, _P, _P, C.POINTER(_U64)]),

@@ -818,6 +818,7 @@ extern "C" int oi_index_view(oi_index *src, oi_ctx *ctx, oi_index **out) {
     alias(v->impact_floor, src->impact_floor);
     v->n_long = src->n_long; alias(v->long_list, src->long_list); alias(v->long_bitmap, src->long_bitmap);
     alias(v->fwd_terms, src->fwd_terms); alias(v->fwd_offsets, src->fwd_offsets);
+    alias(v->doc_attrs, src->doc_attrs); // (never reallocated: the view sees later in-place updates of the source's)
     *out = v;
     return OI_OK;
 }
@@ -1081,6 +1082,39 @@ extern "C" int oi_index_set_bm25_mode(oi_index *idx, int mode) {
     return OI_OK;
 }
 
+// {group, stamp} per local row, interleaved (one 8-byte load on a kernel's hit path).  The buffer is allocated by the first
+// call and only overwritten after that (stream-ordered on the ctx): views alias it and see every later update.
+extern "C" int oi_index_set_doc_attrs(oi_index *idx, const uint32_t *group, const uint32_t *stamp, int location) {
+    if (!idx) { oi_set_error("null index"); return OI_ERR_INVALID_ARG; }
+    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "set_doc_attrs: bad location %d", location);
+    if (idx->is_view) { oi_set_error("set_doc_attrs: a view's attributes are its source's"); return OI_ERR_STATE; }
+    oi_ctx *ctx = idx->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    const uint64_t n = idx->n_docs;
+    if (n == 0) return OI_OK;
+    if (!idx->doc_attrs.p) OI_CHECK(idx->doc_attrs.ensure(sizeof(uint32_t) * 2 * (size_t)n));
+    uint32_t *d = idx->doc_attrs.as<uint32_t>();
+    hipStream_t st = ctx->stream;
+    if (location == OI_HOST) {
+        std::vector<uint32_t> h(2 * (size_t)n, 0u);
+        for (uint64_t i = 0; i < n; ++i) {
+            if (group) h[2 * i] = group[i];
+            if (stamp) h[2 * i + 1] = stamp[i];
+        }
+        OI_HIP_CHECK(hipMemcpyAsync(d, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        OI_HIP_CHECK(hipStreamSynchronize(st));
+        return OI_OK;
+    }
+    // device arrays: two strided copies into the interleaved buffer (a NULL array: zeros)
+    const uint32_t *src[2] = {group, stamp};
+    for (int c = 0; c < 2; ++c) {
+        if (src[c]) OI_HIP_CHECK(hipMemcpy2DAsync(d + c, 8, src[c], 4, 4, n, hipMemcpyDeviceToDevice, st));
+        else OI_HIP_CHECK(hipMemset2DAsync(d + c, 8, 0, 4, n, st));
+    }
+    return OI_OK;
+}
+
 extern "C" int oi_index_local_stats(oi_index *idx, uint64_t *total_tokens_out, uint32_t *df_out_host) {
     if (!idx) { oi_set_error("null index"); return OI_ERR_INVALID_ARG; }
     if (idx->is_view) { oi_set_error("index view: read-only (set the data on the index it was taken from)"); return OI_ERR_STATE; }
@@ -1116,17 +1150,21 @@ namespace {
 struct QueryStage {
     const float *qv;
     const uint32_t *qt, *qo;
+    const uint4 *filt = nullptr; // a filtered search: the queries' oi_doc_filter (16 B each), device
 };
 
+// filters != null (a filtered search): staged with the queries -- in the same DMA for OI_HOST, as given for OI_DEVICE
 int stage_queries(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B, int location,
-                  QueryStage *out) {
+                  QueryStage *out, const oi_doc_filter *filters = nullptr) {
+    static_assert(sizeof(oi_doc_filter) == sizeof(uint4), "oi_doc_filter is 16 bytes");
     oi_ctx *ctx = idx->ctx;
-    if (location == OI_DEVICE) { *out = QueryStage{qv, qt, qo}; return OI_OK; }
+    if (location == OI_DEVICE) { *out = QueryStage{qv, qt, qo, reinterpret_cast<const uint4 *>(filters)}; return OI_OK; }
     hipStream_t st = ctx->stream;
-    // one page-locked staging buffer, one DMA: [vectors | terms | offsets], each part 16-byte aligned
+    // one page-locked staging buffer, one DMA: [vectors | terms | offsets (| filters)], each part 16-byte aligned
     const uint32_t nt = qo[B];
     const size_t vb = sizeof(float) * (size_t)B * idx->dim, tb = sizeof(uint32_t) * (size_t)(nt ? nt : 1), ob = sizeof(uint32_t) * ((size_t)B + 1);
-    const size_t off_t = (vb + 15) & ~(size_t)15, off_o = off_t + ((tb + 15) & ~(size_t)15), total = off_o + ob;
+    const size_t off_t = (vb + 15) & ~(size_t)15, off_o = off_t + ((tb + 15) & ~(size_t)15);
+    const size_t off_f = off_o + ((ob + 15) & ~(size_t)15), total = filters ? off_f + sizeof(oi_doc_filter) * (size_t)B : off_o + ob;
     DevBuf &a = ctx->buf("q_stage");
     OI_CHECK(a.ensure(total));
     OI_CHECK(ctx->pin_in.ensure(total));
@@ -1134,12 +1172,21 @@ int stage_queries(oi_index *idx, const float *qv, const uint32_t *qt, const uint
     memcpy(h, qv, vb);
     if (nt) memcpy(h + off_t, qt, sizeof(uint32_t) * nt);
     memcpy(h + off_o, qo, ob);
+    if (filters) memcpy(h + off_f, filters, sizeof(oi_doc_filter) * (size_t)B);
     OI_HIP_CHECK(hipMemcpyAsync(a.p, h, total, hipMemcpyHostToDevice, st));
     uint8_t *d = a.as<uint8_t>();
     *out = QueryStage{reinterpret_cast<const float *>(d), reinterpret_cast<const uint32_t *>(d + off_t),
-                      reinterpret_cast<const uint32_t *>(d + off_o)};
+                      reinterpret_cast<const uint32_t *>(d + off_o), filters ? reinterpret_cast<const uint4 *>(d + off_f) : nullptr};
     return OI_OK;
 }
+// A filtered search needs the index's doc attributes
+int check_filter_state(oi_index *idx, const oi_doc_filter *filters) {
+    if (filters && !idx->doc_attrs.p) { oi_set_error("filtered search: the index has no doc attributes (oi_index_set_doc_attrs)"); return OI_ERR_STATE; }
+    return OI_OK;
+}
+const uint2 *attrs_of(oi_index *idx, const QueryStage &q) { return q.filt ? idx->doc_attrs.as<uint2>() : nullptr; }
+// (graph keys: a filtered call differs from the unfiltered one by the filters pointer, folded into the call-kind word)
+uint64_t call_kind(uint64_t kind, const oi_doc_filter *filters) { return kind | ((uint64_t)(uintptr_t)filters << 8); }
 
 // The fused result block [scores K | docs K | counts B] (contiguous in HBM) to the caller's three host arrays: one DMA into
 // the context's page-locked buffer, the stream synchronised, three host copies.
@@ -1167,18 +1214,19 @@ int check_search_args(oi_index *idx, const float *qv, const uint32_t *qt, const 
 
 } // namespace
 
-extern "C" int oi_search_lists(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B,
-                               uint32_t depth, int location, float *cos_s, uint32_t *cos_d, uint32_t *cos_c,
-                               float *bm_s, uint32_t *bm_d, uint32_t *bm_c) {
+static int search_lists_impl(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B,
+                             uint32_t depth, int location, float *cos_s, uint32_t *cos_d, uint32_t *cos_c,
+                             float *bm_s, uint32_t *bm_d, uint32_t *bm_c, const oi_doc_filter *filters) {
     OI_CHECK(check_search_args(idx, qv, qt, qo, B, depth));
     OI_REQUIRE(cos_s && cos_d && cos_c && bm_s && bm_d && bm_c, "search_lists: null output buffer");
     oi_ctx *ctx = idx->ctx;
     std::lock_guard<std::mutex> g(ctx->mu);
+    OI_CHECK(check_filter_state(idx, filters));
     OI_HIP_CHECK(hipSetDevice(ctx->device));
     QueryStage q;
-    OI_CHECK(stage_queries(idx, qv, qt, qo, B, location, &q));
+    OI_CHECK(stage_queries(idx, qv, qt, qo, B, location, &q, filters));
     if (location == OI_DEVICE)
-        return search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, cos_s, cos_d, cos_c, bm_s, bm_d, bm_c);
+        return search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, cos_s, cos_d, cos_c, bm_s, bm_d, bm_c, q.filt, attrs_of(idx, q));
     hipStream_t st = ctx->stream;
     const size_t L = (size_t)B * depth;
     DevBuf &o = ctx->buf("lists_out");
@@ -1189,7 +1237,7 @@ extern "C" int oi_search_lists(oi_index *idx, const float *qv, const uint32_t *q
     uint32_t *d_bd = reinterpret_cast<uint32_t *>(d_bs + L);
     uint32_t *d_cc = d_bd + L, *d_bc = d_cc + B;
     OI_HIP_CHECK(hipMemsetAsync(o.p, 0, L * 16 + (size_t)B * 8, st));
-    OI_CHECK(search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, d_cs, d_cd, d_cc, d_bs, d_bd, d_bc));
+    OI_CHECK(search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, d_cs, d_cd, d_cc, d_bs, d_bd, d_bc, q.filt, attrs_of(idx, q)));
     OI_HIP_CHECK(hipMemcpyAsync(cos_s, d_cs, L * 4, hipMemcpyDeviceToHost, st));
     OI_HIP_CHECK(hipMemcpyAsync(cos_d, d_cd, L * 4, hipMemcpyDeviceToHost, st));
     OI_HIP_CHECK(hipMemcpyAsync(bm_s, d_bs, L * 4, hipMemcpyDeviceToHost, st));
@@ -1198,6 +1246,16 @@ extern "C" int oi_search_lists(oi_index *idx, const float *qv, const uint32_t *q
     OI_HIP_CHECK(hipMemcpyAsync(bm_c, d_bc, (size_t)B * 4, hipMemcpyDeviceToHost, st));
     OI_HIP_CHECK(hipStreamSynchronize(st));
     return check_overflow_locked(ctx);
+}
+extern "C" int oi_search_lists(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B,
+                               uint32_t depth, int location, float *cos_s, uint32_t *cos_d, uint32_t *cos_c,
+                               float *bm_s, uint32_t *bm_d, uint32_t *bm_c) {
+    return search_lists_impl(idx, qv, qt, qo, B, depth, location, cos_s, cos_d, cos_c, bm_s, bm_d, bm_c, nullptr);
+}
+extern "C" int oi_search_lists_filtered(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B,
+                                        uint32_t depth, const oi_doc_filter *filters, int location, float *cos_s, uint32_t *cos_d,
+                                        uint32_t *cos_c, float *bm_s, uint32_t *bm_d, uint32_t *bm_c) {
+    return search_lists_impl(idx, qv, qt, qo, B, depth, location, cos_s, cos_d, cos_c, bm_s, bm_d, bm_c, filters);
 }
 
 extern "C" int oi_rrf_fuse(oi_ctx *ctx, const uint32_t *docs_a, const uint32_t *counts_a, const uint32_t *docs_b,
@@ -1277,18 +1335,20 @@ extern "C" int oi_merge_lists(oi_ctx *ctx, const float *scores, const uint32_t *
     return OI_OK;
 }
 
-extern "C" int oi_search(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B,
-                         uint32_t depth, uint32_t k, int location, float *scores_out, uint32_t *docs_out,
-                         uint32_t *counts_out) {
+static int search_impl(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B,
+                       uint32_t depth, uint32_t k, int location, float *scores_out, uint32_t *docs_out,
+                       uint32_t *counts_out, const oi_doc_filter *filters) {
     OI_CHECK(check_search_args(idx, qv, qt, qo, B, depth));
     OI_REQUIRE(k >= 1 && k <= OI_MAX_DEPTH, "search: k=%u outside [1,%u]", k, OI_MAX_DEPTH);
     OI_REQUIRE(scores_out && docs_out && counts_out, "search: null output buffer");
     oi_ctx *ctx = idx->ctx;
     std::lock_guard<std::mutex> g(ctx->mu);
+    OI_CHECK(check_filter_state(idx, filters));
     OI_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     QueryStage q;
-    OI_CHECK(stage_queries(idx, qv, qt, qo, B, location, &q));
+    OI_CHECK(stage_queries(idx, qv, qt, qo, B, location, &q, filters));
+    const uint2 *attrs = attrs_of(idx, q);
     const size_t L = (size_t)B * depth, K = (size_t)B * k;
     DevBuf &o = ctx->buf("search_lists");
     OI_CHECK(o.ensure(L * 16 + (size_t)B * 8 + 64));
@@ -1298,18 +1358,18 @@ extern "C" int oi_search(oi_index *idx, const float *qv, const uint32_t *qt, con
     uint32_t *d_bd = reinterpret_cast<uint32_t *>(d_bs + L);
     uint32_t *d_cc = d_bd + L, *d_bc = d_cc + B;
     if (location == OI_DEVICE) {
-        const uint64_t key[10] = {idx->uid, 3, (uint64_t)(uintptr_t)qv, (uint64_t)(uintptr_t)qt, (uint64_t)(uintptr_t)qo,
+        const uint64_t key[10] = {idx->uid, call_kind(3, filters), (uint64_t)(uintptr_t)qv, (uint64_t)(uintptr_t)qt, (uint64_t)(uintptr_t)qo,
                                   ((uint64_t)B << 32) | depth, (uint64_t)(uintptr_t)scores_out,
                                   ((uint64_t)ctx->cosine_mode << 16) | ((uint64_t)idx->bm25_mode << 8) | (ctx->overlap_legs ? 1u : 0u),
                                   ((uint64_t)idx->max_query_terms << 32) | k, (uint64_t)(uintptr_t)docs_out ^ ((uint64_t)(uintptr_t)counts_out << 1)};
         return run_captured(ctx, key, [&]() -> int {
             OI_HIP_CHECK(hipMemsetAsync(d_cc, 0, (size_t)B * 8, ctx->stream));
-            OI_CHECK(search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, d_cs, d_cd, d_cc, d_bs, d_bd, d_bc));
+            OI_CHECK(search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, d_cs, d_cd, d_cc, d_bs, d_bd, d_bc, q.filt, attrs));
             return oi_launch_rrf(ctx, d_cd, d_cc, d_bd, d_bc, B, depth, k, scores_out, docs_out, counts_out);
         });
     }
     OI_HIP_CHECK(hipMemsetAsync(d_cc, 0, (size_t)B * 8, st));
-    OI_CHECK(search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, d_cs, d_cd, d_cc, d_bs, d_bd, d_bc));
+    OI_CHECK(search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, d_cs, d_cd, d_cc, d_bs, d_bd, d_bc, q.filt, attrs));
     DevBuf &f = ctx->buf("search_out");
     OI_CHECK(f.ensure((2 * K + B) * 4 + 64));
     float *d_so = f.as<float>();
@@ -1318,6 +1378,16 @@ extern "C" int oi_search(oi_index *idx, const float *qv, const uint32_t *qt, con
     OI_CHECK(oi_launch_rrf(ctx, d_cd, d_cc, d_bd, d_bc, B, depth, k, d_so, d_do, d_co));
     OI_CHECK(results_to_host(ctx, d_so, K, B, scores_out, docs_out, counts_out));
     return check_overflow_locked(ctx);
+}
+extern "C" int oi_search(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B,
+                         uint32_t depth, uint32_t k, int location, float *scores_out, uint32_t *docs_out,
+                         uint32_t *counts_out) {
+    return search_impl(idx, qv, qt, qo, B, depth, k, location, scores_out, docs_out, counts_out, nullptr);
+}
+extern "C" int oi_search_filtered(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B,
+                                  uint32_t depth, uint32_t k, const oi_doc_filter *filters, int location, float *scores_out,
+                                  uint32_t *docs_out, uint32_t *counts_out) {
+    return search_impl(idx, qv, qt, qo, B, depth, k, location, scores_out, docs_out, counts_out, filters);
 }
 
 // ---------------------------------------------------------------- diagnostics of the bf16 screen
@@ -1356,16 +1426,17 @@ extern "C" int oi_screen_probe(oi_index *idx, const float *query_vecs, uint32_t 
 }
 
 // ---------------------------------------------------------------- packed multi-GPU exchange
-extern "C" int oi_search_lists_packed(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo,
-                                      uint32_t B, uint32_t depth, int location, uint32_t *packed_out) {
+static int search_lists_packed_impl(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo,
+                                    uint32_t B, uint32_t depth, int location, uint32_t *packed_out, const oi_doc_filter *filters) {
     OI_CHECK(check_search_args(idx, qv, qt, qo, B, depth));
     OI_REQUIRE(packed_out, "search_lists_packed: null output buffer");
     oi_ctx *ctx = idx->ctx;
     std::lock_guard<std::mutex> g(ctx->mu);
+    OI_CHECK(check_filter_state(idx, filters));
     OI_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     QueryStage q;
-    OI_CHECK(stage_queries(idx, qv, qt, qo, B, location, &q));
+    OI_CHECK(stage_queries(idx, qv, qt, qo, B, location, &q, filters));
     const size_t L = (size_t)B * depth, W = (size_t)OI_PACKED_WORDS(B, depth);
     uint32_t *d_out = packed_out;
     if (location != OI_DEVICE) {
@@ -1377,10 +1448,10 @@ extern "C" int oi_search_lists_packed(oi_index *idx, const float *qv, const uint
     uint32_t *dc = d_out + 2 * L, *cn = d_out + 4 * L;
     auto body = [&]() -> int {
         OI_HIP_CHECK(hipMemsetAsync(d_out + 4 * L, 0, (size_t)B * 8, ctx->stream)); // counts
-        return search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, sc, dc, cn, sc + L, dc + L, cn + B);
+        return search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, sc, dc, cn, sc + L, dc + L, cn + B, q.filt, attrs_of(idx, q));
     };
     if (location == OI_DEVICE) {
-        const uint64_t key[10] = {idx->uid, 1, (uint64_t)(uintptr_t)qv, (uint64_t)(uintptr_t)qt, (uint64_t)(uintptr_t)qo,
+        const uint64_t key[10] = {idx->uid, call_kind(1, filters), (uint64_t)(uintptr_t)qv, (uint64_t)(uintptr_t)qt, (uint64_t)(uintptr_t)qo,
                                   ((uint64_t)B << 32) | depth, (uint64_t)(uintptr_t)packed_out,
                                   ((uint64_t)ctx->cosine_mode << 16) | ((uint64_t)idx->bm25_mode << 8) | (ctx->overlap_legs ? 1u : 0u),
                                   idx->max_query_terms, 0};
@@ -1390,6 +1461,15 @@ extern "C" int oi_search_lists_packed(oi_index *idx, const float *qv, const uint
     OI_HIP_CHECK(hipMemcpyAsync(packed_out, d_out, W * 4, hipMemcpyDeviceToHost, st));
     OI_HIP_CHECK(hipStreamSynchronize(st));
     return check_overflow_locked(ctx);
+}
+extern "C" int oi_search_lists_packed(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo,
+                                      uint32_t B, uint32_t depth, int location, uint32_t *packed_out) {
+    return search_lists_packed_impl(idx, qv, qt, qo, B, depth, location, packed_out, nullptr);
+}
+extern "C" int oi_search_lists_packed_filtered(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo,
+                                               uint32_t B, uint32_t depth, const oi_doc_filter *filters, int location,
+                                               uint32_t *packed_out) {
+    return search_lists_packed_impl(idx, qv, qt, qo, B, depth, location, packed_out, filters);
 }
 
 // All shards' packed lists (device) -> global top-depth per list -> RRF top-k into device outputs.  ctx->mu held.
@@ -1520,9 +1600,9 @@ extern "C" int oi_index_finalize_sharded(oi_index *idx, oi_comm *comm) {
     return apply_screen_copy_policy(idx);
 }
 
-extern "C" int oi_search_sharded(oi_index *idx, oi_comm *comm, const float *qv, const uint32_t *qt, const uint32_t *qo,
-                                 uint32_t B, uint32_t depth, uint32_t k, int location, float *scores_out,
-                                 uint32_t *docs_out, uint32_t *counts_out) {
+static int search_sharded_impl(oi_index *idx, oi_comm *comm, const float *qv, const uint32_t *qt, const uint32_t *qo,
+                               uint32_t B, uint32_t depth, uint32_t k, int location, float *scores_out,
+                               uint32_t *docs_out, uint32_t *counts_out, const oi_doc_filter *filters) {
     OI_CHECK(check_search_args(idx, qv, qt, qo, B, depth));
     if (!comm) { oi_set_error("null communicator"); return OI_ERR_INVALID_ARG; }
     OI_REQUIRE(k >= 1 && k <= OI_MAX_DEPTH, "search: k=%u outside [1,%u]", k, OI_MAX_DEPTH);
@@ -1530,10 +1610,11 @@ extern "C" int oi_search_sharded(oi_index *idx, oi_comm *comm, const float *qv, 
     oi_ctx *ctx = idx->ctx;
     OI_REQUIRE(comm->ctx == ctx, "search_sharded: the communicator belongs to another context");
     std::lock_guard<std::mutex> g(ctx->mu);
+    OI_CHECK(check_filter_state(idx, filters));
     OI_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     QueryStage q;
-    OI_CHECK(stage_queries(idx, qv, qt, qo, B, location, &q));
+    OI_CHECK(stage_queries(idx, qv, qt, qo, B, location, &q, filters));
     const size_t L = (size_t)B * depth, W = (size_t)OI_PACKED_WORDS(B, depth), K = (size_t)B * k;
     DevBuf &pk = ctx->buf("sharded_packed"), &fl = ctx->buf("sharded_flat");
     OI_CHECK(pk.ensure(W * 4));
@@ -1542,7 +1623,7 @@ extern "C" int oi_search_sharded(oi_index *idx, oi_comm *comm, const float *qv, 
     OI_HIP_CHECK(hipMemsetAsync(d_p + 4 * L, 0, (size_t)B * 8, st)); // counts
     float *sc = reinterpret_cast<float *>(d_p);
     uint32_t *dc = d_p + 2 * L, *cn = d_p + 4 * L;
-    OI_CHECK(search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, sc, dc, cn, sc + L, dc + L, cn + B));
+    OI_CHECK(search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, sc, dc, cn, sc + L, dc + L, cn + B, q.filt, attrs_of(idx, q)));
     // the ONE exchange per batch: every rank's packed lists to every rank (1 MB per rank at B=64, k'=1000)
     OI_CHECK(oi_rccl_all_gather_u32(comm->nccl, d_p, fl.as<uint32_t>(), W, st));
     if (location == OI_DEVICE)
@@ -1555,4 +1636,14 @@ extern "C" int oi_search_sharded(oi_index *idx, oi_comm *comm, const float *qv, 
     OI_CHECK(fuse_packed_device(ctx, fl.as<uint32_t>(), comm->world, B, depth, k, o_s, o_d, o_c));
     OI_CHECK(results_to_host(ctx, o_s, K, B, scores_out, docs_out, counts_out));
     return check_overflow_locked(ctx);
+}
+extern "C" int oi_search_sharded(oi_index *idx, oi_comm *comm, const float *qv, const uint32_t *qt, const uint32_t *qo,
+                                 uint32_t B, uint32_t depth, uint32_t k, int location, float *scores_out,
+                                 uint32_t *docs_out, uint32_t *counts_out) {
+    return search_sharded_impl(idx, comm, qv, qt, qo, B, depth, k, location, scores_out, docs_out, counts_out, nullptr);
+}
+extern "C" int oi_search_sharded_filtered(oi_index *idx, oi_comm *comm, const float *qv, const uint32_t *qt, const uint32_t *qo,
+                                          uint32_t B, uint32_t depth, uint32_t k, const oi_doc_filter *filters, int location,
+                                          float *scores_out, uint32_t *docs_out, uint32_t *counts_out) {
+    return search_sharded_impl(idx, comm, qv, qt, qo, B, depth, k, location, scores_out, docs_out, counts_out, filters);
 }

@@ -86,6 +86,8 @@ struct BsArgs {
     const uint2 *qctx;          // [nq][64] per query and lane j: {cell index of (term j, window 0) or ~0 without a run, idf bits} (plan)
     uint32_t *queue;            // the launch's hand-out counter (zeroed by the plan kernel)
     uint32_t n_chunks;          // the weight axis is cut into this many ranges: wave w starts with range w, then draws
+    const uint4 *filt;          // FILT: [nq] the queries' doc filters (offset to q_begin); attrs[local doc] = {group, stamp}
+    const uint2 *attrs;
 };
 
 __device__ __forceinline__ uint32_t bs_lds_addr(const void *p) {
@@ -166,7 +168,7 @@ struct BsTable {
 // TIMING (a diagnostic instantiation, never the product's launch): s_memtime stamps around the sections of a wave's life,
 // summed over the waves into a.timing[0..9] = wait, pass A, sweep, pass B, table + bounds, finish + end of task, issue,
 // query setup, whole wave, waves; [10] = the longest wave.
-template <int W, bool TIMING = false>
+template <int W, bool TIMING = false, bool FILT = false>
 __global__ __launch_bounds__(BS_WPB * 64) void bm25_stream_kernel(const BsArgs a) {
     using L = BsLds<W>;
     unsigned long long t_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -253,6 +255,7 @@ __global__ __launch_bounds__(BS_WPB * 64) void bm25_stream_kernel(const BsArgs a
 
     // ================================================================ the task being scored
     uint32_t t_q = 0, t_blk = 0, t_doc0 = 0, t_tau = 0, t_tau_q = 0, out_n = 0, st_n = 0, t_M = 0;
+    uint4 t_filt = make_uint4(0u, 0u, 0u, 0u); // FILT: the query's doc filter
     uint32_t q_tb = 0, q_T = 0; // the query's terms
     uint64_t *t_seg = a.pools;
     const uint32_t seg_cap = a.seg_cap;
@@ -323,6 +326,7 @@ __global__ __launch_bounds__(BS_WPB * 64) void bm25_stream_kernel(const BsArgs a
         st_n = rem;
     };
     auto emit1 = [&](bool k, uint32_t score_bits, uint32_t doc) __attribute__((always_inline)) { // all lanes call; score > 0: its key is bits | sign
+        if constexpr (FILT) k = k && oi_doc_passes(t_filt, a.attrs[doc - a.doc_id_base]); // (the doc filter: after the threshold)
         const unsigned long long m = __ballot(k);
         if (m) {
             if (k) stage[st_n + (uint32_t)__popcll(m & lt_mask)] = ((uint64_t)(score_bits | 0x80000000u) << 32) | (uint64_t)(~doc);
@@ -577,6 +581,7 @@ __global__ __launch_bounds__(BS_WPB * 64) void bm25_stream_kernel(const BsArgs a
         if (t_first_q == 0xFFFFFFFFu) t_first_q = r;
 #endif
         t_tau_q = bs_rfl(s_tau[r]);
+        if constexpr (FILT) t_filt = a.filt[r];
         q_tb = bs_rfl(a.q_offsets[a.q_begin + r]);
         q_T = bs_rfl(a.q_offsets[a.q_begin + r + 1]) - q_tb;
         const bool long_query = q_T > 64u;
@@ -834,6 +839,7 @@ int oi_launch_bm25_stream(oi_index *idx, const uint32_t *d_q_terms, const uint32
     a.block0 = block_begin; a.nbh = block_end - block_begin; a.q_begin = q_begin; a.nq = nq;
     a.seg_cnt_stride = pool.seg_cnt_stride; a.carry_cap = pool.carry_cap; a.seg_cap = pool.seg_cap; a.depth = depth;
     a.timing = nullptr;
+    a.filt = nullptr; a.attrs = nullptr;
     const uint64_t n_tasks = (uint64_t)a.nbh * nq;
     a.queue = reinterpret_cast<uint32_t *>(const_cast<uint32_t *>(a.unit) + BS_MAX_Q) + (block_begin ? 1 : 0); // one counter per phase
     a.qctx = reinterpret_cast<const uint2 *>(a.unit + BS_MAX_Q + 2);
@@ -853,6 +859,8 @@ int oi_launch_bm25_stream(oi_index *idx, const uint32_t *d_q_terms, const uint32
         return OI_OK;
     };
 #ifdef OI_ABLATION
+    // (the diagnostic launches below are unfiltered instantiations: a filtered search does not take them)
+    OI_REQUIRE(!pool.filt || !oi_ablation_env("OI_BM25_STREAM_TIMING"), "bm25 (stream): the TIMING builds take no doc filter");
     if (oi_ablation_env("OI_BM25_STREAM_TIMING") && strcmp(oi_ablation_env("OI_BM25_STREAM_TIMING"), "light") == 0) {
         DevBuf &tb = ctx->buf("bm25_stream_timing");
         const size_t tbytes = (32 + 2048 * 4 + 4096 * 4) * sizeof(unsigned long long);
@@ -944,10 +952,17 @@ int oi_launch_bm25_stream(oi_index *idx, const uint32_t *d_q_terms, const uint32
                 h[14] / wv, h[12] / wv, h[11] / wv, h[13] / wv, h[15] / wv);
         return OI_OK;
     }
-    if (half_windows) { OI_CHECK(launch(bm25_stream_kernel<BS_FINE>, BsLds<BS_FINE>::TOTAL)); OI_HIP_CHECK(hipGetLastError()); return OI_OK; }
+    if (half_windows) {
+        OI_REQUIRE(!pool.filt, "bm25 (stream): the 16384-doc window build takes no doc filter");
+        OI_CHECK(launch(bm25_stream_kernel<BS_FINE>, BsLds<BS_FINE>::TOTAL)); OI_HIP_CHECK(hipGetLastError()); return OI_OK;
+    }
 #endif
     (void)half_windows;
-    OI_CHECK(launch(bm25_stream_kernel<BS_BLOCK>, BsLds<BS_BLOCK>::TOTAL));
+    if (pool.filt) { // a filtered search: the instantiation with the doc filter
+        a.filt = pool.filt + q_begin; a.attrs = pool.attrs;
+        OI_CHECK(launch(bm25_stream_kernel<BS_BLOCK, false, true>, BsLds<BS_BLOCK>::TOTAL));
+    } else
+        OI_CHECK(launch(bm25_stream_kernel<BS_BLOCK>, BsLds<BS_BLOCK>::TOTAL));
     OI_HIP_CHECK(hipGetLastError());
     return OI_OK;
 }

@@ -17,7 +17,7 @@
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ------------------------------------------------------------------ GEMV (B <= 8)
-template <int NQ>
+template <int NQ, bool FILT>
 __global__ __launch_bounds__(256) void cosine_gemv_filter(const float *__restrict__ rows, uint64_t row_begin,
                                                            uint64_t row_end, uint32_t dim,
                                                            const float *__restrict__ queries,
@@ -25,7 +25,8 @@ __global__ __launch_bounds__(256) void cosine_gemv_filter(const float *__restric
                                                            uint32_t *seg_cnt, uint32_t cnt_stride,
                                                            const uint32_t *tau_keys, uint64_t pool_stride,
                                                            uint32_t seg_cap, uint32_t *overflow,
-                                                           const uint32_t *run_gate) {
+                                                           const uint32_t *run_gate,
+                                                           const uint4 *__restrict__ filt, const uint2 *__restrict__ attrs) {
     // run_gate != null: a launch of the gated exact pipeline behind the screen (cosine_prefilter.hip) -- exits at once unless open
     if (run_gate && *run_gate == 0u) return;
     // Survivors go to THIS workgroup's segment of the query's pool (LDS fill counter, published once at the
@@ -75,7 +76,9 @@ __global__ __launch_bounds__(256) void cosine_gemv_filter(const float *__restric
             a = oi_wave_sum(a);
             if ((int)lane == q) mine = a;
         }
-        if (lane < NQ && mine == mine && oi_f32_key(mine) >= tau) {
+        bool hit = lane < NQ && mine == mine && oi_f32_key(mine) >= tau;
+        if constexpr (FILT) hit = hit && oi_doc_passes(filt[lane], attrs[r]); // (the doc filter: hits only)
+        if (hit) {
             const uint32_t pos = atomicAdd(&fill[lane], 1u); // LDS
             if (pos < seg_cap)
                 pools[(uint64_t)lane * pool_stride + (uint64_t)blockIdx.x * seg_cap + pos] = oi_rank_key(mine, doc_id_base + (uint32_t)r);
@@ -137,7 +140,7 @@ void oi_cosine_gemv_geometry(const oi_ctx *ctx, uint64_t n_rows, uint32_t *n_seg
 #define CM_BK 32
 #define CM_LD (CM_BK + 1) // +1 float: conflict-free ds_read_b32 down a column
 
-template <int NQT>
+template <int NQT, bool FILT>
 __global__ __launch_bounds__(256) void cosine_mfma_filter(const float *__restrict__ rows, uint64_t row_begin,
                                                            uint64_t row_end, uint32_t dim,
                                                            const float *__restrict__ queries, // [32*NQT][dim], zero padded
@@ -145,7 +148,8 @@ __global__ __launch_bounds__(256) void cosine_mfma_filter(const float *__restric
                                                            uint64_t *pools, uint32_t *pool_counts,
                                                            uint32_t cnt_stride, const uint32_t *tau_keys,
                                                            uint64_t pool_stride, uint32_t pool_cap,
-                                                           uint32_t *overflow) {
+                                                           uint32_t *overflow,
+                                                           const uint4 *__restrict__ filt, const uint2 *__restrict__ attrs) {
     __shared__ float sA[CM_ROWS * CM_LD];
     __shared__ float sQ[32 * NQT * CM_LD];
     const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -210,7 +214,7 @@ __global__ __launch_bounds__(256) void cosine_mfma_filter(const float *__restric
             for (int r = 0; r < 16; ++r) {
                 const uint64_t row = r0 + 32u * w + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 const float s = acc[t][r];
-                if (row < row_end && s == s && oi_f32_key(s) >= tau[t])
+                if (row < row_end && s == s && oi_f32_key(s) >= tau[t] && (!FILT || oi_doc_passes(filt[q], attrs[row])))
                     oi_pool_append(pools + (uint64_t)q * pool_stride, pool_counts + (uint64_t)q * cnt_stride, pool_cap,
                                    overflow, oi_rank_key(s, doc_id_base + (uint32_t)row));
             }
@@ -252,9 +256,16 @@ int oi_launch_cosine_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, u
     if (n_queries <= 8) {
         dim3 g((uint32_t)gemv_blocks(ctx, n_rows)), b(256);
 #define OI_GEMV(NQ)                                                                                     \
-    hipLaunchKernelGGL(cosine_gemv_filter<NQ>, g, b, 0, ctx->stream, rows, row_begin, row_end, dim,     \
-                       d_queries, doc_id_base, pool.keys + pool.carry_cap, pool.seg_cnt,                 \
-                       pool.seg_cnt_stride, pool.tau_keys, pool.stride, pool.seg_cap, pool.overflow, ctx->run_gate)
+    if (pool.filt)                                                                                      \
+        hipLaunchKernelGGL((cosine_gemv_filter<NQ, true>), g, b, 0, ctx->stream, rows, row_begin, row_end, dim, \
+                           d_queries, doc_id_base, pool.keys + pool.carry_cap, pool.seg_cnt,             \
+                           pool.seg_cnt_stride, pool.tau_keys, pool.stride, pool.seg_cap, pool.overflow, \
+                           ctx->run_gate, pool.filt, pool.attrs);                                        \
+    else                                                                                                \
+        hipLaunchKernelGGL((cosine_gemv_filter<NQ, false>), g, b, 0, ctx->stream, rows, row_begin, row_end, dim, \
+                           d_queries, doc_id_base, pool.keys + pool.carry_cap, pool.seg_cnt,             \
+                           pool.seg_cnt_stride, pool.tau_keys, pool.stride, pool.seg_cap, pool.overflow, \
+                           ctx->run_gate, nullptr, nullptr)
         // queries beyond n_queries are not readable: dispatch on the exact count
         switch (n_queries) {
             case 1: OI_GEMV(1); break;
@@ -283,20 +294,20 @@ int oi_launch_cosine_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, u
         p.carry_cnt += q0;
         p.seg_cnt += (uint64_t)q0 * pool.seg_cnt_stride;
         p.tau_keys += q0;
+        if (p.filt) p.filt += q0;
         const float *qptr = d_queries + (uint64_t)q0 * dim;
-        if (ksplit && ctx->cosine_mode == OI_COSINE_SPLIT && oi_cosine_split_supported(dim)) {
+        if (ksplit && ctx->cosine_mode == OI_COSINE_SPLIT && oi_cosine_split_supported(dim) && !p.filt) { // (filtered: the K-split)
             OI_CHECK(oi_launch_cosine_split(ctx, rows, row_begin, row_end, dim, qptr, nq_here, doc_id_base, p));
         } else if (ksplit) {
             OI_CHECK(oi_launch_cosine_ksplit(ctx, rows, row_begin, row_end, dim, qptr, nq_here, left >= 64,
                                              doc_id_base, p));
-        } else if (left >= 64)
-            hipLaunchKernelGGL(cosine_mfma_filter<2>, dim3((uint32_t)blocks), dim3(256), 0, ctx->stream, rows,
+        } else {
+            auto kernel = left >= 64 ? (p.filt ? cosine_mfma_filter<2, true> : cosine_mfma_filter<2, false>)
+                                     : (p.filt ? cosine_mfma_filter<1, true> : cosine_mfma_filter<1, false>);
+            hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(256), 0, ctx->stream, rows,
                                row_begin, row_end, dim, qptr, nq_here, doc_id_base, p.keys + p.carry_cap, p.seg_cnt,
-                               p.seg_cnt_stride, p.tau_keys, p.stride, p.seg_cap, p.overflow);
-        else
-            hipLaunchKernelGGL(cosine_mfma_filter<1>, dim3((uint32_t)blocks), dim3(256), 0, ctx->stream, rows,
-                               row_begin, row_end, dim, qptr, nq_here, doc_id_base, p.keys + p.carry_cap, p.seg_cnt,
-                               p.seg_cnt_stride, p.tau_keys, p.stride, p.seg_cap, p.overflow);
+                               p.seg_cnt_stride, p.tau_keys, p.stride, p.seg_cap, p.overflow, p.filt, p.attrs);
+        }
         OI_HIP_CHECK(hipGetLastError());
         if (q0 + 64 >= n_queries) break;
     }

@@ -117,12 +117,13 @@ __device__ __forceinline__ void cb_wait() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int D, int NQT>
+template <int D, int NQT, bool FILT>
 __global__ __launch_bounds__(256, 1) void cosine_bf16_filter(
     const uint16_t *__restrict__ rows, uint64_t row_begin, uint64_t row_end,
     const uint16_t *__restrict__ queries, // bf16 [32*NQT][D], zero padded
     uint32_t n_queries, uint32_t doc_id_base, uint64_t *pools, uint32_t *seg_cnt, uint32_t seg_cnt_stride,
-    const uint32_t *tau_keys, uint64_t pool_stride, uint32_t carry_cap, uint32_t seg_cap, uint32_t *overflow) {
+    const uint32_t *tau_keys, uint64_t pool_stride, uint32_t carry_cap, uint32_t seg_cap, uint32_t *overflow,
+    const uint4 *__restrict__ filt, const uint2 *__restrict__ attrs) { // FILT: the doc filter after the threshold
     constexpr int NKC = D / CB_SLOT_K;                    // ring slots per tile
     constexpr int NBUF = NKC % 8 == 0 ? 8 : (NKC % 6 == 0 ? 6 : NKC);
     constexpr int P = NBUF - 1;                           // slots in flight ahead of the one being consumed
@@ -240,7 +241,7 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_filter(
                 for (int r = 0; r < 16; ++r) {
                     const uint64_t row = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                     const float s = acc[t][r];
-                    if (row < row_end && s == s && oi_f32_key(s) >= tau[t]) {
+                    if (row < row_end && s == s && oi_f32_key(s) >= tau[t] && (!FILT || oi_doc_passes(filt[q], attrs[row]))) {
                         const uint32_t pos = atomicAdd(&seg_fill[q], 1u); // LDS
                         if (pos < seg_cap) my_seg[(uint64_t)q * pool_stride + pos] = oi_rank_key(s, doc_id_base + (uint32_t)row);
                         else *overflow = 1u;
@@ -1007,10 +1008,11 @@ static int launch_bf16(oi_ctx *ctx, const uint16_t *rows, uint64_t row_begin, ui
                        uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
     constexpr int NKC = D / CB_SLOT_K, NBUF = NKC % 8 == 0 ? 8 : (NKC % 6 == 0 ? 6 : NKC);
     constexpr size_t smem = 4 * NBUF * CB_SLOT_BYTES + 64 * 4;
-    OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(cosine_bf16_filter<D, NQT>), (size_t)(smem)));
-    hipLaunchKernelGGL((cosine_bf16_filter<D, NQT>), dim3(p.n_segs), dim3(256), smem, ctx->stream, rows, row_begin,
+    auto kernel = p.filt ? cosine_bf16_filter<D, NQT, true> : cosine_bf16_filter<D, NQT, false>;
+    OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(kernel), (size_t)(smem)));
+    hipLaunchKernelGGL(kernel, dim3(p.n_segs), dim3(256), smem, ctx->stream, rows, row_begin,
                        row_end, q, nq, doc_id_base, p.keys, p.seg_cnt, p.seg_cnt_stride, p.tau_keys, p.stride,
-                       p.carry_cap, p.seg_cap, p.overflow);
+                       p.carry_cap, p.seg_cap, p.overflow, p.filt, p.attrs);
     OI_HIP_CHECK(hipGetLastError());
     return OI_OK;
 }
@@ -1082,8 +1084,11 @@ int oi_launch_cosine_bf16_chunk(oi_ctx *ctx, const uint16_t *rows, uint64_t row_
     OI_REQUIRE(oi_cosine_bf16_supported(dim), "cosine (bf16 corpus): dim %u not instantiated (384, 768, 1024)", dim);
     // siblings: every group of this batch is a full pair of 128-query passes (256, 512, ... queries at d = 1024) and the chunk
     // is long enough to give every pair of workgroups a tile
+    // A filtered search is pinned to the one-pass-per-group kernel (cosine_bf16_filter), the only one with the
+    // doc filter: groups of 32 queries at d = 1024, 64 otherwise, never the pair / quad / query-split kernels or siblings
+    const bool filtered = pool.filt != nullptr;
     const uint32_t sib_mode = cb_sibling_mode();
-    const bool siblings = sib_mode != 0 && dim == 1024 && n_queries >= 256 && n_queries % 256 == 0 &&
+    const bool siblings = !filtered && sib_mode != 0 && dim == 1024 && n_queries >= 256 && n_queries % 256 == 0 &&
                           row_end > row_begin && (row_end - row_begin) >= (uint64_t)CB_TILE_ROWS * ctx->num_cus;
     oi_cosine_bf16_geometry(ctx, row_end > row_begin ? row_end - row_begin : 0, &pool.n_segs, &pool.seg_cap, siblings);
     OI_REQUIRE(pool.n_segs <= pool.seg_cnt_stride && pool.carry_cap + (uint64_t)pool.n_segs * pool.seg_cap <= pool.stride,
@@ -1104,7 +1109,7 @@ int oi_launch_cosine_bf16_chunk(oi_ctx *ctx, const uint16_t *rows, uint64_t row_
     ProfScope ps(ctx, "cosine");
     for (uint32_t q0 = 0; q0 < n_queries;) {
         const uint32_t left = n_queries - q0;
-        uint32_t group = solo_only ? (dim == 1024 ? 32u : 64u) : cb_group(dim, left);
+        uint32_t group = solo_only || filtered ? (dim == 1024 ? 32u : 64u) : cb_group(dim, left);
         if (no_quad && group > 96u) group = 96u;
         if (siblings) group = 256u;
         const uint32_t nq_here = std::min(group, left);
@@ -1114,6 +1119,7 @@ int oi_launch_cosine_bf16_chunk(oi_ctx *ctx, const uint16_t *rows, uint64_t row_
         p.carry_cnt += q0;
         p.seg_cnt += (uint64_t)q0 * pool.seg_cnt_stride;
         p.tau_keys += q0;
+        if (p.filt) p.filt += q0;
         const uint16_t *qptr = qb.as<uint16_t>() + (uint64_t)q0 * dim;
 #define CB_SOLO(DD, T) OI_CHECK((launch_bf16<DD, T>(ctx, rows, row_begin, row_end, qptr, nq_here, doc_id_base, p)))
 #define CB_PAIR(DD, T) OI_CHECK((launch_bf16_pair<DD, T>(ctx, rows, row_begin, row_end, qptr, nq_here, doc_id_base, p)))

@@ -320,13 +320,14 @@ __global__ __launch_bounds__(256, 1) void cosine_ksplit_filter(
 // D[(l>>4)*4 + r][l&15] is accumulator register r.  A wave's 32x64 tile = 2 row tiles x 4 query tiles.
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
-template <int D, int NQT>
+template <int D, int NQT, bool FILT>
 __global__ __launch_bounds__(256, 1) void cosine_ksplit16_filter(
     const float *__restrict__ rows, uint64_t row_begin, uint64_t row_end,
     const float *__restrict__ queries, // [32*NQT][D], zero padded
     uint32_t n_queries, uint32_t doc_id_base, uint64_t *pools, uint32_t *seg_cnt, uint32_t seg_cnt_stride,
     const uint32_t *tau_keys, uint64_t pool_stride, uint32_t carry_cap, uint32_t seg_cap, uint32_t *overflow,
-    const uint32_t *run_gate) { // run_gate != null: part of the gated exact pipeline (cosine_prefilter.hip)
+    const uint32_t *run_gate, // run_gate != null: part of the gated exact pipeline (cosine_prefilter.hip)
+    const uint4 *__restrict__ filt, const uint2 *__restrict__ attrs) { // FILT: the doc filter after the threshold
     if (run_gate && *run_gate == 0u) return;
     constexpr int KS = D / 4, NKC = KS / KS_CHUNK_K, NBUF = NKC <= 6 ? NKC : NKC / 2, P = NBUF - 1;
     constexpr int NQ16 = 2 * NQT;        // query tiles of 16
@@ -412,7 +413,7 @@ __global__ __launch_bounds__(256, 1) void cosine_ksplit16_filter(
         const uint32_t t = (uint32_t)i % NQ16, rt = (uint32_t)i / NQ16;
         const uint32_t q = 16u * t + li;
         const uint64_t row = prev_row0 + 16u * rt + 4u * kk + w;
-        if (have_prev && row < row_end && s == s && oi_f32_key(s) >= tau[t]) {
+        if (have_prev && row < row_end && s == s && oi_f32_key(s) >= tau[t] && (!FILT || oi_doc_passes(filt[q], attrs[row]))) {
             const uint32_t pos = atomicAdd(&seg_fill[q], 1u); // LDS
             if (pos < seg_cap) my_seg[(uint64_t)q * pool_stride + pos] = oi_rank_key(s, doc_id_base + (uint32_t)row);
             else *overflow = 1u;
@@ -500,10 +501,11 @@ static int launch_ksplit16(oi_ctx *ctx, const float *rows, uint64_t row_begin, u
                            uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
     constexpr int KS = D / 4, NKC = KS / KS_CHUNK_K, NBUF = NKC <= 6 ? NKC : NKC / 2;
     constexpr size_t smem = 4 * NBUF * KS_SLOT_BYTES + 4 * (NQT * 16 * 64) * 4 + 64 * 4;
-    OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(cosine_ksplit16_filter<D, NQT>), (size_t)(smem)));
-    hipLaunchKernelGGL((cosine_ksplit16_filter<D, NQT>), dim3(p.n_segs), dim3(256), smem, ctx->stream, rows,
+    auto kernel = p.filt ? cosine_ksplit16_filter<D, NQT, true> : cosine_ksplit16_filter<D, NQT, false>;
+    OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(kernel), (size_t)(smem)));
+    hipLaunchKernelGGL(kernel, dim3(p.n_segs), dim3(256), smem, ctx->stream, rows,
                        row_begin, row_end, q, nq, doc_id_base, p.keys, p.seg_cnt, p.seg_cnt_stride, p.tau_keys,
-                       p.stride, p.carry_cap, p.seg_cap, p.overflow, ctx->run_gate);
+                       p.stride, p.carry_cap, p.seg_cap, p.overflow, ctx->run_gate, p.filt, p.attrs);
     OI_HIP_CHECK(hipGetLastError());
     return OI_OK;
 }
@@ -562,6 +564,7 @@ int oi_launch_cosine_ksplit(oi_ctx *ctx, const float *rows, uint64_t row_begin, 
     // session, 10M x 768, B=64: 9.07 vs 9.35 ms); OI_KS_SHAPE=32 selects the other build.
     static const bool shape16 = !(oi_ablation_env("OI_KS_SHAPE") && atoi(oi_ablation_env("OI_KS_SHAPE")) == 32);
     OI_REQUIRE(shape16 || !ctx->run_gate, "cosine_ksplit: only the 16x16x4 build takes a run gate");
+    OI_REQUIRE(shape16 || !p.filt, "cosine_ksplit: only the 16x16x4 build takes a doc filter");
 #define OI_KS(DD)                                                                                       \
     case DD:                                                                                            \
         if (shape16)                                                                                    \

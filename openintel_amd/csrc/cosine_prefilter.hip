@@ -555,7 +555,8 @@ __global__ __launch_bounds__(256) void pf_rescore_kernel(const float *__restrict
                                                          uint32_t *out_cnt, uint64_t out_stride,
                                                          const uint32_t *__restrict__ extra_docs, uint32_t n_extra,
                                                          const uint32_t *__restrict__ spec_max, const uint32_t *__restrict__ tau_final,
-                                                         uint32_t *gate, uint32_t *fail_host) {
+                                                         uint32_t *gate, uint32_t *fail_host,
+                                                         const uint4 *__restrict__ filt, const uint2 *__restrict__ attrs) {
     // spec_max != null: the check of the speculative thresholds rides along (spec_max[q] > tau_final[q] voids the batch's screen; no launch of its own): the
     // gated exact pipeline is enqueued after this kernel
     if (spec_max && blockIdx.x == 0 && threadIdx.x == 0 && spec_max[blockIdx.y] > tau_final[blockIdx.y]) {
@@ -570,6 +571,17 @@ __global__ __launch_bounds__(256) void pf_rescore_kernel(const float *__restrict
     c0 = c0 < cap ? c0 : cap;
     const uint32_t c = c0 + n_extra;
     const uint32_t nvec = dim >> 2;
+    // filt != null (a filtered search): a long row that fails query q's filter is left out, the ones that pass go to
+    // c0 + (their rank among the passing long rows) -- the survivors passed the filter in the screen already
+    const uint4 fq = filt ? filt[q] : make_uint4(0u, 0u, 0u, 0u);
+    auto long_passing = [&](uint32_t j) { // long rows [0, j) that pass (every lane of the wave calls it, j uniform)
+        uint32_t cnt = 0;
+        for (uint32_t k0 = 0; k0 < j; k0 += 64) {
+            const uint32_t k = k0 + lane;
+            cnt += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(k < j && oi_doc_passes(fq, attrs[extra_docs[k]])));
+        }
+        return cnt;
+    };
     const float4 *qv = reinterpret_cast<const float4 *>(queries + (uint64_t)q * dim);
     // four survivors per wave and trip: their rows' loads are all in flight before the first reduction (one row at a
     // time this kernel was a chain of HBM round trips: 68 us for 2450 survivors x 64 queries at d = 768)
@@ -602,10 +614,20 @@ __global__ __launch_bounds__(256) void pf_rescore_kernel(const float *__restrict
             const uint64_t r = (uint64_t)(doc[u] - doc_id_base);
             float s = oi_wave_sum(a[u]);
             if (!(r < n_rows)) s = 0.f; // (a key outside the shard: cannot happen; scored 0 as before)
+            if (filt && i0 + u >= c0 && i0 + u < c) { // (wave-uniform)
+                const uint32_t j = i0 + u - c0, slot = c0 + long_passing(j);
+                if (lane == 0 && oi_doc_passes(fq, attrs[extra_docs[j]])) out_pools[(uint64_t)q * out_stride + slot] = oi_rank_key(s, doc[u]);
+                continue;
+            }
             if (lane == 0 && i0 + u < c) out_pools[(uint64_t)q * out_stride + i0 + u] = oi_rank_key(s, doc[u]);
         }
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) out_cnt[q] = c;
+    if (filt) {
+        if (blockIdx.x == 0 && threadIdx.x < 64) {
+            const uint32_t cf = c0 + long_passing(n_extra);
+            if (threadIdx.x == 0) out_cnt[q] = cf;
+        }
+    } else if (blockIdx.x == 0 && threadIdx.x == 0) out_cnt[q] = c;
 }
 
 // ------------------------------------------------------------------ speculative thresholds (round 5)
@@ -762,6 +784,7 @@ int oi_launch_cosine_screen_chunk(oi_ctx *ctx, const float *rows, uint64_t row_b
     oi_cosine_screen_geometry(ctx, row_end > row_begin ? row_end - row_begin : 0, &pool.n_segs, &pool.seg_cap);
     OI_REQUIRE(pool.n_segs <= pool.seg_cnt_stride && pool.carry_cap + (uint64_t)pool.n_segs * pool.seg_cap <= pool.stride,
                "cosine screen: chunk does not fit the candidate pool");
+    OI_REQUIRE(!pool.filt, "cosine screen: a filtered search does not take the f32-stream screen (search.hip routes it)");
     if (row_end <= row_begin || n_queries == 0) return OI_OK;
     ProfScope ps(ctx, "cosine");
     for (uint32_t q0 = 0; q0 < n_queries; q0 += 64) {
@@ -800,7 +823,7 @@ int oi_launch_rescore(oi_ctx *ctx, const float *rows, uint64_t n_rows, uint32_t 
     ProfScope ps(ctx, "rescore");
     hipLaunchKernelGGL(pf_rescore_kernel, dim3(64, n_queries), dim3(256), 0, ctx->stream, rows, dim, doc_id_base, n_rows,
                        d_queries, in.keys, in.carry_cnt, in.stride, in.carry_cap, out.keys, out.carry_cnt, out.stride, extra_docs,
-                       n_extra, spec_max, tau_final, gate, fail_host);
+                       n_extra, spec_max, tau_final, gate, fail_host, out.filt, out.attrs);
     OI_HIP_CHECK(hipGetLastError());
     return OI_OK;
 }

@@ -119,12 +119,13 @@ __device__ __forceinline__ uint32_t sc_incl_scan(uint32_t v) { // wave-wide incl
         st_n -= nf_;                                                                                                   \
     } while (0)
 
-template <int D, int NQT, int NBUF>
+template <int D, int NQT, int NBUF, bool FILT>
 __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
     const uint16_t *__restrict__ rows, uint64_t row_begin, uint64_t row_end,
     const uint16_t *__restrict__ queries, // bf16 [32*NQT][D], zero padded (pf_stage_queries_kernel)
     uint32_t n_queries, uint32_t doc_id_base, uint64_t *pools, uint32_t *seg_cnt, uint32_t seg_cnt_stride,
-    const uint32_t *tau_keys, uint64_t pool_stride, uint32_t carry_cap, uint32_t seg_cap, uint32_t *overflow) {
+    const uint32_t *tau_keys, uint64_t pool_stride, uint32_t carry_cap, uint32_t seg_cap, uint32_t *overflow,
+    const uint4 *__restrict__ filt, const uint2 *__restrict__ attrs) { // FILT: the doc filter (oi_filter_tile) after the threshold
     constexpr int NKC = D / SC_SLOT_K;    // ring slots per tile
     constexpr int P = NBUF - 1;           // slots in flight ahead of the one being consumed
     constexpr int KSTEPS = D / 16;        // MFMA groups per tile: four per slot
@@ -267,6 +268,7 @@ __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
                     if ((uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * lh >= left) m &= ~(0x00010001u << r);
             }
             if (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull) {
+                if constexpr (FILT) m = oi_filter_tile<NQT>(m, filt, attrs, row0, lh, li);
                 const uint32_t cnt = (uint32_t)__builtin_popcount(m);
                 const uint32_t incl = sc_incl_scan(cnt);
                 const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
@@ -333,16 +335,22 @@ __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
 #define OI_COPY_NBUF_DEFAULT 8
 #endif
 
+template <int D, int NQT, int NBUF, bool FILT>
+static int launch_copy_screen_k(oi_ctx *ctx, const uint16_t *rows, uint64_t row_begin, uint64_t row_end, const uint16_t *q,
+                                uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
+    constexpr size_t smem = 4 * NBUF * SC_SLOT_BYTES + 64 * 4 + SC_STAGE_LDS;
+    OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(cosine_copy_screen<D, NQT, NBUF, FILT>), (size_t)(smem)));
+    hipLaunchKernelGGL((cosine_copy_screen<D, NQT, NBUF, FILT>), dim3(p.n_segs), dim3(256), smem, ctx->stream, rows, row_begin,
+                       row_end, q, nq, doc_id_base, p.keys, p.seg_cnt, p.seg_cnt_stride, p.tau_keys, p.stride,
+                       p.carry_cap, p.seg_cap, p.overflow, p.filt, p.attrs);
+    OI_HIP_CHECK(hipGetLastError());
+    return OI_OK;
+}
 template <int D, int NQT, int NBUF>
 static int launch_copy_screen(oi_ctx *ctx, const uint16_t *rows, uint64_t row_begin, uint64_t row_end, const uint16_t *q,
                               uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
-    constexpr size_t smem = 4 * NBUF * SC_SLOT_BYTES + 64 * 4 + SC_STAGE_LDS;
-    OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(cosine_copy_screen<D, NQT, NBUF>), (size_t)(smem)));
-    hipLaunchKernelGGL((cosine_copy_screen<D, NQT, NBUF>), dim3(p.n_segs), dim3(256), smem, ctx->stream, rows, row_begin,
-                       row_end, q, nq, doc_id_base, p.keys, p.seg_cnt, p.seg_cnt_stride, p.tau_keys, p.stride,
-                       p.carry_cap, p.seg_cap, p.overflow);
-    OI_HIP_CHECK(hipGetLastError());
-    return OI_OK;
+    return p.filt ? launch_copy_screen_k<D, NQT, NBUF, true>(ctx, rows, row_begin, row_end, q, nq, doc_id_base, p)
+                  : launch_copy_screen_k<D, NQT, NBUF, false>(ctx, rows, row_begin, row_end, q, nq, doc_id_base, p);
 }
 
 template <int D, int NQT>
@@ -377,6 +385,7 @@ int oi_launch_cosine_screen_copy_chunk(oi_ctx *ctx, const uint16_t *copy_rows, u
         p.carry_cnt += q0;
         p.seg_cnt += (uint64_t)q0 * pool.seg_cnt_stride;
         p.tau_keys += q0;
+        if (p.filt) p.filt += q0;
         const uint16_t *qptr = q_bf16 + (uint64_t)q0 * dim;
         const bool two = nq_here > 32;
         if (dim == 768) {

@@ -287,12 +287,13 @@ __device__ __forceinline__ uint32_t i8s_incl_scan(uint32_t v) { // wave-wide inc
         st_n -= nf_;                                                                                                   \
     } while (0)
 
-template <int D, int NQT, int NBUF>
+template <int D, int NQT, int NBUF, bool FILT>
 __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
     const uint8_t *__restrict__ rows, const float *__restrict__ meta, uint64_t row_begin, uint64_t row_end,
     const int8_t *__restrict__ qhi, const int8_t *__restrict__ qlo, // [32*NQT][D] each (i8s_stage_kernel)
     const float *__restrict__ qf, uint32_t qf_stride, uint32_t n_queries, uint32_t doc_id_base, uint64_t *pools, uint32_t *seg_cnt,
-    uint32_t seg_cnt_stride, const uint32_t *tau_keys, uint64_t pool_stride, uint32_t carry_cap, uint32_t seg_cap, uint32_t *overflow) {
+    uint32_t seg_cnt_stride, const uint32_t *tau_keys, uint64_t pool_stride, uint32_t carry_cap, uint32_t seg_cap, uint32_t *overflow,
+    const uint4 *__restrict__ filt, const uint2 *__restrict__ attrs) { // FILT: the doc filter (oi_filter_tile) after the threshold
     constexpr int NKC = D / 128;          // ring slots per tile
     constexpr int P = NBUF - 1;           // slots in flight ahead of the one being consumed
     constexpr int KSTEPS = D / 32;        // MFMA groups per tile: four per slot
@@ -478,6 +479,7 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
                 return oi_rank_key(score(t, r, sr[r & 3]) - fmaf(er[r & 3], qn[t], cq[t]), doc_id_base + row);
             };
             if (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull) {
+                if constexpr (FILT) m = oi_filter_tile<NQT>(m, filt, attrs, row0, lh, li);
                 const uint32_t cnt = (uint32_t)__builtin_popcount(m);
                 const uint32_t incl = i8s_incl_scan(cnt);
                 const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
@@ -535,16 +537,22 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
     }
 }
 
+template <int D, int NQT, int NBUF, bool FILT>
+static int launch_i8_screen_k(oi_ctx *ctx, const uint8_t *rows, const float *meta, uint64_t row_begin, uint64_t row_end, const int8_t *qhi,
+                              const int8_t *qlo, const float *qf, uint32_t qf_stride, uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
+    constexpr size_t smem = 4 * NBUF * I8S_SLOT_BYTES + 8 * I8S_META_BYTES + 256 + I8S_STAGE_LDS + NQT * (D / 32) * 64 * 16;
+    OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(cosine_i8_screen<D, NQT, NBUF, FILT>), (size_t)(smem)));
+    hipLaunchKernelGGL((cosine_i8_screen<D, NQT, NBUF, FILT>), dim3(p.n_segs), dim3(256), smem, ctx->stream, rows, meta, row_begin, row_end,
+                       qhi, qlo, qf, qf_stride, nq, doc_id_base, p.keys, p.seg_cnt, p.seg_cnt_stride, p.tau_keys, p.stride, p.carry_cap,
+                       p.seg_cap, p.overflow, p.filt, p.attrs);
+    OI_HIP_CHECK(hipGetLastError());
+    return OI_OK;
+}
 template <int D, int NQT, int NBUF>
 static int launch_i8_screen(oi_ctx *ctx, const uint8_t *rows, const float *meta, uint64_t row_begin, uint64_t row_end, const int8_t *qhi,
                             const int8_t *qlo, const float *qf, uint32_t qf_stride, uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
-    constexpr size_t smem = 4 * NBUF * I8S_SLOT_BYTES + 8 * I8S_META_BYTES + 256 + I8S_STAGE_LDS + NQT * (D / 32) * 64 * 16;
-    OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(cosine_i8_screen<D, NQT, NBUF>), (size_t)(smem)));
-    hipLaunchKernelGGL((cosine_i8_screen<D, NQT, NBUF>), dim3(p.n_segs), dim3(256), smem, ctx->stream, rows, meta, row_begin, row_end,
-                       qhi, qlo, qf, qf_stride, nq, doc_id_base, p.keys, p.seg_cnt, p.seg_cnt_stride, p.tau_keys, p.stride, p.carry_cap,
-                       p.seg_cap, p.overflow);
-    OI_HIP_CHECK(hipGetLastError());
-    return OI_OK;
+    return p.filt ? launch_i8_screen_k<D, NQT, NBUF, true>(ctx, rows, meta, row_begin, row_end, qhi, qlo, qf, qf_stride, nq, doc_id_base, p)
+                  : launch_i8_screen_k<D, NQT, NBUF, false>(ctx, rows, meta, row_begin, row_end, qhi, qlo, qf, qf_stride, nq, doc_id_base, p);
 }
 
 // All queries of a batch over rows [row_begin, row_end) of the index's int8 copy (n_rows_total rows).  qi8 / qf: staged by
@@ -568,6 +576,7 @@ int oi_launch_cosine_screen_i8_chunk(oi_ctx *ctx, const uint8_t *i8_copy, uint64
         p.carry_cnt += q0;
         p.seg_cnt += (uint64_t)q0 * pool.seg_cnt_stride;
         p.tau_keys += q0;
+        if (p.filt) p.filt += q0;
         const int8_t *qhi = qi8 + (uint64_t)q0 * dim, *qlo = qi8 + ((uint64_t)np + q0) * dim;
         const float *qfp = qf + q0;
         const bool two = nq_here > 32;

@@ -128,6 +128,33 @@ __device__ __forceinline__ uint32_t oi_wave_sum(uint32_t v) {
     return v;
 }
 
+// The doc filter of a filtered search (oi_doc_filter): f = {group_mask, group_value, stamp_lo, stamp_hi} of the
+// query, a = {group, stamp} of the row (oi_index_set_doc_attrs).  Tested only where a kernel has a hit, after its threshold.
+__device__ __forceinline__ bool oi_doc_passes(const uint4 f, const uint2 a) {
+    return (a.x & f.x) == f.y && f.z <= a.y && a.y <= f.w;
+}
+// The screens' tile epilogue under a filter: bit 16 t + r of m is (query 32 t + li, row row0 + (r&3) + 8 (r>>2) + 4 lh) of a
+// 32-row tile (local rows; a row past the corpus has no bit).  A lane loads each of its 16 rows' attributes at most once
+// per tile, whatever NQT, and its queries' filters only when the tile has a hit.
+template <int NQT>
+__device__ __forceinline__ uint32_t oi_filter_tile(uint32_t m, const uint4 *__restrict__ filt, const uint2 *__restrict__ attrs,
+                                                   uint64_t row0, uint32_t lh, uint32_t li) {
+    if (m == 0u) return 0u;
+    uint4 f[NQT];
+#pragma unroll
+    for (int t = 0; t < NQT; ++t) f[t] = (m >> (16 * t)) & 0xFFFFu ? filt[32u * t + li] : make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        if (m & (0x00010001u << r)) {
+            const uint2 a = attrs[row0 + (uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * lh];
+#pragma unroll
+            for (int t = 0; t < NQT; ++t)
+                if (!oi_doc_passes(f[t], a)) m &= ~(1u << (16 * t + r));
+        }
+    }
+    return m;
+}
+
 // Append one entry to a candidate pool; entries past `cap` are dropped and flagged.
 __device__ __forceinline__ void oi_pool_append(uint64_t *pool, uint32_t *count, uint32_t cap,
                                                uint32_t *overflow, uint64_t key) {

@@ -191,6 +191,9 @@ struct oi_index {
     // per-row absmax scale) then, 256-B aligned, f32 {scale, e_r} per row (+ 64 rows of zero padding) and bits of max e_r over
     // the rows that are not long
     DevBuf screen_i8;
+    // the doc attributes of filtered searches (oi_index_set_doc_attrs): {group, stamp} per local row, n_docs x 8 B; allocated
+    // by the first call, overwritten in place by later ones (never reallocated: views alias it)
+    DevBuf doc_attrs;
 
     // staged forward index (between set_forward and finalize)
     bool forward_set = false, finalized = false;
@@ -222,8 +225,11 @@ struct oi_index {
 };
 
 // search.hip: one hybrid search on the device (the entry points in api.hip stage the queries and copy the results)
+// d_filt / d_attrs: a filtered search -- d_filt[B] the queries' {group_mask, group_value, stamp_lo, stamp_hi},
+// d_attrs the index's {group, stamp} per local row; both null: the unfiltered search
 int search_lists_device(oi_index *idx, const float *d_qv, const uint32_t *d_qt, const uint32_t *d_qo, uint32_t B, uint32_t depth,
-                        float *cos_s, uint32_t *cos_d, uint32_t *cos_c, float *bm_s, uint32_t *bm_d, uint32_t *bm_c);
+                        float *cos_s, uint32_t *cos_d, uint32_t *cos_c, float *bm_s, uint32_t *bm_d, uint32_t *bm_c,
+                        const uint4 *d_filt = nullptr, const uint2 *d_attrs = nullptr);
 void oi_spec_take_failure(oi_ctx *ctx); // a failed speculation check seen since the last look: back off
 
 // ---------------------------------------------------------------- kernels (host launchers)
@@ -266,6 +272,10 @@ struct PoolView {
     uint32_t n_segs;          // segments in use
     uint32_t seg_cnt_stride;  // allocated segments per query
     uint32_t *overflow;       // single device word, set nonzero if a segment overflowed (bug guard)
+    // a filtered search: filt[q] = query q's {group_mask, group_value, stamp_lo, stamp_hi}, offset with tau_keys;
+    // attrs[row] = {group, stamp} of local row `row`.  Null: unfiltered (the kernels' unfiltered instantiations).
+    const uint4 *filt = nullptr;
+    const uint2 *attrs = nullptr;
 };
 // Optional behaviour of a select launch (cosine_prefilter.hip): eps2 != null = margin mode (keep every key within
 // eps2[q] of the k-th score; needs compact, no sorted output, carry_cap >= 4096; an overflowing query sets

@@ -117,6 +117,7 @@ struct Search { // the call's arguments; all pointers device
     uint32_t B, depth;
     float *cos_s; uint32_t *cos_d, *cos_c;
     float *bm_s; uint32_t *bm_d, *bm_c;
+    const uint4 *filt; const uint2 *attrs; // a filtered search: per-query doc filters, the index's {group, stamp} per row
 };
 // none: no cosine list wanted; bf16: a bf16 corpus (cosine_bf16.hip); exact: f32 GEMV, K-split, split-precision or tile (chosen
 // per chunk by oi_launch_cosine_chunk); the bf16 screen, then rescoring and the gated exact pipeline, with bf16(x) converted from the
@@ -154,11 +155,13 @@ Plan plan_search(const Search &s) {
     if (!s.cos_s) p.cos = CosRoute::none;
     else if (idx->rows_bf16) p.cos = CosRoute::bf16;
     else if (!screen) p.cos = CosRoute::exact;
-    else if (!want_copy) p.cos = CosRoute::screen_f32;
+    else if (!want_copy) p.cos = s.filt ? CosRoute::exact : CosRoute::screen_f32; // (filtered: the f32-stream screen has no filter)
     else if (B > 8 && idx->screen_copy.p && idx->screen_i8.p) p.cos = CosRoute::screen_i8;
     else p.cos = CosRoute::screen_copy;
     p.bm25 = bm25_mode_of(idx);
     if (p.bm25 == BM25_SCAN && !(idx->fwd_terms.p && idx->total_tokens > 0)) p.bm25 = BM25_STREAM; // (no forward tokens to scan)
+    // A filtered search: every BM25 mode runs the stream kernel (the four give bit-identical lists; only it has the filter)
+    if (s.filt) p.bm25 = BM25_STREAM;
     // ---- pool capacities
     // cosine: the corpus is scored in chunks; a chunk can append at most one entry per row and query, so a chunk sized from the
     // pool's free room can never overflow it (no overflow path to handle, no data-dependent sizing).  BM25: every doc block
@@ -184,7 +187,9 @@ Plan plan_search(const Search &s) {
     // launches 11 us of 0.34 ms); for spec_skip searches after a failed check.  OI_NO_SPEC=1, OI_SPEC_GROWTH (ablation builds): A/B.
     uint64_t first = oi_screen_first_chunk_rows(ctx, depth), growth = oi_chunk_growth(B);
     const uint64_t pool_max = p.pf_stride - p.pf_carry - p.pf_slack; // rows one screen launch may take (> 0 unless n = 0)
-    if (screened(p.cos) && B > 8) {
+    // No speculation under a filter: the prediction takes the first chunk for a fair sample of the PASSING rows, which a filter
+    // on a corpus stored by ticker or time never is; the ctx's back-off is neither consumed nor changed.
+    if (screened(p.cos) && B > 8 && !s.filt) {
         oi_spec_take_failure(ctx);
         p.spec = ctx->speculate && !K.no_spec && !ctx->use_graphs;
         if (p.spec && ctx->spec_skip) { --ctx->spec_skip; p.spec = false; }
@@ -249,7 +254,8 @@ int bm25_stream(const Search &s, const PoolView &bm) {
     // small pruned segments of the former second phase.  At 10M docs that bound is HIGHER than the first phase's (the 1024th
     // impact of one term over all docs vs the 1000th score over an eighth of them), and a launch, a select and the first
     // phase's 30 K candidates per query go away.  OI_BM25_TWO_PHASE=1 (A/B): the phases as before.
-    const bool floors = idx->impact_floor.p != nullptr && !knobs().bm25_two_phase;
+    // (no floors under a doc filter: a floor bounds the depth-th score of ALL docs, not of the passing ones -- DESIGN 4.7)
+    const bool floors = idx->impact_floor.p != nullptr && !knobs().bm25_two_phase && !s.filt;
     const uint32_t first = floors ? nb : nb > 48 ? std::max<uint32_t>(8, nb / knobs().bm25_first_div) : nb;
     const uint32_t cap1 = oi_bm25_stream_seg_cap(depth, !floors), cap2 = oi_bm25_stream_seg_cap(depth, false);
     const uint64_t sstride = (uint64_t)carry_cap + std::max<uint64_t>((uint64_t)first * cap1, (uint64_t)nb * cap2);
@@ -264,7 +270,7 @@ int bm25_stream(const Search &s, const PoolView &bm) {
         uint32_t *w = sc.as<uint32_t>();
         // (the plan launch also zeroes the pass's pool state: carry_cnt[pass] tau[pass] seg_cnt[pass][nb])
         OI_CHECK(oi_launch_bm25_plan(idx, s.qt, s.qo, q0, nq, w, swords, depth, (uint32_t)pass, (uint32_t)pass, floors));
-        PoolView W1{sp.as<uint64_t>(), w, w + 2 * (size_t)pass, w + pass, sstride, carry_cap, cap1, first, nb, bm.overflow};
+        PoolView W1{sp.as<uint64_t>(), w, w + 2 * (size_t)pass, w + pass, sstride, carry_cap, cap1, first, nb, bm.overflow, s.filt, s.attrs};
         OI_CHECK(oi_launch_bm25_stream(idx, s.qt, s.qo, q0, nq, depth, W1, 0, first));
         PoolView W2 = W1;
         if (first < nb) {
@@ -390,6 +396,7 @@ int fork_bm25(const Search &s, const Plan &p, const PoolView &bm) {
 // bf16 corpus: the same chunk schedule; a workgroup's segment is rounded up to four tiles per wave round
 int cosine_bf16(const Search &s, const Plan &p, PoolView C) {
     oi_index *idx = s.idx;
+    C.filt = s.filt; C.attrs = s.attrs; // (filtered: oi_launch_cosine_bf16_chunk pins the search to cosine_bf16_filter)
     const uint64_t bslack = 128ull * ((uint64_t)s.ctx->num_cus + 1), room = p.cos_stride - OI_MAX_DEPTH;
     const uint64_t max_chunk = room > bslack ? room - bslack : 0;
     if (max_chunk == 0) { oi_set_error("search: cosine pool too small"); return OI_ERR_STATE; }
@@ -408,6 +415,7 @@ int cosine_exact(const Search &s, PoolView X, const float *q, uint32_t Bp, uint6
     oi_index *idx = s.idx;
     SelectExtra ex; ex.run_gate = gate;
     if (screen_tau) X.tau_keys = screen_tau;
+    X.filt = s.filt; X.attrs = s.attrs;
     const uint64_t first = gate ? max_chunk : oi_first_chunk_rows(s.depth);
     for (const Chunk &c : chunk_schedule(idx->n_docs, first, oi_chunk_growth(s.B), max_chunk, true)) {
         OI_CHECK(oi_launch_cosine_chunk(s.ctx, idx->rows, c.r, c.e, idx->dim, q, s.B, Bp, idx->doc_id_base, X));
@@ -435,8 +443,8 @@ int cosine_screen(const Search &s, const Plan &p, const Pools &P, uint32_t *w, c
     float *eps2 = reinterpret_cast<float *>(w + 3 * (size_t)B);
     uint32_t *gate = w + 4 * (size_t)B, *pf_seg = gate + 4;
     uint32_t *spec_tau = pf_seg + (size_t)B * segs, *spec_max = spec_tau + B;
-    PoolView PF{pk.as<uint64_t>(), pf_cnt, pf_seg, pf_tau, p.pf_stride, p.pf_carry, 0, 0, segs, P.cos.overflow};
-    PoolView RS{rk.as<uint64_t>(), rs_cnt, pf_seg, nullptr, rs_cap, rs_cap, 0, 0, segs, P.cos.overflow};
+    PoolView PF{pk.as<uint64_t>(), pf_cnt, pf_seg, pf_tau, p.pf_stride, p.pf_carry, 0, 0, segs, P.cos.overflow, s.filt, s.attrs};
+    PoolView RS{rk.as<uint64_t>(), rs_cnt, pf_seg, nullptr, rs_cap, rs_cap, 0, 0, segs, P.cos.overflow, s.filt, s.attrs};
     OI_CHECK(oi_launch_screen_stage(ctx, s.qv, B, dim, idx->max_row_norm.as<uint32_t>(), qb.as<uint16_t>(), eps2, gate));
     SelectExtra mx; mx.eps2 = eps2; mx.margin_gate = gate;
     if (idx->n_long) { mx.skip_bitmap = idx->long_bitmap.as<uint32_t>(); mx.skip_base = idx->doc_id_base; }
@@ -550,9 +558,10 @@ void oi_spec_take_failure(oi_ctx *ctx) {
 }
 // Device-side ranked lists for a batch; all pointers device.
 int search_lists_device(oi_index *idx, const float *d_qv, const uint32_t *d_qt, const uint32_t *d_qo, uint32_t B, uint32_t depth,
-                        float *cos_s, uint32_t *cos_d, uint32_t *cos_c, float *bm_s, uint32_t *bm_d, uint32_t *bm_c) {
+                        float *cos_s, uint32_t *cos_d, uint32_t *cos_c, float *bm_s, uint32_t *bm_d, uint32_t *bm_c,
+                        const uint4 *d_filt, const uint2 *d_attrs) {
     oi_ctx *ctx = idx->ctx;
-    const Search s{idx, ctx, d_qv, d_qt, d_qo, B, depth, cos_s, cos_d, cos_c, bm_s, bm_d, bm_c};
+    const Search s{idx, ctx, d_qv, d_qt, d_qo, B, depth, cos_s, cos_d, cos_c, bm_s, bm_d, bm_c, d_filt, d_attrs};
     const Plan p = plan_search(s);
     Pools P;
     // the bf16 screen's state words (cosine_screen) ride in the same memset; the depth-sized segments of P.bm belong to the

@@ -159,6 +159,42 @@ class HybridIndex(PostRetriever):
         the forward index).  Bit-identical lists."""
         _lib.check(self.lib.oi_index_set_bm25_mode(self.handle, int(mode)))
 
+    def set_doc_attrs(self, group=None, stamp=None) -> None:
+        """Per-document attributes of filtered searches (oi_index_set_doc_attrs): `group` and `stamp`, n_docs uint32 each
+        (numpy arrays, or torch CUDA tensors of int32 / uint32), indexed by local row; None = zeros.  The first call allocates
+        them, later ones overwrite them in place (retag or soft-delete documents; views see the update)."""
+        arrs = []
+        dev = _is_dev(group) or _is_dev(stamp)
+        for a in (group, stamp):
+            if a is None:
+                arrs.append(None)
+            elif dev:
+                assert _is_dev(a) and a.is_contiguous() and a.numel() == self.n_docs and a.element_size() == 4
+                arrs.append(a)
+            else:
+                a = _np(a, np.uint32)
+                assert a.size == self.n_docs
+                arrs.append(a)
+        _lib.check(self.lib.oi_index_set_doc_attrs(self.handle, _lib.ptr(arrs[0]), _lib.ptr(arrs[1]),
+                                                   _lib.OI_DEVICE if dev else _lib.OI_HOST))
+        if dev:
+            self.ctx.synchronize()  # (the strided copies out of the caller's tensors have completed: nothing to keep alive)
+
+    def _filters(self, filters, dev: bool, B: int):
+        """(n_queries, 4) uint32 {group_mask, group_value, stamp_lo, stamp_hi} per query, on the queries' side."""
+        if dev:
+            import torch
+            if not _is_dev(filters):
+                f = np.ascontiguousarray(np.asarray(filters, dtype=np.uint32).reshape(B, 4))
+                filters = torch.from_numpy(f.view(np.int32)).to("cuda:%d" % self.ctx.device)
+            assert filters.is_contiguous() and filters.numel() == 4 * B and filters.element_size() == 4
+            self._filt_keep = filters  # (an asynchronous call reads it later)
+            return filters
+        if _is_dev(filters):
+            filters = filters.cpu().numpy()
+        f = np.ascontiguousarray(np.asarray(filters).astype(np.uint32, copy=False).reshape(B, 4))
+        return f
+
     def set_max_query_terms(self, max_terms: int) -> None:
         """Contract for the batch BM25 scan: no query has more terms than this (default 16)."""
         _lib.check(self.lib.oi_index_set_max_query_terms(self.handle, int(max_terms)))
@@ -198,11 +234,20 @@ class HybridIndex(PostRetriever):
         assert int(query_vecs.shape[1]) == self.dim
         return dev, B, query_vecs, query_terms, q_term_offsets
 
-    def search_lists(self, query_vecs, query_terms, q_term_offsets, depth: int = DEFAULT_DEPTH) -> RankedLists:
+    def search_lists(self, query_vecs, query_terms, q_term_offsets, depth: int = DEFAULT_DEPTH, filters=None) -> RankedLists:
+        """filters: None, or (n_queries, 4) uint32 doc filters (oi_doc_filter rows; host array or torch CUDA tensor)."""
         dev, B, qv, qt, qo = self._queries(query_vecs, query_terms, q_term_offsets)
         out = RankedLists(*(self._alloc(dev, s, d) for s, d in (
             ((B, depth), np.float32), ((B, depth), np.uint32), ((B,), np.uint32),
             ((B, depth), np.float32), ((B, depth), np.uint32), ((B,), np.uint32))))
+        if filters is not None:
+            f = self._filters(filters, dev, B)
+            _lib.check(self.lib.oi_search_lists_filtered(
+                self.handle, _lib.ptr(qv), _lib.ptr(qt), _lib.ptr(qo), B, int(depth), _lib.ptr(f),
+                _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(out.cos_scores), _lib.ptr(out.cos_docs),
+                _lib.ptr(out.cos_counts), _lib.ptr(out.bm25_scores), _lib.ptr(out.bm25_docs),
+                _lib.ptr(out.bm25_counts)))
+            return out
         _lib.check(self.lib.oi_search_lists(
             self.handle, _lib.ptr(qv), _lib.ptr(qt), _lib.ptr(qo), B, int(depth),
             _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(out.cos_scores), _lib.ptr(out.cos_docs),
@@ -210,24 +255,37 @@ class HybridIndex(PostRetriever):
             _lib.ptr(out.bm25_counts)))
         return out
 
-    def search_lists_packed(self, query_vecs, query_terms, q_term_offsets, depth: int = DEFAULT_DEPTH, out=None):
+    def search_lists_packed(self, query_vecs, query_terms, q_term_offsets, depth: int = DEFAULT_DEPTH, out=None,
+                            filters=None):
         """The shard's two lists in the multi-GPU exchange format (include/openintel_hip.h,
         OI_PACKED_WORDS): one flat int32/uint32 buffer, ready for all_gather_into_tensor."""
         dev, B, qv, qt, qo = self._queries(query_vecs, query_terms, q_term_offsets)
         words = packed_words(B, depth)
         if out is None:
             out = self._alloc(dev, (words,), np.uint32)
+        if filters is not None:
+            f = self._filters(filters, dev, B)
+            _lib.check(self.lib.oi_search_lists_packed_filtered(self.handle, _lib.ptr(qv), _lib.ptr(qt), _lib.ptr(qo), B,
+                                                                int(depth), _lib.ptr(f), _lib.OI_DEVICE if dev else _lib.OI_HOST,
+                                                                _lib.ptr(out)))
+            return out
         _lib.check(self.lib.oi_search_lists_packed(self.handle, _lib.ptr(qv), _lib.ptr(qt), _lib.ptr(qo), B,
                                                    int(depth), _lib.OI_DEVICE if dev else _lib.OI_HOST,
                                                    _lib.ptr(out)))
         return out
 
     def search(self, query_vecs, query_terms, q_term_offsets, k: int = DEFAULT_K,
-               depth: int = DEFAULT_DEPTH, out: Optional[SearchResult] = None) -> SearchResult:
+               depth: int = DEFAULT_DEPTH, out: Optional[SearchResult] = None, filters=None) -> SearchResult:
         dev, B, qv, qt, qo = self._queries(query_vecs, query_terms, q_term_offsets)
         if out is None:
             out = SearchResult(self._alloc(dev, (B, k), np.float32), self._alloc(dev, (B, k), np.uint32),
                                self._alloc(dev, (B,), np.uint32))
+        if filters is not None:
+            f = self._filters(filters, dev, B)
+            _lib.check(self.lib.oi_search_filtered(self.handle, _lib.ptr(qv), _lib.ptr(qt), _lib.ptr(qo), B, int(depth),
+                                                   int(k), _lib.ptr(f), _lib.OI_DEVICE if dev else _lib.OI_HOST,
+                                                   _lib.ptr(out.scores), _lib.ptr(out.docs), _lib.ptr(out.counts)))
+            return out
         _lib.check(self.lib.oi_search(self.handle, _lib.ptr(qv), _lib.ptr(qt), _lib.ptr(qo), B, int(depth), int(k),
                                       _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(out.scores),
                                       _lib.ptr(out.docs), _lib.ptr(out.counts)))
@@ -240,13 +298,20 @@ class HybridIndex(PostRetriever):
         _lib.check(self.lib.oi_index_finalize_sharded(self.handle, comm.handle))
 
     def search_sharded(self, comm: "NativeComm", query_vecs, query_terms, q_term_offsets, k: int = DEFAULT_K,
-                       depth: int = DEFAULT_DEPTH, out: Optional[SearchResult] = None) -> SearchResult:
+                       depth: int = DEFAULT_DEPTH, out: Optional[SearchResult] = None, filters=None) -> SearchResult:
         """Collective over `comm`, same queries on every rank: this shard's lists -> ONE ncclAllGather -> global merge ->
         RRF, in one C call (oi_search_sharded).  Identical result on every rank."""
         dev, B, qv, qt, qo = self._queries(query_vecs, query_terms, q_term_offsets)
         if out is None:
             out = SearchResult(self._alloc(dev, (B, k), np.float32), self._alloc(dev, (B, k), np.uint32),
                                self._alloc(dev, (B,), np.uint32))
+        if filters is not None:
+            f = self._filters(filters, dev, B)
+            _lib.check(self.lib.oi_search_sharded_filtered(self.handle, comm.handle, _lib.ptr(qv), _lib.ptr(qt), _lib.ptr(qo),
+                                                           B, int(depth), int(k), _lib.ptr(f),
+                                                           _lib.OI_DEVICE if dev else _lib.OI_HOST,
+                                                           _lib.ptr(out.scores), _lib.ptr(out.docs), _lib.ptr(out.counts)))
+            return out
         _lib.check(self.lib.oi_search_sharded(self.handle, comm.handle, _lib.ptr(qv), _lib.ptr(qt), _lib.ptr(qo), B,
                                               int(depth), int(k), _lib.OI_DEVICE if dev else _lib.OI_HOST,
                                               _lib.ptr(out.scores), _lib.ptr(out.docs), _lib.ptr(out.counts)))

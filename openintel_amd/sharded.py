@@ -67,8 +67,9 @@ class ShardedRetriever:
         self.local.finalize(n_global, tok_global, gdf.cpu().numpy().astype(np.uint32))
 
     # ---- query
-    def search(self, qv, qt, qo, k: int, depth: int, check: bool = True):
-        """Returns (scores [B,k], docs [B,k], counts [B]) -- identical on every rank.
+    def search(self, qv, qt, qo, k: int, depth: int, check: bool = True, filters=None):
+        """Returns (scores [B,k], docs [B,k], counts [B]) -- identical on every rank.  filters: None, or (B, 4) uint32 doc
+        filters (oi_doc_filter rows): each rank filters its own shard, the exchange and the fusion are unchanged.
 
         The device path is asynchronous and the library reports a candidate-pool overflow (OI_ERR_OVERFLOW, a bug
         guard) only at a host-visible point: with check=True (default) the engine is synchronised after the fuse so
@@ -77,7 +78,8 @@ class ShardedRetriever:
         import torch
         if self.fuse_packed is not None:
             B = int(qv.shape[0])
-            packed = self.local.search_lists_packed(qv, qt, qo, depth=depth)
+            kw = {} if filters is None else {"filters": filters}   # (a shard without filters: any search_lists_packed)
+            packed = self.local.search_lists_packed(qv, qt, qo, depth=depth, **kw)
             if self.exchange:
                 flat = torch.empty(self.world * packed.numel(), dtype=packed.dtype, device=packed.device)
                 self.dist.all_gather_into_tensor(flat, packed, group=self.group)   # the ONE exchange per batch
@@ -87,7 +89,7 @@ class ShardedRetriever:
             if check:
                 self.check()
             return out
-        L = self.local.search_lists(qv, qt, qo, depth=depth)
+        L = self.local.search_lists(qv, qt, qo, depth=depth, **({} if filters is None else {"filters": filters}))
         if self.world == 1:
             cos_d, cos_c, bm_d, bm_c = L.cos_docs, L.cos_counts, L.bm25_docs, L.bm25_counts
         else:
