@@ -486,6 +486,53 @@ int oi_search_sharded_filtered(oi_index *idx, oi_comm *comm, const float *query_
                                uint32_t *counts_out);
 
 /* ------------------------------------------------------------------------- */
+/* Text to term ids: the tokeniser and the hashed vocabulary                   */
+/* ------------------------------------------------------------------------- */
+/*
+ * What connects post TEXT to the u32 term ids of oi_index_set_forward and of every oi_search* call.
+ *
+ * TOKENS of a text are the reference's (src/adapters/analyzer/lexicon.rs:54-58): Unicode lowercase, then the maximal runs
+ * of ASCII [0-9a-z].  At byte level: A-Z -> a-z; U+212A (E2 84 AA) -> 'k', joining the token around it; U+0130 (C4 B0) ->
+ * 'i' followed by a separator; every other byte >= 0x80 separates.  A text boundary always cuts a token ("abc" | "def" in
+ * adjacent texts are two tokens).  The input is valid UTF-8, as for oi_lexicon_analyze.
+ *
+ * TERM ID of a token whose lowercased bytes are b[0..len) -- the hashing trick, no dictionary to build, ship or all-reduce;
+ * a document and a query, and two ranks of a sharded index, agree by construction:
+ *     h = 0xcbf29ce484222325;  for i < min(len, OI_TEXT_TOKEN_HASH_BYTES):  h = (h ^ b[i]) * 0x100000001b3    (FNV-1a, mod 2^64)
+ *     h ^= h >> 33;  h *= 0xff51afd7ed558ccd;  h ^= h >> 33;  h *= 0xc4ceb9fe1a85ec53;  h ^= h >> 33           (fmix64)
+ *     term = (uint32_t)(((h >> 32) * (uint64_t)vocab) >> 32)
+ * A token longer than OI_TEXT_TOKEN_HASH_BYTES lowercased bytes hashes by its first 64; it is still ONE token and ends
+ * where its run ends.  Collisions merge terms (not an error): about T^2 / 2V colliding pairs for T distinct tokens in a
+ * vocabulary of V.  Term ids come out in text order, duplicates kept (a forward index wants tf; a repeated query term
+ * counts each time).  The output is a pure function of the input.
+ *
+ * oi_text_terms: text i = blob[offsets[i] .. offsets[i+1]) (n_texts + 1 offsets, offsets[0] == 0, offsets[n_texts] ==
+ *   blob_bytes) -- the buffers of oi_lexicon_analyze[_device], so one blob in HBM serves the analyzer and the index.
+ *   Text i's ids are term_ids_out[text_offsets_out[i] .. text_offsets_out[i+1]); *total_out_host (may be NULL) = their
+ *   number.  term_ids_out == NULL: count only (offsets and total), so a caller sizes its buffer with one call and fills it
+ *   with the next.  Otherwise total > term_capacity -> OI_ERR_OVERFLOW, nothing written past the capacity (the ctx stays
+ *   usable); (blob_bytes + 1) / 2 is always enough.  location says where EVERY buffer but total_out_host lives.
+ *   OI_DEVICE: asynchronous on the ctx stream when total_out_host == NULL and term_capacity >= (blob_bytes + 1) / 2 (or
+ *   count only); otherwise the call synchronises the stream once (the total comes back).  OI_HOST: synchronous.
+ * oi_query_terms: the same over a batch of query texts with u32 offsets: its outputs are exactly the `query_terms` /
+ *   `q_term_offsets` pair of the oi_search* calls (which are unchanged: a host tokenises, then searches).
+ * oi_index_set_text: tokenise with the index's own vocab straight into the forward index and stage it -- bit for bit what
+ *   oi_text_terms followed by oi_index_set_forward gives, without the caller ever holding the ids.  offsets: n_docs + 1.
+ *   State rules of oi_index_set_forward (a view: OI_ERR_STATE; at most 2^32 - 2 tokens per shard).
+ * All three with OI_DEVICE: the offsets cannot be checked by the library.  They must be non-decreasing, start at 0 and end at
+ * blob_bytes; otherwise the output offsets (and with them the index oi_index_set_text stages) are unspecified -- the
+ * call still writes nothing outside the buffers it was given.
+ */
+#define OI_TEXT_TOKEN_HASH_BYTES 64u
+int oi_text_terms(oi_ctx *ctx, const uint8_t *blob, const uint64_t *offsets, uint64_t n_texts, uint64_t blob_bytes,
+                  uint32_t vocab, int location, uint32_t *term_ids_out, uint64_t term_capacity,
+                  uint64_t *text_offsets_out, uint64_t *total_out_host);
+int oi_query_terms(oi_ctx *ctx, const uint8_t *blob, const uint32_t *offsets, uint32_t n_queries, uint32_t blob_bytes,
+                   uint32_t vocab, int location, uint32_t *query_terms_out, uint64_t term_capacity,
+                   uint32_t *q_term_offsets_out, uint64_t *total_out_host);
+int oi_index_set_text(oi_index *idx, const uint8_t *blob, const uint64_t *offsets, uint64_t blob_bytes, int location);
+
+/* ------------------------------------------------------------------------- */
 /* The pipelined query behind the C ABI: several batches in flight             */
 /* ------------------------------------------------------------------------- */
 /*
@@ -549,7 +596,7 @@ int oi_screen_probe(oi_index *idx, const float *query_vecs, uint32_t n_queries, 
 
 /* Timing hooks for bench.py: when enabled, HIP events are recorded on the ctx stream
  * around every kernel launch, grouped by tag ("cosine", "bm25", "select", "rrf",
- * "lexicon", "social_summary").  oi_profile_read returns the summed duration (ms) of
+ * "lexicon", "social_summary", "text_count", "text_emit").  oi_profile_read returns the summed duration (ms) of
  * the launches with that tag and their count since the last reset.  enable: 0 off, 1 every
  * tagged launch, 2 only the "cosine" launches (two event packets per launch cost a few us of
  * stream time each: a timed region that only needs its dominant kernel asks for 2). */

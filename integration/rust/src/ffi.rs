@@ -153,6 +153,15 @@ extern "C" {
                              q_term_offsets: *const u32, n_queries: u32, depth: u32, k: u32, location: c_int,
                              scores_out: *mut f32, docs_out: *mut u32, counts_out: *mut u32) -> c_int;
 
+    // text -> term ids (the reference's tokens hashed onto [0, vocab); offsets[0] == 0, offsets[n] == blob_bytes)
+    pub fn oi_text_terms(ctx: *mut OiCtx, blob: *const u8, offsets: *const u64, n_texts: u64, blob_bytes: u64, vocab: u32,
+                         location: c_int, term_ids_out: *mut u32, term_capacity: u64, text_offsets_out: *mut u64,
+                         total_out_host: *mut u64) -> c_int;
+    pub fn oi_query_terms(ctx: *mut OiCtx, blob: *const u8, offsets: *const u32, n_queries: u32, blob_bytes: u32, vocab: u32,
+                          location: c_int, query_terms_out: *mut u32, term_capacity: u64, q_term_offsets_out: *mut u32,
+                          total_out_host: *mut u64) -> c_int;
+    pub fn oi_index_set_text(idx: *mut OiIndex, blob: *const u8, offsets: *const u64, blob_bytes: u64, location: c_int) -> c_int;
+
     // filtered search (per-document group / stamp attributes, one oi_doc_filter per query)
     pub fn oi_index_set_doc_attrs(idx: *mut OiIndex, group: *const u32, stamp: *const u32, location: c_int) -> c_int;
     pub fn oi_search_lists_filtered(idx: *mut OiIndex, query_vecs: *const f32, query_terms: *const u32, q_term_offsets: *const u32,

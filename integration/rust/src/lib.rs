@@ -63,6 +63,21 @@ pub fn gather<'a, I: IntoIterator<Item = &'a str>>(texts: I) -> (Vec<u8>, Vec<u6
     (blob, offsets)
 }
 
+/// Query texts -> the `query_terms` of `HipIndex::search*` (`oi_query_terms`): the tokens of lexicon.rs:54-58 hashed onto
+/// [0, vocab), in text order, duplicates kept.  `vocab` is the index's.
+pub fn query_terms(ctx: &HipCtx, texts: &[&str], vocab: u32) -> Result<Vec<Vec<u32>>, HipError> {
+    let (blob, offsets64) = gather(texts.iter().copied());
+    assert!(blob.len() <= u32::MAX as usize && texts.len() < u32::MAX as usize, "a query batch has u32 offsets: under 4 GiB of text");
+    let offsets: Vec<u32> = offsets64.iter().map(|&o| o as u32).collect();
+    let mut terms = vec![0u32; (blob.len() + 1) / 2 + 1];
+    let mut toffs = vec![0u32; texts.len() + 1];
+    check(unsafe {
+        ffi::oi_query_terms(ctx.raw(), blob.as_ptr(), offsets.as_ptr(), texts.len() as u32, blob.len() as u32, vocab, ffi::OI_HOST,
+                            terms.as_mut_ptr(), terms.len() as u64, toffs.as_mut_ptr(), std::ptr::null_mut())
+    })?;
+    Ok((0..texts.len()).map(|q| terms[toffs[q] as usize..toffs[q + 1] as usize].to_vec()).collect())
+}
+
 /// `LexiconAnalyzer::score` for every text (lexicon.rs:53-73): (polarity, speculative), index-aligned.
 pub fn analyze_texts(ctx: &HipCtx, texts: &[&str]) -> Result<Vec<(f64, bool)>, HipError> {
     let (blob, offsets) = gather(texts.iter().copied());
@@ -214,6 +229,22 @@ impl HipIndex {
         let me = HipIndex { ctx, idx, dim, n_docs: n_docs as usize, source: None };
         check(unsafe { ffi::oi_index_set_embeddings(me.idx, rows.as_mut_ptr(), ffi::OI_HOST, 1) })?;
         check(unsafe { ffi::oi_index_set_forward(me.idx, terms.as_ptr(), offsets.as_ptr(), ffi::OI_HOST) })?;
+        let mut tokens = 0u64;
+        check(unsafe { ffi::oi_index_local_stats(me.idx, &mut tokens, std::ptr::null_mut()) })?;
+        check(unsafe { ffi::oi_index_finalize(me.idx, n_docs, tokens, std::ptr::null()) })?;
+        Ok(me)
+    }
+    /// `build` from the posts' TEXT (`oi_index_set_text`): the reference's tokens (lexicon.rs:54-58) hashed onto [0, vocab),
+    /// so there is no dictionary to keep; queries go through `query_terms` with the same vocab.
+    pub fn build_from_texts(ctx: Arc<HipCtx>, rows: &mut [f32], dim: usize, vocab: u32, texts: &[&str]) -> Result<Self, HipError> {
+        let n_docs = (rows.len() / dim) as u64;
+        assert_eq!(texts.len() as u64, n_docs, "one text per embedding row");
+        let (blob, offsets) = gather(texts.iter().copied());
+        let mut idx = std::ptr::null_mut();
+        check(unsafe { ffi::oi_index_create(ctx.raw(), n_docs, dim as u32, vocab, 0, &mut idx) })?;
+        let me = HipIndex { ctx, idx, dim, n_docs: n_docs as usize, source: None };
+        check(unsafe { ffi::oi_index_set_embeddings(me.idx, rows.as_mut_ptr(), ffi::OI_HOST, 1) })?;
+        check(unsafe { ffi::oi_index_set_text(me.idx, blob.as_ptr(), offsets.as_ptr(), blob.len() as u64, ffi::OI_HOST) })?;
         let mut tokens = 0u64;
         check(unsafe { ffi::oi_index_local_stats(me.idx, &mut tokens, std::ptr::null_mut()) })?;
         check(unsafe { ffi::oi_index_finalize(me.idx, n_docs, tokens, std::ptr::null()) })?;

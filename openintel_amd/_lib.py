@@ -18,6 +18,7 @@ OI_MAX_DEPTH = 1024
 OI_MAX_DIM = 1024
 OI_BM25_BLOCK_DOCS = 32768
 OI_N_CATALYST_KEYWORDS = 16
+OI_TEXT_TOKEN_HASH_BYTES = 64
 OI_COSINE_EXACT, OI_COSINE_SPLIT, OI_COSINE_SCREEN, OI_COSINE_SCREEN_COPY, OI_COSINE_SCREEN_STREAM = 0, 1, 2, 3, 4
 OI_SCREEN_COPY_AUTO, OI_SCREEN_COPY_NEVER, OI_SCREEN_COPY_ALWAYS = 0, 1, 2
 
@@ -117,6 +118,9 @@ SIGNATURES = {
     "oi_search_lists_packed_filtered": (_I, [_P, _P, _P, _P, _U32, _U32, _P, _I, _P]),
     "oi_search_filtered": (_I, [_P, _P, _P, _P, _U32, _U32, _U32, _P, _I, _P, _P, _P]),
     "oi_search_sharded_filtered": (_I, [_P, _P, _P, _P, _P, _U32, _U32, _U32, _P, _I, _P, _P, _P]),
+    "oi_text_terms": (_I, [_P, _P, _P, _U64, _U64, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
+    "oi_query_terms": (_I, [_P, _P, _P, _U32, _U32, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
+    "oi_index_set_text": (_I, [_P, _P, _P, _U64, _I]),
     "oi_pipeline_create": (_I, [_P, _P, _U32, _U32, _U32, _U32, _U32, C.POINTER(_P)]),
     "oi_pipeline_destroy": (None, [_P]),
     "oi_pipeline_submit": (_I, [_P, _P, _P, _P, _U32, _I, _P, _P, _P, C.POINTER(_U64)]),

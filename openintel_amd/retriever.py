@@ -81,6 +81,66 @@ def pack_query_terms(term_lists: Sequence[Sequence[int]]) -> Tuple[np.ndarray, n
     return flat, offs
 
 
+def _packed_texts(texts, off_dtype):
+    """texts: a sequence of str (packed here, host) or a (blob, offsets) pair (numpy arrays, or torch CUDA tensors: uint8
+    blob + 8-byte / 4-byte integer offsets).  -> (is_device, blob, offsets, n_texts, blob_bytes)."""
+    if isinstance(texts, tuple) and len(texts) == 2 and not isinstance(texts[0], str):
+        blob, offsets = texts
+        if _is_dev(blob):
+            assert blob.is_contiguous() and offsets.is_contiguous() and blob.element_size() == 1
+            assert offsets.element_size() == np.dtype(off_dtype).itemsize, "offsets: %s wanted" % np.dtype(off_dtype).name
+            return True, blob, offsets, int(offsets.numel()) - 1, int(blob.numel())
+        blob, offsets = _np(blob, np.uint8), np.asarray(offsets)
+    else:
+        from .analyzer import pack_posts
+        blob, offsets = pack_posts(list(texts))
+    if int(offsets[-1]) > np.iinfo(off_dtype).max:  # (a cast would wrap silently)
+        raise ValueError("%d bytes of text do not fit %s offsets" % (int(offsets[-1]), np.dtype(off_dtype).name))
+    offsets = _np(offsets, off_dtype)
+    return False, blob, offsets, int(offsets.size) - 1, int(blob.size)
+
+
+def _text_terms(ctx: HipContext, texts, vocab: int, off_dtype, count_only: bool):
+    lib = ctx.lib
+    fn = lib.oi_text_terms if off_dtype is np.uint64 else lib.oi_query_terms
+    dev, blob, offsets, n, nbytes = _packed_texts(texts, off_dtype)
+    loc = _lib.OI_DEVICE if dev else _lib.OI_HOST
+    if dev:
+        import torch
+        where = blob.device
+        out_offs = torch.zeros(n + 1, dtype=torch.int64 if off_dtype is np.uint64 else torch.int32, device=where)
+    else:
+        out_offs = np.zeros(n + 1, dtype=off_dtype)
+    total = C.c_uint64()
+    if count_only:
+        _lib.check(fn(ctx.handle, _lib.ptr(blob), _lib.ptr(offsets), n, nbytes, int(vocab), loc, None, 0, _lib.ptr(out_offs),
+                      C.byref(total)))
+        return total.value, out_offs
+    if not dev:
+        # host text is copied to the GPU by the call: ONE call, into a buffer that is always large enough (two tokens need a
+        # separator between them)
+        ids = np.zeros(max((nbytes + 1) // 2, 1), dtype=np.uint32)
+        _lib.check(fn(ctx.handle, _lib.ptr(blob), _lib.ptr(offsets), n, nbytes, int(vocab), loc, _lib.ptr(ids), ids.size,
+                      _lib.ptr(out_offs), C.byref(total)))
+        return ids[:total.value].copy() if total.value < ids.size else ids, out_offs
+    # text in HBM: nothing is copied, so one call for the size (the count pass, 0.7 ms per 10M posts) and one to fill a
+    # buffer of exactly that size rather than holding 2 B of ids per byte of text
+    _lib.check(fn(ctx.handle, _lib.ptr(blob), _lib.ptr(offsets), n, nbytes, int(vocab), loc, None, 0, _lib.ptr(out_offs),
+                  C.byref(total)))
+    ids = torch.zeros(max(total.value, 1), dtype=torch.int32, device=where)
+    _lib.check(fn(ctx.handle, _lib.ptr(blob), _lib.ptr(offsets), n, nbytes, int(vocab), loc, _lib.ptr(ids), total.value,
+                  _lib.ptr(out_offs), None))
+    return ids[:total.value], out_offs
+
+
+def text_terms(ctx: HipContext, texts, vocab: int, count_only: bool = False):
+    """oi_text_terms: the reference's tokens of every text hashed onto [0, vocab), in text order, duplicates kept.
+    texts: a sequence of str, or (blob, offsets) as analyzer.pack_posts makes them (numpy, or torch CUDA tensors -- the
+    outputs then stay in HBM: int32 ids holding the u32 bits, int64 offsets).  -> (term_ids, text_offsets[n + 1]);
+    count_only: (total, text_offsets) without producing the ids."""
+    return _text_terms(ctx, texts, vocab, np.uint64, count_only)
+
+
 class HybridIndex(PostRetriever):
     """One corpus shard resident in HBM: n_docs x dim f32 rows + a blocked BM25 inverted index."""
 
@@ -130,6 +190,30 @@ class HybridIndex(PostRetriever):
             assert doc_offsets.size == self.n_docs + 1
             loc = _lib.OI_HOST
         _lib.check(self.lib.oi_index_set_forward(self.handle, _lib.ptr(term_ids), _lib.ptr(doc_offsets), loc))
+
+    def set_text(self, texts) -> None:
+        """set_forward from the posts' TEXT (oi_index_set_text): tokenised on the GPU with this index's vocab as the hash
+        range -- bit for bit text_terms() + set_forward(), without the ids ever reaching the caller.  texts: n_docs str, or
+        (blob, offsets) as analyzer.pack_posts makes them (numpy, or torch CUDA tensors: the blob the analyzer reads)."""
+        dev, blob, offsets, n, nbytes = _packed_texts(texts, np.uint64)
+        assert n == self.n_docs, "one text per document of the shard"
+        _lib.check(self.lib.oi_index_set_text(self.handle, _lib.ptr(blob), _lib.ptr(offsets), nbytes,
+                                              _lib.OI_DEVICE if dev else _lib.OI_HOST))
+
+    def query_terms(self, texts):
+        """Query texts -> (query_terms, q_term_offsets) as every search call takes them (oi_query_terms, this index's
+        vocab): sequence of str, or (blob, u32 offsets); device in, device out."""
+        return _text_terms(self.ctx, texts, self.vocab, np.uint32, False)
+
+    def search_text(self, query_vecs, query_texts, k: int = DEFAULT_K, depth: int = DEFAULT_DEPTH,
+                    out: Optional[SearchResult] = None, filters=None) -> SearchResult:
+        """search() with the lexical side given as text: query_terms(query_texts), then search.  Host strings go with
+        host vectors; a device (blob, offsets) pair with device vectors."""
+        qt, qo = self.query_terms(query_texts)
+        assert _is_dev(qt) == _is_dev(query_vecs), "query vectors and query texts must live in the same place"
+        if _is_dev(qt) and qt.numel() == 0:
+            qt = self._alloc(True, (1,), np.uint32)
+        return self.search(query_vecs, qt, qo, k=k, depth=depth, out=out, filters=filters)
 
     def long_rows(self) -> int:
         """Rows the screened cosine scorer sets aside (always rescored, never part of its thresholds): oi_index_long_rows."""

@@ -3,7 +3,10 @@
 Path:
   build   every rank holds rows [base, base + n_local) of the corpus.  BM25 needs GLOBAL
           statistics: one all-reduce of the (vocab) document-frequency vector and of
-          (n_docs, token count) before the impacts are computed.
+          (n_docs, token count) before the impacts are computed.  From post TEXT each rank
+          simply calls HybridIndex.set_text on its own shard: term ids are hashes of the tokens
+          (oi_text_terms), so the ranks agree on every id without exchanging a dictionary, and
+          the queries go through HybridIndex.query_terms on every rank alike.
   query   queries are replicated.  Each rank produces its shard's two ranked lists of depth k'
           (cosine, BM25).  RRF needs GLOBAL ranks, so the exchange is ONE all-gather of the packed
           per-shard lists (B x 2 x k' x 8 B per rank ~ 1 MB at B=64, k'=1000: latency-bound over
