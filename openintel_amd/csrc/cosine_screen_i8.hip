@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
     constexpr int P = NBUF - 1;           // slots in flight ahead of the one being consumed
     constexpr int KSTEPS = D / 32;        // MFMA groups per tile: four per slot
     constexpr uint32_t RING = NBUF * I8S_SLOT_BYTES;
-    static_assert(D % 128 == 0 && P >= 1 && P <= 2 * NKC, "unsupported ring depth for this D");
+    static_assert(D % 128 == 0 && P >= 2 && P <= 2 * NKC, "unsupported ring depth for this D");
     constexpr uint32_t QLO_LDS = NQT * KSTEPS * 64 * 16; // the lo parts, fragment-major (one conflict-free ds_read_b128 each)
     static_assert(NQT * KSTEPS * 4 <= 200, "the hi query block must fit the register file");
     static_assert(4 * RING + 4 * 2 * I8S_META_BYTES + 256 + I8S_STAGE_LDS + QLO_LDS <= 160 * 1024, "LDS");
@@ -398,6 +398,21 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
         });
         issue_meta(0); // (4 NKC pieces younger than it when tile 0's epilogue waits for it)
         uint32_t rd_off = 0, wr_off = (NBUF - 1) * I8S_SLOT_BYTES;
+        // The fragment reads run a k-step ahead of the MFMAs that use them (one wave per SIMD: a waited-for LDS round trip is
+        // time nothing else fills).  The lo fragments do not depend on the tile, so their rotation runs across tiles: the last
+        // k-step of a tile reads the first one's for the next tile.
+        auto lo_frag = [&](int t, int s) {
+            return *reinterpret_cast<const i8s_i32x4 *>(qlo_lds + ((t * KSTEPS + s) * 64 + lane) * 16);
+        };
+        i8s_i32x4 b_cur[NQT];
+#ifndef I8S_NO_MFMA
+#pragma unroll
+        for (int t = 0; t < NQT; ++t) b_cur[t] = lo_frag(t, 0);
+#endif
+
+        // (the meta load between the pieces only makes a counted wait wait for one piece more)
+        i8s_wait<4 * (P - 1)>();
+        i8s_i32x4 a_cur = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + frag_off[0]);
 
         for (uint64_t ti = 0; ti < my_nt; ++ti) {
             i8s_i32x16 ah[NQT], al[NQT];
@@ -406,22 +421,36 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { ah[t][r] = 0; al[t][r] = 0; }
 
-            i8s_wait<4 * (P - 1)>(); // (the meta load between the pieces only makes a counted wait wait for one piece more)
-            i8s_i32x4 a_cur = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + rd_off + frag_off[0]);
             i8s_static_for<0, NKC * 4>([&](auto gi_) {
                 constexpr int gi = decltype(gi_)::value;
                 constexpr int kc = gi / 4, g = gi % 4;
                 constexpr int sn = kc + P;
                 constexpr int tn = sn / NKC, kn = sn % NKC;
-                i8s_i32x4 a_nxt = a_cur;
-                if constexpr (g < 3) a_nxt = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + rd_off + frag_off[g + 1]);
+                // ---- the reads of k-step gi + 1, into registers no MFMA in flight reads
+                i8s_i32x4 a_nxt;
+                if constexpr (g < 3) {
+                    a_nxt = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + rd_off + frag_off[g + 1]);
+                } else {
+                    // the next slot (after the tile's last slot: the next tile's first; past the last tile: zeros nobody uses).
+                    // Slots kc + 2 .. kc + P - 1 and three pieces of slot kc + P are younger than its pieces.
+                    i8s_wait<4 * (P - 1) - 1>();
+                    const uint32_t nx_off = rd_off + I8S_SLOT_BYTES == RING ? 0u : rd_off + I8S_SLOT_BYTES;
+                    a_nxt = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + nx_off + frag_off[0]);
+                }
 #ifndef I8S_NO_MFMA // (ablation builds: the stream without the matrix instructions; every score 0, results WRONG)
+                i8s_i32x4 b_nxt[NQT];
+#pragma unroll
+                for (int t = 0; t < NQT; ++t) b_nxt[t] = lo_frag(t, (gi + 1) % KSTEPS);
+                // (without this the compiler sinks the reads back next to their use and waits for each with lgkmcnt(0); with
+                // it it retires them with counted waits -- tests/test_screen_i8_schedule.py)
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int t = 0; t < NQT; ++t) {
-                    const i8s_i32x4 b_lo = *reinterpret_cast<const i8s_i32x4 *>(qlo_lds + ((t * KSTEPS + gi) * 64 + lane) * 16);
                     ah[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_cur, qh[t][gi], ah[t], 0, 0, 0);
-                    al[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_cur, b_lo, al[t], 0, 0, 0);
+                    al[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_cur, b_cur[t], al[t], 0, 0, 0);
                 }
+#pragma unroll
+                for (int t = 0; t < NQT; ++t) b_cur[t] = b_nxt[t];
 #else
                 asm volatile("" : : "v"(a_cur));
 #endif
@@ -429,10 +458,6 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
                 if constexpr (g == 3) {
                     wr_off = rd_off;
                     rd_off = rd_off + I8S_SLOT_BYTES == RING ? 0u : rd_off + I8S_SLOT_BYTES;
-                    if constexpr (kc + 1 < NKC) {
-                        i8s_wait<4 * (P - 1)>();
-                        a_nxt = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + rd_off + frag_off[0]);
-                    }
                 }
                 a_cur = a_nxt;
             });
@@ -473,6 +498,11 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
                 for (int r = 0; r < 16; ++r)
                     if ((uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * lh >= left) m &= ~(0x00010001u << r);
             }
+#if defined(I8S_NO_DMA) || defined(I8S_NO_MFMA)
+            // (ablation builds: every score is 0 and every pair would pass, where the product passes < 1 % of them: nothing
+            // survives here, and the test above still runs -- the compiler cannot tell)
+            if (seg_cap != 0xFFFFFFFFu) m = 0u;
+#endif
             auto lower_key = [&](int t, int r, uint32_t row) -> uint64_t { // (survivors only: the metadata read again)
                 float sr[4], er[4];
                 meta4(r >> 2, sr, er);
