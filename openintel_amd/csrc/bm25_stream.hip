@@ -45,6 +45,7 @@
 
 #include "oi_device.h"
 #include "oi_internal.h"
+#include "oi_lds_dma.h"
 
 #define BS_BLOCK OI_BM25_BLOCK_DOCS
 #define BS_FINE OI_BM25_FINE_DOCS
@@ -90,9 +91,6 @@ struct BsArgs {
     const uint2 *attrs;
 };
 
-__device__ __forceinline__ uint32_t bs_lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)p;
-}
 __device__ __forceinline__ uint32_t bs_rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ uint32_t bs_readlane(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
 
@@ -128,16 +126,6 @@ __device__ __forceinline__ void bs_wait_vm(uint32_t y) {
     case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
     default: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
     }
-}
-// inclusive scan over the 64 lanes (the DPP sequence LLVM's atomic optimizer emits for gfx9: no LDS traffic)
-__device__ __forceinline__ uint32_t bs_incl_scan(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
-    return v;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -205,7 +193,7 @@ __global__ __launch_bounds__(BS_WPB * 64) void bm25_stream_kernel(const BsArgs a
     const uint4 *ring16 = reinterpret_cast<const uint4 *>(wl + L::OFF_RING);
     uint64_t *s_cum = reinterpret_cast<uint64_t *>(smem + BS_WPB * L::WAVE);
     uint32_t *s_tau = reinterpret_cast<uint32_t *>(s_cum + BS_MAX_Q + 2); // the queries' thresholds (fixed for the launch)
-    const uint32_t ring_w = bs_lds_addr(wl + L::OFF_RING), desc_w = bs_lds_addr(desc);
+    const uint32_t ring_w = oi_lds_addr(wl + L::OFF_RING), desc_w = oi_lds_addr(desc);
 
     // ---- prologue: the plan's prefix and the thresholds in LDS, this wave's maps and accumulators zero
     for (uint32_t i = tid; i <= a.nq; i += BS_WPB * 64) s_cum[i] = a.cum[i];
@@ -275,7 +263,7 @@ __global__ __launch_bounds__(BS_WPB * 64) void bm25_stream_kernel(const BsArgs a
             }
             uint32_t mine = 0;
             for (int i = 0; i < 4; ++i) mine += hist[255u - (lane * 4u + i)];
-            const uint32_t incl = bs_incl_scan(mine);
+            const uint32_t incl = oi_wave_incl_scan(mine);
             const unsigned long long ball = __ballot(incl >= kk);
             const uint32_t owner = ball ? (uint32_t)__builtin_ctzll(ball) : 63u;
             uint32_t cum = incl - mine, d = 255u - lane * 4u;
@@ -310,7 +298,7 @@ __global__ __launch_bounds__(BS_WPB * 64) void bm25_stream_kernel(const BsArgs a
     // stage[] (and accdoc[] / acc[] below) are exchanges between the lanes of one wave through LDS, like head[]: a lane reads
     // what OTHER lanes wrote.  The compiler barriers keep every such read behind the writes it depends on and in front of the
     // next round's writes (with plain accesses only, that rested on hipcc never forwarding a lane's own earlier store
-    // to its load here -- the transformation that caused round 4's fault at head[]; cosine_prefilter.hip's PF_FLUSH does the same).
+    // to its load here -- the transformation that caused round 4's fault at head[]; OI_STAGE_FLUSH_TO_POOL does the same).
     auto flush64 = [&]() __attribute__((always_inline)) { // 64 staged keys leave for the segment
         if (out_n + 64u > seg_cap) prune();
         asm volatile("" ::: "memory");
@@ -417,7 +405,7 @@ __global__ __launch_bounds__(BS_WPB * 64) void bm25_stream_kernel(const BsArgs a
         uint32_t ex[WPL];
 #pragma unroll
         for (uint32_t k = 0; k < WPL; ++k) { ex[k] = run; run += (uint32_t)__popc(mwd[k]); }
-        const uint32_t incl = bs_incl_scan(run);
+        const uint32_t incl = oi_wave_incl_scan(run);
         const uint32_t base = incl - run;
         t_M = bs_readlane(incl, 63);
         if (t_M) {
@@ -494,7 +482,7 @@ __global__ __launch_bounds__(BS_WPB * 64) void bm25_stream_kernel(const BsArgs a
         const uint32_t s = (NWB == 1 || win == 0) ? c0 : c1, e = NWB == 1 ? c2 : (win == 0 ? c1 : c2);
         const uint32_t cs = s & ~1u;
         const uint32_t n = e > s ? (e - cs + 127u) >> 7 : 0u; // chunks of run `lane`
-        const uint32_t incl = bs_incl_scan(n), excl = incl - n;
+        const uint32_t incl = oi_wave_incl_scan(n), excl = incl - n;
         t.C = bs_readlane(incl, 63);
         t.slow = long_query || t.C > 64u;
         t.pos = 0; t.lohi = 0; t.idf = 0;

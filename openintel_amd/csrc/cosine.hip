@@ -289,12 +289,7 @@ int oi_launch_cosine_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, u
     for (uint32_t q0 = 0; q0 < n_queries_padded; q0 += 64) {
         const uint32_t left = n_queries_padded - q0;
         const uint32_t nq_here = (n_queries - q0) < 64 ? (n_queries - q0) : 64;
-        PoolView p = pool;
-        p.keys += (uint64_t)q0 * pool.stride;
-        p.carry_cnt += q0;
-        p.seg_cnt += (uint64_t)q0 * pool.seg_cnt_stride;
-        p.tau_keys += q0;
-        if (p.filt) p.filt += q0;
+        const PoolView p = pool.for_queries(q0);
         const float *qptr = d_queries + (uint64_t)q0 * dim;
         if (ksplit && ctx->cosine_mode == OI_COSINE_SPLIT && oi_cosine_split_supported(dim) && !p.filt) { // (filtered: the K-split)
             OI_CHECK(oi_launch_cosine_split(ctx, rows, row_begin, row_end, dim, qptr, nq_here, doc_id_base, p));

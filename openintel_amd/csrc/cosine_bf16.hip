@@ -14,7 +14,7 @@
 //     waves never meet -- no cross-wave sum, no barrier after the prologue;
 //   * each wave streams its tiles through its own LDS ring of 4 KiB slots (32 rows x 128 B = 64 bf16
 //     of K) with buffer_load ... lds, P slots ahead, ordered by counted s_waitcnt vmcnt, the prefetch
-//     running across tile boundaries (same DMA, descriptor and swizzle as cosine_ksplit.hip);
+//     running across tile boundaries (oi_lds_dma.h);
 //   * a lane's A fragment (8 consecutive bf16 of its row) is one conflict-free ds_read_b128 per MFMA
 //     group; the filter + pool append come straight out of the accumulators (the 32x32 D layout maps
 //     a lane to one query column), into this workgroup's private pool segment.
@@ -25,6 +25,7 @@
 
 #include "oi_device.h"
 #include "oi_internal.h"
+#include "oi_lds_dma.h"
 
 #ifndef OI_TILE_CONTIG
 #define OI_TILE_CONTIG 0
@@ -38,63 +39,11 @@
 
 typedef float cb_f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 cb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t cb_u32x4 __attribute__((ext_vector_type(4)));
 
 #define CB_TILE_ROWS 32
 #define CB_SLOT_K 64                 // bf16 of K per ring slot row (128 B)
 #define CB_SLOT_BYTES (CB_TILE_ROWS * 128)
 
-__device__ __forceinline__ uint32_t cb_lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)p;
-}
-__device__ __forceinline__ cb_u32x4 cb_make_srd(const uint16_t *base, uint64_t bytes) {
-    const uint64_t b = (uint64_t)base;
-    cb_u32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    r[1] = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32) & 0xFFFFu); // stride 0
-    r[2] = __builtin_amdgcn_readfirstlane((uint32_t)(bytes > 0xFFFFFFFFull ? 0xFFFFFFFFull : bytes));
-    r[3] = 0x00020000u;
-    return r;
-}
-// One 1-KiB LDS-DMA piece (8 rows x 128 B).  Lanes past the descriptor's end read as zero: the ragged
-// last tile needs no clamping.  hipcc does not see these loads: they are ordered by cb_wait<N>().
-// STREAM = true: the once-read policy of oi_device.h (non-temporal).  STREAM = false: the default cache policy -- the quad
-// kernel's sibling workgroups (below) read every tile TWICE on one XCD and want the first read to stay in its L2.
-template <bool STREAM = true>
-__device__ __forceinline__ void cb_issue_piece(const cb_u32x4 &srd, uint32_t voff, uint32_t soff, uint32_t lds_dst,
-                                               bool skip) {
-    if (skip) return;
-    uint32_t keep;
-    const uint32_t d = __builtin_amdgcn_readfirstlane(lds_dst);
-    const uint32_t so = __builtin_amdgcn_readfirstlane(soff);
-    if constexpr (STREAM)
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %4\n\t"
-            "s_nop 0\n\t"
-            "buffer_load_dwordx4 %1, %2, %3 offen " OI_DMA_NT "lds\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(voff), "s"(srd), "s"(so), "s"(d)
-            : "memory");
-    else
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %4\n\t"
-            "s_nop 0\n\t"
-            "buffer_load_dwordx4 %1, %2, %3 offen lds\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(voff), "s"(srd), "s"(so), "s"(d)
-            : "memory");
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void cb_static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        cb_static_for<I + 1, N>(f);
-    }
-}
 // MFMA with the B operand named as AGPRs.  gfx950's matrix instructions take srcA / srcB from either half of the unified
 // register file, but the builtin lets the compiler choose: with more than 256 registers of resident queries it parks the
 // excess in AGPRs as SPILL slots and copies four registers back with v_accvgpr_read in front of every MFMA that needs them
@@ -110,11 +59,6 @@ __device__ __forceinline__ void cb_mfma_agpr_first(cb_f32x16 &acc, const cb_bf16
 }
 __device__ __forceinline__ void cb_mfma_drain() { // >= 19 wait states: the last MFMA's result is readable by any instruction
     asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void cb_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 template <int D, int NQT, bool FILT>
@@ -172,7 +116,7 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_filter(
             const uint32_t prow = 8 * m + (lane >> 3);
             voff[m] = prow * (uint32_t)(D * 2) + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
         }
-        const uint32_t ring_w = cb_lds_addr(ring) + w * (NBUF * CB_SLOT_BYTES);
+        const uint32_t ring_w = oi_lds_addr(ring) + w * (NBUF * CB_SLOT_BYTES);
         const unsigned char *ring_rd = ring + w * (NBUF * CB_SLOT_BYTES);
         // fragment read address inside a slot: row li, logical 16-B column (2g + lh)
         uint32_t frag_off[4];
@@ -182,9 +126,9 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_filter(
         auto tile_row0 = [&](uint64_t ti) { return row_begin + (first + ti * stride) * (uint64_t)CB_TILE_ROWS; };
         auto tile_srd = [&](uint64_t ti) {
             const uint64_t r0 = tile_row0(ti);
-            return cb_make_srd(rows + r0 * D, (row_end - r0) * (uint64_t)(D * 2));
+            return oi_make_srd(rows + r0 * D, (row_end - r0) * (uint64_t)(D * 2));
         };
-        cb_u32x4 cur = tile_srd(0), nxt = tile_srd(my_nt > 1 ? 1 : 0);
+        oi_u32x4 cur = tile_srd(0), nxt = tile_srd(my_nt > 1 ? 1 : 0);
         // Every load hipcc knows about (queries, thresholds) is retired HERE, with a wait it models:
         // otherwise it re-waits for them inside the tile loop and drains the DMA ring.
         __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only
@@ -192,7 +136,7 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_filter(
         for (int kc = 0; kc < P; ++kc) // prologue: slots 0..P-1 of the first tile
 #pragma unroll
             for (int m = 0; m < 4; ++m)
-                cb_issue_piece(cur, voff[m], kc * 128, ring_w + (kc % NBUF) * CB_SLOT_BYTES + m * 1024, false);
+                oi_dma_piece(cur, voff[m], kc * 128, ring_w + (kc % NBUF) * CB_SLOT_BYTES + m * 1024);
 
         for (uint64_t ti = 0; ti < my_nt; ++ti) {
             const bool has_next_tile = ti + 1 < my_nt;
@@ -206,9 +150,9 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_filter(
             // fragment, NQT MFMAs on the current one, and DMA piece g of slot kc + P into the buffer slot
             // kc - 1 has vacated; at g == 3 the next fragment is (kc + 1, 0), behind the counted wait that
             // retires slot kc + 1 (P - 1 younger slots stay in flight).
-            cb_wait<4 * (P - 1)>();
+            oi_wait_vm<4 * (P - 1)>();
             cb_bf16x8 a_cur = *reinterpret_cast<const cb_bf16x8 *>(ring_rd + frag_off[0]);
-            cb_static_for<0, NKC * 4>([&](auto gi_) {
+            oi_static_for<0, NKC * 4>([&](auto gi_) {
                 constexpr int gi = decltype(gi_)::value;
                 constexpr int kc = gi / 4, g = gi % 4;
                 constexpr int sn = kc + P; // slot refilled during this slot's groups
@@ -219,13 +163,13 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_filter(
                 for (int t = 0; t < NQT; ++t)
                     acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur, qreg[t][gi], acc[t], 0, 0, 0);
                 if constexpr (sn < NKC)
-                    cb_issue_piece(cur, voff[g], sn * 128, ring_w + (sn % NBUF) * CB_SLOT_BYTES + g * 1024, false);
+                    oi_dma_piece(cur, voff[g], sn * 128, ring_w + (sn % NBUF) * CB_SLOT_BYTES + g * 1024);
                 else
-                    cb_issue_piece(nxt, voff[g], (sn - NKC) * 128, ring_w + (sn % NBUF) * CB_SLOT_BYTES + g * 1024,
+                    oi_dma_piece(nxt, voff[g], (sn - NKC) * 128, ring_w + (sn % NBUF) * CB_SLOT_BYTES + g * 1024,
                                    !has_next_tile);
                 if constexpr (g == 3 && kc + 1 < NKC) {
-                    if (kc + P < NKC || has_next_tile) cb_wait<4 * (P - 1)>();
-                    else cb_wait<4 * (NKC - 2 - kc)>();
+                    if (kc + P < NKC || has_next_tile) oi_wait_vm<4 * (P - 1)>();
+                    else oi_wait_vm<4 * (NKC - 2 - kc)>();
                     a_nxt = *reinterpret_cast<const cb_bf16x8 *>(ring_rd + ((kc + 1) % NBUF) * CB_SLOT_BYTES + frag_off[0]);
                 }
                 a_cur = a_nxt;
@@ -325,7 +269,7 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_pair(
         const uint32_t prow = 8 * m + (lane >> 3);
         voff[m] = prow * (uint32_t)(D * 2) + kh * (uint32_t)(KH * 2) + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
     }
-    const uint32_t ring_w = cb_lds_addr(ring) + w * (NBUF * CB_SLOT_BYTES);
+    const uint32_t ring_w = oi_lds_addr(ring) + w * (NBUF * CB_SLOT_BYTES);
     const unsigned char *ring_rd = ring + w * (NBUF * CB_SLOT_BYTES);
     uint32_t frag_off[4];
 #pragma unroll
@@ -334,16 +278,16 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_pair(
     auto tile_row0 = [&](uint64_t ti) { return row_begin + (first + ti * stride) * (uint64_t)CB_TILE_ROWS; };
     auto tile_srd = [&](uint64_t ti) {
         const uint64_t r0 = tile_row0(ti < my_nt ? ti : 0);
-        return cb_make_srd(rows + r0 * D, (row_end - r0) * (uint64_t)(D * 2));
+        return oi_make_srd(rows + r0 * D, (row_end - r0) * (uint64_t)(D * 2));
     };
-    cb_u32x4 cur = tile_srd(0), nxt = tile_srd(1);
+    oi_u32x4 cur = tile_srd(0), nxt = tile_srd(1);
     __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only: retire every load hipcc knows about, here
     if (my_nt) {
 #pragma unroll
         for (int kc = 0; kc < P; ++kc)
 #pragma unroll
             for (int m = 0; m < 4; ++m)
-                cb_issue_piece(cur, voff[m], kc * 128, ring_w + (kc % NBUF) * CB_SLOT_BYTES + m * 1024, false);
+                oi_dma_piece(cur, voff[m], kc * 128, ring_w + (kc % NBUF) * CB_SLOT_BYTES + m * 1024);
     }
 
     for (uint64_t ti = 0; ti < trips; ++ti) {
@@ -355,9 +299,9 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_pair(
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
         if (active) {
-            cb_wait<4 * (P - 1)>();
+            oi_wait_vm<4 * (P - 1)>();
             cb_bf16x8 a_cur = *reinterpret_cast<const cb_bf16x8 *>(ring_rd + frag_off[0]);
-            cb_static_for<0, NKC * 4>([&](auto gi_) {
+            oi_static_for<0, NKC * 4>([&](auto gi_) {
                 constexpr int gi = decltype(gi_)::value;
                 constexpr int kc = gi / 4, g = gi % 4;
                 constexpr int sn = kc + P;
@@ -368,13 +312,13 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_pair(
                 for (int t = 0; t < NQT; ++t)
                     acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur, qreg[t][gi], acc[t], 0, 0, 0);
                 if constexpr (sn < NKC)
-                    cb_issue_piece(cur, voff[g], sn * 128, ring_w + (sn % NBUF) * CB_SLOT_BYTES + g * 1024, false);
+                    oi_dma_piece(cur, voff[g], sn * 128, ring_w + (sn % NBUF) * CB_SLOT_BYTES + g * 1024);
                 else
-                    cb_issue_piece(nxt, voff[g], (sn - NKC) * 128, ring_w + (sn % NBUF) * CB_SLOT_BYTES + g * 1024,
+                    oi_dma_piece(nxt, voff[g], (sn - NKC) * 128, ring_w + (sn % NBUF) * CB_SLOT_BYTES + g * 1024,
                                    !has_next_tile);
                 if constexpr (g == 3 && kc + 1 < NKC) {
-                    if (kc + P < NKC || has_next_tile) cb_wait<4 * (P - 1)>();
-                    else cb_wait<4 * (NKC - 2 - kc)>();
+                    if (kc + P < NKC || has_next_tile) oi_wait_vm<4 * (P - 1)>();
+                    else oi_wait_vm<4 * (NKC - 2 - kc)>();
                     a_nxt = *reinterpret_cast<const cb_bf16x8 *>(ring_rd + ((kc + 1) % NBUF) * CB_SLOT_BYTES + frag_off[0]);
                 }
                 a_cur = a_nxt;
@@ -507,7 +451,7 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_quad(
         const uint32_t prow = 8 * m + (lane >> 3);
         voff[m] = prow * (uint32_t)(D * 2) + w * (uint32_t)(KQ * 2) + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
     }
-    const uint32_t ring_w = cb_lds_addr(ring) + w * RING;
+    const uint32_t ring_w = oi_lds_addr(ring) + w * RING;
     const unsigned char *ring_rd = ring + w * RING;
     uint32_t frag_off[4];
 #pragma unroll
@@ -516,17 +460,17 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_quad(
     auto tile_row0 = [&](uint64_t ti) { return row_begin + (first + ti * stride) * (uint64_t)CB_TILE_ROWS; };
     auto tile_srd = [&](uint64_t ti) { // past this workgroup's last tile: an EMPTY descriptor (loads return zeros)
         const uint64_t r0 = tile_row0(ti < my_nt ? ti : 0);
-        return cb_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 2) : 0ull);
+        return oi_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 2) : 0ull);
     };
-    cb_u32x4 s0 = tile_srd(0), s1 = tile_srd(1), s2 = tile_srd(2);
+    oi_u32x4 s0 = tile_srd(0), s1 = tile_srd(1), s2 = tile_srd(2);
     __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only: retire every load hipcc knows about, here
     if (my_nt) {
-        cb_static_for<0, P>([&](auto j_) { // prologue: logical slots 0..P-1 (tile j / NKC, slot j % NKC) into ring slots 0..P-1
+        oi_static_for<0, P>([&](auto j_) { // prologue: logical slots 0..P-1 (tile j / NKC, slot j % NKC) into ring slots 0..P-1
             constexpr int j = decltype(j_)::value;
             constexpr int tj = j / NKC, kj = j % NKC;
 #pragma unroll
             for (int m = 0; m < 4; ++m)
-                cb_issue_piece<STREAM>(tj == 0 ? s0 : s1, voff[m], kj * 128, ring_w + j * CB_SLOT_BYTES + m * 1024, false);
+                oi_dma_piece<STREAM>(tj == 0 ? s0 : s1, voff[m], kj * 128, ring_w + j * CB_SLOT_BYTES + m * 1024);
         });
     }
     // ring offsets (bytes, wave-uniform): the slot being consumed, and the one vacated before it = the refill target
@@ -592,7 +536,7 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_quad(
     // share the tiles).  The ring is continuous across tiles, so the next tile's first slot is read during this tile's last.
     cb_bf16x8 fr_cur[4], fr_nxt[4];
     if (my_nt) {
-        cb_wait<4 * (P - 1)>();
+        oi_wait_vm<4 * (P - 1)>();
 #pragma unroll
         for (int g = 0; g < 4; ++g) fr_cur[g] = *reinterpret_cast<const cb_bf16x8 *>(ring_rd + rd_off + frag_off[g]);
     }
@@ -604,7 +548,7 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_quad(
             // DMA piece g of logical slot kc + P (one or two tiles ahead; an empty descriptor past the last tile: the refill
             // ALWAYS issues, so every counted wait is the same constant) into the slot vacated last (wr_off).
             cb_f32x4 pp[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-            cb_static_for<0, NKC * 4>([&](auto gi_) {
+            oi_static_for<0, NKC * 4>([&](auto gi_) {
                 constexpr int gi = decltype(gi_)::value;
                 constexpr int kc = gi / 4, g = gi % 4;
                 constexpr int sn = kc + P;
@@ -612,7 +556,7 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_quad(
                 constexpr int rb = gi / 4, ej = gi % 4; // the previous tile's epilogue: register block rb, step ej
                 if constexpr (g == 0) {
                     const uint32_t nx_off = rd_off + CB_SLOT_BYTES == RING ? 0u : rd_off + CB_SLOT_BYTES;
-                    cb_wait<4 * (P - 2)>();
+                    oi_wait_vm<4 * (P - 2)>();
 #pragma unroll
                     for (int h = 0; h < 4; ++h) fr_nxt[h] = *reinterpret_cast<const cb_bf16x8 *>(ring_rd + nx_off + frag_off[h]);
                 }
@@ -624,7 +568,7 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_quad(
                     if constexpr (gi == 0) cb_mfma_agpr_first(acc[t], fr_cur[g], qreg[t][gi]);
                     else cb_mfma_agpr(acc[t], fr_cur[g], qreg[t][gi]);
                 }
-                cb_issue_piece<STREAM>(tn == 1 ? s1 : s2, voff[g], kn * 128, ring_w + wr_off + g * 1024, false);
+                oi_dma_piece<STREAM>(tn == 1 ? s1 : s2, voff[g], kn * 128, ring_w + wr_off + g * 1024);
                 if constexpr ((DBG == 0 || DBG == 3) && ej == 3) { // ... block rb summed, filtered, appended
                     if (have_prev) finish_block(std::integral_constant<int, rb>{}, pp);
                 }
@@ -669,9 +613,9 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_quad(
         s1 = s2;
         s2 = tile_srd(ti + 3);
     }
-    cb_wait<0>(); // the zero-filling refills issued past the last tile have landed before the LDS goes back
+    oi_wait_vm<0>(); // the zero-filling refills issued past the last tile have landed before the LDS goes back
     if ((DBG == 0 || DBG == 3) && have_prev) // the last tile's epilogue has no MFMA loop to hide in
-        cb_static_for<0, 4>([&](auto rb_) {
+        oi_static_for<0, 4>([&](auto rb_) {
             constexpr int rb = decltype(rb_)::value;
             cb_f32x4 p[3];
 #pragma unroll
@@ -706,19 +650,7 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_quad(
 #ifndef CQ_NHB
 #define CQ_NHB 4
 #endif
-#define CQ_STAGE 256
-#define CQ_STAGE_FLUSH 64u
-#define CQ_LDS (CQ_NHB * CQ_HT_BYTES + 128 * 4 + 4 * CQ_STAGE * 12)
-
-__device__ __forceinline__ uint32_t cq_incl_scan(uint32_t v) { // wave-wide inclusive prefix sum (DPP, no LDS)
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-    return v;
-}
+#define CQ_LDS (CQ_NHB * CQ_HT_BYTES + 128 * 4 + OI_STAGE_LDS)
 
 template <int SIB>
 __global__ __launch_bounds__(256, 1) void cosine_bf16_qsplit(
@@ -738,8 +670,8 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_qsplit(
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6);                 // the query tile of this wave
     const uint32_t li = lane & 31, lh = lane >> 5;
-    uint64_t *stage_keys = reinterpret_cast<uint64_t *>(smem + RING + 512) + w * CQ_STAGE;
-    uint32_t *stage_q = reinterpret_cast<uint32_t *>(smem + RING + 512 + 4 * CQ_STAGE * 8) + w * CQ_STAGE;
+    uint64_t *stage_keys = reinterpret_cast<uint64_t *>(smem + RING + 512) + w * OI_STAGE;
+    uint32_t *stage_q = reinterpret_cast<uint32_t *>(smem + RING + 512 + 4 * OI_STAGE * 8) + w * OI_STAGE;
     uint32_t st_head = 0, st_n = 0;
 
     uint32_t half = 0, wg = blockIdx.x, n_wg = gridDim.x; // siblings: see cosine_bf16_quad
@@ -782,7 +714,7 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_qsplit(
         const uint32_t prow = 8 * m + (lane >> 3);
         voff[m] = prow * (uint32_t)(D * 2) + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
     }
-    const uint32_t ring_w = cb_lds_addr(ring);
+    const uint32_t ring_w = oi_lds_addr(ring);
     uint32_t frag_off[4]; // fragment of MFMA group g of a slot: row li, logical 16-B column 2 g + lh
 #pragma unroll
     for (int g = 0; g < 4; ++g) frag_off[g] = li * 128 + (((2 * g + lh) ^ ((li >> 1) & 7)) << 4);
@@ -790,16 +722,16 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_qsplit(
     auto tile_row0 = [&](uint64_t ti) { return row_begin + (first + ti * stride) * (uint64_t)CB_TILE_ROWS; };
     auto tile_srd = [&](uint64_t ti) { // past this workgroup's last tile: an EMPTY descriptor (loads return zeros)
         const uint64_t r0 = tile_row0(ti < my_nt ? ti : 0);
-        return cb_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 2) : 0ull);
+        return oi_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 2) : 0ull);
     };
     // this wave's pieces of one half tile (slots 2 w and 2 w + 1): K half `hh` of the tile described by `srd`
-    auto issue_slot = [&](const cb_u32x4 &srd, uint32_t hh, uint32_t jj, uint32_t buf_off) __attribute__((always_inline)) {
+    auto issue_slot = [&](const oi_u32x4 &srd, uint32_t hh, uint32_t jj, uint32_t buf_off) __attribute__((always_inline)) {
         const uint32_t j = 2u * w + jj;
 #pragma unroll
         for (int m = 0; m < 4; ++m)
-            cb_issue_piece<STREAM>(srd, voff[m], hh * 1024u + j * 128u, ring_w + buf_off + j * CB_SLOT_BYTES + m * 1024, false);
+            oi_dma_piece<STREAM>(srd, voff[m], hh * 1024u + j * 128u, ring_w + buf_off + j * CB_SLOT_BYTES + m * 1024);
     };
-    cb_u32x4 s0 = tile_srd(0), s1 = tile_srd(1), s2 = tile_srd(2);
+    oi_u32x4 s0 = tile_srd(0), s1 = tile_srd(1), s2 = tile_srd(2);
     __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only: retire every load hipcc knows about, here
     __syncthreads();                    // seg_fill is zero before any wave appends
     // The slot stream is continuous over half tiles and tiles.  Fragments are read THREE slots ahead of the matrix pipe (a slot
@@ -811,12 +743,12 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_qsplit(
     // by the barrier's lgkmcnt(0), completed -- its buffer is refilled with half tile h + NHB right after the barrier.
     cb_bf16x8 fr[4][4]; // fragments of slots g, g + 1, g + 2 (and the one being read): slot g lives in fr[g % 4]
     if (my_nt) {
-        cb_static_for<0, NHB>([&](auto h_) { // prologue: half tiles 0 .. NHB - 1 (tile h / 2, K half h % 2) fill the ring
+        oi_static_for<0, NHB>([&](auto h_) { // prologue: half tiles 0 .. NHB - 1 (tile h / 2, K half h % 2) fill the ring
             constexpr int h = decltype(h_)::value;
             issue_slot(h / 2 == 0 ? s0 : s1, h % 2, 0, h * CQ_HT_BYTES);
             issue_slot(h / 2 == 0 ? s0 : s1, h % 2, 1, h * CQ_HT_BYTES);
         });
-        cb_wait<8 * (NHB - 1)>(); // this wave's pieces of half tile 0 ...
+        oi_wait_vm<8 * (NHB - 1)>(); // this wave's pieces of half tile 0 ...
     }
     __syncthreads();              // ... and everyone's
     if (my_nt) {
@@ -829,13 +761,13 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_qsplit(
 
     for (uint64_t ti = 0; ti < my_nt; ++ti) {
         cb_f32x16 acc;
-        cb_static_for<0, 2>([&](auto hh_) {
+        oi_static_for<0, 2>([&](auto hh_) {
             constexpr int hh = decltype(hh_)::value;
             const uint32_t nx_off = rd_off + CQ_HT_BYTES == RING ? 0u : rd_off + CQ_HT_BYTES;
-            cb_static_for<0, CQ_HT_SLOTS>([&](auto j_) {
+            oi_static_for<0, CQ_HT_SLOTS>([&](auto j_) {
                 constexpr int j = decltype(j_)::value;
                 if constexpr (j == 5) {
-                    cb_wait<8 * (NHB - 2)>(); // this wave's pieces of the NEXT half tile are in LDS ...
+                    oi_wait_vm<8 * (NHB - 2)>(); // this wave's pieces of the NEXT half tile are in LDS ...
                     __syncthreads();          // ... and everyone's; everyone has finished reading THIS half tile's buffer
                 }
 #if defined(CQ_NOREADS) // (variant builds, timings only: the DMA stream and the barriers alone -- no fragment reads, no matrix pipe)
@@ -892,32 +824,21 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_qsplit(
         }
         if (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull) {
             const uint32_t cnt = (uint32_t)__builtin_popcount(m);
-            const uint32_t incl = cq_incl_scan(cnt);
+            const uint32_t incl = oi_wave_incl_scan(cnt);
             const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            if (total <= CQ_STAGE - CQ_STAGE_FLUSH) { // sparse tile: staged in LDS, 64 keys leave with one store instruction
+            if (total <= OI_STAGE - OI_STAGE_FLUSH) { // sparse tile: staged in LDS, 64 keys leave with one store instruction
                 uint32_t idx = st_head + st_n + incl - cnt;
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
                     if (m & (1u << r)) {
                         const uint32_t row = (uint32_t)row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        stage_keys[idx & (CQ_STAGE - 1)] = oi_rank_key(acc[r], doc_id_base + row);
-                        stage_q[idx & (CQ_STAGE - 1)] = my_q;
+                        stage_keys[idx & (OI_STAGE - 1)] = oi_rank_key(acc[r], doc_id_base + row);
+                        stage_q[idx & (OI_STAGE - 1)] = my_q;
                         ++idx;
                     }
                 st_n += total;
-                while (st_n >= CQ_STAGE_FLUSH) {
-                    asm volatile("" ::: "memory");
-                    {
-                        const uint32_t i_ = (st_head + lane) & (CQ_STAGE - 1);
-                        const uint64_t key_ = stage_keys[i_];
-                        const uint32_t q_ = stage_q[i_];
-                        const uint32_t pos_ = atomicAdd(&seg_fill[q_], 1u);
-                        if (pos_ < seg_cap) my_seg[(uint64_t)q_ * pool_stride + pos_] = key_;
-                        else *overflow = 1u;
-                    }
-                    asm volatile("" ::: "memory");
-                    st_head = (st_head + CQ_STAGE_FLUSH) & (CQ_STAGE - 1);
-                    st_n -= CQ_STAGE_FLUSH;
+                while (st_n >= OI_STAGE_FLUSH) {
+                    OI_STAGE_FLUSH_TO_POOL(OI_STAGE_FLUSH);
                 }
             } else { // dense tile (no threshold yet): straight to the pool
                 uint32_t pos = atomicAdd(&seg_fill[my_q], cnt);
@@ -937,18 +858,9 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_qsplit(
         s2 = tile_srd(ti + 3);
     }
     if (st_n) { // the staged rest
-        asm volatile("" ::: "memory");
-        if (lane < st_n) {
-            const uint32_t i_ = (st_head + lane) & (CQ_STAGE - 1);
-            const uint64_t key_ = stage_keys[i_];
-            const uint32_t q_ = stage_q[i_];
-            const uint32_t pos_ = atomicAdd(&seg_fill[q_], 1u);
-            if (pos_ < seg_cap) my_seg[(uint64_t)q_ * pool_stride + pos_] = key_;
-            else *overflow = 1u;
-        }
-        asm volatile("" ::: "memory");
+        OI_STAGE_FLUSH_TO_POOL(st_n);
     }
-    cb_wait<0>(); // the zero-filling refills issued past the last tile have landed before the LDS goes back
+    oi_wait_vm<0>(); // the zero-filling refills issued past the last tile have landed before the LDS goes back
     __syncthreads();
     if (tid < 128 && tid < n_queries) {
         const uint32_t c = seg_fill[tid];
@@ -1114,12 +1026,7 @@ int oi_launch_cosine_bf16_chunk(oi_ctx *ctx, const uint16_t *rows, uint64_t row_
         if (siblings) group = 256u;
         const uint32_t nq_here = std::min(group, left);
         const uint32_t nqt = (nq_here + 31u) / 32u; // query tiles of 32 in this launch
-        PoolView p = pool;
-        p.keys += (uint64_t)q0 * pool.stride;
-        p.carry_cnt += q0;
-        p.seg_cnt += (uint64_t)q0 * pool.seg_cnt_stride;
-        p.tau_keys += q0;
-        if (p.filt) p.filt += q0;
+        const PoolView p = pool.for_queries(q0);
         const uint16_t *qptr = qb.as<uint16_t>() + (uint64_t)q0 * dim;
 #define CB_SOLO(DD, T) OI_CHECK((launch_bf16<DD, T>(ctx, rows, row_begin, row_end, qptr, nq_here, doc_id_base, p)))
 #define CB_PAIR(DD, T) OI_CHECK((launch_bf16_pair<DD, T>(ctx, rows, row_begin, row_end, qptr, nq_here, doc_id_base, p)))

@@ -28,6 +28,7 @@
 
 #include "oi_device.h"
 #include "oi_internal.h"
+#include "oi_lds_dma.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -36,12 +37,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define KS_CHUNK_K 32                       // floats of K per ring slot row (128 B)
 #define KS_SLOT_BYTES (KS_TILE_ROWS * KS_CHUNK_K * 4) // 4 KiB
 
-__device__ __forceinline__ uint32_t lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)p;
-}
-
-// Four 1-KiB LDS-DMA pieces = one ring slot.  hipcc does not see these loads: they are ordered
-// by ks_wait<N>() below (cdna_hip_programming.md section 5.7).  M0 carries the LDS destination.
+// Four 1-KiB LDS-DMA pieces = one ring slot, from 64-bit per-lane addresses (the contract: oi_lds_dma.h).  The tile
+// loops issue oi_dma_piece instead, one piece per MFMA group: buffer_load ... lds with a wave-uniform descriptor and a
+// 32-bit per-lane offset is short enough to hide under a 64-cycle matrix instruction (a global_load_lds is not -- it
+// cost ~80 exposed cycles per piece here).
 __device__ __forceinline__ void ks_issue_slot(const float *p0, const float *p1, const float *p2,
                                               const float *p3, uint32_t lds_dst, bool skip = false) {
     if (skip) return;
@@ -66,48 +65,6 @@ __device__ __forceinline__ void ks_issue_slot(const float *p0, const float *p1, 
         : "=&s"(keep)
         : "v"(p0), "v"(p1), "v"(p2), "v"(p3), "s"(d0), "s"(d1), "s"(d2), "s"(d3)
         : "memory");
-}
-// One 1-KiB LDS-DMA piece (8 rows x 128 B), issued one per MFMA group.  buffer_load ... lds with a
-// wave-uniform descriptor and a 32-bit per-lane offset: its issue is short enough to hide under a
-// 64-cycle matrix instruction (a global_load_lds with 64-bit per-lane addresses is not -- it cost
-// ~80 exposed cycles per piece here).  Lanes past the descriptor's end read as zero: the ragged
-// last tile needs no clamping.
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4 ks_make_srd(const float *base, uint64_t bytes) {
-    const uint64_t b = (uint64_t)base;
-    u32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    r[1] = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32) & 0xFFFFu); // stride 0
-    r[2] = __builtin_amdgcn_readfirstlane((uint32_t)(bytes > 0xFFFFFFFFull ? 0xFFFFFFFFull : bytes));
-    r[3] = 0x00020000u;
-    return r;
-}
-__device__ __forceinline__ void ks_issue_piece(const u32x4 &srd, uint32_t voff, uint32_t soff, uint32_t lds_dst,
-                                               bool skip) {
-    if (skip) return;
-    uint32_t keep;
-    const uint32_t d = __builtin_amdgcn_readfirstlane(lds_dst);
-    const uint32_t so = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %4\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %2, %3 offen " OI_DMA_NT "lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(srd), "s"(so), "s"(d)
-        : "memory");
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void ks_static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        ks_static_for<I + 1, N>(f);
-    }
-}
-template <int N>
-__device__ __forceinline__ void ks_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 // keep a value alive without cost (diagnostic builds).  Inline asm with AMDGPU constraints must
 // live in __device__ functions: directly inside a __global__ body it silently drops the host stub.
@@ -178,7 +135,7 @@ __global__ __launch_bounds__(256, 1) void cosine_ksplit_filter(
         piece_row[m] = 8 * m + (lane >> 3);
         piece_col[m] = ((lane & 7) ^ ((piece_row[m] >> 1) & 7)) * 4 + w * KS; // float offset in the row
     }
-    const uint32_t ring_w = lds_addr(ring) + w * (NBUF * KS_SLOT_BYTES);
+    const uint32_t ring_w = oi_lds_addr(ring) + w * (NBUF * KS_SLOT_BYTES);
     const unsigned char *ring_rd = ring + w * (NBUF * KS_SLOT_BYTES);
     // fragment read address inside a slot: row li, logical 16-B column (2g + lh)
     uint32_t frag_off[4];
@@ -195,9 +152,9 @@ __global__ __launch_bounds__(256, 1) void cosine_ksplit_filter(
         uint64_t tile_id = blockIdx.x + ti * gridDim.x;
         if constexpr ((DBG & 8) != 0) tile_id &= 63;
         const uint64_t r0 = row_begin + tile_id * (uint64_t)KS_TILE_ROWS;
-        return ks_make_srd(rows + r0 * D, (row_end - r0) * (uint64_t)(D * 4));
+        return oi_make_srd(rows + r0 * D, (row_end - r0) * (uint64_t)(D * 4));
     };
-    u32x4 cur = tile_srd(0), nxt = tile_srd(my_nt > 1 ? 1 : 0);
+    oi_u32x4 cur = tile_srd(0), nxt = tile_srd(my_nt > 1 ? 1 : 0);
     // Every load hipcc knows about (queries, thresholds) is retired HERE, with a wait it models:
     // otherwise it re-waits for them at the top of the tile loop (vmcnt(1)) and drains the DMA ring.
     __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only
@@ -206,7 +163,7 @@ __global__ __launch_bounds__(256, 1) void cosine_ksplit_filter(
     for (int kc = 0; kc < P; ++kc)
 #pragma unroll
         for (int m = 0; m < 4; ++m)
-            ks_issue_piece(cur, voff[m], kc * KS_CHUNK_K * 4, ring_w + (kc % NBUF) * KS_SLOT_BYTES + m * 1024, no_dma);
+            oi_dma_piece(cur, voff[m], kc * KS_CHUNK_K * 4, ring_w + (kc % NBUF) * KS_SLOT_BYTES + m * 1024, no_dma);
 
     // ---- deferred epilogue.  A tile's partial sums are written to LDS right after its last MFMA;
     // the cross-wave sum + filter of tile t then rides INSIDE tile t+1's MFMA stream (barrier A at
@@ -245,9 +202,9 @@ __global__ __launch_bounds__(256, 1) void cosine_ksplit_filter(
         //                 them -- DMA piece g of slot kc+P into the buffer slot kc-1 has vacated;
         //                 at g == 3 the next fragment is (kc+1,0), behind the counted wait that
         //                 retires slot kc+1 (P-1 younger slots stay in flight).
-        ks_wait<4 * (P - 1)>();
+        oi_wait_vm<4 * (P - 1)>();
         f32x4 a_cur = *reinterpret_cast<const f32x4 *>(ring_rd + frag_off[0]);
-        ks_static_for<0, NKC * 4>([&](auto gi_) {
+        oi_static_for<0, NKC * 4>([&](auto gi_) {
             constexpr int gi = decltype(gi_)::value;
             constexpr int kc = gi / 4, g = gi % 4;
             constexpr int sn = kc + P; // slot refilled during this slot's groups
@@ -265,10 +222,10 @@ __global__ __launch_bounds__(256, 1) void cosine_ksplit_filter(
                 }
                 if (j == 0) { // one DMA piece per group, right behind the group's first MFMAs
                     if constexpr (sn < NKC)
-                        ks_issue_piece(cur, voff[g], sn * KS_CHUNK_K * 4, ring_w + (sn % NBUF) * KS_SLOT_BYTES + g * 1024,
+                        oi_dma_piece(cur, voff[g], sn * KS_CHUNK_K * 4, ring_w + (sn % NBUF) * KS_SLOT_BYTES + g * 1024,
                                        no_dma);
                     else
-                        ks_issue_piece(nxt, voff[g], (sn - NKC) * KS_CHUNK_K * 4,
+                        oi_dma_piece(nxt, voff[g], (sn - NKC) * KS_CHUNK_K * 4,
                                        ring_w + (sn % NBUF) * KS_SLOT_BYTES + g * 1024, no_dma || !has_next_tile);
                 }
             }
@@ -278,8 +235,8 @@ __global__ __launch_bounds__(256, 1) void cosine_ksplit_filter(
                 if constexpr (gi == EPI_GB) { if (have_prev) ks_barrier(); }                     // (B) `red` is free again
             }
             if constexpr (g == 3 && kc + 1 < NKC) {
-                if (kc + P < NKC || has_next_tile) ks_wait<4 * (P - 1)>();
-                else ks_wait<4 * (NKC - 2 - kc)>();
+                if (kc + P < NKC || has_next_tile) oi_wait_vm<4 * (P - 1)>();
+                else oi_wait_vm<4 * (NKC - 2 - kc)>();
                 a_nxt = *reinterpret_cast<const f32x4 *>(ring_rd + ((kc + 1) % NBUF) * KS_SLOT_BYTES + frag_off[0]);
             }
             a_cur = a_nxt;
@@ -377,7 +334,7 @@ __global__ __launch_bounds__(256, 1) void cosine_ksplit16_filter(
         const uint32_t pcol = ((lane & 7) ^ ((prow >> 1) & 7)) * 4 + w * KS;
         voff[m] = prow * (uint32_t)(D * 4) + pcol * 4u;
     }
-    const uint32_t ring_w = lds_addr(ring) + w * (NBUF * KS_SLOT_BYTES);
+    const uint32_t ring_w = oi_lds_addr(ring) + w * (NBUF * KS_SLOT_BYTES);
     const unsigned char *ring_rd = ring + w * (NBUF * KS_SLOT_BYTES);
     // fragment (row tile rt, group g in the slot): row 16 rt + li, logical 16-B column 4 g + kk
     uint32_t frag_off[2][2];
@@ -392,15 +349,15 @@ __global__ __launch_bounds__(256, 1) void cosine_ksplit16_filter(
     // branch around the prefetch and a single set of wait counts -- a branch-free tile body.
     auto tile_srd = [&](uint64_t ti) {
         const uint64_t r0 = row_begin + (blockIdx.x + (ti < my_nt ? ti : 0) * gridDim.x) * (uint64_t)KS_TILE_ROWS;
-        return ks_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 4) : 0ull);
+        return oi_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 4) : 0ull);
     };
-    u32x4 cur = tile_srd(0), nxt = tile_srd(1);
+    oi_u32x4 cur = tile_srd(0), nxt = tile_srd(1);
     __builtin_amdgcn_s_waitcnt(0x0F70); // retire every load hipcc knows about before the DMA ring starts
 #pragma unroll
     for (int kc = 0; kc < P; ++kc)
 #pragma unroll
         for (int m = 0; m < 4; ++m)
-            ks_issue_piece(cur, voff[m], kc * KS_CHUNK_K * 4, ring_w + (kc % NBUF) * KS_SLOT_BYTES + m * 1024, false);
+            oi_dma_piece(cur, voff[m], kc * KS_CHUNK_K * 4, ring_w + (kc % NBUF) * KS_SLOT_BYTES + m * 1024);
 
     float *my_red = red + w * RED_FLOATS;
     uint64_t prev_row0 = 0;
@@ -431,10 +388,10 @@ __global__ __launch_bounds__(256, 1) void cosine_ksplit16_filter(
 #pragma unroll
             for (int t = 0; t < NQ16; ++t) acc[rt][t] = f32x4v{0.f, 0.f, 0.f, 0.f};
 
-        ks_wait<4 * (P - 1)>();
+        oi_wait_vm<4 * (P - 1)>();
         f32x4 a0 = *reinterpret_cast<const f32x4 *>(ring_rd + frag_off[0][0]);
         f32x4 a1 = *reinterpret_cast<const f32x4 *>(ring_rd + frag_off[1][0]);
-        ks_static_for<0, NG>([&](auto gi_) {
+        oi_static_for<0, NG>([&](auto gi_) {
             constexpr int gi = decltype(gi_)::value;
             constexpr int kc = gi / 2, g = gi % 2;
             constexpr int sn = kc + P;
@@ -454,9 +411,9 @@ __global__ __launch_bounds__(256, 1) void cosine_ksplit16_filter(
                     constexpr int dummy = 0; (void)dummy;
                     const int m = 2 * g + (e >> 1);
                     if constexpr (sn < NKC)
-                        ks_issue_piece(cur, voff[m], sn * KS_CHUNK_K * 4, ring_w + (sn % NBUF) * KS_SLOT_BYTES + m * 1024, false);
+                        oi_dma_piece(cur, voff[m], sn * KS_CHUNK_K * 4, ring_w + (sn % NBUF) * KS_SLOT_BYTES + m * 1024);
                     else
-                        ks_issue_piece(nxt, voff[m], (sn - NKC) * KS_CHUNK_K * 4,
+                        oi_dma_piece(nxt, voff[m], (sn - NKC) * KS_CHUNK_K * 4,
                                        ring_w + (sn % NBUF) * KS_SLOT_BYTES + m * 1024, false);
                 }
             }
@@ -468,7 +425,7 @@ __global__ __launch_bounds__(256, 1) void cosine_ksplit16_filter(
             }
             if constexpr (gi == NG - 1) ks_barrier();                                     // (B) `red` is free again
             if constexpr (g == 1 && kc + 1 < NKC) {
-                ks_wait<4 * (P - 1)>();
+                oi_wait_vm<4 * (P - 1)>();
                 n0 = *reinterpret_cast<const f32x4 *>(ring_rd + ((kc + 1) % NBUF) * KS_SLOT_BYTES + frag_off[0][0]);
                 n1 = *reinterpret_cast<const f32x4 *>(ring_rd + ((kc + 1) % NBUF) * KS_SLOT_BYTES + frag_off[1][0]);
             }

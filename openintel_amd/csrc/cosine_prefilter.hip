@@ -52,97 +52,22 @@
 
 #include "oi_device.h"
 #include "oi_internal.h"
+#include "oi_lds_dma.h"
 
 typedef float pf_f32x16 __attribute__((ext_vector_type(16)));
 typedef float pf_f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 pf_bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t pf_u32x4 __attribute__((ext_vector_type(4)));
 
 #define PF_TILE_ROWS 32
 #define PF_SLOT_K 32                 // floats of K per ring slot row (128 B)
 #define PF_SLOT_BYTES (PF_TILE_ROWS * 128)
 
-__device__ __forceinline__ uint32_t pf_lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)p;
-}
-__device__ __forceinline__ pf_u32x4 pf_make_srd(const float *base, uint64_t bytes) {
-    const uint64_t b = (uint64_t)base;
-    pf_u32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    r[1] = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32) & 0xFFFFu); // stride 0
-    r[2] = __builtin_amdgcn_readfirstlane((uint32_t)(bytes > 0xFFFFFFFFull ? 0xFFFFFFFFull : bytes));
-    r[3] = 0x00020000u;
-    return r;
-}
-// One 1-KiB LDS-DMA piece (8 rows x 128 B).  Lanes past the descriptor's end read as zero: the ragged last
-// tile and the tile after the last one (empty descriptor) need no branch.  hipcc does not see these loads:
-// they are ordered by pf_wait<N>().
-__device__ __forceinline__ void pf_issue_piece(const pf_u32x4 &srd, uint32_t voff, uint32_t soff, uint32_t lds_dst) {
-    uint32_t keep;
-    const uint32_t d = __builtin_amdgcn_readfirstlane(lds_dst);
-    const uint32_t so = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %4\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %2, %3 offen " OI_DMA_NT "lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(srd), "s"(so), "s"(d)
-        : "memory");
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void pf_static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        pf_static_for<I + 1, N>(f);
-    }
-}
-template <int N>
-__device__ __forceinline__ void pf_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 __device__ __forceinline__ pf_bf16x8 pf_pack(const pf_f32x4 &a, const pf_f32x4 &b) {
     pf_bf16x8 r;
     r[0] = (__bf16)a[0]; r[1] = (__bf16)a[1]; r[2] = (__bf16)a[2]; r[3] = (__bf16)a[3]; // v_cvt_pk_bf16_f32 (RNE)
     r[4] = (__bf16)b[0]; r[5] = (__bf16)b[1]; r[6] = (__bf16)b[2]; r[7] = (__bf16)b[3];
     return r;
 }
-
-// Survivor staging of the screen kernel: PF_STAGE entries per wave (a power of two), flushed PF_STAGE_FLUSH at a time (fewer than
-// PF_STAGE_FLUSH stay between tiles, so a tile of up to PF_STAGE - PF_STAGE_FLUSH survivors is staged).
-#define PF_STAGE 256
-#define PF_STAGE_FLUSH 64u
-#define PF_STAGE_LDS (4 * PF_STAGE * 12)
-__device__ __forceinline__ uint32_t pf_incl_scan(uint32_t v) { // wave-wide inclusive prefix sum (DPP, no LDS)
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
-    return v;
-}
-// The first NF staged entries of the wave leave for the pool: lane l takes entry st_head + l, its position in its query's
-// segment from ONE LDS atomic, one store instruction for all of them.  (A macro: a lambda would take st_head / st_n by
-// reference and hipcc then keeps them in scratch.)  The compiler barriers keep the staging writes of other lanes in front of
-// these reads, and these reads in front of the next tile's writes (LDS operations of a wave execute in order).
-#define PF_FLUSH(NF)                                                                                                   \
-    do {                                                                                                               \
-        const uint32_t nf_ = (NF);                                                                                     \
-        asm volatile("" ::: "memory");                                                                                 \
-        if (lane < nf_) {                                                                                              \
-            const uint32_t i_ = (st_head + lane) & (PF_STAGE - 1);                                                     \
-            const uint64_t key_ = stage_keys[i_];                                                                      \
-            const uint32_t q_ = stage_q[i_];                                                                           \
-            const uint32_t pos_ = atomicAdd(&seg_fill[q_], 1u);                                                        \
-            if (pos_ < seg_cap) my_seg[(uint64_t)q_ * pool_stride + pos_] = key_;                                      \
-            else *overflow = 1u;                                                                                       \
-        }                                                                                                              \
-        asm volatile("" ::: "memory");                                                                                 \
-        st_head = (st_head + nf_) & (PF_STAGE - 1);                                                                    \
-        st_n -= nf_;                                                                                                   \
-    } while (0)
 
 template <int D, int NQT>
 __global__ __launch_bounds__(256, 1) void cosine_screen_filter(
@@ -166,9 +91,9 @@ __global__ __launch_bounds__(256, 1) void cosine_screen_filter(
     const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t li = lane & 31, lh = lane >> 5;
     // the wave's staging ring of survivors (keys and their queries), behind seg_fill
-    uint64_t *stage_keys = reinterpret_cast<uint64_t *>(smem + 4 * NBUF * PF_SLOT_BYTES + 256) + w * PF_STAGE;
-    uint32_t *stage_q = reinterpret_cast<uint32_t *>(smem + 4 * NBUF * PF_SLOT_BYTES + 256 + 4 * PF_STAGE * 8) + w * PF_STAGE;
-    uint32_t st_head = 0, st_n = 0; // wave-uniform: first staged entry (mod PF_STAGE), staged entries (< PF_STAGE_FLUSH between tiles)
+    uint64_t *stage_keys = reinterpret_cast<uint64_t *>(smem + 4 * NBUF * PF_SLOT_BYTES + 256) + w * OI_STAGE;
+    uint32_t *stage_q = reinterpret_cast<uint32_t *>(smem + 4 * NBUF * PF_SLOT_BYTES + 256 + 4 * OI_STAGE * 8) + w * OI_STAGE;
+    uint32_t st_head = 0, st_n = 0; // wave-uniform: first staged entry (mod OI_STAGE), staged entries (< OI_STAGE_FLUSH between tiles)
 
     // ---- every query over the whole K, in registers for the whole launch: B[k = 16 s + 8 lh + 0..7][n = li]
     pf_bf16x8 qreg[NQT][KSTEPS];
@@ -208,7 +133,7 @@ __global__ __launch_bounds__(256, 1) void cosine_screen_filter(
             const uint32_t prow = 8 * m + (lane >> 3);
             voff[m] = prow * (uint32_t)(D * 4) + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
         }
-        const uint32_t ring_w = pf_lds_addr(ring) + w * (NBUF * PF_SLOT_BYTES);
+        const uint32_t ring_w = oi_lds_addr(ring) + w * (NBUF * PF_SLOT_BYTES);
         const unsigned char *ring_rd = ring + w * (NBUF * PF_SLOT_BYTES);
         // fragment of k-step g of a slot: row li, floats 16 g + 8 lh + 0..7 = logical 16-B columns 4g + 2lh, + 1
         uint32_t frag_off[2][2];
@@ -220,9 +145,9 @@ __global__ __launch_bounds__(256, 1) void cosine_screen_filter(
         auto tile_row0 = [&](uint64_t ti) { return row_begin + (first + ti * stride) * (uint64_t)PF_TILE_ROWS; };
         auto tile_srd = [&](uint64_t ti) { // past this wave's last tile: an EMPTY descriptor (loads return zeros)
             const uint64_t r0 = tile_row0(ti < my_nt ? ti : 0);
-            return pf_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 4) : 0ull);
+            return oi_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 4) : 0ull);
         };
-        pf_u32x4 cur = tile_srd(0), nxt = tile_srd(1);
+        oi_u32x4 cur = tile_srd(0), nxt = tile_srd(1);
         // Every load hipcc knows about (queries, thresholds) is retired HERE, with a wait it models:
         // otherwise it re-waits for them inside the tile loop and drains the DMA ring.
         __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only
@@ -230,7 +155,7 @@ __global__ __launch_bounds__(256, 1) void cosine_screen_filter(
         for (int kc = 0; kc < P; ++kc) // prologue: slots 0..P-1 of the first tile
 #pragma unroll
             for (int m = 0; m < 4; ++m)
-                pf_issue_piece(cur, voff[m], kc * 128, ring_w + (kc % NBUF) * PF_SLOT_BYTES + m * 1024);
+                oi_dma_piece(cur, voff[m], kc * 128, ring_w + (kc % NBUF) * PF_SLOT_BYTES + m * 1024);
 
         for (uint64_t ti = 0; ti < my_nt; ++ti) {
             pf_f32x16 acc[NQT];
@@ -243,10 +168,10 @@ __global__ __launch_bounds__(256, 1) void cosine_screen_filter(
             // floats, NQT MFMAs on the current operand, DMA pieces 2g, 2g+1 of slot kc + P into the buffer
             // slot kc - 1 has vacated, convert the floats read; at g == 1 the next k-step is (kc + 1, 0),
             // behind the counted wait that retires slot kc + 1 (P - 1 younger slots stay in flight).
-            pf_wait<4 * (P - 1)>();
+            oi_wait_vm<4 * (P - 1)>();
             pf_bf16x8 a_cur = pf_pack(*reinterpret_cast<const pf_f32x4 *>(ring_rd + frag_off[0][0]),
                                       *reinterpret_cast<const pf_f32x4 *>(ring_rd + frag_off[0][1]));
-            pf_static_for<0, NKC * 2>([&](auto gi_) {
+            oi_static_for<0, NKC * 2>([&](auto gi_) {
                 constexpr int gi = decltype(gi_)::value;
                 constexpr int kc = gi / 2, g = gi % 2;
                 constexpr int sn = kc + P; // slot refilled during this slot's k-steps
@@ -261,12 +186,12 @@ __global__ __launch_bounds__(256, 1) void cosine_screen_filter(
 #pragma unroll
                 for (int m = 2 * g; m < 2 * g + 2; ++m) {
                     if constexpr (sn < NKC)
-                        pf_issue_piece(cur, voff[m], sn * 128, ring_w + (sn % NBUF) * PF_SLOT_BYTES + m * 1024);
+                        oi_dma_piece(cur, voff[m], sn * 128, ring_w + (sn % NBUF) * PF_SLOT_BYTES + m * 1024);
                     else
-                        pf_issue_piece(nxt, voff[m], (sn - NKC) * 128, ring_w + (sn % NBUF) * PF_SLOT_BYTES + m * 1024);
+                        oi_dma_piece(nxt, voff[m], (sn - NKC) * 128, ring_w + (sn % NBUF) * PF_SLOT_BYTES + m * 1024);
                 }
                 if constexpr (g == 1 && kc + 1 < NKC) {
-                    pf_wait<4 * (P - 1)>();
+                    oi_wait_vm<4 * (P - 1)>();
                     f0 = *reinterpret_cast<const pf_f32x4 *>(ring_rd + ((kc + 1) % NBUF) * PF_SLOT_BYTES + frag_off[0][0]);
                     f1 = *reinterpret_cast<const pf_f32x4 *>(ring_rd + ((kc + 1) % NBUF) * PF_SLOT_BYTES + frag_off[0][1]);
                 }
@@ -293,9 +218,9 @@ __global__ __launch_bounds__(256, 1) void cosine_screen_filter(
             }
             if (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull) {
                 const uint32_t cnt = (uint32_t)__builtin_popcount(m);
-                const uint32_t incl = pf_incl_scan(cnt);
+                const uint32_t incl = oi_wave_incl_scan(cnt);
                 const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                if (total <= PF_STAGE - PF_STAGE_FLUSH) {
+                if (total <= OI_STAGE - OI_STAGE_FLUSH) {
                     // SPARSE tile (every tile once a threshold stands): the survivors go to the wave's LDS staging ring, and
                     // 64 of them leave with ONE store instruction.  A store per survivor sat in the same in-order vmcnt queue
                     // as the DMA pieces: every counted wait then also waited for slots it did not need yet (the stores behind
@@ -307,13 +232,13 @@ __global__ __launch_bounds__(256, 1) void cosine_screen_filter(
                         for (int r = 0; r < 16; ++r)
                             if (m & (1u << (16 * t + r))) {
                                 const uint32_t row = (uint32_t)row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                                stage_keys[idx & (PF_STAGE - 1)] = oi_rank_key(acc[t][r], doc_id_base + row);
-                                stage_q[idx & (PF_STAGE - 1)] = 32u * t + li;
+                                stage_keys[idx & (OI_STAGE - 1)] = oi_rank_key(acc[t][r], doc_id_base + row);
+                                stage_q[idx & (OI_STAGE - 1)] = 32u * t + li;
                                 ++idx;
                             }
                     st_n += total;
-                    while (st_n >= PF_STAGE_FLUSH) {
-                        PF_FLUSH(PF_STAGE_FLUSH);
+                    while (st_n >= OI_STAGE_FLUSH) {
+                        OI_STAGE_FLUSH_TO_POOL(OI_STAGE_FLUSH);
                     }
                 } else {
                     // DENSE tile (the first chunk, scored without a threshold: every score passes): straight to the pool
@@ -340,7 +265,7 @@ __global__ __launch_bounds__(256, 1) void cosine_screen_filter(
             nxt = tile_srd(ti + 2);
         }
         if (st_n) {
-            PF_FLUSH(st_n);
+            OI_STAGE_FLUSH_TO_POOL(st_n);
         }
     }
     __syncthreads(); // every wave's appends are counted
@@ -767,7 +692,7 @@ template <int D, int NQT>
 static int launch_screen(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end, const uint16_t *q,
                          uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
     constexpr int NKC = D / PF_SLOT_K, NBUF = NKC % 8 == 0 ? 8 : (NKC % 6 == 0 ? 6 : NKC);
-    constexpr size_t smem = 4 * NBUF * PF_SLOT_BYTES + 64 * 4 + PF_STAGE_LDS;
+    constexpr size_t smem = 4 * NBUF * PF_SLOT_BYTES + 64 * 4 + OI_STAGE_LDS;
     OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(cosine_screen_filter<D, NQT>), (size_t)(smem)));
     hipLaunchKernelGGL((cosine_screen_filter<D, NQT>), dim3(p.n_segs), dim3(256), smem, ctx->stream, rows, row_begin,
                        row_end, q, nq, doc_id_base, p.keys, p.seg_cnt, p.seg_cnt_stride, p.tau_keys, p.stride,
@@ -789,11 +714,7 @@ int oi_launch_cosine_screen_chunk(oi_ctx *ctx, const float *rows, uint64_t row_b
     ProfScope ps(ctx, "cosine");
     for (uint32_t q0 = 0; q0 < n_queries; q0 += 64) {
         const uint32_t nq_here = std::min(64u, n_queries - q0);
-        PoolView p = pool;
-        p.keys += (uint64_t)q0 * pool.stride;
-        p.carry_cnt += q0;
-        p.seg_cnt += (uint64_t)q0 * pool.seg_cnt_stride;
-        p.tau_keys += q0;
+        PoolView p = pool.for_queries(q0); // (no filter here: required above)
         static const bool tau_max = oi_ablation_env("OI_SCREEN_TAU_MAX") != nullptr; // A/B (WRONG results): chunks of >= 1M rows pass nothing
         if (tau_max && row_end - row_begin >= (1u << 20)) {
             DevBuf &tb = ctx->buf("abl_tau_max");

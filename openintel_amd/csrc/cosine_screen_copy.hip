@@ -20,18 +20,19 @@
 //     the HBM rate and needs ~3 K of matrix pipe: the extra scalar work is free, bytes in flight are what it is short of.
 //   * the refill of slot s + P always issues (an empty descriptor past the wave's last tile returns zeros), so every
 //     counted wait is the same constant and the tile loop has no tail cases.
-// Survivors leave through the per-wave LDS staging ring of the f32 screen (64 keys per store instruction: a store per
-// survivor sits in the same in-order vmcnt queue as the DMA pieces and makes every counted wait wait for more than it needs).
+// Survivors leave through the per-wave LDS staging ring (oi_lds_dma.h, OI_STAGE_FLUSH_TO_POOL: 64 keys per store instruction;
+// a store per survivor sits in the same in-order vmcnt queue as the DMA pieces and makes every counted wait wait for more
+// than it needs).
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
 #include "oi_device.h"
 #include "oi_internal.h"
+#include "oi_lds_dma.h"
 
 typedef float sc_f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 sc_bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t sc_u32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef OI_TILE_CONTIG
 #define OI_TILE_CONTIG 0
@@ -39,25 +40,8 @@ typedef uint32_t sc_u32x4 __attribute__((ext_vector_type(4)));
 #define SC_TILE_ROWS 32
 #define SC_SLOT_K 64                 // bf16 of K per ring slot row (128 B)
 #define SC_SLOT_BYTES (SC_TILE_ROWS * 128)
-#define SC_STAGE 256                 // staged survivors per wave (a power of two)
-#define SC_STAGE_FLUSH 64u
-#define SC_STAGE_LDS (4 * SC_STAGE * 12)
-
-__device__ __forceinline__ uint32_t sc_lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)p;
-}
-__device__ __forceinline__ sc_u32x4 sc_make_srd(const uint16_t *base, uint64_t bytes) {
-    const uint64_t b = (uint64_t)base;
-    sc_u32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    r[1] = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32) & 0xFFFFu); // stride 0
-    r[2] = __builtin_amdgcn_readfirstlane((uint32_t)(bytes > 0xFFFFFFFFull ? 0xFFFFFFFFull : bytes));
-    r[3] = 0x00020000u;
-    return r;
-}
-// One 1-KiB LDS-DMA piece (8 rows x 128 B).  Lanes past the descriptor's end read as zero: the ragged last tile and the
-// tiles after the last one (empty descriptor) need no branch.  hipcc does not see these loads: sc_wait<N>() orders them.
-__device__ __forceinline__ void sc_issue_piece(const sc_u32x4 &srd, uint32_t voff, uint32_t soff, uint32_t lds_dst) {
+// One ring piece: oi_dma_piece, but for the variant builds that take the DMA out of this kernel.
+__device__ __forceinline__ void sc_issue_piece(const oi_u32x4 &srd, uint32_t voff, uint32_t soff, uint32_t lds_dst) {
 #if defined(SC_AGG_NO_DMA) && SC_AGG_NO_DMA == 1
     // (variant builds, tools/r05_victim_probe.py: which trait of this kernel disturbs a neighbour wave?  The same bytes loaded
     // into registers nobody reads instead of into LDS; the ring is zeroed at the start, every score is 0: results WRONG.)
@@ -66,58 +50,9 @@ __device__ __forceinline__ void sc_issue_piece(const sc_u32x4 &srd, uint32_t vof
 #elif defined(SC_AGG_NO_DMA)
     (void)srd; (void)voff; (void)soff; (void)lds_dst; // (variant builds: no loads at all)
 #else
-    uint32_t keep;
-    const uint32_t d = __builtin_amdgcn_readfirstlane(lds_dst);
-    const uint32_t so = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %4\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %2, %3 offen " OI_DMA_NT "lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(srd), "s"(so), "s"(d)
-        : "memory");
+    oi_dma_piece(srd, voff, soff, lds_dst);
 #endif
 }
-template <int I, int N, class F>
-__device__ __forceinline__ void sc_static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        sc_static_for<I + 1, N>(f);
-    }
-}
-template <int N>
-__device__ __forceinline__ void sc_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ uint32_t sc_incl_scan(uint32_t v) { // wave-wide inclusive prefix sum (DPP, no LDS)
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
-    return v;
-}
-// The first NF staged entries of the wave leave for the pool (cosine_prefilter.hip: PF_FLUSH -- same contract; the compiler
-// barriers keep other lanes' staging writes in front of these reads and these reads in front of the next tile's writes).
-#define SC_FLUSH(NF)                                                                                                   \
-    do {                                                                                                               \
-        const uint32_t nf_ = (NF);                                                                                     \
-        asm volatile("" ::: "memory");                                                                                 \
-        if (lane < nf_) {                                                                                              \
-            const uint32_t i_ = (st_head + lane) & (SC_STAGE - 1);                                                     \
-            const uint64_t key_ = stage_keys[i_];                                                                      \
-            const uint32_t q_ = stage_q[i_];                                                                           \
-            const uint32_t pos_ = atomicAdd(&seg_fill[q_], 1u);                                                        \
-            if (pos_ < seg_cap) my_seg[(uint64_t)q_ * pool_stride + pos_] = key_;                                      \
-            else *overflow = 1u;                                                                                       \
-        }                                                                                                              \
-        asm volatile("" ::: "memory");                                                                                 \
-        st_head = (st_head + nf_) & (SC_STAGE - 1);                                                                    \
-        st_n -= nf_;                                                                                                   \
-    } while (0)
 
 template <int D, int NQT, int NBUF, bool FILT>
 __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
@@ -132,7 +67,7 @@ __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
     constexpr uint32_t RING = NBUF * SC_SLOT_BYTES;
     static_assert(D % SC_SLOT_K == 0 && P >= 1 && P <= 2 * NKC, "unsupported ring depth for this D");
     static_assert(NQT * KSTEPS * 4 <= 400, "the query block must fit the register file");
-    static_assert(4 * RING + 256 + SC_STAGE_LDS <= 160 * 1024, "LDS");
+    static_assert(4 * RING + 256 + OI_STAGE_LDS <= 160 * 1024, "LDS");
 
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     unsigned char *ring = smem;                                          // [4][NBUF][4 KiB]
@@ -142,9 +77,9 @@ __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t li = lane & 31, lh = lane >> 5;
-    uint64_t *stage_keys = reinterpret_cast<uint64_t *>(smem + 4 * RING + 256) + w * SC_STAGE;
-    uint32_t *stage_q = reinterpret_cast<uint32_t *>(smem + 4 * RING + 256 + 4 * SC_STAGE * 8) + w * SC_STAGE;
-    uint32_t st_head = 0, st_n = 0; // wave-uniform: first staged entry (mod SC_STAGE), staged entries (< SC_STAGE_FLUSH between tiles)
+    uint64_t *stage_keys = reinterpret_cast<uint64_t *>(smem + 4 * RING + 256) + w * OI_STAGE;
+    uint32_t *stage_q = reinterpret_cast<uint32_t *>(smem + 4 * RING + 256 + 4 * OI_STAGE * 8) + w * OI_STAGE;
+    uint32_t st_head = 0, st_n = 0; // wave-uniform: first staged entry (mod OI_STAGE), staged entries (< OI_STAGE_FLUSH between tiles)
 
     // ---- every query over the whole K, in registers for the whole launch: B[k = 16 s + 8 lh + 0..7][n = li]
     sc_bf16x8 qreg[NQT][KSTEPS];
@@ -189,7 +124,7 @@ __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
             const uint32_t prow = 8 * m + (lane >> 3);
             voff[m] = prow * (uint32_t)(D * 2) + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
         }
-        const uint32_t ring_w = sc_lds_addr(ring) + w * RING;
+        const uint32_t ring_w = oi_lds_addr(ring) + w * RING;
         const unsigned char *ring_rd = ring + w * RING;
         // fragment of MFMA group g of a slot: row li, bf16 16 g + 8 lh + 0..7 = logical 16-B column 2g + lh
         uint32_t frag_off[4];
@@ -199,13 +134,13 @@ __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
         auto tile_row0 = [&](uint64_t ti) { return row_begin + (first + ti * stride) * (uint64_t)SC_TILE_ROWS; };
         auto tile_srd = [&](uint64_t ti) { // past this wave's last tile: an EMPTY descriptor (loads return zeros)
             const uint64_t r0 = tile_row0(ti < my_nt ? ti : 0);
-            return sc_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 2) : 0ull);
+            return oi_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 2) : 0ull);
         };
-        sc_u32x4 s0 = tile_srd(0), s1 = tile_srd(1), s2 = tile_srd(2);
+        oi_u32x4 s0 = tile_srd(0), s1 = tile_srd(1), s2 = tile_srd(2);
         // Every load hipcc knows about (queries, thresholds) is retired HERE, with a wait it models:
         // otherwise it re-waits for them inside the tile loop and drains the DMA ring.
         __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only
-        sc_static_for<0, P>([&](auto j_) { // prologue: logical slots 0..P-1 (tile j / NKC, slot j % NKC) into ring slots 0..P-1
+        oi_static_for<0, P>([&](auto j_) { // prologue: logical slots 0..P-1 (tile j / NKC, slot j % NKC) into ring slots 0..P-1
             constexpr int j = decltype(j_)::value;
             constexpr int tj = j / NKC, kj = j % NKC;
 #pragma unroll
@@ -225,9 +160,9 @@ __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
             // Slot kc of this tile sits at rd_off.  Per MFMA group (kc, g): read the next fragment, NQT MFMAs on the
             // current one, DMA piece g of logical slot kc + P into the slot vacated last (wr_off); after g == 3 the
             // counted wait retires slot kc + 1 (P - 1 younger slots stay in flight) and the offsets move on.
-            sc_wait<4 * (P - 1)>();
+            oi_wait_vm<4 * (P - 1)>();
             sc_bf16x8 a_cur = *reinterpret_cast<const sc_bf16x8 *>(ring_rd + rd_off + frag_off[0]);
-            sc_static_for<0, NKC * 4>([&](auto gi_) {
+            oi_static_for<0, NKC * 4>([&](auto gi_) {
                 constexpr int gi = decltype(gi_)::value;
                 constexpr int kc = gi / 4, g = gi % 4;
                 constexpr int sn = kc + P;           // logical slot (relative to this tile) refilled during this slot
@@ -246,7 +181,7 @@ __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
                     wr_off = rd_off;
                     rd_off = rd_off + SC_SLOT_BYTES == RING ? 0u : rd_off + SC_SLOT_BYTES;
                     if constexpr (kc + 1 < NKC) {
-                        sc_wait<4 * (P - 1)>();
+                        oi_wait_vm<4 * (P - 1)>();
                         a_nxt = *reinterpret_cast<const sc_bf16x8 *>(ring_rd + rd_off + frag_off[0]);
                     }
                 }
@@ -270,9 +205,9 @@ __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
             if (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull) {
                 if constexpr (FILT) m = oi_filter_tile<NQT>(m, filt, attrs, row0, lh, li);
                 const uint32_t cnt = (uint32_t)__builtin_popcount(m);
-                const uint32_t incl = sc_incl_scan(cnt);
+                const uint32_t incl = oi_wave_incl_scan(cnt);
                 const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                if (total <= SC_STAGE - SC_STAGE_FLUSH) {
+                if (total <= OI_STAGE - OI_STAGE_FLUSH) {
                     // SPARSE tile (every tile once a threshold stands): staged, 64 leave with one store instruction
                     uint32_t idx = st_head + st_n + incl - cnt;
 #pragma unroll
@@ -281,13 +216,13 @@ __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
                         for (int r = 0; r < 16; ++r)
                             if (m & (1u << (16 * t + r))) {
                                 const uint32_t row = (uint32_t)row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                                stage_keys[idx & (SC_STAGE - 1)] = oi_rank_key(acc[t][r], doc_id_base + row);
-                                stage_q[idx & (SC_STAGE - 1)] = 32u * t + li;
+                                stage_keys[idx & (OI_STAGE - 1)] = oi_rank_key(acc[t][r], doc_id_base + row);
+                                stage_q[idx & (OI_STAGE - 1)] = 32u * t + li;
                                 ++idx;
                             }
                     st_n += total;
-                    while (st_n >= SC_STAGE_FLUSH) {
-                        SC_FLUSH(SC_STAGE_FLUSH);
+                    while (st_n >= OI_STAGE_FLUSH) {
+                        OI_STAGE_FLUSH_TO_POOL(OI_STAGE_FLUSH);
                     }
                 } else {
                     // DENSE tile (the first chunk, scored without a threshold: every score passes): straight to the pool
@@ -315,9 +250,9 @@ __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
             s2 = tile_srd(ti + 3);
         }
         if (st_n) {
-            SC_FLUSH(st_n);
+            OI_STAGE_FLUSH_TO_POOL(st_n);
         }
-        sc_wait<0>(); // the zero-filling refills issued past the last tile have landed before the LDS goes back
+        oi_wait_vm<0>(); // the zero-filling refills issued past the last tile have landed before the LDS goes back
     }
     __syncthreads(); // every wave's appends are counted
     if (tid < 32 * NQT && tid < n_queries) {
@@ -338,7 +273,7 @@ __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
 template <int D, int NQT, int NBUF, bool FILT>
 static int launch_copy_screen_k(oi_ctx *ctx, const uint16_t *rows, uint64_t row_begin, uint64_t row_end, const uint16_t *q,
                                 uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
-    constexpr size_t smem = 4 * NBUF * SC_SLOT_BYTES + 64 * 4 + SC_STAGE_LDS;
+    constexpr size_t smem = 4 * NBUF * SC_SLOT_BYTES + 64 * 4 + OI_STAGE_LDS;
     OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(cosine_copy_screen<D, NQT, NBUF, FILT>), (size_t)(smem)));
     hipLaunchKernelGGL((cosine_copy_screen<D, NQT, NBUF, FILT>), dim3(p.n_segs), dim3(256), smem, ctx->stream, rows, row_begin,
                        row_end, q, nq, doc_id_base, p.keys, p.seg_cnt, p.seg_cnt_stride, p.tau_keys, p.stride,
@@ -380,12 +315,7 @@ int oi_launch_cosine_screen_copy_chunk(oi_ctx *ctx, const uint16_t *copy_rows, u
     ProfScope ps(ctx, "cosine");
     for (uint32_t q0 = 0; q0 < n_queries; q0 += 64) {
         const uint32_t nq_here = std::min(64u, n_queries - q0);
-        PoolView p = pool;
-        p.keys += (uint64_t)q0 * pool.stride;
-        p.carry_cnt += q0;
-        p.seg_cnt += (uint64_t)q0 * pool.seg_cnt_stride;
-        p.tau_keys += q0;
-        if (p.filt) p.filt += q0;
+        const PoolView p = pool.for_queries(q0);
         const uint16_t *qptr = q_bf16 + (uint64_t)q0 * dim;
         const bool two = nq_here > 32;
         if (dim == 768) {

@@ -42,18 +42,15 @@
 
 #include "oi_device.h"
 #include "oi_internal.h"
+#include "oi_lds_dma.h"
 
 typedef int i8s_i32x4 __attribute__((ext_vector_type(4)));
 typedef int i8s_i32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t i8s_u32x4 __attribute__((ext_vector_type(4)));
 typedef float i8s_f32x4 __attribute__((ext_vector_type(4)));
 
 #define I8S_TILE_ROWS 32
 #define I8S_SLOT_BYTES (I8S_TILE_ROWS * 128) // 32 rows x 128 i8 of K
 #define I8S_META_BYTES 256                   // 32 rows x {scale, e_r}
-#define I8S_STAGE 256
-#define I8S_STAGE_FLUSH 64u
-#define I8S_STAGE_LDS (4 * I8S_STAGE * 12)
 #define I8S_PAD_ROWS 64
 
 // ------------------------------------------------------------------ the copy
@@ -200,39 +197,16 @@ int oi_launch_screen_stage_i8(oi_ctx *ctx, const float *d_queries, uint32_t n_qu
 }
 
 // ------------------------------------------------------------------ the screen
-__device__ __forceinline__ uint32_t i8s_lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)p;
-}
-__device__ __forceinline__ i8s_u32x4 i8s_make_srd(const void *base, uint64_t bytes) {
-    const uint64_t b = (uint64_t)base;
-    i8s_u32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    r[1] = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32) & 0xFFFFu); // stride 0
-    r[2] = __builtin_amdgcn_readfirstlane((uint32_t)(bytes > 0xFFFFFFFFull ? 0xFFFFFFFFull : bytes));
-    r[3] = 0x00020000u;
-    return r;
-}
-// One 1-KiB LDS-DMA piece (8 rows x 128 B); lanes past the descriptor's end read as zero (cosine_screen_copy.hip: sc_issue_piece).
-__device__ __forceinline__ void i8s_issue_piece(const i8s_u32x4 &srd, uint32_t voff, uint32_t soff, uint32_t lds_dst) {
+// One ring piece: oi_dma_piece, but for the ablation builds that take the DMA out of this kernel.
+__device__ __forceinline__ void i8s_issue_piece(const oi_u32x4 &srd, uint32_t voff, uint32_t soff, uint32_t lds_dst) {
 #ifdef I8S_NO_DMA
     (void)srd; (void)voff; (void)soff; (void)lds_dst; // (ablation builds: no loads at all; results WRONG)
 #else
-    uint32_t keep;
-    const uint32_t d = __builtin_amdgcn_readfirstlane(lds_dst);
-    const uint32_t so = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %4\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %2, %3 offen " OI_DMA_NT "lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(srd), "s"(so), "s"(d)
-        : "memory");
+    oi_dma_piece(srd, voff, soff, lds_dst);
 #endif
 }
 // The tile's metadata: 64 lanes x 4 B = 32 rows x {scale, e_r} into the wave's meta slot.
-__device__ __forceinline__ void i8s_issue_meta(const i8s_u32x4 &srd, uint32_t voff, uint32_t lds_dst) {
+__device__ __forceinline__ void i8s_issue_meta(const oi_u32x4 &srd, uint32_t voff, uint32_t lds_dst) {
 #ifdef I8S_NO_DMA
     (void)srd; (void)voff; (void)lds_dst;
 #else
@@ -249,43 +223,6 @@ __device__ __forceinline__ void i8s_issue_meta(const i8s_u32x4 &srd, uint32_t vo
         : "memory");
 #endif
 }
-template <int I, int N, class F>
-__device__ __forceinline__ void i8s_static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        i8s_static_for<I + 1, N>(f);
-    }
-}
-template <int N>
-__device__ __forceinline__ void i8s_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ uint32_t i8s_incl_scan(uint32_t v) { // wave-wide inclusive prefix sum (DPP, no LDS)
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
-    return v;
-}
-// cosine_screen_copy.hip: SC_FLUSH (the same contract)
-#define I8S_FLUSH(NF)                                                                                                  \
-    do {                                                                                                               \
-        const uint32_t nf_ = (NF);                                                                                     \
-        asm volatile("" ::: "memory");                                                                                 \
-        if (lane < nf_) {                                                                                              \
-            const uint32_t i_ = (st_head + lane) & (I8S_STAGE - 1);                                                    \
-            const uint64_t key_ = stage_keys[i_];                                                                      \
-            const uint32_t q_ = stage_q[i_];                                                                           \
-            const uint32_t pos_ = atomicAdd(&seg_fill[q_], 1u);                                                        \
-            if (pos_ < seg_cap) my_seg[(uint64_t)q_ * pool_stride + pos_] = key_;                                      \
-            else *overflow = 1u;                                                                                       \
-        }                                                                                                              \
-        asm volatile("" ::: "memory");                                                                                 \
-        st_head = (st_head + nf_) & (I8S_STAGE - 1);                                                                   \
-        st_n -= nf_;                                                                                                   \
-    } while (0)
 
 template <int D, int NQT, int NBUF, bool FILT>
 __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
@@ -301,21 +238,21 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
     static_assert(D % 128 == 0 && P >= 2 && P <= 2 * NKC, "unsupported ring depth for this D");
     constexpr uint32_t QLO_LDS = NQT * KSTEPS * 64 * 16; // the lo parts, fragment-major (one conflict-free ds_read_b128 each)
     static_assert(NQT * KSTEPS * 4 <= 200, "the hi query block must fit the register file");
-    static_assert(4 * RING + 4 * 2 * I8S_META_BYTES + 256 + I8S_STAGE_LDS + QLO_LDS <= 160 * 1024, "LDS");
+    static_assert(4 * RING + 4 * 2 * I8S_META_BYTES + 256 + OI_STAGE_LDS + QLO_LDS <= 160 * 1024, "LDS");
 
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     unsigned char *ring = smem;                                                          // [4][NBUF][4 KiB]
     unsigned char *meta_lds = smem + 4 * RING;                                           // [4][2][256 B]
     uint32_t *seg_fill = reinterpret_cast<uint32_t *>(smem + 4 * RING + 8 * I8S_META_BYTES); // [64]
     unsigned char *stage_base = smem + 4 * RING + 8 * I8S_META_BYTES + 256;
-    unsigned char *qlo_lds = stage_base + I8S_STAGE_LDS; // [NQT][KSTEPS][64 lanes][16 B], shared by the four waves
+    unsigned char *qlo_lds = stage_base + OI_STAGE_LDS; // [NQT][KSTEPS][64 lanes][16 B], shared by the four waves
 
     OI_CLAIM_WHOLE_SIMD(); // (MFMA kernel: nothing else may run on this CU -- oi_device.h)
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t li = lane & 31, lh = lane >> 5;
-    uint64_t *stage_keys = reinterpret_cast<uint64_t *>(stage_base) + w * I8S_STAGE;
-    uint32_t *stage_q = reinterpret_cast<uint32_t *>(stage_base + 4 * I8S_STAGE * 8) + w * I8S_STAGE;
+    uint64_t *stage_keys = reinterpret_cast<uint64_t *>(stage_base) + w * OI_STAGE;
+    uint32_t *stage_q = reinterpret_cast<uint32_t *>(stage_base + 4 * OI_STAGE * 8) + w * OI_STAGE;
     uint32_t st_head = 0, st_n = 0;
 
     // ---- every query over the whole K: B[k = 32 s + 16 lh + 0..15][n = li].  The hi parts in registers for the whole launch (192
@@ -369,9 +306,9 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
             const uint32_t prow = 8 * m + (lane >> 3);
             voff[m] = prow * (uint32_t)D + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
         }
-        const uint32_t ring_w = i8s_lds_addr(ring) + w * RING;
+        const uint32_t ring_w = oi_lds_addr(ring) + w * RING;
         const unsigned char *ring_rd = ring + w * RING;
-        const uint32_t meta_w = i8s_lds_addr(meta_lds) + w * 2 * I8S_META_BYTES;
+        const uint32_t meta_w = oi_lds_addr(meta_lds) + w * 2 * I8S_META_BYTES;
         const unsigned char *meta_rd = meta_lds + w * 2 * I8S_META_BYTES;
         // fragment of MFMA group g of a slot: row li, i8 32 g + 16 lh + 0..15 = logical 16-B column 2g + lh
         uint32_t frag_off[4];
@@ -381,15 +318,15 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
         auto tile_row0 = [&](uint64_t ti) { return row_begin + (first + ti * stride) * (uint64_t)I8S_TILE_ROWS; };
         auto tile_srd = [&](uint64_t ti) { // past this wave's last tile: an EMPTY descriptor (loads return zeros)
             const uint64_t r0 = tile_row0(ti < my_nt ? ti : 0);
-            return i8s_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)D : 0ull);
+            return oi_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)D : 0ull);
         };
         auto issue_meta = [&](uint64_t ti) { // rows past the end read as zeros (scale 0); called for ti < my_nt only
             const uint64_t r0 = tile_row0(ti);
-            i8s_issue_meta(i8s_make_srd(meta + 2 * r0, (row_end - r0) * 8ull), lane * 4u, meta_w + (uint32_t)(ti & 1) * I8S_META_BYTES);
+            i8s_issue_meta(oi_make_srd(meta + 2 * r0, (row_end - r0) * 8ull), lane * 4u, meta_w + (uint32_t)(ti & 1) * I8S_META_BYTES);
         };
-        i8s_u32x4 s0 = tile_srd(0), s1 = tile_srd(1), s2 = tile_srd(2);
-        __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): every load hipcc knows about is retired here (cosine_screen_copy.hip)
-        i8s_static_for<0, P>([&](auto j_) {
+        oi_u32x4 s0 = tile_srd(0), s1 = tile_srd(1), s2 = tile_srd(2);
+        __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): every load hipcc knows about is retired here (oi_lds_dma.h)
+        oi_static_for<0, P>([&](auto j_) {
             constexpr int j = decltype(j_)::value;
             constexpr int tj = j / NKC, kj = j % NKC;
 #pragma unroll
@@ -411,7 +348,7 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
 #endif
 
         // (the meta load between the pieces only makes a counted wait wait for one piece more)
-        i8s_wait<4 * (P - 1)>();
+        oi_wait_vm<4 * (P - 1)>();
         i8s_i32x4 a_cur = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + frag_off[0]);
 
         for (uint64_t ti = 0; ti < my_nt; ++ti) {
@@ -421,7 +358,7 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { ah[t][r] = 0; al[t][r] = 0; }
 
-            i8s_static_for<0, NKC * 4>([&](auto gi_) {
+            oi_static_for<0, NKC * 4>([&](auto gi_) {
                 constexpr int gi = decltype(gi_)::value;
                 constexpr int kc = gi / 4, g = gi % 4;
                 constexpr int sn = kc + P;
@@ -433,7 +370,7 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
                 } else {
                     // the next slot (after the tile's last slot: the next tile's first; past the last tile: zeros nobody uses).
                     // Slots kc + 2 .. kc + P - 1 and three pieces of slot kc + P are younger than its pieces.
-                    i8s_wait<4 * (P - 1) - 1>();
+                    oi_wait_vm<4 * (P - 1) - 1>();
                     const uint32_t nx_off = rd_off + I8S_SLOT_BYTES == RING ? 0u : rd_off + I8S_SLOT_BYTES;
                     a_nxt = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + nx_off + frag_off[0]);
                 }
@@ -465,7 +402,7 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
             // ---- this tile's metadata: issued before the 4 NKC pieces of this tile's refills, so vmcnt(4 NKC) retires it.
             // Register r of query tile t holds D[row (r&3) + 8 (r>>2) + 4 lh][query 32 t + li]: rows 8 j + 4 lh + 0..3, 32 B of
             // {scale, e_r}, read four rows at a time (the query block leaves ~60 registers for everything else)
-            i8s_wait<4 * NKC>();
+            oi_wait_vm<4 * NKC>();
             const unsigned char *mt = meta_rd + (uint32_t)(ti & 1) * I8S_META_BYTES;
             auto meta4 = [&](int j, float (&sr)[4], float (&er)[4]) {
                 const i8s_f32x4 u0 = *reinterpret_cast<const i8s_f32x4 *>(mt + (8 * j + 4 * lh) * 8);
@@ -511,9 +448,9 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
             if (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull) {
                 if constexpr (FILT) m = oi_filter_tile<NQT>(m, filt, attrs, row0, lh, li);
                 const uint32_t cnt = (uint32_t)__builtin_popcount(m);
-                const uint32_t incl = i8s_incl_scan(cnt);
+                const uint32_t incl = oi_wave_incl_scan(cnt);
                 const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                if (total <= I8S_STAGE - I8S_STAGE_FLUSH) {
+                if (total <= OI_STAGE - OI_STAGE_FLUSH) {
                     uint32_t idx = st_head + st_n + incl - cnt;
 #pragma unroll
                     for (int t = 0; t < NQT; ++t)
@@ -521,13 +458,13 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
                         for (int r = 0; r < 16; ++r)
                             if (m & (1u << (16 * t + r))) {
                                 const uint32_t row = (uint32_t)row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                                stage_keys[idx & (I8S_STAGE - 1)] = lower_key(t, r, row);
-                                stage_q[idx & (I8S_STAGE - 1)] = 32u * t + li;
+                                stage_keys[idx & (OI_STAGE - 1)] = lower_key(t, r, row);
+                                stage_q[idx & (OI_STAGE - 1)] = 32u * t + li;
                                 ++idx;
                             }
                     st_n += total;
-                    while (st_n >= I8S_STAGE_FLUSH) {
-                        I8S_FLUSH(I8S_STAGE_FLUSH);
+                    while (st_n >= OI_STAGE_FLUSH) {
+                        OI_STAGE_FLUSH_TO_POOL(OI_STAGE_FLUSH);
                     }
                 } else {
                     uint32_t pos[NQT];
@@ -556,9 +493,9 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
             s2 = tile_srd(ti + 3);
         }
         if (st_n) {
-            I8S_FLUSH(st_n);
+            OI_STAGE_FLUSH_TO_POOL(st_n);
         }
-        i8s_wait<0>(); // the zero-filling refills issued past the last tile have landed before the LDS goes back
+        oi_wait_vm<0>(); // the zero-filling refills issued past the last tile have landed before the LDS goes back
     }
     __syncthreads();
     if (tid < 32 * NQT && tid < n_queries) {
@@ -570,7 +507,7 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
 template <int D, int NQT, int NBUF, bool FILT>
 static int launch_i8_screen_k(oi_ctx *ctx, const uint8_t *rows, const float *meta, uint64_t row_begin, uint64_t row_end, const int8_t *qhi,
                               const int8_t *qlo, const float *qf, uint32_t qf_stride, uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
-    constexpr size_t smem = 4 * NBUF * I8S_SLOT_BYTES + 8 * I8S_META_BYTES + 256 + I8S_STAGE_LDS + NQT * (D / 32) * 64 * 16;
+    constexpr size_t smem = 4 * NBUF * I8S_SLOT_BYTES + 8 * I8S_META_BYTES + 256 + OI_STAGE_LDS + NQT * (D / 32) * 64 * 16;
     OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(cosine_i8_screen<D, NQT, NBUF, FILT>), (size_t)(smem)));
     hipLaunchKernelGGL((cosine_i8_screen<D, NQT, NBUF, FILT>), dim3(p.n_segs), dim3(256), smem, ctx->stream, rows, meta, row_begin, row_end,
                        qhi, qlo, qf, qf_stride, nq, doc_id_base, p.keys, p.seg_cnt, p.seg_cnt_stride, p.tau_keys, p.stride, p.carry_cap,
@@ -601,12 +538,7 @@ int oi_launch_cosine_screen_i8_chunk(oi_ctx *ctx, const uint8_t *i8_copy, uint64
     ProfScope ps(ctx, "cosine");
     for (uint32_t q0 = 0; q0 < n_queries; q0 += 64) {
         const uint32_t nq_here = std::min(64u, n_queries - q0);
-        PoolView p = pool;
-        p.keys += (uint64_t)q0 * pool.stride;
-        p.carry_cnt += q0;
-        p.seg_cnt += (uint64_t)q0 * pool.seg_cnt_stride;
-        p.tau_keys += q0;
-        if (p.filt) p.filt += q0;
+        const PoolView p = pool.for_queries(q0);
         const int8_t *qhi = qi8 + (uint64_t)q0 * dim, *qlo = qi8 + ((uint64_t)np + q0) * dim;
         const float *qfp = qf + q0;
         const bool two = nq_here > 32;

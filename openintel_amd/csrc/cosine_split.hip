@@ -14,8 +14,8 @@
 // Shape: one workgroup per CU, 4 waves splitting K (wave w owns k in [w D/4, (w+1) D/4)):
 //   * the wave's K-slice of all 64 queries, already split into (H, M, L) bf16 planes by the staging
 //     kernel, lives in registers as MFMA B operands (3 x 96 VGPRs at d = 768);
-//   * the f32 rows stream through the wave's own LDS ring exactly as in cosine_ksplit.hip (4 KiB slots of
-//     32 rows x 32 floats, buffer_load ... lds, counted vmcnt waits, prefetch across tiles);
+//   * the f32 rows stream through the wave's own LDS ring (4 KiB slots of 32 rows x 32 floats; oi_lds_dma.h:
+//     buffer_load ... lds, counted vmcnt waits; the prefetch runs across tiles);
 //   * per 16 k: two ds_read_b128 (the lane's 8 consecutive floats), ~44 VALU to split and pack them into
 //     the three A operands -- issued in the shadow of the 12 MFMAs (32 cycles each) they feed;
 //   * the big term hH accumulates apart from the five small ones (added at the end), then the four waves'
@@ -26,54 +26,15 @@
 
 #include "oi_device.h"
 #include "oi_internal.h"
+#include "oi_lds_dma.h"
 
 typedef float cs_f32x16 __attribute__((ext_vector_type(16)));
 typedef float cs_f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 cs_bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t cs_u32x4 __attribute__((ext_vector_type(4)));
 
 #define CS_TILE_ROWS 32
 #define CS_SLOT_BYTES 4096 // 32 rows x 128 B (32 floats of K)
 
-__device__ __forceinline__ uint32_t cs_lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)p;
-}
-__device__ __forceinline__ cs_u32x4 cs_make_srd(const float *base, uint64_t bytes) {
-    const uint64_t b = (uint64_t)base;
-    cs_u32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    r[1] = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32) & 0xFFFFu);
-    r[2] = __builtin_amdgcn_readfirstlane((uint32_t)(bytes > 0xFFFFFFFFull ? 0xFFFFFFFFull : bytes));
-    r[3] = 0x00020000u;
-    return r;
-}
-__device__ __forceinline__ void cs_issue_piece(const cs_u32x4 &srd, uint32_t voff, uint32_t soff, uint32_t lds_dst,
-                                               bool skip) {
-    if (skip) return;
-    uint32_t keep;
-    const uint32_t d = __builtin_amdgcn_readfirstlane(lds_dst);
-    const uint32_t so = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %4\n\t"
-        "s_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %2, %3 offen " OI_DMA_NT "lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(srd), "s"(so), "s"(d)
-        : "memory");
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void cs_static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        cs_static_for<I + 1, N>(f);
-    }
-}
-template <int N>
-__device__ __forceinline__ void cs_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 __device__ __forceinline__ void cs_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // 8 consecutive floats of a row -> the three bf16x8 A operands (h, m, l), x = h + m + l exactly.
@@ -151,13 +112,13 @@ __global__ __launch_bounds__(256, 1) void cosine_split_filter(
     if (my_nt == 0) return;
     uint64_t *my_seg = pools + carry_cap + (uint64_t)blockIdx.x * seg_cap;
 
-    uint32_t voff[4]; // per-lane source of the 4 DMA pieces of a slot (cosine_ksplit.hip: same swizzle)
+    uint32_t voff[4]; // per-lane source of the 4 DMA pieces of a slot (swizzled: 16-B column c of row r at c ^ ((r >> 1) & 7))
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
         const uint32_t prow = 8 * m + (lane >> 3);
         voff[m] = prow * (uint32_t)(D * 4) + w * (uint32_t)(KS * 4) + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
     }
-    const uint32_t ring_w = cs_lds_addr(ring) + w * (NBUF * CS_SLOT_BYTES);
+    const uint32_t ring_w = oi_lds_addr(ring) + w * (NBUF * CS_SLOT_BYTES);
     const unsigned char *ring_rd = ring + w * (NBUF * CS_SLOT_BYTES);
     // fragment (slot half g in {0,1}): the lane's floats 16 g + 8 lh .. + 8 = logical 16-B columns 4g + 2lh, + 1
     uint32_t frag_off[2][2];
@@ -172,15 +133,15 @@ __global__ __launch_bounds__(256, 1) void cosine_split_filter(
     // scheduler interleave the split arithmetic with the MFMAs.
     auto tile_srd = [&](uint64_t ti) {
         const uint64_t r0 = tile_row0(ti < my_nt ? ti : 0);
-        return cs_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 4) : 0ull);
+        return oi_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 4) : 0ull);
     };
-    cs_u32x4 cur = tile_srd(0), nxt = tile_srd(1);
+    oi_u32x4 cur = tile_srd(0), nxt = tile_srd(1);
     __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only: retire every load hipcc knows about, here
 #pragma unroll
     for (int kc = 0; kc < P; ++kc)
 #pragma unroll
         for (int m = 0; m < 4; ++m)
-            cs_issue_piece(cur, voff[m], kc * 128, ring_w + (kc % NBUF) * CS_SLOT_BYTES + m * 1024, (DBG & 1) != 0);
+            oi_dma_piece(cur, voff[m], kc * 128, ring_w + (kc % NBUF) * CS_SLOT_BYTES + m * 1024, (DBG & 1) != 0);
     float *my_red = red + w * RED;
 
     // ---- deferred epilogue (as in cosine_ksplit.hip).  A tile's partial sums go to LDS right after its last
@@ -220,7 +181,7 @@ __global__ __launch_bounds__(256, 1) void cosine_split_filter(
 #pragma unroll
         for (int r = 0; r < 16; ++r) cor2[0][r] = 0.f;
 
-        cs_wait<4 * (P - 1)>();
+        oi_wait_vm<4 * (P - 1)>();
         cs_bf16x8 ah, am, al; // A operands of the current k-step
         {
             const cs_f32x4 f0 = *reinterpret_cast<const cs_f32x4 *>(ring_rd + frag_off[0][0]);
@@ -228,7 +189,7 @@ __global__ __launch_bounds__(256, 1) void cosine_split_filter(
             if constexpr ((DBG & 4) != 0) { CsPack pk; pk.u[0] = __float_as_uint(f0[0]); pk.u[1] = __float_as_uint(f0[1]); pk.u[2] = __float_as_uint(f1[0]); pk.u[3] = __float_as_uint(f1[1]); ah = am = al = pk.v; }
             else cs_split8(f0, f1, ah, am, al);
         }
-        cs_static_for<0, NG>([&](auto gi_) {
+        oi_static_for<0, NG>([&](auto gi_) {
             constexpr int gi = decltype(gi_)::value; // k-step of the tile
             constexpr int kc = gi / 2, g = gi % 2;
             constexpr int sn = kc + P;               // slot refilled during this slot's k-steps
@@ -283,9 +244,9 @@ __global__ __launch_bounds__(256, 1) void cosine_split_filter(
 #pragma unroll
             for (int m = 2 * g; m < 2 * g + 2; ++m) {
                 if constexpr (sn < NKC)
-                    cs_issue_piece(cur, voff[m], sn * 128, ring_w + (sn % NBUF) * CS_SLOT_BYTES + m * 1024, (DBG & 1) != 0);
+                    oi_dma_piece(cur, voff[m], sn * 128, ring_w + (sn % NBUF) * CS_SLOT_BYTES + m * 1024, (DBG & 1) != 0);
                 else
-                    cs_issue_piece(nxt, voff[m], (sn - NKC) * 128, ring_w + (sn % NBUF) * CS_SLOT_BYTES + m * 1024,
+                    oi_dma_piece(nxt, voff[m], (sn - NKC) * 128, ring_w + (sn % NBUF) * CS_SLOT_BYTES + m * 1024,
                                    (DBG & 1) != 0);
             }
             if constexpr (gi == EPI_G0 - 1 && !(DBG & 8)) cs_barrier();                        // (A) partials visible
@@ -297,7 +258,7 @@ __global__ __launch_bounds__(256, 1) void cosine_split_filter(
             if constexpr (gi == EPI_GB && !(DBG & 8)) cs_barrier();                            // (B) `red` is free again
             // the next k-step reads slot kc + 1 when this one is the slot's first half: it has to have landed
             // (the two pieces of slot kc + P issued just above may still be in flight with P - 2 younger slots)
-            if constexpr (g == 0 && kc + 1 < NKC) cs_wait<4 * (P - 2) + 2>();
+            if constexpr (g == 0 && kc + 1 < NKC) oi_wait_vm<4 * (P - 2) + 2>();
             ah = nh; am = nm; al = nl;
         });
 

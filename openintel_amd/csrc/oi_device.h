@@ -127,6 +127,17 @@ __device__ __forceinline__ uint32_t oi_wave_sum(uint32_t v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, OI_WAVE);
     return v;
 }
+// Wave-wide inclusive prefix sum in six DPP steps (the sequence LLVM's atomic optimizer emits for gfx9): no LDS round trips,
+// unlike __shfl_up.  Lane 63 holds the total.
+__device__ __forceinline__ uint32_t oi_wave_incl_scan(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
+    return v;
+}
 
 // The doc filter of a filtered search (oi_doc_filter): f = {group_mask, group_value, stamp_lo, stamp_hi} of the
 // query, a = {group, stamp} of the row (oi_index_set_doc_attrs).  Tested only where a kernel has a hit, after its threshold.

@@ -276,6 +276,18 @@ struct PoolView {
     // attrs[row] = {group, stamp} of local row `row`.  Null: unfiltered (the kernels' unfiltered instantiations).
     const uint4 *filt = nullptr;
     const uint2 *attrs = nullptr;
+
+    // The same pools seen from query q0 on (a launcher's pass over queries q0 .. q0 + 63): every per-query array moves,
+    // a null tau_keys / filt stays null, geometry, overflow and attrs (per row) stay.
+    PoolView for_queries(uint32_t q0) const {
+        PoolView p = *this;
+        p.keys += (uint64_t)q0 * stride;
+        p.carry_cnt += q0;
+        p.seg_cnt += (uint64_t)q0 * seg_cnt_stride;
+        if (p.tau_keys) p.tau_keys += q0;
+        if (p.filt) p.filt += q0;
+        return p;
+    }
 };
 // Optional behaviour of a select launch (cosine_prefilter.hip): eps2 != null = margin mode (keep every key within
 // eps2[q] of the k-th score; needs compact, no sorted output, carry_cap >= 4096; an overflowing query sets

@@ -317,16 +317,6 @@ __device__ __forceinline__ void sel_append(uint64_t *dst, uint32_t *count, uint3
     if (take && pos < cap) dst[pos] = key;
 }
 
-// wave-wide inclusive prefix sum in DPP steps (no LDS round trips, unlike __shfl_up)
-__device__ __forceinline__ uint32_t sel_incl_scan(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
-    return v;
-}
 // hist[digit] += weight for the active lanes; the two most common digits of the wave go in as one atomic each
 __device__ __forceinline__ void sel_hist_add_w(uint32_t *hist, bool active, uint32_t digit, uint32_t weight) {
     const uint32_t lane = threadIdx.x & 63;
@@ -337,7 +327,7 @@ __device__ __forceinline__ void sel_hist_add_w(uint32_t *hist, bool active, uint
         const uint32_t leader = (uint32_t)__builtin_ctzll(m);
         const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)digit, (int)leader);
         const bool same = active && digit == d0;
-        const uint32_t sum = (uint32_t)__builtin_amdgcn_readlane((int)sel_incl_scan(same ? weight : 0u), 63);
+        const uint32_t sum = (uint32_t)__builtin_amdgcn_readlane((int)oi_wave_incl_scan(same ? weight : 0u), 63);
         if (lane == leader) atomicAdd(&hist[d0], sum);
         active = active && !same;
     }
@@ -512,7 +502,7 @@ __device__ __forceinline__ uint32_t sel_flat_select(const SelFlat &K, uint32_t k
             __syncthreads();
             if (tid < 64) { // wave 0: the super-bin, then the bin, holding the kk-th key counted from the top -- two scans, no walk
                 const uint32_t x = sh.hist[63u - tid];
-                const uint32_t incl = sel_incl_scan(x);
+                const uint32_t incl = oi_wave_incl_scan(x);
                 const unsigned long long ball = __ballot(incl >= kk);
                 if (!ball) {
                     if (tid == 0) sh.bin_cnt = 0xFFFFFFFFu; // fewer than kk valid keys
@@ -520,7 +510,7 @@ __device__ __forceinline__ uint32_t sel_flat_select(const SelFlat &K, uint32_t k
                     const uint32_t l1 = (uint32_t)__builtin_ctzll(ball), sb = 63u - l1;
                     const uint32_t kk2 = kk - (uint32_t)__builtin_amdgcn_readlane((int)(incl - x), (int)l1);
                     const uint32_t y = tid < 32u ? sh.hist2k[32u * sb + 31u - tid] : 0u;
-                    const uint32_t incl2 = sel_incl_scan(y);
+                    const uint32_t incl2 = oi_wave_incl_scan(y);
                     const unsigned long long ball2 = __ballot(incl2 >= kk2); // (non-empty: the super-bin holds >= kk2 keys)
                     const uint32_t l2 = ball2 ? (uint32_t)__builtin_ctzll(ball2) : 31u;
                     // (read with every lane active: inside the one-lane branch below hipcc computes incl2 - y for that lane only)
@@ -560,7 +550,7 @@ __device__ __forceinline__ uint32_t sel_flat_select(const SelFlat &K, uint32_t k
             const float edge = oi_key_f32(tkey);
             auto keep = [&](bool valid, uint64_t kv) { return valid && (uint32_t)(kv >> 32) >= t32 && sel_row_keep(rm, kv, edge, eps2); };
             for_each([&](bool valid, uint64_t kv) { mine += keep(valid, kv) ? 1u : 0u; });
-            const uint32_t incl = sel_incl_scan(mine);
+            const uint32_t incl = oi_wave_incl_scan(mine);
             const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             uint32_t base = 0;
             if (lane == 0 && tot) base = atomicAdd(&sh.cnt, tot);
@@ -710,7 +700,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_flat_kernel(
         c[u] = v;
         local += v;
     }
-    const uint32_t incl = sel_incl_scan(local);
+    const uint32_t incl = oi_wave_incl_scan(local);
     if (lane == 63) sh.wave_tot[wv] = incl;
     if (tid == 0) { sh.cnt = 0; sh.min_key = ~0ull; }
     __syncthreads();

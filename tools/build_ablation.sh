@@ -6,9 +6,11 @@ set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $R/openintel_amd/csrc/_obj_abl
 cd $R/openintel_amd/csrc/_obj_abl
+# an object is stale when its source or ANY header is newer (openintel_amd/build.py: _deps_mtime)
+newest_h=$(ls -t $R/openintel_amd/csrc/*.h $R/include/openintel_hip.h | head -1)
 for f in $R/openintel_amd/csrc/*.hip; do
   o=$(basename ${f%.hip}).o
-  if [ "$1" = "--force" ] || [ ! -f $o ] || [ $f -nt $o ] || [ $R/openintel_amd/csrc/oi_internal.h -nt $o ]; then
+  if [ "$1" = "--force" ] || [ ! -f $o ] || [ $f -nt $o ] || [ $newest_h -nt $o ]; then
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -DOI_ABLATION ${OI_ABL_EXTRA:-} -Wno-unused-result -I$R/include -I$R/openintel_amd/csrc -c $f -o $o &
   fi
 done
