@@ -362,6 +362,8 @@ int oi_index_set_max_query_terms(oi_index *idx, uint32_t max_terms);
  * Outputs, each n_queries x depth, row q sorted by (score desc, doc id asc),
  * first counts[q] entries valid:
  *   cosine list: dot(query, row);  BM25 list: only docs with score > 0.
+ * Non-finite rows (OI_COSINE_EXACT): a row whose dot product is NaN under IEEE arithmetic (0 x inf and inf - inf included) is
+ * never listed and a +inf or -inf score ranks where IEEE orders it, whatever the batch size.
  */
 int oi_search_lists(oi_index *idx, const float *query_vecs, const uint32_t *query_terms,
                     const uint32_t *q_term_offsets, uint32_t n_queries, uint32_t depth,

@@ -52,16 +52,26 @@ __global__ __launch_bounds__(256) void cosine_gemv_filter(const float *__restric
     uint32_t tau = 0;
     if (lane < NQ) tau = tau_keys[lane];
 
-    // Two rows per trip, every load unpredicated (a lane past the row's end re-reads the row's last float4
-    // and multiplies it by the zeros its query registers hold there): all of a trip's loads are in flight
-    // together instead of each waiting at the end of its own branch.
+    // Two rows per trip, every load unpredicated (a lane past the row's end re-reads the row's last float4):
+    // all of a trip's loads are in flight together instead of each waiting at the end of its own branch.
+    // What such a lane re-read is replaced by zeros with a select, not multiplied by the zeros its query
+    // registers hold there: 0 x inf is NaN, and a row with an infinity in its last float4 would lose its score
+    // (tests/test_gpu_exact_edges.py: the same batch at B = 8 and B = 9).
     uint32_t vidx[4];
+    bool live[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const uint32_t v = lane + 64u * c;
-        vidx[c] = v < nvec ? v : nvec - 1u;
+        live[c] = v < nvec;
+        vidx[c] = live[c] ? v : nvec - 1u;
     }
-    auto score_row = [&](const float4 (&x)[4], uint64_t r) {
+    auto score_row = [&](const float4 (&xl)[4], uint64_t r) {
+        float4 x[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { // (per component: four v_cndmask, no branch around a copy)
+            x[c].x = live[c] ? xl[c].x : 0.f; x[c].y = live[c] ? xl[c].y : 0.f;
+            x[c].z = live[c] ? xl[c].z : 0.f; x[c].w = live[c] ? xl[c].w : 0.f;
+        }
         float mine = 0.f;
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
