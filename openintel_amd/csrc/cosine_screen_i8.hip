@@ -35,6 +35,7 @@
 // own LDS ring of 4 KiB slots (32 rows x 128 i8) with buffer_load ... lds, ordered by counted s_waitcnt vmcnt.  Per 32 k of a tile:
 // one ds_read_b128, 2 NQT v_mfma_i32_32x32x32_i8 (the cycles of the bf16 32x32x16: the matrix time per tile is the bf16 screen's,
 // the bytes are half).  The tile's 32 {scale, e_r} pairs (256 B) ride one more LDS-DMA load, issued a tile ahead.
+// The test of a tile against those pairs runs inside the NEXT tile's matrix span, its survivors leave after that span.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -46,7 +47,11 @@
 
 typedef int i8s_i32x4 __attribute__((ext_vector_type(4)));
 typedef int i8s_i32x16 __attribute__((ext_vector_type(16)));
-typedef float i8s_f32x4 __attribute__((ext_vector_type(4)));
+typedef float i8s_f32x2 __attribute__((ext_vector_type(2)));
+template <int N>
+struct i8s_ivec {
+    typedef int type __attribute__((ext_vector_type(N)));
+};
 
 #define I8S_TILE_ROWS 32
 #define I8S_SLOT_BYTES (I8S_TILE_ROWS * 128) // 32 rows x 128 i8 of K
@@ -351,84 +356,129 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
         oi_wait_vm<4 * (P - 1)>();
         i8s_i32x4 a_cur = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + frag_off[0]);
 
-        for (uint64_t ti = 0; ti < my_nt; ++ti) {
-            i8s_i32x16 ah[NQT], al[NQT];
+        // ---- The tile test runs ONE TILE LATE, inside the next tile's matrix span (the matrix pipe was idle through it, and no
+        // piece was issued).  After a tile's last MFMA its S = 128 S_h + S_l goes to registers of its own (S); the accumulators
+        // are cleared and the next tile starts; k-steps T0 .. T0 + NSL - 1 of that span each test RPK register rows of S against
+        // the row's {scale, e_r}, read from the tile's meta slot a k-step ahead.  The survivor path and the refill of the meta
+        // slot follow the span; the last tile of a wave is tested after the loop, in the iteration without a span.  Tile 0's span
+        // tests a "tile -1" (S = 0, whatever the meta slot holds) whose mask is dropped.
+        // The meta ring: tile i's pairs are in slot i & 1, issued at the end of iteration i - 1 (tile 0: before the loop), read by
+        // span i + 1 and by the survivor path after it; then the slot takes tile i + 2's.
+        // vmcnt: the first meta read of span i + 1 sits in k-step T0 - 1 = 3 behind the ring's own wait vmcnt(4 (P - 1) - 1).
+        // Younger than tile i's meta load by then: the 4 NKC pieces of span i, tile i + 1's meta load (span i + 1 exists, so it
+        // was issued), three pieces of span i + 1 and whatever the survivor path stored: at least 4 NKC + 4, and the ring's wait
+        // leaves no more than 4 (P - 1) - 1 outstanding.  (The iteration without a span waits for everything.)
+        constexpr int NS = 16 * NQT;
+        constexpr int RPK = KSTEPS >= 20 ? 1 : 2; // register rows tested per k-step
+        constexpr int NSL = 16 / RPK, T0 = 4;     // slices, the first slice's k-step
+        static_assert(T0 + NSL <= KSTEPS, "the tile test does not fit the span");
+        static_assert(4 * NKC + 4 >= 4 * (P - 1) - 1, "the ring's wait in k-step 3 must retire the previous tile's metadata");
+        typename i8s_ivec<NS>::type S;
 #pragma unroll
-            for (int t = 0; t < NQT; ++t)
+        for (int i = 0; i < NS; ++i) S[i] = 0;
+        i8s_i32x16 ah[NQT], al[NQT];
+        i8s_f32x2 md_cur[RPK];
 #pragma unroll
-                for (int r = 0; r < 16; ++r) { ah[t][r] = 0; al[t][r] = 0; }
+        for (int u = 0; u < RPK; ++u) md_cur[u] = i8s_f32x2{0.f, 0.f};
+        // Register r of query tile t holds D[row (r&3) + 8 (r>>2) + 4 lh][query 32 t + li]
+        const uint32_t lh32 = 32u * lh;
+        auto meta_row = [&](const unsigned char *mt, int r) { // {scale, e_r} of register row r
+            return *reinterpret_cast<const i8s_f32x2 *>(mt + lh32 + ((r & 3) + 8 * (r >> 2)) * 8);
+        };
+        // keep (q, r) when s~ + e_r |q^| + c_q >= T.  Single v_mul_f32 / v_fma_f32: left to itself hipcc pairs the two query
+        // tiles' products into v_pk_*_f32 ... op_sel between the MFMAs, the form DESIGN section 7 found losing products there.
+        auto test_row = [&](int t, int r, const i8s_f32x2 md) -> uint32_t {
+            const float sc = oi_mul_unpacked((float)S[16 * t + r], oi_mul_unpacked(md[0], qa[t]));
+            return sc >= oi_fma_unpacked(-md[1], qn[t], tc[t]) ? 1u << (16 * t + r) : 0u;
+        };
 
-            oi_static_for<0, NKC * 4>([&](auto gi_) {
-                constexpr int gi = decltype(gi_)::value;
-                constexpr int kc = gi / 4, g = gi % 4;
-                constexpr int sn = kc + P;
-                constexpr int tn = sn / NKC, kn = sn % NKC;
-                // ---- the reads of k-step gi + 1, into registers no MFMA in flight reads
-                i8s_i32x4 a_nxt;
-                if constexpr (g < 3) {
-                    a_nxt = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + rd_off + frag_off[g + 1]);
-                } else {
-                    // the next slot (after the tile's last slot: the next tile's first; past the last tile: zeros nobody uses).
-                    // Slots kc + 2 .. kc + P - 1 and three pieces of slot kc + P are younger than its pieces.
-                    oi_wait_vm<4 * (P - 1) - 1>();
-                    const uint32_t nx_off = rd_off + I8S_SLOT_BYTES == RING ? 0u : rd_off + I8S_SLOT_BYTES;
-                    a_nxt = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + nx_off + frag_off[0]);
-                }
-#ifndef I8S_NO_MFMA // (ablation builds: the stream without the matrix instructions; every score 0, results WRONG)
-                i8s_i32x4 b_nxt[NQT];
-#pragma unroll
-                for (int t = 0; t < NQT; ++t) b_nxt[t] = lo_frag(t, (gi + 1) % KSTEPS);
-                // (without this the compiler sinks the reads back next to their use and waits for each with lgkmcnt(0); with
-                // it it retires them with counted waits -- tests/test_screen_i8_schedule.py)
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int t = 0; t < NQT; ++t) {
-                    ah[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_cur, qh[t][gi], ah[t], 0, 0, 0);
-                    al[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_cur, b_cur[t], al[t], 0, 0, 0);
-                }
-#pragma unroll
-                for (int t = 0; t < NQT; ++t) b_cur[t] = b_nxt[t];
-#else
-                asm volatile("" : : "v"(a_cur));
-#endif
-                i8s_issue_piece(tn == 0 ? s0 : (tn == 1 ? s1 : s2), voff[g], kn * 128, ring_w + wr_off + g * 1024);
-                if constexpr (g == 3) {
-                    wr_off = rd_off;
-                    rd_off = rd_off + I8S_SLOT_BYTES == RING ? 0u : rd_off + I8S_SLOT_BYTES;
-                }
-                a_cur = a_nxt;
-            });
-
-            // ---- this tile's metadata: issued before the 4 NKC pieces of this tile's refills, so vmcnt(4 NKC) retires it.
-            // Register r of query tile t holds D[row (r&3) + 8 (r>>2) + 4 lh][query 32 t + li]: rows 8 j + 4 lh + 0..3, 32 B of
-            // {scale, e_r}, read four rows at a time (the query block leaves ~60 registers for everything else)
-            oi_wait_vm<4 * NKC>();
-            const unsigned char *mt = meta_rd + (uint32_t)(ti & 1) * I8S_META_BYTES;
-            auto meta4 = [&](int j, float (&sr)[4], float (&er)[4]) {
-                const i8s_f32x4 u0 = *reinterpret_cast<const i8s_f32x4 *>(mt + (8 * j + 4 * lh) * 8);
-                const i8s_f32x4 u1 = *reinterpret_cast<const i8s_f32x4 *>(mt + (8 * j + 4 * lh) * 8 + 16);
-                sr[0] = u0[0]; er[0] = u0[1]; sr[1] = u0[2]; er[1] = u0[3];
-                sr[2] = u1[0]; er[2] = u1[1]; sr[3] = u1[2]; er[3] = u1[3];
-            };
-            auto score = [&](int t, int r, float sr) -> float {
-                const int S = ah[t][r] * 128 + al[t][r];
-                return (float)S * (sr * qa[t]);
-            };
-
-            // ---- filter + append: keep (q, r) when s~ + e_r |q^| + c_q >= T; the key is the lower bound s~ - e_r |q^| - c_q
-            const uint64_t row0 = tile_row0(ti);
+        for (uint64_t ti = 0;; ++ti) {
+            const bool live = ti < my_nt; // (the last iteration has no span: it tests and drains the last tile)
+            const unsigned char *mt = meta_rd + (uint32_t)((ti + 1) & 1) * I8S_META_BYTES; // tile ti - 1's
             uint32_t m = 0;
+            if (live) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float sr[4], er[4];
-                meta4(j, sr, er);
+                for (int t = 0; t < NQT; ++t)
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
+                    for (int r = 0; r < 16; ++r) { ah[t][r] = 0; al[t][r] = 0; }
+
+                oi_static_for<0, NKC * 4>([&](auto gi_) {
+                    constexpr int gi = decltype(gi_)::value;
+                    constexpr int kc = gi / 4, g = gi % 4;
+                    constexpr int sn = kc + P;
+                    constexpr int tn = sn / NKC, kn = sn % NKC;
+                    // ---- the reads of k-step gi + 1, into registers no MFMA in flight reads
+                    i8s_i32x4 a_nxt;
+                    if constexpr (g < 3) {
+                        a_nxt = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + rd_off + frag_off[g + 1]);
+                    } else {
+                        // the next slot (after the tile's last slot: the next tile's first; past the last tile: zeros nobody
+                        // uses).  Slots kc + 2 .. kc + P - 1 and three pieces of slot kc + P are younger than its pieces.
+                        oi_wait_vm<4 * (P - 1) - 1>();
+                        const uint32_t nx_off = rd_off + I8S_SLOT_BYTES == RING ? 0u : rd_off + I8S_SLOT_BYTES;
+                        a_nxt = *reinterpret_cast<const i8s_i32x4 *>(ring_rd + nx_off + frag_off[0]);
+                    }
+                    i8s_f32x2 md_nxt[RPK];
+                    if constexpr (gi >= T0 - 1 && gi < T0 - 1 + NSL) {
 #pragma unroll
-                    for (int t = 0; t < NQT; ++t)
-                        m |= score(t, 4 * j + i, sr[i]) >= fmaf(-er[i], qn[t], tc[t]) ? 1u << (16 * t + 4 * j + i) : 0u;
-                asm volatile("" ::: "memory"); // (one group of metadata live at a time)
+                        for (int u = 0; u < RPK; ++u) md_nxt[u] = meta_row(mt, RPK * (gi - (T0 - 1)) + u);
+                    }
+#ifndef I8S_NO_MFMA // (ablation builds: the stream without the matrix instructions; every score 0, results WRONG)
+                    i8s_i32x4 b_nxt[NQT];
+#pragma unroll
+                    for (int t = 0; t < NQT; ++t) b_nxt[t] = lo_frag(t, (gi + 1) % KSTEPS);
+#endif
+                    // (without this the compiler sinks the reads back next to their use and waits for each with lgkmcnt(0);
+                    // with it it retires them with counted waits -- tests/test_screen_i8_schedule.py)
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int t = 0; t < NQT; ++t) {
+#ifndef I8S_NO_MFMA
+                        ah[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_cur, qh[t][gi], ah[t], 0, 0, 0);
+                        al[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_cur, b_cur[t], al[t], 0, 0, 0);
+#else
+                        asm volatile("" : : "v"(a_cur));
+#endif
+                        // ---- the previous tile's test, a slice per k-step, under the first query tile's MFMAs (the fences
+                        // keep MFMA pair, test, MFMA pair, then the piece and the next reads: left alone the scheduler queues
+                        // every test behind the k-step's last MFMA, where the matrix pipe waits for them)
+                        if constexpr (gi >= T0 && gi < T0 + NSL) if (t == 0) {
+#pragma unroll
+                            for (int u = 0; u < RPK; ++u)
+#pragma unroll
+                                for (int tt = 0; tt < NQT; ++tt) m |= test_row(tt, RPK * (gi - T0) + u, md_cur[u]);
+                            asm volatile("" : "+v"(m)); // (the slice stays in its k-step)
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+#ifndef I8S_NO_MFMA
+#pragma unroll
+                    for (int t = 0; t < NQT; ++t) b_cur[t] = b_nxt[t];
+#endif
+                    if constexpr (gi >= T0 - 1 && gi < T0 - 1 + NSL) {
+#pragma unroll
+                        for (int u = 0; u < RPK; ++u) md_cur[u] = md_nxt[u];
+                    }
+                    i8s_issue_piece(tn == 0 ? s0 : (tn == 1 ? s1 : s2), voff[g], kn * 128, ring_w + wr_off + g * 1024);
+                    if constexpr (g == 3) {
+                        wr_off = rd_off;
+                        rd_off = rd_off + I8S_SLOT_BYTES == RING ? 0u : rd_off + I8S_SLOT_BYTES;
+                    }
+                    a_cur = a_nxt;
+                });
+            } else {
+                oi_wait_vm<0>(); // the last tile's metadata (and the zero-filling refills issued past the last tile)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const i8s_f32x2 md = meta_row(mt, r);
+#pragma unroll
+                    for (int t = 0; t < NQT; ++t) m |= test_row(t, r, md);
+                }
             }
+
+            // ---- append tile ti - 1's survivors; the key is the lower bound s~ - e_r |q^| - c_q
+            const uint64_t row0 = tile_row0(ti ? ti - 1 : 0);
+            if (ti == 0) m = 0u; // "tile -1"
             if (row_end - row0 < (uint64_t)I8S_TILE_ROWS) { // the ragged last tile: rows past the end read as zeros
                 const uint32_t left = (uint32_t)(row_end - row0);
 #pragma unroll
@@ -440,28 +490,32 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
             // survives here, and the test above still runs -- the compiler cannot tell)
             if (seg_cap != 0xFFFFFFFFu) m = 0u;
 #endif
-            auto lower_key = [&](int t, int r, uint32_t row) -> uint64_t { // (survivors only: the metadata read again)
-                float sr[4], er[4];
-                meta4(r >> 2, sr, er);
-                return oi_rank_key(score(t, r, sr[r & 3]) - fmaf(er[r & 3], qn[t], cq[t]), doc_id_base + row);
-            };
             if (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull) {
                 if constexpr (FILT) m = oi_filter_tile<NQT>(m, filt, attrs, row0, lh, li);
                 const uint32_t cnt = (uint32_t)__builtin_popcount(m);
                 const uint32_t incl = oi_wave_incl_scan(cnt);
                 const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+                // Only the (t, r) some lane kept are visited: `any` is wave-uniform, so S is indexed by a scalar.  Ascending
+                // (t, r) per lane, as the staging order and the pool contents have always been.
+                const uint32_t any = oi_wave_or(m);
+                auto lower_key = [&](int t, uint32_t r) -> uint64_t { // (survivors only: the metadata read again)
+                    const uint32_t rit = (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const i8s_f32x2 md = *reinterpret_cast<const i8s_f32x2 *>(mt + rit * 8);
+                    const float sc = (float)S[16 * t + r] * (md[0] * qa[t]);
+                    return oi_rank_key(sc - fmaf(md[1], qn[t], cq[t]), doc_id_base + ((uint32_t)row0 + rit));
+                };
                 if (total <= OI_STAGE - OI_STAGE_FLUSH) {
                     uint32_t idx = st_head + st_n + incl - cnt;
 #pragma unroll
                     for (int t = 0; t < NQT; ++t)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
+                        for (uint32_t wd = (any >> (16 * t)) & 0xFFFFu; wd; wd &= wd - 1) {
+                            const uint32_t r = (uint32_t)__builtin_ctz(wd);
                             if (m & (1u << (16 * t + r))) {
-                                const uint32_t row = (uint32_t)row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                                stage_keys[idx & (OI_STAGE - 1)] = lower_key(t, r, row);
+                                stage_keys[idx & (OI_STAGE - 1)] = lower_key(t, r);
                                 stage_q[idx & (OI_STAGE - 1)] = 32u * t + li;
                                 ++idx;
                             }
+                        }
                     st_n += total;
                     while (st_n >= OI_STAGE_FLUSH) {
                         OI_STAGE_FLUSH_TO_POOL(OI_STAGE_FLUSH);
@@ -474,11 +528,10 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
 #pragma unroll
                     for (int t = 0; t < NQT; ++t) {
                         uint64_t *dst = my_seg + (uint64_t)(32u * t + li) * pool_stride;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
+                        for (uint32_t wd = (any >> (16 * t)) & 0xFFFFu; wd; wd &= wd - 1) {
+                            const uint32_t r = (uint32_t)__builtin_ctz(wd);
                             if (m & (1u << (16 * t + r))) {
-                                const uint32_t row = (uint32_t)row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                                if (pos[t] < seg_cap) dst[pos[t]] = lower_key(t, r, row);
+                                if (pos[t] < seg_cap) dst[pos[t]] = lower_key(t, r);
                                 else *overflow = 1u;
                                 ++pos[t];
                             }
@@ -486,7 +539,14 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
                     }
                 }
             }
-            // the next tile's metadata into the other meta slot (this tile's reads have all returned: their values were used)
+            if (!live) break;
+            // ---- this tile's S (the survivor path above was the last reader of the previous tile's)
+#pragma unroll
+            for (int t = 0; t < NQT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) S[16 * t + r] = ah[t][r] * 128 + al[t][r];
+            // the next tile's metadata into the slot the previous tile's just left (its reads have all returned: their values
+            // were used)
             if (ti + 1 < my_nt) issue_meta(ti + 1);
             s0 = s1;
             s1 = s2;

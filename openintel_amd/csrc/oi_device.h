@@ -93,6 +93,12 @@ __device__ __forceinline__ float oi_fma_unpacked(float x, float y, float a) {
     return a;
 #endif
 }
+// Its plain-multiply twin: one v_mul_f32 (the rounding of x * y), never half of a packed pair.
+__device__ __forceinline__ float oi_mul_unpacked(float x, float y) {
+    float r;
+    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+    return r;
+}
 
 // Order-preserving map f32 -> u32 (ascending).  -0.0 is folded into +0.0 first so
 // that equal scores compare equal; NaN must be rejected by the caller.
@@ -137,6 +143,17 @@ __device__ __forceinline__ uint32_t oi_wave_incl_scan(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
     return v;
+}
+
+// The OR of v over the wave, wave-uniform (the steps of oi_wave_incl_scan: lane 63 ends with every lane's bits).
+__device__ __forceinline__ uint32_t oi_wave_or(uint32_t v) {
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
 // The doc filter of a filtered search (oi_doc_filter): f = {group_mask, group_value, stamp_lo, stamp_hi} of the
