@@ -488,6 +488,57 @@ int oi_search_sharded_filtered(oi_index *idx, oi_comm *comm, const float *query_
                                uint32_t *counts_out);
 
 /* ------------------------------------------------------------------------- */
+/* Near-duplicate collapse of ranked lists                                      */
+/* ------------------------------------------------------------------------- */
+/*
+ * Retweets, cross-posts and copy-pasta fill a ranked list with copies of one post.  These calls collapse them on the GPU (a
+ * batched Gram matrix over rows already in HBM) instead of leaving every host to download pool x dim floats per query.
+ * Builder-defined like the whole retrieval path; no reference counterpart (the reference has no embeddings, SURVEY.md
+ * section 0).
+ *
+ * sim(a, b) is the dot product of the two STORED rows: for an f32 corpus the f32 rows as the index holds them (the cosine
+ * for unit rows -- the convention of oi_search_lists), for a bf16 corpus the bf16 rows widened exactly to f32.  The library's
+ * value is accumulated in f32 and is within 1e-5 of the f64 value for rows of norm <= 1.  A NaN similarity is never ">= t".
+ *
+ * The rule, on a ranked list e_0 .. e_{c-1} (rank order, c = counts[q]) and a threshold t: walk the list in rank order;
+ * e_i is KEPT when no kept e_j, j < i, has sim(e_i, e_j) >= t; otherwise it is COLLAPSED INTO ITS REPRESENTATIVE, the
+ * best-ranked kept e_j with sim >= t (the first such entry, not the most similar one).  Greedy, not transitive: A~B, B~C,
+ * A!~C keeps A and C.  Out come the kept entries in rank order, cut at k, each with its input score bit for bit;
+ * dup_counts[r] is 1 + the number of entries of the WHOLE input list collapsed into kept entry r, those ranked after the
+ * k-th kept entry included.
+ *
+ * An entry whose doc id lies outside this handle's shard [doc_id_base, doc_id_base + n_docs) is a SINGLETON: it is kept,
+ * nothing collapses into it, and no row is read for it.  This is the rule that keeps the kernels in bounds on any input;
+ * there is no error for it.  (The same doc id twice in a list is two entries like any other two.)
+ *
+ * Pairs whose true similarity is within 1e-5 of t may fall on either side: the result is the greedy collapse under the
+ * library's f32 similarities (a k-ordered fused-multiply-add chain), deterministic for a given build and input -- compare
+ * the ties of two summation orders under OI_COSINE_SCREEN above.
+ *
+ * oi_collapse_lists: any ranked list of this index's documents (cosine, BM25 or fused).  Input row stride `depth`
+ *   (1 .. OI_MAX_DEPTH), output row stride `k` (1 .. OI_MAX_DEPTH), first counts_out[q] entries of a row valid.  scores may
+ *   be NULL: scores_out is then not written and may be NULL too.  dup_counts_out may be NULL.  OI_DEVICE: asynchronous on
+ *   the ctx stream, like oi_rrf_fuse.  Works on a view; needs the embeddings only (no forward index, no finalize): an index
+ *   without embeddings -> OI_ERR_STATE.  threshold NaN, depth or k out of range, a null required buffer -> OI_ERR_INVALID_ARG.
+ * oi_search_collapsed: by definition oi_search_filtered(.., depth, k = pool, filters) followed by
+ *   oi_collapse_lists(.., depth = pool, threshold, k) -- the fused pool-list stays on the device between the two.
+ *   filters == NULL: the unfiltered search.  pool in [1, OI_MAX_DEPTH], k in [1, pool]; scores out are the RRF scores.
+ *   Graph replay (oi_set_graph_replay): the collapse launches are captured with the rest of the call; the key includes
+ *   pool, k, the threshold and all four output pointers.
+ * Workspace: a pair mask of at most 32 MB per searching context, whatever n_queries (the batch runs in slices of queries).
+ *
+ * NOT covered: oi_search_sharded* and oi_pipeline_*.  A globally merged list holds rows of other ranks, and collapsing it
+ * needs a row exchange.  Until then a sharded host can collapse per shard with oi_collapse_lists, under the singleton rule.
+ */
+int oi_collapse_lists(oi_index *idx, const float *scores, const uint32_t *docs, const uint32_t *counts,
+                      uint32_t n_queries, uint32_t depth, float threshold, uint32_t k, int location,
+                      float *scores_out, uint32_t *docs_out, uint32_t *counts_out, uint32_t *dup_counts_out);
+int oi_search_collapsed(oi_index *idx, const float *query_vecs, const uint32_t *query_terms,
+                        const uint32_t *q_term_offsets, uint32_t n_queries, uint32_t depth, uint32_t pool, uint32_t k,
+                        float threshold, const oi_doc_filter *filters, int location,
+                        float *scores_out, uint32_t *docs_out, uint32_t *counts_out, uint32_t *dup_counts_out);
+
+/* ------------------------------------------------------------------------- */
 /* Text to term ids: the tokeniser and the hashed vocabulary                   */
 /* ------------------------------------------------------------------------- */
 /*

@@ -179,6 +179,15 @@ extern "C" {
                                       filters: *const OiDocFilter, location: c_int, scores_out: *mut f32, docs_out: *mut u32,
                                       counts_out: *mut u32) -> c_int;
 
+    // near-duplicate collapse of ranked lists (scores / scores_out and dup_counts_out may be null)
+    pub fn oi_collapse_lists(idx: *mut OiIndex, scores: *const f32, docs: *const u32, counts: *const u32, n_queries: u32,
+                             depth: u32, threshold: f32, k: u32, location: c_int, scores_out: *mut f32, docs_out: *mut u32,
+                             counts_out: *mut u32, dup_counts_out: *mut u32) -> c_int;
+    pub fn oi_search_collapsed(idx: *mut OiIndex, query_vecs: *const f32, query_terms: *const u32, q_term_offsets: *const u32,
+                               n_queries: u32, depth: u32, pool: u32, k: u32, threshold: f32, filters: *const OiDocFilter,
+                               location: c_int, scores_out: *mut f32, docs_out: *mut u32, counts_out: *mut u32,
+                               dup_counts_out: *mut u32) -> c_int;
+
     pub fn oi_pipeline_create(idx: *mut OiIndex, comm: *mut OiComm, lanes: u32, max_queries: u32, max_query_terms: u32,
                               depth: u32, k: u32, out: *mut *mut OiPipeline) -> c_int;
     pub fn oi_pipeline_destroy(p: *mut OiPipeline);

@@ -280,6 +280,27 @@ impl HipIndex {
         })?;
         Ok(ranked(&s, &d, &c, k))
     }
+    /// `search_filtered` with k = pool, then the near-duplicate collapse of each fused list (`oi_search_collapsed`): an entry
+    /// whose stored row has a dot product >= threshold with a better-ranked kept entry is folded into it.  Per query: the
+    /// kept posts (<= k, RRF scores) and, index-aligned, how many posts of the pool each one stands for (itself included).
+    /// filters: None = unfiltered.
+    pub fn search_collapsed(&self, query_vecs: &[f32], query_terms: &[Vec<u32>], filters: Option<&[ffi::OiDocFilter]>, k: usize,
+                            depth: usize, pool: usize, threshold: f32) -> Result<Vec<(Vec<RankedPost>, Vec<u32>)>, HipError> {
+        let b = query_terms.len();
+        assert_eq!(query_vecs.len(), b * self.dim);
+        if let Some(f) = filters {
+            assert_eq!(f.len(), b);
+        }
+        let (flat, offs) = flatten_terms(query_terms);
+        let (mut s, mut d, mut c, mut n) = (vec![0f32; b * k], vec![0u32; b * k], vec![0u32; b], vec![0u32; b * k]);
+        check(unsafe {
+            ffi::oi_search_collapsed(self.idx, query_vecs.as_ptr(), flat.as_ptr(), offs.as_ptr(), b as u32, depth as u32,
+                                     pool as u32, k as u32, threshold, filters.map_or(std::ptr::null(), |f| f.as_ptr()),
+                                     ffi::OI_HOST, s.as_mut_ptr(), d.as_mut_ptr(), c.as_mut_ptr(), n.as_mut_ptr())
+        })?;
+        let posts = ranked(&s, &d, &c, k);
+        Ok(posts.into_iter().enumerate().map(|(q, p)| { let m = p.len(); (p, n[q * k..q * k + m].to_vec()) }).collect())
+    }
     /// Hybrid BM25 + cosine + RRF: one ranked list (<= k) per query, in query order.
     pub fn search(&self, query_vecs: &[f32], query_terms: &[Vec<u32>], k: usize, depth: usize) -> Result<Vec<Vec<RankedPost>>, HipError> {
         let b = query_terms.len();

@@ -118,6 +118,8 @@ SIGNATURES = {
     "oi_search_lists_packed_filtered": (_I, [_P, _P, _P, _P, _U32, _U32, _P, _I, _P]),
     "oi_search_filtered": (_I, [_P, _P, _P, _P, _U32, _U32, _U32, _P, _I, _P, _P, _P]),
     "oi_search_sharded_filtered": (_I, [_P, _P, _P, _P, _P, _U32, _U32, _U32, _P, _I, _P, _P, _P]),
+    "oi_collapse_lists": (_I, [_P, _P, _P, _P, _U32, _U32, C.c_float, _U32, _I, _P, _P, _P, _P]),
+    "oi_search_collapsed": (_I, [_P, _P, _P, _P, _U32, _U32, _U32, _U32, C.c_float, _P, _I, _P, _P, _P, _P]),
     "oi_text_terms": (_I, [_P, _P, _P, _U64, _U64, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_query_terms": (_I, [_P, _P, _P, _U32, _U32, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_index_set_text": (_I, [_P, _P, _P, _U64, _I]),

@@ -1390,6 +1390,117 @@ extern "C" int oi_search_filtered(oi_index *idx, const float *qv, const uint32_t
     return search_impl(idx, qv, qt, qo, B, depth, k, location, scores_out, docs_out, counts_out, filters);
 }
 
+// ---------------------------------------------------------------- near-duplicate collapse (collapse.hip)
+// Every argument check precedes the first HIP call (the scalars first: they can be judged without a handle).
+static int check_collapse_args(const char *what, float threshold, uint32_t depth, uint32_t k) {
+    OI_REQUIRE(threshold == threshold, "%s: threshold is NaN", what);
+    OI_REQUIRE(depth >= 1 && depth <= OI_MAX_DEPTH, "%s: depth / pool = %u outside [1,%u]", what, depth, OI_MAX_DEPTH);
+    OI_REQUIRE(k >= 1 && k <= OI_MAX_DEPTH, "%s: k=%u outside [1,%u]", what, k, OI_MAX_DEPTH);
+    return OI_OK;
+}
+static int check_collapse_state(const char *what, oi_index *idx) {
+    if (!idx) { oi_set_error("%s: null index", what); return OI_ERR_INVALID_ARG; }
+    if (!idx->rows && !idx->rows_bf16) { oi_set_error("%s: the index has no embeddings (oi_index_set_embeddings)", what); return OI_ERR_STATE; }
+    return OI_OK;
+}
+// [scores K | docs K | counts B | dup K] (contiguous in HBM) to the caller's host arrays (scores_out / dup_out may be null)
+static int collapsed_to_host(oi_ctx *ctx, const float *d_block, size_t K, uint32_t B, float *scores_out, uint32_t *docs_out,
+                             uint32_t *counts_out, uint32_t *dup_out) {
+    const size_t bytes = (3 * K + B) * 4;
+    OI_CHECK(ctx->pin_out.ensure(bytes));
+    OI_HIP_CHECK(hipMemcpyAsync(ctx->pin_out.p, d_block, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    OI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    const uint8_t *h = ctx->pin_out.as<uint8_t>();
+    if (scores_out) memcpy(scores_out, h, K * 4);
+    memcpy(docs_out, h + K * 4, K * 4);
+    memcpy(counts_out, h + 2 * K * 4, (size_t)B * 4);
+    if (dup_out) memcpy(dup_out, h + (2 * K + B) * 4, K * 4);
+    return OI_OK;
+}
+
+extern "C" int oi_collapse_lists(oi_index *idx, const float *scores, const uint32_t *docs, const uint32_t *counts, uint32_t B,
+                                 uint32_t depth, float threshold, uint32_t k, int location, float *scores_out, uint32_t *docs_out,
+                                 uint32_t *counts_out, uint32_t *dup_counts_out) {
+    OI_CHECK(check_collapse_args("collapse_lists", threshold, depth, k));
+    OI_REQUIRE(docs && counts && docs_out && counts_out, "collapse_lists: null buffer");
+    OI_REQUIRE(!scores || scores_out, "collapse_lists: scores given without scores_out");
+    OI_CHECK(check_collapse_state("collapse_lists", idx));
+    if (B == 0) return OI_OK;
+    oi_ctx *ctx = idx->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    if (!scores) scores_out = nullptr;
+    if (location == OI_DEVICE)
+        return oi_launch_collapse(idx, scores, docs, counts, B, depth, threshold, k, scores_out, docs_out, counts_out, dup_counts_out);
+    hipStream_t st = ctx->stream;
+    const size_t L = (size_t)B * depth, K = (size_t)B * k;
+    DevBuf &w = ctx->buf("collapse_io");
+    OI_CHECK(w.ensure((2 * L + B + 3 * K + B) * 4 + 64));
+    uint32_t *d_d = w.as<uint32_t>(), *d_c = d_d + L;
+    float *d_s = reinterpret_cast<float *>(d_c + B), *d_so = d_s + L;
+    uint32_t *d_do = reinterpret_cast<uint32_t *>(d_so + K), *d_co = d_do + K, *d_dup = d_co + B;
+    OI_HIP_CHECK(hipMemcpyAsync(d_d, docs, L * 4, hipMemcpyHostToDevice, st));
+    OI_HIP_CHECK(hipMemcpyAsync(d_c, counts, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    if (scores) OI_HIP_CHECK(hipMemcpyAsync(d_s, scores, L * 4, hipMemcpyHostToDevice, st));
+    OI_HIP_CHECK(hipMemsetAsync(d_so, 0, (3 * K + B) * 4, st));
+    OI_CHECK(oi_launch_collapse(idx, scores ? d_s : nullptr, d_d, d_c, B, depth, threshold, k, scores ? d_so : nullptr, d_do, d_co, d_dup));
+    return collapsed_to_host(ctx, d_so, K, B, scores_out, docs_out, counts_out, dup_counts_out);
+}
+
+// oi_search_filtered(depth, k = pool) into a device buffer, then the collapse of that fused list
+extern "C" int oi_search_collapsed(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B, uint32_t depth,
+                                   uint32_t pool, uint32_t k, float threshold, const oi_doc_filter *filters, int location,
+                                   float *scores_out, uint32_t *docs_out, uint32_t *counts_out, uint32_t *dup_counts_out) {
+    OI_CHECK(check_collapse_args("search_collapsed", threshold, pool, k));
+    OI_REQUIRE(k <= pool, "search_collapsed: k=%u exceeds pool=%u", k, pool);
+    OI_REQUIRE(scores_out && docs_out && counts_out, "search_collapsed: null output buffer");
+    OI_CHECK(check_collapse_state("search_collapsed", idx));
+    OI_CHECK(check_search_args(idx, qv, qt, qo, B, depth));
+    oi_ctx *ctx = idx->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    OI_CHECK(check_filter_state(idx, filters));
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    QueryStage q;
+    OI_CHECK(stage_queries(idx, qv, qt, qo, B, location, &q, filters));
+    const uint2 *attrs = attrs_of(idx, q);
+    const size_t L = (size_t)B * depth, P = (size_t)B * pool, K = (size_t)B * k;
+    DevBuf &o = ctx->buf("search_lists"), &pl = ctx->buf("collapse_pool");
+    OI_CHECK(o.ensure(L * 16 + (size_t)B * 8 + 64));
+    OI_CHECK(pl.ensure((2 * P + B) * 4 + 64));
+    float *d_cs = o.as<float>();
+    uint32_t *d_cd = reinterpret_cast<uint32_t *>(d_cs + L);
+    float *d_bs = reinterpret_cast<float *>(d_cd + L);
+    uint32_t *d_bd = reinterpret_cast<uint32_t *>(d_bs + L);
+    uint32_t *d_cc = d_bd + L, *d_bc = d_cc + B;
+    float *d_ps = pl.as<float>(); // the fused pool-list: it never leaves the device
+    uint32_t *d_pd = reinterpret_cast<uint32_t *>(d_ps + P), *d_pc = d_pd + P;
+    auto body = [&](float *so, uint32_t *dd, uint32_t *co, uint32_t *dup) -> int {
+        OI_HIP_CHECK(hipMemsetAsync(d_cc, 0, (size_t)B * 8, ctx->stream));
+        OI_CHECK(search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, d_cs, d_cd, d_cc, d_bs, d_bd, d_bc, q.filt, attrs));
+        OI_CHECK(oi_launch_rrf(ctx, d_cd, d_cc, d_bd, d_bc, B, depth, pool, d_ps, d_pd, d_pc));
+        return oi_launch_collapse(idx, d_ps, d_pd, d_pc, B, pool, threshold, k, so, dd, co, dup);
+    };
+    if (location == OI_DEVICE) {
+        uint32_t tbits;
+        memcpy(&tbits, &threshold, 4);
+        const uint64_t key[10] = {idx->uid, call_kind(5, filters), (uint64_t)(uintptr_t)qv, (uint64_t)(uintptr_t)qt, (uint64_t)(uintptr_t)qo,
+                                  ((uint64_t)B << 32) | depth, (uint64_t)(uintptr_t)scores_out,
+                                  ((uint64_t)tbits << 32) | ((uint64_t)ctx->cosine_mode << 16) | ((uint64_t)idx->bm25_mode << 8) | (ctx->overlap_legs ? 1u : 0u),
+                                  ((uint64_t)idx->max_query_terms << 32) | ((uint64_t)pool << 16) | k,
+                                  (uint64_t)(uintptr_t)docs_out ^ ((uint64_t)(uintptr_t)counts_out << 1) ^ ((uint64_t)(uintptr_t)dup_counts_out << 2)};
+        return run_captured(ctx, key, [&]() -> int { return body(scores_out, docs_out, counts_out, dup_counts_out); });
+    }
+    DevBuf &f = ctx->buf("collapse_out");
+    OI_CHECK(f.ensure((3 * K + B) * 4 + 64));
+    float *d_so = f.as<float>();
+    uint32_t *d_do = reinterpret_cast<uint32_t *>(d_so + K), *d_co = d_do + K, *d_dup = d_co + B;
+    OI_HIP_CHECK(hipMemsetAsync(f.p, 0, (3 * K + B) * 4, st));
+    OI_CHECK(body(d_so, d_do, d_co, d_dup));
+    OI_CHECK(collapsed_to_host(ctx, d_so, K, B, scores_out, docs_out, counts_out, dup_counts_out));
+    return check_overflow_locked(ctx);
+}
+
 // ---------------------------------------------------------------- diagnostics of the bf16 screen
 extern "C" int oi_screen_probe(oi_index *idx, const float *query_vecs, uint32_t B, uint64_t row_begin, uint32_t n_rows,
                                float *screen_scores_out, float *eps_out) {

@@ -315,6 +315,11 @@ int oi_launch_lists_to_pool(oi_ctx *ctx, const float *scores, const uint32_t *do
 int oi_launch_rrf(oi_ctx *ctx, const uint32_t *docs_a, const uint32_t *counts_a, const uint32_t *docs_b,
                   const uint32_t *counts_b, uint32_t n_queries, uint32_t depth, uint32_t k,
                   float *scores_out, uint32_t *docs_out, uint32_t *counts_out);
+// collapse.hip: the near-duplicate collapse of ranked lists -- device lists in and out, asynchronous on the ctx
+// stream; d_scores / scores_out and dup_out may be null
+int oi_launch_collapse(oi_index *idx, const float *d_scores, const uint32_t *d_docs, const uint32_t *d_counts, uint32_t n_queries,
+                       uint32_t depth, float threshold, uint32_t k, float *scores_out, uint32_t *docs_out, uint32_t *counts_out,
+                       uint32_t *dup_out);
 // cosine.hip
 // Sets pool.n_segs / pool.seg_cap for this chunk (the following select must use the same view).
 int oi_launch_cosine_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end,

@@ -39,6 +39,12 @@ class SearchResult:
     counts: object   # [B] valid entries per row
 
 
+@dataclass
+class CollapsedResult(SearchResult):
+    """A SearchResult whose near-duplicates were collapsed (oi_collapse_lists / oi_search_collapsed)."""
+    dup_counts: object = None   # [B, k] u32: entries of the input list each kept entry stands for, itself included
+
+
 class PostRetriever(abc.ABC):
     """New port: rank stored posts for a batch of (embedding, term-id) queries."""
 
@@ -373,6 +379,42 @@ class HybridIndex(PostRetriever):
         _lib.check(self.lib.oi_search(self.handle, _lib.ptr(qv), _lib.ptr(qt), _lib.ptr(qo), B, int(depth), int(k),
                                       _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(out.scores),
                                       _lib.ptr(out.docs), _lib.ptr(out.counts)))
+        return out
+
+    # ---------------------------------------------------------------- near-duplicate collapse
+    def collapse_lists(self, scores, docs, counts, threshold: float, k: int) -> "CollapsedResult":
+        """oi_collapse_lists: ranked lists of this index's documents ([B, depth] docs, [B] counts; scores [B, depth] or None)
+        with every entry whose stored row has a dot product >= threshold with a better-ranked kept entry folded into it.
+        Host arrays in, host arrays out; torch CUDA tensors in, tensors out (asynchronous on the ctx stream)."""
+        dev = _is_dev(docs)
+        if not dev:
+            docs, counts = _np(docs, np.uint32), _np(counts, np.uint32)
+            scores = None if scores is None else _np(scores, np.float32)
+        else:
+            assert docs.is_contiguous() and counts.is_contiguous() and (scores is None or scores.is_contiguous())
+        B, depth = int(docs.shape[0]), int(docs.shape[1])
+        out = CollapsedResult(None if scores is None else self._alloc(dev, (B, k), np.float32), self._alloc(dev, (B, k), np.uint32),
+                              self._alloc(dev, (B,), np.uint32), self._alloc(dev, (B, k), np.uint32))
+        _lib.check(self.lib.oi_collapse_lists(self.handle, _lib.ptr(scores), _lib.ptr(docs), _lib.ptr(counts), B, depth,
+                                              float(threshold), int(k), _lib.OI_DEVICE if dev else _lib.OI_HOST,
+                                              _lib.ptr(out.scores), _lib.ptr(out.docs), _lib.ptr(out.counts),
+                                              _lib.ptr(out.dup_counts)))
+        return out
+
+    def search_collapsed(self, query_vecs, query_terms, q_term_offsets, k: int = DEFAULT_K, depth: int = DEFAULT_DEPTH,
+                         pool: int = DEFAULT_DEPTH, threshold: float = 0.9, filters=None,
+                         out: Optional["CollapsedResult"] = None) -> "CollapsedResult":
+        """oi_search_collapsed: search(k=pool, filters) followed by collapse_lists(threshold, k) with the fused pool-list kept
+        on the device.  Scores are the RRF scores of the kept documents."""
+        dev, B, qv, qt, qo = self._queries(query_vecs, query_terms, q_term_offsets)
+        if out is None:
+            out = CollapsedResult(self._alloc(dev, (B, k), np.float32), self._alloc(dev, (B, k), np.uint32),
+                                  self._alloc(dev, (B,), np.uint32), self._alloc(dev, (B, k), np.uint32))
+        f = None if filters is None else self._filters(filters, dev, B)
+        _lib.check(self.lib.oi_search_collapsed(self.handle, _lib.ptr(qv), _lib.ptr(qt), _lib.ptr(qo), B, int(depth), int(pool),
+                                                int(k), float(threshold), _lib.ptr(f), _lib.OI_DEVICE if dev else _lib.OI_HOST,
+                                                _lib.ptr(out.scores), _lib.ptr(out.docs), _lib.ptr(out.counts),
+                                                _lib.ptr(out.dup_counts)))
         return out
 
     # ---------------------------------------------------------------- the sharded query with RCCL inside the library
