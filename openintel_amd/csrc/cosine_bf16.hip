@@ -33,9 +33,6 @@
 #ifndef OI_BF16_SIB_DEFAULT
 #define OI_BF16_SIB_DEFAULT 2 // (round 5: 256-query batches at d = 1024 take their two passes as sibling workgroups on one XCD)
 #endif
-#ifndef CB_QUAD_NBUF
-#define CB_QUAD_NBUF 6 // ring slots per wave of the quad kernel (4 = one tile's worth, rounds 2-4; 6 is what the LDS holds)
-#endif
 
 typedef float cb_f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 cb_bf16x8 __attribute__((ext_vector_type(8)));
@@ -47,7 +44,7 @@ typedef __bf16 cb_bf16x8 __attribute__((ext_vector_type(8)));
 // MFMA with the B operand named as AGPRs.  gfx950's matrix instructions take srcA / srcB from either half of the unified
 // register file, but the builtin lets the compiler choose: with more than 256 registers of resident queries it parks the
 // excess in AGPRs as SPILL slots and copies four registers back with v_accvgpr_read in front of every MFMA that needs them
-// (quad kernel: 304 copies in the tile loop, 8 per group of four MFMAs -- as much vector issue time as the epilogue).  Here the
+// (128 queries split by K over the waves: 304 copies in the tile loop, 8 per group of four MFMAs).  Here the
 // whole query block lives in AGPRs and is read from there; the accumulators stay in VGPRs (the epilogue stores them to LDS).
 // The compiler does not see the matrix pipe's latency through an asm: a reader of `acc` other than the next cb_mfma_agpr of
 // the same accumulator must come after cb_mfma_drain().
@@ -361,290 +358,30 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_pair(
     }
 }
 
-// ------------------------------------------------------------------ 128 queries per corpus pass
-// configs[4] is 256 queries at d = 1024: 32 per pass with the solo kernel, 96 with the pair kernel (three passes).  Here
-// the four waves of a workgroup share EVERY 32-row tile, each holding one QUARTER of K of 128 queries in registers
-// (128 x 256 bf16 = 64 KB = 256 VGPRs) and streaming its quarter of the rows through its own ring: two passes.  The four
-// partial 32 x 128 tiles meet once per tile, and the epilogue is split four ways too: wave w owns query tile w -- it parks
-// the three partial tiles it does not own in LDS, and after one barrier adds the other waves' partials of ITS tile to its
-// own (K quarters in order 0..3) and filters.  A second barrier lets the buffer be reused (the four epilogues are the
-// same size, so nobody waits long at it; the DMA ring keeps the loads of the next tile in flight across both).
-template <int D, int DBG = 0, int SIB = 0> // DBG (ablation builds): 1 = no reduction / epilogue / barriers (streaming + MFMA only), 2 = no epilogue work
-__global__ __launch_bounds__(256, 1) void cosine_bf16_quad(
-    const uint16_t *__restrict__ rows, uint64_t row_begin, uint64_t row_end,
-    const uint16_t *__restrict__ queries, // bf16 [128 (x 2 with siblings)][D], zero padded
-    uint32_t n_queries, uint32_t doc_id_base, uint64_t *pools, uint32_t *seg_cnt, uint32_t seg_cnt_stride,
-    const uint32_t *tau_keys, uint64_t pool_stride, uint32_t carry_cap, uint32_t seg_cap, uint32_t *overflow) {
-    constexpr int NQT = 4;
-    constexpr uint32_t sib = SIB;
-    constexpr bool STREAM = SIB == 0; // siblings: default cache policy (HBM then sees every tile ONCE: 25.63 GB per 256-query batch
-                                      // at 12.5M x 1024 by the FETCH_SIZE counter, against 42 GB with non-temporal loads and 51.2 GB without siblings)
-    // SIBLINGS (round 5).  256 queries at d = 1024 are two passes of this kernel over the corpus; one CU cannot hold more than
-    // 128 queries (the 256 x 1024 bf16 block IS the register file of a CU).  With sib != 0 the two passes run as ONE launch:
-    // the grid is cut into pairs of workgroups that walk the SAME tile sequence, one with queries 0..127 and one with 128..255
-    // (own pool segments, own thresholds), so a tile fetched from HBM by whichever sibling gets there first is read by the other
-    // out of cache -- HBM sees the corpus once per 256 queries instead of twice.  A sibling that hits cache runs faster until
-    // it leads and misses: the pair stays together by itself, nothing synchronises them.
-    //   sib == 1: siblings are blockIdx 2j, 2j + 1 (dispatched to neighbouring XCDs: they share the memory-side Infinity Cache)
-    //   sib == 2: siblings are 16 a + x and 16 a + 8 + x (x = blockIdx % 8: the SAME XCD under round-robin dispatch -- they share its L2)
-    uint32_t half = 0, wg = blockIdx.x, n_wg = gridDim.x;
-    if (sib == 1) { half = blockIdx.x & 1u; wg = blockIdx.x >> 1; n_wg = gridDim.x >> 1; }
-    else if (sib == 2) { half = (blockIdx.x >> 3) & 1u; wg = ((blockIdx.x >> 4) << 3) | (blockIdx.x & 7u); n_wg = gridDim.x >> 1; }
-    if (half) { // (uniform) the second 128 queries: their block of every per-query array
-        queries += (uint64_t)128 * D;
-        pools += (uint64_t)128 * pool_stride;
-        seg_cnt += (uint64_t)128 * seg_cnt_stride;
-        tau_keys += 128;
-        n_queries = n_queries > 128u ? n_queries - 128u : 0u;
-    } else if (sib && n_queries > 128u) n_queries = 128u;
-    constexpr int KQ = D / 4;                 // K of one wave
-    constexpr int NKC = KQ / CB_SLOT_K;       // ring slots per tile and wave
-    // Round 5: the ring is SIX slots deep and indexed at run time (as cosine_screen_copy.hip's), where rounds 2-4 had the four
-    // slots of one tile: 3 slots = 12 KB in flight per wave against 16 KB consumed per tile, and no refill is issued while a
-    // wave parks / waits at the two barriers of a tile -- the kernel was bound by HBM LATENCY, not bandwidth: 12 KB x 1024 waves
-    // per 2.2 us of loaded latency = the 5.6 TB/s it streamed at (tools/r05_sib_ab.py: 7080 cycles per tile, 2048 of them MFMA).
-    // Five slots ahead (20 KB) is what the LDS has room for once the park buffer holds only the 12 partial tiles that are
-    // actually parked (48 KB; it was laid out for 16).
-    constexpr int NBUF = CB_QUAD_NBUF;
-    constexpr int P = NBUF - 1;
-    constexpr int KSTEPS = KQ / 16;
-    constexpr int RED = 16 * 64;              // floats of one parked partial query tile (32 rows x 32 queries)
-    constexpr uint32_t RING = NBUF * CB_SLOT_BYTES;
-    static_assert(KQ % CB_SLOT_K == 0 && P >= NKC && P <= 2 * NKC, "unsupported ring depth");
-    static_assert(NQT * KSTEPS * 4 <= 400, "the query block must fit the register file");
-    static_assert(NKC * 4 == 16, "the epilogue is spread over 16 MFMA groups");
-
-    extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
-    unsigned char *ring = smem;                                                      // [4][NBUF][4 KiB]
-    float *red = reinterpret_cast<float *>(smem + 4 * RING);                         // [4 writers][3 foreign query tiles][RED]
-    uint32_t *seg_fill = reinterpret_cast<uint32_t *>(red + 12 * RED);               // [128]
-
-    OI_CLAIM_WHOLE_SIMD(); // (MFMA kernel: nothing else may run on this CU -- oi_device.h)
-    const uint32_t tid = threadIdx.x, lane = tid & 63;
-    const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6); // K quarter, and the query tile this wave finishes
-    const uint32_t li = lane & 31, lh = lane >> 5;
-
-    cb_bf16x8 qreg[NQT][KSTEPS]; // this wave's quarter of K of every query
-#pragma unroll
-    for (int t = 0; t < NQT; ++t)
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s)
-            qreg[t][s] = *reinterpret_cast<const cb_bf16x8 *>(queries + (uint64_t)(32 * t + li) * D + w * KQ + 16 * s + 8 * lh);
-    const uint32_t my_q = 32u * w + li;
-    const uint32_t my_tau = my_q < n_queries ? tau_keys[my_q] : 0xFFFFFFFFu;
-    // (a key of 0 = no threshold yet; -0.0 passes a +0.0 threshold here where the key order would stop it: a harmless extra
-    // candidate, the selects work on keys)
-    const float tau_f = my_tau == 0u ? -__builtin_inff() : oi_key_f32(my_tau);
-    if (tid < 32 * NQT) seg_fill[tid] = 0;
-    __syncthreads();
-
-    // ---- tiles of this WORKGROUP (of this sibling pair): wg, + n_wg, ...
-    const uint64_t n_rows = row_end - row_begin;
-    const uint64_t n_tiles = (n_rows + CB_TILE_ROWS - 1) / CB_TILE_ROWS;
-    const uint64_t first = wg, stride = n_wg;
-    const uint64_t my_nt = first < n_tiles ? (n_tiles - first + stride - 1) / stride : 0;
-    uint64_t *my_seg = pools + carry_cap + (uint64_t)wg * seg_cap;
-
-    uint32_t voff[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const uint32_t prow = 8 * m + (lane >> 3);
-        voff[m] = prow * (uint32_t)(D * 2) + w * (uint32_t)(KQ * 2) + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
-    }
-    const uint32_t ring_w = oi_lds_addr(ring) + w * RING;
-    const unsigned char *ring_rd = ring + w * RING;
-    uint32_t frag_off[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) frag_off[g] = li * 128 + (((2 * g + lh) ^ ((li >> 1) & 7)) << 4);
-
-    auto tile_row0 = [&](uint64_t ti) { return row_begin + (first + ti * stride) * (uint64_t)CB_TILE_ROWS; };
-    auto tile_srd = [&](uint64_t ti) { // past this workgroup's last tile: an EMPTY descriptor (loads return zeros)
-        const uint64_t r0 = tile_row0(ti < my_nt ? ti : 0);
-        return oi_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 2) : 0ull);
-    };
-    oi_u32x4 s0 = tile_srd(0), s1 = tile_srd(1), s2 = tile_srd(2);
-    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only: retire every load hipcc knows about, here
-    if (my_nt) {
-        oi_static_for<0, P>([&](auto j_) { // prologue: logical slots 0..P-1 (tile j / NKC, slot j % NKC) into ring slots 0..P-1
-            constexpr int j = decltype(j_)::value;
-            constexpr int tj = j / NKC, kj = j % NKC;
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-                oi_dma_piece<STREAM>(tj == 0 ? s0 : s1, voff[m], kj * 128, ring_w + j * CB_SLOT_BYTES + m * 1024);
-        });
-    }
-    // ring offsets (bytes, wave-uniform): the slot being consumed, and the one vacated before it = the refill target
-    uint32_t rd_off = 0, wr_off = (NBUF - 1) * CB_SLOT_BYTES;
-
-    // The epilogue of tile i-1 (sum of the four K quarters of this wave's query tile, filter, append) is spread over the
-    // 16 MFMA groups of tile i: it runs in the shadow of the matrix pipe and of the DMA instead of holding both up
-    // (stand-alone it cost 65 % on top of the streaming loop).  Round 3 cut its LDS and issue traffic (the loop alone
-    // streams at 6.4-6.6 TB/s, the round-2 epilogue took it to 5.2):
-    //   * a wave keeps the partial of the query tile it OWNS in registers (16 copies per tile) and parks only the three
-    //     it does not own -- 48 KB per tile and workgroup instead of 64;
-    //   * parked as [writer][query tile][register block rb][lane][4 registers]: 12 ds_write_b128 per wave instead of 64
-    //     ds_write_b32, and the owner reads 12 ds_read_b128 (256 B/clk) instead of 64 ds_read_b32 (128 B/clk);
-    //   * the three foreign partials of a register block are read in groups 4 rb, 4 rb + 1, 4 rb + 2 (before the MFMAs) and
-    //     summed in group 4 rb + 3: score = ((own + p[w+1]) + p[w+2]) + p[w+3] (writers mod 4) -- a fixed order per query
-    //     tile, so a score is the same bits run to run (the order depends on the query's slot: see finish_block); ONE branch per block tests max(four scores) >= tau, the per-register
-    //     test and the ragged-tile cut are behind it (survivors are rare once a threshold exists).
-    uint64_t row0_prev = 0;
-    bool have_prev = false;
-    uint32_t rows_prev = 0; // rows of the previous tile inside the chunk (32 but for the last)
-    typedef float cb_f32x4 __attribute__((ext_vector_type(4)));
-    cb_f32x4 *red4 = reinterpret_cast<cb_f32x4 *>(red); // [writer][query tile][rb][lane]
-    // [writer x][the three query tiles x does not own, in tile order][rb][lane]: tile t sits at index t (t < x) or t - 1 (t > x)
-    cb_f32x4 *park_base = red4 + (w * 12) * 64 + lane;          // + ((t < w ? t : t - 1) * 4 + rb) * 64
-    const cb_f32x4 *rd_base[3];                                 // writer x = (w + 1 + j) % 4, query tile w: + rb * 64
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const uint32_t x = (w + 1 + j) & 3u;
-        rd_base[j] = red4 + ((x * 3 + (w < x ? w : w - 1u)) * 4) * 64 + lane;
-    }
-    cb_f32x16 own; // this wave's partial of its own query tile, previous tile
-    auto finish_block = [&](auto rb_, const cb_f32x4 (&p)[3]) {
-        constexpr int rb = decltype(rb_)::value;
-        float sc[4];
-        // own quarter first, then the others in writer order w+1, w+2, w+3 (mod 4): a fixed order per QUERY TILE, so a score is the
-        // same bits run to run -- but the K-quarter order depends on the owning wave, i.e. on the query's slot in the batch: the
-        // same (query, row) pair can differ in the last ulp between slots (inside the 1e-5 bar; tests/test_gpu_bf16.py compares
-        // with the oracle at that bar, not bit for bit).  Summing in K order 0..3 whatever the owner was built in round 4 and
-        // cost 26 % of the launch (0.772 -> 0.976 ms: the order is a run-time property of the wave, four variants per score): not kept.
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sc[i] = ((own[4 * rb + i] + p[0][i]) + p[1][i]) + p[2][i];
-        if (DBG == 3) { if (sc[0] + sc[1] + sc[2] + sc[3] == 12345.678f) *overflow = 2u; return; } // sums only
-        // tau_f is the threshold as a float (-inf while there is none, NaN for a padded query: every compare false); a NaN
-        // score drops out of the max and fails its own compare
-        const float mx = fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3]));
-        if (mx >= tau_f) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const uint32_t rr = (uint32_t)(i + 8 * rb) + 4u * lh; // row of register 4 rb + i inside the tile
-                if (rr < rows_prev && sc[i] >= tau_f) {
-                    const uint32_t pos = atomicAdd(&seg_fill[my_q], 1u); // LDS
-                    if (pos < seg_cap) my_seg[(uint64_t)my_q * pool_stride + pos] = oi_rank_key(sc[i], doc_id_base + (uint32_t)(row0_prev + rr));
-                    else *overflow = 1u;
-                }
-            }
-        }
-    };
-
-    // The fragments of a WHOLE slot (4 x 16 B per lane) are read one slot ahead of the matrix pipe (round 5): a group is four
-    // MFMAs = 128 cycles, and a fragment read issued one group ahead (rounds 2-4) came back later than that whenever the LDS
-    // pipe was busy with the four waves' DMA writes and partial-tile traffic -- the wave then sat at lgkmcnt(0) in front of
-    // every group (stream + MFMA alone: 4500 cycles per tile for 2048 of MFMA, with HBM no longer the limit once siblings
-    // share the tiles).  The ring is continuous across tiles, so the next tile's first slot is read during this tile's last.
-    cb_bf16x8 fr_cur[4], fr_nxt[4];
-    if (my_nt) {
-        oi_wait_vm<4 * (P - 1)>();
-#pragma unroll
-        for (int g = 0; g < 4; ++g) fr_cur[g] = *reinterpret_cast<const cb_bf16x8 *>(ring_rd + rd_off + frag_off[g]);
-    }
-    for (uint64_t ti = 0; ti < my_nt; ++ti) {
-        cb_f32x16 acc[NQT];
-        {
-            // Slot kc of this tile sits at rd_off, its fragments in fr_cur.  Per slot: the counted wait that retires slot
-            // kc + 1 (P - 2 younger slots stay in flight), its four fragment reads, then per MFMA group (kc, g) four MFMAs and
-            // DMA piece g of logical slot kc + P (one or two tiles ahead; an empty descriptor past the last tile: the refill
-            // ALWAYS issues, so every counted wait is the same constant) into the slot vacated last (wr_off).
-            cb_f32x4 pp[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-            oi_static_for<0, NKC * 4>([&](auto gi_) {
-                constexpr int gi = decltype(gi_)::value;
-                constexpr int kc = gi / 4, g = gi % 4;
-                constexpr int sn = kc + P;
-                constexpr int tn = sn / NKC, kn = sn % NKC; // tn is 1 or 2 (P >= NKC)
-                constexpr int rb = gi / 4, ej = gi % 4; // the previous tile's epilogue: register block rb, step ej
-                if constexpr (g == 0) {
-                    const uint32_t nx_off = rd_off + CB_SLOT_BYTES == RING ? 0u : rd_off + CB_SLOT_BYTES;
-                    oi_wait_vm<4 * (P - 2)>();
-#pragma unroll
-                    for (int h = 0; h < 4; ++h) fr_nxt[h] = *reinterpret_cast<const cb_bf16x8 *>(ring_rd + nx_off + frag_off[h]);
-                }
-                if constexpr ((DBG == 0 || DBG == 3) && ej < 3) { // a foreign partial of block rb: read before the MFMAs
-                    if (have_prev) pp[ej] = rd_base[ej][rb * 64];
-                }
-#pragma unroll
-                for (int t = 0; t < NQT; ++t) {
-                    if constexpr (gi == 0) cb_mfma_agpr_first(acc[t], fr_cur[g], qreg[t][gi]);
-                    else cb_mfma_agpr(acc[t], fr_cur[g], qreg[t][gi]);
-                }
-                oi_dma_piece<STREAM>(tn == 1 ? s1 : s2, voff[g], kn * 128, ring_w + wr_off + g * 1024);
-                if constexpr ((DBG == 0 || DBG == 3) && ej == 3) { // ... block rb summed, filtered, appended
-                    if (have_prev) finish_block(std::integral_constant<int, rb>{}, pp);
-                }
-                if constexpr (g == 3) {
-                    wr_off = rd_off;
-                    rd_off = rd_off + CB_SLOT_BYTES == RING ? 0u : rd_off + CB_SLOT_BYTES;
-#pragma unroll
-                    for (int h = 0; h < 4; ++h) fr_cur[h] = fr_nxt[h];
-                }
-            });
-            cb_mfma_drain(); // the accumulators are read (parked / copied) next
-        }
-        if (DBG == 1) {
-            float x = 0.f;
-#pragma unroll
-            for (int t = 0; t < NQT; ++t) x += acc[t][0] + acc[t][7] + acc[t][15];
-            if (x == 12345.678f) *overflow = 2u;
-            s0 = s1;
-            s1 = s2;
-            s2 = tile_srd(ti + 3);
-            continue;
-        }
-        __syncthreads(); // everyone has consumed the parked partials of the previous tile
-        // ---- the four quarters meet: a wave parks the three query tiles it does not own and keeps its own
-#pragma unroll
-        for (int t = 0; t < NQT; ++t) {
-            if ((uint32_t)t != w) { // uniform
-#pragma unroll
-                for (int rb = 0; rb < 4; ++rb) {
-                    cb_f32x4 v = {acc[t][4 * rb], acc[t][4 * rb + 1], acc[t][4 * rb + 2], acc[t][4 * rb + 3]};
-                    park_base[(((uint32_t)t < w ? t : t - 1) * 4 + rb) * 64] = v;
-                }
-            } else {
-                own = acc[t];
-            }
-        }
-        row0_prev = tile_row0(ti);
-        rows_prev = row_end - row0_prev < 32 ? (uint32_t)(row_end - row0_prev) : 32u;
-        have_prev = true;
-        __syncthreads(); // parked: readable during the next tile's MFMA groups
-        s0 = s1;
-        s1 = s2;
-        s2 = tile_srd(ti + 3);
-    }
-    oi_wait_vm<0>(); // the zero-filling refills issued past the last tile have landed before the LDS goes back
-    if ((DBG == 0 || DBG == 3) && have_prev) // the last tile's epilogue has no MFMA loop to hide in
-        oi_static_for<0, 4>([&](auto rb_) {
-            constexpr int rb = decltype(rb_)::value;
-            cb_f32x4 p[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) p[j] = rd_base[j][rb * 64];
-            finish_block(rb_, p);
-        });
-    __syncthreads();
-    if (tid < 32 * NQT && tid < n_queries) {
-        const uint32_t c = seg_fill[tid];
-        seg_cnt[(uint64_t)tid * seg_cnt_stride + wg] = c < seg_cap ? c : seg_cap;
-    }
-}
-
-// ------------------------------------------------------------------ 128 queries per pass, split by QUERY (round 5)
-// The quad kernel above splits K over the four waves, so every 32 x 128 score tile exists as four partial tiles that meet
-// through LDS: 48 KB parked and read back per tile, two barriers, three adds per score -- 2.2 of its 8.3 ms per 256-query
-// batch at a 12.5M-row shard once sibling workgroups had taken HBM out of the way.  Here the four waves split
-// the QUERIES: wave w holds queries 32 w .. 32 w + 31 over the WHOLE K (32 x 1024 bf16 = 64 KB = 256 AGPRs), every tile is
-// DMA'd into LDS once (each wave loads a quarter of it) and read by all four waves.  A wave's accumulators then hold complete
-// scores: no partial tiles, no reduction, and a score is one MFMA accumulation chain in K order -- the same bits whatever the
-// query's slot in the batch.  The price is LDS read traffic: every fragment feeds ONE MFMA instead of four, 256 KB of
-// ds_read_b128 per tile and CU = 2048 LDS cycles beside 2048 matrix-pipe cycles per wave; the kernel is built to keep both busy:
+// ------------------------------------------------------------------ 128 queries per corpus pass, split by QUERY
+// configs[4] is 256 queries at d = 1024: 32 per pass with the solo kernel, 96 with the pair kernel (three passes).  One CU
+// cannot hold more than 128 queries (the 256 x 1024 bf16 block IS the register file of a CU): here a workgroup takes 128, two
+// passes.  The four waves split the QUERIES: wave w holds queries 32 w .. 32 w + 31 over the WHOLE K (32 x 1024 bf16 = 64 KB =
+// 256 AGPRs), every tile is DMA'd into LDS once (each wave loads a quarter of it) and read by all four waves.  A wave's
+// accumulators hold complete scores: no partial tiles, no cross-wave reduction (a K split over the waves spent 2.2 of its
+// 8.3 ms per 256-query batch at a 12.5M-row shard on parking and summing partial tiles: DESIGN.md 4.2), and a score is one MFMA
+// accumulation chain in K order -- the same bits whatever the query's slot in the batch.  The price is LDS read traffic: every
+// fragment feeds ONE MFMA instead of four, 256 KB of ds_read_b128 per tile and CU = 2048 LDS cycles beside 2048 matrix-pipe
+// cycles per wave; the kernel is built to keep both busy:
 //   * the tile moves as two HALF tiles (512 k = 8 slots of 4 KiB, 32 KB) through a ring of CQ_NHB half-tile buffers; wave w
 //     issues the DMA pieces of slots 2 w, 2 w + 1 of every half tile, three half tiles ahead;
 //   * ONE barrier per half tile does both jobs: every wave has waited for its own pieces of half tile h (counted vmcnt) before
 //     it, so after it all of h is in LDS; and every wave has finished reading h - 1, whose buffer is refilled right after;
-//   * fragments are read a whole slot (4 x 16 B per lane) ahead of the matrix pipe.
-// Sibling workgroups (SIB = 2: two workgroups of one XCD, 128 queries each, same tile sequence, default cache policy) as in
-// the quad kernel: HBM sees the corpus once per 256 queries.
+//   * fragments are read three slots (4 x 16 B per lane each) ahead of the matrix pipe.
+//
+// SIBLINGS (SIB = 2).  256 queries are two passes of 128.  With siblings the two passes run as ONE launch: the grid is cut
+// into pairs of workgroups that walk the SAME tile sequence, one with queries 0..127 and one with 128..255 (own pool segments,
+// own thresholds), so a tile fetched from HBM by whichever sibling gets there first is read by the other out of cache -- HBM
+// sees the corpus once per 256 queries instead of twice.  A sibling that hits cache runs faster until it leads and misses: the
+// pair stays together by itself, nothing synchronises them.  The siblings are blockIdx 16 a + x and 16 a + 8 + x (x =
+// blockIdx % 8): the SAME XCD under round-robin dispatch, so they share its L2.  They read with the default cache policy
+// (STREAM off), where a lone pass loads non-temporally: HBM then sees every tile ONCE, 25.63 GB per 256-query batch at
+// 12.5M x 1024 by the FETCH_SIZE counter, against 42 GB with non-temporal loads and 51.2 GB without siblings.
 #define CQ_HT_SLOTS 8
 #define CQ_HT_BYTES (CQ_HT_SLOTS * CB_SLOT_BYTES)
 #ifndef CQ_NHB
@@ -674,10 +411,10 @@ __global__ __launch_bounds__(256, 1) void cosine_bf16_qsplit(
     uint32_t *stage_q = reinterpret_cast<uint32_t *>(smem + RING + 512 + 4 * OI_STAGE * 8) + w * OI_STAGE;
     uint32_t st_head = 0, st_n = 0;
 
-    uint32_t half = 0, wg = blockIdx.x, n_wg = gridDim.x; // siblings: see cosine_bf16_quad
-    if (SIB == 1) { half = blockIdx.x & 1u; wg = blockIdx.x >> 1; n_wg = gridDim.x >> 1; }
-    else if (SIB == 2) { half = (blockIdx.x >> 3) & 1u; wg = ((blockIdx.x >> 4) << 3) | (blockIdx.x & 7u); n_wg = gridDim.x >> 1; }
-    if (half) {
+    static_assert(SIB == 0 || SIB == 2, "SIB: 0 = a lone pass of 128 queries, 2 = sibling workgroups on one XCD");
+    uint32_t half = 0, wg = blockIdx.x, n_wg = gridDim.x; // (siblings: workgroup pair `wg` of n_wg, query half `half`)
+    if (SIB == 2) { half = (blockIdx.x >> 3) & 1u; wg = ((blockIdx.x >> 4) << 3) | (blockIdx.x & 7u); n_wg = gridDim.x >> 1; }
+    if (half) { // (uniform) the second 128 queries: their block of every per-query array
         queries += (uint64_t)128 * D;
         pools += (uint64_t)128 * pool_stride;
         seg_cnt += (uint64_t)128 * seg_cnt_stride;
@@ -893,18 +630,18 @@ bool oi_cosine_bf16_supported(uint32_t dim) { return dim == 384 || dim == 768 ||
 static uint32_t cb_group(uint32_t dim, uint32_t left) {
     const uint32_t solo = dim == 1024 ? 32u : 64u;
     if (left <= solo) return solo;
-    if (dim == 1024) return left > 96u ? 128u : 96u; // 128: the quad kernel (a quarter of K per wave)
+    if (dim == 1024) return left > 96u ? 128u : 96u; // 128: cosine_bf16_qsplit (32 queries per wave)
     return (left + 95u) / 96u < (left + 63u) / 64u ? 96u : 64u;
 }
 
+// How 256 queries at d = 1024 take their two passes of 128 (cosine_bf16_qsplit): as ONE launch of sibling workgroups sharing
+// every tile through their XCD's L2 (see the kernel), or -- OI_BF16_SIB=0, A/B -- as two launches one after the other.
+static bool cb_siblings_on() {
+    const char *e = oi_ablation_env("OI_BF16_SIB");
+    return (e ? atoi(e) : OI_BF16_SIB_DEFAULT) != 0;
+}
 // Pool geometry of one chunk.  Segments are per workgroup; a workgroup's waves take 4 tiles per round
 // (solo kernel) or 2 (pair kernel) -- the cap below covers both.
-// How 256 queries at d = 1024 take their two passes of 128 (the quad kernel): 0 = two launches one after the other (rounds
-// 2-4), 1 / 2 = ONE launch of sibling workgroups sharing every tile through the Infinity Cache / the XCD's L2 (see the kernel).
-static uint32_t cb_sibling_mode() {
-    const char *e = oi_ablation_env("OI_BF16_SIB");
-    return e ? (uint32_t)atoi(e) : OI_BF16_SIB_DEFAULT;
-}
 void oi_cosine_bf16_geometry(const oi_ctx *ctx, uint64_t n_rows, uint32_t *n_segs, uint32_t *seg_cap, bool siblings) {
     const uint64_t n_tiles = (n_rows + CB_TILE_ROWS - 1) / CB_TILE_ROWS;
     const uint64_t quads = (n_tiles + 3) / 4;
@@ -956,40 +693,6 @@ static int launch_bf16_qsplit(oi_ctx *ctx, const uint16_t *rows, uint64_t row_be
     return OI_OK;
 }
 
-template <int D, int DBG, int SIB>
-static int launch_bf16_quad_k(oi_ctx *ctx, const uint16_t *rows, uint64_t row_begin, uint64_t row_end, const uint16_t *q,
-                              uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
-    const uint32_t grid = SIB ? 2u * p.n_segs : p.n_segs; // (siblings: p.n_segs pairs, one pool segment per pair and query half)
-    constexpr size_t smem = 4 * CB_QUAD_NBUF * CB_SLOT_BYTES + 12 * (16 * 64) * 4 + 128 * 4;
-    static_assert(smem <= 160 * 1024, "LDS");
-    OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(cosine_bf16_quad<D, DBG, SIB>), (size_t)(smem)));
-    hipLaunchKernelGGL((cosine_bf16_quad<D, DBG, SIB>), dim3(grid), dim3(256), smem, ctx->stream, rows, row_begin, row_end, q, nq,
-                       doc_id_base, p.keys, p.seg_cnt, p.seg_cnt_stride, p.tau_keys, p.stride, p.carry_cap, p.seg_cap,
-                       p.overflow);
-    OI_HIP_CHECK(hipGetLastError());
-    return OI_OK;
-}
-
-template <int D>
-static int launch_bf16_quad(oi_ctx *ctx, const uint16_t *rows, uint64_t row_begin, uint64_t row_end, const uint16_t *q,
-                            uint32_t nq, uint32_t doc_id_base, const PoolView &p, uint32_t sib = 0) {
-#ifdef OI_ABLATION
-    static const char *dbg_s = oi_ablation_env("OI_QUAD_DBG");
-    const int dbg = dbg_s ? atoi(dbg_s) : 0;
-    if (dbg == 1) return sib ? launch_bf16_quad_k<D, 1, 2>(ctx, rows, row_begin, row_end, q, nq, doc_id_base, p)
-                             : launch_bf16_quad_k<D, 1, 0>(ctx, rows, row_begin, row_end, q, nq, doc_id_base, p);
-    if (dbg == 3) return sib ? launch_bf16_quad_k<D, 3, 2>(ctx, rows, row_begin, row_end, q, nq, doc_id_base, p)
-                             : launch_bf16_quad_k<D, 3, 0>(ctx, rows, row_begin, row_end, q, nq, doc_id_base, p);
-    if (sib == 1) return launch_bf16_quad_k<D, 0, 1>(ctx, rows, row_begin, row_end, q, nq, doc_id_base, p);
-#endif
-    // Round 5: 128 queries per pass split by QUERY over the waves (cosine_bf16_qsplit) instead of by K.  OI_BF16_QUAD=1 (A/B): the K split.
-    static const bool k_split = oi_ablation_env("OI_BF16_QUAD") != nullptr;
-    if (D == 1024 && !k_split) return sib ? launch_bf16_qsplit<2>(ctx, rows, row_begin, row_end, q, nq, doc_id_base, p)
-                                          : launch_bf16_qsplit<0>(ctx, rows, row_begin, row_end, q, nq, doc_id_base, p);
-    if (sib) return launch_bf16_quad_k<D, 0, 2>(ctx, rows, row_begin, row_end, q, nq, doc_id_base, p);
-    return launch_bf16_quad_k<D, 0, 0>(ctx, rows, row_begin, row_end, q, nq, doc_id_base, p);
-}
-
 // All queries of a batch over rows [row_begin, row_end) of a bf16 corpus.  d_queries: f32 [n_queries][dim].
 int oi_launch_cosine_bf16_chunk(oi_ctx *ctx, const uint16_t *rows, uint64_t row_begin, uint64_t row_end, uint32_t dim,
                                 const float *d_queries, uint32_t n_queries, uint32_t doc_id_base, PoolView &pool) {
@@ -997,10 +700,9 @@ int oi_launch_cosine_bf16_chunk(oi_ctx *ctx, const uint16_t *rows, uint64_t row_
     // siblings: every group of this batch is a full pair of 128-query passes (256, 512, ... queries at d = 1024) and the chunk
     // is long enough to give every pair of workgroups a tile
     // A filtered search is pinned to the one-pass-per-group kernel (cosine_bf16_filter), the only one with the
-    // doc filter: groups of 32 queries at d = 1024, 64 otherwise, never the pair / quad / query-split kernels or siblings
+    // doc filter: groups of 32 queries at d = 1024, 64 otherwise, never the pair / query-split kernels or siblings
     const bool filtered = pool.filt != nullptr;
-    const uint32_t sib_mode = cb_sibling_mode();
-    const bool siblings = !filtered && sib_mode != 0 && dim == 1024 && n_queries >= 256 && n_queries % 256 == 0 &&
+    const bool siblings = !filtered && cb_siblings_on() && dim == 1024 && n_queries >= 256 && n_queries % 256 == 0 &&
                           row_end > row_begin && (row_end - row_begin) >= (uint64_t)CB_TILE_ROWS * ctx->num_cus;
     oi_cosine_bf16_geometry(ctx, row_end > row_begin ? row_end - row_begin : 0, &pool.n_segs, &pool.seg_cap, siblings);
     OI_REQUIRE(pool.n_segs <= pool.seg_cnt_stride && pool.carry_cap + (uint64_t)pool.n_segs * pool.seg_cap <= pool.stride,
@@ -1032,8 +734,8 @@ int oi_launch_cosine_bf16_chunk(oi_ctx *ctx, const uint16_t *rows, uint64_t row_
 #define CB_PAIR(DD, T) OI_CHECK((launch_bf16_pair<DD, T>(ctx, rows, row_begin, row_end, qptr, nq_here, doc_id_base, p)))
         const bool pair = nq_here > (dim == 1024 ? 32u : 64u);
         if (dim == 1024) {
-            if (nq_here > 128u) OI_CHECK((launch_bf16_quad<1024>(ctx, rows, row_begin, row_end, qptr, nq_here, doc_id_base, p, sib_mode)));
-            else if (nq_here > 96u) OI_CHECK((launch_bf16_quad<1024>(ctx, rows, row_begin, row_end, qptr, nq_here, doc_id_base, p)));
+            if (nq_here > 128u) OI_CHECK(launch_bf16_qsplit<2>(ctx, rows, row_begin, row_end, qptr, nq_here, doc_id_base, p)); // (siblings)
+            else if (nq_here > 96u) OI_CHECK(launch_bf16_qsplit<0>(ctx, rows, row_begin, row_end, qptr, nq_here, doc_id_base, p));
             else if (!pair) CB_SOLO(1024, 1);
             else if (nqt == 2) CB_PAIR(1024, 2);
             else CB_PAIR(1024, 3);

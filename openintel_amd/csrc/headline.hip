@@ -31,7 +31,7 @@
 // the patterns.  Hits are rare; each keyword hit becomes a node in a per-title list, folded at the
 // end into the keyword mask and the first-occurrence order the reference's Vec has.  Tiles that do
 // not fit the window, or that hold more hits than nodes, are done one lane per title
-// (hl_scan_title), which is also kernel v1.
+// (hl_scan_title).
 #include "oi_device.h"
 #include "oi_internal.h"
 
@@ -175,29 +175,6 @@ __device__ static void hl_scan_title(const R &rd, uint32_t beg, uint32_t end, co
     about_out = about;
 }
 
-// Kernel v1 (OI_HEADLINE_V1): 256 titles per workgroup, one lane walks one title straight from HBM.
-__global__ __launch_bounds__(HL_THREADS) void headline_scan_kernel_v1(const uint8_t *__restrict__ blob,
-                                                                     const uint64_t *__restrict__ offsets, uint64_t n,
-                                                                     const HlParams *__restrict__ params,
-                                                                     uint16_t *__restrict__ mask_out,
-                                                                     uint64_t *__restrict__ order_out,
-                                                                     uint8_t *__restrict__ about_out) {
-    __shared__ __attribute__((aligned(16))) HlHot hot;
-    for (uint32_t i = threadIdx.x; i < sizeof(HlHot) / 16; i += HL_THREADS)
-        reinterpret_cast<uint4 *>(&hot)[i] = reinterpret_cast<const uint4 *>(&params->hot)[i];
-    __syncthreads();
-    const uint64_t t = (uint64_t)blockIdx.x * HL_THREADS + threadIdx.x;
-    if (t >= n) return;
-    const uint64_t tb = offsets[t], te = offsets[t + 1];
-    HlMemReader rd{blob + tb};
-    uint32_t mask, about;
-    uint64_t order;
-    hl_scan_title(rd, 0u, (uint32_t)(te - tb), hot, params, mask, order, about);
-    mask_out[t] = (uint16_t)mask;
-    order_out[t] = order;
-    about_out[t] = (uint8_t)about;
-}
-
 // ---------------------------------------------------------------- byte-parallel kernel
 struct HlShared {
     HlHot hot;
@@ -245,9 +222,13 @@ __device__ __forceinline__ uint32_t hl_u8(const uint8_t *table, uint32_t i) {
     return (reinterpret_cast<const uint32_t *>(table)[i >> 2] >> (8u * (i & 3u))) & 0xFFu;
 }
 
-// 32 alnum bits starting at chunk c's first byte (bit i = byte 16c + i)
+// 32 alnum bits starting at chunk c's first byte (bit i = byte 16c + i): am[1 + c] | am[2 + c] << 16, as ONE 2-byte-aligned
+// ds_read_b32.  Spelled as the 32-bit read it is: whether the compiler folds two 16-bit reads into one depends on what
+// else the translation unit instantiates.
 __device__ static inline uint32_t hl_am32(const HlShared &s, uint32_t c) {
-    return (uint32_t)s.am[1 + c] | ((uint32_t)s.am[2 + c] << 16);
+    uint32_t v;
+    __builtin_memcpy(&v, &s.am[1 + c], 4);
+    return v;
 }
 
 // Words 1.. of pattern p against the title's tokens after the one ending at `q`; `end` = title end.
@@ -386,7 +367,7 @@ __device__ __forceinline__ void hl_load_text(const uint8_t *__restrict__ blob, u
     }
 }
 
-template <bool TM> // TM: per-phase cycle counters (development aid)
+template <bool TM> // TM: per-phase cycle counters (development aid; launched by -DOI_ABLATION builds only)
 // (4 waves per SIMD: the LDS budget allows four workgroups per CU, the registers must too.)
 __global__ __launch_bounds__(HL_THREADS, 4) void headline_scan_kernel(const uint8_t *__restrict__ blob,
                                                                   const uint64_t *__restrict__ offsets, uint64_t n,
@@ -732,30 +713,28 @@ int oi_launch_headline_scan_params(oi_ctx *ctx, const uint8_t *d_blob, const uin
     while (tile > 8u && (n + tile - 1) / tile < 2ull * (uint64_t)ctx->num_cus) tile >>= 1;
     if (forced >= 1 && forced <= HL_MAX_TILE) tile = forced;
     static const int dbg = oi_ablation_env("OI_HEADLINE_DBG") ? atoi(oi_ablation_env("OI_HEADLINE_DBG")) : 0; // ablations (wrong results)
-    static const bool v1 = oi_ablation_env("OI_HEADLINE_V1") != nullptr; // one lane per title (kept for A/B runs)
-    const uint64_t per_wg = v1 ? HL_THREADS : tile;
-    OI_REQUIRE((n + per_wg - 1) / per_wg <= 0x7FFFFFFFull, "headline scan: too many titles for one launch");
-    const uint32_t grid = (uint32_t)((n + per_wg - 1) / per_wg);
+    OI_REQUIRE((n + tile - 1) / tile <= 0x7FFFFFFFull, "headline scan: too many titles for one launch");
+    const uint32_t grid = (uint32_t)((n + tile - 1) / tile);
     unsigned long long *d_timing = nullptr;
-    if (oi_ablation_env("OI_HEADLINE_TIMING")) {
+#ifdef OI_ABLATION
+    const bool timed = oi_ablation_env("OI_HEADLINE_TIMING") != nullptr; // the TM variant; its counters go to stderr
+    if (timed) {
         DevBuf &tb = ctx->buf("hl_timing");
         OI_CHECK(tb.ensure(8 * sizeof(unsigned long long)));
         OI_HIP_CHECK(hipMemsetAsync(tb.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
         d_timing = tb.as<unsigned long long>();
     }
+    auto kernel = timed ? headline_scan_kernel<true> : headline_scan_kernel<false>;
+#else
+    auto kernel = headline_scan_kernel<false>;
+#endif
     ctx->prof_begin("headline");
-    if (v1)
-        hipLaunchKernelGGL(headline_scan_kernel_v1, dim3(grid), dim3(HL_THREADS), 0, ctx->stream, d_blob, d_offsets, n,
-                           dpp, d_mask, d_order, d_about);
-    else if (d_timing)
-        hipLaunchKernelGGL(headline_scan_kernel<true>, dim3(grid), dim3(HL_THREADS), 0, ctx->stream, d_blob, d_offsets,
-                           n, blob_bytes, tile, dpp, d_mask, d_order, d_about, dbg, d_timing);
-    else
-        hipLaunchKernelGGL(headline_scan_kernel<false>, dim3(grid), dim3(HL_THREADS), 0, ctx->stream, d_blob, d_offsets,
-                           n, blob_bytes, tile, dpp, d_mask, d_order, d_about, dbg, d_timing);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(HL_THREADS), 0, ctx->stream, d_blob, d_offsets, n, blob_bytes, tile, dpp,
+                       d_mask, d_order, d_about, dbg, d_timing);
     ctx->prof_end("headline");
     OI_HIP_CHECK(hipGetLastError());
-    if (d_timing) {
+#ifdef OI_ABLATION
+    if (timed) {
         unsigned long long h[8];
         OI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         OI_HIP_CHECK(hipMemcpy(h, d_timing, sizeof(h), hipMemcpyDeviceToHost));
@@ -764,6 +743,7 @@ int oi_launch_headline_scan_params(oi_ctx *ctx, const uint8_t *d_blob, const uin
                         "barrier %.0f results %.0f | waves %llu candidates/wave %.1f\n",
                 tile, h[0] / w, h[1] / w, h[2] / w, h[3] / w, h[4] / w, h[5] / w, h[6], h[7] / w);
     }
+#endif
     return OI_OK;
 }
 

@@ -51,7 +51,7 @@ struct oi_ctx;
 int oi_dyn_lds(oi_ctx *ctx, const void *kernel, size_t bytes);
 
 // A/B switches, ablation builds ("timings only, results wrong by construction") and the first-generation kernels are
-// reachable through environment variables ONLY in a -DOI_ABLATION build (tools/*.sh, tools/ks_ablate.py build one
+// reachable through environment variables ONLY in a -DOI_ABLATION build (tools/build_ablation.sh builds one
 // with OI_EXTRA_HIPCC_FLAGS=-DOI_ABLATION).  The product build ignores them: a stray variable cannot change what
 // the C ABI returns.  (OI_COSINE_MODE / OI_BM25_MODE select between documented, tested, equivalent modes and stay.)
 #ifdef OI_ABLATION

@@ -16,8 +16,8 @@ struct Knobs {
     uint32_t bm25_first_div = env_int("OI_BM25_FIRST_DIV", 8, 1);
     bool screen_no_round = env_set("OI_SCREEN_NO_ROUND"), no_spec = env_set("OI_NO_SPEC"), no_overlap = env_set("OI_NO_OVERLAP");
     bool bm25_early = env_set("OI_BM25_EARLY"), small_gemv = env_set("OI_SMALL_BATCH_GEMV"), bm25_two_phase = env_set("OI_BM25_TWO_PHASE");
-    // the first-generation cosine / select kernels and the 32-wide K-split tile have no screen in front of them
-    bool exact_only = env_set("OI_COSINE_V1") || env_set("OI_SELECT_V1") || env_int("OI_KS_SHAPE", 0, 0) == 32;
+    // the first-generation cosine / select kernels have no screen in front of them
+    bool exact_only = env_set("OI_COSINE_V1") || env_set("OI_SELECT_V1");
 };
 const Knobs &knobs() { static const Knobs k; return k; }
 

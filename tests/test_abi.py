@@ -69,6 +69,19 @@ def test_product_build_has_no_ablation_switches():
     assert b"OI_COSINE_MODE" in blob and b"OI_BM25_MODE" in blob   # the two documented mode selectors stay
 
 
+def test_product_build_has_no_retired_kernels():
+    """The superseded kernels that only an ablation switch could launch are gone from the product binary (the timing variant
+    of the headline scan lives on in -DOI_ABLATION builds only); the kernels that replaced them are in it."""
+    from openintel_amd import build, _lib
+    build.build()
+    blob = open(_lib.LIB_PATH, "rb").read()
+    for name in (b"cosine_ksplit_filter", b"cosine_bf16_quad", b"lexicon_kernel_v1", b"headline_scan_kernel_v1",
+                 b"headline_scan_kernelILb1E"):
+        assert name not in blob, name
+    for name in (b"cosine_ksplit16_filter", b"cosine_bf16_qsplit", b"lexicon_scan_kernel", b"headline_scan_kernelILb0E"):
+        assert name in blob, name
+
+
 def test_null_handles_are_refused_without_touching_a_device():
     """Argument checks come before any HIP or RCCL call: a null handle is OI_ERR_INVALID_ARG with a message, on a box with no
     GPU too (round 3's new entry points included)."""

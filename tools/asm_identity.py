@@ -1,17 +1,26 @@
 #!/usr/bin/env python3
 """Is the gfx950 assembly of every kernel what it was at REV (default HEAD~1)?
 
-    python tools/asm_identity.py [REV] [-k SUBSTRING] [-j JOBS]
+    python tools/asm_identity.py [REV] [-k SUBSTRING] [-j JOBS] [--per-kernel [--json FILE]]
 
 The gate of a refactor that must not move device code: every csrc/*.hip of REV (from `git archive`, in a temporary
 directory) and of the working tree is compiled with the library's own flags plus --cuda-device-only -S, for the product
 build and for the variant builds the tools use, and the two .s files are compared after dropping the lines that name
 __hip_cuid_<hash> (a per-translation-unit hash).  One line per (file, variant); exit status 1 on any difference.
 -k: only the (file, variant) lines containing SUBSTRING.
+
+--per-kernel: the gate of a change that removes or adds kernels.  Each .s is cut at its function symbols (the compiler's
+"Begin function" marks: kernels with their descriptors, and the device functions that were not inlined), comments are
+dropped and so is the function's index in local labels (.LBB7_24 -> .LBB_24, .Ltmp, .Lfunc_*), which moves when a
+neighbour goes.  Functions in both trees are compared, with the differing lines printed; those only in REV are listed as
+removed, those only in the working tree as added.  Exit status 1 if a function in both trees differs.  --json: the table.
 """
 import argparse
+import difflib
 import io
+import json
 import os
+import re
 import subprocess
 import sys
 import tarfile
@@ -47,11 +56,45 @@ def asm(tree, name, defs, out_dir):
         return [l for l in f if "__hip_cuid_" not in l], ""
 
 
+BEGIN = re.compile(r"-- Begin function (\S+)")
+LABEL = re.compile(r"\.L(BB|JTI|CPI|tmp|func_begin|func_end)\d+")
+
+
+def functions(lines):
+    """{symbol: normalised lines} of one .s: from a function's Begin mark to the next one's (or the end of the code)."""
+    out, cur = {}, None
+    for l in lines:
+        m = BEGIN.search(l)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+        elif l.lstrip().startswith((".p2alignl", ".amdgpu_metadata")) or ".AMDGPU.gpr_maximums" in l:
+            cur = None
+        l = LABEL.sub(r".L\1", l.split(";")[0]).strip()
+        if cur is not None and l and not l.startswith((".section", ".text")):  # (a section line names the NEXT function)
+            cur.append(l)
+    return out
+
+
+def per_kernel(job, old, new):
+    """Rows (file, variant, function, verdict, differing lines) of one (file, variant)."""
+    fo, fn = functions(old), functions(new)
+    rows = []
+    for sym in sorted(set(fo) | set(fn)):
+        if sym not in fn or sym not in fo:
+            rows.append((sym, "removed" if sym in fo else "added", []))
+            continue
+        d = [l for l in difflib.unified_diff(fo[sym], fn[sym], "REV", "tree", n=0, lineterm="") if l[:2] not in ("--", "++", "@@")]
+        rows.append((sym, "DIFFERS in %d lines" % len(d) if d else "identical (%d lines)" % len(fn[sym]), d))
+    return [(job[0] + ".hip", " ".join(job[1]) or "(product)", *r) for r in rows]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("rev", nargs="?", default="HEAD~1")
     ap.add_argument("-k", default="")
     ap.add_argument("-j", type=int, default=min(16, os.cpu_count() or 4))
+    ap.add_argument("--per-kernel", action="store_true")
+    ap.add_argument("--json", default="")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         old = os.path.join(tmp, "old")
@@ -66,15 +109,28 @@ def main():
             (o, eo), (n, en) = asm(old, *job, os.path.join(tmp, "old_s")), asm(ROOT, *job, os.path.join(tmp, "new_s"))
             if o is None or n is None:
                 return job, -1, len(o or n or []), eo or en
+            if a.per_kernel:
+                return job, 0, len(n), per_kernel(job, o, n)
             return job, len(o) - sum(x == y for x, y in zip(o, n)) + max(0, len(n) - len(o)), len(n), ""
 
-        bad = 0
+        bad, table = 0, []
         with ThreadPoolExecutor(max_workers=max(1, a.j)) as ex:
             for (name, defs), diff, lines, err in ex.map(one, jobs):
+                if a.per_kernel and diff == 0:
+                    for f, v, fun, verdict, d in err:
+                        print("%-22s %-34s %-22s %s" % (f, v, verdict, fun), flush=True)
+                        for l in d[:40]:
+                            print("        " + l)
+                        bad += verdict.startswith("DIFFERS")
+                        table.append({"file": f, "variant": v, "function": fun, "verdict": verdict, "diff": d})
+                    continue
                 verdict = "identical" if diff == 0 else ("DOES NOT COMPILE\n" + err if diff < 0 else "DIFFERS in %d lines" % diff)
                 print("%-22s %-34s %7d lines  %s" % (name + ".hip", " ".join(defs) or "(product)", lines, verdict), flush=True)
                 bad += diff != 0
-        print("%d of %d differ from %s" % (bad, len(jobs), a.rev))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(table, f, indent=1)
+        print("%d of %d differ from %s" % (bad, len(table) if a.per_kernel else len(jobs), a.rev))
         return 1 if bad else 0
 
 

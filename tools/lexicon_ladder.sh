@@ -1,6 +1,6 @@
 #!/bin/bash
 # Ablation ladder of the lexicon scan, times and VALU/SALU/LDS instruction counts per level (GPU box).
-#   bash tools/lexicon_ladder.sh [levels]   (OI_LEXICON_V2=1 for the second-generation kernel: levels 0..5)
+#   bash tools/lexicon_ladder.sh [levels]
 # Results under gpurun_out/lex_ladder/.
 set -e
 cd "$(dirname "$0")/.."
