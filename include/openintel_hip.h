@@ -539,6 +539,56 @@ int oi_search_collapsed(oi_index *idx, const float *query_vecs, const uint32_t *
                         float *scores_out, uint32_t *docs_out, uint32_t *counts_out, uint32_t *dup_counts_out);
 
 /* ------------------------------------------------------------------------- */
+/* Similarity volume: posts like a query, counted per time bucket              */
+/* ------------------------------------------------------------------------- */
+/*
+ * Every other retrieval call returns a ranked list of at most OI_MAX_DEPTH posts.  This one keeps a COUNT instead of a list:
+ * "how many posts of the index are like this one, and how has that number moved hour by hour?" -- the aggregation
+ * counterpart of the filtered search.  Builder-defined like the whole retrieval path; no reference counterpart (the reference
+ * counts posts per source in social_summary, it has no embeddings: SURVEY.md section 0).
+ *
+ * What a count is.  counts_out[q][b] is the number of local documents d of the handle for which all of these hold:
+ *   1. d passes filters[q].  filters == NULL means every document passes.
+ *   2. bucket_width == 0, or stamp_origin <= stamp[d] and (stamp[d] - stamp_origin) / bucket_width == b.  This is evaluated
+ *      in 64 bits, so origin + n * width may exceed 2^32.
+ *   3. sim(q, d) >= threshold.
+ *
+ * What sim is.  sim is the f32 value of the library's rescoring chain: lane l accumulates x_k * q_k over the float4s
+ * l, l + 64, .. in k order with single fused multiply-adds, the wave butterfly sum follows.  The result is the score a
+ * default (screened) oi_search_lists returns for that row, within 1e-5 of the f64 dot product for rows of norm <= 1.  On a
+ * bf16 corpus the row is widened exactly and the query is rounded to bf16 the way that corpus's scorer rounds it.  A NaN
+ * similarity is never >= t.
+ *
+ * Routes.  The value of sim does not depend on the route, so every route returns the same counts bit for bit: the call is
+ * deterministic and its result is independent of cosine mode, screening-copy policy and batch composition.  An f32 corpus of
+ * dim 384 / 768 with a bf16 screening copy under OI_COSINE_SCREEN / OI_COSINE_SCREEN_COPY is counted by ONE stream of the
+ * copy: a pair whose screen score clears the threshold by the query's proven error bound is counted without its f32 row
+ * being read, only the pairs inside the bound are rescored.  Everything else (other dims, a bf16 corpus, no copy,
+ * OI_COSINE_EXACT / _SPLIT / _SCREEN_STREAM, a query without a bound, more than 4 Mi undecided pairs) takes the exact chain
+ * over every row: correct for any input, slower.
+ *
+ * Rules.  spec is always a host pointer.  location says where the query vectors, the filters and counts_out live.
+ * OI_DEVICE is asynchronous on the ctx stream.  The call needs embeddings only: no forward index, no finalize (an index
+ * without embeddings -> OI_ERR_STATE), and it works on a view.  bucket_width > 0 or filters != NULL on an index without
+ * attributes returns OI_ERR_STATE.  n_queries == 0 is OI_OK; n_queries <= 4096.  The call is not captured by graph replay
+ * (oi_set_graph_replay) and always runs eagerly.  Workspace per searching context: the histogram and, on the screen route,
+ * a band buffer of 32 MB (oi_workspace_bytes counts both).
+ * Profile tags: "volume" (the stream), "volume_band" (the rescoring of the undecided pairs), "volume_exact" (the exact
+ * route, and the runs of the fallback inside a screened call that really counted the batch).
+ *
+ * NOT covered: oi_search_sharded* and oi_pipeline_*.  Counts of shards add, so a sharded host sums the per-rank arrays.
+ */
+#define OI_MAX_VOLUME_BUCKETS 1024u
+typedef struct oi_volume_spec {
+    float    threshold;     /* count documents with sim >= threshold.  NaN: OI_ERR_INVALID_ARG; +-inf allowed */
+    uint32_t stamp_origin;  /* lower edge of bucket 0 */
+    uint32_t bucket_width;  /* > 0: bucket = (stamp - origin) / width.  0: no time axis, n_buckets must be 1 */
+    uint32_t n_buckets;     /* 1 .. OI_MAX_VOLUME_BUCKETS */
+} oi_volume_spec;
+int oi_similar_volume(oi_index *idx, const float *query_vecs, uint32_t n_queries, const oi_volume_spec *spec,
+                      const oi_doc_filter *filters, int location, uint32_t *counts_out /* [n_queries][n_buckets] */);
+
+/* ------------------------------------------------------------------------- */
 /* Text to term ids: the tokeniser and the hashed vocabulary                   */
 /* ------------------------------------------------------------------------- */
 /*
@@ -649,7 +699,7 @@ int oi_screen_probe(oi_index *idx, const float *query_vecs, uint32_t n_queries, 
 
 /* Timing hooks for bench.py: when enabled, HIP events are recorded on the ctx stream
  * around every kernel launch, grouped by tag ("cosine", "bm25", "select", "rrf",
- * "lexicon", "social_summary", "text_count", "text_emit").  oi_profile_read returns the summed duration (ms) of
+ * "lexicon", "social_summary", "text_count", "text_emit", "volume", "volume_band", "volume_exact").  oi_profile_read returns the summed duration (ms) of
  * the launches with that tag and their count since the last reset.  enable: 0 off, 1 every
  * tagged launch, 2 only the "cosine" launches (two event packets per launch cost a few us of
  * stream time each: a timed region that only needs its dominant kernel asks for 2). */

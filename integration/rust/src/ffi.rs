@@ -45,6 +45,18 @@ pub struct OiDocFilter {
     pub stamp_hi: u32,
 }
 
+/// `oi_volume_spec`: count documents with sim >= threshold per bucket (stamp - stamp_origin) / bucket_width;
+/// bucket_width == 0 means no time axis (n_buckets must be 1).
+#[repr(C)]
+#[derive(Debug, Clone, Copy, PartialEq)]
+pub struct OiVolumeSpec {
+    pub threshold: f32,
+    pub stamp_origin: u32,
+    pub bucket_width: u32,
+    pub n_buckets: u32,
+}
+pub const OI_MAX_VOLUME_BUCKETS: u32 = 1024;
+
 pub const OI_OK: c_int = 0;
 pub const OI_ERR_ANALYZER_MISMATCH: c_int = -3;
 pub const OI_ERR_OVERFLOW: c_int = -8;
@@ -187,6 +199,10 @@ extern "C" {
                                n_queries: u32, depth: u32, pool: u32, k: u32, threshold: f32, filters: *const OiDocFilter,
                                location: c_int, scores_out: *mut f32, docs_out: *mut u32, counts_out: *mut u32,
                                dup_counts_out: *mut u32) -> c_int;
+
+    // similarity volume: counts_out[n_queries][n_buckets]; spec is a host pointer whatever `location`; filters may be null
+    pub fn oi_similar_volume(idx: *mut OiIndex, query_vecs: *const f32, n_queries: u32, spec: *const OiVolumeSpec,
+                             filters: *const OiDocFilter, location: c_int, counts_out: *mut u32) -> c_int;
 
     pub fn oi_pipeline_create(idx: *mut OiIndex, comm: *mut OiComm, lanes: u32, max_queries: u32, max_query_terms: u32,
                               depth: u32, k: u32, out: *mut *mut OiPipeline) -> c_int;

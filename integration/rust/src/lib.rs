@@ -301,6 +301,25 @@ impl HipIndex {
         let posts = ranked(&s, &d, &c, k);
         Ok(posts.into_iter().enumerate().map(|(q, p)| { let m = p.len(); (p, n[q * k..q * k + m].to_vec()) }).collect())
     }
+    /// How many posts of the shard are like each query, per time bucket (`oi_similar_volume`): per query `n_buckets` counts of
+    /// the documents that pass its filter, whose stamp falls into bucket (stamp - stamp_origin) / bucket_width and whose
+    /// similarity -- the f32 score `search` ranks by -- is >= spec.threshold.  filters: None = every document passes.
+    /// Counts of shards add.
+    pub fn similar_volume(&self, query_vecs: &[f32], spec: ffi::OiVolumeSpec, filters: Option<&[ffi::OiDocFilter]>)
+                          -> Result<Vec<Vec<u32>>, HipError> {
+        assert_eq!(query_vecs.len() % self.dim, 0);
+        let b = query_vecs.len() / self.dim;
+        if let Some(f) = filters {
+            assert_eq!(f.len(), b);
+        }
+        let nb = spec.n_buckets as usize;
+        let mut counts = vec![0u32; b * nb];
+        check(unsafe {
+            ffi::oi_similar_volume(self.idx, query_vecs.as_ptr(), b as u32, &spec, filters.map_or(std::ptr::null(), |f| f.as_ptr()),
+                                   ffi::OI_HOST, counts.as_mut_ptr())
+        })?;
+        Ok(counts.chunks(nb.max(1)).map(|c| c.to_vec()).collect())
+    }
     /// Hybrid BM25 + cosine + RRF: one ranked list (<= k) per query, in query order.
     pub fn search(&self, query_vecs: &[f32], query_terms: &[Vec<u32>], k: usize, depth: usize) -> Result<Vec<Vec<RankedPost>>, HipError> {
         let b = query_terms.len();

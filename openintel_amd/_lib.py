@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(HERE, "libopenintel_hip.so")
 OI_HOST, OI_DEVICE = 0, 1
 OI_MAX_DEPTH = 1024
 OI_MAX_DIM = 1024
+OI_MAX_VOLUME_BUCKETS = 1024
 OI_BM25_BLOCK_DOCS = 32768
 OI_N_CATALYST_KEYWORDS = 16
 OI_TEXT_TOKEN_HASH_BYTES = 64
@@ -59,6 +60,16 @@ class DocFilter(C.Structure):
         ("group_value", C.c_uint32),
         ("stamp_lo", C.c_uint32),
         ("stamp_hi", C.c_uint32),
+    ]
+
+
+class VolumeSpec(C.Structure):
+    """oi_volume_spec: count documents with sim >= threshold, per bucket (stamp - stamp_origin) // bucket_width."""
+    _fields_ = [
+        ("threshold", C.c_float),
+        ("stamp_origin", C.c_uint32),
+        ("bucket_width", C.c_uint32),
+        ("n_buckets", C.c_uint32),
     ]
 
 
@@ -120,6 +131,7 @@ SIGNATURES = {
     "oi_search_sharded_filtered": (_I, [_P, _P, _P, _P, _P, _U32, _U32, _U32, _P, _I, _P, _P, _P]),
     "oi_collapse_lists": (_I, [_P, _P, _P, _P, _U32, _U32, C.c_float, _U32, _I, _P, _P, _P, _P]),
     "oi_search_collapsed": (_I, [_P, _P, _P, _P, _U32, _U32, _U32, _U32, C.c_float, _P, _I, _P, _P, _P, _P]),
+    "oi_similar_volume": (_I, [_P, _P, _U32, _P, _P, _I, _P]),
     "oi_text_terms": (_I, [_P, _P, _P, _U64, _U64, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_query_terms": (_I, [_P, _P, _P, _U32, _U32, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_index_set_text": (_I, [_P, _P, _P, _U64, _I]),

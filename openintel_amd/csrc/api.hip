@@ -112,6 +112,10 @@ extern "C" int oi_profile_reset(oi_ctx *ctx, int enable) {
     for (auto &kv : ctx->prof)
         for (auto &s : kv.second) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     ctx->prof.clear();
+    {   // the fallback-run counter of oi_similar_volume ("volume_exact" above) starts over with the spans
+        auto vr = ctx->ws.find("volume_runs");
+        if (vr != ctx->ws.end() && vr->second.p) (void)hipMemsetAsync(vr->second.p, 0, 16, ctx->stream);
+    }
     ctx->prof_enabled = enable == 2 ? 2 : (enable != 0 ? 1 : 0);
     return OI_OK;
 }
@@ -148,12 +152,35 @@ extern "C" int oi_profile_read(oi_ctx *ctx, const char *kernel_tag, double *tota
         if (launches_out) *launches_out = 0;
         return OI_OK;
     }
+    if (strcmp(kernel_tag, "volume_state") == 0) { // diagnostics of the last oi_similar_volume: undecided pairs its stream sent to the band
+        uint32_t w[4] = {0, 0, 0, 0};               // (may exceed the 4 Mi the buffer holds); bit 0 = a query had no bound, bit 1 = band overflow
+        auto vs = ctx->ws.find("volume_state");
+        if (vs != ctx->ws.end() && vs->second.p) OI_HIP_CHECK(hipMemcpy(w, vs->second.p, 16, hipMemcpyDeviceToHost));
+        if (total_ms_out) *total_ms_out = (double)w[2];
+        if (launches_out) *launches_out = (w[0] ? 1u : 0u) | (w[1] ? 2u : 0u);
+        return OI_OK;
+    }
     auto it = ctx->prof.find(kernel_tag);
     if (it != ctx->prof.end())
         for (auto &s : it->second) {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) { total += ms; ++n; }
         }
+    if (strcmp(kernel_tag, "volume_exact") == 0) {
+        // the gated fallback inside screened oi_similar_volume calls ("volume_fallback": launched every time, exits at once
+        // unless the call needs it) counts here only for the runs that really counted a batch (cosine_volume.hip)
+        uint32_t runs = 0;
+        auto vr = ctx->ws.find("volume_runs");
+        if (vr != ctx->ws.end() && vr->second.p) OI_HIP_CHECK(hipMemcpy(&runs, vr->second.p, 4, hipMemcpyDeviceToHost));
+        auto fb = ctx->prof.find("volume_fallback");
+        if (runs && fb != ctx->prof.end()) {
+            for (auto &s : fb->second) {
+                float ms = 0.f;
+                if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) total += ms;
+            }
+            n += runs;
+        }
+    }
     if (total_ms_out) *total_ms_out = total;
     if (launches_out) *launches_out = n;
     return OI_OK;
@@ -1499,6 +1526,46 @@ extern "C" int oi_search_collapsed(oi_index *idx, const float *qv, const uint32_
     OI_CHECK(body(d_so, d_do, d_co, d_dup));
     OI_CHECK(collapsed_to_host(ctx, d_so, K, B, scores_out, docs_out, counts_out, dup_counts_out));
     return check_overflow_locked(ctx);
+}
+
+// ---------------------------------------------------------------- similarity volume (cosine_volume.hip)
+// Every argument check precedes the first HIP call (the spec first: it can be judged without a handle).  Never captured.
+extern "C" int oi_similar_volume(oi_index *idx, const float *qv, uint32_t B, const oi_volume_spec *spec, const oi_doc_filter *filters,
+                                 int location, uint32_t *counts_out) {
+    OI_REQUIRE(spec, "similar_volume: null spec");
+    OI_REQUIRE(spec->threshold == spec->threshold, "similar_volume: threshold is NaN");
+    OI_REQUIRE(spec->n_buckets >= 1 && spec->n_buckets <= OI_MAX_VOLUME_BUCKETS, "similar_volume: n_buckets=%u outside [1,%u]",
+               spec->n_buckets, OI_MAX_VOLUME_BUCKETS);
+    OI_REQUIRE(spec->bucket_width != 0 || spec->n_buckets == 1, "similar_volume: bucket_width=0 (no time axis) with n_buckets=%u",
+               spec->n_buckets);
+    OI_REQUIRE(B <= 4096, "similar_volume: n_queries=%u outside [0,4096]", B);
+    OI_REQUIRE(B == 0 || (qv && counts_out), "similar_volume: null buffer");
+    if (!idx) { oi_set_error("similar_volume: null index"); return OI_ERR_INVALID_ARG; }
+    if (!idx->rows && !idx->rows_bf16) { oi_set_error("similar_volume: the index has no embeddings (oi_index_set_embeddings)"); return OI_ERR_STATE; }
+    oi_ctx *ctx = idx->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if ((filters || spec->bucket_width) && !idx->doc_attrs.p) {
+        oi_set_error("similar_volume: filters / time buckets need the index's doc attributes (oi_index_set_doc_attrs)");
+        return OI_ERR_STATE;
+    }
+    if (B == 0) return OI_OK;
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    static_assert(sizeof(oi_doc_filter) == sizeof(uint4), "oi_doc_filter is 16 bytes");
+    if (location == OI_DEVICE) return oi_launch_similar_volume(idx, qv, B, *spec, reinterpret_cast<const uint4 *>(filters), counts_out);
+    hipStream_t st = ctx->stream;
+    const size_t vb = (sizeof(float) * (size_t)B * idx->dim + 15) & ~(size_t)15, fb = filters ? sizeof(oi_doc_filter) * (size_t)B : 0;
+    const size_t cb = sizeof(uint32_t) * (size_t)B * spec->n_buckets;
+    DevBuf &w = ctx->buf("volume_io"); // [vectors | filters | counts]
+    OI_CHECK(w.ensure(vb + fb + cb + 64));
+    uint8_t *d = w.as<uint8_t>();
+    OI_HIP_CHECK(hipMemcpyAsync(d, qv, sizeof(float) * (size_t)B * idx->dim, hipMemcpyHostToDevice, st));
+    if (filters) OI_HIP_CHECK(hipMemcpyAsync(d + vb, filters, fb, hipMemcpyHostToDevice, st));
+    uint32_t *d_counts = reinterpret_cast<uint32_t *>(d + vb + fb);
+    OI_CHECK(oi_launch_similar_volume(idx, reinterpret_cast<const float *>(d), B, *spec,
+                                      filters ? reinterpret_cast<const uint4 *>(d + vb) : nullptr, d_counts));
+    OI_HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, cb, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipStreamSynchronize(st));
+    return OI_OK;
 }
 
 // ---------------------------------------------------------------- diagnostics of the bf16 screen

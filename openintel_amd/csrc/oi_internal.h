@@ -320,6 +320,10 @@ int oi_launch_rrf(oi_ctx *ctx, const uint32_t *docs_a, const uint32_t *counts_a,
 int oi_launch_collapse(oi_index *idx, const float *d_scores, const uint32_t *d_docs, const uint32_t *d_counts, uint32_t n_queries,
                        uint32_t depth, float threshold, uint32_t k, float *scores_out, uint32_t *docs_out, uint32_t *counts_out,
                        uint32_t *dup_out);
+// cosine_volume.hip: the similarity volume -- device queries / filters in, device counts [n_queries][n_buckets]
+// out, asynchronous on the ctx stream; d_filt may be null
+int oi_launch_similar_volume(oi_index *idx, const float *d_q, uint32_t n_queries, const oi_volume_spec &spec, const uint4 *d_filt,
+                             uint32_t *d_counts);
 // cosine.hip
 // Sets pool.n_segs / pool.seg_cap for this chunk (the following select must use the same view).
 int oi_launch_cosine_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end,

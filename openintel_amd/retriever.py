@@ -417,6 +417,27 @@ class HybridIndex(PostRetriever):
                                                 _lib.ptr(out.dup_counts)))
         return out
 
+    # ---------------------------------------------------------------- similarity volume
+    def similar_volume(self, query_vecs, threshold: float, n_buckets: int = 1, stamp_origin: int = 0, bucket_width: int = 0,
+                       filters=None):
+        """oi_similar_volume: [B, n_buckets] uint32 counts of this shard's documents with sim(q, d) >= threshold that pass
+        filters[q] and whose stamp falls into bucket (stamp - stamp_origin) // bucket_width (bucket_width = 0: no time axis,
+        one bucket).  sim is the f32 score a default search_lists returns for the row.  Host array in, numpy out; torch CUDA
+        tensor in, tensor out (asynchronous on the ctx stream).  Counts of shards add."""
+        dev = _is_dev(query_vecs)
+        if dev:
+            assert query_vecs.is_contiguous() and query_vecs.element_size() == 4
+        else:
+            query_vecs = _np(query_vecs, np.float32)
+        B = int(query_vecs.shape[0])
+        assert B == 0 or int(query_vecs.shape[1]) == self.dim
+        spec = _lib.VolumeSpec(float(threshold), int(stamp_origin), int(bucket_width), int(n_buckets))
+        out = self._alloc(dev, (B, max(int(n_buckets), 0)), np.uint32)
+        f = None if filters is None else self._filters(filters, dev, B)
+        _lib.check(self.lib.oi_similar_volume(self.handle, _lib.ptr(query_vecs), B, C.byref(spec), _lib.ptr(f),
+                                              _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(out)))
+        return out
+
     # ---------------------------------------------------------------- the sharded query with RCCL inside the library
     def finalize_sharded(self, comm: "NativeComm") -> None:
         """Collective over `comm`: all-reduce of (n_docs, tokens, df) inside the library, then the impacts from the global
