@@ -589,6 +589,73 @@ int oi_similar_volume(oi_index *idx, const float *query_vecs, uint32_t n_queries
                       const oi_doc_filter *filters, int location, uint32_t *counts_out /* [n_queries][n_buckets] */);
 
 /* ------------------------------------------------------------------------- */
+/* Similarity summary: the sentiment of posts like a query, per time bucket    */
+/* ------------------------------------------------------------------------- */
+/*
+ * oi_similar_volume says how many posts are like a query; this call says what they FEEL: the raw sums of social_summary
+ * (oi_social_counters: bullish / bearish / neutral, speculative count, posts per source, polarity sum) over exactly the
+ * documents oi_similar_volume counts, one record per query and time bucket.  Nothing per post returns to the host.
+ * Builder-defined like the whole retrieval path (the reference summarises a list of posts it already holds:
+ * speculation_engine.rs:76-97; it has no embeddings).
+ *
+ * Signals.  oi_index_set_signals gives every local row its signal: `n_docs` entries each, indexed by LOCAL row, exactly
+ * the buffers oi_lexicon_analyze[_device] writes and oi_social_summary reads (sources: 0 = reddit, 1 = bluesky; NULL = all
+ * reddit).  With OI_DEVICE a host chains oi_lexicon_analyze_device -> oi_index_set_signals over the blob it also hands to
+ * oi_index_set_text.  The index keeps one 8-byte record per row:
+ *   v        = Polarity::new(polarity[d]): NaN -> 0, clamped to [-1, 1]
+ *   pol_q30  = (int32) rint(v * 2^30), f64 round-to-nearest-even (the product is exact in f64)
+ *   class    = bullish if v > bull_bear_threshold, bearish if v < -bull_bear_threshold, else neutral: the reference's
+ *              comparisons on the f64 value (speculation_engine.rs:87-95)
+ *   spec     = speculative[d] != 0,  source = sources[d] != 0
+ * The class is fixed at set time with the caller's threshold; the summary call takes none.  The state rules are those of
+ * oi_index_set_doc_attrs: the buffer (8 B per row) is allocated by the first call, never reallocated and overwritten in
+ * place, stream-ordered on the index's ctx, by later calls; views alias it and see updates; a view made before signals
+ * existed has none; on a view: OI_ERR_STATE; allowed before or after finalize.  bull_bear_threshold NaN, a null polarity or
+ * speculative -> OI_ERR_INVALID_ARG.
+ *
+ * What a record is.  out[q][b] holds the social_summary raw sums over the local documents d of the handle for which all of
+ * these hold -- word for word the clauses of oi_similar_volume, with the query's own threshold:
+ *   1. d passes filters[q].  filters == NULL means every document passes.
+ *   2. bucket_width == 0, or stamp_origin <= stamp[d] and (stamp[d] - stamp_origin) / bucket_width == b (evaluated in 64 bits).
+ *   3. sim(q, d) >= t_q, where t_q = thresholds[q], or spec->threshold when thresholds == NULL.  sim is oi_similar_volume's
+ *      sim.  A NaN thresholds[q] counts nothing for that query, in both locations (no score is >= NaN).
+ * total, by_source[2], bullish, bearish, neutral and spec_count are exact integers.
+ * polarity_sum = (double)(sum of pol_q30) * 2^-30, the sum taken in 64-bit integers.
+ *
+ * The contract that follows from it:
+ *   - the result is deterministic and independent of the route, the order of the atomics, the cosine mode, the copy policy
+ *     and the batch composition;
+ *   - polarity_sum is an integer multiple of 2^-30;
+ *   - |polarity_sum - sum of Polarity::new(polarity[d])| <= total * 2^-31;
+ *   - the sum is exact when every polarity is dyadic, as in the reference's fixture (all of {-1, 0, 1});
+ *   - sums of shards add exactly below 2^23 in magnitude;
+ *   - total equals oi_similar_volume's count for the same arguments.
+ *
+ * Rules.  Those of oi_similar_volume: spec is always a host pointer; location says where the query vectors, the thresholds,
+ * the filters and out live; OI_DEVICE is asynchronous on the ctx stream; embeddings only (no forward index, no finalize); it
+ * works on a view; n_queries == 0 is OI_OK; n_queries <= 4096; not captured by graph replay.  In addition
+ * n_queries * n_buckets > OI_MAX_SUMMARY_CELLS -> OI_ERR_INVALID_ARG; an index without signals -> OI_ERR_STATE;
+ * bucket_width > 0 or filters != NULL on an index without attributes -> OI_ERR_STATE.  Workspace per searching context: 64 B
+ * per cell, and the volume's 32 MB band buffer on the screen route (oi_workspace_bytes counts both).
+ * Profile tags: "summary" (the stream), "summary_band" (the rescoring of the undecided pairs), "summary_exact" (the exact
+ * route, and the runs of the fallback inside a screened call that really summed the batch).
+ *
+ * NOT covered: oi_search_sharded* and oi_pipeline_*.  A sharded host adds the records of its ranks.
+ */
+#define OI_MAX_SUMMARY_CELLS (1u << 18)
+typedef struct oi_summary_spec {
+    float    threshold;      /* used when thresholds == NULL; NaN then: OI_ERR_INVALID_ARG; +-inf allowed */
+    uint32_t stamp_origin;   /* exactly oi_volume_spec's meaning and limits */
+    uint32_t bucket_width;
+    uint32_t n_buckets;
+} oi_summary_spec;
+int oi_index_set_signals(oi_index *idx, const double *polarity, const uint8_t *speculative,
+                         const uint8_t *sources /* may be NULL: all reddit */, double bull_bear_threshold, int location);
+int oi_similar_summary(oi_index *idx, const float *query_vecs, uint32_t n_queries, const oi_summary_spec *spec,
+                       const float *thresholds /* [n_queries] where `location` says, or NULL */,
+                       const oi_doc_filter *filters, int location, oi_social_counters *out /* [n_queries][n_buckets] */);
+
+/* ------------------------------------------------------------------------- */
 /* Text to term ids: the tokeniser and the hashed vocabulary                   */
 /* ------------------------------------------------------------------------- */
 /*
@@ -699,7 +766,8 @@ int oi_screen_probe(oi_index *idx, const float *query_vecs, uint32_t n_queries, 
 
 /* Timing hooks for bench.py: when enabled, HIP events are recorded on the ctx stream
  * around every kernel launch, grouped by tag ("cosine", "bm25", "select", "rrf",
- * "lexicon", "social_summary", "text_count", "text_emit", "volume", "volume_band", "volume_exact").  oi_profile_read returns the summed duration (ms) of
+ * "lexicon", "social_summary", "text_count", "text_emit", "volume", "volume_band", "volume_exact",
+ * "summary", "summary_band", "summary_exact").  oi_profile_read returns the summed duration (ms) of
  * the launches with that tag and their count since the last reset.  enable: 0 off, 1 every
  * tagged launch, 2 only the "cosine" launches (two event packets per launch cost a few us of
  * stream time each: a timed region that only needs its dominant kernel asks for 2). */

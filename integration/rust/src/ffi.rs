@@ -57,6 +57,17 @@ pub struct OiVolumeSpec {
 }
 pub const OI_MAX_VOLUME_BUCKETS: u32 = 1024;
 
+/// `oi_summary_spec`: `oi_volume_spec`'s time axis; `threshold` is every query's unless the call is given a thresholds array.
+#[repr(C)]
+#[derive(Debug, Clone, Copy, PartialEq)]
+pub struct OiSummarySpec {
+    pub threshold: f32,
+    pub stamp_origin: u32,
+    pub bucket_width: u32,
+    pub n_buckets: u32,
+}
+pub const OI_MAX_SUMMARY_CELLS: u32 = 1 << 18;
+
 pub const OI_OK: c_int = 0;
 pub const OI_ERR_ANALYZER_MISMATCH: c_int = -3;
 pub const OI_ERR_OVERFLOW: c_int = -8;
@@ -203,6 +214,14 @@ extern "C" {
     // similarity volume: counts_out[n_queries][n_buckets]; spec is a host pointer whatever `location`; filters may be null
     pub fn oi_similar_volume(idx: *mut OiIndex, query_vecs: *const f32, n_queries: u32, spec: *const OiVolumeSpec,
                              filters: *const OiDocFilter, location: c_int, counts_out: *mut u32) -> c_int;
+
+    // similarity summary: one signal record per local row (sources may be null: all reddit), then out[n_queries][n_buckets]
+    // records of social_summary sums; spec is a host pointer whatever `location`; thresholds and filters may be null
+    pub fn oi_index_set_signals(idx: *mut OiIndex, polarity: *const f64, speculative: *const u8, sources: *const u8,
+                                bull_bear_threshold: f64, location: c_int) -> c_int;
+    pub fn oi_similar_summary(idx: *mut OiIndex, query_vecs: *const f32, n_queries: u32, spec: *const OiSummarySpec,
+                              thresholds: *const f32, filters: *const OiDocFilter, location: c_int,
+                              out: *mut OiSocialCounters) -> c_int;
 
     pub fn oi_pipeline_create(idx: *mut OiIndex, comm: *mut OiComm, lanes: u32, max_queries: u32, max_query_terms: u32,
                               depth: u32, k: u32, out: *mut *mut OiPipeline) -> c_int;

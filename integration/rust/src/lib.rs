@@ -320,6 +320,42 @@ impl HipIndex {
         })?;
         Ok(counts.chunks(nb.max(1)).map(|c| c.to_vec()).collect())
     }
+    /// The per-post signals the summary sums (`oi_index_set_signals`): what the lexicon analyzer returned for the shard's posts,
+    /// n_docs entries each, local rows; sources: 0 = reddit, 1 = bluesky, None = all reddit.  The bullish / bearish class of a
+    /// post is fixed here with `bull_bear_threshold`.  A later call overwrites the signals in place.
+    pub fn set_signals(&self, polarity: &[f64], speculative: &[u8], sources: Option<&[u8]>, bull_bear_threshold: f64)
+                       -> Result<(), HipError> {
+        assert_eq!(polarity.len(), self.n_docs, "one signal per document of the shard"); // (the C call reads n_docs of each)
+        assert_eq!(speculative.len(), self.n_docs);
+        if let Some(s) = sources {
+            assert_eq!(s.len(), self.n_docs);
+        }
+        check(unsafe {
+            ffi::oi_index_set_signals(self.idx, polarity.as_ptr(), speculative.as_ptr(), sources.map_or(std::ptr::null(), |s| s.as_ptr()),
+                                      bull_bear_threshold, ffi::OI_HOST)
+        })
+    }
+    /// The sentiment of the posts like each query, per time bucket (`oi_similar_summary`): per query `n_buckets` records of the
+    /// social_summary sums over exactly the documents `similar_volume` counts.  thresholds: one per query, None = spec.threshold
+    /// for all.  Integer fields exact, polarity_sum a 64-bit integer sum of 2^-30 steps: deterministic.  Records of shards add.
+    pub fn similar_summary(&self, query_vecs: &[f32], spec: ffi::OiSummarySpec, thresholds: Option<&[f32]>,
+                           filters: Option<&[ffi::OiDocFilter]>) -> Result<Vec<Vec<ffi::OiSocialCounters>>, HipError> {
+        assert_eq!(query_vecs.len() % self.dim, 0);
+        let b = query_vecs.len() / self.dim;
+        if let Some(f) = filters {
+            assert_eq!(f.len(), b);
+        }
+        if let Some(t) = thresholds {
+            assert_eq!(t.len(), b);
+        }
+        let nb = spec.n_buckets as usize;
+        let mut out = vec![ffi::OiSocialCounters::default(); b * nb];
+        check(unsafe {
+            ffi::oi_similar_summary(self.idx, query_vecs.as_ptr(), b as u32, &spec, thresholds.map_or(std::ptr::null(), |t| t.as_ptr()),
+                                    filters.map_or(std::ptr::null(), |f| f.as_ptr()), ffi::OI_HOST, out.as_mut_ptr())
+        })?;
+        Ok(out.chunks(nb.max(1)).map(|c| c.to_vec()).collect())
+    }
     /// Hybrid BM25 + cosine + RRF: one ranked list (<= k) per query, in query order.
     pub fn search(&self, query_vecs: &[f32], query_terms: &[Vec<u32>], k: usize, depth: usize) -> Result<Vec<Vec<RankedPost>>, HipError> {
         let b = query_terms.len();

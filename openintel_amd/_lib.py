@@ -17,6 +17,7 @@ OI_HOST, OI_DEVICE = 0, 1
 OI_MAX_DEPTH = 1024
 OI_MAX_DIM = 1024
 OI_MAX_VOLUME_BUCKETS = 1024
+OI_MAX_SUMMARY_CELLS = 1 << 18
 OI_BM25_BLOCK_DOCS = 32768
 OI_N_CATALYST_KEYWORDS = 16
 OI_TEXT_TOKEN_HASH_BYTES = 64
@@ -65,6 +66,16 @@ class DocFilter(C.Structure):
 
 class VolumeSpec(C.Structure):
     """oi_volume_spec: count documents with sim >= threshold, per bucket (stamp - stamp_origin) // bucket_width."""
+    _fields_ = [
+        ("threshold", C.c_float),
+        ("stamp_origin", C.c_uint32),
+        ("bucket_width", C.c_uint32),
+        ("n_buckets", C.c_uint32),
+    ]
+
+
+class SummarySpec(C.Structure):
+    """oi_summary_spec: oi_volume_spec's time axis; threshold is every query's unless the call is given a thresholds array."""
     _fields_ = [
         ("threshold", C.c_float),
         ("stamp_origin", C.c_uint32),
@@ -132,6 +143,8 @@ SIGNATURES = {
     "oi_collapse_lists": (_I, [_P, _P, _P, _P, _U32, _U32, C.c_float, _U32, _I, _P, _P, _P, _P]),
     "oi_search_collapsed": (_I, [_P, _P, _P, _P, _U32, _U32, _U32, _U32, C.c_float, _P, _I, _P, _P, _P, _P]),
     "oi_similar_volume": (_I, [_P, _P, _U32, _P, _P, _I, _P]),
+    "oi_index_set_signals": (_I, [_P, _P, _P, _P, C.c_double, _I]),
+    "oi_similar_summary": (_I, [_P, _P, _U32, _P, _P, _P, _I, _P]),
     "oi_text_terms": (_I, [_P, _P, _P, _U64, _U64, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_query_terms": (_I, [_P, _P, _P, _U32, _U32, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_index_set_text": (_I, [_P, _P, _P, _U64, _I]),

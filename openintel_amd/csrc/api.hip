@@ -112,8 +112,9 @@ extern "C" int oi_profile_reset(oi_ctx *ctx, int enable) {
     for (auto &kv : ctx->prof)
         for (auto &s : kv.second) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     ctx->prof.clear();
-    {   // the fallback-run counter of oi_similar_volume ("volume_exact" above) starts over with the spans
-        auto vr = ctx->ws.find("volume_runs");
+    for (const char *runs : {"volume_runs", "summary_runs"}) {
+        // the fallback-run counters of oi_similar_volume / oi_similar_summary ("volume_exact", "summary_exact") start over with the spans
+        auto vr = ctx->ws.find(runs);
         if (vr != ctx->ws.end() && vr->second.p) (void)hipMemsetAsync(vr->second.p, 0, 16, ctx->stream);
     }
     ctx->prof_enabled = enable == 2 ? 2 : (enable != 0 ? 1 : 0);
@@ -152,9 +153,11 @@ extern "C" int oi_profile_read(oi_ctx *ctx, const char *kernel_tag, double *tota
         if (launches_out) *launches_out = 0;
         return OI_OK;
     }
-    if (strcmp(kernel_tag, "volume_state") == 0) { // diagnostics of the last oi_similar_volume: undecided pairs its stream sent to the band
-        uint32_t w[4] = {0, 0, 0, 0};               // (may exceed the 4 Mi the buffer holds); bit 0 = a query had no bound, bit 1 = band overflow
-        auto vs = ctx->ws.find("volume_state");
+    if (strcmp(kernel_tag, "volume_state") == 0 || strcmp(kernel_tag, "summary_state") == 0) {
+        // diagnostics of the last oi_similar_volume / oi_similar_summary: undecided pairs its stream sent to the band (may exceed
+        // the 4 Mi the buffer holds); bit 0 = a query had no bound, bit 1 = band overflow
+        uint32_t w[4] = {0, 0, 0, 0};
+        auto vs = ctx->ws.find(kernel_tag);
         if (vs != ctx->ws.end() && vs->second.p) OI_HIP_CHECK(hipMemcpy(w, vs->second.p, 16, hipMemcpyDeviceToHost));
         if (total_ms_out) *total_ms_out = (double)w[2];
         if (launches_out) *launches_out = (w[0] ? 1u : 0u) | (w[1] ? 2u : 0u);
@@ -166,13 +169,15 @@ extern "C" int oi_profile_read(oi_ctx *ctx, const char *kernel_tag, double *tota
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) { total += ms; ++n; }
         }
-    if (strcmp(kernel_tag, "volume_exact") == 0) {
-        // the gated fallback inside screened oi_similar_volume calls ("volume_fallback": launched every time, exits at once
-        // unless the call needs it) counts here only for the runs that really counted a batch (cosine_volume.hip)
+    const bool vol_exact = strcmp(kernel_tag, "volume_exact") == 0;
+    if (vol_exact || strcmp(kernel_tag, "summary_exact") == 0) {
+        // the gated fallback inside screened oi_similar_volume / oi_similar_summary calls ("volume_fallback", "summary_fallback":
+        // launched every time, exits at once unless the call needs it) counts here only for the runs that really counted a batch
+        // (cosine_volume.hip, cosine_summary.hip)
         uint32_t runs = 0;
-        auto vr = ctx->ws.find("volume_runs");
+        auto vr = ctx->ws.find(vol_exact ? "volume_runs" : "summary_runs");
         if (vr != ctx->ws.end() && vr->second.p) OI_HIP_CHECK(hipMemcpy(&runs, vr->second.p, 4, hipMemcpyDeviceToHost));
-        auto fb = ctx->prof.find("volume_fallback");
+        auto fb = ctx->prof.find(vol_exact ? "volume_fallback" : "summary_fallback");
         if (runs && fb != ctx->prof.end()) {
             for (auto &s : fb->second) {
                 float ms = 0.f;
@@ -846,6 +851,7 @@ extern "C" int oi_index_view(oi_index *src, oi_ctx *ctx, oi_index **out) {
     v->n_long = src->n_long; alias(v->long_list, src->long_list); alias(v->long_bitmap, src->long_bitmap);
     alias(v->fwd_terms, src->fwd_terms); alias(v->fwd_offsets, src->fwd_offsets);
     alias(v->doc_attrs, src->doc_attrs); // (never reallocated: the view sees later in-place updates of the source's)
+    alias(v->signals, src->signals);     // (likewise)
     *out = v;
     return OI_OK;
 }
@@ -1139,6 +1145,36 @@ extern "C" int oi_index_set_doc_attrs(oi_index *idx, const uint32_t *group, cons
         if (src[c]) OI_HIP_CHECK(hipMemcpy2DAsync(d + c, 8, src[c], 4, 4, n, hipMemcpyDeviceToDevice, st));
         else OI_HIP_CHECK(hipMemset2DAsync(d + c, 8, 0, 4, n, st));
     }
+    return OI_OK;
+}
+
+// One 8-byte signal record per local row (cosine_summary.hip: the pack kernel).  The allocation rules of doc_attrs: made by
+// the first call, only overwritten after that (stream-ordered on the ctx), aliased by views.
+extern "C" int oi_index_set_signals(oi_index *idx, const double *polarity, const uint8_t *speculative, const uint8_t *sources,
+                                    double bull_bear_threshold, int location) {
+    OI_REQUIRE(bull_bear_threshold == bull_bear_threshold, "set_signals: bull_bear_threshold is NaN");
+    OI_REQUIRE(polarity && speculative, "set_signals: null buffer (%s)", polarity ? "speculative" : "polarity");
+    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "set_signals: bad location %d", location);
+    if (!idx) { oi_set_error("set_signals: null index"); return OI_ERR_INVALID_ARG; }
+    if (idx->is_view) { oi_set_error("set_signals: a view's signals are its source's"); return OI_ERR_STATE; }
+    oi_ctx *ctx = idx->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    const uint64_t n = idx->n_docs;
+    if (n == 0) return OI_OK;
+    if (!idx->signals.p) OI_CHECK(idx->signals.ensure(sizeof(uint2) * (size_t)n));
+    hipStream_t st = ctx->stream;
+    if (location == OI_DEVICE) return oi_launch_pack_signals(ctx, polarity, speculative, sources, n, bull_bear_threshold, idx->signals.as<uint2>());
+    DevBuf &w = ctx->buf("signals_io"); // [polarity | speculative | sources]
+    const size_t pb = sizeof(double) * (size_t)n;
+    OI_CHECK(w.ensure(pb + 2 * (size_t)n));
+    uint8_t *d = w.as<uint8_t>();
+    OI_HIP_CHECK(hipMemcpyAsync(d, polarity, pb, hipMemcpyHostToDevice, st));
+    OI_HIP_CHECK(hipMemcpyAsync(d + pb, speculative, n, hipMemcpyHostToDevice, st));
+    if (sources) OI_HIP_CHECK(hipMemcpyAsync(d + pb + n, sources, n, hipMemcpyHostToDevice, st));
+    OI_CHECK(oi_launch_pack_signals(ctx, reinterpret_cast<const double *>(d), d + pb, sources ? d + pb + n : nullptr, n, bull_bear_threshold,
+                                    idx->signals.as<uint2>()));
+    OI_HIP_CHECK(hipStreamSynchronize(st));
     return OI_OK;
 }
 
@@ -1564,6 +1600,52 @@ extern "C" int oi_similar_volume(oi_index *idx, const float *qv, uint32_t B, con
     OI_CHECK(oi_launch_similar_volume(idx, reinterpret_cast<const float *>(d), B, *spec,
                                       filters ? reinterpret_cast<const uint4 *>(d + vb) : nullptr, d_counts));
     OI_HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, cb, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipStreamSynchronize(st));
+    return OI_OK;
+}
+
+// ---------------------------------------------------------------- similarity summary (cosine_summary.hip)
+// The checks of oi_similar_volume in its order, before the first HIP call.  Never captured.
+extern "C" int oi_similar_summary(oi_index *idx, const float *qv, uint32_t B, const oi_summary_spec *spec, const float *thresholds,
+                                  const oi_doc_filter *filters, int location, oi_social_counters *out) {
+    OI_REQUIRE(spec, "similar_summary: null spec");
+    OI_REQUIRE(thresholds || spec->threshold == spec->threshold, "similar_summary: threshold is NaN (and no thresholds array)");
+    OI_REQUIRE(spec->n_buckets >= 1 && spec->n_buckets <= OI_MAX_VOLUME_BUCKETS, "similar_summary: n_buckets=%u outside [1,%u]",
+               spec->n_buckets, OI_MAX_VOLUME_BUCKETS);
+    OI_REQUIRE(spec->bucket_width != 0 || spec->n_buckets == 1, "similar_summary: bucket_width=0 (no time axis) with n_buckets=%u",
+               spec->n_buckets);
+    OI_REQUIRE(B <= 4096, "similar_summary: n_queries=%u outside [0,4096]", B);
+    OI_REQUIRE((uint64_t)B * spec->n_buckets <= OI_MAX_SUMMARY_CELLS, "similar_summary: n_queries * n_buckets = %llu cells, more than %u",
+               (unsigned long long)B * spec->n_buckets, OI_MAX_SUMMARY_CELLS);
+    OI_REQUIRE(B == 0 || (qv && out), "similar_summary: null buffer");
+    if (!idx) { oi_set_error("similar_summary: null index"); return OI_ERR_INVALID_ARG; }
+    if (!idx->rows && !idx->rows_bf16) { oi_set_error("similar_summary: the index has no embeddings (oi_index_set_embeddings)"); return OI_ERR_STATE; }
+    oi_ctx *ctx = idx->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!idx->signals.p) { oi_set_error("similar_summary: the index has no signals (oi_index_set_signals)"); return OI_ERR_STATE; }
+    if ((filters || spec->bucket_width) && !idx->doc_attrs.p) {
+        oi_set_error("similar_summary: filters / time buckets need the index's doc attributes (oi_index_set_doc_attrs)");
+        return OI_ERR_STATE;
+    }
+    if (B == 0) return OI_OK;
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    if (location == OI_DEVICE)
+        return oi_launch_similar_summary(idx, qv, B, *spec, thresholds, reinterpret_cast<const uint4 *>(filters), out);
+    hipStream_t st = ctx->stream;
+    const size_t vb = (sizeof(float) * (size_t)B * idx->dim + 15) & ~(size_t)15, fb = filters ? sizeof(oi_doc_filter) * (size_t)B : 0;
+    const size_t tb = thresholds ? (sizeof(float) * (size_t)B + 15) & ~(size_t)15 : 0;
+    const size_t ob = sizeof(oi_social_counters) * (size_t)B * spec->n_buckets;
+    DevBuf &w = ctx->buf("summary_io"); // [vectors | filters | thresholds | records]
+    OI_CHECK(w.ensure(vb + fb + tb + ob + 64));
+    uint8_t *d = w.as<uint8_t>();
+    OI_HIP_CHECK(hipMemcpyAsync(d, qv, sizeof(float) * (size_t)B * idx->dim, hipMemcpyHostToDevice, st));
+    if (filters) OI_HIP_CHECK(hipMemcpyAsync(d + vb, filters, fb, hipMemcpyHostToDevice, st));
+    if (thresholds) OI_HIP_CHECK(hipMemcpyAsync(d + vb + fb, thresholds, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, st));
+    oi_social_counters *d_out = reinterpret_cast<oi_social_counters *>(d + vb + fb + tb);
+    OI_CHECK(oi_launch_similar_summary(idx, reinterpret_cast<const float *>(d), B, *spec,
+                                       thresholds ? reinterpret_cast<const float *>(d + vb + fb) : nullptr,
+                                       filters ? reinterpret_cast<const uint4 *>(d + vb) : nullptr, d_out));
+    OI_HIP_CHECK(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st));
     OI_HIP_CHECK(hipStreamSynchronize(st));
     return OI_OK;
 }

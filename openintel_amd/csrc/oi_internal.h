@@ -194,6 +194,9 @@ struct oi_index {
     // the doc attributes of filtered searches (oi_index_set_doc_attrs): {group, stamp} per local row, n_docs x 8 B; allocated
     // by the first call, overwritten in place by later ones (never reallocated: views alias it)
     DevBuf doc_attrs;
+    // the signal records of oi_similar_summary (oi_index_set_signals): {pol_q30, class + 3 spec + 6 source} per local row,
+    // n_docs x 8 B; the same allocation rules as doc_attrs (views alias it)
+    DevBuf signals;
 
     // staged forward index (between set_forward and finalize)
     bool forward_set = false, finalized = false;
@@ -324,6 +327,15 @@ int oi_launch_collapse(oi_index *idx, const float *d_scores, const uint32_t *d_d
 // out, asynchronous on the ctx stream; d_filt may be null
 int oi_launch_similar_volume(oi_index *idx, const float *d_q, uint32_t n_queries, const oi_volume_spec &spec, const uint4 *d_filt,
                              uint32_t *d_counts);
+// the bf16 corpus's rounding of the queries (cb_stage_queries: RNE, inf / NaN truncated), widened back to f32 for the chain
+int oi_launch_volume_round_queries(oi_ctx *ctx, const float *d_q, uint64_t total, float *d_out);
+// cosine_summary.hip: the similarity summary -- the pack kernel of oi_index_set_signals (device arrays in, the
+// index's records out) and the call itself: device queries / thresholds / filters in, device records [n_queries][n_buckets]
+// out, asynchronous on the ctx stream; d_thresholds (null: spec.threshold for every query) and d_filt may be null
+int oi_launch_pack_signals(oi_ctx *ctx, const double *d_pol, const uint8_t *d_spec, const uint8_t *d_sources, uint64_t n, double tau,
+                           uint2 *d_out);
+int oi_launch_similar_summary(oi_index *idx, const float *d_q, uint32_t n_queries, const oi_summary_spec &spec, const float *d_thresholds,
+                              const uint4 *d_filt, oi_social_counters *d_out);
 // cosine.hip
 // Sets pool.n_segs / pool.seg_cap for this chunk (the following select must use the same view).
 int oi_launch_cosine_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end,

@@ -82,11 +82,18 @@ class SpeculationEngine:
     def aggregate_counters(ticker: Ticker, counters: _lib.SocialCounters, market: Optional[MarketSnapshot], now,
                            cfg: EngineConfig) -> SpeculationReport:
         SpeculationEngine._check_market_ticker(ticker, market)
-        by_source = {k: int(counters.by_source[int(k)]) for k in SourceKind.ALL if counters.by_source[int(k)]}
-        social = SpeculationEngine._social_from_sums(int(counters.total), by_source, int(counters.bullish),
-                                                     int(counters.bearish), int(counters.neutral),
-                                                     int(counters.spec_count), float(counters.polarity_sum))
-        return SpeculationEngine._finish(ticker, social, market, now, cfg)
+        return SpeculationEngine._finish(ticker, SpeculationEngine.social_from_counters(counters), market, now, cfg)
+
+    @staticmethod
+    def social_from_counters(record) -> SocialSummary:
+        """The SocialSummary of one raw-sums record: a _lib.SocialCounters, or one element of an analyzer.COUNTERS_DTYPE array
+        (what HybridIndex.similar_summary returns per query and bucket)."""
+        if not isinstance(record, _lib.SocialCounters):
+            from .analyzer import counters_record
+            record = counters_record(record)
+        by_source = {k: int(record.by_source[int(k)]) for k in SourceKind.ALL if record.by_source[int(k)]}
+        return SpeculationEngine._social_from_sums(int(record.total), by_source, int(record.bullish), int(record.bearish),
+                                                   int(record.neutral), int(record.spec_count), float(record.polarity_sum))
 
     # ------------------------------------------------------------------ shared pieces
     @staticmethod

@@ -438,6 +438,91 @@ class HybridIndex(PostRetriever):
                                               _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(out)))
         return out
 
+    # ---------------------------------------------------------------- similarity summary
+    def set_signals(self, polarity, speculative, sources=None, bull_bear_threshold: float = 0.2) -> None:
+        """The per-post signals similar_summary sums (oi_index_set_signals): `polarity` float64 and `speculative` uint8 as the
+        lexicon analyzer returns them, `sources` uint8 (0 = reddit, 1 = bluesky; None = all reddit), n_docs each, indexed by
+        local row -- numpy arrays, or torch CUDA tensors (nothing per post touches the host).  A post's bullish / bearish
+        class is fixed here with `bull_bear_threshold`.  The first call allocates 8 B per row, later ones overwrite them in
+        place (views see the update)."""
+        dev = _is_dev(polarity)
+        arrs = []
+        for a, dt in ((polarity, np.float64), (speculative, np.uint8), (sources, np.uint8)):
+            if a is None:
+                arrs.append(None)
+            elif dev:
+                assert _is_dev(a) and a.is_contiguous() and a.numel() == self.n_docs and a.element_size() == np.dtype(dt).itemsize
+                arrs.append(a)
+            else:
+                a = _np(a, dt)
+                assert a.size == self.n_docs
+                arrs.append(a)
+        _lib.check(self.lib.oi_index_set_signals(self.handle, _lib.ptr(arrs[0]), _lib.ptr(arrs[1]), _lib.ptr(arrs[2]),
+                                                 float(bull_bear_threshold), _lib.OI_DEVICE if dev else _lib.OI_HOST))
+        if dev:
+            self.ctx.synchronize()  # (the pack kernel has read the caller's tensors: nothing to keep alive)
+
+    def set_signals_from_text(self, texts, sources=None, bull_bear_threshold: float = 0.2) -> None:
+        """set_signals from the posts' TEXT: the lexicon scan on the device (oi_lexicon_analyze_device), then the pack
+        (oi_index_set_signals, OI_DEVICE) -- the two C calls composed, the signals never reach the host.  texts: n_docs
+        str, or (blob, offsets) as analyzer.pack_posts makes them (numpy, or torch CUDA tensors: the blob set_text reads)."""
+        import torch
+        dev, blob, offsets, n, nbytes = _packed_texts(texts, np.uint64)
+        assert n == self.n_docs, "one text per document of the shard"
+        where = "cuda:%d" % self.ctx.device
+        if not dev:
+            blob = torch.from_numpy(np.concatenate([blob, np.zeros(8, np.uint8)])).to(where)  # (never an empty tensor)
+            offsets = torch.from_numpy(offsets.view(np.int64)).to(where)
+        pol = torch.zeros(n, dtype=torch.float64, device=where)
+        spec = torch.zeros(n, dtype=torch.uint8, device=where)
+        if sources is not None and not _is_dev(sources):
+            sources = torch.from_numpy(_np(sources, np.uint8)).to(where)
+        _lib.check(self.lib.oi_lexicon_analyze_device(self.ctx.handle, _lib.ptr(blob), _lib.ptr(offsets), n, nbytes,
+                                                      _lib.ptr(pol), _lib.ptr(spec)))
+        self.set_signals(pol, spec, sources, bull_bear_threshold)
+
+    def similar_summary(self, query_vecs, threshold, n_buckets: int = 1, stamp_origin: int = 0, bucket_width: int = 0,
+                        filters=None):
+        """oi_similar_summary: [B, n_buckets] records (analyzer.COUNTERS_DTYPE, 64 bytes) of the social_summary sums over the
+        documents similar_volume counts -- those with sim(q, d) >= threshold that pass filters[q] and fall into the bucket.
+        threshold: a float, or one per query (array; a NaN entry counts nothing).  Integer fields exact; polarity_sum is a
+        64-bit integer sum in steps of 2^-30, so the result does not depend on route, order or batch.  Host array in, numpy
+        record array out; torch CUDA tensor in, an int64 tensor [B, n_buckets, 8] holding the records' bits out
+        (asynchronous on the ctx stream; .cpu().numpy().view(COUNTERS_DTYPE) reads it).  Records of shards add.
+        SpeculationEngine.social_from_counters turns a record into a SocialSummary."""
+        from .analyzer import COUNTERS_DTYPE
+        dev = _is_dev(query_vecs)
+        if dev:
+            assert query_vecs.is_contiguous() and query_vecs.element_size() == 4
+        else:
+            query_vecs = _np(query_vecs, np.float32)
+        B = int(query_vecs.shape[0])
+        assert B == 0 or int(query_vecs.shape[1]) == self.dim
+        nb = max(int(n_buckets), 0)
+        thr = None
+        if not _is_dev(threshold) and np.ndim(threshold) == 0:
+            spec = _lib.SummarySpec(float(threshold), int(stamp_origin), int(bucket_width), int(n_buckets))
+        else:
+            spec = _lib.SummarySpec(0.0, int(stamp_origin), int(bucket_width), int(n_buckets))
+            if dev:
+                import torch
+                if not _is_dev(threshold):
+                    threshold = torch.from_numpy(_np(threshold, np.float32)).to("cuda:%d" % self.ctx.device)
+                assert threshold.is_contiguous() and threshold.numel() == B and threshold.element_size() == 4
+                self._thr_keep = thr = threshold  # (an asynchronous call reads it later)
+            else:
+                thr = _np(threshold.cpu().numpy() if _is_dev(threshold) else threshold, np.float32)
+                assert thr.size == B
+        if dev:
+            import torch
+            out = torch.zeros((B, nb, 8), dtype=torch.int64, device="cuda:%d" % self.ctx.device)
+        else:
+            out = np.zeros((B, nb), dtype=COUNTERS_DTYPE)
+        f = None if filters is None else self._filters(filters, dev, B)
+        _lib.check(self.lib.oi_similar_summary(self.handle, _lib.ptr(query_vecs), B, C.byref(spec), _lib.ptr(thr), _lib.ptr(f),
+                                               _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(out)))
+        return out
+
     # ---------------------------------------------------------------- the sharded query with RCCL inside the library
     def finalize_sharded(self, comm: "NativeComm") -> None:
         """Collective over `comm`: all-reduce of (n_docs, tokens, df) inside the library, then the impacts from the global
