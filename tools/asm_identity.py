@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Is the gfx950 assembly of every kernel what it was at REV (default HEAD~1)?
 
-    python tools/asm_identity.py [REV] [-k SUBSTRING] [-j JOBS] [--per-kernel [--json FILE]]
+    python tools/asm_identity.py [REV] [-k SUBSTRING] [-j JOBS] [--per-kernel [--json FILE] [--rename 'OLD=NEW' ...]]
 
 The gate of a refactor that must not move device code: every csrc/*.hip of REV (from `git archive`, in a temporary
 directory) and of the working tree is compiled with the library's own flags plus --cuda-device-only -S, for the product
@@ -14,6 +14,12 @@ __hip_cuid_<hash> (a per-translation-unit hash).  One line per (file, variant); 
 dropped and so is the function's index in local labels (.LBB7_24 -> .LBB_24, .Ltmp, .Lfunc_*), which moves when a
 neighbour goes.  Functions in both trees are compared, with the differing lines printed; those only in REV are listed as
 removed, those only in the working tree as added.  Exit status 1 if a function in both trees differs.  --json: the table.
+
+--rename 'OLD=NEW' (repeatable): a function of REV whose demangled name (c++filt -p: no parameter list) matches the regular
+expression OLD in full is compared with the working tree's function whose demangled name is NEW (\\1.. are OLD's groups), e.g.
+--rename 'cosine_volume_screen<(.*)>=vo_stream_kernel<\\1, VoCount>'.  The pair is one row, "REV name -> tree name", identical
+or DIFFERS like any other.  Within a compared body the function's own symbol is a placeholder on both sides, so the kernel
+descriptor and its .set lines compare.
 """
 import argparse
 import difflib
@@ -21,6 +27,7 @@ import io
 import json
 import os
 import re
+import shutil
 import subprocess
 import sys
 import tarfile
@@ -75,16 +82,45 @@ def functions(lines):
     return out
 
 
-def per_kernel(job, old, new):
+def demangled(symbols):
+    """{symbol: its demangled name without the parameter list}"""
+    tool = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
+    if not tool:
+        sys.exit("--rename matches demangled names and needs c++filt (or llvm-cxxfilt) on the PATH: none found")
+    symbols = sorted(symbols)
+    out = subprocess.run([tool, "-p"], input="\n".join(symbols), check=True, capture_output=True, text=True).stdout.splitlines()
+    return dict(zip(symbols, out))
+
+
+def renamed(fo, fn, renames):
+    """{REV symbol: tree symbol} of the functions a --rename pairs (both must exist, the tree's not in REV under its own name)"""
+    if not renames or not fo or not fn:
+        return {}
+    names = demangled(set(fo) | set(fn))
+    by_name = {names[s]: s for s in fn if s not in fo}
+    pairs = {}
+    for so in fo:
+        for pat, new in renames:
+            m = re.fullmatch(pat, names[so])
+            if m and so not in fn and m.expand(new) in by_name:
+                pairs[so] = by_name[m.expand(new)]
+                break
+    return pairs
+
+
+def per_kernel(job, old, new, renames=()):
     """Rows (file, variant, function, verdict, differing lines) of one (file, variant)."""
     fo, fn = functions(old), functions(new)
+    pairs = renamed(fo, fn, renames)
     rows = []
-    for sym in sorted(set(fo) | set(fn)):
-        if sym not in fn or sym not in fo:
+    for sym in sorted((set(fo) | set(fn)) - set(pairs.values())):
+        to = pairs.get(sym, sym)
+        if to not in fn or sym not in fo:
             rows.append((sym, "removed" if sym in fo else "added", []))
             continue
-        d = [l for l in difflib.unified_diff(fo[sym], fn[sym], "REV", "tree", n=0, lineterm="") if l[:2] not in ("--", "++", "@@")]
-        rows.append((sym, "DIFFERS in %d lines" % len(d) if d else "identical (%d lines)" % len(fn[sym]), d))
+        a, b = ([l.replace(s, "<self>") for l in f] for s, f in ((sym, fo[sym]), (to, fn[to])))
+        d = [l for l in difflib.unified_diff(a, b, "REV", "tree", n=0, lineterm="") if l[:2] not in ("--", "++", "@@")]
+        rows.append((sym if to == sym else sym + " -> " + to, "DIFFERS in %d lines" % len(d) if d else "identical (%d lines)" % len(b), d))
     return [(job[0] + ".hip", " ".join(job[1]) or "(product)", *r) for r in rows]
 
 
@@ -95,7 +131,9 @@ def main():
     ap.add_argument("-j", type=int, default=min(16, os.cpu_count() or 4))
     ap.add_argument("--per-kernel", action="store_true")
     ap.add_argument("--json", default="")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW")
     a = ap.parse_args()
+    renames = [tuple(r.split("=", 1)) for r in a.rename]
     with tempfile.TemporaryDirectory() as tmp:
         old = os.path.join(tmp, "old")
         tar = subprocess.run(["git", "-C", ROOT, "archive", a.rev, "openintel_amd/csrc", "include"], check=True, capture_output=True)
@@ -110,7 +148,7 @@ def main():
             if o is None or n is None:
                 return job, -1, len(o or n or []), eo or en
             if a.per_kernel:
-                return job, 0, len(n), per_kernel(job, o, n)
+                return job, 0, len(n), per_kernel(job, o, n, renames)
             return job, len(o) - sum(x == y for x, y in zip(o, n)) + max(0, len(n) - len(o)), len(n), ""
 
         bad, table = 0, []

@@ -22,6 +22,7 @@ import argparse
 import csv
 import json
 import os
+import re
 import sys
 import time
 
@@ -31,8 +32,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 COPY_STREAM_TBPS = 7.0   # the copy screen's measured rate
-KERNELS = ("cosine_summary_screen", "summary_band_kernel", "summary_exact_kernel", "summary_finish_kernel", "cosine_volume_screen",
-           "volume_band_kernel", "volume_exact_kernel")
+# the kernels of the two tallies: label -> what its name in the trace matches (the family's templates carry the tally as their
+# last argument)
+KERNELS = {"vo_stream_kernel<SmSum>": r"vo_stream_kernel<[^>]*SmSum>", "vo_band_kernel<SmSum>": r"vo_band_kernel<SmSum>",
+           "vo_exact_kernel<SmSum>": r"vo_exact_kernel<[^>]*SmSum>", "summary_finish_kernel": r"summary_finish_kernel",
+           "vo_stream_kernel<VoCount>": r"vo_stream_kernel<[^>]*VoCount>", "vo_band_kernel<VoCount>": r"vo_band_kernel<VoCount>",
+           "vo_exact_kernel<VoCount>": r"vo_exact_kernel<[^>]*VoCount>"}
 
 
 def merge(timing_path, stats_csv):
@@ -41,8 +46,8 @@ def merge(timing_path, stats_csv):
     with open(stats_csv, newline="") as f:
         for row in csv.DictReader(f):
             name = row.get("Name") or row.get("KernelName") or ""
-            for tag in KERNELS:
-                if tag in name:
+            for tag, pattern in KERNELS.items():
+                if re.search(pattern, name):
                     k = kern.setdefault(tag, {"calls": 0, "total_ns": 0.0})
                     k["calls"] += int(row["Calls"])
                     k["total_ns"] += float(row["TotalDurationNs"])
