@@ -770,7 +770,10 @@ int oi_screen_probe(oi_index *idx, const float *query_vecs, uint32_t n_queries, 
  * "summary", "summary_band", "summary_exact").  oi_profile_read returns the summed duration (ms) of
  * the launches with that tag and their count since the last reset.  enable: 0 off, 1 every
  * tagged launch, 2 only the "cosine" launches (two event packets per launch cost a few us of
- * stream time each: a timed region that only needs its dominant kernel asks for 2). */
+ * stream time each: a timed region that only needs its dominant kernel asks for 2).
+ * The screened cosine route also tags "cosine_gated", "rescreen", "rescore" and "spec".  "spec" COUNTS the speculative
+ * thresholds computed in a search, one span per prediction; the prediction is computed inside the preceding margin select,
+ * whose time is under "select", so the span is empty and its duration reads ~0. */
 int oi_profile_reset(oi_ctx *ctx, int enable);
 int oi_profile_read(oi_ctx *ctx, const char *kernel_tag, double *total_ms_out, uint64_t *launches_out);
 

@@ -52,6 +52,7 @@
 
 #include "oi_device.h"
 #include "oi_internal.h"
+#include "oi_screen_stage.h"
 #include "oi_lds_dma.h"
 
 typedef float pf_f32x16 __attribute__((ext_vector_type(16)));
@@ -365,21 +366,7 @@ __global__ __launch_bounds__(256) void pf_row_norm_class_kernel(const float *__r
     }
 }
 
-// The margin of one query (see the header): |s~ - s^| <= eps for every row of the corpus, s^ the rescoring
-// kernel's f32 score.  X, E: the corpus maxima above; qn = |q|, qtn = |bf16(q)|, en = |bf16(q) - q|, all f32.
-//   * 1.001 covers the f32 rounding of the five norms (sums of <= 1024 squares: 1e-4 at the very most);
-//   * squares below 2^-126 may have been flushed out of a norm: each norm is short by at most
-//     sqrt(d) 2^-63 < 4e-18, added back here;
-//   * products / inputs below 2^-126 may be flushed by the conversions and the matrix pipe: d 2^-120 (X + |q|).
-#define PF_NORM_LIMIT 1.0e15f
-#define PF_QNORM_MIN 1.0e-12f
-__device__ __forceinline__ float pf_eps(float X, float E, float qn, float qtn, float en, uint32_t dim) {
-    const float tiny = 4.0e-18f, d = (float)dim;
-    const float Xs = X + tiny, Es = E + tiny, qts = qtn + tiny, ens = en + tiny;
-    const float acc = d * 2.384185791015625e-07f; // d * 2^-22
-    return 1.001f * (Es * qts + Xs * ens + acc * (Xs + Es) * qts) + d * 7.5231638452626401e-37f * (Xs + qn) + 1.0e-30f;
-}
-
+// (the margin of one query, pf_eps, and the per-query staging body: oi_screen_stage.h)
 // Per query: bf16 copy (RNE, zero padded to n_padded rows) and the screen's margin 2 eps; a norm that is not
 // finite, too large for the bf16 products to stay finite, or too small for its rounding errors to be measured in
 // f32 opens the exact pipeline instead (gate).
@@ -389,39 +376,9 @@ __global__ __launch_bounds__(256) void pf_stage_queries_kernel(const float *__re
                                                                const uint32_t *__restrict__ max_norm_bits,
                                                                uint16_t *__restrict__ out, float *__restrict__ eps2,
                                                                uint32_t *gate) {
-    const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
     for (uint32_t row = wave; row < n_padded; row += n_waves) {
-        float ss = 0.f, st = 0.f, se = 0.f;
-        for (uint32_t k = lane; k < dim; k += 64) {
-            uint16_t v = 0;
-            if (row < n_queries) {
-                const float f = q[(uint64_t)row * dim + k];
-                const uint32_t u = __float_as_uint(f);
-                v = (u & 0x7F800000u) == 0x7F800000u ? (uint16_t)(u >> 16)                        // inf / NaN: truncate
-                                                     : (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); // RNE
-                const float ft = __uint_as_float((uint32_t)v << 16), e = ft - f; // exact: f rounded to 8 of its 24 bits
-                ss = fmaf(f, f, ss);
-                st = fmaf(ft, ft, st);
-                se = fmaf(e, e, se);
-            }
-            out[(uint64_t)row * dim + k] = v;
-        }
-        if (row < n_queries) {
-            ss = oi_wave_sum(ss);
-            st = oi_wave_sum(st);
-            se = oi_wave_sum(se);
-            const float qn = sqrtf(ss), qtn = sqrtf(st), en = sqrtf(se);
-            const float X = __uint_as_float(max_norm_bits[0]), E = __uint_as_float(max_norm_bits[1]);
-            const bool ok = qn < PF_NORM_LIMIT && qn >= PF_QNORM_MIN && qtn < PF_NORM_LIMIT && X < PF_NORM_LIMIT &&
-                            E < PF_NORM_LIMIT && en == en; // false for NaN as well
-            if (lane == 0) {
-                // A query without a bound gets an infinite margin: its threshold never rises, every key stays
-                // inside the margin, the survivors overflow and the exact kernel scores it against every row.
-                eps2[row] = ok ? 2.0f * pf_eps(X, E, qn, qtn, en, dim) : __builtin_inff();
-                if (!ok) *gate = 1u;
-            }
-        }
+        pf_stage_query_row(q, row, n_queries, dim, max_norm_bits, out, eps2, gate);
     }
 }
 
@@ -556,6 +513,8 @@ __global__ __launch_bounds__(256) void pf_rescore_kernel(const float *__restrict
 }
 
 // ------------------------------------------------------------------ speculative thresholds (round 5)
+// (The product computes the prediction inside the margin select that precedes the next chunk -- select.hip: sel_rth_score_key,
+// sel_spec_words, the same words -- and launches pf_spec_kernel only in ablation builds, OI_SPEC_KERNEL; the reasoning below holds for both.)
 // The screen's threshold after m of n rows is PROVEN: tau~_m - 2 eps, tau~_m the k'-th best screen score of those m rows.  It is
 // weak while m << n (k' of 28 672 rows: 3.5 % of the next chunk pass; the final one passes 0.01 %), and every survivor of a weak
 // threshold costs staging, pool traffic and select time.  What the final threshold will be can be PREDICTED from the same m rows:
@@ -631,6 +590,24 @@ int oi_launch_spec_threshold(oi_ctx *ctx, const PoolView &pool, uint32_t n_queri
     hipLaunchKernelGGL(pf_spec_kernel, dim3(n_queries), dim3(256), 0, ctx->stream, pool.keys, pool.carry_cnt, pool.stride, pool.carry_cap, r,
                        eps2, pool.tau_keys, spec_tau, spec_max);
     OI_HIP_CHECK(hipGetLastError());
+    return OI_OK;
+}
+
+#ifdef OI_ABLATION
+// OI_SPEC_KERNEL=2: the words of the select's fused prediction against this file's kernel's, query by query
+__global__ void pf_spec_compare_kernel(uint32_t n, const uint32_t *tau_a, const uint32_t *max_a, const uint32_t *tau_b, const uint32_t *max_b) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < n && (tau_a[q] != tau_b[q] || max_a[q] != max_b[q]))
+        printf("SPEC MISMATCH q=%u: select (%08x, %08x) pf_spec_kernel (%08x, %08x)\n", q, tau_a[q], max_a[q], tau_b[q], max_b[q]);
+}
+#endif
+int oi_launch_spec_compare(oi_ctx *ctx, uint32_t n_queries, const uint32_t *tau_a, const uint32_t *max_a, const uint32_t *tau_b,
+                           const uint32_t *max_b) {
+#ifdef OI_ABLATION
+    if (n_queries == 0) return OI_OK;
+    hipLaunchKernelGGL(pf_spec_compare_kernel, dim3((n_queries + 255) / 256), dim3(256), 0, ctx->stream, n_queries, tau_a, max_a, tau_b, max_b);
+    OI_HIP_CHECK(hipGetLastError());
+#endif
     return OI_OK;
 }
 

@@ -43,6 +43,7 @@
 
 #include "oi_device.h"
 #include "oi_internal.h"
+#include "oi_screen_stage.h"
 #include "oi_lds_dma.h"
 
 typedef int i8s_i32x4 __attribute__((ext_vector_type(4)));
@@ -138,65 +139,89 @@ int oi_launch_make_screen_i8(oi_ctx *ctx, const float *rows, uint64_t n, uint32_
 // does not hold for (not finite, norm out of the bf16 screen's range) gets m2 = inf and opens the gate.
 #define I8S_NORM_LIMIT 1.0e15f
 #define I8S_QNORM_MIN 1.0e-12f
+// (one query row: all 64 lanes of the wave call)
+__device__ __forceinline__ void i8s_stage_query_row(const float *__restrict__ q, uint32_t row, uint32_t n_queries, uint32_t n_padded, uint32_t dim,
+                                                    const uint32_t *__restrict__ max_norm_bits, const uint32_t *__restrict__ emax_bits,
+                                                    int8_t *__restrict__ qi8, float *__restrict__ qf, uint32_t *gate) {
+    const uint32_t lane = threadIdx.x & 63;
+    const bool real = row < n_queries;
+    float amax = 0.f;
+    bool fin = true;
+    for (uint32_t k = lane; k < dim; k += 64) {
+        const float f = real ? q[(uint64_t)row * dim + k] : 0.f;
+        fin = fin && (f - f == 0.f);
+        amax = fmaxf(amax, fabsf(f));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, OI_WAVE));
+    fin = __builtin_amdgcn_ballot_w64(!fin) == 0ull;
+    const float a = fin ? amax / 127.f : 0.f;
+    double qn2 = 0.0, en2 = 0.0;
+    for (uint32_t k = lane; k < dim; k += 64) {
+        const float f = real ? q[(uint64_t)row * dim + k] : 0.f;
+        float h = 0.f, l = 0.f;
+        if (a > 0.f) {
+            const float t = f / a;
+            h = fminf(127.f, fmaxf(-127.f, rintf(t)));
+            l = fminf(127.f, fmaxf(-127.f, rintf((t - h) * 128.f)));
+        }
+        const double qh = (double)a * ((double)h + (double)l * 0.0078125); // exact in f64
+        qn2 += qh * qh;
+        en2 += (qh - (double)f) * (qh - (double)f);
+        qi8[(uint64_t)row * dim + k] = (int8_t)(int)h;
+        qi8[((uint64_t)n_padded + row) * dim + k] = (int8_t)(int)l;
+    }
+    qn2 = oi_wave_sum(qn2);
+    en2 = oi_wave_sum(en2);
+    if (lane == 0) {
+        const float up = 1.00000095367431640625f; // 1 + 2^-20
+        const float qn = (float)sqrt(qn2) * up, en = (float)sqrt(en2) * up;
+        const float X = __uint_as_float(max_norm_bits[0]), em = __uint_as_float(*emax_bits);
+        const bool ok = fin && amax > 0.f && qn < I8S_NORM_LIMIT && qn >= I8S_QNORM_MIN && X < I8S_NORM_LIMIT && em < I8S_NORM_LIMIT;
+        const float rnd = 3.814697265625e-06f + (float)dim * 2.384185791015625e-07f; // 2^-18 + d 2^-22
+        const float cq = 1.001f * (X * en + rnd * (X + em) * (qn + en)) + 1.0e-27f;
+        const float m2 = 2.002f * (em * qn + cq);
+        qf[row] = ok ? a : 0.f;
+        qf[n_padded + row] = ok ? qn : 0.f;
+        qf[2 * n_padded + row] = ok ? cq : 0.f;
+        qf[3 * n_padded + row] = ok || !real ? m2 : __builtin_inff();
+        if (real && !ok) *gate = 1u;
+    }
+}
 __global__ __launch_bounds__(256) void i8s_stage_kernel(const float *__restrict__ q, uint32_t n_queries, uint32_t n_padded, uint32_t dim,
                                                         const uint32_t *__restrict__ max_norm_bits, const uint32_t *__restrict__ emax_bits,
                                                         int8_t *__restrict__ qi8, float *__restrict__ qf, uint32_t *gate) {
-    const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
     for (uint32_t row = wave; row < n_padded; row += n_waves) {
-        const bool real = row < n_queries;
-        float amax = 0.f;
-        bool fin = true;
-        for (uint32_t k = lane; k < dim; k += 64) {
-            const float f = real ? q[(uint64_t)row * dim + k] : 0.f;
-            fin = fin && (f - f == 0.f);
-            amax = fmaxf(amax, fabsf(f));
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, OI_WAVE));
-        fin = __builtin_amdgcn_ballot_w64(!fin) == 0ull;
-        const float a = fin ? amax / 127.f : 0.f;
-        double qn2 = 0.0, en2 = 0.0;
-        for (uint32_t k = lane; k < dim; k += 64) {
-            const float f = real ? q[(uint64_t)row * dim + k] : 0.f;
-            float h = 0.f, l = 0.f;
-            if (a > 0.f) {
-                const float t = f / a;
-                h = fminf(127.f, fmaxf(-127.f, rintf(t)));
-                l = fminf(127.f, fmaxf(-127.f, rintf((t - h) * 128.f)));
-            }
-            const double qh = (double)a * ((double)h + (double)l * 0.0078125); // exact in f64
-            qn2 += qh * qh;
-            en2 += (qh - (double)f) * (qh - (double)f);
-            qi8[(uint64_t)row * dim + k] = (int8_t)(int)h;
-            qi8[((uint64_t)n_padded + row) * dim + k] = (int8_t)(int)l;
-        }
-        qn2 = oi_wave_sum(qn2);
-        en2 = oi_wave_sum(en2);
-        if (lane == 0) {
-            const float up = 1.00000095367431640625f; // 1 + 2^-20
-            const float qn = (float)sqrt(qn2) * up, en = (float)sqrt(en2) * up;
-            const float X = __uint_as_float(max_norm_bits[0]), em = __uint_as_float(*emax_bits);
-            const bool ok = fin && amax > 0.f && qn < I8S_NORM_LIMIT && qn >= I8S_QNORM_MIN && X < I8S_NORM_LIMIT && em < I8S_NORM_LIMIT;
-            const float rnd = 3.814697265625e-06f + (float)dim * 2.384185791015625e-07f; // 2^-18 + d 2^-22
-            const float cq = 1.001f * (X * en + rnd * (X + em) * (qn + en)) + 1.0e-27f;
-            const float m2 = 2.002f * (em * qn + cq);
-            qf[row] = ok ? a : 0.f;
-            qf[n_padded + row] = ok ? qn : 0.f;
-            qf[2 * n_padded + row] = ok ? cq : 0.f;
-            qf[3 * n_padded + row] = ok || !real ? m2 : __builtin_inff();
-            if (real && !ok) *gate = 1u;
-        }
+        i8s_stage_query_row(q, row, n_queries, n_padded, dim, max_norm_bits, emax_bits, qi8, qf, gate);
+    }
+}
+
+// The int8 route stages both tiers' blocks in ONE launch: per query row the int8 body above, then the bf16 screen's
+// (oi_screen_stage.h: bf16 copy, eps2, gate) -- the words pf_stage_queries_kernel writes, the row read a second time from cache.
+__global__ __launch_bounds__(256) void i8s_stage_both_kernel(const float *__restrict__ q, uint32_t n_queries, uint32_t n_padded, uint32_t dim,
+                                                             const uint32_t *__restrict__ max_norm_bits, const uint32_t *__restrict__ emax_bits,
+                                                             int8_t *__restrict__ qi8, float *__restrict__ qf, uint16_t *__restrict__ q_bf16,
+                                                             float *__restrict__ eps2, uint32_t *gate) {
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t row = wave; row < n_padded; row += n_waves) {
+        i8s_stage_query_row(q, row, n_queries, n_padded, dim, max_norm_bits, emax_bits, qi8, qf, gate);
+        pf_stage_query_row(q, row, n_queries, dim, max_norm_bits, q_bf16, eps2, gate);
     }
 }
 
 int oi_launch_screen_stage_i8(oi_ctx *ctx, const float *d_queries, uint32_t n_queries, uint32_t dim, const uint32_t *max_norm_bits,
-                              const uint8_t *i8_copy, uint64_t n_rows, int8_t *qi8, float *qf, uint32_t *gate) {
+                              const uint8_t *i8_copy, uint64_t n_rows, int8_t *qi8, float *qf, uint32_t *gate, uint16_t *q_bf16,
+                              float *eps2) {
     const uint32_t n_padded = (n_queries + 31u) & ~31u;
     if (n_padded == 0) return OI_OK;
     const uint32_t *emax = reinterpret_cast<const uint32_t *>(i8_copy + oi_screen_i8_meta_offset(n_rows, dim)) + 2 * (n_rows + I8S_PAD_ROWS);
-    hipLaunchKernelGGL(i8s_stage_kernel, dim3((n_padded + 3) / 4), dim3(256), 0, ctx->stream, d_queries, n_queries, n_padded, dim,
-                       max_norm_bits, emax, qi8, qf, gate);
+    if (q_bf16) // the bf16 screen's block as well (oi_launch_screen_stage's outputs)
+        hipLaunchKernelGGL(i8s_stage_both_kernel, dim3((n_padded + 3) / 4), dim3(256), 0, ctx->stream, d_queries, n_queries, n_padded, dim,
+                           max_norm_bits, emax, qi8, qf, q_bf16, eps2, gate);
+    else
+        hipLaunchKernelGGL(i8s_stage_kernel, dim3((n_padded + 3) / 4), dim3(256), 0, ctx->stream, d_queries, n_queries, n_padded, dim,
+                           max_norm_bits, emax, qi8, qf, gate);
     OI_HIP_CHECK(hipGetLastError());
     return OI_OK;
 }

@@ -307,6 +307,10 @@ struct SelectExtra {
     const float *row_meta = nullptr;
     uint32_t meta_base = 0;
     const float *row_qn = nullptr, *row_cq = nullptr;
+    // margin mode: the speculative threshold rides in the select (cosine_prefilter.hip: what pf_spec_kernel computes, from the
+    // keys the select holds): spec_rank = r > 0 and both pointers set
+    uint32_t spec_rank = 0;
+    uint32_t *spec_tau = nullptr, *spec_max = nullptr;
 };
 int oi_launch_select(oi_ctx *ctx, const PoolView &pool, uint32_t n_queries, uint32_t k, bool compact,
                      float *out_scores, uint32_t *out_docs, uint32_t *out_counts, uint32_t out_stride,
@@ -378,7 +382,9 @@ size_t oi_screen_i8_meta_offset(uint64_t n, uint32_t dim);
 int oi_launch_make_screen_i8(oi_ctx *ctx, const float *rows, uint64_t n, uint32_t dim, const uint32_t *long_bitmap, uint8_t *out);
 // per search: i8 hi / lo query blocks (qi8: [2][n_padded][dim]) and four floats per query in qf: qa, qn, cq, eps2 (the tier's margin)
 int oi_launch_screen_stage_i8(oi_ctx *ctx, const float *d_queries, uint32_t n_queries, uint32_t dim, const uint32_t *max_norm_bits,
-                              const uint8_t *i8_copy, uint64_t n_rows, int8_t *qi8, float *qf, uint32_t *gate);
+                              const uint8_t *i8_copy, uint64_t n_rows, int8_t *qi8, float *qf, uint32_t *gate,
+                              uint16_t *q_bf16 = nullptr, float *eps2 = nullptr);
+// (q_bf16 / eps2 set: the same launch also writes what oi_launch_screen_stage writes -- the int8 route stages once)
 int oi_launch_cosine_screen_i8_chunk(oi_ctx *ctx, const uint8_t *i8_copy, uint64_t n_rows_total, uint64_t row_begin, uint64_t row_end,
                                      uint32_t dim, const int8_t *qi8, const float *qf, uint32_t n_queries, uint32_t doc_id_base,
                                      PoolView &pool);
@@ -393,8 +399,13 @@ int oi_launch_screen_probe(oi_ctx *ctx, const float *rows, uint64_t row_begin, u
 // speculative thresholds of the screen (cosine_prefilter.hip): the r-th best screen score so far - 2 eps, if above the proven
 // threshold, for the NEXT chunk (spec_tau), the largest one used per query (spec_max); the check against the final one rides in
 // oi_launch_rescore (spec_max, tau_final, gate, fail_host)
+// (the product computes them inside the margin select that precedes the next chunk -- SelectExtra::spec_rank, select.hip; the
+// separate launch stays for A/B runs of ablation builds, OI_SPEC_KERNEL, and oi_launch_spec_compare reports, from the device, any
+// word of theirs that differs)
 int oi_launch_spec_threshold(oi_ctx *ctx, const PoolView &pool, uint32_t n_queries, uint32_t r, const float *eps2, uint32_t *spec_tau,
                              uint32_t *spec_max);
+int oi_launch_spec_compare(oi_ctx *ctx, uint32_t n_queries, const uint32_t *tau_a, const uint32_t *max_a, const uint32_t *tau_b,
+                           const uint32_t *max_b);
 int oi_launch_rescore(oi_ctx *ctx, const float *rows, uint64_t n_rows, uint32_t dim, uint32_t doc_id_base,
                       const float *d_queries, uint32_t n_queries, const PoolView &in, const PoolView &out,
                       const uint32_t *extra_docs = nullptr, uint32_t n_extra = 0, const uint32_t *spec_max = nullptr,

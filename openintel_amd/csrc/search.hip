@@ -197,7 +197,7 @@ Plan plan_search(const Search &s) {
             if (hipHostMalloc(reinterpret_cast<void **>(&ctx->spec_fail_host), 64, hipHostMallocDefault) == hipSuccess) *ctx->spec_fail_host = 0;
             else { (void)hipGetLastError(); ctx->spec_fail_host = nullptr; p.spec = false; } // (no way to hear of a failed check: no speculation)
         }
-        if (p.spec && n) { // does the rank after the FIRST chunk qualify (pf_spec_kernel is launched when 2 r <= k')?
+        if (p.spec && n) { // does the rank after the FIRST chunk qualify (a prediction is made, in the chunk's margin select, when 2 r <= k')?
             // a SHORT first chunk (a quarter of the proven schedule's, >= 8192 rows, >= 8 k': its only job is the sample the
             // prediction is read from) when everything after it fits ONE launch -- a shard: 8 192 rows, then the rest
             // (1.25M rows: 0.540 -> 0.523 ms against 28 672 + the rest); a corpus that needs three launches anyway keeps the
@@ -445,7 +445,9 @@ int cosine_screen(const Search &s, const Plan &p, const Pools &P, uint32_t *w, c
     uint32_t *spec_tau = pf_seg + (size_t)B * segs, *spec_max = spec_tau + B;
     PoolView PF{pk.as<uint64_t>(), pf_cnt, pf_seg, pf_tau, p.pf_stride, p.pf_carry, 0, 0, segs, P.cos.overflow, s.filt, s.attrs};
     PoolView RS{rk.as<uint64_t>(), rs_cnt, pf_seg, nullptr, rs_cap, rs_cap, 0, 0, segs, P.cos.overflow, s.filt, s.attrs};
-    OI_CHECK(oi_launch_screen_stage(ctx, s.qv, B, dim, idx->max_row_norm.as<uint32_t>(), qb.as<uint16_t>(), eps2, gate));
+    // (the int8 route stages the bf16 block in its own staging launch, below; OI_STAGE_SPLIT, ablation builds: two launches as before)
+    static const bool stage_split = oi_ablation_env("OI_STAGE_SPLIT") != nullptr;
+    if (!i8 || stage_split) OI_CHECK(oi_launch_screen_stage(ctx, s.qv, B, dim, idx->max_row_norm.as<uint32_t>(), qb.as<uint16_t>(), eps2, gate));
     SelectExtra mx; mx.eps2 = eps2; mx.margin_gate = gate;
     if (idx->n_long) { mx.skip_bitmap = idx->long_bitmap.as<uint32_t>(); mx.skip_base = idx->doc_id_base; }
     if (copy && !idx->screen_copy.p) { // made once, on the first search that asks for it (n x d x 2 B of HBM)
@@ -466,7 +468,7 @@ int cosine_screen(const Search &s, const Plan &p, const Pools &P, uint32_t *w, c
         qi8 = reinterpret_cast<int8_t *>(qs.p);
         qf8 = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(qs.p) + qi8_bytes);
         OI_CHECK(oi_launch_screen_stage_i8(ctx, s.qv, B, dim, idx->max_row_norm.as<uint32_t>(), idx->screen_i8.as<uint8_t>(), n,
-                                           qi8, qf8, gate));
+                                           qi8, qf8, gate, stage_split ? nullptr : qb.as<uint16_t>(), stage_split ? nullptr : eps2));
         m8.eps2 = qf8 + 3 * (size_t)n_padded; m8.row_qn = qf8 + (size_t)n_padded; m8.row_cq = qf8 + 2 * (size_t)n_padded;
         m8.cand = cb.as<uint64_t>(); m8.cand_cap = OI_I8_CARRY;
         m8.row_meta = reinterpret_cast<const float *>(idx->screen_i8.as<uint8_t>() + oi_screen_i8_meta_offset(n, dim));
@@ -489,15 +491,32 @@ int cosine_screen(const Search &s, const Plan &p, const Pools &P, uint32_t *w, c
         PF.tau_keys = proven_tau;
         OI_CHECK(rc_screen);
         if (p.late_fork && last) OI_CHECK(fork_bm25(s, p, P.bm)); // ... enqueued after it: the screen's workgroups get their CUs first
-        OI_CHECK(oi_launch_select(ctx, PF, B, depth, /*compact=*/true, nullptr, nullptr, nullptr, depth, i8 ? &m8 : &mx));
+        // The prediction for the next chunk rides in this chunk's margin select (select.hip), which holds the carried keys in
+        // registers.  expected rank of the final k'-th among the e rows seen: depth e / n; three times that plus twelve
+        // OI_SPEC_KERNEL (ablation builds): 1 = the separate pf_spec_kernel launch as before; 2 = both, compared on the device
+        static const int spec_kernel = oi_ablation_env("OI_SPEC_KERNEL") ? atoi(oi_ablation_env("OI_SPEC_KERNEL")) : 0;
+        const uint64_t rank = (3ull * depth * e + n - 1) / n + 12;
+        const bool spec_here = p.spec && !last && 2 * rank <= depth;
+        SelectExtra sx = i8 ? m8 : mx;
+        if (spec_here && spec_kernel != 1) { sx.spec_rank = (uint32_t)rank; sx.spec_tau = spec_tau; sx.spec_max = spec_max; }
+        uint32_t *chk = nullptr; // OI_SPEC_KERNEL=2: spec_tau'[B] spec_max'[B], spec_max' starting from the words the select starts from
+        if (spec_here && spec_kernel == 2) {
+            DevBuf &cw = ctx->buf("spec_check");
+            OI_CHECK(cw.ensure(sizeof(uint32_t) * 2 * (size_t)B));
+            chk = cw.as<uint32_t>();
+            OI_HIP_CHECK(hipMemcpyAsync(chk + B, spec_max, sizeof(uint32_t) * B, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        OI_CHECK(oi_launch_select(ctx, PF, B, depth, /*compact=*/true, nullptr, nullptr, nullptr, depth, &sx));
         spec_next = false;
-        if (p.spec && !last) {
-            // expected rank of the final k'-th among the e rows seen: depth e / n; three times that plus twelve
-            const uint64_t rank = (3ull * depth * e + n - 1) / n + 12;
-            if (2 * rank <= depth) {
-                OI_CHECK(oi_launch_spec_threshold(ctx, PF, B, (uint32_t)rank, i8 ? m8.eps2 : eps2, spec_tau, spec_max));
-                spec_next = spec_any = true;
+        if (spec_here) {
+            // (the profile's "spec" spans count the predictions made: an empty one where the select made it)
+            if (spec_kernel != 1) { ProfScope ps(ctx, "spec"); }
+            if (spec_kernel == 1) OI_CHECK(oi_launch_spec_threshold(ctx, PF, B, (uint32_t)rank, sx.eps2, spec_tau, spec_max));
+            if (chk) {
+                OI_CHECK(oi_launch_spec_threshold(ctx, PF, B, (uint32_t)rank, sx.eps2, chk, chk + B));
+                OI_CHECK(oi_launch_spec_compare(ctx, B, spec_tau, spec_max, chk, chk + B));
             }
+            spec_next = spec_any = true;
         }
     }
     if (spec_any) ++ctx->spec_searches;

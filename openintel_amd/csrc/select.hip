@@ -237,11 +237,29 @@ struct SelRowMargin {
     uint32_t base;
     float qn, cq;
 };
-__device__ __forceinline__ bool sel_row_keep(const SelRowMargin *rm, uint64_t kv, float edge, float eps2) {
-    if (!rm) return true;
-    const float e = rm->meta[2 * (uint64_t)(oi_rank_key_doc(kv) - rm->base) + 1];
+// (the gather and the test apart: the fast margin path issues a group of gathers before it evaluates any)
+__device__ __forceinline__ float sel_row_e(const SelRowMargin *rm, uint64_t kv) {
+    return rm->meta[2 * (uint64_t)(oi_rank_key_doc(kv) - rm->base) + 1];
+}
+__device__ __forceinline__ bool sel_row_test(const SelRowMargin *rm, uint64_t kv, float e, float edge, float eps2) {
     const float u = oi_rank_key_score(kv) + 2.002f * (e * rm->qn + rm->cq);
     return u >= edge - 9.5367431640625e-07f * (fabsf(edge) + eps2);
+}
+__device__ __forceinline__ bool sel_row_keep(const SelRowMargin *rm, uint64_t kv, float edge, float eps2) {
+    if (!rm) return true;
+    return sel_row_test(rm, kv, sel_row_e(rm, kv), edge, eps2);
+}
+
+// The speculative threshold of a query from the r-th largest score key of its carry region (sel_rth_score_key; have: r keys were
+// there) -- pf_spec_kernel's last step (cosine_prefilter.hip), word for word: lowered by the margin, never below the proven
+// threshold tau, and the largest one used is remembered for the check.  One thread calls.
+__device__ __forceinline__ void sel_spec_words(bool have, uint32_t rth_key, float eps2, uint32_t tau, uint32_t *spec_tau, uint32_t *spec_max) {
+    if (!have) { *spec_tau = tau; return; } // too few keys kept: the proven threshold as it is
+    const float s = oi_key_f32(rth_key) - eps2; // (a query without a bound has eps2 = +inf: -inf, no speculation)
+    const uint32_t T = s == s ? oi_f32_key(s) : 0u;
+    const uint32_t st = T > tau ? T : tau;
+    *spec_tau = st;
+    if (st > tau && st > *spec_max) *spec_max = st;
 }
 
 struct SelShared {
@@ -384,6 +402,95 @@ __device__ __forceinline__ void sel_threshold(FE &&for_each, uint32_t kk_in, Sel
     __syncthreads(); // sh.prefix / sh.kk may be rewritten by the next call
 }
 
+// sh.hist2k holds a histogram of 2048 digits (filled, barrier passed): which digit holds the kk-th key counted from the top?
+// -> sh.prefix = the digit, sh.kk = the rank inside it, sh.bin_cnt = 1; fewer than kk keys: sh.bin_cnt = 0xFFFFFFFF.  All threads
+// call; the words are readable on return (and rewritten by the next call: a barrier before that).
+__device__ __forceinline__ void sel_rank_bin2k(SelShared &sh, uint32_t kk, int pass) {
+    const uint32_t tid = threadIdx.x;
+    { // 64 super-bins of 32 bins: a thread adds two bins, a DPP row (16 lanes) the 32 of a super-bin -- conflict-free reads
+        uint32_t v = sh.hist2k[2 * tid] + sh.hist2k[2 * tid + 1];
+        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
+        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
+        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
+        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
+        if ((tid & 15u) == 15u) sh.hist[tid >> 4] = v; // super-bin s = bins [32 s, 32 s + 32)
+    }
+    __syncthreads();
+    if (tid < 64) { // wave 0: the super-bin, then the bin, holding the kk-th key counted from the top -- two scans, no walk
+        const uint32_t x = sh.hist[63u - tid];
+        const uint32_t incl = oi_wave_incl_scan(x);
+        const unsigned long long ball = __ballot(incl >= kk);
+        if (!ball) {
+            if (tid == 0) sh.bin_cnt = 0xFFFFFFFFu; // fewer than kk valid keys
+        } else {
+            const uint32_t l1 = (uint32_t)__builtin_ctzll(ball), sb = 63u - l1;
+            const uint32_t kk2 = kk - (uint32_t)__builtin_amdgcn_readlane((int)(incl - x), (int)l1);
+            const uint32_t y = tid < 32u ? sh.hist2k[32u * sb + 31u - tid] : 0u;
+            const uint32_t incl2 = oi_wave_incl_scan(y);
+            const unsigned long long ball2 = __ballot(incl2 >= kk2); // (non-empty: the super-bin holds >= kk2 keys)
+            const uint32_t l2 = ball2 ? (uint32_t)__builtin_ctzll(ball2) : 31u;
+            // (read with every lane active: inside the one-lane branch below hipcc computes incl2 - y for that lane only)
+            const uint32_t above = (uint32_t)__builtin_amdgcn_readlane((int)(incl2 - y), (int)l2);
+            if (tid == 0) {
+                sh.prefix = (uint64_t)(32u * sb + 31u - l2);
+                sh.kk = kk2 - above;
+                sh.bin_cnt = 1u;
+#ifdef OI_ABLATION
+                if (sel_dbg_on > 1) { // OI_SELECT_STAMPS=2: self-check against the plain walk from the top
+                    uint32_t cum = 0; int dd = 2047;
+                    for (; dd >= 0; --dd) { if (cum + sh.hist2k[dd] >= kk) break; cum += sh.hist2k[dd]; }
+                    if ((uint32_t)dd != (uint32_t)sh.prefix || kk - cum != sh.kk)
+                        printf("MISMATCH q=%u pass=%d kk=%u: walk (%d, %u) super-bin (%u, %u) sb=%u l1=%u kk2=%u l2=%u\n", blockIdx.x, pass, kk, dd, kk - cum,
+                               (uint32_t)sh.prefix, sh.kk, sb, l1, kk2, l2);
+                }
+#endif
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// The r-th largest 32-bit score key of the keys `for_each` enumerates (f(valid, key), the same keys on every call; 1 <= r <= their
+// number): digits of 11, 11 and 10 bits from the top through the same histogram.  This is the key pf_spec_kernel
+// (cosine_prefilter.hip) finds in the carry region -- the r-th largest of a set is unique -- taken from the keys the select
+// already holds.  All threads call; the result is uniform.  sh.hist2k / prefix / kk / bin_cnt are free on entry and on return.
+template <class FE>
+__device__ __forceinline__ uint32_t sel_rth_score_key(FE &&for_each, uint32_t r, SelShared &sh) {
+    const uint32_t tid = threadIdx.x;
+    uint32_t kk = r, pfx = 0;
+#pragma unroll
+    for (int pass = 0; pass < 3; ++pass) {
+        const int shift = pass == 0 ? 21 : pass == 1 ? 10 : 0, bits = pass == 2 ? 10 : 11;
+        sh.hist2k[tid] = 0;
+        sh.hist2k[tid + SEL_THREADS] = 0;
+        __syncthreads();
+        if (pass == 0) { // (few leading digits: runs per thread, then per wave, as in the margin select's first pass)
+            uint32_t run_d = 0, run_c = 0;
+            for_each([&](bool valid, uint64_t kv) {
+                if (valid) {
+                    const uint32_t d = (uint32_t)(kv >> 53);
+                    if (run_c && d != run_d) { atomicAdd(&sh.hist2k[run_d], run_c); run_c = 0; }
+                    run_d = d;
+                    ++run_c;
+                }
+            });
+            sel_hist_add_w(sh.hist2k, run_c != 0u, run_d, run_c);
+        } else {
+            for_each([&](bool valid, uint64_t kv) {
+                const uint32_t sk = (uint32_t)(kv >> 32);
+                if (valid && (sk >> (shift + bits)) == pfx) atomicAdd(&sh.hist2k[(sk >> shift) & ((1u << bits) - 1u)], 1u);
+            });
+        }
+        __syncthreads();
+        sel_rank_bin2k(sh, kk, 2 + pass);
+        const uint32_t d = sh.bin_cnt != 0xFFFFFFFFu ? (uint32_t)sh.prefix : 0u; // (r <= the number of keys: always found)
+        kk = sh.kk;
+        __syncthreads();
+        pfx = (pfx << bits) | d;
+    }
+    return pfx;
+}
+
 // Selects the top min(n, k) keys of K into sel[], returns their number.  KPT > 0: the keys live in registers
 // (n <= KPT * SEL_THREADS); KPT == 0: every pass re-loads them through the flat view.  sh.cnt == 0 on entry.
 //
@@ -395,7 +502,11 @@ template <int KPT>
 __device__ __forceinline__ uint32_t sel_flat_select(const SelFlat &K, uint32_t k, SelShared &sh, uint64_t *sel,
                                                     uint64_t *cand, float eps2, bool *in_cand, uint32_t *margin_tau,
                                                     bool *margin_overflow, const uint32_t *skip, uint32_t skip_base,
-                                                    uint64_t *mc, uint32_t mcap, const SelRowMargin *rm) {
+                                                    uint64_t *mc, uint32_t mcap, const SelRowMargin *rm, uint64_t *carry,
+                                                    bool *in_carry, uint32_t spec_rank, uint32_t *spec_key) {
+    // carry (KPT > 0, the fast margin path): this query's carry region.  Every key of the pool is in registers before the first
+    // barrier, so the survivors are written there directly (*in_carry = true) instead of to mc and copied; and with spec_rank
+    // = r, r <= the survivors kept, *spec_key = the r-th largest score key among them (sel_rth_score_key), else left alone.
     // skip (the screen's two-class margin): keys of docs marked in this bitmap do not take part -- they are scored exactly
     // whatever happens here, and their screen scores must not move the threshold (cosine_prefilter.hip)
     auto skipped = [&](uint64_t kv) -> bool {
@@ -491,47 +602,7 @@ __device__ __forceinline__ uint32_t sel_flat_select(const SelFlat &K, uint32_t k
                 });
             }
             __syncthreads();
-            { // 64 super-bins of 32 bins: a thread adds two bins, a DPP row (16 lanes) the 32 of a super-bin -- conflict-free reads
-                uint32_t v = sh.hist2k[2 * tid] + sh.hist2k[2 * tid + 1];
-                v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
-                v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
-                v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
-                v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
-                if ((tid & 15u) == 15u) sh.hist[tid >> 4] = v; // super-bin s = bins [32 s, 32 s + 32)
-            }
-            __syncthreads();
-            if (tid < 64) { // wave 0: the super-bin, then the bin, holding the kk-th key counted from the top -- two scans, no walk
-                const uint32_t x = sh.hist[63u - tid];
-                const uint32_t incl = oi_wave_incl_scan(x);
-                const unsigned long long ball = __ballot(incl >= kk);
-                if (!ball) {
-                    if (tid == 0) sh.bin_cnt = 0xFFFFFFFFu; // fewer than kk valid keys
-                } else {
-                    const uint32_t l1 = (uint32_t)__builtin_ctzll(ball), sb = 63u - l1;
-                    const uint32_t kk2 = kk - (uint32_t)__builtin_amdgcn_readlane((int)(incl - x), (int)l1);
-                    const uint32_t y = tid < 32u ? sh.hist2k[32u * sb + 31u - tid] : 0u;
-                    const uint32_t incl2 = oi_wave_incl_scan(y);
-                    const unsigned long long ball2 = __ballot(incl2 >= kk2); // (non-empty: the super-bin holds >= kk2 keys)
-                    const uint32_t l2 = ball2 ? (uint32_t)__builtin_ctzll(ball2) : 31u;
-                    // (read with every lane active: inside the one-lane branch below hipcc computes incl2 - y for that lane only)
-                    const uint32_t above = (uint32_t)__builtin_amdgcn_readlane((int)(incl2 - y), (int)l2);
-                    if (tid == 0) {
-                        sh.prefix = (uint64_t)(32u * sb + 31u - l2);
-                        sh.kk = kk2 - above;
-                        sh.bin_cnt = 1u;
-#ifdef OI_ABLATION
-                        if (sel_dbg_on > 1) { // OI_SELECT_STAMPS=2: self-check against the plain walk from the top
-                            uint32_t cum = 0; int dd = 2047;
-                            for (; dd >= 0; --dd) { if (cum + sh.hist2k[dd] >= kk) break; cum += sh.hist2k[dd]; }
-                            if ((uint32_t)dd != (uint32_t)sh.prefix || kk - cum != sh.kk)
-                                printf("MISMATCH q=%u pass=%d kk=%u: walk (%d, %u) super-bin (%u, %u) sb=%u l1=%u kk2=%u l2=%u\n", blockIdx.x, pass, kk, dd, kk - cum,
-                                       (uint32_t)sh.prefix, sh.kk, sb, l1, kk2, l2);
-                        }
-#endif
-                    }
-                }
-            }
-            __syncthreads();
+            sel_rank_bin2k(sh, kk, pass);
             enough = sh.bin_cnt != 0xFFFFFFFFu;
             const uint32_t d = (uint32_t)sh.prefix;
             kk = sh.kk;
@@ -549,18 +620,65 @@ __device__ __forceinline__ uint32_t sel_flat_select(const SelFlat &K, uint32_t k
             uint32_t mine = 0;
             const float edge = oi_key_f32(tkey);
             auto keep = [&](bool valid, uint64_t kv) { return valid && (uint32_t)(kv >> 32) >= t32 && sel_row_keep(rm, kv, edge, eps2); };
-            for_each([&](bool valid, uint64_t kv) { mine += keep(valid, kv) ? 1u : 0u; });
+            uint32_t verdict = 0; // KPT > 0, bit j: key[j] survives -- each key is tested ONCE, the storing pass reads the mask
+            if constexpr (KPT > 0) {
+#pragma unroll
+                for (int j = 0; j < KPT; ++j) // the cheap global test first
+                    if ((uint32_t)j < kpt && first + (uint32_t)j * 64 < n && !((dead >> j) & 1u) && (uint32_t)(key[j] >> 32) >= t32) verdict |= 1u << j;
+                if (rm) { // the row test: the gathers of a group of keys that passed are issued together, then evaluated
+                    constexpr int G = KPT < 8 ? KPT : 8;
+#pragma unroll
+                    for (int j0 = 0; j0 < KPT; j0 += G) {
+                        if ((uint32_t)j0 < kpt) { // (uniform)
+                            float e[G];
+#pragma unroll
+                            for (int u = 0; u < G; ++u) e[u] = (verdict >> (j0 + u)) & 1u ? sel_row_e(rm, key[j0 + u]) : 0.f;
+#pragma unroll
+                            for (int u = 0; u < G; ++u)
+                                if (((verdict >> (j0 + u)) & 1u) && !sel_row_test(rm, key[j0 + u], e[u], edge, eps2)) verdict &= ~(1u << (j0 + u));
+                        }
+                    }
+                }
+                mine = (uint32_t)__popc(verdict);
+            } else {
+                for_each([&](bool valid, uint64_t kv) { mine += keep(valid, kv) ? 1u : 0u; });
+            }
             const uint32_t incl = oi_wave_incl_scan(mine);
             const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             uint32_t base = 0;
             if (lane == 0 && tot) base = atomicAdd(&sh.cnt, tot);
             uint32_t pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)base) + incl - mine;
-            for_each([&](bool valid, uint64_t kv) {
-                if (keep(valid, kv)) {
-                    if (pos < mcap) mc[pos] = kv;
-                    ++pos;
+            if constexpr (KPT > 0) {
+                uint32_t stored = 0; // bit j: key[j] went into the carry region (all of verdict unless the survivors overflow it)
+#pragma unroll
+                for (int j = 0; j < KPT; ++j) {
+                    if ((verdict >> j) & 1u) {
+                        if (pos < mcap) { carry[pos] = key[j]; stored |= 1u << j; }
+                        ++pos;
+                    }
                 }
-            });
+                *in_carry = true;
+                __syncthreads();
+                const uint32_t c = sh.cnt, kept = c > mcap ? mcap : c;
+                SEL_STAMP(5);
+                if (spec_rank && kept >= spec_rank) // (uniform) the prediction, over the keys that were stored
+                    *spec_key = sel_rth_score_key([&](auto &&f) {
+#pragma unroll
+                        for (int j = 0; j < KPT; ++j)
+                            if ((uint32_t)j < kpt) f((stored >> j) & 1u, key[j]);
+                    }, spec_rank, sh);
+                *in_cand = true;
+                *margin_tau = t32;
+                *margin_overflow = c > mcap;
+                return kept;
+            } else {
+                for_each([&](bool valid, uint64_t kv) {
+                    if (keep(valid, kv)) {
+                        if (pos < mcap) mc[pos] = kv;
+                        ++pos;
+                    }
+                });
+            }
             __syncthreads();
             const uint32_t c = sh.cnt;
             *in_cand = true;
@@ -667,7 +785,8 @@ __global__ __launch_bounds__(SEL_THREADS) void select_flat_kernel(
     uint32_t carry_cap, uint32_t seg_cap, uint32_t n_segs, uint32_t seg_cnt_stride, uint32_t *overflow,
     uint32_t k, int compact, float *out_scores, uint32_t *out_docs, uint32_t *out_counts, uint32_t out_stride,
     const float *eps2, uint32_t *margin_gate, const uint32_t *run_gate, const uint32_t *skip, uint32_t skip_base,
-    uint64_t *cand_g, uint32_t cand_cap, const float *row_meta, uint32_t meta_base, const float *row_qn, const float *row_cq) {
+    uint64_t *cand_g, uint32_t cand_cap, const float *row_meta, uint32_t meta_base, const float *row_qn, const float *row_cq,
+    uint32_t spec_rank, uint32_t *spec_tau, uint32_t *spec_max) {
     // run_gate: this launch belongs to the gated exact pipeline (cosine_prefilter.hip) and only runs when the
     // screen gave up.  eps2: margin mode (see sel_flat_select); its overflow opens that gate.
     if (run_gate && *run_gate == 0u) return;
@@ -730,19 +849,27 @@ __global__ __launch_bounds__(SEL_THREADS) void select_flat_kernel(
     SEL_STAMP(1);
 
     uint32_t m, m_tau = 0;
-    bool in_cand = false, m_over = false;
-    if (K.n <= 4 * SEL_THREADS) m = sel_flat_select<4>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm);
-    else if (K.n <= 8 * SEL_THREADS) m = sel_flat_select<8>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm);
-    else if (K.n <= 16 * SEL_THREADS) m = sel_flat_select<16>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm);
-    else if (K.n <= SEL_KPT_MAX * SEL_THREADS) m = sel_flat_select<SEL_KPT_MAX>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm);
-    else m = sel_flat_select<0>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm);
+    bool in_cand = false, m_over = false, in_carry = false;
+    uint32_t spec_key = 0;
+    if (K.n <= 4 * SEL_THREADS) m = sel_flat_select<4>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm, pool, &in_carry, spec_rank, &spec_key);
+    else if (K.n <= 8 * SEL_THREADS) m = sel_flat_select<8>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm, pool, &in_carry, spec_rank, &spec_key);
+    else if (K.n <= 16 * SEL_THREADS) m = sel_flat_select<16>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm, pool, &in_carry, spec_rank, &spec_key);
+    else if (K.n <= SEL_KPT_MAX * SEL_THREADS) m = sel_flat_select<SEL_KPT_MAX>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm, pool, &in_carry, spec_rank, &spec_key);
+    else m = sel_flat_select<0>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm, pool, &in_carry, spec_rank, &spec_key);
     if (in_cand) { // margin mode: an unsorted superset of the top k in cand[]; only ever compacted
         if (m_over && tid == 0 && margin_gate) *margin_gate = 1u;
-        for (uint32_t i = tid; i < m; i += SEL_THREADS) pool[i] = mc[i];
+        if (!in_carry) // (the fast path with the keys in registers wrote the carry region itself)
+            for (uint32_t i = tid; i < m; i += SEL_THREADS) pool[i] = mc[i];
         for (uint32_t sg = tid; sg < n_segs; sg += SEL_THREADS) segc[sg] = 0;
+        if (spec_rank && !in_carry && m >= spec_rank) // (uniform) the prediction from the keys just copied
+            spec_key = sel_rth_score_key([&](auto &&f) {
+                for (uint32_t i0 = 0; i0 < m; i0 += SEL_THREADS) f(i0 + tid < m, mc[i0 + tid < m ? i0 + tid : 0]);
+            }, spec_rank, sh);
         if (tid == 0) {
             carry_cnt[q] = m;
-            if (tau_keys && m_tau > tau_keys[q]) tau_keys[q] = m_tau;
+            uint32_t tau = tau_keys ? tau_keys[q] : 0u;
+            if (tau_keys && m_tau > tau) tau_keys[q] = tau = m_tau;
+            if (spec_rank) sel_spec_words(m >= spec_rank, spec_key, e2, tau, spec_tau + q, spec_max + q);
         }
 #ifdef OI_ABLATION
         __syncthreads();
@@ -791,6 +918,14 @@ __global__ __launch_bounds__(SEL_THREADS) void select_flat_kernel(
                 if (t > tau_keys[q]) tau_keys[q] = t;
             }
         }
+        if (spec_rank) { // a margin select of a pool of <= k keys (or of fewer than k valid ones): the prediction all the same
+            __syncthreads();
+            if (m >= spec_rank) // (uniform)
+                spec_key = sel_rth_score_key([&](auto &&f) {
+                    for (uint32_t i0 = 0; i0 < m; i0 += SEL_THREADS) f(i0 + tid < m, sel[i0 + tid < m ? i0 + tid : 0]);
+                }, spec_rank, sh);
+            if (tid == 0) sel_spec_words(m >= spec_rank, spec_key, e2, tau_keys ? tau_keys[q] : 0u, spec_tau + q, spec_max + q);
+        }
     }
 }
 
@@ -816,6 +951,9 @@ int oi_launch_select(oi_ctx *ctx, const PoolView &pool, uint32_t n_queries, uint
         OI_REQUIRE(!extra->eps2 || (compact && !out_scores && pool.carry_cap >= mcap),
                    "select: margin mode compacts into a carry region of >= %u keys", mcap);
     }
+    const bool spec = extra && extra->spec_rank;
+    OI_REQUIRE(!spec || (extra->eps2 && extra->spec_tau && extra->spec_max && pool.tau_keys),
+               "select: a speculative threshold needs margin mode, thresholds and both output arrays");
     if ((!v1 || special) && pool.n_segs <= SEL_MAX_SEGS) {
         hipLaunchKernelGGL(select_flat_kernel, dim3(n_queries), dim3(SEL_THREADS), 0, ctx->stream, pool.keys,
                            pool.carry_cnt, pool.seg_cnt, pool.tau_keys, pool.stride, pool.carry_cap, pool.seg_cap,
@@ -824,7 +962,8 @@ int oi_launch_select(oi_ctx *ctx, const PoolView &pool, uint32_t n_queries, uint
                            extra ? extra->run_gate : nullptr, extra && extra->eps2 ? extra->skip_bitmap : nullptr,
                            extra ? extra->skip_base : 0u, extra && extra->eps2 ? extra->cand : nullptr,
                            extra && extra->eps2 ? extra->cand_cap : 0u, extra && extra->eps2 ? extra->row_meta : nullptr,
-                           extra ? extra->meta_base : 0u, extra ? extra->row_qn : nullptr, extra ? extra->row_cq : nullptr);
+                           extra ? extra->meta_base : 0u, extra ? extra->row_qn : nullptr, extra ? extra->row_cq : nullptr,
+                           spec ? extra->spec_rank : 0u, spec ? extra->spec_tau : nullptr, spec ? extra->spec_max : nullptr);
         OI_HIP_CHECK(hipGetLastError());
         return OI_OK;
     }
