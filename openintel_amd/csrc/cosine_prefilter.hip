@@ -54,17 +54,18 @@
 #include "oi_internal.h"
 #include "oi_screen_stage.h"
 #include "oi_lds_dma.h"
+#include "oi_screen_tile.h"
 
-typedef float pf_f32x16 __attribute__((ext_vector_type(16)));
 typedef float pf_f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 pf_bf16x8 __attribute__((ext_vector_type(8)));
 
-#define PF_TILE_ROWS 32
 #define PF_SLOT_K 32                 // floats of K per ring slot row (128 B)
-#define PF_SLOT_BYTES (PF_TILE_ROWS * 128)
+// ring depth of cosine_screen_filter: a compile-time ring index, so the depth divides the tile's slot count
+constexpr int pf_nbuf(int d) { return (d / PF_SLOT_K) % 8 == 0 ? 8 : ((d / PF_SLOT_K) % 6 == 0 ? 6 : d / PF_SLOT_K); }
+// its dynamic LDS: the four rings, then the pool sink's seg_fill and staging ring
+constexpr size_t pf_lds(int d) { return oi_ring_lds(pf_nbuf(d)) + OI_POOL_SINK_LDS; }
 
-__device__ __forceinline__ pf_bf16x8 pf_pack(const pf_f32x4 &a, const pf_f32x4 &b) {
-    pf_bf16x8 r;
+__device__ __forceinline__ oi_bf16x8 pf_pack(const pf_f32x4 &a, const pf_f32x4 &b) {
+    oi_bf16x8 r;
     r[0] = (__bf16)a[0]; r[1] = (__bf16)a[1]; r[2] = (__bf16)a[2]; r[3] = (__bf16)a[3]; // v_cvt_pk_bf16_f32 (RNE)
     r[4] = (__bf16)b[0]; r[5] = (__bf16)b[1]; r[6] = (__bf16)b[2]; r[7] = (__bf16)b[3];
     return r;
@@ -77,65 +78,31 @@ __global__ __launch_bounds__(256, 1) void cosine_screen_filter(
     uint32_t n_queries, uint32_t doc_id_base, uint64_t *pools, uint32_t *seg_cnt, uint32_t seg_cnt_stride,
     const uint32_t *tau_keys, uint64_t pool_stride, uint32_t carry_cap, uint32_t seg_cap, uint32_t *overflow) {
     constexpr int NKC = D / PF_SLOT_K;                    // ring slots per tile
-    constexpr int NBUF = NKC % 8 == 0 ? 8 : (NKC % 6 == 0 ? 6 : NKC);
+    constexpr int NBUF = pf_nbuf(D);
     constexpr int P = NBUF - 1;                           // slots in flight ahead of the one being consumed
-    constexpr int KSTEPS = D / 16;                        // MFMA groups per tile: two per slot
+    constexpr uint32_t ROW_BYTES = D * 4;
     static_assert(D % PF_SLOT_K == 0 && NKC % NBUF == 0 && P >= 1 && P < NKC, "unsupported D");
-    static_assert(NQT * KSTEPS * 4 <= 400, "the query block must fit the register file");
 
-    extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
-    unsigned char *ring = smem;                                                         // [4][NBUF][4 KiB]
-    uint32_t *seg_fill = reinterpret_cast<uint32_t *>(smem + 4 * NBUF * PF_SLOT_BYTES); // [64]
+    extern __shared__ __attribute__((aligned(1024))) unsigned char smem[]; // [4][NBUF][4 KiB] of ring, then the sink's
 
     OI_CLAIM_WHOLE_SIMD(); // (MFMA kernel: nothing else may run on this CU -- oi_device.h)
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t li = lane & 31, lh = lane >> 5;
-    // the wave's staging ring of survivors (keys and their queries), behind seg_fill
-    uint64_t *stage_keys = reinterpret_cast<uint64_t *>(smem + 4 * NBUF * PF_SLOT_BYTES + 256) + w * OI_STAGE;
-    uint32_t *stage_q = reinterpret_cast<uint32_t *>(smem + 4 * NBUF * PF_SLOT_BYTES + 256 + 4 * OI_STAGE * 8) + w * OI_STAGE;
-    uint32_t st_head = 0, st_n = 0; // wave-uniform: first staged entry (mod OI_STAGE), staged entries (< OI_STAGE_FLUSH between tiles)
 
-    // ---- every query over the whole K, in registers for the whole launch: B[k = 16 s + 8 lh + 0..7][n = li]
-    pf_bf16x8 qreg[NQT][KSTEPS];
-#pragma unroll
-    for (int t = 0; t < NQT; ++t)
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s)
-            qreg[t][s] = *reinterpret_cast<const pf_bf16x8 *>(queries + (uint64_t)(32 * t + li) * D + 16 * s + 8 * lh);
-    // Screen thresholds (tau~ - 2 eps) of the queries this lane filters, as FLOATS: for a score s that is not a NaN,
-    // oi_f32_key(s) >= key  <=>  s >= oi_key_f32(key) (the key is strictly monotone on floats after s + 0 has made -0 a +0, and
-    // the comparison does not tell -0 from +0 either); keys at or below key(-inf) pass every such score (-inf), keys above
-    // key(+inf) -- 0xFFFFFFFF: no query in this slot -- map to NaN bit patterns, which no score is >=.  A NaN score fails the
-    // comparison by itself.  One v_cmp per score instead of the key's five instructions.
+    oi_bf16x8 qreg[NQT][D / 16];
+    oi_tile_load_queries<D, NQT>(qreg, queries, li, lh);
     float tauf[NQT];
-#pragma unroll
-    for (int t = 0; t < NQT; ++t) {
-        const uint32_t q = 32u * t + li;
-        const uint32_t k = q < n_queries ? tau_keys[q] : 0xFFFFFFFFu;
-        tauf[t] = k <= 0x007FFFFFu ? -__builtin_inff() : oi_key_f32(k);
-    }
-    if (tid < 32 * NQT) seg_fill[tid] = 0;
-    __syncthreads(); // the only barrier before the end: seg_fill is zero before any wave appends
+    oi_tile_thresholds<NQT>(tauf, tau_keys, n_queries, li);
+    OiPoolSink sink;
+    sink.open<NQT>(smem + oi_ring_lds(NBUF), w, pools, carry_cap, seg_cap, pool_stride, doc_id_base, overflow);
 
-    // ---- tiles of this WAVE: (blockIdx.x * 4 + w), + 4 * gridDim.x, ...
-    const uint64_t n_rows = row_end - row_begin;
-    const uint64_t n_tiles = (n_rows + PF_TILE_ROWS - 1) / PF_TILE_ROWS;
-    const uint64_t first = (uint64_t)blockIdx.x * 4 + w, stride = (uint64_t)gridDim.x * 4;
-    const uint64_t my_nt = first < n_tiles ? (n_tiles - first + stride - 1) / stride : 0;
-    uint64_t *my_seg = pools + carry_cap + (uint64_t)blockIdx.x * seg_cap;
-
-    if (my_nt) {
-        // per-lane source of the 4 DMA pieces of a slot: piece m covers tile rows 8m..8m+7; lane l -> row
-        // 8m + (l>>3), physical 16-B column l&7 holding LOGICAL column (l&7) ^ ((row>>1)&7)
+    const OiWaveTiles wt = oi_wave_tiles(row_begin, row_end, w);
+    if (wt.my_nt) {
         uint32_t voff[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const uint32_t prow = 8 * m + (lane >> 3);
-            voff[m] = prow * (uint32_t)(D * 4) + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
-        }
-        const uint32_t ring_w = oi_lds_addr(ring) + w * (NBUF * PF_SLOT_BYTES);
-        const unsigned char *ring_rd = ring + w * (NBUF * PF_SLOT_BYTES);
+        oi_tile_voff<ROW_BYTES>(voff, lane);
+        const uint32_t ring_w = oi_lds_addr(smem) + w * (NBUF * OI_SLOT_BYTES);
+        const unsigned char *ring_rd = smem + w * (NBUF * OI_SLOT_BYTES);
         // fragment of k-step g of a slot: row li, floats 16 g + 8 lh + 0..7 = logical 16-B columns 4g + 2lh, + 1
         uint32_t frag_off[2][2];
 #pragma unroll
@@ -143,23 +110,16 @@ __global__ __launch_bounds__(256, 1) void cosine_screen_filter(
 #pragma unroll
             for (int h = 0; h < 2; ++h) frag_off[g][h] = li * 128 + (((4 * g + 2 * lh + h) ^ ((li >> 1) & 7)) << 4);
 
-        auto tile_row0 = [&](uint64_t ti) { return row_begin + (first + ti * stride) * (uint64_t)PF_TILE_ROWS; };
-        auto tile_srd = [&](uint64_t ti) { // past this wave's last tile: an EMPTY descriptor (loads return zeros)
-            const uint64_t r0 = tile_row0(ti < my_nt ? ti : 0);
-            return oi_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 4) : 0ull);
-        };
-        oi_u32x4 cur = tile_srd(0), nxt = tile_srd(1);
-        // Every load hipcc knows about (queries, thresholds) is retired HERE, with a wait it models:
-        // otherwise it re-waits for them inside the tile loop and drains the DMA ring.
-        __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only
+        oi_u32x4 cur = wt.srd<ROW_BYTES>(rows, 0), nxt = wt.srd<ROW_BYTES>(rows, 1);
+        oi_tile_retire_visible_loads();
 #pragma unroll
         for (int kc = 0; kc < P; ++kc) // prologue: slots 0..P-1 of the first tile
 #pragma unroll
             for (int m = 0; m < 4; ++m)
-                oi_dma_piece(cur, voff[m], kc * 128, ring_w + (kc % NBUF) * PF_SLOT_BYTES + m * 1024);
+                oi_dma_piece(cur, voff[m], kc * 128, ring_w + (kc % NBUF) * OI_SLOT_BYTES + m * 1024);
 
-        for (uint64_t ti = 0; ti < my_nt; ++ti) {
-            pf_f32x16 acc[NQT];
+        for (uint64_t ti = 0; ti < wt.my_nt; ++ti) {
+            oi_f32x16 acc[NQT];
 #pragma unroll
             for (int t = 0; t < NQT; ++t)
 #pragma unroll
@@ -170,7 +130,7 @@ __global__ __launch_bounds__(256, 1) void cosine_screen_filter(
             // slot kc - 1 has vacated, convert the floats read; at g == 1 the next k-step is (kc + 1, 0),
             // behind the counted wait that retires slot kc + 1 (P - 1 younger slots stay in flight).
             oi_wait_vm<4 * (P - 1)>();
-            pf_bf16x8 a_cur = pf_pack(*reinterpret_cast<const pf_f32x4 *>(ring_rd + frag_off[0][0]),
+            oi_bf16x8 a_cur = pf_pack(*reinterpret_cast<const pf_f32x4 *>(ring_rd + frag_off[0][0]),
                                       *reinterpret_cast<const pf_f32x4 *>(ring_rd + frag_off[0][1]));
             oi_static_for<0, NKC * 2>([&](auto gi_) {
                 constexpr int gi = decltype(gi_)::value;
@@ -178,8 +138,8 @@ __global__ __launch_bounds__(256, 1) void cosine_screen_filter(
                 constexpr int sn = kc + P; // slot refilled during this slot's k-steps
                 pf_f32x4 f0, f1;
                 if constexpr (g == 0) {
-                    f0 = *reinterpret_cast<const pf_f32x4 *>(ring_rd + (kc % NBUF) * PF_SLOT_BYTES + frag_off[1][0]);
-                    f1 = *reinterpret_cast<const pf_f32x4 *>(ring_rd + (kc % NBUF) * PF_SLOT_BYTES + frag_off[1][1]);
+                    f0 = *reinterpret_cast<const pf_f32x4 *>(ring_rd + (kc % NBUF) * OI_SLOT_BYTES + frag_off[1][0]);
+                    f1 = *reinterpret_cast<const pf_f32x4 *>(ring_rd + (kc % NBUF) * OI_SLOT_BYTES + frag_off[1][1]);
                 }
 #pragma unroll
                 for (int t = 0; t < NQT; ++t)
@@ -187,93 +147,27 @@ __global__ __launch_bounds__(256, 1) void cosine_screen_filter(
 #pragma unroll
                 for (int m = 2 * g; m < 2 * g + 2; ++m) {
                     if constexpr (sn < NKC)
-                        oi_dma_piece(cur, voff[m], sn * 128, ring_w + (sn % NBUF) * PF_SLOT_BYTES + m * 1024);
+                        oi_dma_piece(cur, voff[m], sn * 128, ring_w + (sn % NBUF) * OI_SLOT_BYTES + m * 1024);
                     else
-                        oi_dma_piece(nxt, voff[m], (sn - NKC) * 128, ring_w + (sn % NBUF) * PF_SLOT_BYTES + m * 1024);
+                        oi_dma_piece(nxt, voff[m], (sn - NKC) * 128, ring_w + (sn % NBUF) * OI_SLOT_BYTES + m * 1024);
                 }
                 if constexpr (g == 1 && kc + 1 < NKC) {
                     oi_wait_vm<4 * (P - 1)>();
-                    f0 = *reinterpret_cast<const pf_f32x4 *>(ring_rd + ((kc + 1) % NBUF) * PF_SLOT_BYTES + frag_off[0][0]);
-                    f1 = *reinterpret_cast<const pf_f32x4 *>(ring_rd + ((kc + 1) % NBUF) * PF_SLOT_BYTES + frag_off[0][1]);
+                    f0 = *reinterpret_cast<const pf_f32x4 *>(ring_rd + ((kc + 1) % NBUF) * OI_SLOT_BYTES + frag_off[0][0]);
+                    f1 = *reinterpret_cast<const pf_f32x4 *>(ring_rd + ((kc + 1) % NBUF) * OI_SLOT_BYTES + frag_off[0][1]);
                 }
                 if constexpr (gi + 1 < NKC * 2) a_cur = pf_pack(f0, f1);
             });
 
-            // ---- filter + append, straight out of the accumulators: register r of query tile t holds
-            // D[row (r&3) + 8 (r>>2) + 4 lh][query 32 t + li]
-            // Round 4: which of the lane's 16 NQT scores pass is collected in a mask first (one compare each); a tile without
-            // a survivor -- most tiles of the large chunks -- leaves through one ballot, and a lane with survivors takes ONE
-            // LDS atomic per query for all of them.  (Round 3 took an atomic and waited for it per score: 200-350 wave
-            // cycles per survivor, 0.13 ms of the 4.9 ms step at 10M rows -- tools/r04_epilogue_probe.sh.)
-            const uint64_t row0 = tile_row0(ti);
-            uint32_t m = 0;
-#pragma unroll
-            for (int t = 0; t < NQT; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) m |= acc[t][r] >= tauf[t] ? 1u << (16 * t + r) : 0u;
-            if (row_end - row0 < (uint64_t)PF_TILE_ROWS) { // the ragged last tile: rows past the end read as zeros
-                const uint32_t left = (uint32_t)(row_end - row0);
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if ((uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * lh >= left) m &= ~(0x00010001u << r);
-            }
-            if (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull) {
-                const uint32_t cnt = (uint32_t)__builtin_popcount(m);
-                const uint32_t incl = oi_wave_incl_scan(cnt);
-                const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                if (total <= OI_STAGE - OI_STAGE_FLUSH) {
-                    // SPARSE tile (every tile once a threshold stands): the survivors go to the wave's LDS staging ring, and
-                    // 64 of them leave with ONE store instruction.  A store per survivor sat in the same in-order vmcnt queue
-                    // as the DMA pieces: every counted wait then also waited for slots it did not need yet (the stores behind
-                    // them), 0.13 ms of the 4.9 ms step at 10M rows (tools/r04_epilogue_probe.sh).
-                    uint32_t idx = st_head + st_n + incl - cnt;
-#pragma unroll
-                    for (int t = 0; t < NQT; ++t)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            if (m & (1u << (16 * t + r))) {
-                                const uint32_t row = (uint32_t)row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                                stage_keys[idx & (OI_STAGE - 1)] = oi_rank_key(acc[t][r], doc_id_base + row);
-                                stage_q[idx & (OI_STAGE - 1)] = 32u * t + li;
-                                ++idx;
-                            }
-                    st_n += total;
-                    while (st_n >= OI_STAGE_FLUSH) {
-                        OI_STAGE_FLUSH_TO_POOL(OI_STAGE_FLUSH);
-                    }
-                } else {
-                    // DENSE tile (the first chunk, scored without a threshold: every score passes): straight to the pool
-                    uint32_t pos[NQT];
-#pragma unroll
-                    for (int t = 0; t < NQT; ++t) // (both atomics are in flight before the first is waited for; adding 0 is harmless)
-                        pos[t] = atomicAdd(&seg_fill[32u * t + li], (uint32_t)__builtin_popcount((m >> (16 * t)) & 0xFFFFu));
-#pragma unroll
-                    for (int t = 0; t < NQT; ++t) {
-                        uint64_t *dst = my_seg + (uint64_t)(32u * t + li) * pool_stride;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            if (m & (1u << (16 * t + r))) {
-                                const uint32_t row = (uint32_t)row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                                if (pos[t] < seg_cap) dst[pos[t]] = oi_rank_key(acc[t][r], doc_id_base + row);
-                                else *overflow = 1u;
-                                ++pos[t];
-                            }
-                        }
-                    }
-                }
-            }
+            const uint64_t row0 = wt.row0(ti);
+            const uint32_t m = oi_tile_mask_ragged(oi_tile_pass_mask<NQT>(acc, tauf), row_end - row0, lh);
+            sink.append<NQT, false>(m, acc, row0, nullptr, nullptr);
             cur = nxt;
-            nxt = tile_srd(ti + 2);
+            nxt = wt.srd<ROW_BYTES>(rows, ti + 2);
         }
-        if (st_n) {
-            OI_STAGE_FLUSH_TO_POOL(st_n);
-        }
+        sink.flush_rest();
     }
-    __syncthreads(); // every wave's appends are counted
-    if (tid < 32 * NQT && tid < n_queries) {
-        const uint32_t c = seg_fill[tid];
-        seg_cnt[(uint64_t)tid * seg_cnt_stride + blockIdx.x] = c < seg_cap ? c : seg_cap;
-    }
+    sink.close<NQT>(n_queries, seg_cnt, seg_cnt_stride);
 }
 
 // ------------------------------------------------------------------ norms, eps, query staging
@@ -299,7 +193,7 @@ __global__ __launch_bounds__(256) void pf_row_norm_max_kernel(const float *__res
             const float4 a = x[v];
             ss = fmaf(a.x, a.x, ss); ss = fmaf(a.y, a.y, ss); ss = fmaf(a.z, a.z, ss); ss = fmaf(a.w, a.w, ss);
             const pf_f32x4 f = {a.x, a.y, a.z, a.w};
-            const pf_bf16x8 b = pf_pack(f, f);
+            const oi_bf16x8 b = pf_pack(f, f);
             const float e0 = (float)b[0] - a.x, e1 = (float)b[1] - a.y, e2 = (float)b[2] - a.z, e3 = (float)b[3] - a.w;
             se = fmaf(e0, e0, se); se = fmaf(e1, e1, se); se = fmaf(e2, e2, se); se = fmaf(e3, e3, se);
         }
@@ -342,7 +236,7 @@ __global__ __launch_bounds__(256) void pf_row_norm_class_kernel(const float *__r
             const float4 a = x[v];
             ss = fmaf(a.x, a.x, ss); ss = fmaf(a.y, a.y, ss); ss = fmaf(a.z, a.z, ss); ss = fmaf(a.w, a.w, ss);
             const pf_f32x4 f = {a.x, a.y, a.z, a.w};
-            const pf_bf16x8 b = pf_pack(f, f);
+            const oi_bf16x8 b = pf_pack(f, f);
             const float e0 = (float)b[0] - a.x, e1 = (float)b[1] - a.y, e2 = (float)b[2] - a.z, e3 = (float)b[3] - a.w;
             se = fmaf(e0, e0, se); se = fmaf(e1, e1, se); se = fmaf(e2, e2, se); se = fmaf(e3, e3, se);
         }
@@ -390,16 +284,16 @@ __global__ __launch_bounds__(64) void pf_probe_kernel(const float *__restrict__ 
                                                       uint32_t n_queries, float *__restrict__ out) {
     const uint32_t lane = threadIdx.x, li = lane & 31, lh = lane >> 5;
     const uint32_t r0 = blockIdx.x * 32, q0 = blockIdx.y * 32;
-    pf_f32x16 acc;
+    oi_f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     const uint32_t row = r0 + li < n_rows ? r0 + li : n_rows - 1; // (rows past the end are not written)
     const float *x = rows + (row_begin + row) * (uint64_t)dim;
     const uint16_t *qq = queries + (uint64_t)(q0 + li) * dim;     // the staged block is zero padded to 32 rows
     for (uint32_t k = 0; k < dim; k += 16) {
-        const pf_bf16x8 a = pf_pack(*reinterpret_cast<const pf_f32x4 *>(x + k + 8 * lh),
+        const oi_bf16x8 a = pf_pack(*reinterpret_cast<const pf_f32x4 *>(x + k + 8 * lh),
                                     *reinterpret_cast<const pf_f32x4 *>(x + k + 8 * lh + 4));
-        const pf_bf16x8 b = *reinterpret_cast<const pf_bf16x8 *>(qq + k + 8 * lh);
+        const oi_bf16x8 b = *reinterpret_cast<const oi_bf16x8 *>(qq + k + 8 * lh);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
     }
 #pragma unroll
@@ -414,7 +308,7 @@ __global__ __launch_bounds__(64) void pf_probe_kernel(const float *__restrict__ 
 __global__ __launch_bounds__(256) void pf_make_copy_kernel(const float *__restrict__ rows, uint64_t n_vec8, uint4 *__restrict__ out) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec8; i += (uint64_t)gridDim.x * blockDim.x) {
         const pf_f32x4 a = *reinterpret_cast<const pf_f32x4 *>(rows + i * 8), b = *reinterpret_cast<const pf_f32x4 *>(rows + i * 8 + 4);
-        const pf_bf16x8 v = pf_pack(a, b);
+        const oi_bf16x8 v = pf_pack(a, b);
         out[i] = *reinterpret_cast<const uint4 *>(&v);
     }
 }
@@ -616,7 +510,7 @@ bool oi_cosine_screen_supported(uint32_t dim) { return dim == 384 || dim == 768;
 
 // Pool geometry of one chunk: one segment per workgroup; its four waves take 4 tiles per round.
 void oi_cosine_screen_geometry(const oi_ctx *ctx, uint64_t n_rows, uint32_t *n_segs, uint32_t *seg_cap) {
-    const uint64_t n_tiles = (n_rows + PF_TILE_ROWS - 1) / PF_TILE_ROWS;
+    const uint64_t n_tiles = (n_rows + OI_TILE_ROWS - 1) / OI_TILE_ROWS;
     const uint64_t quads = (n_tiles + 3) / 4;
     // The persistent screen takes 7/8 of the CUs, one workgroup each.  It is HBM-bound: 208..224 of 256 CUs stream the corpus as
     // fast as 256 (4.82-4.92 vs 4.97 ms per 10M-row batch), and the CUs left free run the small kernels of whatever else is in
@@ -628,7 +522,7 @@ void oi_cosine_screen_geometry(const oi_ctx *ctx, uint64_t n_rows, uint32_t *n_s
     static const bool small_full = oi_ablation_env("OI_SCREEN_SMALL_FULL") != nullptr; // A/B: a chunk of <= one quad per CU takes every CU
     const uint64_t grid = small_full && quads <= (uint64_t)ctx->num_cus ? (quads ? quads : 1) : (quads < cus ? (quads ? quads : 1) : cus);
     *n_segs = (uint32_t)grid;
-    *seg_cap = (uint32_t)((quads + grid - 1) / grid) * 4 * PF_TILE_ROWS;
+    *seg_cap = (uint32_t)((quads + grid - 1) / grid) * 4 * OI_TILE_ROWS;
 }
 
 int oi_launch_row_norm_classes(oi_ctx *ctx, const float *rows, uint64_t n, uint32_t dim, float X0, float E0, uint32_t *cls,
@@ -668,8 +562,7 @@ int oi_launch_screen_stage(oi_ctx *ctx, const float *d_queries, uint32_t n_queri
 template <int D, int NQT>
 static int launch_screen(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end, const uint16_t *q,
                          uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
-    constexpr int NKC = D / PF_SLOT_K, NBUF = NKC % 8 == 0 ? 8 : (NKC % 6 == 0 ? 6 : NKC);
-    constexpr size_t smem = 4 * NBUF * PF_SLOT_BYTES + 64 * 4 + OI_STAGE_LDS;
+    constexpr size_t smem = pf_lds(D);
     OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(cosine_screen_filter<D, NQT>), (size_t)(smem)));
     hipLaunchKernelGGL((cosine_screen_filter<D, NQT>), dim3(p.n_segs), dim3(256), smem, ctx->stream, rows, row_begin,
                        row_end, q, nq, doc_id_base, p.keys, p.seg_cnt, p.seg_cnt_stride, p.tau_keys, p.stride,

@@ -10,6 +10,8 @@
 // bit (tests/test_gpu_prefilter.py).  Only the bytes differ: 2 d per row and batch instead of 4 d -- the kernel is an HBM
 // stream, so that is the whole point.
 //
+// The kernel is setup, the shared tile step and the shared pool epilogue of oi_screen_tile.h (OiCopyRing, OiPoolSink); what
+// follows says why they are shaped as they are.
 // Kernel shape: cosine_screen_filter's with the conversion gone.  One persistent workgroup on 7/8 of the CUs, 4 waves, no
 // K-split: a wave holds all 64 queries over the whole K as bf16 B operands, owns whole 32-row tiles and streams them through
 // its own LDS ring of 4 KiB slots (32 rows x 64 bf16) with buffer_load ... lds, ordered by counted s_waitcnt vmcnt.  Per 16 k
@@ -30,16 +32,8 @@
 #include "oi_device.h"
 #include "oi_internal.h"
 #include "oi_lds_dma.h"
+#include "oi_screen_tile.h"
 
-typedef float sc_f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 sc_bf16x8 __attribute__((ext_vector_type(8)));
-
-#ifndef OI_TILE_CONTIG
-#define OI_TILE_CONTIG 0
-#endif
-#define SC_TILE_ROWS 32
-#define SC_SLOT_K 64                 // bf16 of K per ring slot row (128 B)
-#define SC_SLOT_BYTES (SC_TILE_ROWS * 128)
 // One ring piece: oi_dma_piece, but for the variant builds that take the DMA out of this kernel.
 __device__ __forceinline__ void sc_issue_piece(const oi_u32x4 &srd, uint32_t voff, uint32_t soff, uint32_t lds_dst) {
 #if defined(SC_AGG_NO_DMA) && SC_AGG_NO_DMA == 1
@@ -53,6 +47,14 @@ __device__ __forceinline__ void sc_issue_piece(const oi_u32x4 &srd, uint32_t vof
     oi_dma_piece(srd, voff, soff, lds_dst);
 #endif
 }
+#ifdef SC_AGG_NO_MFMA // (variant builds: the stream without the matrix instructions; every score 0, results WRONG)
+#define SC_MFMA false
+#else
+#define SC_MFMA true
+#endif
+
+// dynamic LDS: the four rings, then the pool sink's seg_fill and staging ring
+constexpr size_t sc_lds(int nbuf) { return oi_ring_lds(nbuf) + OI_POOL_SINK_LDS; }
 
 template <int D, int NQT, int NBUF, bool FILT>
 __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
@@ -61,204 +63,42 @@ __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
     uint32_t n_queries, uint32_t doc_id_base, uint64_t *pools, uint32_t *seg_cnt, uint32_t seg_cnt_stride,
     const uint32_t *tau_keys, uint64_t pool_stride, uint32_t carry_cap, uint32_t seg_cap, uint32_t *overflow,
     const uint4 *__restrict__ filt, const uint2 *__restrict__ attrs) { // FILT: the doc filter (oi_filter_tile) after the threshold
-    constexpr int NKC = D / SC_SLOT_K;    // ring slots per tile
-    constexpr int P = NBUF - 1;           // slots in flight ahead of the one being consumed
-    constexpr int KSTEPS = D / 16;        // MFMA groups per tile: four per slot
-    constexpr uint32_t RING = NBUF * SC_SLOT_BYTES;
-    static_assert(D % SC_SLOT_K == 0 && P >= 1 && P <= 2 * NKC, "unsupported ring depth for this D");
-    static_assert(NQT * KSTEPS * 4 <= 400, "the query block must fit the register file");
-    static_assert(4 * RING + 256 + OI_STAGE_LDS <= 160 * 1024, "LDS");
+    using Ring = OiCopyRing<D, NBUF, sc_issue_piece>;
+    static_assert(sc_lds(NBUF) <= 160 * 1024, "LDS");
 
-    extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
-    unsigned char *ring = smem;                                          // [4][NBUF][4 KiB]
-    uint32_t *seg_fill = reinterpret_cast<uint32_t *>(smem + 4 * RING);  // [64]
+    extern __shared__ __attribute__((aligned(1024))) unsigned char smem[]; // [4][NBUF][4 KiB] of ring, then the sink's
 
     OI_CLAIM_WHOLE_SIMD(); // (MFMA kernel: nothing else may run on this CU -- oi_device.h)
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t li = lane & 31, lh = lane >> 5;
-    uint64_t *stage_keys = reinterpret_cast<uint64_t *>(smem + 4 * RING + 256) + w * OI_STAGE;
-    uint32_t *stage_q = reinterpret_cast<uint32_t *>(smem + 4 * RING + 256 + 4 * OI_STAGE * 8) + w * OI_STAGE;
-    uint32_t st_head = 0, st_n = 0; // wave-uniform: first staged entry (mod OI_STAGE), staged entries (< OI_STAGE_FLUSH between tiles)
 
-    // ---- every query over the whole K, in registers for the whole launch: B[k = 16 s + 8 lh + 0..7][n = li]
-    sc_bf16x8 qreg[NQT][KSTEPS];
-#pragma unroll
-    for (int t = 0; t < NQT; ++t)
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s)
-            qreg[t][s] = *reinterpret_cast<const sc_bf16x8 *>(queries + (uint64_t)(32 * t + li) * D + 16 * s + 8 * lh);
-    // thresholds (tau~ - 2 eps) as floats: see cosine_screen_filter -- one v_cmp per score; no query in the slot = NaN
-    float tauf[NQT];
-#pragma unroll
-    for (int t = 0; t < NQT; ++t) {
-        const uint32_t q = 32u * t + li;
-        const uint32_t k = q < n_queries ? tau_keys[q] : 0xFFFFFFFFu;
-        tauf[t] = k <= 0x007FFFFFu ? -__builtin_inff() : oi_key_f32(k);
-    }
-    if (tid < 32 * NQT) seg_fill[tid] = 0;
+    oi_bf16x8 qreg[NQT][D / 16];
+    oi_tile_load_queries<D, NQT>(qreg, queries, li, lh);
+    float tauf[NQT]; // thresholds (tau~ - 2 eps) as floats: one v_cmp per score; no query in the slot = NaN
+    oi_tile_thresholds<NQT>(tauf, tau_keys, n_queries, li);
 #ifdef SC_AGG_NO_DMA
-    for (uint32_t i = tid; i < 4 * RING / 4; i += 256) reinterpret_cast<uint32_t *>(ring)[i] = 0u;
+    for (uint32_t i = tid; i < oi_ring_lds(NBUF) / 4; i += 256) reinterpret_cast<uint32_t *>(smem)[i] = 0u;
 #endif
-    __syncthreads(); // the only barrier before the end: seg_fill is zero before any wave appends
+    OiPoolSink sink;
+    sink.open<NQT>(smem + oi_ring_lds(NBUF), w, pools, carry_cap, seg_cap, pool_stride, doc_id_base, overflow);
 
-    // ---- tiles of this WAVE: (blockIdx.x * 4 + w), + 4 * gridDim.x, ...
-    const uint64_t n_rows = row_end - row_begin;
-    const uint64_t n_tiles = (n_rows + SC_TILE_ROWS - 1) / SC_TILE_ROWS;
-#if OI_TILE_CONTIG // A/B: every wave owns a CONTIGUOUS run of tiles (sequential pages) instead of every stride-th tile
-    const uint64_t n_waves_ = (uint64_t)gridDim.x * 4, per_ = (n_tiles + n_waves_ - 1) / n_waves_;
-    const uint64_t first = ((uint64_t)blockIdx.x * 4 + w) * per_, stride = 1;
-    const uint64_t my_nt = first < n_tiles ? (n_tiles - first < per_ ? n_tiles - first : per_) : 0;
-#else
-    const uint64_t first = (uint64_t)blockIdx.x * 4 + w, stride = (uint64_t)gridDim.x * 4;
-    const uint64_t my_nt = first < n_tiles ? (n_tiles - first + stride - 1) / stride : 0;
-#endif
-    uint64_t *my_seg = pools + carry_cap + (uint64_t)blockIdx.x * seg_cap;
-
-    if (my_nt) {
-        // per-lane source of the 4 DMA pieces of a slot: piece m covers tile rows 8m..8m+7; lane l -> row
-        // 8m + (l>>3), physical 16-B column l&7 holding LOGICAL column (l&7) ^ ((row>>1)&7)
-        uint32_t voff[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const uint32_t prow = 8 * m + (lane >> 3);
-            voff[m] = prow * (uint32_t)(D * 2) + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
+    const OiWaveTiles wt = oi_wave_tiles(row_begin, row_end, w);
+    if (wt.my_nt) {
+        Ring ring;
+        ring.begin(wt, rows, smem + w * Ring::BYTES, lane);
+        for (uint64_t ti = 0; ti < wt.my_nt; ++ti) {
+            oi_f32x16 acc[NQT];
+            ring.template tile<NQT, SC_MFMA>(acc, qreg);
+            const uint64_t row0 = wt.row0(ti);
+            const uint32_t m = oi_tile_mask_ragged(oi_tile_pass_mask<NQT>(acc, tauf), row_end - row0, lh);
+            sink.append<NQT, FILT>(m, acc, row0, filt, attrs);
+            ring.next(wt, rows, ti);
         }
-        const uint32_t ring_w = oi_lds_addr(ring) + w * RING;
-        const unsigned char *ring_rd = ring + w * RING;
-        // fragment of MFMA group g of a slot: row li, bf16 16 g + 8 lh + 0..7 = logical 16-B column 2g + lh
-        uint32_t frag_off[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) frag_off[g] = li * 128 + (((2 * g + lh) ^ ((li >> 1) & 7)) << 4);
-
-        auto tile_row0 = [&](uint64_t ti) { return row_begin + (first + ti * stride) * (uint64_t)SC_TILE_ROWS; };
-        auto tile_srd = [&](uint64_t ti) { // past this wave's last tile: an EMPTY descriptor (loads return zeros)
-            const uint64_t r0 = tile_row0(ti < my_nt ? ti : 0);
-            return oi_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 2) : 0ull);
-        };
-        oi_u32x4 s0 = tile_srd(0), s1 = tile_srd(1), s2 = tile_srd(2);
-        // Every load hipcc knows about (queries, thresholds) is retired HERE, with a wait it models:
-        // otherwise it re-waits for them inside the tile loop and drains the DMA ring.
-        __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only
-        oi_static_for<0, P>([&](auto j_) { // prologue: logical slots 0..P-1 (tile j / NKC, slot j % NKC) into ring slots 0..P-1
-            constexpr int j = decltype(j_)::value;
-            constexpr int tj = j / NKC, kj = j % NKC;
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-                sc_issue_piece(tj == 0 ? s0 : (tj == 1 ? s1 : s2), voff[m], kj * 128, ring_w + j * SC_SLOT_BYTES + m * 1024);
-        });
-        // ring offsets (bytes, wave-uniform): the slot being consumed, and the one vacated before it = the refill target
-        uint32_t rd_off = 0, wr_off = (NBUF - 1) * SC_SLOT_BYTES;
-
-        for (uint64_t ti = 0; ti < my_nt; ++ti) {
-            sc_f32x16 acc[NQT];
-#pragma unroll
-            for (int t = 0; t < NQT; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-            // Slot kc of this tile sits at rd_off.  Per MFMA group (kc, g): read the next fragment, NQT MFMAs on the
-            // current one, DMA piece g of logical slot kc + P into the slot vacated last (wr_off); after g == 3 the
-            // counted wait retires slot kc + 1 (P - 1 younger slots stay in flight) and the offsets move on.
-            oi_wait_vm<4 * (P - 1)>();
-            sc_bf16x8 a_cur = *reinterpret_cast<const sc_bf16x8 *>(ring_rd + rd_off + frag_off[0]);
-            oi_static_for<0, NKC * 4>([&](auto gi_) {
-                constexpr int gi = decltype(gi_)::value;
-                constexpr int kc = gi / 4, g = gi % 4;
-                constexpr int sn = kc + P;           // logical slot (relative to this tile) refilled during this slot
-                constexpr int tn = sn / NKC, kn = sn % NKC;
-                sc_bf16x8 a_nxt = a_cur;
-                if constexpr (g < 3) a_nxt = *reinterpret_cast<const sc_bf16x8 *>(ring_rd + rd_off + frag_off[g + 1]);
-#ifndef SC_AGG_NO_MFMA // (variant builds: the stream without the matrix instructions; every score 0, results WRONG)
-#pragma unroll
-                for (int t = 0; t < NQT; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur, qreg[t][gi], acc[t], 0, 0, 0);
-#else
-                asm volatile("" : : "v"(a_cur));
-#endif
-                sc_issue_piece(tn == 0 ? s0 : (tn == 1 ? s1 : s2), voff[g], kn * 128, ring_w + wr_off + g * 1024);
-                if constexpr (g == 3) {
-                    wr_off = rd_off;
-                    rd_off = rd_off + SC_SLOT_BYTES == RING ? 0u : rd_off + SC_SLOT_BYTES;
-                    if constexpr (kc + 1 < NKC) {
-                        oi_wait_vm<4 * (P - 1)>();
-                        a_nxt = *reinterpret_cast<const sc_bf16x8 *>(ring_rd + rd_off + frag_off[0]);
-                    }
-                }
-                a_cur = a_nxt;
-            });
-
-            // ---- filter + append, straight out of the accumulators (cosine_screen_filter's epilogue): register r of
-            // query tile t holds D[row (r&3) + 8 (r>>2) + 4 lh][query 32 t + li]
-            const uint64_t row0 = tile_row0(ti);
-            uint32_t m = 0;
-#pragma unroll
-            for (int t = 0; t < NQT; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) m |= acc[t][r] >= tauf[t] ? 1u << (16 * t + r) : 0u;
-            if (row_end - row0 < (uint64_t)SC_TILE_ROWS) { // the ragged last tile: rows past the end read as zeros
-                const uint32_t left = (uint32_t)(row_end - row0);
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if ((uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * lh >= left) m &= ~(0x00010001u << r);
-            }
-            if (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull) {
-                if constexpr (FILT) m = oi_filter_tile<NQT>(m, filt, attrs, row0, lh, li);
-                const uint32_t cnt = (uint32_t)__builtin_popcount(m);
-                const uint32_t incl = oi_wave_incl_scan(cnt);
-                const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                if (total <= OI_STAGE - OI_STAGE_FLUSH) {
-                    // SPARSE tile (every tile once a threshold stands): staged, 64 leave with one store instruction
-                    uint32_t idx = st_head + st_n + incl - cnt;
-#pragma unroll
-                    for (int t = 0; t < NQT; ++t)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            if (m & (1u << (16 * t + r))) {
-                                const uint32_t row = (uint32_t)row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                                stage_keys[idx & (OI_STAGE - 1)] = oi_rank_key(acc[t][r], doc_id_base + row);
-                                stage_q[idx & (OI_STAGE - 1)] = 32u * t + li;
-                                ++idx;
-                            }
-                    st_n += total;
-                    while (st_n >= OI_STAGE_FLUSH) {
-                        OI_STAGE_FLUSH_TO_POOL(OI_STAGE_FLUSH);
-                    }
-                } else {
-                    // DENSE tile (the first chunk, scored without a threshold: every score passes): straight to the pool
-                    uint32_t pos[NQT];
-#pragma unroll
-                    for (int t = 0; t < NQT; ++t)
-                        pos[t] = atomicAdd(&seg_fill[32u * t + li], (uint32_t)__builtin_popcount((m >> (16 * t)) & 0xFFFFu));
-#pragma unroll
-                    for (int t = 0; t < NQT; ++t) {
-                        uint64_t *dst = my_seg + (uint64_t)(32u * t + li) * pool_stride;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            if (m & (1u << (16 * t + r))) {
-                                const uint32_t row = (uint32_t)row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                                if (pos[t] < seg_cap) dst[pos[t]] = oi_rank_key(acc[t][r], doc_id_base + row);
-                                else *overflow = 1u;
-                                ++pos[t];
-                            }
-                        }
-                    }
-                }
-            }
-            s0 = s1;
-            s1 = s2;
-            s2 = tile_srd(ti + 3);
-        }
-        if (st_n) {
-            OI_STAGE_FLUSH_TO_POOL(st_n);
-        }
-        oi_wait_vm<0>(); // the zero-filling refills issued past the last tile have landed before the LDS goes back
+        sink.flush_rest();
+        ring.end();
     }
-    __syncthreads(); // every wave's appends are counted
-    if (tid < 32 * NQT && tid < n_queries) {
-        const uint32_t c = seg_fill[tid];
-        seg_cnt[(uint64_t)tid * seg_cnt_stride + blockIdx.x] = c < seg_cap ? c : seg_cap;
-    }
+    sink.close<NQT>(n_queries, seg_cnt, seg_cnt_stride);
 }
 
 // ------------------------------------------------------------------ host
@@ -273,7 +113,7 @@ __global__ __launch_bounds__(256, 1) void cosine_copy_screen(
 template <int D, int NQT, int NBUF, bool FILT>
 static int launch_copy_screen_k(oi_ctx *ctx, const uint16_t *rows, uint64_t row_begin, uint64_t row_end, const uint16_t *q,
                                 uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
-    constexpr size_t smem = 4 * NBUF * SC_SLOT_BYTES + 64 * 4 + OI_STAGE_LDS;
+    constexpr size_t smem = sc_lds(NBUF);
     OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(cosine_copy_screen<D, NQT, NBUF, FILT>), (size_t)(smem)));
     hipLaunchKernelGGL((cosine_copy_screen<D, NQT, NBUF, FILT>), dim3(p.n_segs), dim3(256), smem, ctx->stream, rows, row_begin,
                        row_end, q, nq, doc_id_base, p.keys, p.seg_cnt, p.seg_cnt_stride, p.tau_keys, p.stride,

@@ -1,6 +1,7 @@
 // oi_lds_dma.h -- what the streaming kernels share: the LDS-DMA ring primitives (descriptor, one 1-KiB piece, the counted
 // wait, the compile-time loop the ring schedules are written in) and the per-wave staging ring the survivors leave through.
-// Users: cosine_ksplit, cosine_split, cosine_bf16, cosine_prefilter, cosine_screen_copy, cosine_screen_i8 (.hip).
+// Users: cosine_ksplit, cosine_split, cosine_bf16, cosine_screen_i8 (.hip), and oi_screen_tile.h: the tile pipeline that
+// cosine_prefilter, cosine_screen_copy, cosine_volume and cosine_summary (.hip, the last two through oi_volume.h) are written on.
 //
 // THE CONTRACT of an LDS-DMA load (`buffer_load_dwordx4 ... lds`: 64 lanes x 16 B from each lane's own source offset into
 // 1 KiB of LDS at M0 + 16 * lane, no register destination):
@@ -102,7 +103,7 @@ __device__ __forceinline__ void oi_wait_vm() {
 // segment from ONE LDS atomic, one store instruction for all of them.  (A macro: a lambda would take st_head / st_n by
 // reference and hipcc then keeps them in scratch.)  The compiler barriers keep the staging writes of other lanes in front of
 // these reads, and these reads in front of the next tile's writes (LDS operations of a wave execute in order).
-// Reads from the enclosing kernel: lane, st_head, st_n (wave-uniform: first staged entry mod OI_STAGE, staged entries),
+// Reads from the enclosing kernel (or from OiPoolSink, oi_screen_tile.h, whose members carry these names): lane, st_head, st_n (wave-uniform: first staged entry mod OI_STAGE, staged entries),
 // stage_keys, stage_q (this wave's), seg_fill, seg_cap, my_seg, pool_stride, overflow.
 #define OI_STAGE_FLUSH_TO_POOL(NF)                                                                                     \
     do {                                                                                                               \

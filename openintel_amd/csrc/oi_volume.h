@@ -14,6 +14,8 @@
 //            Thr thr_block(Thr, q0)               the threshold argument of the launch that begins at query q0
 //            int finish(ctx, n_cells, out)        cells -> the caller's array, on the ctx stream
 // VoCount (cosine_volume.hip) and SmSum (cosine_summary.hip) are the two there are.
+// The stream kernel's tile pipeline (query block, tile ownership, the bf16 copy ring, the score test) is oi_screen_tile.h's, shared
+// with cosine_copy_screen; its own are the two thresholds and the tallying epilogue with the band staging.
 #pragma once
 
 #include <algorithm>
@@ -22,19 +24,16 @@
 #include "oi_device.h"
 #include "oi_internal.h"
 #include "oi_lds_dma.h"
+#include "oi_screen_tile.h"
 
-typedef float vo_f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 vo_bf16x8 __attribute__((ext_vector_type(8)));
-
-#define VO_TILE_ROWS 32
-#define VO_SLOT_K 64                 // bf16 of K per ring slot row (128 B)
-#define VO_SLOT_BYTES (VO_TILE_ROWS * 128)
 #define VO_BAND_CAP (4u << 20)       // undecided pairs per call: 32 MB, the collapse mask's budget
 #define VO_NBUF 8                    // the copy screen's ring depth (cosine_screen_copy.hip: depth is not what holds the stream)
 // state words of a call (zeroed by it): [0] gate (a query without a bound), [1] band overflow, [2] band fill
 #define VO_GATE 0
 #define VO_OVERFLOW 1
 #define VO_BAND_CNT 2
+// dynamic LDS of vo_stream_kernel: the four rings, then the waves' staged band pairs
+constexpr size_t vo_lds(int nbuf) { return oi_ring_lds(nbuf) + 4 * OI_STAGE * 8; }
 
 // Clause 2 of the definition: the bucket of a stamp.  stamp >= origin makes the 32-bit difference exact, so origin + n * width
 // may exceed 2^32 without a 64-bit division.
@@ -87,7 +86,7 @@ __device__ __forceinline__ float vo_chain4(const float4 x, const float4 y, float
 }
 
 // ------------------------------------------------------------------ route 1: the stream
-// cosine_copy_screen's tile loop (see there for the ring, its counted waits and the operand layout) over ALL rows in one
+// The tile pipeline of oi_screen_tile.h (see there for the ring, its counted waits and the operand layout) over ALL rows in one
 // launch, with the tallying epilogue.  FILT: the queries carry doc filters.  attrs is also set when only buckets are asked for.
 template <int D, int NQT, int NBUF, bool FILT, class Tally>
 __global__ __launch_bounds__(256, 1) void vo_stream_kernel(
@@ -97,32 +96,21 @@ __global__ __launch_bounds__(256, 1) void vo_stream_kernel(
     const uint4 *__restrict__ filt, const uint2 *__restrict__ attrs, uint32_t origin, uint32_t width, uint32_t n_buckets,
     const uint32_t *__restrict__ long_bitmap, const Tally tally, uint64_t *band, uint32_t band_cap, uint32_t *band_cnt,
     uint32_t *overflow) {
-    constexpr int NKC = D / VO_SLOT_K;    // ring slots per tile
-    constexpr int P = NBUF - 1;           // slots in flight ahead of the one being consumed
-    constexpr int KSTEPS = D / 16;        // MFMA groups per tile: four per slot
-    constexpr uint32_t RING = NBUF * VO_SLOT_BYTES;
-    static_assert(D % VO_SLOT_K == 0 && P >= 1 && P <= 2 * NKC, "unsupported ring depth for this D");
-    static_assert(NQT * KSTEPS * 4 <= 400, "the query block must fit the register file");
-    static_assert(4 * RING + 4 * OI_STAGE * 8 <= 160 * 1024, "LDS");
+    using Ring = OiCopyRing<D, NBUF>;
+    static_assert(vo_lds(NBUF) <= 160 * 1024, "LDS");
 
-    extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
-    unsigned char *ring = smem; // [4][NBUF][4 KiB]
+    extern __shared__ __attribute__((aligned(1024))) unsigned char smem[]; // [4][NBUF][4 KiB] of ring, then the staged band pairs
 
     if (state_in[VO_GATE] != 0u) return; // a query of the batch has no bound: route 2 tallies the batch (uniform over the grid)
     OI_CLAIM_WHOLE_SIMD(); // (MFMA kernel: nothing else may run on this CU -- oi_device.h)
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t li = lane & 31, lh = lane >> 5;
-    uint64_t *stage_keys = reinterpret_cast<uint64_t *>(smem + 4 * RING) + w * OI_STAGE; // the wave's staged band pairs
+    uint64_t *stage_keys = reinterpret_cast<uint64_t *>(smem + oi_ring_lds(NBUF)) + w * OI_STAGE; // the wave's staged band pairs
     uint32_t st_head = 0, st_n = 0; // wave-uniform: first staged entry (mod OI_STAGE), staged entries (< OI_STAGE_FLUSH between tiles)
 
-    // ---- every query over the whole K, in registers for the whole launch: B[k = 16 s + 8 lh + 0..7][n = li]
-    vo_bf16x8 qreg[NQT][KSTEPS];
-#pragma unroll
-    for (int t = 0; t < NQT; ++t)
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s)
-            qreg[t][s] = *reinterpret_cast<const vo_bf16x8 *>(queries + (uint64_t)(32 * t + li) * D + 16 * s + 8 * lh);
+    oi_bf16x8 qreg[NQT][D / 16];
+    oi_tile_load_queries<D, NQT>(qreg, queries, li, lh);
     // the two thresholds of the queries this lane tests, from the query's own t_q, rounded OUTWARD (eps_q is half of what the
     // staging kernel stores: it keeps 2 eps for the margin selects); no query in the slot, or a NaN t_q = NaN, which no score is >=
     float lo[NQT], hi[NQT];
@@ -137,88 +125,21 @@ __global__ __launch_bounds__(256, 1) void vo_stream_kernel(
         }
     }
 
-    // ---- tiles of this WAVE: (blockIdx.x * 4 + w), + 4 * gridDim.x, ...
-    const uint64_t n_tiles = (n_rows + VO_TILE_ROWS - 1) / VO_TILE_ROWS;
-    const uint64_t first = (uint64_t)blockIdx.x * 4 + w, stride = (uint64_t)gridDim.x * 4;
-    const uint64_t my_nt = first < n_tiles ? (n_tiles - first + stride - 1) / stride : 0;
-
-    if (my_nt) {
-        uint32_t voff[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const uint32_t prow = 8 * m + (lane >> 3);
-            voff[m] = prow * (uint32_t)(D * 2) + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
-        }
-        const uint32_t ring_w = oi_lds_addr(ring) + w * RING;
-        const unsigned char *ring_rd = ring + w * RING;
-        uint32_t frag_off[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) frag_off[g] = li * 128 + (((2 * g + lh) ^ ((li >> 1) & 7)) << 4);
-
-        auto tile_row0 = [&](uint64_t ti) { return (first + ti * stride) * (uint64_t)VO_TILE_ROWS; };
-        auto tile_srd = [&](uint64_t ti) { // past this wave's last tile: an EMPTY descriptor (loads return zeros)
-            const uint64_t r0 = tile_row0(ti < my_nt ? ti : 0);
-            return oi_make_srd(rows + r0 * D, ti < my_nt ? (n_rows - r0) * (uint64_t)(D * 2) : 0ull);
-        };
-        oi_u32x4 s0 = tile_srd(0), s1 = tile_srd(1), s2 = tile_srd(2);
-        // Every load hipcc knows about (queries, margins) is retired HERE, with a wait it models (oi_lds_dma.h)
-        __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only
-        oi_static_for<0, P>([&](auto j_) { // prologue: logical slots 0..P-1 (tile j / NKC, slot j % NKC) into ring slots 0..P-1
-            constexpr int j = decltype(j_)::value;
-            constexpr int tj = j / NKC, kj = j % NKC;
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-                oi_dma_piece(tj == 0 ? s0 : (tj == 1 ? s1 : s2), voff[m], kj * 128, ring_w + j * VO_SLOT_BYTES + m * 1024);
-        });
-        uint32_t rd_off = 0, wr_off = (NBUF - 1) * VO_SLOT_BYTES;
-
-        for (uint64_t ti = 0; ti < my_nt; ++ti) {
-            vo_f32x16 acc[NQT];
-#pragma unroll
-            for (int t = 0; t < NQT; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-            oi_wait_vm<4 * (P - 1)>();
-            vo_bf16x8 a_cur = *reinterpret_cast<const vo_bf16x8 *>(ring_rd + rd_off + frag_off[0]);
-            oi_static_for<0, NKC * 4>([&](auto gi_) {
-                constexpr int gi = decltype(gi_)::value;
-                constexpr int kc = gi / 4, g = gi % 4;
-                constexpr int sn = kc + P;           // logical slot (relative to this tile) refilled during this slot
-                constexpr int tn = sn / NKC, kn = sn % NKC;
-                vo_bf16x8 a_nxt = a_cur;
-                if constexpr (g < 3) a_nxt = *reinterpret_cast<const vo_bf16x8 *>(ring_rd + rd_off + frag_off[g + 1]);
-#pragma unroll
-                for (int t = 0; t < NQT; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur, qreg[t][gi], acc[t], 0, 0, 0);
-                oi_dma_piece(tn == 0 ? s0 : (tn == 1 ? s1 : s2), voff[g], kn * 128, ring_w + wr_off + g * 1024);
-                if constexpr (g == 3) {
-                    wr_off = rd_off;
-                    rd_off = rd_off + VO_SLOT_BYTES == RING ? 0u : rd_off + VO_SLOT_BYTES;
-                    if constexpr (kc + 1 < NKC) {
-                        oi_wait_vm<4 * (P - 1)>();
-                        a_nxt = *reinterpret_cast<const vo_bf16x8 *>(ring_rd + rd_off + frag_off[0]);
-                    }
-                }
-                a_cur = a_nxt;
-            });
+    const OiWaveTiles wt = oi_wave_tiles(0, n_rows, w);
+    if (wt.my_nt) {
+        Ring ring;
+        ring.begin(wt, rows, smem + w * Ring::BYTES, lane);
+        for (uint64_t ti = 0; ti < wt.my_nt; ++ti) {
+            oi_f32x16 acc[NQT];
+            ring.template tile<NQT>(acc, qreg);
 
             // ---- the tallying epilogue, straight out of the accumulators: register r of query tile t holds
-            // D[row (r&3) + 8 (r>>2) + 4 lh][query 32 t + li].  The test costs what the screen's costs (one compare per score);
+            // D[row oi_tile_row(row0, r, lh)][query 32 t + li].  The test costs what the screen's costs (one compare per score);
             // everything else is behind the ballot.
-            const uint64_t row0 = tile_row0(ti);
-            uint32_t m = 0;
-#pragma unroll
-            for (int t = 0; t < NQT; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) m |= acc[t][r] >= lo[t] ? 1u << (16 * t + r) : 0u;
+            const uint64_t row0 = wt.row0(ti);
+            uint32_t m = oi_tile_pass_mask<NQT>(acc, lo);
             if (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull) {
-                if (n_rows - row0 < (uint64_t)VO_TILE_ROWS) { // the ragged last tile: rows past the end read as zeros
-                    const uint32_t left = (uint32_t)(n_rows - row0);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        if ((uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * lh >= left) m &= ~(0x00010001u << r);
-                }
+                m = oi_tile_mask_ragged(m, n_rows - row0, lh);
                 if constexpr (FILT) m = oi_filter_tile<NQT>(m, filt, attrs, row0, lh, li);
                 // per row with a bit left: its bucket (the stamp is loaded for such rows only) and the long-row bitmap; then
                 // a proven hit is tallied (the row's record loaded at its first one), a band pair keeps its bit
@@ -226,7 +147,7 @@ __global__ __launch_bounds__(256, 1) void vo_stream_kernel(
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     if (m & (0x00010001u << r)) {
-                        const uint32_t row = (uint32_t)row0 + (uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * lh;
+                        const uint32_t row = oi_tile_row((uint32_t)row0, r, lh);
                         uint32_t b = 0;
                         bool ok = true;
                         if (width != 0u) ok = vo_bucket(attrs[row].y, origin, width, n_buckets, &b);
@@ -257,7 +178,7 @@ __global__ __launch_bounds__(256, 1) void vo_stream_kernel(
 #pragma unroll
                             for (int r = 0; r < 16; ++r)
                                 if (mb & (1u << (16 * t + r))) {
-                                    const uint32_t row = (uint32_t)row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                                    const uint32_t row = oi_tile_row((uint32_t)row0, r, lh);
                                     stage_keys[idx & (OI_STAGE - 1)] = ((uint64_t)(q_base + 32u * t + li) << 32) | row;
                                     ++idx;
                                 }
@@ -276,7 +197,7 @@ __global__ __launch_bounds__(256, 1) void vo_stream_kernel(
 #pragma unroll
                             for (int r = 0; r < 16; ++r)
                                 if (mb & (1u << (16 * t + r))) {
-                                    const uint32_t row = (uint32_t)row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                                    const uint32_t row = oi_tile_row((uint32_t)row0, r, lh);
                                     if (pos < band_cap && pos >= base) band[pos] = ((uint64_t)(q_base + 32u * t + li) << 32) | row;
                                     else *overflow = 1u;
                                     ++pos;
@@ -284,14 +205,12 @@ __global__ __launch_bounds__(256, 1) void vo_stream_kernel(
                     }
                 }
             }
-            s0 = s1;
-            s1 = s2;
-            s2 = tile_srd(ti + 3);
+            ring.next(wt, rows, ti);
         }
         if (st_n) {
             VO_STAGE_FLUSH_TO_BAND(st_n);
         }
-        oi_wait_vm<0>(); // the zero-filling refills issued past the last tile have landed before the LDS goes back
+        ring.end();
     }
 }
 
@@ -433,7 +352,7 @@ template <int D, int NQT, bool FILT, class Tally>
 static int vo_launch_stream(oi_ctx *ctx, uint32_t grid, const uint16_t *rows, uint64_t n, const uint16_t *q, uint32_t nq, uint32_t q_base,
                             typename Tally::Thr thr, const float *eps2, uint32_t *state, const uint4 *filt, const uint2 *attrs,
                             const oi_volume_spec &sp, const uint32_t *long_bitmap, const Tally &tally, uint64_t *band) {
-    constexpr size_t smem = 4 * VO_NBUF * VO_SLOT_BYTES + 4 * OI_STAGE * 8;
+    constexpr size_t smem = vo_lds(VO_NBUF);
     OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(vo_stream_kernel<D, NQT, VO_NBUF, FILT, Tally>), smem));
     hipLaunchKernelGGL((vo_stream_kernel<D, NQT, VO_NBUF, FILT, Tally>), dim3(grid), dim3(256), smem, ctx->stream, rows, n, q, nq, q_base, thr,
                        eps2, state, filt, attrs, sp.stamp_origin, sp.bucket_width, sp.n_buckets, long_bitmap, tally, band,
