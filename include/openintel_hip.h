@@ -656,6 +656,74 @@ int oi_similar_summary(oi_index *idx, const float *query_vecs, uint32_t n_querie
                        const oi_doc_filter *filters, int location, oi_social_counters *out /* [n_queries][n_buckets] */);
 
 /* ------------------------------------------------------------------------- */
+/* Similarity leaderboard: posts like a query, summed and ranked per group key */
+/* ------------------------------------------------------------------------- */
+/*
+ * oi_similar_volume and oi_similar_summary break their result down along the time axis (the documents' stamp).  This call
+ * breaks it down along the other per-document attribute, the GROUP (oi_index_set_doc_attrs: "a ticker id and source bits"):
+ * "which tickers are the posts like this query about, and what do those posts feel?" -- one social_summary record per query
+ * and key, all of them (dense) or the best `top` ranked on the device.  One stream of the screening copy decides every
+ * (query, document) pair, whatever the number of keys.  Builder-defined like the whole retrieval path; its host counterpart
+ * in the reference is the ranking of run_compare (src/mcp/tools.rs:227-349), which analyses a list of tickers one by one.
+ *
+ * The key.  key(d) = (group[d] & key_mask) >> ctz(key_mask).  key_mask is non-zero and one contiguous run of bits.  A document
+ * whose key is >= n_keys belongs to no cell, like a stamp outside every bucket.
+ *
+ * What a cell is.  Cell (q, key) holds the social_summary raw sums over the local documents d of the handle for which all of
+ * these hold -- word for word the clauses of oi_similar_summary, with "bucket" replaced by "key":
+ *   1. d passes filters[q].  filters == NULL means every document passes.  A time window is expressed here, through the
+ *      filter's stamp_lo / stamp_hi.
+ *   2. key(d) == key.
+ *   3. sim(q, d) >= t_q, where t_q = thresholds[q], or spec->threshold when thresholds == NULL.  sim is oi_similar_volume's
+ *      sim.  A NaN thresholds[q] counts nothing for that query, in both locations (no score is >= NaN).
+ * The sums are oi_similar_summary's: total, by_source[2], bullish, bearish, neutral and spec_count are exact integers, and
+ * polarity_sum = (double)(sum of pol_q30) * 2^-30, the sum taken in 64-bit integers.  The result is therefore deterministic and
+ * independent of the route, the order of the atomics, the cosine mode, the copy policy and the batch composition; summed over
+ * the keys it equals oi_similar_summary's one-bucket record for the same arguments when every document has a key.
+ *
+ * Dense output (top == 0).  records_out[q][key] for key < n_keys; keys_out, counts_out and qualified_out are not written and
+ * may be NULL.  This is what a sharded host adds across its ranks.
+ *
+ * Ranked output (top >= 1).  The rank value v of a cell is its record's total, spec_count, bullish or bearish, chosen by
+ * rank_by.  The listed keys of a query are those with total >= max(min_total, 1), ordered by (v descending, key ascending) and
+ * cut at top -- the library's usual 64-bit rank key, v << 32 | ~key.  keys_out[q][r] and records_out[q][r] have row stride top;
+ * counts_out[q] is the number listed; qualified_out[q] (may be NULL) is the number of keys that qualified before the cut.
+ * Entries past counts_out[q] are key 0xFFFFFFFF and an all-zero record.
+ *
+ * Rules.  Those of oi_similar_summary: spec is always a host pointer; location says where the query vectors, the thresholds,
+ * the filters and all four outputs live; OI_DEVICE is asynchronous on the ctx stream; embeddings only (no forward index, no
+ * finalize); it works on a view; n_queries == 0 is OI_OK; n_queries <= 4096; not captured by graph replay.  An index without
+ * signals, or without doc attributes (the key axis always needs them), -> OI_ERR_STATE.  n_queries * n_keys >
+ * OI_MAX_GROUP_CELLS, a bad key_mask, n_keys, top or rank_by, a null required buffer -> OI_ERR_INVALID_ARG with the number in
+ * the message; every argument check precedes the first device call.  Workspace per searching context: 64 B per cell, 8 B
+ * more per cell for ranked output, and the volume's 32 MB band buffer on the screen route (oi_workspace_bytes counts all).
+ * Profile tags: "groups" (the stream), "groups_band" (the rescoring of the undecided pairs), "groups_exact" (the exact
+ * route, and the runs of the fallback inside a screened call that really summed the batch), "groups_rank" (the rank keys and
+ * the ranking of ranked output).
+ *
+ * NOT covered: oi_search_sharded* and oi_pipeline_*.  Records of shards add, so a sharded host asks every rank for dense
+ * output, adds the records and ranks the sums; ranked lists of shards cannot be merged exactly (a key outside every shard's
+ * list may lead the sum).
+ */
+#define OI_MAX_GROUP_KEYS  65536u
+#define OI_MAX_GROUP_CELLS (1u << 20)     /* n_queries * n_keys; 64 MB of cells */
+enum { OI_GROUP_RANK_TOTAL = 0, OI_GROUP_RANK_SPEC = 1, OI_GROUP_RANK_BULLISH = 2, OI_GROUP_RANK_BEARISH = 3 };
+typedef struct oi_groups_spec {
+    float    threshold;   /* used when thresholds == NULL (NaN then: OI_ERR_INVALID_ARG; +-inf allowed) */
+    uint32_t key_mask;    /* non-zero, one contiguous run of bits */
+    uint32_t n_keys;      /* 1 .. min(2^popcount(key_mask), OI_MAX_GROUP_KEYS) */
+    uint32_t top;         /* 0: dense output;  1 .. OI_MAX_DEPTH: ranked output */
+    uint32_t rank_by;     /* OI_GROUP_RANK_* */
+    uint32_t min_total;   /* ranked output lists a key only when its total >= max(min_total, 1) */
+} oi_groups_spec;
+int oi_similar_groups(oi_index *idx, const float *query_vecs, uint32_t n_queries, const oi_groups_spec *spec,
+                      const float *thresholds /* [n_queries] where `location` says, or NULL */,
+                      const oi_doc_filter *filters, int location,
+                      oi_social_counters *records_out /* [n_queries][n_keys], or [n_queries][top] */,
+                      uint32_t *keys_out /* [n_queries][top] */, uint32_t *counts_out /* [n_queries] */,
+                      uint32_t *qualified_out /* [n_queries], may be NULL */);
+
+/* ------------------------------------------------------------------------- */
 /* Text to term ids: the tokeniser and the hashed vocabulary                   */
 /* ------------------------------------------------------------------------- */
 /*
@@ -766,7 +834,8 @@ int oi_screen_probe(oi_index *idx, const float *query_vecs, uint32_t n_queries, 
 
 /* Timing hooks for bench.py: when enabled, HIP events are recorded on the ctx stream
  * around every kernel launch, grouped by tag ("cosine", "bm25", "select", "rrf",
- * "lexicon", "social_summary", "text_count", "text_emit", "volume", "volume_band", "volume_exact",
+ * "lexicon", "social_summary", "text_count", "text_emit", "groups", "groups_band", "groups_exact", "groups_rank",
+ * "volume", "volume_band", "volume_exact",
  * "summary", "summary_band", "summary_exact").  oi_profile_read returns the summed duration (ms) of
  * the launches with that tag and their count since the last reset.  enable: 0 off, 1 every
  * tagged launch, 2 only the "cosine" launches (two event packets per launch cost a few us of

@@ -8,6 +8,7 @@
  * point (post_analyzer.rs:7-11 / lexicon.rs:106-120's sentences), sums a pooled batch per ticker, and runs one hybrid query of a 1000-post index
  * (BASELINE configs[0]'s shape: 384-d, top-10). */
 #include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -23,6 +24,11 @@ int main(void) {
     oi_ctx *ctx = NULL;
     int rc;
     if (oi_abi_version() != OI_ABI_VERSION) return fail("oi_abi_version", oi_abi_version());
+    /* oi_groups_spec as the Python and Rust bindings lay it out: six 4-byte fields, no padding */
+    if (sizeof(oi_groups_spec) != 24 || offsetof(oi_groups_spec, threshold) != 0 || offsetof(oi_groups_spec, key_mask) != 4 ||
+        offsetof(oi_groups_spec, n_keys) != 8 || offsetof(oi_groups_spec, top) != 12 || offsetof(oi_groups_spec, rank_by) != 16 ||
+        offsetof(oi_groups_spec, min_total) != 20 || sizeof(oi_social_counters) != 64)
+        return fail("oi_groups_spec layout", (int)sizeof(oi_groups_spec));
     rc = oi_create(0, &ctx);
     if (rc == OI_ERR_NO_DEVICE) {
         if (ctx != NULL || oi_last_error()[0] == '\0') return fail("no-device contract", rc);

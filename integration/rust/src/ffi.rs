@@ -68,6 +68,25 @@ pub struct OiSummarySpec {
 }
 pub const OI_MAX_SUMMARY_CELLS: u32 = 1 << 18;
 
+/// `oi_groups_spec`: the key of a document is (group & key_mask) >> ctz(key_mask); top == 0 asks for dense records, top >= 1 for
+/// the best `top` keys by `rank_by` among those with total >= max(min_total, 1).
+#[repr(C)]
+#[derive(Debug, Clone, Copy, PartialEq)]
+pub struct OiGroupsSpec {
+    pub threshold: f32,
+    pub key_mask: u32,
+    pub n_keys: u32,
+    pub top: u32,
+    pub rank_by: u32,
+    pub min_total: u32,
+}
+pub const OI_MAX_GROUP_KEYS: u32 = 65536;
+pub const OI_MAX_GROUP_CELLS: u32 = 1 << 20;
+pub const OI_GROUP_RANK_TOTAL: u32 = 0;
+pub const OI_GROUP_RANK_SPEC: u32 = 1;
+pub const OI_GROUP_RANK_BULLISH: u32 = 2;
+pub const OI_GROUP_RANK_BEARISH: u32 = 3;
+
 pub const OI_OK: c_int = 0;
 pub const OI_ERR_ANALYZER_MISMATCH: c_int = -3;
 pub const OI_ERR_OVERFLOW: c_int = -8;
@@ -222,6 +241,13 @@ extern "C" {
     pub fn oi_similar_summary(idx: *mut OiIndex, query_vecs: *const f32, n_queries: u32, spec: *const OiSummarySpec,
                               thresholds: *const f32, filters: *const OiDocFilter, location: c_int,
                               out: *mut OiSocialCounters) -> c_int;
+
+    // similarity leaderboard: records per (query, key) -- dense [n_queries][n_keys] (top == 0; the other outputs may be null), or
+    // the best `top` keys ranked: records and keys [n_queries][top], counts and (may be null) qualified [n_queries]
+    pub fn oi_similar_groups(idx: *mut OiIndex, query_vecs: *const f32, n_queries: u32, spec: *const OiGroupsSpec,
+                             thresholds: *const f32, filters: *const OiDocFilter, location: c_int,
+                             records_out: *mut OiSocialCounters, keys_out: *mut u32, counts_out: *mut u32,
+                             qualified_out: *mut u32) -> c_int;
 
     pub fn oi_pipeline_create(idx: *mut OiIndex, comm: *mut OiComm, lanes: u32, max_queries: u32, max_query_terms: u32,
                               depth: u32, k: u32, out: *mut *mut OiPipeline) -> c_int;

@@ -356,6 +356,40 @@ impl HipIndex {
         })?;
         Ok(out.chunks(nb.max(1)).map(|c| c.to_vec()).collect())
     }
+    /// Which group keys (tickers) the posts like each query are about, and what those posts feel (`oi_similar_groups`): the
+    /// social_summary sums per key = (group & key_mask) >> ctz(key_mask), under `similar_summary`'s clauses.  spec.top == 0: per
+    /// query `n_keys` records, keys implied (entry i is (i, record i)).  spec.top >= 1: per query the listed (key, record) pairs,
+    /// best first by spec.rank_by, ties by key; the second value is the number of keys that qualified before the cut.
+    pub fn similar_groups(&self, query_vecs: &[f32], spec: ffi::OiGroupsSpec, thresholds: Option<&[f32]>,
+                          filters: Option<&[ffi::OiDocFilter]>)
+                          -> Result<Vec<(Vec<(u32, ffi::OiSocialCounters)>, u32)>, HipError> {
+        assert_eq!(query_vecs.len() % self.dim, 0);
+        let b = query_vecs.len() / self.dim;
+        if let Some(f) = filters {
+            assert_eq!(f.len(), b);
+        }
+        if let Some(t) = thresholds {
+            assert_eq!(t.len(), b);
+        }
+        let ranked = spec.top > 0;
+        let per_q = (if ranked { spec.top } else { spec.n_keys }) as usize;
+        let mut records = vec![ffi::OiSocialCounters::default(); b * per_q];
+        let (mut keys, mut counts, mut qualified) = (vec![0u32; if ranked { b * per_q } else { 0 }], vec![0u32; b], vec![0u32; b]);
+        check(unsafe {
+            ffi::oi_similar_groups(self.idx, query_vecs.as_ptr(), b as u32, &spec, thresholds.map_or(std::ptr::null(), |t| t.as_ptr()),
+                                   filters.map_or(std::ptr::null(), |f| f.as_ptr()), ffi::OI_HOST, records.as_mut_ptr(),
+                                   if ranked { keys.as_mut_ptr() } else { std::ptr::null_mut() },
+                                   if ranked { counts.as_mut_ptr() } else { std::ptr::null_mut() },
+                                   if ranked { qualified.as_mut_ptr() } else { std::ptr::null_mut() })
+        })?;
+        Ok((0..b)
+            .map(|q| {
+                let m = if ranked { counts[q] as usize } else { per_q };
+                let list = (0..m).map(|i| (if ranked { keys[q * per_q + i] } else { i as u32 }, records[q * per_q + i])).collect();
+                (list, if ranked { qualified[q] } else { per_q as u32 })
+            })
+            .collect())
+    }
     /// Hybrid BM25 + cosine + RRF: one ranked list (<= k) per query, in query order.
     pub fn search(&self, query_vecs: &[f32], query_terms: &[Vec<u32>], k: usize, depth: usize) -> Result<Vec<Vec<RankedPost>>, HipError> {
         let b = query_terms.len();

@@ -14,12 +14,12 @@ from .domain import (Alignment, AnalyzerMismatch, Confidence, DomainError, Engin
                      PostSignal, PostText, SocialPost, SourceFailure, SourceKind, Ticker)
 from .engine import SpeculationEngine
 from .sharded import ShardedAnalyzer, ShardedPipeline, ShardedRetriever, make_hip_sharded, make_hip_sharded_analyzer, shard_bounds
-from .retriever import (CollapsedResult, HybridIndex, NativeComm, NativePipeline, PostRetriever, SearchResult, fuse_packed, merge_lists, pack_query_terms,
+from .retriever import (CollapsedResult, GroupRanking, HybridIndex, NativeComm, NativePipeline, PostRetriever, SearchResult, fuse_packed, merge_lists, pack_query_terms,
                         packed_words, rrf_fuse, text_terms, unpack_lists)
 
 __all__ = [
     "HipContext", "HipLexiconAnalyzer", "PostAnalyzer", "pack_posts", "SpeculationEngine", "HybridIndex",
-    "PostRetriever", "SearchResult", "CollapsedResult", "merge_lists", "rrf_fuse", "pack_query_terms", "fuse_packed", "packed_words",
+    "PostRetriever", "SearchResult", "CollapsedResult", "GroupRanking", "merge_lists", "rrf_fuse", "pack_query_terms", "fuse_packed", "packed_words",
     "unpack_lists", "text_terms", "HeadlineScanner", "company_name_forms", "Alignment",
     "AnalyzerMismatch", "Confidence", "DomainError", "EngineConfig", "MarketSnapshot", "PostSignal", "PostText",
     "SocialPost", "SourceFailure", "SourceKind", "Ticker", "ShardedAnalyzer", "ShardedPipeline", "ShardedRetriever", "make_hip_sharded",

@@ -18,6 +18,9 @@ OI_MAX_DEPTH = 1024
 OI_MAX_DIM = 1024
 OI_MAX_VOLUME_BUCKETS = 1024
 OI_MAX_SUMMARY_CELLS = 1 << 18
+OI_MAX_GROUP_KEYS = 65536
+OI_MAX_GROUP_CELLS = 1 << 20
+OI_GROUP_RANK_TOTAL, OI_GROUP_RANK_SPEC, OI_GROUP_RANK_BULLISH, OI_GROUP_RANK_BEARISH = 0, 1, 2, 3
 OI_BM25_BLOCK_DOCS = 32768
 OI_N_CATALYST_KEYWORDS = 16
 OI_TEXT_TOKEN_HASH_BYTES = 64
@@ -84,6 +87,19 @@ class SummarySpec(C.Structure):
     ]
 
 
+class GroupsSpec(C.Structure):
+    """oi_groups_spec: the key of a document is (group & key_mask) >> ctz(key_mask); top == 0 asks for dense records, top >= 1
+    for the best `top` keys by rank_by among those with total >= max(min_total, 1)."""
+    _fields_ = [
+        ("threshold", C.c_float),
+        ("key_mask", C.c_uint32),
+        ("n_keys", C.c_uint32),
+        ("top", C.c_uint32),
+        ("rank_by", C.c_uint32),
+        ("min_total", C.c_uint32),
+    ]
+
+
 _P = C.c_void_p
 _U32, _U64, _I = C.c_uint32, C.c_uint64, C.c_int
 
@@ -145,6 +161,7 @@ SIGNATURES = {
     "oi_similar_volume": (_I, [_P, _P, _U32, _P, _P, _I, _P]),
     "oi_index_set_signals": (_I, [_P, _P, _P, _P, C.c_double, _I]),
     "oi_similar_summary": (_I, [_P, _P, _U32, _P, _P, _P, _I, _P]),
+    "oi_similar_groups": (_I, [_P, _P, _U32, _P, _P, _P, _I, _P, _P, _P, _P]),
     "oi_text_terms": (_I, [_P, _P, _P, _U64, _U64, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_query_terms": (_I, [_P, _P, _P, _U32, _U32, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_index_set_text": (_I, [_P, _P, _P, _U64, _I]),

@@ -9,6 +9,7 @@ Host mirror of the reference's batch tools (paths relative to the openintel repo
     ScanArgs / ScanEntry / ScanOutput / run_scan   src/mcp/tools.rs:163-225
     RankBy / CompareArgs / RankedEntry / CompareError / CompareOutput
     rank_metric / sort_ranked / run_compare        src/mcp/tools.rs:227-352
+    rank_group_records / compare_index             src/mcp/tools.rs:323-349 over the index's per-ticker sums (oi_similar_groups)
     SentimentSummary / sentiment_for (per dip row) src/domain/dip.rs:428-431, src/application/dip.rs:175-194
 
 The reference runs `application::analyze` once per ticker (`join_all`, tools.rs:206-220) and never pools posts of
@@ -35,7 +36,7 @@ from typing import List, Optional, Sequence
 from .analyzer import PostAnalyzer, counters_record
 from .application import (DISCLAIMER, AnalysisRequest, MarketDataSource, SocialDataSource, _debug_name, _json_f64,
                           _pretty, _Raw, gather, report_to_wire)
-from .domain import Alignment, AnalyzerMismatch, DomainError, EngineConfig, SourceKind, SpeculationReport
+from .domain import Alignment, AnalyzerMismatch, DomainError, EngineConfig, SourceKind, SpeculationReport, Ticker
 from .engine import SpeculationEngine
 
 
@@ -290,6 +291,55 @@ def run_compare(args: CompareArgs, social_sources: Sequence[SocialDataSource], m
             ranked.append(RankedEntry(ticker=t, rank_metric=rank_metric(res, args.rank_by), report=res))
     sort_ranked(ranked, args.rank_by)
     return CompareOutput(rank_by=args.rank_by, ranked=ranked, errors=errors)
+
+
+# ----------------------------------------------------------------------------- compare over the index (oi_similar_groups)
+def rank_group_records(keys, records, count: int, tickers, rank_by: RankBy, market_by_ticker=None,
+                       now: Optional[_dt.datetime] = None, cfg: EngineConfig = EngineConfig()) -> CompareOutput:
+    """tools.rs:323-349 over the ranked output of one query of `HybridIndex.similar_groups`: the first `count` entries of
+    `keys` / `records` (analyzer.COUNTERS_DTYPE) are the tickers' raw social_summary sums, already reduced on the device where
+    the reference analyses each ticker's posts.  `tickers` names the keys (a sequence indexed by key, or a mapping); each
+    listed key gives `SpeculationEngine.aggregate_counters(ticker, record, market, now, cfg)` with `market_by_ticker`'s
+    snapshot for that name (none: a social-only report), then a RankedEntry with `rank_metric`, in the device's order before
+    the stable `sort_ranked`.  A key without a name, an invalid name or a mismatching market snapshot goes to `errors`."""
+    if now is None:
+        now = _dt.datetime.now(_dt.timezone.utc)
+    markets = market_by_ticker or {}
+    ranked: List[RankedEntry] = []
+    errors: List[CompareError] = []
+    for r in range(int(count)):
+        key = int(keys[r])
+        if isinstance(tickers, dict):
+            name = tickers.get(key)
+        else:
+            name = tickers[key] if 0 <= key < len(tickers) else None
+        if name is None:
+            errors.append(CompareError(ticker="#%d" % key, error="group key %d has no ticker name" % key))
+            continue
+        try:
+            report = SpeculationEngine.aggregate_counters(Ticker.parse(name), counters_record(records[r]), markets.get(name), now, cfg)
+        except DomainError as e:
+            errors.append(CompareError(ticker=name, error=str(e)))
+            continue
+        ranked.append(RankedEntry(ticker=name, rank_metric=rank_metric(report, rank_by), report=report))
+    sort_ranked(ranked, rank_by)
+    return CompareOutput(rank_by=rank_by, ranked=ranked, errors=errors)
+
+
+def compare_index(index, query_vec, threshold: float, tickers, key_mask: int, rank_by: RankBy = RankBy.CROWDING, top: int = 100,
+                  min_total: Optional[int] = None, filters=None, n_keys: Optional[int] = None, market_by_ticker=None,
+                  now: Optional[_dt.datetime] = None, cfg: EngineConfig = EngineConfig()) -> CompareOutput:
+    """compare_tickers answered from the index: "which tickers are the posts like this query about, and what do they feel?"
+    ONE ranked `similar_groups` call by total for the single query `query_vec` (the `top` most-mentioned tickers with at least
+    `min_total` posts, default `cfg.min_sample`), then `rank_group_records`.  n_keys defaults to the number of names (a
+    mapping: its largest key + 1).  The index's signals must have been set with `cfg.bull_bear_threshold`."""
+    import numpy as np
+    if n_keys is None:
+        n_keys = (max(tickers) + 1) if isinstance(tickers, dict) else len(tickers)
+    q = np.ascontiguousarray(np.asarray(query_vec, dtype=np.float32).reshape(1, -1))
+    res = index.similar_groups(q, float(threshold), int(key_mask), int(n_keys), top=int(top), rank_by="total",
+                               min_total=int(cfg.min_sample if min_total is None else min_total), filters=filters)
+    return rank_group_records(res.keys[0], res.records[0], int(res.counts[0]), tickers, rank_by, market_by_ticker, now, cfg)
 
 
 # ----------------------------------------------------------------------------- wire format (#[derive(Serialize)])

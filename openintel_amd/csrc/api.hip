@@ -112,8 +112,8 @@ extern "C" int oi_profile_reset(oi_ctx *ctx, int enable) {
     for (auto &kv : ctx->prof)
         for (auto &s : kv.second) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     ctx->prof.clear();
-    for (const char *runs : {"volume_runs", "summary_runs"}) {
-        // the fallback-run counters of oi_similar_volume / oi_similar_summary ("volume_exact", "summary_exact") start over with the spans
+    for (const char *runs : {"volume_runs", "summary_runs", "groups_runs"}) {
+        // the fallback-run counters of oi_similar_volume / _summary / _groups ("volume_exact", "summary_exact", "groups_exact") start over with the spans
         auto vr = ctx->ws.find(runs);
         if (vr != ctx->ws.end() && vr->second.p) (void)hipMemsetAsync(vr->second.p, 0, 16, ctx->stream);
     }
@@ -153,8 +153,8 @@ extern "C" int oi_profile_read(oi_ctx *ctx, const char *kernel_tag, double *tota
         if (launches_out) *launches_out = 0;
         return OI_OK;
     }
-    if (strcmp(kernel_tag, "volume_state") == 0 || strcmp(kernel_tag, "summary_state") == 0) {
-        // diagnostics of the last oi_similar_volume / oi_similar_summary: undecided pairs its stream sent to the band (may exceed
+    if (strcmp(kernel_tag, "volume_state") == 0 || strcmp(kernel_tag, "summary_state") == 0 || strcmp(kernel_tag, "groups_state") == 0) {
+        // diagnostics of the last oi_similar_volume / oi_similar_summary / oi_similar_groups: undecided pairs its stream sent to the band (may exceed
         // the 4 Mi the buffer holds); bit 0 = a query had no bound, bit 1 = band overflow
         uint32_t w[4] = {0, 0, 0, 0};
         auto vs = ctx->ws.find(kernel_tag);
@@ -169,15 +169,16 @@ extern "C" int oi_profile_read(oi_ctx *ctx, const char *kernel_tag, double *tota
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) { total += ms; ++n; }
         }
-    const bool vol_exact = strcmp(kernel_tag, "volume_exact") == 0;
-    if (vol_exact || strcmp(kernel_tag, "summary_exact") == 0) {
-        // the gated fallback inside screened oi_similar_volume / oi_similar_summary calls ("volume_fallback", "summary_fallback":
-        // launched every time, exits at once unless the call needs it) counts here only for the runs that really counted a batch
-        // (cosine_volume.hip, cosine_summary.hip)
+    const char *family = strcmp(kernel_tag, "volume_exact") == 0 ? "volume" : strcmp(kernel_tag, "summary_exact") == 0 ? "summary"
+                       : strcmp(kernel_tag, "groups_exact") == 0 ? "groups" : nullptr;
+    if (family) {
+        // the gated fallback inside screened oi_similar_volume / _summary / _groups calls ("volume_fallback", "summary_fallback",
+        // "groups_fallback": launched every time, exits at once unless the call needs it) counts here only for the runs that really
+        // counted a batch (cosine_volume.hip, cosine_summary.hip, cosine_groups.hip)
         uint32_t runs = 0;
-        auto vr = ctx->ws.find(vol_exact ? "volume_runs" : "summary_runs");
+        auto vr = ctx->ws.find(std::string(family) + "_runs");
         if (vr != ctx->ws.end() && vr->second.p) OI_HIP_CHECK(hipMemcpy(&runs, vr->second.p, 4, hipMemcpyDeviceToHost));
-        auto fb = ctx->prof.find(vol_exact ? "volume_fallback" : "summary_fallback");
+        auto fb = ctx->prof.find(std::string(family) + "_fallback");
         if (runs && fb != ctx->prof.end()) {
             for (auto &s : fb->second) {
                 float ms = 0.f;
@@ -1646,6 +1647,68 @@ extern "C" int oi_similar_summary(oi_index *idx, const float *qv, uint32_t B, co
                                        thresholds ? reinterpret_cast<const float *>(d + vb + fb) : nullptr,
                                        filters ? reinterpret_cast<const uint4 *>(d + vb) : nullptr, d_out));
     OI_HIP_CHECK(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipStreamSynchronize(st));
+    return OI_OK;
+}
+
+// ---------------------------------------------------------------- similarity leaderboard (cosine_groups.hip)
+// The checks of oi_similar_summary in its order (the spec first: it can be judged without a handle), before the first HIP call.
+// Never captured.
+extern "C" int oi_similar_groups(oi_index *idx, const float *qv, uint32_t B, const oi_groups_spec *spec, const float *thresholds,
+                                 const oi_doc_filter *filters, int location, oi_social_counters *records_out, uint32_t *keys_out,
+                                 uint32_t *counts_out, uint32_t *qualified_out) {
+    OI_REQUIRE(spec, "similar_groups: null spec");
+    OI_REQUIRE(thresholds || spec->threshold == spec->threshold, "similar_groups: threshold is NaN (and no thresholds array)");
+    const uint32_t mask = spec->key_mask, run = mask ? mask >> __builtin_ctz(mask) : 0u;
+    OI_REQUIRE(mask != 0 && (run & (run + 1u)) == 0u, "similar_groups: key_mask=0x%x is not one contiguous run of bits", mask);
+    const uint64_t key_space = std::min<uint64_t>(1ull << __builtin_popcount(mask), OI_MAX_GROUP_KEYS);
+    OI_REQUIRE(spec->n_keys >= 1 && spec->n_keys <= key_space, "similar_groups: n_keys=%u outside [1,%llu] (key_mask=0x%x)", spec->n_keys,
+               (unsigned long long)key_space, mask);
+    OI_REQUIRE(spec->top <= OI_MAX_DEPTH, "similar_groups: top=%u outside [0,%u]", spec->top, OI_MAX_DEPTH);
+    OI_REQUIRE(spec->rank_by <= OI_GROUP_RANK_BEARISH, "similar_groups: rank_by=%u is not an OI_GROUP_RANK_* value", spec->rank_by);
+    OI_REQUIRE(B <= 4096, "similar_groups: n_queries=%u outside [0,4096]", B);
+    OI_REQUIRE((uint64_t)B * spec->n_keys <= OI_MAX_GROUP_CELLS, "similar_groups: n_queries * n_keys = %llu cells, more than %u",
+               (unsigned long long)B * spec->n_keys, OI_MAX_GROUP_CELLS);
+    OI_REQUIRE(B == 0 || (qv && records_out), "similar_groups: null buffer");
+    OI_REQUIRE(B == 0 || spec->top == 0 || (keys_out && counts_out), "similar_groups: null buffer (keys_out / counts_out with top=%u)", spec->top);
+    if (!idx) { oi_set_error("similar_groups: null index"); return OI_ERR_INVALID_ARG; }
+    if (!idx->rows && !idx->rows_bf16) { oi_set_error("similar_groups: the index has no embeddings (oi_index_set_embeddings)"); return OI_ERR_STATE; }
+    oi_ctx *ctx = idx->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!idx->signals.p) { oi_set_error("similar_groups: the index has no signals (oi_index_set_signals)"); return OI_ERR_STATE; }
+    if (!idx->doc_attrs.p) {
+        oi_set_error("similar_groups: the key axis needs the index's doc attributes (oi_index_set_doc_attrs)");
+        return OI_ERR_STATE;
+    }
+    if (B == 0) return OI_OK;
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    if (location == OI_DEVICE)
+        return oi_launch_similar_groups(idx, qv, B, *spec, thresholds, reinterpret_cast<const uint4 *>(filters), records_out, keys_out,
+                                        counts_out, qualified_out);
+    hipStream_t st = ctx->stream;
+    const size_t per_q = spec->top ? spec->top : spec->n_keys; // records (and, ranked, keys) per query
+    const size_t vb = (sizeof(float) * (size_t)B * idx->dim + 15) & ~(size_t)15, fb = filters ? sizeof(oi_doc_filter) * (size_t)B : 0;
+    const size_t tb = thresholds ? (sizeof(float) * (size_t)B + 15) & ~(size_t)15 : 0;
+    const size_t rb = sizeof(oi_social_counters) * (size_t)B * per_q;
+    const size_t kb = spec->top ? sizeof(uint32_t) * (size_t)B * per_q : 0, cb = spec->top ? sizeof(uint32_t) * (size_t)B : 0;
+    DevBuf &w = ctx->buf("groups_io"); // [vectors | filters | thresholds | records | keys | counts | qualified]
+    OI_CHECK(w.ensure(vb + fb + tb + rb + kb + 2 * cb + 64));
+    uint8_t *d = w.as<uint8_t>();
+    OI_HIP_CHECK(hipMemcpyAsync(d, qv, sizeof(float) * (size_t)B * idx->dim, hipMemcpyHostToDevice, st));
+    if (filters) OI_HIP_CHECK(hipMemcpyAsync(d + vb, filters, fb, hipMemcpyHostToDevice, st));
+    if (thresholds) OI_HIP_CHECK(hipMemcpyAsync(d + vb + fb, thresholds, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, st));
+    oi_social_counters *d_rec = reinterpret_cast<oi_social_counters *>(d + vb + fb + tb);
+    uint32_t *d_keys = reinterpret_cast<uint32_t *>(d + vb + fb + tb + rb), *d_counts = d_keys + (size_t)B * per_q, *d_qual = d_counts + B;
+    OI_CHECK(oi_launch_similar_groups(idx, reinterpret_cast<const float *>(d), B, *spec,
+                                      thresholds ? reinterpret_cast<const float *>(d + vb + fb) : nullptr,
+                                      filters ? reinterpret_cast<const uint4 *>(d + vb) : nullptr, d_rec, spec->top ? d_keys : nullptr,
+                                      spec->top ? d_counts : nullptr, spec->top ? d_qual : nullptr));
+    OI_HIP_CHECK(hipMemcpyAsync(records_out, d_rec, rb, hipMemcpyDeviceToHost, st));
+    if (spec->top) {
+        OI_HIP_CHECK(hipMemcpyAsync(keys_out, d_keys, kb, hipMemcpyDeviceToHost, st));
+        OI_HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, cb, hipMemcpyDeviceToHost, st));
+        if (qualified_out) OI_HIP_CHECK(hipMemcpyAsync(qualified_out, d_qual, cb, hipMemcpyDeviceToHost, st));
+    }
     OI_HIP_CHECK(hipStreamSynchronize(st));
     return OI_OK;
 }

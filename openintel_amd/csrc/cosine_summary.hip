@@ -10,22 +10,9 @@
 // pol_q30 (words 12, 13), then two words of padding.  A hit costs ONE u32 atomic, and one 64-bit atomic more only when the
 // post's polarity is not zero (most posts hit no lexicon word).  Every sum is an integer sum, so the result does not depend
 // on the order of the atomics or on the route that found a hit; summary_finish_kernel folds a cell into oi_social_counters.
+// The cell itself (sm_add; sm_fold for the other finish) is oi_summary_cell.h's, shared with cosine_groups.hip.
+#include "oi_summary_cell.h"
 #include "oi_volume.h"
-
-#define SM_CELL_WORDS 16
-#define SM_CELL_SUM 12   // word offset of the i64 sum inside a cell (8-byte aligned: cells are 64 B)
-// classes of a record, as social_summary_kernel tests them (speculation_engine.rs:87-95)
-#define SM_BULLISH 0u
-#define SM_BEARISH 1u
-#define SM_NEUTRAL 2u
-
-// One hit: the record sg = {pol_q30 bits, flag combination < 12} of the row goes into cell `cell`.
-__device__ __forceinline__ void sm_add(uint32_t *cells, uint64_t cell, const uint2 sg) {
-    uint32_t *c = cells + cell * SM_CELL_WORDS;
-    atomicAdd(c + sg.y, 1u);
-    if (sg.x != 0u)
-        atomicAdd(reinterpret_cast<unsigned long long *>(c + SM_CELL_SUM), (unsigned long long)(long long)(int32_t)sg.x);
-}
 
 // ------------------------------------------------------------------ the signal records
 // Polarity::new (polarity.rs:8-14: NaN -> 0, clamp to [-1, 1]), then the reference's comparisons on that f64 value; v * 2^30
@@ -43,7 +30,8 @@ __global__ __launch_bounds__(256) void summary_pack_signals_kernel(const double 
 }
 
 // A cell's 12 counts folded into the caller's record; polarity_sum = (double)(sum of pol_q30) * 2^-30, one rounding at most
-// (the conversion: the scaling by a power of two is exact).
+// (the conversion: the scaling by a power of two is exact).  (sm_fold's statements, kept here as they were: through the
+// helper hipcc allocates this kernel's registers differently, and the kernels the existing calls launch do not move.)
 __global__ __launch_bounds__(256) void summary_finish_kernel(const uint32_t *__restrict__ cells, uint64_t n_cells,
                                                              oi_social_counters *__restrict__ out) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_cells; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -83,6 +71,7 @@ struct SmSum {
     __device__ __forceinline__ void add(uint64_t cell, const Rec sg) const { sm_add(cells, cell, sg); }
 
     static constexpr uint32_t CELL_WORDS = SM_CELL_WORDS;
+    static constexpr bool KEY_AXIS = false;
     static constexpr VoNames NAMES = {"summary_state", "summary_runs", "summary_q_rounded", "summary_q_bf16",
                                       "summary", "summary_band", "summary_exact", "summary_fallback"};
     static const float *thr_block(const float *thr_q, uint32_t q0) { return thr_q ? thr_q + q0 : nullptr; }

@@ -340,6 +340,12 @@ int oi_launch_pack_signals(oi_ctx *ctx, const double *d_pol, const uint8_t *d_sp
                            uint2 *d_out);
 int oi_launch_similar_summary(oi_index *idx, const float *d_q, uint32_t n_queries, const oi_summary_spec &spec, const float *d_thresholds,
                               const uint4 *d_filt, oi_social_counters *d_out);
+// cosine_groups.hip: the similarity leaderboard -- device queries / thresholds / filters in; dense (spec.top == 0):
+// device records [n_queries][n_keys] out; ranked: records and keys [n_queries][top], counts and (may be null) qualified
+// [n_queries] out.  Asynchronous on the ctx stream; d_thresholds and d_filt may be null
+int oi_launch_similar_groups(oi_index *idx, const float *d_q, uint32_t n_queries, const oi_groups_spec &spec, const float *d_thresholds,
+                             const uint4 *d_filt, oi_social_counters *d_records, uint32_t *d_keys, uint32_t *d_counts,
+                             uint32_t *d_qualified);
 // cosine.hip
 // Sets pool.n_segs / pool.seg_cap for this chunk (the following select must use the same view).
 int oi_launch_cosine_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end,

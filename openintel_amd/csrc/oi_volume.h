@@ -11,9 +11,12 @@
 //            Rec, Rec load(row)                   what a row adds; the stream loads it at the row's first proven hit
 //            void add(cell, Rec)                  one hit
 //   host     CELL_WORDS, NAMES                    words per cell; the workspace names and profile tags
+//            KEY_AXIS                             false: clause 2 is the time bucket of the row's stamp (vo_bucket).  true: it is the
+//                                                 KEY of the row's group (vo_key), and the kernels' three u32 arguments
+//                                                 origin / width / n_buckets carry key_mask / its shift / n_keys
 //            Thr thr_block(Thr, q0)               the threshold argument of the launch that begins at query q0
 //            int finish(ctx, n_cells, out)        cells -> the caller's array, on the ctx stream
-// VoCount (cosine_volume.hip) and SmSum (cosine_summary.hip) are the two there are.
+// VoCount (cosine_volume.hip), SmSum (cosine_summary.hip) and GrSum (cosine_groups.hip, the key axis) are the three there are.
 // The stream kernel's tile pipeline (query block, tile ownership, the bf16 copy ring, the score test) is oi_screen_tile.h's, shared
 // with cosine_copy_screen; its own are the two thresholds and the tallying epilogue with the band staging.
 #pragma once
@@ -43,6 +46,19 @@ __device__ __forceinline__ bool vo_bucket(uint32_t stamp, uint32_t origin, uint3
     const uint32_t k = (stamp - origin) / width;
     *b = k;
     return k < n_buckets;
+}
+
+// Clause 2 on the key axis (oi_similar_groups): key = (group & mask) >> shift; a key >= n_keys belongs to no cell.
+__device__ __forceinline__ bool vo_key(uint32_t group, uint32_t mask, uint32_t shift, uint32_t n_keys, uint32_t *b) {
+    const uint32_t k = (group & mask) >> shift;
+    *b = k;
+    return k < n_keys;
+}
+// Clause 2 of a tally, for a row whose attributes are at hand.
+template <class Tally>
+__device__ __forceinline__ bool vo_cell(const uint2 at, uint32_t origin, uint32_t width, uint32_t n_buckets, uint32_t *b) {
+    if constexpr (Tally::KEY_AXIS) return vo_key(at.x, origin, width, n_buckets, b);
+    else return vo_bucket(at.y, origin, width, n_buckets, b);
 }
 
 // The first NF staged band pairs of the wave leave for the band buffer: ONE atomic claims their room, one store instruction
@@ -150,7 +166,8 @@ __global__ __launch_bounds__(256, 1) void vo_stream_kernel(
                         const uint32_t row = oi_tile_row((uint32_t)row0, r, lh);
                         uint32_t b = 0;
                         bool ok = true;
-                        if (width != 0u) ok = vo_bucket(attrs[row].y, origin, width, n_buckets, &b);
+                        if constexpr (Tally::KEY_AXIS) ok = vo_key(attrs[row].x, origin, width, n_buckets, &b);
+                        else if (width != 0u) ok = vo_bucket(attrs[row].y, origin, width, n_buckets, &b);
                         if (long_bitmap && ((long_bitmap[row >> 5] >> (row & 31)) & 1u)) ok = false; // (the bound does not hold: band kernel)
                         if (ok) {
                             bool have = false;
@@ -267,7 +284,7 @@ __global__ __launch_bounds__(256) void vo_band_kernel(const float *__restrict__ 
                 if (attrs) {
                     const uint2 at = attrs[row[u]];
                     if (filt) ok = oi_doc_passes(filt[q[u]], at);
-                    ok = ok && vo_bucket(at.y, origin, width, n_buckets, &b);
+                    ok = ok && vo_cell<Tally>(at, origin, width, n_buckets, &b);
                 }
                 if (ok) tally.add((uint64_t)q[u] * n_buckets + b, tally.load(row[u]));
             }
@@ -301,7 +318,7 @@ __global__ __launch_bounds__(256) void vo_exact_kernel(const void *__restrict__ 
         uint32_t b = 0;
         if (attrs) {
             at = attrs[r];
-            if (!vo_bucket(at.y, origin, width, n_buckets, &b)) continue; // (wave-uniform)
+            if (!vo_cell<Tally>(at, origin, width, n_buckets, &b)) continue; // (wave-uniform)
         }
         const typename Tally::Rec rec = tally.load(r);
         for (uint32_t q0 = 0; q0 < n_queries; q0 += 4) {
@@ -378,7 +395,7 @@ static int vo_launch_exact(oi_ctx *ctx, const void *rows, uint64_t n, uint32_t d
     return OI_OK;
 }
 
-// One call of the family.  Device queries / filters (and, in thr, possibly thresholds) in, the tally's finished cells out;
+// One call of the family.  (On the key axis sp carries {threshold, key_mask, shift, n_keys}.)  Device queries / filters (and, in thr, possibly thresholds) in, the tally's finished cells out;
 // asynchronous on the ctx stream.  The argument and state checks are the entry point's (api.hip).  tally comes with everything
 // but its cells.
 template <class Tally, class Out>
@@ -391,7 +408,7 @@ static int vo_launch_similar(oi_index *idx, const float *d_q, uint32_t B, const 
     const uint64_t n = idx->n_docs;
     const uint32_t dim = idx->dim;
     const uint64_t n_cells = (uint64_t)B * sp.n_buckets, words = n_cells * Tally::CELL_WORDS;
-    const uint2 *attrs = (d_filt || sp.bucket_width) ? idx->doc_attrs.as<uint2>() : nullptr;
+    const uint2 *attrs = (Tally::KEY_AXIS || d_filt || sp.bucket_width) ? idx->doc_attrs.as<uint2>() : nullptr; // (the key axis always reads the group)
     // state (16 B, see VO_GATE ..) and the cells behind it, zeroed per call; the fallback-run counter lives on
     DevBuf &sb = ctx->buf(N.state), &rb = ctx->buf(N.runs);
     OI_CHECK(sb.ensure(64 + words * 4));

@@ -45,6 +45,19 @@ class CollapsedResult(SearchResult):
     dup_counts: object = None   # [B, k] u32: entries of the input list each kept entry stands for, itself included
 
 
+@dataclass
+class GroupRanking:
+    """Ranked output of HybridIndex.similar_groups (oi_similar_groups with top >= 1); row stride `top`."""
+    keys: object        # [B, top] u32 (a torch tensor holds the same bits as int32): 0xFFFFFFFF past counts[q]
+    records: object     # [B, top] analyzer.COUNTERS_DTYPE (torch: int64 [B, top, 8]): all zero past counts[q]
+    counts: object      # [B] u32: keys listed
+    qualified: object   # [B] u32: keys with total >= max(min_total, 1), before the cut at `top`
+
+
+GROUP_RANKS = {"total": _lib.OI_GROUP_RANK_TOTAL, "spec": _lib.OI_GROUP_RANK_SPEC, "bullish": _lib.OI_GROUP_RANK_BULLISH,
+               "bearish": _lib.OI_GROUP_RANK_BEARISH}
+
+
 class PostRetriever(abc.ABC):
     """New port: rank stored posts for a batch of (embedding, term-id) queries."""
 
@@ -522,6 +535,58 @@ class HybridIndex(PostRetriever):
         _lib.check(self.lib.oi_similar_summary(self.handle, _lib.ptr(query_vecs), B, C.byref(spec), _lib.ptr(thr), _lib.ptr(f),
                                                _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(out)))
         return out
+
+    # ---------------------------------------------------------------- similarity leaderboard
+    def similar_groups(self, query_vecs, threshold, key_mask: int, n_keys: int, top: int = 0, rank_by="total", min_total: int = 0,
+                       filters=None):
+        """oi_similar_groups: the social_summary sums of the documents like each query per KEY of their group attribute,
+        key = (group & key_mask) >> ctz(key_mask) (a ticker id, say) -- similar_summary's clauses with the key in the bucket's
+        place (filters carry a time window), same thresholds (a float, or one per query; a NaN entry counts nothing), same
+        deterministic integer sums.  top == 0: [B, n_keys] records (analyzer.COUNTERS_DTYPE), what shards add.  top >= 1: a
+        GroupRanking of the best `top` keys per query by rank_by ("total", "spec", "bullish", "bearish", or an
+        OI_GROUP_RANK_* value; ties by key ascending) among the keys with total >= max(min_total, 1): keys [B, top] uint32
+        (0xFFFFFFFF past the count), records [B, top], counts [B], qualified [B] (keys that qualified before the cut).  Host
+        array in, numpy out; torch CUDA tensor in, tensors out (records as int64 [B, ., 8] holding the records' bits;
+        asynchronous on the ctx stream)."""
+        from .analyzer import COUNTERS_DTYPE
+        dev = _is_dev(query_vecs)
+        if dev:
+            assert query_vecs.is_contiguous() and query_vecs.element_size() == 4
+        else:
+            query_vecs = _np(query_vecs, np.float32)
+        B = int(query_vecs.shape[0])
+        assert B == 0 or int(query_vecs.shape[1]) == self.dim
+        by = GROUP_RANKS[rank_by] if isinstance(rank_by, str) else int(rank_by)
+        top = int(top)
+        thr = None
+        if not _is_dev(threshold) and np.ndim(threshold) == 0:
+            spec = _lib.GroupsSpec(float(threshold), int(key_mask), int(n_keys), top, by, int(min_total))
+        else:
+            spec = _lib.GroupsSpec(0.0, int(key_mask), int(n_keys), top, by, int(min_total))
+            if dev:
+                import torch
+                if not _is_dev(threshold):
+                    threshold = torch.from_numpy(_np(threshold, np.float32)).to("cuda:%d" % self.ctx.device)
+                assert threshold.is_contiguous() and threshold.numel() == B and threshold.element_size() == 4
+                self._thr_keep = thr = threshold  # (an asynchronous call reads it later)
+            else:
+                thr = _np(threshold.cpu().numpy() if _is_dev(threshold) else threshold, np.float32)
+                assert thr.size == B
+        per_q = max(top if top else int(n_keys), 0)
+        if dev:
+            import torch
+            records = torch.zeros((B, per_q, 8), dtype=torch.int64, device="cuda:%d" % self.ctx.device)
+        else:
+            records = np.zeros((B, per_q), dtype=COUNTERS_DTYPE)
+        keys = counts = qualified = None
+        if top:
+            keys, counts, qualified = (self._alloc(dev, (B, per_q), np.uint32), self._alloc(dev, (B,), np.uint32),
+                                       self._alloc(dev, (B,), np.uint32))
+        f = None if filters is None else self._filters(filters, dev, B)
+        _lib.check(self.lib.oi_similar_groups(self.handle, _lib.ptr(query_vecs), B, C.byref(spec), _lib.ptr(thr), _lib.ptr(f),
+                                              _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(records), _lib.ptr(keys),
+                                              _lib.ptr(counts), _lib.ptr(qualified)))
+        return GroupRanking(keys, records, counts, qualified) if top else records
 
     # ---------------------------------------------------------------- the sharded query with RCCL inside the library
     def finalize_sharded(self, comm: "NativeComm") -> None:
