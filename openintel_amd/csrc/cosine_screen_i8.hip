@@ -412,9 +412,16 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
         };
         // keep (q, r) when s~ + e_r |q^| + c_q >= T.  Single v_mul_f32 / v_fma_f32: left to itself hipcc pairs the two query
         // tiles' products into v_pk_*_f32 ... op_sel between the MFMAs, the form DESIGN section 7 found losing products there.
+        // A lane that keeps a pair also keeps the pair's s~ and e_r (two selects on the compare's own condition): a tile in
+        // which no lane kept more than one pair is appended from these, without reading S or the metadata again.  Only a lane
+        // with exactly one bit in the tile's unmasked m reads them, and that bit's test wrote them: they are never cleared.
+        float cap_sc = 0.f, cap_er = 0.f;
         auto test_row = [&](int t, int r, const i8s_f32x2 md) -> uint32_t {
             const float sc = oi_mul_unpacked((float)S[16 * t + r], oi_mul_unpacked(md[0], qa[t]));
-            return sc >= oi_fma_unpacked(-md[1], qn[t], tc[t]) ? 1u << (16 * t + r) : 0u;
+            const bool pass = sc >= oi_fma_unpacked(-md[1], qn[t], tc[t]);
+            cap_sc = pass ? sc : cap_sc;
+            cap_er = pass ? md[1] : cap_er;
+            return pass ? 1u << (16 * t + r) : 0u;
         };
 
         for (uint64_t ti = 0;; ++ti) {
@@ -472,7 +479,7 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
                             for (int u = 0; u < RPK; ++u)
 #pragma unroll
                                 for (int tt = 0; tt < NQT; ++tt) m |= test_row(tt, RPK * (gi - T0) + u, md_cur[u]);
-                            asm volatile("" : "+v"(m)); // (the slice stays in its k-step)
+                            asm volatile("" : "+v"(m), "+v"(cap_sc), "+v"(cap_er)); // (the slice stays in its k-step)
                         }
                         __builtin_amdgcn_sched_barrier(0);
                     }
@@ -504,61 +511,86 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
             // ---- append tile ti - 1's survivors; the key is the lower bound s~ - e_r |q^| - c_q
             const uint64_t row0 = tile_row0(ti ? ti - 1 : 0);
             if (ti == 0) m = 0u; // "tile -1"
+            const uint32_t m_tested = m; // every pair whose test wrote cap_sc / cap_er, before the masks below drop some
             if (row_end - row0 < (uint64_t)I8S_TILE_ROWS) { // the ragged last tile: rows past the end read as zeros
                 const uint32_t left = (uint32_t)(row_end - row0);
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
                     if ((uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * lh >= left) m &= ~(0x00010001u << r);
             }
-#if defined(I8S_NO_DMA) || defined(I8S_NO_MFMA)
+#if defined(I8S_NO_DMA) || defined(I8S_NO_MFMA) || defined(I8S_NO_APPEND)
             // (ablation builds: every score is 0 and every pair would pass, where the product passes < 1 % of them: nothing
-            // survives here, and the test above still runs -- the compiler cannot tell)
+            // survives here, and the test above still runs -- the compiler cannot tell.  I8S_NO_APPEND alone: the product's
+            // kernel with every survivor dropped, i.e. what the two append paths below cost together; results WRONG)
             if (seg_cap != 0xFFFFFFFFu) m = 0u;
 #endif
             if (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull) {
                 if constexpr (FILT) m = oi_filter_tile<NQT>(m, filt, attrs, row0, lh, li);
-                const uint32_t cnt = (uint32_t)__builtin_popcount(m);
-                const uint32_t incl = oi_wave_incl_scan(cnt);
-                const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                // Only the (t, r) some lane kept are visited: `any` is wave-uniform, so S is indexed by a scalar.  Ascending
-                // (t, r) per lane, as the staging order and the pool contents have always been.
-                const uint32_t any = oi_wave_or(m);
-                auto lower_key = [&](int t, uint32_t r) -> uint64_t { // (survivors only: the metadata read again)
-                    const uint32_t rit = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const i8s_f32x2 md = *reinterpret_cast<const i8s_f32x2 *>(mt + rit * 8);
-                    const float sc = (float)S[16 * t + r] * (md[0] * qa[t]);
-                    return oi_rank_key(sc - fmaf(md[1], qn[t], cq[t]), doc_id_base + ((uint32_t)row0 + rit));
-                };
-                if (total <= OI_STAGE - OI_STAGE_FLUSH) {
-                    uint32_t idx = st_head + st_n + incl - cnt;
-#pragma unroll
-                    for (int t = 0; t < NQT; ++t)
-                        for (uint32_t wd = (any >> (16 * t)) & 0xFFFFu; wd; wd &= wd - 1) {
-                            const uint32_t r = (uint32_t)__builtin_ctz(wd);
-                            if (m & (1u << (16 * t + r))) {
-                                stage_keys[idx & (OI_STAGE - 1)] = lower_key(t, r);
-                                stage_q[idx & (OI_STAGE - 1)] = 32u * t + li;
-                                ++idx;
-                            }
-                        }
-                    st_n += total;
+                // ---- No lane tested more than one pair in (three tiles of four with a survivor, under a prediction): every
+                // survivor is appended from what its test kept.  The position is the count of lanes with a pair below this one
+                // (the ascending-lane order of the path below, where a lane's own pairs follow each other), the key the
+                // arithmetic of lower_key on the same s~ and e_r.  At most 64 pairs: they are always staged.
+                static_assert(64u <= OI_STAGE - OI_STAGE_FLUSH, "a tile of one pair per lane must fit the staging ring");
+                if (__builtin_amdgcn_ballot_w64((m_tested & (m_tested - 1u)) != 0u) == 0ull) {
+                    const uint64_t has = __builtin_amdgcn_ballot_w64(m != 0u);
+                    if (m != 0u) {
+                        const uint32_t bit = (uint32_t)__builtin_ctz(m), r = bit & 15u;
+                        const bool t1 = NQT > 1 && bit >= 16u;
+                        const uint32_t rit = (r & 3) + 8 * (r >> 2) + 4 * lh;
+                        const float low = cap_sc - fmaf(cap_er, t1 ? qn[NQT - 1] : qn[0], t1 ? cq[NQT - 1] : cq[0]);
+                        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(has >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)has, 0u));
+                        const uint32_t idx = (st_head + st_n + below) & (OI_STAGE - 1);
+                        stage_keys[idx] = oi_rank_key(low, doc_id_base + ((uint32_t)row0 + rit));
+                        stage_q[idx] = (t1 ? 32u : 0u) + li;
+                    }
+                    st_n += (uint32_t)__builtin_popcountll(has);
                     while (st_n >= OI_STAGE_FLUSH) {
                         OI_STAGE_FLUSH_TO_POOL(OI_STAGE_FLUSH);
                     }
                 } else {
-                    uint32_t pos[NQT];
+                    const uint32_t cnt = (uint32_t)__builtin_popcount(m);
+                    const uint32_t incl = oi_wave_incl_scan(cnt);
+                    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+                    // Only the (t, r) some lane kept are visited: `any` is wave-uniform, so S is indexed by a scalar.  Ascending
+                    // (t, r) per lane, as the staging order and the pool contents have always been.
+                    const uint32_t any = oi_wave_or(m);
+                    auto lower_key = [&](int t, uint32_t r) -> uint64_t { // (survivors only: the metadata read again)
+                        const uint32_t rit = (r & 3) + 8 * (r >> 2) + 4 * lh;
+                        const i8s_f32x2 md = *reinterpret_cast<const i8s_f32x2 *>(mt + rit * 8);
+                        const float sc = (float)S[16 * t + r] * (md[0] * qa[t]);
+                        return oi_rank_key(sc - fmaf(md[1], qn[t], cq[t]), doc_id_base + ((uint32_t)row0 + rit));
+                    };
+                    if (total <= OI_STAGE - OI_STAGE_FLUSH) {
+                        uint32_t idx = st_head + st_n + incl - cnt;
 #pragma unroll
-                    for (int t = 0; t < NQT; ++t)
-                        pos[t] = atomicAdd(&seg_fill[32u * t + li], (uint32_t)__builtin_popcount((m >> (16 * t)) & 0xFFFFu));
+                        for (int t = 0; t < NQT; ++t)
+                            for (uint32_t wd = (any >> (16 * t)) & 0xFFFFu; wd; wd &= wd - 1) {
+                                const uint32_t r = (uint32_t)__builtin_ctz(wd);
+                                if (m & (1u << (16 * t + r))) {
+                                    stage_keys[idx & (OI_STAGE - 1)] = lower_key(t, r);
+                                    stage_q[idx & (OI_STAGE - 1)] = 32u * t + li;
+                                    ++idx;
+                                }
+                            }
+                        st_n += total;
+                        while (st_n >= OI_STAGE_FLUSH) {
+                            OI_STAGE_FLUSH_TO_POOL(OI_STAGE_FLUSH);
+                        }
+                    } else {
+                        uint32_t pos[NQT];
 #pragma unroll
-                    for (int t = 0; t < NQT; ++t) {
-                        uint64_t *dst = my_seg + (uint64_t)(32u * t + li) * pool_stride;
-                        for (uint32_t wd = (any >> (16 * t)) & 0xFFFFu; wd; wd &= wd - 1) {
-                            const uint32_t r = (uint32_t)__builtin_ctz(wd);
-                            if (m & (1u << (16 * t + r))) {
-                                if (pos[t] < seg_cap) dst[pos[t]] = lower_key(t, r);
-                                else *overflow = 1u;
-                                ++pos[t];
+                        for (int t = 0; t < NQT; ++t)
+                            pos[t] = atomicAdd(&seg_fill[32u * t + li], (uint32_t)__builtin_popcount((m >> (16 * t)) & 0xFFFFu));
+#pragma unroll
+                        for (int t = 0; t < NQT; ++t) {
+                            uint64_t *dst = my_seg + (uint64_t)(32u * t + li) * pool_stride;
+                            for (uint32_t wd = (any >> (16 * t)) & 0xFFFFu; wd; wd &= wd - 1) {
+                                const uint32_t r = (uint32_t)__builtin_ctz(wd);
+                                if (m & (1u << (16 * t + r))) {
+                                    if (pos[t] < seg_cap) dst[pos[t]] = lower_key(t, r);
+                                    else *overflow = 1u;
+                                    ++pos[t];
+                                }
                             }
                         }
                     }

@@ -19,7 +19,9 @@ STAGE = ("pf_stage_queries_kernel", "i8s_stage_both_kernel")
 
 
 def short(name):
-    return name.split("(")[0].split("<")[0].split("::")[-1].split()[-1][-40:]  # ("void name<...>(args)" -> name)
+    # "void name<...>(args)" -> name; a name that opens with "(anonymous namespace)::" (torch's own kernels) keeps its tail
+    head = name.replace("(anonymous namespace)::", "").split("(")[0].split("<")[0].split("::")[-1].split()
+    return head[-1][-40:] if head else name[-40:]
 
 
 def load(d):
