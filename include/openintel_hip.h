@@ -724,6 +724,69 @@ int oi_similar_groups(oi_index *idx, const float *query_vecs, uint32_t n_queries
                       uint32_t *qualified_out /* [n_queries], may be NULL */);
 
 /* ------------------------------------------------------------------------- */
+/* Similarity share: each post counted once, under the query it is most like   */
+/* ------------------------------------------------------------------------- */
+/*
+ * oi_similar_volume, oi_similar_summary and oi_similar_groups decide every (query, document) pair on its own: a post that
+ * resembles three queries of a batch is counted three times.  This call is the EXCLUSIVE form, for a batch of narratives
+ * ("short squeeze", "earnings beat", "lawsuit", "dilution") among which the posts are to be divided: every post is counted at
+ * most once, under the query it is most like.  It is the classification counterpart of the threshold family and the
+ * assignment step of any clustering a host may run over the index.  Builder-defined like the whole retrieval path.
+ *
+ * The definition.  For a local document d, the CANDIDATES are the queries q for which clauses 1 and 3 of oi_similar_summary
+ * hold:
+ *   - d passes filters[q].  filters == NULL means every document passes.
+ *   - sim(q, d) >= t_q, where t_q = thresholds[q], or spec->threshold when thresholds == NULL.  sim is oi_similar_volume's
+ *     sim.  A NaN t_q makes q nobody's candidate.  A NaN similarity is never >=.
+ * The WINNER of d is the candidate with the largest sim(q, d), compared as the f32 values of the library's chain.  Ties go
+ * to the smallest q.
+ * d is ASSIGNED when it has a winner and clause 2 holds: bucket_width == 0, or stamp_origin <= stamp[d] and
+ * b = (stamp[d] - stamp_origin) / bucket_width < n_buckets (evaluated in 64 bits).
+ * out[q][b] holds the social_summary raw sums over the documents assigned to q in bucket b.  The fields and the integer
+ * arithmetic are oi_similar_summary's: total, by_source[2], bullish, bearish, neutral and spec_count are exact integers, and
+ * polarity_sum = (double)(sum of pol_q30) * 2^-30, the sum taken in 64-bit integers.
+ * labels_out[d] is the winner of an assigned document and 0xFFFFFFFF for every other row.  labels_out may be NULL.
+ *
+ * The contract that follows from it:
+ *   - every document is in at most one cell;
+ *   - out[q][b].total <= oi_similar_summary's for the same arguments;
+ *   - summed over q, the totals equal the number of documents with at least one candidate and a bucket;
+ *   - with n_queries == 1 the records are oi_similar_summary's bit for bit;
+ *   - so are they with pairwise disjoint filters;
+ *   - a query that repeats an earlier one with the same threshold and filter gets all-zero records;
+ *   - the result is deterministic and independent of the route, the order of the atomics, the cosine mode and the copy policy;
+ *   - unlike its siblings it DOES depend on the batch composition: adding, removing or reordering queries moves posts
+ *     between records.  That is the point of the call;
+ *   - pairs whose true similarities lie within 1e-5 of each other, or of the threshold, may fall either way under the f32
+ *     chain (the same sentence as for the collapse and the screen).
+ *
+ * Rules.  Those of oi_similar_summary: spec is always a host pointer; location says where the query vectors, the thresholds,
+ * the filters, out and labels_out live; OI_DEVICE is asynchronous on the ctx stream; embeddings only (no forward index, no
+ * finalize); it works on a view; n_queries == 0 is OI_OK (labels_out, when given, is all 0xFFFFFFFF); n_queries <= 4096;
+ * n_queries * n_buckets <= OI_MAX_SUMMARY_CELLS; not captured by graph replay.  An index without signals -> OI_ERR_STATE;
+ * bucket_width > 0 or filters != NULL on an index without attributes -> OI_ERR_STATE.  A null spec, index, query or out
+ * buffer, a NaN spec->threshold without an array, n_queries or the cell count out of range -> OI_ERR_INVALID_ARG with the
+ * number in the message; every argument check precedes the first device call.
+ * Routes.  Up to 64 queries on a screened f32 corpus (dim 384 / 768 with a screening copy) take ONE stream of the copy: a row
+ * that a single query can reach is decided there, the others are rescored exactly.  More than 64 queries, other corpora and
+ * the exact cosine modes take the exact route; the result is the same.
+ * Workspace per searching context: 64 B per cell; on the stream route also the volume's 32 MB band buffer, 16.25 MB of keys
+ * beside it and `best`, 8 B per local row (oi_workspace_bytes counts all of them); with OI_HOST, 4 B per local row more when
+ * labels_out is given.
+ * Profile tags: "share" (the stream), "share_band" (rescoring and commit of the undecided rows), "share_exact" (the exact
+ * route, and the runs of the fallback inside a screened call that really did the work); "share_state" reads the band fill
+ * and the gate / overflow bits of the last call.
+ *
+ * NOT covered: oi_search_sharded* and oi_pipeline_*.  Winners of shards do not add when the QUERIES are sharded; a host that
+ * shards the queries must exchange the per-row best key.  (Shards of the DOCUMENTS hold disjoint rows: their records add.)
+ */
+int oi_similar_share(oi_index *idx, const float *query_vecs, uint32_t n_queries, const oi_summary_spec *spec,
+                     const float *thresholds /* [n_queries] where `location` says, or NULL */,
+                     const oi_doc_filter *filters, int location,
+                     oi_social_counters *out /* [n_queries][n_buckets] */,
+                     uint32_t *labels_out /* [n_docs] by LOCAL row where `location` says, or NULL */);
+
+/* ------------------------------------------------------------------------- */
 /* Text to term ids: the tokeniser and the hashed vocabulary                   */
 /* ------------------------------------------------------------------------- */
 /*
@@ -842,7 +905,8 @@ int oi_screen_probe(oi_index *idx, const float *query_vecs, uint32_t n_queries, 
  * stream time each: a timed region that only needs its dominant kernel asks for 2).
  * The screened cosine route also tags "cosine_gated", "rescreen", "rescore" and "spec".  "spec" COUNTS the speculative
  * thresholds computed in a search, one span per prediction; the prediction is computed inside the preceding margin select,
- * whose time is under "select", so the span is empty and its duration reads ~0. */
+ * whose time is under "select", so the span is empty and its duration reads ~0.
+ * The list of tags ends with those of oi_similar_share: "share", "share_band", "share_exact". */
 int oi_profile_reset(oi_ctx *ctx, int enable);
 int oi_profile_read(oi_ctx *ctx, const char *kernel_tag, double *total_ms_out, uint64_t *launches_out);
 

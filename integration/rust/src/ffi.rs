@@ -249,6 +249,12 @@ extern "C" {
                              records_out: *mut OiSocialCounters, keys_out: *mut u32, counts_out: *mut u32,
                              qualified_out: *mut u32) -> c_int;
 
+    // similarity share: the summary's arguments, every document counted at most once, under the query it is most like;
+    // labels_out [n_docs] by local row (0xFFFFFFFF: not assigned) may be null
+    pub fn oi_similar_share(idx: *mut OiIndex, query_vecs: *const f32, n_queries: u32, spec: *const OiSummarySpec,
+                            thresholds: *const f32, filters: *const OiDocFilter, location: c_int,
+                            out: *mut OiSocialCounters, labels_out: *mut u32) -> c_int;
+
     pub fn oi_pipeline_create(idx: *mut OiIndex, comm: *mut OiComm, lanes: u32, max_queries: u32, max_query_terms: u32,
                               depth: u32, k: u32, out: *mut *mut OiPipeline) -> c_int;
     pub fn oi_pipeline_destroy(p: *mut OiPipeline);

@@ -356,6 +356,31 @@ impl HipIndex {
         })?;
         Ok(out.chunks(nb.max(1)).map(|c| c.to_vec()).collect())
     }
+    /// The posts divided among the queries of a batch (`oi_similar_share`): `similar_summary`'s records, but every document is
+    /// counted at most once, under the candidate query with the largest similarity (ties to the smallest query).  With
+    /// `labels` the second value holds, per local row, the winner of an assigned document and 0xFFFFFFFF for every other row.
+    /// Deterministic; unlike its siblings the result depends on the batch composition.
+    pub fn similar_share(&self, query_vecs: &[f32], spec: ffi::OiSummarySpec, thresholds: Option<&[f32]>,
+                         filters: Option<&[ffi::OiDocFilter]>, labels: bool)
+                         -> Result<(Vec<Vec<ffi::OiSocialCounters>>, Option<Vec<u32>>), HipError> {
+        assert_eq!(query_vecs.len() % self.dim, 0);
+        let b = query_vecs.len() / self.dim;
+        if let Some(f) = filters {
+            assert_eq!(f.len(), b);
+        }
+        if let Some(t) = thresholds {
+            assert_eq!(t.len(), b);
+        }
+        let nb = spec.n_buckets as usize;
+        let mut out = vec![ffi::OiSocialCounters::default(); b * nb];
+        let mut lab = if labels { Some(vec![u32::MAX; self.n_docs]) } else { None };
+        check(unsafe {
+            ffi::oi_similar_share(self.idx, query_vecs.as_ptr(), b as u32, &spec, thresholds.map_or(std::ptr::null(), |t| t.as_ptr()),
+                                  filters.map_or(std::ptr::null(), |f| f.as_ptr()), ffi::OI_HOST, out.as_mut_ptr(),
+                                  lab.as_mut().map_or(std::ptr::null_mut(), |l| l.as_mut_ptr()))
+        })?;
+        Ok((out.chunks(nb.max(1)).map(|c| c.to_vec()).collect(), lab))
+    }
     /// Which group keys (tickers) the posts like each query are about, and what those posts feel (`oi_similar_groups`): the
     /// social_summary sums per key = (group & key_mask) >> ctz(key_mask), under `similar_summary`'s clauses.  spec.top == 0: per
     /// query `n_keys` records, keys implied (entry i is (i, record i)).  spec.top >= 1: per query the listed (key, record) pairs,

@@ -162,6 +162,7 @@ SIGNATURES = {
     "oi_index_set_signals": (_I, [_P, _P, _P, _P, C.c_double, _I]),
     "oi_similar_summary": (_I, [_P, _P, _U32, _P, _P, _P, _I, _P]),
     "oi_similar_groups": (_I, [_P, _P, _U32, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "oi_similar_share": (_I, [_P, _P, _U32, _P, _P, _P, _I, _P, _P]),
     "oi_text_terms": (_I, [_P, _P, _P, _U64, _U64, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_query_terms": (_I, [_P, _P, _P, _U32, _U32, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_index_set_text": (_I, [_P, _P, _P, _U64, _I]),

@@ -10,6 +10,7 @@ Host mirror of the reference's batch tools (paths relative to the openintel repo
     RankBy / CompareArgs / RankedEntry / CompareError / CompareOutput
     rank_metric / sort_ranked / run_compare        src/mcp/tools.rs:227-352
     rank_group_records / compare_index             src/mcp/tools.rs:323-349 over the index's per-ticker sums (oi_similar_groups)
+    VoiceShare / share_of_voice                    builder-defined: the records of oi_similar_share as fractions per bucket
     SentimentSummary / sentiment_for (per dip row) src/domain/dip.rs:428-431, src/application/dip.rs:175-194
 
 The reference runs `application::analyze` once per ticker (`join_all`, tools.rs:206-220) and never pools posts of
@@ -340,6 +341,28 @@ def compare_index(index, query_vec, threshold: float, tickers, key_mask: int, ra
     res = index.similar_groups(q, float(threshold), int(key_mask), int(n_keys), top=int(top), rank_by="total",
                                min_total=int(cfg.min_sample if min_total is None else min_total), filters=filters)
     return rank_group_records(res.keys[0], res.records[0], int(res.counts[0]), tickers, rank_by, market_by_ticker, now, cfg)
+
+
+# ----------------------------------------------------------------------------- share of voice (oi_similar_share)
+@dataclass
+class VoiceShare:  # builder-defined (the reference divides no posts among narratives)
+    total: int                 # posts assigned to the query in the bucket
+    fraction: float            # total / the bucket's assigned posts over all queries; 0.0 in a bucket without any
+    social: "object"           # SocialSummary of the assigned posts (SpeculationEngine.social_from_counters)
+
+
+def share_of_voice(records) -> List[List[VoiceShare]]:
+    """Each query's share of the posts `HybridIndex.similar_share` assigned, per bucket: `records` is its [B, n_buckets]
+    array (analyzer.COUNTERS_DTYPE; every post is in at most one cell, so a bucket's totals add up to its assigned posts).
+    Entry [q][b] holds the query's total, its fraction of the bucket's total over all queries, and the SocialSummary of its
+    posts.  A bucket no query has a post in gives fraction 0.0 everywhere."""
+    B = len(records)
+    nb = len(records[0]) if B else 0
+    sums = [sum(int(records[q][b]["total"]) for q in range(B)) for b in range(nb)]
+    return [[VoiceShare(total=int(records[q][b]["total"]),
+                        fraction=(int(records[q][b]["total"]) / sums[b]) if sums[b] else 0.0,
+                        social=SpeculationEngine.social_from_counters(records[q][b]))
+             for b in range(nb)] for q in range(B)]
 
 
 # ----------------------------------------------------------------------------- wire format (#[derive(Serialize)])

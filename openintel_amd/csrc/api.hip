@@ -112,8 +112,9 @@ extern "C" int oi_profile_reset(oi_ctx *ctx, int enable) {
     for (auto &kv : ctx->prof)
         for (auto &s : kv.second) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     ctx->prof.clear();
-    for (const char *runs : {"volume_runs", "summary_runs", "groups_runs"}) {
-        // the fallback-run counters of oi_similar_volume / _summary / _groups ("volume_exact", "summary_exact", "groups_exact") start over with the spans
+    for (const char *runs : {"volume_runs", "summary_runs", "groups_runs", "share_runs"}) {
+        // the fallback-run counters of oi_similar_volume / _summary / _groups / _share ("volume_exact", "summary_exact", "groups_exact",
+        // "share_exact") start over with the spans
         auto vr = ctx->ws.find(runs);
         if (vr != ctx->ws.end() && vr->second.p) (void)hipMemsetAsync(vr->second.p, 0, 16, ctx->stream);
     }
@@ -153,8 +154,9 @@ extern "C" int oi_profile_read(oi_ctx *ctx, const char *kernel_tag, double *tota
         if (launches_out) *launches_out = 0;
         return OI_OK;
     }
-    if (strcmp(kernel_tag, "volume_state") == 0 || strcmp(kernel_tag, "summary_state") == 0 || strcmp(kernel_tag, "groups_state") == 0) {
-        // diagnostics of the last oi_similar_volume / oi_similar_summary / oi_similar_groups: undecided pairs its stream sent to the band (may exceed
+    if (strcmp(kernel_tag, "volume_state") == 0 || strcmp(kernel_tag, "summary_state") == 0 || strcmp(kernel_tag, "groups_state") == 0 ||
+        strcmp(kernel_tag, "share_state") == 0) {
+        // diagnostics of the last oi_similar_volume / oi_similar_summary / oi_similar_groups / oi_similar_share: undecided pairs its stream sent to the band (may exceed
         // the 4 Mi the buffer holds); bit 0 = a query had no bound, bit 1 = band overflow
         uint32_t w[4] = {0, 0, 0, 0};
         auto vs = ctx->ws.find(kernel_tag);
@@ -170,10 +172,10 @@ extern "C" int oi_profile_read(oi_ctx *ctx, const char *kernel_tag, double *tota
             if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) { total += ms; ++n; }
         }
     const char *family = strcmp(kernel_tag, "volume_exact") == 0 ? "volume" : strcmp(kernel_tag, "summary_exact") == 0 ? "summary"
-                       : strcmp(kernel_tag, "groups_exact") == 0 ? "groups" : nullptr;
+                       : strcmp(kernel_tag, "groups_exact") == 0 ? "groups" : strcmp(kernel_tag, "share_exact") == 0 ? "share" : nullptr;
     if (family) {
-        // the gated fallback inside screened oi_similar_volume / _summary / _groups calls ("volume_fallback", "summary_fallback",
-        // "groups_fallback": launched every time, exits at once unless the call needs it) counts here only for the runs that really
+        // the gated fallback inside screened oi_similar_volume / _summary / _groups / _share calls ("volume_fallback", "summary_fallback",
+        // "groups_fallback", "share_fallback": launched every time, exits at once unless the call needs it) counts here only for the runs that really
         // counted a batch (cosine_volume.hip, cosine_summary.hip, cosine_groups.hip)
         uint32_t runs = 0;
         auto vr = ctx->ws.find(std::string(family) + "_runs");
@@ -1709,6 +1711,59 @@ extern "C" int oi_similar_groups(oi_index *idx, const float *qv, uint32_t B, con
         OI_HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, cb, hipMemcpyDeviceToHost, st));
         if (qualified_out) OI_HIP_CHECK(hipMemcpyAsync(qualified_out, d_qual, cb, hipMemcpyDeviceToHost, st));
     }
+    OI_HIP_CHECK(hipStreamSynchronize(st));
+    return OI_OK;
+}
+
+// ---------------------------------------------------------------- similarity share (cosine_share.hip)
+// The checks of oi_similar_summary in its order, before the first HIP call.  Never captured.  labels_out may be null.
+extern "C" int oi_similar_share(oi_index *idx, const float *qv, uint32_t B, const oi_summary_spec *spec, const float *thresholds,
+                                const oi_doc_filter *filters, int location, oi_social_counters *out, uint32_t *labels_out) {
+    OI_REQUIRE(spec, "similar_share: null spec");
+    OI_REQUIRE(thresholds || spec->threshold == spec->threshold, "similar_share: threshold is NaN (and no thresholds array)");
+    OI_REQUIRE(spec->n_buckets >= 1 && spec->n_buckets <= OI_MAX_VOLUME_BUCKETS, "similar_share: n_buckets=%u outside [1,%u]",
+               spec->n_buckets, OI_MAX_VOLUME_BUCKETS);
+    OI_REQUIRE(spec->bucket_width != 0 || spec->n_buckets == 1, "similar_share: bucket_width=0 (no time axis) with n_buckets=%u",
+               spec->n_buckets);
+    OI_REQUIRE(B <= 4096, "similar_share: n_queries=%u outside [0,4096]", B);
+    OI_REQUIRE((uint64_t)B * spec->n_buckets <= OI_MAX_SUMMARY_CELLS, "similar_share: n_queries * n_buckets = %llu cells, more than %u",
+               (unsigned long long)B * spec->n_buckets, OI_MAX_SUMMARY_CELLS);
+    OI_REQUIRE(B == 0 || (qv && out), "similar_share: null buffer");
+    if (!idx) { oi_set_error("similar_share: null index"); return OI_ERR_INVALID_ARG; }
+    if (!idx->rows && !idx->rows_bf16) { oi_set_error("similar_share: the index has no embeddings (oi_index_set_embeddings)"); return OI_ERR_STATE; }
+    oi_ctx *ctx = idx->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!idx->signals.p) { oi_set_error("similar_share: the index has no signals (oi_index_set_signals)"); return OI_ERR_STATE; }
+    if ((filters || spec->bucket_width) && !idx->doc_attrs.p) {
+        oi_set_error("similar_share: filters / time buckets need the index's doc attributes (oi_index_set_doc_attrs)");
+        return OI_ERR_STATE;
+    }
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t lb = labels_out ? sizeof(uint32_t) * (size_t)idx->n_docs : 0;
+    if (B == 0) { // no query: no row has a candidate
+        if (lb && location == OI_DEVICE) OI_HIP_CHECK(hipMemsetAsync(labels_out, 0xFF, lb, st));
+        else if (lb) memset(labels_out, 0xFF, lb);
+        return OI_OK;
+    }
+    if (location == OI_DEVICE)
+        return oi_launch_similar_share(idx, qv, B, *spec, thresholds, reinterpret_cast<const uint4 *>(filters), out, labels_out);
+    const size_t vb = (sizeof(float) * (size_t)B * idx->dim + 15) & ~(size_t)15, fb = filters ? sizeof(oi_doc_filter) * (size_t)B : 0;
+    const size_t tb = thresholds ? (sizeof(float) * (size_t)B + 15) & ~(size_t)15 : 0;
+    const size_t ob = sizeof(oi_social_counters) * (size_t)B * spec->n_buckets;
+    DevBuf &w = ctx->buf("share_io"); // [vectors | filters | thresholds | records | labels]
+    OI_CHECK(w.ensure(vb + fb + tb + ob + lb + 64));
+    uint8_t *d = w.as<uint8_t>();
+    OI_HIP_CHECK(hipMemcpyAsync(d, qv, sizeof(float) * (size_t)B * idx->dim, hipMemcpyHostToDevice, st));
+    if (filters) OI_HIP_CHECK(hipMemcpyAsync(d + vb, filters, fb, hipMemcpyHostToDevice, st));
+    if (thresholds) OI_HIP_CHECK(hipMemcpyAsync(d + vb + fb, thresholds, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, st));
+    oi_social_counters *d_out = reinterpret_cast<oi_social_counters *>(d + vb + fb + tb);
+    uint32_t *d_labels = lb ? reinterpret_cast<uint32_t *>(d + vb + fb + tb + ob) : nullptr;
+    OI_CHECK(oi_launch_similar_share(idx, reinterpret_cast<const float *>(d), B, *spec,
+                                     thresholds ? reinterpret_cast<const float *>(d + vb + fb) : nullptr,
+                                     filters ? reinterpret_cast<const uint4 *>(d + vb) : nullptr, d_out, d_labels));
+    OI_HIP_CHECK(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st));
+    if (lb) OI_HIP_CHECK(hipMemcpyAsync(labels_out, d_labels, lb, hipMemcpyDeviceToHost, st));
     OI_HIP_CHECK(hipStreamSynchronize(st));
     return OI_OK;
 }

@@ -346,6 +346,10 @@ int oi_launch_similar_summary(oi_index *idx, const float *d_q, uint32_t n_querie
 int oi_launch_similar_groups(oi_index *idx, const float *d_q, uint32_t n_queries, const oi_groups_spec &spec, const float *d_thresholds,
                              const uint4 *d_filt, oi_social_counters *d_records, uint32_t *d_keys, uint32_t *d_counts,
                              uint32_t *d_qualified);
+// cosine_share.hip: the similarity share -- the summary's arguments; device records [n_queries][n_buckets] and
+// (may be null) labels [n_docs] by local row out.  Asynchronous on the ctx stream; d_thresholds and d_filt may be null
+int oi_launch_similar_share(oi_index *idx, const float *d_q, uint32_t n_queries, const oi_summary_spec &spec, const float *d_thresholds,
+                            const uint4 *d_filt, oi_social_counters *d_out, uint32_t *d_labels);
 // cosine.hip
 // Sets pool.n_segs / pool.seg_cap for this chunk (the following select must use the same view).
 int oi_launch_cosine_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end,

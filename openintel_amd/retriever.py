@@ -588,6 +588,51 @@ class HybridIndex(PostRetriever):
                                               _lib.ptr(counts), _lib.ptr(qualified)))
         return GroupRanking(keys, records, counts, qualified) if top else records
 
+    # ---------------------------------------------------------------- similarity share
+    def similar_share(self, query_vecs, threshold, n_buckets: int = 1, stamp_origin: int = 0, bucket_width: int = 0,
+                      filters=None, labels: bool = False):
+        """oi_similar_share: similar_summary's [B, n_buckets] records, but every document is counted at most ONCE, under the
+        query it is most like: among the queries whose filter it passes and whose threshold its similarity reaches (a float,
+        or one per query; a NaN entry is nobody's candidate) the one with the largest similarity wins, ties to the smallest
+        query.  Deterministic, and -- unlike similar_summary -- dependent on the batch composition: that is the point.
+        labels=True returns (records, labels): labels [n_docs] uint32 by local row, the winner of an assigned document and
+        0xFFFFFFFF for every other row.  Host array in, numpy out; torch CUDA tensor in, tensors out (records as int64
+        [B, n_buckets, 8] holding the records' bits; asynchronous on the ctx stream).  batch.share_of_voice turns the records
+        into each query's fraction of the assigned posts."""
+        from .analyzer import COUNTERS_DTYPE
+        dev = _is_dev(query_vecs)
+        if dev:
+            assert query_vecs.is_contiguous() and query_vecs.element_size() == 4
+        else:
+            query_vecs = _np(query_vecs, np.float32)
+        B = int(query_vecs.shape[0])
+        assert B == 0 or int(query_vecs.shape[1]) == self.dim
+        nb = max(int(n_buckets), 0)
+        thr = None
+        if not _is_dev(threshold) and np.ndim(threshold) == 0:
+            spec = _lib.SummarySpec(float(threshold), int(stamp_origin), int(bucket_width), int(n_buckets))
+        else:
+            spec = _lib.SummarySpec(0.0, int(stamp_origin), int(bucket_width), int(n_buckets))
+            if dev:
+                import torch
+                if not _is_dev(threshold):
+                    threshold = torch.from_numpy(_np(threshold, np.float32)).to("cuda:%d" % self.ctx.device)
+                assert threshold.is_contiguous() and threshold.numel() == B and threshold.element_size() == 4
+                self._thr_keep = thr = threshold  # (an asynchronous call reads it later)
+            else:
+                thr = _np(threshold.cpu().numpy() if _is_dev(threshold) else threshold, np.float32)
+                assert thr.size == B
+        if dev:
+            import torch
+            out = torch.zeros((B, nb, 8), dtype=torch.int64, device="cuda:%d" % self.ctx.device)
+        else:
+            out = np.zeros((B, nb), dtype=COUNTERS_DTYPE)
+        lab = self._alloc(dev, (self.n_docs,), np.uint32) if labels else None
+        f = None if filters is None else self._filters(filters, dev, B)
+        _lib.check(self.lib.oi_similar_share(self.handle, _lib.ptr(query_vecs), B, C.byref(spec), _lib.ptr(thr), _lib.ptr(f),
+                                             _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(out), _lib.ptr(lab)))
+        return (out, lab) if labels else out
+
     # ---------------------------------------------------------------- the sharded query with RCCL inside the library
     def finalize_sharded(self, comm: "NativeComm") -> None:
         """Collective over `comm`: all-reduce of (n_docs, tokens, df) inside the library, then the impacts from the global
