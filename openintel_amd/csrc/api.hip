@@ -1567,95 +1567,105 @@ extern "C" int oi_search_collapsed(oi_index *idx, const float *qv, const uint32_
     return check_overflow_locked(ctx);
 }
 
-// ---------------------------------------------------------------- similarity volume (cosine_volume.hip)
-// Every argument check precedes the first HIP call (the spec first: it can be judged without a handle).  Never captured.
-extern "C" int oi_similar_volume(oi_index *idx, const float *qv, uint32_t B, const oi_volume_spec *spec, const oi_doc_filter *filters,
-                                 int location, uint32_t *counts_out) {
-    OI_REQUIRE(spec, "similar_volume: null spec");
-    OI_REQUIRE(spec->threshold == spec->threshold, "similar_volume: threshold is NaN");
-    OI_REQUIRE(spec->n_buckets >= 1 && spec->n_buckets <= OI_MAX_VOLUME_BUCKETS, "similar_volume: n_buckets=%u outside [1,%u]",
-               spec->n_buckets, OI_MAX_VOLUME_BUCKETS);
-    OI_REQUIRE(spec->bucket_width != 0 || spec->n_buckets == 1, "similar_volume: bucket_width=0 (no time axis) with n_buckets=%u",
-               spec->n_buckets);
-    OI_REQUIRE(B <= 4096, "similar_volume: n_queries=%u outside [0,4096]", B);
-    OI_REQUIRE(B == 0 || (qv && counts_out), "similar_volume: null buffer");
-    if (!idx) { oi_set_error("similar_volume: null index"); return OI_ERR_INVALID_ARG; }
-    if (!idx->rows && !idx->rows_bf16) { oi_set_error("similar_volume: the index has no embeddings (oi_index_set_embeddings)"); return OI_ERR_STATE; }
-    oi_ctx *ctx = idx->ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if ((filters || spec->bucket_width) && !idx->doc_attrs.p) {
-        oi_set_error("similar_volume: filters / time buckets need the index's doc attributes (oi_index_set_doc_attrs)");
-        return OI_ERR_STATE;
-    }
-    if (B == 0) return OI_OK;
-    OI_HIP_CHECK(hipSetDevice(ctx->device));
-    static_assert(sizeof(oi_doc_filter) == sizeof(uint4), "oi_doc_filter is 16 bytes");
-    if (location == OI_DEVICE) return oi_launch_similar_volume(idx, qv, B, *spec, reinterpret_cast<const uint4 *>(filters), counts_out);
-    hipStream_t st = ctx->stream;
-    const size_t vb = (sizeof(float) * (size_t)B * idx->dim + 15) & ~(size_t)15, fb = filters ? sizeof(oi_doc_filter) * (size_t)B : 0;
-    const size_t cb = sizeof(uint32_t) * (size_t)B * spec->n_buckets;
-    DevBuf &w = ctx->buf("volume_io"); // [vectors | filters | counts]
-    OI_CHECK(w.ensure(vb + fb + cb + 64));
-    uint8_t *d = w.as<uint8_t>();
-    OI_HIP_CHECK(hipMemcpyAsync(d, qv, sizeof(float) * (size_t)B * idx->dim, hipMemcpyHostToDevice, st));
-    if (filters) OI_HIP_CHECK(hipMemcpyAsync(d + vb, filters, fb, hipMemcpyHostToDevice, st));
-    uint32_t *d_counts = reinterpret_cast<uint32_t *>(d + vb + fb);
-    OI_CHECK(oi_launch_similar_volume(idx, reinterpret_cast<const float *>(d), B, *spec,
-                                      filters ? reinterpret_cast<const uint4 *>(d + vb) : nullptr, d_counts));
-    OI_HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, cb, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipStreamSynchronize(st));
+// ---------------------------------------------------------------- the threshold family's entry points (oi_volume.h)
+// What oi_similar_volume / _summary / _groups / _share check and stage alike, written once; `call` is the entry point's name in
+// the messages.  In every call the checks keep their order -- the spec first (it can be judged without a handle), then the
+// buffers, the index, its state -- and all of them precede the first HIP call.  None of the four is ever captured.
+
+// The spec of the three calls with a time axis.  per_query: the call takes a thresholds array; max_cells: its cap on
+// n_queries * n_buckets (0: none).
+static int similar_check_spec(const char *call, float threshold, const float *thresholds, bool per_query, uint32_t n_buckets,
+                              uint32_t bucket_width, uint32_t B, uint32_t max_cells) {
+    OI_REQUIRE(thresholds || threshold == threshold, "%s: threshold is NaN%s", call, per_query ? " (and no thresholds array)" : "");
+    OI_REQUIRE(n_buckets >= 1 && n_buckets <= OI_MAX_VOLUME_BUCKETS, "%s: n_buckets=%u outside [1,%u]", call, n_buckets, OI_MAX_VOLUME_BUCKETS);
+    OI_REQUIRE(bucket_width != 0 || n_buckets == 1, "%s: bucket_width=0 (no time axis) with n_buckets=%u", call, n_buckets);
+    OI_REQUIRE(B <= 4096, "%s: n_queries=%u outside [0,4096]", call, B);
+    OI_REQUIRE(!max_cells || (uint64_t)B * n_buckets <= max_cells, "%s: n_queries * n_buckets = %llu cells, more than %u", call,
+               (unsigned long long)B * n_buckets, max_cells);
     return OI_OK;
 }
 
-// ---------------------------------------------------------------- similarity summary (cosine_summary.hip)
-// The checks of oi_similar_volume in its order, before the first HIP call.  Never captured.
-extern "C" int oi_similar_summary(oi_index *idx, const float *qv, uint32_t B, const oi_summary_spec *spec, const float *thresholds,
-                                  const oi_doc_filter *filters, int location, oi_social_counters *out) {
-    OI_REQUIRE(spec, "similar_summary: null spec");
-    OI_REQUIRE(thresholds || spec->threshold == spec->threshold, "similar_summary: threshold is NaN (and no thresholds array)");
-    OI_REQUIRE(spec->n_buckets >= 1 && spec->n_buckets <= OI_MAX_VOLUME_BUCKETS, "similar_summary: n_buckets=%u outside [1,%u]",
-               spec->n_buckets, OI_MAX_VOLUME_BUCKETS);
-    OI_REQUIRE(spec->bucket_width != 0 || spec->n_buckets == 1, "similar_summary: bucket_width=0 (no time axis) with n_buckets=%u",
-               spec->n_buckets);
-    OI_REQUIRE(B <= 4096, "similar_summary: n_queries=%u outside [0,4096]", B);
-    OI_REQUIRE((uint64_t)B * spec->n_buckets <= OI_MAX_SUMMARY_CELLS, "similar_summary: n_queries * n_buckets = %llu cells, more than %u",
-               (unsigned long long)B * spec->n_buckets, OI_MAX_SUMMARY_CELLS);
-    OI_REQUIRE(B == 0 || (qv && out), "similar_summary: null buffer");
-    if (!idx) { oi_set_error("similar_summary: null index"); return OI_ERR_INVALID_ARG; }
-    if (!idx->rows && !idx->rows_bf16) { oi_set_error("similar_summary: the index has no embeddings (oi_index_set_embeddings)"); return OI_ERR_STATE; }
-    oi_ctx *ctx = idx->ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (!idx->signals.p) { oi_set_error("similar_summary: the index has no signals (oi_index_set_signals)"); return OI_ERR_STATE; }
-    if ((filters || spec->bucket_width) && !idx->doc_attrs.p) {
-        oi_set_error("similar_summary: filters / time buckets need the index's doc attributes (oi_index_set_doc_attrs)");
+// The index and its state.  g takes the context's lock where every call took it: behind the embeddings check.  attrs_for: who
+// needs the doc attributes ("... need" / "... needs"), or null when this call does not.
+static int similar_check_state(const char *call, oi_index *idx, bool signals, const char *attrs_for, std::unique_lock<std::mutex> &g) {
+    if (!idx) { oi_set_error("%s: null index", call); return OI_ERR_INVALID_ARG; }
+    if (!idx->rows && !idx->rows_bf16) { oi_set_error("%s: the index has no embeddings (oi_index_set_embeddings)", call); return OI_ERR_STATE; }
+    g = std::unique_lock<std::mutex>(idx->ctx->mu);
+    if (signals && !idx->signals.p) { oi_set_error("%s: the index has no signals (oi_index_set_signals)", call); return OI_ERR_STATE; }
+    if (attrs_for && !idx->doc_attrs.p) {
+        oi_set_error("%s: %s the index's doc attributes (oi_index_set_doc_attrs)", call, attrs_for);
         return OI_ERR_STATE;
     }
-    if (B == 0) return OI_OK;
-    OI_HIP_CHECK(hipSetDevice(ctx->device));
-    if (location == OI_DEVICE)
-        return oi_launch_similar_summary(idx, qv, B, *spec, thresholds, reinterpret_cast<const uint4 *>(filters), out);
+    return OI_OK;
+}
+#define SIMILAR_TIME_AXIS "filters / time buckets need"
+
+// The host location: [vectors | filters | thresholds | outputs ...] in the call's workspace `io`, copied in; launch(vectors,
+// thresholds, filters, first output) on the device; then every output with a host pointer copied back, and the stream awaited.
+// An output without one (null) still has its room: the launch may write it.
+struct SimilarOut { void *host; size_t bytes; };
+template <class Launch>
+static int similar_staged(oi_index *idx, const char *io, const float *qv, uint32_t B, const float *thresholds, const oi_doc_filter *filters,
+                          std::initializer_list<SimilarOut> outs, Launch launch) {
+    static_assert(sizeof(oi_doc_filter) == sizeof(uint4), "oi_doc_filter is 16 bytes");
+    oi_ctx *ctx = idx->ctx;
     hipStream_t st = ctx->stream;
     const size_t vb = (sizeof(float) * (size_t)B * idx->dim + 15) & ~(size_t)15, fb = filters ? sizeof(oi_doc_filter) * (size_t)B : 0;
     const size_t tb = thresholds ? (sizeof(float) * (size_t)B + 15) & ~(size_t)15 : 0;
-    const size_t ob = sizeof(oi_social_counters) * (size_t)B * spec->n_buckets;
-    DevBuf &w = ctx->buf("summary_io"); // [vectors | filters | thresholds | records]
+    size_t ob = 0;
+    for (const SimilarOut &o : outs) ob += o.bytes;
+    DevBuf &w = ctx->buf(io);
     OI_CHECK(w.ensure(vb + fb + tb + ob + 64));
-    uint8_t *d = w.as<uint8_t>();
+    uint8_t *d = w.as<uint8_t>(), *d_out = d + vb + fb + tb;
     OI_HIP_CHECK(hipMemcpyAsync(d, qv, sizeof(float) * (size_t)B * idx->dim, hipMemcpyHostToDevice, st));
     if (filters) OI_HIP_CHECK(hipMemcpyAsync(d + vb, filters, fb, hipMemcpyHostToDevice, st));
     if (thresholds) OI_HIP_CHECK(hipMemcpyAsync(d + vb + fb, thresholds, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, st));
-    oi_social_counters *d_out = reinterpret_cast<oi_social_counters *>(d + vb + fb + tb);
-    OI_CHECK(oi_launch_similar_summary(idx, reinterpret_cast<const float *>(d), B, *spec,
-                                       thresholds ? reinterpret_cast<const float *>(d + vb + fb) : nullptr,
-                                       filters ? reinterpret_cast<const uint4 *>(d + vb) : nullptr, d_out));
-    OI_HIP_CHECK(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st));
+    OI_CHECK(launch(reinterpret_cast<const float *>(d), thresholds ? reinterpret_cast<const float *>(d + vb + fb) : nullptr,
+                    filters ? reinterpret_cast<const uint4 *>(d + vb) : nullptr, d_out));
+    for (const SimilarOut &o : outs) {
+        if (o.host && o.bytes) OI_HIP_CHECK(hipMemcpyAsync(o.host, d_out, o.bytes, hipMemcpyDeviceToHost, st));
+        d_out += o.bytes;
+    }
     OI_HIP_CHECK(hipStreamSynchronize(st));
     return OI_OK;
 }
 
-// ---------------------------------------------------------------- similarity leaderboard (cosine_groups.hip)
-// The checks of oi_similar_summary in its order (the spec first: it can be judged without a handle), before the first HIP call.
-// Never captured.
+// similarity volume (cosine_volume.hip)
+extern "C" int oi_similar_volume(oi_index *idx, const float *qv, uint32_t B, const oi_volume_spec *spec, const oi_doc_filter *filters,
+                                 int location, uint32_t *counts_out) {
+    OI_REQUIRE(spec, "similar_volume: null spec");
+    OI_CHECK(similar_check_spec("similar_volume", spec->threshold, nullptr, false, spec->n_buckets, spec->bucket_width, B, 0));
+    OI_REQUIRE(B == 0 || (qv && counts_out), "similar_volume: null buffer");
+    std::unique_lock<std::mutex> g;
+    OI_CHECK(similar_check_state("similar_volume", idx, false, (filters || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
+    if (B == 0) return OI_OK;
+    OI_HIP_CHECK(hipSetDevice(idx->ctx->device));
+    if (location == OI_DEVICE) return oi_launch_similar_volume(idx, qv, B, *spec, reinterpret_cast<const uint4 *>(filters), counts_out);
+    return similar_staged(idx, "volume_io", qv, B, nullptr, filters, {{counts_out, sizeof(uint32_t) * (size_t)B * spec->n_buckets}},
+                          [&](const float *q, const float *, const uint4 *f, uint8_t *o) {
+                              return oi_launch_similar_volume(idx, q, B, *spec, f, reinterpret_cast<uint32_t *>(o));
+                          });
+}
+
+// similarity summary (cosine_summary.hip)
+extern "C" int oi_similar_summary(oi_index *idx, const float *qv, uint32_t B, const oi_summary_spec *spec, const float *thresholds,
+                                  const oi_doc_filter *filters, int location, oi_social_counters *out) {
+    OI_REQUIRE(spec, "similar_summary: null spec");
+    OI_CHECK(similar_check_spec("similar_summary", spec->threshold, thresholds, true, spec->n_buckets, spec->bucket_width, B, OI_MAX_SUMMARY_CELLS));
+    OI_REQUIRE(B == 0 || (qv && out), "similar_summary: null buffer");
+    std::unique_lock<std::mutex> g;
+    OI_CHECK(similar_check_state("similar_summary", idx, true, (filters || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
+    if (B == 0) return OI_OK;
+    OI_HIP_CHECK(hipSetDevice(idx->ctx->device));
+    if (location == OI_DEVICE)
+        return oi_launch_similar_summary(idx, qv, B, *spec, thresholds, reinterpret_cast<const uint4 *>(filters), out);
+    return similar_staged(idx, "summary_io", qv, B, thresholds, filters, {{out, sizeof(oi_social_counters) * (size_t)B * spec->n_buckets}},
+                          [&](const float *q, const float *t, const uint4 *f, uint8_t *o) {
+                              return oi_launch_similar_summary(idx, q, B, *spec, t, f, reinterpret_cast<oi_social_counters *>(o));
+                          });
+}
+
+// similarity leaderboard (cosine_groups.hip): its spec is its own, the rest as above
 extern "C" int oi_similar_groups(oi_index *idx, const float *qv, uint32_t B, const oi_groups_spec *spec, const float *thresholds,
                                  const oi_doc_filter *filters, int location, oi_social_counters *records_out, uint32_t *keys_out,
                                  uint32_t *counts_out, uint32_t *qualified_out) {
@@ -1673,99 +1683,47 @@ extern "C" int oi_similar_groups(oi_index *idx, const float *qv, uint32_t B, con
                (unsigned long long)B * spec->n_keys, OI_MAX_GROUP_CELLS);
     OI_REQUIRE(B == 0 || (qv && records_out), "similar_groups: null buffer");
     OI_REQUIRE(B == 0 || spec->top == 0 || (keys_out && counts_out), "similar_groups: null buffer (keys_out / counts_out with top=%u)", spec->top);
-    if (!idx) { oi_set_error("similar_groups: null index"); return OI_ERR_INVALID_ARG; }
-    if (!idx->rows && !idx->rows_bf16) { oi_set_error("similar_groups: the index has no embeddings (oi_index_set_embeddings)"); return OI_ERR_STATE; }
-    oi_ctx *ctx = idx->ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (!idx->signals.p) { oi_set_error("similar_groups: the index has no signals (oi_index_set_signals)"); return OI_ERR_STATE; }
-    if (!idx->doc_attrs.p) {
-        oi_set_error("similar_groups: the key axis needs the index's doc attributes (oi_index_set_doc_attrs)");
-        return OI_ERR_STATE;
-    }
+    std::unique_lock<std::mutex> g;
+    OI_CHECK(similar_check_state("similar_groups", idx, true, "the key axis needs", g));
     if (B == 0) return OI_OK;
-    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    OI_HIP_CHECK(hipSetDevice(idx->ctx->device));
     if (location == OI_DEVICE)
         return oi_launch_similar_groups(idx, qv, B, *spec, thresholds, reinterpret_cast<const uint4 *>(filters), records_out, keys_out,
                                         counts_out, qualified_out);
-    hipStream_t st = ctx->stream;
     const size_t per_q = spec->top ? spec->top : spec->n_keys; // records (and, ranked, keys) per query
-    const size_t vb = (sizeof(float) * (size_t)B * idx->dim + 15) & ~(size_t)15, fb = filters ? sizeof(oi_doc_filter) * (size_t)B : 0;
-    const size_t tb = thresholds ? (sizeof(float) * (size_t)B + 15) & ~(size_t)15 : 0;
     const size_t rb = sizeof(oi_social_counters) * (size_t)B * per_q;
     const size_t kb = spec->top ? sizeof(uint32_t) * (size_t)B * per_q : 0, cb = spec->top ? sizeof(uint32_t) * (size_t)B : 0;
-    DevBuf &w = ctx->buf("groups_io"); // [vectors | filters | thresholds | records | keys | counts | qualified]
-    OI_CHECK(w.ensure(vb + fb + tb + rb + kb + 2 * cb + 64));
-    uint8_t *d = w.as<uint8_t>();
-    OI_HIP_CHECK(hipMemcpyAsync(d, qv, sizeof(float) * (size_t)B * idx->dim, hipMemcpyHostToDevice, st));
-    if (filters) OI_HIP_CHECK(hipMemcpyAsync(d + vb, filters, fb, hipMemcpyHostToDevice, st));
-    if (thresholds) OI_HIP_CHECK(hipMemcpyAsync(d + vb + fb, thresholds, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, st));
-    oi_social_counters *d_rec = reinterpret_cast<oi_social_counters *>(d + vb + fb + tb);
-    uint32_t *d_keys = reinterpret_cast<uint32_t *>(d + vb + fb + tb + rb), *d_counts = d_keys + (size_t)B * per_q, *d_qual = d_counts + B;
-    OI_CHECK(oi_launch_similar_groups(idx, reinterpret_cast<const float *>(d), B, *spec,
-                                      thresholds ? reinterpret_cast<const float *>(d + vb + fb) : nullptr,
-                                      filters ? reinterpret_cast<const uint4 *>(d + vb) : nullptr, d_rec, spec->top ? d_keys : nullptr,
-                                      spec->top ? d_counts : nullptr, spec->top ? d_qual : nullptr));
-    OI_HIP_CHECK(hipMemcpyAsync(records_out, d_rec, rb, hipMemcpyDeviceToHost, st));
-    if (spec->top) {
-        OI_HIP_CHECK(hipMemcpyAsync(keys_out, d_keys, kb, hipMemcpyDeviceToHost, st));
-        OI_HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, cb, hipMemcpyDeviceToHost, st));
-        if (qualified_out) OI_HIP_CHECK(hipMemcpyAsync(qualified_out, d_qual, cb, hipMemcpyDeviceToHost, st));
-    }
-    OI_HIP_CHECK(hipStreamSynchronize(st));
-    return OI_OK;
+    return similar_staged(idx, "groups_io", qv, B, thresholds, filters, {{records_out, rb}, {keys_out, kb}, {counts_out, cb}, {qualified_out, cb}},
+                          [&](const float *q, const float *t, const uint4 *f, uint8_t *o) {
+                              uint32_t *d_keys = reinterpret_cast<uint32_t *>(o + rb), *d_counts = d_keys + (size_t)B * per_q, *d_qual = d_counts + B;
+                              return oi_launch_similar_groups(idx, q, B, *spec, t, f, reinterpret_cast<oi_social_counters *>(o),
+                                                              spec->top ? d_keys : nullptr, spec->top ? d_counts : nullptr, spec->top ? d_qual : nullptr);
+                          });
 }
 
-// ---------------------------------------------------------------- similarity share (cosine_share.hip)
-// The checks of oi_similar_summary in its order, before the first HIP call.  Never captured.  labels_out may be null.
+// similarity share (cosine_share.hip).  labels_out may be null.
 extern "C" int oi_similar_share(oi_index *idx, const float *qv, uint32_t B, const oi_summary_spec *spec, const float *thresholds,
                                 const oi_doc_filter *filters, int location, oi_social_counters *out, uint32_t *labels_out) {
     OI_REQUIRE(spec, "similar_share: null spec");
-    OI_REQUIRE(thresholds || spec->threshold == spec->threshold, "similar_share: threshold is NaN (and no thresholds array)");
-    OI_REQUIRE(spec->n_buckets >= 1 && spec->n_buckets <= OI_MAX_VOLUME_BUCKETS, "similar_share: n_buckets=%u outside [1,%u]",
-               spec->n_buckets, OI_MAX_VOLUME_BUCKETS);
-    OI_REQUIRE(spec->bucket_width != 0 || spec->n_buckets == 1, "similar_share: bucket_width=0 (no time axis) with n_buckets=%u",
-               spec->n_buckets);
-    OI_REQUIRE(B <= 4096, "similar_share: n_queries=%u outside [0,4096]", B);
-    OI_REQUIRE((uint64_t)B * spec->n_buckets <= OI_MAX_SUMMARY_CELLS, "similar_share: n_queries * n_buckets = %llu cells, more than %u",
-               (unsigned long long)B * spec->n_buckets, OI_MAX_SUMMARY_CELLS);
+    OI_CHECK(similar_check_spec("similar_share", spec->threshold, thresholds, true, spec->n_buckets, spec->bucket_width, B, OI_MAX_SUMMARY_CELLS));
     OI_REQUIRE(B == 0 || (qv && out), "similar_share: null buffer");
-    if (!idx) { oi_set_error("similar_share: null index"); return OI_ERR_INVALID_ARG; }
-    if (!idx->rows && !idx->rows_bf16) { oi_set_error("similar_share: the index has no embeddings (oi_index_set_embeddings)"); return OI_ERR_STATE; }
-    oi_ctx *ctx = idx->ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (!idx->signals.p) { oi_set_error("similar_share: the index has no signals (oi_index_set_signals)"); return OI_ERR_STATE; }
-    if ((filters || spec->bucket_width) && !idx->doc_attrs.p) {
-        oi_set_error("similar_share: filters / time buckets need the index's doc attributes (oi_index_set_doc_attrs)");
-        return OI_ERR_STATE;
-    }
-    OI_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
+    std::unique_lock<std::mutex> g;
+    OI_CHECK(similar_check_state("similar_share", idx, true, (filters || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
+    OI_HIP_CHECK(hipSetDevice(idx->ctx->device));
     const size_t lb = labels_out ? sizeof(uint32_t) * (size_t)idx->n_docs : 0;
     if (B == 0) { // no query: no row has a candidate
-        if (lb && location == OI_DEVICE) OI_HIP_CHECK(hipMemsetAsync(labels_out, 0xFF, lb, st));
+        if (lb && location == OI_DEVICE) OI_HIP_CHECK(hipMemsetAsync(labels_out, 0xFF, lb, idx->ctx->stream));
         else if (lb) memset(labels_out, 0xFF, lb);
         return OI_OK;
     }
     if (location == OI_DEVICE)
         return oi_launch_similar_share(idx, qv, B, *spec, thresholds, reinterpret_cast<const uint4 *>(filters), out, labels_out);
-    const size_t vb = (sizeof(float) * (size_t)B * idx->dim + 15) & ~(size_t)15, fb = filters ? sizeof(oi_doc_filter) * (size_t)B : 0;
-    const size_t tb = thresholds ? (sizeof(float) * (size_t)B + 15) & ~(size_t)15 : 0;
     const size_t ob = sizeof(oi_social_counters) * (size_t)B * spec->n_buckets;
-    DevBuf &w = ctx->buf("share_io"); // [vectors | filters | thresholds | records | labels]
-    OI_CHECK(w.ensure(vb + fb + tb + ob + lb + 64));
-    uint8_t *d = w.as<uint8_t>();
-    OI_HIP_CHECK(hipMemcpyAsync(d, qv, sizeof(float) * (size_t)B * idx->dim, hipMemcpyHostToDevice, st));
-    if (filters) OI_HIP_CHECK(hipMemcpyAsync(d + vb, filters, fb, hipMemcpyHostToDevice, st));
-    if (thresholds) OI_HIP_CHECK(hipMemcpyAsync(d + vb + fb, thresholds, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, st));
-    oi_social_counters *d_out = reinterpret_cast<oi_social_counters *>(d + vb + fb + tb);
-    uint32_t *d_labels = lb ? reinterpret_cast<uint32_t *>(d + vb + fb + tb + ob) : nullptr;
-    OI_CHECK(oi_launch_similar_share(idx, reinterpret_cast<const float *>(d), B, *spec,
-                                     thresholds ? reinterpret_cast<const float *>(d + vb + fb) : nullptr,
-                                     filters ? reinterpret_cast<const uint4 *>(d + vb) : nullptr, d_out, d_labels));
-    OI_HIP_CHECK(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st));
-    if (lb) OI_HIP_CHECK(hipMemcpyAsync(labels_out, d_labels, lb, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipStreamSynchronize(st));
-    return OI_OK;
+    return similar_staged(idx, "share_io", qv, B, thresholds, filters, {{out, ob}, {labels_out, lb}},
+                          [&](const float *q, const float *t, const uint4 *f, uint8_t *o) {
+                              return oi_launch_similar_share(idx, q, B, *spec, t, f, reinterpret_cast<oi_social_counters *>(o),
+                                                             lb ? reinterpret_cast<uint32_t *>(o + ob) : nullptr);
+                          });
 }
 
 // ---------------------------------------------------------------- diagnostics of the bf16 screen

@@ -211,7 +211,7 @@ struct GrSum {
     __device__ __forceinline__ void add(uint64_t cell, const Rec sg) const { sm_add(cells, cell, sg); }
 
     static constexpr uint32_t CELL_WORDS = SM_CELL_WORDS;
-    static constexpr bool KEY_AXIS = true;
+    static constexpr bool KEY_AXIS = true, EXCLUSIVE = false;
     static constexpr VoNames NAMES = {"groups_state", "groups_runs", "groups_q_rounded", "groups_q_bf16",
                                       "groups", "groups_band", "groups_exact", "groups_fallback"};
     static const float *thr_block(const float *thr_q, uint32_t q0) { return thr_q ? thr_q + q0 : nullptr; }

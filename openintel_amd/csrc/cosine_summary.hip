@@ -71,7 +71,7 @@ struct SmSum {
     __device__ __forceinline__ void add(uint64_t cell, const Rec sg) const { sm_add(cells, cell, sg); }
 
     static constexpr uint32_t CELL_WORDS = SM_CELL_WORDS;
-    static constexpr bool KEY_AXIS = false;
+    static constexpr bool KEY_AXIS = false, EXCLUSIVE = false;
     static constexpr VoNames NAMES = {"summary_state", "summary_runs", "summary_q_rounded", "summary_q_bf16",
                                       "summary", "summary_band", "summary_exact", "summary_fallback"};
     static const float *thr_block(const float *thr_q, uint32_t q0) { return thr_q ? thr_q + q0 : nullptr; }

@@ -32,7 +32,7 @@ struct VoCount {
     __device__ __forceinline__ void add(uint64_t cell, Rec) const { atomicAdd(&cells[cell], 1u); }
 
     static constexpr uint32_t CELL_WORDS = 1;
-    static constexpr bool KEY_AXIS = false;
+    static constexpr bool KEY_AXIS = false, EXCLUSIVE = false;
     static constexpr VoNames NAMES = {"volume_state", "volume_runs", "volume_q_rounded", "volume_q_bf16",
                                       "volume", "volume_band", "volume_exact", "volume_fallback"};
     static float thr_block(float t, uint32_t) { return t; }

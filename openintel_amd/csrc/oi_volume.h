@@ -1,6 +1,7 @@
-// oi_volume.h -- the threshold family: oi_similar_volume (cosine_volume.hip) and oi_similar_summary
-// (cosine_summary.hip) are ONE set of kernels and one host driver, written here once as templates over a TALLY:
-// what a document that passes the three clauses (filter, bucket, sim >= t_q) adds to its (query, bucket) cell.
+// oi_volume.h -- the threshold family: oi_similar_volume (cosine_volume.hip), oi_similar_summary
+// (cosine_summary.hip, 4.11), oi_similar_groups (cosine_groups.hip, 4.12) and oi_similar_share (cosine_share.hip, 4.13) are ONE set
+// of kernels and one host driver, written here once as templates over a TALLY: what a document that passes the three clauses
+// (filter, bucket, sim >= t_q) adds to its (query, bucket) cell.
 //
 // A tally is a small struct passed to the kernels by value (it sits in the kernel arguments where the output pointer would):
 //   device   uint32_t *cells;                    the call's cells, CELL_WORDS u32 each (the driver sets and slices it)
@@ -14,9 +15,22 @@
 //            KEY_AXIS                             false: clause 2 is the time bucket of the row's stamp (vo_bucket).  true: it is the
 //                                                 KEY of the row's group (vo_key), and the kernels' three u32 arguments
 //                                                 origin / width / n_buckets carry key_mask / its shift / n_keys
+//            EXCLUSIVE                            false: every (query, row) pair is decided on its own (load / add above).  true:
+//                                                 a row enters ONE cell, that of its best candidate query -- see below
 //            Thr thr_block(Thr, q0)               the threshold argument of the launch that begins at query q0
 //            int finish(ctx, n_cells, out)        cells -> the caller's array, on the ctx stream
-// VoCount (cosine_volume.hip), SmSum (cosine_summary.hip) and GrSum (cosine_groups.hip, the key axis) are the three there are.
+// An EXCLUSIVE tally has no load / add.  The kernels compare a row's candidates first (the stream: a sole surviving bit at or
+// above hi is proven, every other bit goes to the band; the band: every candidate pair is published, a later pass picks the
+// row's best; the exact route: a running best pair per row; the fallback's clear takes the labels too) and call
+//   device   void assign(q, row, attrs, origin, width, n_buckets)   row is q's: clause 2, then the cell (the stream's proven rows)
+//            void assign_cell(cell, q, row)                          the same with clause 2 already evaluated (the exact route)
+//            void publish(pair, q, row, sim, candidate)              pair of the band kernel: every pair of the launch, once
+//            uint32_t *labels;                                       [n_rows] or null: the query a row went to, VO_NO_QUERY
+//   host     int begin(ctx, n_rows, screen)       before the routes: its per-call presets and workspaces
+//            int commit(ctx, band, state, B, long_list, n_long, attrs, spec)   behind the band kernel, inside its profile span
+// and its stream route takes a batch of at most 64 queries (one launch: a row's candidates must all meet in one tile).
+// VoCount (cosine_volume.hip), SmSum (cosine_summary.hip), GrSum (cosine_groups.hip, the key axis) and ShTally (cosine_share.hip,
+// the exclusive one) are the four there are.
 // The stream kernel's tile pipeline (query block, tile ownership, the bf16 copy ring, the score test) is oi_screen_tile.h's, shared
 // with cosine_copy_screen; its own are the two thresholds and the tallying epilogue with the band staging.
 #pragma once
@@ -35,6 +49,7 @@
 #define VO_GATE 0
 #define VO_OVERFLOW 1
 #define VO_BAND_CNT 2
+#define VO_NO_QUERY 0xFFFFFFFFu      // an exclusive tally's label of a row that no query takes
 // dynamic LDS of vo_stream_kernel: the four rings, then the waves' staged band pairs
 constexpr size_t vo_lds(int nbuf) { return oi_ring_lds(nbuf) + 4 * OI_STAGE * 8; }
 
@@ -157,29 +172,69 @@ __global__ __launch_bounds__(256, 1) void vo_stream_kernel(
             if (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull) {
                 m = oi_tile_mask_ragged(m, n_rows - row0, lh);
                 if constexpr (FILT) m = oi_filter_tile<NQT>(m, filt, attrs, row0, lh, li);
-                // per row with a bit left: its bucket (the stamp is loaded for such rows only) and the long-row bitmap; then
-                // a proven hit is tallied (the row's record loaded at its first one), a band pair keeps its bit
                 uint32_t mb = 0;
+                if constexpr (Tally::EXCLUSIVE) {
+                    // The launch holds the WHOLE batch (vo_launch_similar screens an exclusive tally only at B <= 64, in one
+                    // launch): a sole bit proves nothing about the queries of another slice.  So q_base is 0 here and 32 t + li
+                    // is the query's own number, as the label and the cell want it.
+                    static_assert(NQT <= 2, "an exclusive batch is at most 64 queries");
+                    if (long_bitmap) { // (the bound does not hold for a long row: the band kernel scores it against every query)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    if (m & (0x00010001u << r)) {
-                        const uint32_t row = oi_tile_row((uint32_t)row0, r, lh);
-                        uint32_t b = 0;
-                        bool ok = true;
-                        if constexpr (Tally::KEY_AXIS) ok = vo_key(attrs[row].x, origin, width, n_buckets, &b);
-                        else if (width != 0u) ok = vo_bucket(attrs[row].y, origin, width, n_buckets, &b);
-                        if (long_bitmap && ((long_bitmap[row >> 5] >> (row & 31)) & 1u)) ok = false; // (the bound does not hold: band kernel)
-                        if (ok) {
-                            bool have = false;
-                            typename Tally::Rec rec{};
+                        for (int r = 0; r < 16; ++r)
+                            if (m & (0x00010001u << r)) {
+                                const uint32_t row = oi_tile_row((uint32_t)row0, r, lh);
+                                if ((long_bitmap[row >> 5] >> (row & 31)) & 1u) m &= ~(0x00010001u << r);
+                            }
+                    }
+                    // A row's bits lie in the 32 lanes of its half-wave (lane = li + 32 lh) and the NQT tiles: one ballot per
+                    // (tile, register) counts them for both halves.  ONE bit, at or above hi: a proven sole candidate (every
+                    // other query is proven below its threshold), assigned here.  Else every bit of the row goes to the band.
 #pragma unroll
-                            for (int t = 0; t < NQT; ++t)
-                                if (m & (1u << (16 * t + r))) {
-                                    if (acc[t][r] >= hi[t]) {
-                                        if (!have) { rec = tally.load(row); have = true; }
-                                        tally.add((uint64_t)(32u * t + li) * n_buckets + b, rec);
-                                    } else mb |= 1u << (16 * t + r);
-                                }
+                    for (int r = 0; r < 16; ++r) {
+                        const uint32_t rbits = m & (0x00010001u << r);
+                        uint32_t cnt = 0;
+#pragma unroll
+                        for (int t = 0; t < NQT; ++t) {
+                            const uint64_t bal = __builtin_amdgcn_ballot_w64((rbits & (1u << (16 * t + r))) != 0u);
+                            cnt += (uint32_t)__builtin_popcount(lh ? (uint32_t)(bal >> 32) : (uint32_t)bal);
+                        }
+                        if (rbits) {
+                            bool proven = false;
+                            if (cnt == 1u) {
+#pragma unroll
+                                for (int t = 0; t < NQT; ++t)
+                                    if ((rbits & (1u << (16 * t + r))) && acc[t][r] >= hi[t]) {
+                                        tally.assign(32u * t + li, oi_tile_row((uint32_t)row0, r, lh), attrs, origin, width, n_buckets);
+                                        proven = true;
+                                    }
+                            }
+                            if (!proven) mb |= rbits;
+                        }
+                    }
+                } else {
+                    // per row with a bit left: its bucket (the stamp is loaded for such rows only) and the long-row bitmap; then
+                    // a proven hit is tallied (the row's record loaded at its first one), a band pair keeps its bit
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        if (m & (0x00010001u << r)) {
+                            const uint32_t row = oi_tile_row((uint32_t)row0, r, lh);
+                            uint32_t b = 0;
+                            bool ok = true;
+                            if constexpr (Tally::KEY_AXIS) ok = vo_key(attrs[row].x, origin, width, n_buckets, &b);
+                            else if (width != 0u) ok = vo_bucket(attrs[row].y, origin, width, n_buckets, &b);
+                            if (long_bitmap && ((long_bitmap[row >> 5] >> (row & 31)) & 1u)) ok = false; // (the bound does not hold: band kernel)
+                            if (ok) {
+                                bool have = false;
+                                typename Tally::Rec rec{};
+#pragma unroll
+                                for (int t = 0; t < NQT; ++t)
+                                    if (m & (1u << (16 * t + r))) {
+                                        if (acc[t][r] >= hi[t]) {
+                                            if (!have) { rec = tally.load(row); have = true; }
+                                            tally.add((uint64_t)(32u * t + li) * n_buckets + b, rec);
+                                        } else mb |= 1u << (16 * t + r);
+                                    }
+                            }
                         }
                     }
                 }
@@ -278,7 +333,11 @@ __global__ __launch_bounds__(256) void vo_band_kernel(const float *__restrict__ 
         for (int u = 0; u < 4; ++u) {
             // (t_q is read ahead of the test: with the call inside the condition hipcc lays the whole kernel out differently)
             const float s = oi_wave_sum(a[u]), tq = tally.thr(q[u], thr);
-            if (lane == 0 && i0 + u < c && s >= tq) {
+            if constexpr (Tally::EXCLUSIVE) {
+                // every pair of the launch leaves its word for the commit; clause 2 is the assignment's
+                if (lane == 0 && i0 + u < c)
+                    tally.publish(i0 + u, q[u], row[u], s, s >= tq && (!filt || oi_doc_passes(filt[q[u]], attrs[row[u]])));
+            } else if (lane == 0 && i0 + u < c && s >= tq) {
                 uint32_t b = 0;
                 bool ok = true;
                 if (attrs) {
@@ -320,7 +379,12 @@ __global__ __launch_bounds__(256) void vo_exact_kernel(const void *__restrict__ 
             at = attrs[r];
             if (!vo_cell<Tally>(at, origin, width, n_buckets, &b)) continue; // (wave-uniform)
         }
-        const typename Tally::Rec rec = tally.load(r);
+        typename Tally::Rec rec{};
+        if constexpr (!Tally::EXCLUSIVE) rec = tally.load(r);
+        // the exclusive tally's running pair: replaced only on `>`, so ties keep the smallest q.  The sums are the same in every
+        // lane (a butterfly of commutative adds), so the pair is wave-uniform.  (-0 > +0 is false: the two tie, as their keys do.)
+        float best_s = 0.f;
+        uint32_t best_q = VO_NO_QUERY;
         for (uint32_t q0 = 0; q0 < n_queries; q0 += 4) {
             const float4 *y[4];
             float a[4];
@@ -341,10 +405,18 @@ __global__ __launch_bounds__(256) void vo_exact_kernel(const void *__restrict__ 
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const float s = oi_wave_sum(a[u]);
-                if (lane == 0 && q0 + u < n_queries && s >= tally.thr(q0 + u, thr) && (!filt || oi_doc_passes(filt[q0 + u], at)))
+                if constexpr (Tally::EXCLUSIVE) {
+                    if (q0 + u < n_queries && s >= tally.thr(q0 + u, thr) && (!filt || oi_doc_passes(filt[q0 + u], at)) &&
+                        (best_q == VO_NO_QUERY || s > best_s)) {
+                        best_s = s;
+                        best_q = q0 + u;
+                    }
+                } else if (lane == 0 && q0 + u < n_queries && s >= tally.thr(q0 + u, thr) && (!filt || oi_doc_passes(filt[q0 + u], at)))
                     tally.add((uint64_t)(q0 + u) * n_buckets + b, rec);
             }
         }
+        if constexpr (Tally::EXCLUSIVE)
+            if (lane == 0 && best_q != VO_NO_QUERY) tally.assign_cell((uint64_t)best_q * n_buckets + b, best_q, r);
     }
 }
 
@@ -355,6 +427,18 @@ __global__ __launch_bounds__(256) void vo_fallback_clear_kernel(uint32_t *cells,
                                                                 uint32_t *runs) {
     if ((state[VO_GATE] | state[VO_OVERFLOW]) == 0u) return;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (uint64_t)gridDim.x * blockDim.x) cells[i] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(runs, 1u);
+}
+// An exclusive tally's: the labels of the abandoned stream go too (labels may be null).  An overload, not one more parameter of
+// the kernel above: a template's parameter list is part of its instances' names, and the three that exist do not move.
+template <class Tally>
+__global__ __launch_bounds__(256) void vo_fallback_clear_kernel(uint32_t *cells, uint64_t words, uint32_t *labels, uint64_t n_rows,
+                                                                const uint32_t *__restrict__ state, uint32_t *runs) {
+    if ((state[VO_GATE] | state[VO_OVERFLOW]) == 0u) return;
+    const uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = i0; i < words; i += step) cells[i] = 0u;
+    if (labels)
+        for (uint64_t i = i0; i < n_rows; i += step) labels[i] = VO_NO_QUERY;
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(runs, 1u);
 }
 
@@ -428,7 +512,10 @@ static int vo_launch_similar(oi_index *idx, const float *d_q, uint32_t B, const 
         q = qr.as<float>();
     }
     const int mode = ctx->cosine_mode;
-    const bool screen = n > 0 && (mode == OI_COSINE_SCREEN || mode == OI_COSINE_SCREEN_COPY) && oi_index_screenable(idx) && idx->screen_copy.p;
+    // (an exclusive tally's stream takes the whole batch in one launch, so that a row's candidates all meet in one tile)
+    const bool screen = n > 0 && (!Tally::EXCLUSIVE || B <= 64u) && (mode == OI_COSINE_SCREEN || mode == OI_COSINE_SCREEN_COPY) &&
+                        oi_index_screenable(idx) && idx->screen_copy.p;
+    if constexpr (Tally::EXCLUSIVE) OI_CHECK(tally.begin(ctx, n, screen));
     if (n == 0) {
         // (nothing to tally)
     } else if (!screen) {
@@ -445,6 +532,7 @@ static int vo_launch_similar(oi_index *idx, const float *d_q, uint32_t B, const 
         float *eps2 = reinterpret_cast<float *>(qb.as<unsigned char>() + qb_bytes);
         OI_CHECK(oi_launch_screen_stage(ctx, q, B, dim, idx->max_row_norm.as<uint32_t>(), q16, eps2, state + VO_GATE));
         const uint32_t *lbm = idx->n_long ? idx->long_bitmap.as<uint32_t>() : nullptr;
+        const uint32_t *llist = idx->n_long ? idx->long_list.as<uint32_t>() : nullptr;
         uint32_t grid = 0, seg_cap = 0;
         oi_cosine_screen_geometry(ctx, n, &grid, &seg_cap); // (the persistent grid of the screens: 7/8 of the CUs)
         {
@@ -469,15 +557,22 @@ static int vo_launch_similar(oi_index *idx, const float *d_q, uint32_t B, const 
         {
             ProfScope ps(ctx, N.band);
             hipLaunchKernelGGL(vo_band_kernel<Tally>, dim3((uint32_t)ctx->num_cus * 4), dim3(256), 0, st, idx->rows, dim, q, B, thr,
-                               bb.as<uint64_t>(), VO_BAND_CAP, state, idx->n_long ? idx->long_list.as<uint32_t>() : nullptr, idx->n_long,
-                               d_filt, attrs, sp.stamp_origin, sp.bucket_width, sp.n_buckets, tally);
+                               bb.as<uint64_t>(), VO_BAND_CAP, state, llist, idx->n_long, d_filt, attrs, sp.stamp_origin, sp.bucket_width,
+                               sp.n_buckets, tally);
             OI_HIP_CHECK(hipGetLastError());
+            if constexpr (Tally::EXCLUSIVE) OI_CHECK(tally.commit(ctx, bb.as<uint64_t>(), state, B, llist, idx->n_long, attrs, sp));
         }
         {
             // the gated fallback: both launches exit at once unless the band overflowed or a query has no bound
             ProfScope ps(ctx, N.fallback);
-            hipLaunchKernelGGL(vo_fallback_clear_kernel<Tally>, dim3((uint32_t)std::min<uint64_t>((words + 255) / 256, 1024)), dim3(256), 0, st,
-                               tally.cells, words, state, rb.as<uint32_t>());
+            if constexpr (Tally::EXCLUSIVE) {
+                const uint64_t most = std::max<uint64_t>(words, tally.labels ? n : 0);
+                hipLaunchKernelGGL(vo_fallback_clear_kernel<Tally>, dim3((uint32_t)std::min<uint64_t>((most + 255) / 256, 1024)), dim3(256), 0,
+                                   st, tally.cells, words, tally.labels, n, state, rb.as<uint32_t>());
+            } else {
+                hipLaunchKernelGGL(vo_fallback_clear_kernel<Tally>, dim3((uint32_t)std::min<uint64_t>((words + 255) / 256, 1024)), dim3(256), 0,
+                                   st, tally.cells, words, state, rb.as<uint32_t>());
+            }
             OI_HIP_CHECK(hipGetLastError());
             OI_CHECK(vo_launch_exact<false>(ctx, idx->rows, n, dim, q, B, thr, state, d_filt, attrs, sp, tally));
         }

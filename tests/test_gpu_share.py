@@ -639,3 +639,63 @@ def test_routes_agree_bit_for_bit():
         assert x[0].tobytes() == a[0].tobytes() and x[1].tobytes() == a[1].tobytes()
     assert (ref[1][stamp == 4] == NO_LABEL).all() and (ref[1][stamp < 4] != NO_LABEL).any()
     view.close()
+
+
+# ------------------------------------------------------------------ 11. what the share has in common with the family's other calls
+def test_calls_of_the_family_interleave_on_one_context():
+    """The band buffer is the family's, the state, best and the pairs' keys are per call: share (labels), summary, share (no
+    labels, HIGHER thresholds: a best key left over from the first call would outrank every pair of this one), groups, volume,
+    share (labels) on ONE context each give the bytes of the same call on a fresh context."""
+    dim, n, B = 384, 2080, 33                                      # two query tiles
+    rows, q = _ints(n, dim, B, seed=111)
+    S = _exact_scores(rows, q)
+    t = ((np.arange(B) % 3) * 20 - 2.5).astype(np.float32)         # -2.5, 17.5, 37.5: most rows have several candidates
+    t2 = t + np.float32(20.0)                                      # fewer candidates per row, still several for many
+    sig = _signals(n, 111)
+    group = (np.arange(n) % 19).astype(np.uint32)                  # keys 16 .. 18 belong to no cell
+    stamp = np.zeros(n, np.uint32)
+    calls = [("share+", lambda i: i.similar_share(q, t, labels=True)),
+             ("summary", lambda i: i.similar_summary(q, t)),
+             ("share", lambda i: (i.similar_share(q, t2), np.zeros(0, np.uint32))),
+             ("groups", lambda i: i.similar_groups(q, t, 0x1F, 16)),
+             ("volume", lambda i: i.similar_volume(q, 17.5)),
+             ("share+", lambda i: i.similar_share(q, t, labels=True))]
+    ctx = _ctx()
+    idx = _index(ctx, rows, sig, group, stamp)
+    refs = {"share+": _ref(S, t, sig), "share": _ref(S, t2, sig)}
+    moved = (refs["share"][1] != NO_LABEL) & (refs["share"][1] != refs["share+"][1])
+    assert moved.any()                         # rows whose winner at t is no candidate at t2, and which another query takes
+    for name, call in calls:
+        fresh = _ctx()
+        view = idx.view(fresh)
+        if name.startswith("share"):
+            got, ran, fill = _ran(ctx, lambda: call(idx))
+            alone, ran_alone, fill_alone = _ran(fresh, lambda: call(view))
+            assert ran == ran_alone == {"share", "share_band"} and fill == fill_alone > 0, (name, ran, ran_alone, fill, fill_alone)
+            _same(got[0], refs[name][0])
+            if name == "share+":
+                _same_both(got, refs[name])
+            assert got[0].tobytes() == alone[0].tobytes() and got[1].tobytes() == alone[1].tobytes(), name
+        else:
+            got, alone = call(idx), call(view)
+            assert got.dtype == alone.dtype and got.shape == alone.shape and got.tobytes() == alone.tobytes(), name
+            assert got.tobytes() != bytes(got.nbytes), name        # (it found something)
+        view.close()
+
+
+def test_the_gated_fallback_without_labels_then_a_screened_call():
+    """The fallback's clear has no label array to reset (labels_out == NULL); the next call on the context is screened and right."""
+    ctx = _ctx()
+    dim, n, B = 384, 3000, 40
+    rows, q = _ints(n, dim, B, seed=90)
+    sig = _signals(n, 90)
+    idx = _index(ctx, rows, sig)
+    huge = q.copy()
+    huge[4] *= np.float32(2.0 ** 60)                               # a norm the screen has no bound for; the scores stay exact
+    t = np.full(B, 10.5, np.float32)
+    got, ran, _ = _ran(ctx, lambda: (idx.similar_share(huge, t), np.zeros(0, np.uint32)))
+    _same(got[0], _ref(_exact_scores(rows, huge), t, sig)[0])
+    assert "share_exact" in ran, ran
+    got, ran, _ = _ran(ctx, lambda: idx.similar_share(q, t, labels=True))
+    _same_both(got, _ref(_exact_scores(rows, q), t, sig))
+    assert "share" in ran and "share_exact" not in ran, ran

@@ -39,7 +39,7 @@ sys.path.insert(0, ROOT)
 from openintel_amd import build as oib  # noqa: E402
 
 DMA_FILES = ["cosine_prefilter", "cosine_screen_copy", "cosine_screen_i8", "cosine_split", "cosine_bf16", "cosine_ksplit",
-             "cosine_volume", "cosine_summary"]
+             "cosine_volume", "cosine_summary", "cosine_groups", "cosine_share"]
 ABL = "-DOI_ABLATION"
 
 
