@@ -64,6 +64,11 @@ class HipContext:
         f, n = self.profile_read("spec_state")
         return int(f), int(n)
 
+    def screen_width(self):
+        """(workgroups of the widest screen launch of the last screened search, the device's CUs)."""
+        w, cus = self.profile_read("screen_width")
+        return int(w), int(cus)
+
     def set_graph_replay(self, enable: bool) -> None:
         """Capture repeated device-buffer query calls into hipGraphs and replay them with one launch (oi_set_graph_replay):
         same kernels, same results, ~0.3 ms less host time per call.  The caller keeps using the same buffers."""

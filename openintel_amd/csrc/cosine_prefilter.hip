@@ -524,6 +524,17 @@ void oi_cosine_screen_geometry(const oi_ctx *ctx, uint64_t n_rows, uint32_t *n_s
     *n_segs = (uint32_t)grid;
     *seg_cap = (uint32_t)((quads + grid - 1) / grid) * 4 * OI_TILE_ROWS;
 }
+// The same geometry at a width the caller chooses.  The int8 screen is not HBM-bound at 7/8 of the CUs, so its
+// chunks take every CU when nothing else wants one while they run (search.hip: plan_search, screen_wgs).  Everything sized by the
+// width is sized for num_cus segments: the state words, the segment counts' stride and the pool's rounding slack (search.hip).
+void oi_cosine_screen_geometry(const oi_ctx *ctx, uint64_t n_rows, uint32_t wgs, uint32_t *n_segs, uint32_t *seg_cap) {
+    const uint64_t n_tiles = (n_rows + OI_TILE_ROWS - 1) / OI_TILE_ROWS;
+    const uint64_t quads = (n_tiles + 3) / 4;
+    const uint64_t cus = std::min<uint64_t>(std::max<uint64_t>(1, wgs), std::max<uint64_t>(1, (uint64_t)ctx->num_cus));
+    const uint64_t grid = quads < cus ? (quads ? quads : 1) : cus;
+    *n_segs = (uint32_t)grid;
+    *seg_cap = (uint32_t)((quads + grid - 1) / grid) * 4 * OI_TILE_ROWS;
+}
 
 int oi_launch_row_norm_classes(oi_ctx *ctx, const float *rows, uint64_t n, uint32_t dim, float X0, float E0, uint32_t *cls,
                                uint32_t *bitmap, uint32_t *list, uint32_t cap) {

@@ -30,7 +30,8 @@
 // rescored whatever happens, as before.  A query without a bound (staging) has m2 = inf: it never gets a threshold, overflows and
 // opens the gate like the bf16 screen's.
 //
-// Kernel shape: cosine_copy_screen's.  One persistent workgroup on 7/8 of the CUs, 4 waves, a wave holds all 64 queries over the
+// Kernel shape: cosine_copy_screen's.  One persistent workgroup per CU (every CU when nothing runs beside the chunks, 7/8 of them
+// otherwise: search.hip, screen_wgs), 4 waves, a wave holds all 64 queries over the
 // whole K as i8 hi / lo B operands (384 VGPRs at d = 768, as the bf16 screen), owns whole 32-row tiles and streams them through its
 // own LDS ring of 4 KiB slots (32 rows x 128 i8) with buffer_load ... lds, ordered by counted s_waitcnt vmcnt.  Per 32 k of a tile:
 // one ds_read_b128, 2 NQT v_mfma_i32_32x32x32_i8 (the cycles of the bf16 32x32x16: the matrix time per tile is the bf16 screen's,
@@ -640,13 +641,16 @@ static int launch_i8_screen(oi_ctx *ctx, const uint8_t *rows, const float *meta,
 }
 
 // All queries of a batch over rows [row_begin, row_end) of the index's int8 copy (n_rows_total rows).  qi8 / qf: staged by
-// oi_launch_screen_stage_i8.  Pool geometry: the bf16 screens' (oi_cosine_screen_geometry).
+// oi_launch_screen_stage_i8.  Pool geometry: the bf16 screens' (oi_cosine_screen_geometry), at `wgs` workgroups when the plan
+// chose a width (0: theirs).
 int oi_launch_cosine_screen_i8_chunk(oi_ctx *ctx, const uint8_t *i8_copy, uint64_t n_rows_total, uint64_t row_begin, uint64_t row_end,
                                      uint32_t dim, const int8_t *qi8, const float *qf, uint32_t n_queries, uint32_t doc_id_base,
-                                     PoolView &pool) {
+                                     PoolView &pool, uint32_t wgs) {
     OI_REQUIRE(oi_cosine_screen_supported(dim), "cosine screen (int8): dim %u not instantiated (384, 768)", dim);
     OI_REQUIRE(row_end <= n_rows_total, "cosine screen (int8): rows past the copy");
-    oi_cosine_screen_geometry(ctx, row_end > row_begin ? row_end - row_begin : 0, &pool.n_segs, &pool.seg_cap);
+    const uint64_t chunk_rows = row_end > row_begin ? row_end - row_begin : 0;
+    if (wgs) oi_cosine_screen_geometry(ctx, chunk_rows, wgs, &pool.n_segs, &pool.seg_cap);
+    else oi_cosine_screen_geometry(ctx, chunk_rows, &pool.n_segs, &pool.seg_cap);
     OI_REQUIRE(pool.n_segs <= pool.seg_cnt_stride && pool.carry_cap + (uint64_t)pool.n_segs * pool.seg_cap <= pool.stride,
                "cosine screen (int8): chunk does not fit the candidate pool");
     if (row_end <= row_begin || n_queries == 0) return OI_OK;

@@ -137,6 +137,7 @@ struct oi_ctx {
     // cosine kernel and the selects launched meanwhile exit at once unless *run_gate is nonzero
     const uint32_t *run_gate = nullptr;
     const uint32_t *last_screen_gate = nullptr; // the gate word of the last screened search (diagnostics)
+    uint32_t last_screen_wgs = 0;               // workgroups of the widest screen launch of the last screened search (diagnostics)
     std::map<std::string, std::vector<ProfSpan>> prof;
     std::vector<hipEvent_t> event_pool;
     bool use_graphs = false;          // oi_set_graph_replay
@@ -379,6 +380,8 @@ inline bool oi_index_screenable(const oi_index *idx) {
     return idx->rows && !idx->rows_bf16 && idx->screen_ok && oi_cosine_screen_supported(idx->dim);
 }
 void oi_cosine_screen_geometry(const oi_ctx *ctx, uint64_t n_rows, uint32_t *n_segs, uint32_t *seg_cap);
+// ... at a width the caller chooses: at most `wgs` workgroups, 1 <= wgs <= ctx->num_cus (the plan's screen_wgs)
+void oi_cosine_screen_geometry(const oi_ctx *ctx, uint64_t n_rows, uint32_t wgs, uint32_t *n_segs, uint32_t *seg_cap);
 int oi_launch_row_norm_max(oi_ctx *ctx, const float *rows, uint64_t n, uint32_t dim, uint32_t *max_bits);
 int oi_launch_screen_stage(oi_ctx *ctx, const float *d_queries, uint32_t n_queries, uint32_t dim,
                            const uint32_t *max_norm_bits, uint16_t *q_bf16, float *eps2, uint32_t *gate);
@@ -397,7 +400,8 @@ int oi_launch_screen_stage_i8(oi_ctx *ctx, const float *d_queries, uint32_t n_qu
 // (q_bf16 / eps2 set: the same launch also writes what oi_launch_screen_stage writes -- the int8 route stages once)
 int oi_launch_cosine_screen_i8_chunk(oi_ctx *ctx, const uint8_t *i8_copy, uint64_t n_rows_total, uint64_t row_begin, uint64_t row_end,
                                      uint32_t dim, const int8_t *qi8, const float *qf, uint32_t n_queries, uint32_t doc_id_base,
-                                     PoolView &pool);
+                                     PoolView &pool, uint32_t wgs = 0);
+// (wgs: the launch's width in workgroups, 0 = the screens' 7/8 of the CUs)
 // the bf16 rescreen: every key of pool's carry (an int8 survivor) becomes its bf16 screen key, in place
 int oi_launch_rescreen_bf16(oi_ctx *ctx, const uint16_t *copy_rows, uint64_t n_rows, uint32_t dim, uint32_t doc_id_base,
                             const uint16_t *q_bf16, uint32_t n_queries, const PoolView &pool);

@@ -15,6 +15,7 @@ struct Knobs {
     uint64_t spec_growth = env_int("OI_SPEC_GROWTH", 128, 2), spec_first_div = env_int("OI_SPEC_FIRST_DIV", 4, 1);
     uint32_t bm25_first_div = env_int("OI_BM25_FIRST_DIV", 8, 1);
     bool screen_no_round = env_set("OI_SCREEN_NO_ROUND"), no_spec = env_set("OI_NO_SPEC"), no_overlap = env_set("OI_NO_OVERLAP");
+    bool bm25_beside_last = env_set("OI_BM25_BESIDE_LAST"), screen_i8_narrow = env_set("OI_SCREEN_I8_NARROW");
     bool bm25_early = env_set("OI_BM25_EARLY"), small_gemv = env_set("OI_SMALL_BATCH_GEMV"), bm25_two_phase = env_set("OI_BM25_TWO_PHASE");
     // the first-generation cosine / select kernels have no screen in front of them
     bool exact_only = env_set("OI_COSINE_V1") || env_set("OI_SELECT_V1");
@@ -72,6 +73,8 @@ uint64_t oi_first_chunk_rows(uint32_t depth) {
 // (cosine_prefilter.hip: oi_cosine_screen_geometry) -- so that no wave of the two short first launches runs one tile more than
 // the others (32000 rows = 1000 tiles on 896 waves: 104 waves with two tiles; 256000 rows: 9.1 per wave, i.e. 10 rounds).
 // Chunk k is 8^k times the first and keeps the property.  OI_SCREEN_NO_ROUND=1 (A/B): as before.
+// The round stays that of 7/8 of the CUs where the int8 route's chunks take every CU (plan_search, screen_wgs): the first chunk is
+// the sample the thresholds come from and must not move, and its 224 quads are one tile per wave at either width.
 uint64_t oi_screen_first_chunk_rows(const oi_ctx *ctx, uint32_t depth) {
     uint64_t rows = oi_first_chunk_rows(depth);
     const uint64_t round = 32ull * 4 * std::max<uint64_t>(1, (uint64_t)ctx->num_cus * 7 / 8);
@@ -131,7 +134,12 @@ struct Plan {
     uint32_t pf_carry = 4096;
     bool spec = false; // speculative screen thresholds
     std::vector<Chunk> screen_chunks; // the screen routes' schedule
-    bool overlap = false, late_fork = false; // the BM25 leg on the side stream; forked in before the screen's last chunk
+    // the BM25 leg on the side stream; late_fork: forked in at the screen's last chunk -- beside it, or (tail_fork, the int8 route)
+    // behind it, beside the cosine leg's tail
+    bool overlap = false, late_fork = false, tail_fork = false;
+    // workgroups of an int8 screen launch: every CU when no other kernel runs beside the chunks, 0 = the screens' 7/8 of the
+    // CUs (oi_cosine_screen_geometry).  The bf16 copy, f32-stream and threshold-family kernels are HBM-bound at 7/8 and keep it.
+    uint32_t screen_wgs = 0;
 };
 bool screened(CosRoute c) { return c == CosRoute::screen_f32 || c == CosRoute::screen_copy || c == CosRoute::screen_i8; }
 
@@ -227,6 +235,24 @@ Plan plan_search(const Search &s) {
     // OI_BM25_EARLY=1 (A/B): the round-3 placement.
     p.late_fork = p.overlap && !K.bm25_early && B > 8 && !p.screen_chunks.empty() &&
                   p.screen_chunks.back().e - p.screen_chunks.back().r >= (512u << 10);
+    // The int8 screen is not HBM-bound at 7/8 of the CUs and its workgroups claim whole CUs: more waves shorten
+    // a chunk (measured: by about half of what they add -- 10M rows, chunk 2 532-546 -> 506 us, chunk 3 799-825 -> 768 us at
+    // 256 against 224 workgroups), but only where no other kernel needs a CU meanwhile.  So on this route the late fork moves
+    // BEHIND the last chunk: ev_fork is recorded after the chunk's launch, the BM25 kernels start when it ends and run beside
+    // the cosine leg's tail -- first on the 192 CUs the 64 workgroups of the chunk's margin select leave idle; the rescreen
+    // beside them takes 130 us instead of 104, and the leg ends about 20 us before the cosine leg (profiles/i8_width_ab.json).
+    // OI_BM25_BESIDE_LAST=1 (A/B): the fork of the bf16 routes.
+    p.tail_fork = p.late_fork && p.cos == CosRoute::screen_i8 && !K.bm25_beside_last;
+    // ... and the chunks take every CU when nothing runs beside them: no BM25 leg on the side stream, or one forked behind the
+    // last chunk.  A leg forked at the start of the search (a last chunk too short to fork late) runs beside the chunks: 7/8.
+    // A search through a VIEW keeps 7/8 as well: a view exists so that a second search can be in flight on the same shard, and
+    // every lane of a pipeline (oi_pipeline_*, the sharded pipeline of the Python package) scores through one -- the other
+    // lane's selects and rescoring and the fusing stream run on the CUs it leaves free.  The first chunk is NOT
+    // re-rounded to the wider grid (oi_screen_first_chunk_rows): it is the sample every threshold comes from, and at 28 672
+    // rows it has fewer quads than either width has workgroups.
+    // OI_SCREEN_I8_NARROW=1 (A/B): 7/8 throughout.
+    if (p.cos == CosRoute::screen_i8 && !idx->is_view && (!p.overlap || p.tail_fork) && !K.screen_i8_narrow)
+        p.screen_wgs = (uint32_t)std::max(1, ctx->num_cus);
     return p;
 }
 
@@ -482,15 +508,19 @@ int cosine_screen(const Search &s, const Plan &p, const Pools &P, uint32_t *w, c
         const bool last = i + 1 == p.screen_chunks.size();
         // the same products, the same bound: only where bf16(x) comes from differs (converted on the fly from the
         // f32 rows, 4 d bytes per row -- or read from the copy, 2 d bytes per row)
-        if (p.late_fork && last) OI_HIP_CHECK(hipEventRecord(ctx->ev_fork, ctx->stream)); // (before the last chunk's launch)
+        if (p.late_fork && !p.tail_fork && last) OI_HIP_CHECK(hipEventRecord(ctx->ev_fork, ctx->stream)); // (before the last chunk's launch)
         uint32_t *const proven_tau = PF.tau_keys;
         if (spec_next) PF.tau_keys = spec_tau; // (this launch only: the selects keep the proven thresholds)
-        const int rc_screen = i8 ? oi_launch_cosine_screen_i8_chunk(ctx, idx->screen_i8.as<uint8_t>(), n, r, e, dim, qi8, qf8, B, idx->doc_id_base, PF)
+        const int rc_screen = i8 ? oi_launch_cosine_screen_i8_chunk(ctx, idx->screen_i8.as<uint8_t>(), n, r, e, dim, qi8, qf8, B, idx->doc_id_base, PF, p.screen_wgs)
                               : copy ? oi_launch_cosine_screen_copy_chunk(ctx, idx->screen_copy.as<uint16_t>(), r, e, dim, qb.as<uint16_t>(), B, idx->doc_id_base, PF)
                                      : oi_launch_cosine_screen_chunk(ctx, idx->rows, r, e, dim, qb.as<uint16_t>(), B, idx->doc_id_base, PF);
         PF.tau_keys = proven_tau;
         OI_CHECK(rc_screen);
-        if (p.late_fork && last) OI_CHECK(fork_bm25(s, p, P.bm)); // ... enqueued after it: the screen's workgroups get their CUs first
+        ctx->last_screen_wgs = i ? std::max(ctx->last_screen_wgs, PF.n_segs) : PF.n_segs;
+        // ... enqueued after it: the screen's workgroups get their CUs first.  tail_fork: the event is recorded here, behind the
+        // launch, so the leg starts when the chunk ends and this chunk's margin select is the first kernel it runs beside.
+        if (p.tail_fork && last) OI_HIP_CHECK(hipEventRecord(ctx->ev_fork, ctx->stream));
+        if (p.late_fork && last) OI_CHECK(fork_bm25(s, p, P.bm));
         // The prediction for the next chunk rides in this chunk's margin select (select.hip), which holds the carried keys in
         // registers.  expected rank of the final k'-th among the e rows seen: depth e / n; three times that plus twelve
         // OI_SPEC_KERNEL (ablation builds): 1 = the separate pf_spec_kernel launch as before; 2 = both, compared on the device
