@@ -787,6 +787,71 @@ int oi_similar_share(oi_index *idx, const float *query_vecs, uint32_t n_queries,
                      uint32_t *labels_out /* [n_docs] by LOCAL row where `location` says, or NULL */);
 
 /* ------------------------------------------------------------------------- */
+/* Narrative discovery: centroid sums and a k-means loop over the index        */
+/* ------------------------------------------------------------------------- */
+/*
+ * oi_similar_share is the ASSIGNMENT step of a clustering over the index; these three calls are the rest of it.  With them a
+ * host asks not "how many posts are like the narratives I know" but "which narratives are there": seed a few vectors, let
+ * assignment and update alternate on the device, and read the moved narratives, their records and the label of every post.
+ * Builder-defined like the whole retrieval path.
+ *
+ * oi_label_sums -- the update step's reduction.  For every local row d with labels[d] < n_clusters: counts[labels[d]] += 1,
+ * and for every k: sums[labels[d]][k] += fix(x_dk), where fix(x) = (int64) rint(v * 2^30) and v is x with NaN -> 0, clamped
+ * to [-1, 1].  x_dk is the stored row element: the f32 value, or the bf16 value widened exactly.  A label >= n_clusters
+ * (0xFFFFFFFF included) is "no cluster": the row is not read, and there is no error for it.  No element of a unit row is
+ * clamped, and x * 2^30 is exact in f32.  The sums are 64-bit integers (|sum| <= 2^62 for any shard), so the result is a
+ * function of the inputs alone -- independent of grid, order of the atomics, route and run -- and the sums and counts of
+ * document shards ADD exactly (the choice of pol_q30 in oi_similar_summary).
+ * Rules: location says where labels, sums_out and counts_out live; OI_DEVICE is asynchronous on the ctx stream and needs no
+ * workspace; OI_HOST stages 4 B per row + 8 B per sum and count in the ctx workspace.  Embeddings only (no forward index, no
+ * finalize, no signals, no attributes); it works on a view; an f32 corpus of any supported dim and a bf16 corpus;
+ * n_clusters in [1, OI_MAX_CENTROIDS].  A null index, null buffer or n_clusters out of range -> OI_ERR_INVALID_ARG with the
+ * number in the message, before the first device call.  Not captured by graph replay.  Profile tag "label_sums".
+ *
+ * oi_centroids_from_sums -- sums to unit vectors; a call of its own because a sharded host adds the per-rank integer sums
+ * and counts first.  Per cluster c: v_k = (double)sums[c][k] * 2^-30; n2 is accumulated from +0.0 in ascending k as
+ * n2 = n2 + v_k * v_k (one rounded f64 multiply, one rounded f64 add, no fma); centroids_out[c][k] = (float)(v_k / sqrt(n2))
+ * with IEEE f64 divide and square root and round-to-nearest-even narrowing.  If counts[c] == 0 or n2 == 0 the cluster keeps
+ * previous[c] bit for bit (all zeros when previous == NULL).  centroids_out may alias previous.  location says where the four
+ * arrays live; n_clusters in [1, OI_MAX_CENTROIDS]; dim a multiple of 4, <= OI_MAX_DIM.  Profile tag "centroids".
+ *
+ * oi_narratives_fit -- the loop.  c_1 = seeds.  Assignment step i is oi_similar_share with queries c_i, spec's first four
+ * fields, no per-query thresholds and `filter` (when given) for every query; it gives labels_i and records_i.  moved_i is the
+ * number of rows with labels_i[d] != labels_{i-1}[d]; for i = 1, the number of assigned rows.  If i > 1 and moved_i == 0 the
+ * fit has converged; if i == max_iters it stops unconverged; otherwise
+ * c_{i+1} = oi_centroids_from_sums(oi_label_sums(labels_i), previous = c_i).  The outputs describe the LAST assignment step:
+ * centroids_out = c_i, records_out = records_i, labels_out = labels_i, info = {i, converged, moved_i, assigned rows}.  So
+ * oi_similar_share with centroids_out as queries and the same spec and filter returns records_out and labels_out bit for
+ * bit.  An empty cluster keeps its vector; a duplicate seed stays empty, by the share's tie rule.
+ * Rules: state and argument rules are oi_similar_share's (signals required; attributes required when a filter or a time axis
+ * is given; it works on a view); n_clusters in [1, OI_MAX_CENTROIDS], max_iters in [1, 64]; spec, filter and info_host are
+ * always host pointers; location covers the seeds and the three outputs; labels_out may be NULL.  The call reads `moved` once
+ * per step: it SYNCHRONISES the ctx stream in both locations.  Never captured by graph replay.  Routes: those of the share.
+ * Workspace, beside the share's: two label arrays (4 B per local row each), the sums (8 B x n_clusters x dim), the counts,
+ * two centroid sets, the replicated filter, and with OI_HOST the records (oi_workspace_bytes counts all of them).
+ * Profile tags: "label_sums" and "centroids" as above, "fit_moved" (the moved / assigned count of a step), and the share's.
+ *
+ * NOT covered: a sharded or pipelined form (shards of the documents add their oi_label_sums outputs and call
+ * oi_centroids_from_sums on the total); seeding is the caller's; one threshold for all clusters; at most 256 clusters.
+ */
+#define OI_MAX_CENTROIDS 256u
+int oi_label_sums(oi_index *idx, const uint32_t *labels /* [n_docs] by LOCAL row */, uint32_t n_clusters, int location,
+                  int64_t *sums_out /* [n_clusters][dim] */, uint64_t *counts_out /* [n_clusters] */);
+int oi_centroids_from_sums(oi_ctx *ctx, const int64_t *sums, const uint64_t *counts, const float *previous /* or NULL */,
+                           uint32_t n_clusters, uint32_t dim, int location, float *centroids_out /* [n_clusters][dim] */);
+
+typedef struct oi_narrative_spec {
+    float    threshold;      /* oi_summary_spec's four fields, same meaning and limits, one threshold for all clusters */
+    uint32_t stamp_origin, bucket_width, n_buckets;
+    uint32_t max_iters;      /* 1 .. 64 assignment steps */
+} oi_narrative_spec;
+typedef struct oi_narrative_info { uint32_t iterations, converged; uint64_t moved, assigned; } oi_narrative_info;
+int oi_narratives_fit(oi_index *idx, const float *seeds /* [n_clusters][dim] */, uint32_t n_clusters,
+                      const oi_narrative_spec *spec, const oi_doc_filter *filter /* ONE, host pointer, or NULL */, int location,
+                      float *centroids_out /* [n_clusters][dim] */, oi_social_counters *records_out /* [n_clusters][n_buckets] */,
+                      uint32_t *labels_out /* [n_docs] by LOCAL row, or NULL */, oi_narrative_info *info_host);
+
+/* ------------------------------------------------------------------------- */
 /* Text to term ids: the tokeniser and the hashed vocabulary                   */
 /* ------------------------------------------------------------------------- */
 /*

@@ -68,6 +68,27 @@ pub struct OiSummarySpec {
 }
 pub const OI_MAX_SUMMARY_CELLS: u32 = 1 << 18;
 
+/// `oi_narrative_spec`: `oi_summary_spec`'s four fields (one threshold for all clusters), then max_iters (1 ..= 64).
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct OiNarrativeSpec {
+    pub threshold: f32,
+    pub stamp_origin: u32,
+    pub bucket_width: u32,
+    pub n_buckets: u32,
+    pub max_iters: u32,
+}
+/// `oi_narrative_info`: assignment steps run, converged (0 / 1), rows moved in the last step, rows it assigned.
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
+pub struct OiNarrativeInfo {
+    pub iterations: u32,
+    pub converged: u32,
+    pub moved: u64,
+    pub assigned: u64,
+}
+pub const OI_MAX_CENTROIDS: u32 = 256;
+
 /// `oi_groups_spec`: the key of a document is (group & key_mask) >> ctz(key_mask); top == 0 asks for dense records, top >= 1 for
 /// the best `top` keys by `rank_by` among those with total >= max(min_total, 1).
 #[repr(C)]
@@ -254,6 +275,17 @@ extern "C" {
     pub fn oi_similar_share(idx: *mut OiIndex, query_vecs: *const f32, n_queries: u32, spec: *const OiSummarySpec,
                             thresholds: *const f32, filters: *const OiDocFilter, location: c_int,
                             out: *mut OiSocialCounters, labels_out: *mut u32) -> c_int;
+
+    // narrative discovery: the update step of a clustering (integer sums per label: exact, shards add), sums -> unit
+    // vectors (previous may be null), and the k-means loop over oi_similar_share (filter: ONE, may be null; labels_out may
+    // be null; spec, filter and info_host are host pointers whatever `location`)
+    pub fn oi_label_sums(idx: *mut OiIndex, labels: *const u32, n_clusters: u32, location: c_int, sums_out: *mut i64,
+                         counts_out: *mut u64) -> c_int;
+    pub fn oi_centroids_from_sums(ctx: *mut OiCtx, sums: *const i64, counts: *const u64, previous: *const f32, n_clusters: u32,
+                                  dim: u32, location: c_int, centroids_out: *mut f32) -> c_int;
+    pub fn oi_narratives_fit(idx: *mut OiIndex, seeds: *const f32, n_clusters: u32, spec: *const OiNarrativeSpec,
+                             filter: *const OiDocFilter, location: c_int, centroids_out: *mut f32,
+                             records_out: *mut OiSocialCounters, labels_out: *mut u32, info_host: *mut OiNarrativeInfo) -> c_int;
 
     pub fn oi_pipeline_create(idx: *mut OiIndex, comm: *mut OiComm, lanes: u32, max_queries: u32, max_query_terms: u32,
                               depth: u32, k: u32, out: *mut *mut OiPipeline) -> c_int;

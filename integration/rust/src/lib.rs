@@ -51,6 +51,22 @@ impl HipCtx {
     }
 }
 
+/// Integer sums and counts (`HipIndex::label_sums`, or the total over the shards of the documents) to unit vectors
+/// (`oi_centroids_from_sums`): sums / |sums| in f64, rounded once.  A cluster with count 0 or an all-zero sum keeps
+/// `previous` (zeros without one).
+pub fn centroids_from_sums(ctx: &HipCtx, sums: &[i64], counts: &[u64], previous: Option<&[f32]>, dim: usize) -> Result<Vec<f32>, HipError> {
+    assert_eq!(sums.len(), counts.len() * dim);
+    if let Some(p) = previous {
+        assert_eq!(p.len(), sums.len());
+    }
+    let mut out = vec![0f32; sums.len()];
+    check(unsafe {
+        ffi::oi_centroids_from_sums(ctx.raw(), sums.as_ptr(), counts.as_ptr(), previous.map_or(std::ptr::null(), |p| p.as_ptr()),
+                                    counts.len() as u32, dim as u32, ffi::OI_HOST, out.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
 /// Gather strings into the FFI layout: one UTF-8 blob + (n + 1) u64 offsets.  In the reference every post owns
 /// its text as a separate heap `String` (social_post.rs:25-27).
 pub fn gather<'a, I: IntoIterator<Item = &'a str>>(texts: I) -> (Vec<u8>, Vec<u64>) {
@@ -380,6 +396,35 @@ impl HipIndex {
                                   lab.as_mut().map_or(std::ptr::null_mut(), |l| l.as_mut_ptr()))
         })?;
         Ok((out.chunks(nb.max(1)).map(|c| c.to_vec()).collect(), lab))
+    }
+    /// The update step of a clustering over the index (`oi_label_sums`): per label c < n_clusters the number of rows that
+    /// carry it and the sum of rint(row * 2^30) over them, as 64-bit integers ([n_clusters * dim], [n_clusters]).  Any other
+    /// label (0xFFFFFFFF, as `similar_share` writes for unassigned rows) is "no cluster".  Exact: shards of the documents add.
+    pub fn label_sums(&self, labels: &[u32], n_clusters: u32) -> Result<(Vec<i64>, Vec<u64>), HipError> {
+        assert_eq!(labels.len(), self.n_docs);
+        let k = n_clusters as usize;
+        let (mut sums, mut counts) = (vec![0i64; k * self.dim], vec![0u64; k]);
+        check(unsafe { ffi::oi_label_sums(self.idx, labels.as_ptr(), n_clusters, ffi::OI_HOST, sums.as_mut_ptr(), counts.as_mut_ptr()) })?;
+        Ok((sums, counts))
+    }
+    /// Which narratives are there (`oi_narratives_fit`): k-means over the index on the device, from `seeds` ([k * dim]).
+    /// Returns the centroids, records and (with `labels`) labels of the LAST assignment step and what the loop did;
+    /// `similar_share` with the centroids as queries reproduces records and labels bit for bit.
+    pub fn fit_narratives(&self, seeds: &[f32], spec: ffi::OiNarrativeSpec, filter: Option<ffi::OiDocFilter>, labels: bool)
+                          -> Result<(Vec<f32>, Vec<Vec<ffi::OiSocialCounters>>, Option<Vec<u32>>, ffi::OiNarrativeInfo), HipError> {
+        assert_eq!(seeds.len() % self.dim, 0);
+        let k = seeds.len() / self.dim;
+        let nb = spec.n_buckets as usize;
+        let mut cent = vec![0f32; k * self.dim];
+        let mut rec = vec![ffi::OiSocialCounters::default(); k * nb];
+        let mut lab = if labels { Some(vec![u32::MAX; self.n_docs]) } else { None };
+        let mut info = ffi::OiNarrativeInfo::default();
+        check(unsafe {
+            ffi::oi_narratives_fit(self.idx, seeds.as_ptr(), k as u32, &spec, filter.as_ref().map_or(std::ptr::null(), |f| f as *const _),
+                                   ffi::OI_HOST, cent.as_mut_ptr(), rec.as_mut_ptr(),
+                                   lab.as_mut().map_or(std::ptr::null_mut(), |l| l.as_mut_ptr()), &mut info)
+        })?;
+        Ok((cent, rec.chunks(nb.max(1)).map(|c| c.to_vec()).collect(), lab, info))
     }
     /// Which group keys (tickers) the posts like each query are about, and what those posts feel (`oi_similar_groups`): the
     /// social_summary sums per key = (group & key_mask) >> ctz(key_mask), under `similar_summary`'s clauses.  spec.top == 0: per

@@ -20,6 +20,7 @@ OI_MAX_VOLUME_BUCKETS = 1024
 OI_MAX_SUMMARY_CELLS = 1 << 18
 OI_MAX_GROUP_KEYS = 65536
 OI_MAX_GROUP_CELLS = 1 << 20
+OI_MAX_CENTROIDS = 256
 OI_GROUP_RANK_TOTAL, OI_GROUP_RANK_SPEC, OI_GROUP_RANK_BULLISH, OI_GROUP_RANK_BEARISH = 0, 1, 2, 3
 OI_BM25_BLOCK_DOCS = 32768
 OI_N_CATALYST_KEYWORDS = 16
@@ -84,6 +85,27 @@ class SummarySpec(C.Structure):
         ("stamp_origin", C.c_uint32),
         ("bucket_width", C.c_uint32),
         ("n_buckets", C.c_uint32),
+    ]
+
+
+class NarrativeSpec(C.Structure):
+    """oi_narrative_spec: oi_summary_spec's four fields (one threshold for all clusters), then max_iters (1 .. 64)."""
+    _fields_ = [
+        ("threshold", C.c_float),
+        ("stamp_origin", C.c_uint32),
+        ("bucket_width", C.c_uint32),
+        ("n_buckets", C.c_uint32),
+        ("max_iters", C.c_uint32),
+    ]
+
+
+class NarrativeInfo(C.Structure):
+    """oi_narrative_info: assignment steps run, converged (0 / 1), rows moved in the last step, rows assigned by it."""
+    _fields_ = [
+        ("iterations", C.c_uint32),
+        ("converged", C.c_uint32),
+        ("moved", C.c_uint64),
+        ("assigned", C.c_uint64),
     ]
 
 
@@ -163,6 +185,9 @@ SIGNATURES = {
     "oi_similar_summary": (_I, [_P, _P, _U32, _P, _P, _P, _I, _P]),
     "oi_similar_groups": (_I, [_P, _P, _U32, _P, _P, _P, _I, _P, _P, _P, _P]),
     "oi_similar_share": (_I, [_P, _P, _U32, _P, _P, _P, _I, _P, _P]),
+    "oi_label_sums": (_I, [_P, _P, _U32, _I, _P, _P]),
+    "oi_centroids_from_sums": (_I, [_P, _P, _P, _P, _U32, _U32, _I, _P]),
+    "oi_narratives_fit": (_I, [_P, _P, _U32, _P, _P, _I, _P, _P, _P, _P]),
     "oi_text_terms": (_I, [_P, _P, _P, _U64, _U64, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_query_terms": (_I, [_P, _P, _P, _U32, _U32, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_index_set_text": (_I, [_P, _P, _P, _U64, _I]),

@@ -11,6 +11,7 @@ Host mirror of the reference's batch tools (paths relative to the openintel repo
     rank_metric / sort_ranked / run_compare        src/mcp/tools.rs:227-352
     rank_group_records / compare_index             src/mcp/tools.rs:323-349 over the index's per-ticker sums (oi_similar_groups)
     VoiceShare / share_of_voice                    builder-defined: the records of oi_similar_share as fractions per bucket
+    discover_narratives                            builder-defined: oi_narratives_fit and the share of voice of what it found
     SentimentSummary / sentiment_for (per dip row) src/domain/dip.rs:428-431, src/application/dip.rs:175-194
 
 The reference runs `application::analyze` once per ticker (`join_all`, tools.rs:206-220) and never pools posts of
@@ -363,6 +364,19 @@ def share_of_voice(records) -> List[List[VoiceShare]]:
                         fraction=(int(records[q][b]["total"]) / sums[b]) if sums[b] else 0.0,
                         social=SpeculationEngine.social_from_counters(records[q][b]))
              for b in range(nb)] for q in range(B)]
+
+
+def discover_narratives(index, seeds, threshold, **kw):
+    """Which narratives are there: `index.fit_narratives(seeds, threshold, **kw)` (k-means over the index on the device,
+    oi_narratives_fit) and the share of voice of what it found -> (NarrativeFit, share_of_voice(fit.records)).  Entry
+    [c][b] of the second is narrative c's share of the assigned posts in bucket b.  Records that live on the device
+    (tensor seeds) are read back for it; the fit itself is returned as it came."""
+    from .analyzer import COUNTERS_DTYPE
+    fit = index.fit_narratives(seeds, threshold, **kw)
+    rec = fit.records
+    if hasattr(rec, "data_ptr"):
+        rec = rec.cpu().numpy().view(COUNTERS_DTYPE).reshape(rec.shape[0], rec.shape[1])
+    return fit, share_of_voice(rec)
 
 
 # ----------------------------------------------------------------------------- wire format (#[derive(Serialize)])

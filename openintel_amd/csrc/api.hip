@@ -1731,6 +1731,125 @@ extern "C" int oi_similar_share(oi_index *idx, const float *qv, uint32_t B, cons
                           });
 }
 
+// ---------------------------------------------------------------- narrative discovery (centroids.hip)
+// The checks keep the family's order: the numbers, the buffers, then the handle; all of them precede the first HIP call.
+
+// the update step's reduction: labels -> integer sums and counts per cluster
+extern "C" int oi_label_sums(oi_index *idx, const uint32_t *labels, uint32_t K, int location, int64_t *sums_out, uint64_t *counts_out) {
+    OI_REQUIRE(K >= 1 && K <= OI_MAX_CENTROIDS, "label_sums: n_clusters=%u outside [1,%u]", K, OI_MAX_CENTROIDS);
+    OI_REQUIRE(labels && sums_out && counts_out, "label_sums: null buffer");
+    std::unique_lock<std::mutex> g;
+    OI_CHECK(similar_check_state("label_sums", idx, false, nullptr, g));
+    oi_ctx *ctx = idx->ctx;
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    if (location == OI_DEVICE) return oi_launch_label_sums(idx, labels, K, sums_out, counts_out);
+    hipStream_t st = ctx->stream;
+    const size_t lb = (sizeof(uint32_t) * (size_t)idx->n_docs + 15) & ~(size_t)15, sb = sizeof(int64_t) * (size_t)K * idx->dim,
+                 cb = sizeof(uint64_t) * (size_t)K;
+    DevBuf &w = ctx->buf("label_sums_io");
+    OI_CHECK(w.ensure(lb + sb + cb));
+    uint8_t *d = w.as<uint8_t>();
+    if (idx->n_docs) OI_HIP_CHECK(hipMemcpyAsync(d, labels, sizeof(uint32_t) * (size_t)idx->n_docs, hipMemcpyHostToDevice, st));
+    OI_CHECK(oi_launch_label_sums(idx, reinterpret_cast<const uint32_t *>(d), K, reinterpret_cast<int64_t *>(d + lb),
+                                  reinterpret_cast<uint64_t *>(d + lb + sb)));
+    OI_HIP_CHECK(hipMemcpyAsync(sums_out, d + lb, sb, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipMemcpyAsync(counts_out, d + lb + sb, cb, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipStreamSynchronize(st));
+    return OI_OK;
+}
+
+// sums -> unit vectors
+extern "C" int oi_centroids_from_sums(oi_ctx *ctx, const int64_t *sums, const uint64_t *counts, const float *previous, uint32_t K,
+                                      uint32_t dim, int location, float *out) {
+    OI_REQUIRE(K >= 1 && K <= OI_MAX_CENTROIDS, "centroids_from_sums: n_clusters=%u outside [1,%u]", K, OI_MAX_CENTROIDS);
+    OI_REQUIRE(dim >= 4 && dim <= OI_MAX_DIM && dim % 4 == 0, "centroids_from_sums: dim=%u is not a multiple of 4 in [4,%u]", dim, OI_MAX_DIM);
+    OI_REQUIRE(sums && counts && out, "centroids_from_sums: null buffer");
+    OI_REQUIRE(ctx, "centroids_from_sums: null ctx");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    if (location == OI_DEVICE) return oi_launch_centroids_from_sums(ctx, sums, counts, previous, K, dim, out);
+    hipStream_t st = ctx->stream;
+    const size_t sb = sizeof(int64_t) * (size_t)K * dim, cb = sizeof(uint64_t) * (size_t)K, vb = sizeof(float) * (size_t)K * dim;
+    DevBuf &w = ctx->buf("centroids_io");
+    OI_CHECK(w.ensure(sb + cb + vb));
+    uint8_t *d = w.as<uint8_t>();
+    float *d_v = reinterpret_cast<float *>(d + sb + cb);
+    OI_HIP_CHECK(hipMemcpyAsync(d, sums, sb, hipMemcpyHostToDevice, st));
+    OI_HIP_CHECK(hipMemcpyAsync(d + sb, counts, cb, hipMemcpyHostToDevice, st));
+    if (previous) OI_HIP_CHECK(hipMemcpyAsync(d_v, previous, vb, hipMemcpyHostToDevice, st));
+    OI_CHECK(oi_launch_centroids_from_sums(ctx, reinterpret_cast<const int64_t *>(d), reinterpret_cast<const uint64_t *>(d + sb),
+                                           previous ? d_v : nullptr, K, dim, d_v)); // (in place: the aliasing form)
+    OI_HIP_CHECK(hipMemcpyAsync(out, d_v, vb, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipStreamSynchronize(st));
+    return OI_OK;
+}
+
+// the loop: assignment (oi_launch_similar_share) and update alternate on the device; the host reads `moved` once per step
+extern "C" int oi_narratives_fit(oi_index *idx, const float *seeds, uint32_t K, const oi_narrative_spec *spec, const oi_doc_filter *filter,
+                                 int location, float *centroids_out, oi_social_counters *records_out, uint32_t *labels_out,
+                                 oi_narrative_info *info_host) {
+    OI_REQUIRE(spec, "narratives_fit: null spec");
+    OI_REQUIRE(K >= 1 && K <= OI_MAX_CENTROIDS, "narratives_fit: n_clusters=%u outside [1,%u]", K, OI_MAX_CENTROIDS);
+    OI_REQUIRE(spec->max_iters >= 1 && spec->max_iters <= 64, "narratives_fit: max_iters=%u outside [1,64]", spec->max_iters);
+    OI_CHECK(similar_check_spec("narratives_fit", spec->threshold, nullptr, false, spec->n_buckets, spec->bucket_width, K, OI_MAX_SUMMARY_CELLS));
+    OI_REQUIRE(seeds && centroids_out && records_out && info_host, "narratives_fit: null buffer");
+    std::unique_lock<std::mutex> g;
+    OI_CHECK(similar_check_state("narratives_fit", idx, true, (filter || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
+    oi_ctx *ctx = idx->ctx;
+    hipStream_t st = ctx->stream;
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    const oi_summary_spec ss = {spec->threshold, spec->stamp_origin, spec->bucket_width, spec->n_buckets};
+    const uint64_t n = idx->n_docs;
+    const uint32_t dim = idx->dim;
+    const bool host = location != OI_DEVICE;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t lb = up(sizeof(uint32_t) * (size_t)n), sb = up(sizeof(int64_t) * (size_t)K * dim), cb = up(sizeof(uint64_t) * (size_t)K),
+                 vb = up(sizeof(float) * (size_t)K * dim), fb = up(sizeof(oi_doc_filter) * (size_t)K),
+                 rbytes = sizeof(oi_social_counters) * (size_t)K * spec->n_buckets, rb = host ? up(rbytes) : 0;
+    DevBuf &w = ctx->buf("narratives");
+    OI_CHECK(w.ensure(2 * lb + sb + cb + 2 * vb + fb + 256 + rb));
+    uint8_t *d = w.as<uint8_t>();
+    uint32_t *d_lab[2] = {reinterpret_cast<uint32_t *>(d), reinterpret_cast<uint32_t *>(d + lb)};
+    int64_t *d_sums = reinterpret_cast<int64_t *>(d + 2 * lb);
+    uint64_t *d_counts = reinterpret_cast<uint64_t *>(d + 2 * lb + sb);
+    float *d_c[2] = {reinterpret_cast<float *>(d + 2 * lb + sb + cb), reinterpret_cast<float *>(d + 2 * lb + sb + cb + vb)};
+    uint4 *d_filt = reinterpret_cast<uint4 *>(d + 2 * lb + sb + cb + 2 * vb);
+    uint64_t *d_moved = reinterpret_cast<uint64_t *>(d + 2 * lb + sb + cb + 2 * vb + fb);
+    oi_social_counters *d_rec = host ? reinterpret_cast<oi_social_counters *>(d + 2 * lb + sb + cb + 2 * vb + fb + 256) : records_out;
+
+    OI_HIP_CHECK(hipMemcpyAsync(d_c[0], seeds, sizeof(float) * (size_t)K * dim, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+    if (filter) {
+        std::vector<oi_doc_filter> rep(K, *filter);
+        OI_HIP_CHECK(hipMemcpyAsync(d_filt, rep.data(), sizeof(oi_doc_filter) * (size_t)K, hipMemcpyHostToDevice, st));
+        OI_HIP_CHECK(hipStreamSynchronize(st)); // (rep leaves scope)
+    }
+    if (n) OI_HIP_CHECK(hipMemsetAsync(d_lab[1], 0xFF, sizeof(uint32_t) * (size_t)n, st)); // labels_0: nobody is assigned
+    oi_narrative_info info = {0, 0, 0, 0};
+    int cur = 0;
+    for (uint32_t i = 1;; ++i) {
+        uint64_t moved[2] = {0, 0};
+        OI_CHECK(oi_launch_similar_share(idx, d_c[cur], K, ss, nullptr, filter ? d_filt : nullptr, d_rec, d_lab[cur]));
+        OI_CHECK(oi_launch_fit_moved(ctx, d_lab[cur], d_lab[cur ^ 1], n, d_moved));
+        OI_HIP_CHECK(hipMemcpyAsync(moved, d_moved, sizeof(moved), hipMemcpyDeviceToHost, st));
+        OI_HIP_CHECK(hipStreamSynchronize(st));
+        info.iterations = i;
+        info.moved = moved[0];
+        info.assigned = moved[1];
+        if (i > 1 && moved[0] == 0) { info.converged = 1; break; }
+        if (i == spec->max_iters) break;
+        OI_CHECK(oi_launch_label_sums(idx, d_lab[cur], K, d_sums, d_counts));
+        OI_CHECK(oi_launch_centroids_from_sums(ctx, d_sums, d_counts, d_c[cur], K, dim, d_c[cur ^ 1]));
+        cur ^= 1; // (centroid set and label array swap together: d_lab[cur ^ 1] is now the previous step's)
+    }
+    const hipMemcpyKind out_kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    OI_HIP_CHECK(hipMemcpyAsync(centroids_out, d_c[cur], sizeof(float) * (size_t)K * dim, out_kind, st));
+    if (host) OI_HIP_CHECK(hipMemcpyAsync(records_out, d_rec, rbytes, hipMemcpyDeviceToHost, st));
+    if (labels_out && n) OI_HIP_CHECK(hipMemcpyAsync(labels_out, d_lab[cur], sizeof(uint32_t) * (size_t)n, out_kind, st));
+    OI_HIP_CHECK(hipStreamSynchronize(st));
+    *info_host = info;
+    return OI_OK;
+}
+
 // ---------------------------------------------------------------- diagnostics of the bf16 screen
 extern "C" int oi_screen_probe(oi_index *idx, const float *query_vecs, uint32_t B, uint64_t row_begin, uint32_t n_rows,
                                float *screen_scores_out, float *eps_out) {

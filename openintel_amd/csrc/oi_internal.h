@@ -351,6 +351,13 @@ int oi_launch_similar_groups(oi_index *idx, const float *d_q, uint32_t n_queries
 // (may be null) labels [n_docs] by local row out.  Asynchronous on the ctx stream; d_thresholds and d_filt may be null
 int oi_launch_similar_share(oi_index *idx, const float *d_q, uint32_t n_queries, const oi_summary_spec &spec, const float *d_thresholds,
                             const uint4 *d_filt, oi_social_counters *d_out, uint32_t *d_labels);
+// centroids.hip: the update step of a clustering over the index, all asynchronous on the ctx stream -- device
+// labels [n_docs] in, device sums [n_clusters][dim] and counts [n_clusters] out (zeroed by the launch); sums to unit vectors
+// (d_previous may be null or d_out); d_out[0] = rows with d_cur != d_prev, d_out[1] = rows with a label
+int oi_launch_label_sums(oi_index *idx, const uint32_t *d_labels, uint32_t n_clusters, int64_t *d_sums, uint64_t *d_counts);
+int oi_launch_centroids_from_sums(oi_ctx *ctx, const int64_t *d_sums, const uint64_t *d_counts, const float *d_previous,
+                                  uint32_t n_clusters, uint32_t dim, float *d_out);
+int oi_launch_fit_moved(oi_ctx *ctx, const uint32_t *d_cur, const uint32_t *d_prev, uint64_t n, uint64_t *d_out);
 // cosine.hip
 // Sets pool.n_segs / pool.seg_cap for this chunk (the following select must use the same view).
 int oi_launch_cosine_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end,

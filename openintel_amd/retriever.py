@@ -54,6 +54,18 @@ class GroupRanking:
     qualified: object   # [B] u32: keys with total >= max(min_total, 1), before the cut at `top`
 
 
+@dataclass
+class NarrativeFit:
+    """Result of HybridIndex.fit_narratives (oi_narratives_fit): everything describes the LAST assignment step."""
+    centroids: object   # [K, dim] f32: the narratives the last step assigned against
+    records: object     # [K, n_buckets] analyzer.COUNTERS_DTYPE (torch: int64 [K, n_buckets, 8])
+    labels: object      # [n_docs] u32 by local row (0xFFFFFFFF: unassigned), or None when not asked for
+    iterations: int     # assignment steps run
+    converged: bool     # a step after the first moved no row
+    moved: int          # rows whose label changed in the last step
+    assigned: int       # rows the last step assigned
+
+
 GROUP_RANKS = {"total": _lib.OI_GROUP_RANK_TOTAL, "spec": _lib.OI_GROUP_RANK_SPEC, "bullish": _lib.OI_GROUP_RANK_BULLISH,
                "bearish": _lib.OI_GROUP_RANK_BEARISH}
 
@@ -633,6 +645,66 @@ class HybridIndex(PostRetriever):
                                              _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(out), _lib.ptr(lab)))
         return (out, lab) if labels else out
 
+    # ---------------------------------------------------------------- narrative discovery
+    def label_sums(self, labels, n_clusters: int):
+        """oi_label_sums, the update step of a clustering: (sums int64 [n_clusters, dim], counts uint64 [n_clusters]) over the
+        rows d with labels[d] < n_clusters -- counts[labels[d]] += 1, sums[labels[d]] += rint(row_d * 2^30) as 64-bit integers
+        (NaN -> 0, clamped to [-1, 1]).  Any other label, 0xFFFFFFFF included, is "no cluster".  Exact: the same bits on every
+        run, and the sums of document shards add.  labels: [n_docs] uint32 by local row as similar_share(labels=True)
+        returns them; numpy in, numpy out; torch CUDA tensor in, tensors out (counts as int64; asynchronous)."""
+        K = int(n_clusters)
+        dev = _is_dev(labels)
+        rows_out = max(min(K, _lib.OI_MAX_CENTROIDS), 1)            # (a count out of range is refused by the library, not here)
+        if dev:
+            import torch
+            assert labels.is_contiguous() and labels.numel() == self.n_docs and labels.element_size() == 4
+            sums = torch.zeros((rows_out, self.dim), dtype=torch.int64, device="cuda:%d" % self.ctx.device)
+            counts = torch.zeros((rows_out,), dtype=torch.int64, device="cuda:%d" % self.ctx.device)
+        else:
+            labels = _np(labels, np.uint32)
+            assert labels.size == self.n_docs
+            sums = np.zeros((rows_out, self.dim), dtype=np.int64)
+            counts = np.zeros((rows_out,), dtype=np.uint64)
+        _lib.check(self.lib.oi_label_sums(self.handle, _lib.ptr(labels), K, _lib.OI_DEVICE if dev else _lib.OI_HOST,
+                                          _lib.ptr(sums), _lib.ptr(counts)))
+        return sums, counts
+
+    def fit_narratives(self, seeds, threshold: float, max_iters: int = 20, n_buckets: int = 1, stamp_origin: int = 0,
+                       bucket_width: int = 0, filter=None, labels: bool = False) -> "NarrativeFit":
+        """oi_narratives_fit: k-means over the index on the device.  Starting from seeds [K, dim], similar_share (one
+        threshold, `filter` -- ONE {group_mask, group_value, stamp_lo, stamp_hi} -- for every cluster) and the centroid update
+        (label_sums + centroids_from_sums) alternate until a step moves no row or max_iters assignment steps ran.  The result
+        describes the last assignment step: similar_share(fit.centroids, ...) reproduces fit.records and fit.labels bit for
+        bit.  An empty cluster keeps its vector.  numpy seeds in, numpy out; torch CUDA tensor in, tensors out.  The call
+        synchronises the ctx stream (it reads the moved count once per step)."""
+        from .analyzer import COUNTERS_DTYPE
+        dev = _is_dev(seeds)
+        if dev:
+            import torch
+            assert seeds.is_contiguous() and seeds.element_size() == 4
+        else:
+            seeds = _np(seeds, np.float32)
+        K = int(seeds.shape[0])
+        assert K == 0 or int(seeds.shape[1]) == self.dim
+        nb = max(int(n_buckets), 0)
+        spec = _lib.NarrativeSpec(float(threshold), int(stamp_origin), int(bucket_width), int(n_buckets), int(max_iters))
+        if dev:
+            cent = torch.zeros((K, self.dim), dtype=torch.float32, device="cuda:%d" % self.ctx.device)
+            rec = torch.zeros((K, nb, 8), dtype=torch.int64, device="cuda:%d" % self.ctx.device)
+        else:
+            cent = np.zeros((K, self.dim), dtype=np.float32)
+            rec = np.zeros((K, nb), dtype=COUNTERS_DTYPE)
+        lab = self._alloc(dev, (self.n_docs,), np.uint32) if labels else None
+        f = None
+        if filter is not None:
+            fa = np.ascontiguousarray(np.asarray(filter.cpu().numpy() if _is_dev(filter) else filter).astype(np.uint32, copy=False).reshape(4))
+            f = _lib.DocFilter(int(fa[0]), int(fa[1]), int(fa[2]), int(fa[3]))
+        info = _lib.NarrativeInfo()
+        _lib.check(self.lib.oi_narratives_fit(self.handle, _lib.ptr(seeds), K, C.byref(spec), None if f is None else C.byref(f),
+                                              _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(cent), _lib.ptr(rec), _lib.ptr(lab),
+                                              C.byref(info)))
+        return NarrativeFit(cent, rec, lab, int(info.iterations), bool(info.converged), int(info.moved), int(info.assigned))
+
     # ---------------------------------------------------------------- the sharded query with RCCL inside the library
     def finalize_sharded(self, comm: "NativeComm") -> None:
         """Collective over `comm`: all-reduce of (n_docs, tokens, df) inside the library, then the impacts from the global
@@ -812,6 +884,30 @@ class NativePipeline:
 
 
 # ---------------------------------------------------------------- list-level ops (any ctx)
+def centroids_from_sums(ctx: HipContext, sums, counts, previous=None):
+    """oi_centroids_from_sums: integer sums [K, dim] and counts [K] (HybridIndex.label_sums's, or the total of several
+    shards') -> unit vectors [K, dim] f32: sums / |sums|, computed in f64 and rounded once.  A cluster with count 0 or an
+    all-zero sum keeps previous[c] (zeros when previous is None).  numpy in, numpy out; torch CUDA tensors in, tensor out."""
+    dev = _is_dev(sums)
+    if dev:
+        import torch
+        assert sums.is_contiguous() and sums.element_size() == 8 and counts.is_contiguous() and counts.element_size() == 8
+        if previous is not None:
+            assert _is_dev(previous) and previous.is_contiguous() and previous.element_size() == 4 and tuple(previous.shape) == tuple(sums.shape)
+        out = torch.zeros(tuple(sums.shape), dtype=torch.float32, device=sums.device)
+    else:
+        sums, counts = _np(sums, np.int64), _np(counts, np.uint64)
+        if previous is not None:
+            previous = _np(previous, np.float32)
+            assert previous.shape == sums.shape
+        out = np.zeros(sums.shape, dtype=np.float32)
+    K, dim = int(sums.shape[0]), int(sums.shape[1])
+    assert int(counts.shape[0]) == K
+    _lib.check(ctx.lib.oi_centroids_from_sums(ctx.handle, _lib.ptr(sums), _lib.ptr(counts), _lib.ptr(previous), K, dim,
+                                              _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(out)))
+    return out
+
+
 def rrf_fuse(ctx: HipContext, docs_a, counts_a, docs_b, counts_b, k: int) -> SearchResult:
     dev = _is_dev(docs_a)
     if not dev:
