@@ -4,11 +4,39 @@
 //   key = orderable(score) << 32 | ~doc_id        (oi_device.h)
 // so "score descending, doc id ascending" is plain descending u64 order and keys of
 // distinct docs are distinct.  One workgroup (1024 threads = 16 waves) owns one query.
+//
+// select_flat_kernel (the pool as one flat array: every product launch) runs sel_flat_select<KPT>, a sequence of stages
+// over a key holder (SelKeys<KPT>: registers, or re-loading for KPT == 0):
+//   sel_take_all      n <= k: everything
+//   sel_margin_bins   margin mode: two 11-bit passes, verdict mask, direct carry write, the prediction
+//   sel_sampled_cut   pools above SEL_CAND keys: a sampled threshold, then the select over the cut
+//   sel_exact         the exact radix select over the whole pool
+//   sel_margin_exact  margin mode behind an exact select: everything within eps2 of the k-th score
+// and ends in sel_finish (sorted output / smallest key, compaction, threshold raise) or, for a margin result, in
+// sel_finish_margin.  select_topk_kernel (more than SEL_MAX_SEGS segments, OI_SELECT_V1) puts a segment walk or an LDS
+// gather in front of the same sel_threshold and sel_finish.  Then lists_to_pool_kernel and rrf_kernel.
 #include "oi_device.h"
 #include "oi_internal.h"
 
 #define SEL_THREADS 1024
 #define SEL_MAX 1024  // == OI_MAX_DEPTH
+
+// One select launch: the pools (PoolView), the request, the optional behaviour (SelectExtra; its margin-mode members are
+// null / 0 outside margin mode).  oi_launch_select fills it once; both kernels take it by value.
+struct SelArgs {
+    uint64_t *pools;
+    uint32_t *carry_cnt, *seg_cnt, *tau_keys, *overflow;
+    uint64_t pool_stride;
+    uint32_t carry_cap, seg_cap, n_segs, seg_cnt_stride, k, out_stride;
+    int compact;
+    float *out_scores;
+    uint32_t *out_docs, *out_counts;
+    const float *eps2, *row_meta, *row_qn, *row_cq;
+    const uint32_t *run_gate, *skip;
+    uint32_t *margin_gate, *spec_tau, *spec_max;
+    uint64_t *cand;
+    uint32_t skip_base, cand_cap, meta_base, spec_rank;
+};
 
 // In-LDS bitonic sort, descending, P a power of two <= 2048, all SEL_THREADS threads call.
 __device__ void bitonic_sort_desc(uint64_t *a, uint32_t P) {
@@ -27,196 +55,6 @@ __device__ void bitonic_sort_desc(uint64_t *a, uint32_t P) {
     }
 }
 
-// Top-k of pool q (carry region + segments, see PoolView).  Small pools are gathered into LDS
-// once; the radix select (8 passes of 8 bits from the top, stopping as soon as the k-th key is
-// alone in its bin) then runs out of LDS.  Large pools are scanned in place, one wave per segment.
-// compact: the pool is rewritten as carry = the selected keys, all segments empty, and the
-// threshold raised to the k-th score, so the next corpus chunk appends after them.
-#define SEL_LDS_KEYS 8192
-
-struct SelSource {
-    const uint64_t *pool;      // this query's pool
-    const uint32_t *segc;      // this query's segment counts
-    const uint64_t *lds_keys;  // non-null: everything already gathered here
-    uint32_t n, c0, carry_cap, seg_cap, n_segs;
-};
-
-template <class F>
-__device__ __forceinline__ void sel_for_each(const SelSource &S, F &&f) {
-    const uint32_t tid = threadIdx.x;
-    if (S.lds_keys) {
-        for (uint32_t i = tid; i < S.n; i += SEL_THREADS) f(S.lds_keys[i]);
-        return;
-    }
-    for (uint32_t i = tid; i < S.c0; i += SEL_THREADS) f(S.pool[i]);
-    const uint32_t lane = tid & 63, wv = tid >> 6;
-    for (uint32_t sg = wv; sg < S.n_segs; sg += SEL_THREADS / 64) {
-        uint32_t c = S.segc[sg];
-        if (c > S.seg_cap) c = S.seg_cap;
-        const uint64_t *base = S.pool + S.carry_cap + (uint64_t)sg * S.seg_cap;
-        for (uint32_t i = lane; i < c; i += 64) f(base[i]);
-    }
-}
-
-__global__ __launch_bounds__(SEL_THREADS) void select_topk_kernel(
-    uint64_t *pools, uint32_t *carry_cnt, uint32_t *seg_cnt, uint32_t *tau_keys, uint64_t pool_stride,
-    uint32_t carry_cap, uint32_t seg_cap, uint32_t n_segs, uint32_t seg_cnt_stride, uint32_t *overflow,
-    uint32_t k, int compact, float *out_scores, uint32_t *out_docs, uint32_t *out_counts, uint32_t out_stride) {
-    __shared__ uint32_t hist[256];
-    __shared__ uint64_t sel[2 * SEL_MAX];
-    __shared__ uint64_t lds_keys[SEL_LDS_KEYS];
-    __shared__ uint32_t s_cnt, s_kk, s_bin_cnt, s_total;
-    __shared__ uint64_t s_prefix;
-
-    const uint32_t q = blockIdx.x, tid = threadIdx.x;
-    uint64_t *pool = pools + (uint64_t)q * pool_stride;
-    uint32_t *segc = seg_cnt + (uint64_t)q * seg_cnt_stride;
-    SelSource S;
-    S.pool = pool; S.segc = segc; S.lds_keys = nullptr;
-    S.carry_cap = carry_cap; S.seg_cap = seg_cap; S.n_segs = n_segs;
-    S.c0 = carry_cnt[q] < carry_cap ? carry_cnt[q] : carry_cap;
-    if (tid == 0) { s_cnt = 0; s_total = 0; }
-    __syncthreads();
-    {
-        uint32_t local = 0;
-        for (uint32_t sg = tid; sg < n_segs; sg += SEL_THREADS) {
-            uint32_t c = segc[sg];
-            if (c > seg_cap) { *overflow = 1u; c = seg_cap; }
-            local += c;
-        }
-        local = oi_wave_sum(local);
-        if ((tid & 63) == 0 && local) atomicAdd(&s_total, local);
-    }
-    __syncthreads();
-    const uint32_t n = S.c0 + s_total;
-    S.n = n;
-    if (n <= SEL_LDS_KEYS) {
-        sel_for_each(S, [&](uint64_t key) { lds_keys[atomicAdd(&s_cnt, 1u)] = key; });
-        __syncthreads();
-        S.lds_keys = lds_keys;
-        if (tid == 0) s_cnt = 0;
-        __syncthreads();
-    }
-
-    uint32_t m; // number selected
-    if (n <= k) {
-        sel_for_each(S, [&](uint64_t key) { sel[atomicAdd(&s_cnt, 1u)] = key; });
-        m = n;
-        __syncthreads();
-    } else {
-        if (tid == 0) { s_prefix = 0; s_kk = k; }
-        int shift = 56;
-        for (;; shift -= 8) {
-            if (tid < 256) hist[tid] = 0;
-            __syncthreads();
-            const uint64_t prefix = s_prefix;
-            if (shift == 56)
-                sel_for_each(S, [&](uint64_t key) { atomicAdd(&hist[(uint32_t)(key >> 56)], 1u); });
-            else
-                sel_for_each(S, [&](uint64_t key) {
-                    if ((key >> (shift + 8)) == prefix) atomicAdd(&hist[(uint32_t)(key >> shift) & 255u], 1u);
-                });
-            __syncthreads();
-            if (tid < 64) { // wave 0: find the digit holding the kk-th key counted from the top
-                const uint32_t kk = s_kk;
-                uint32_t mine = 0;
-                for (int i = 0; i < 4; ++i) mine += hist[255 - (tid * 4 + i)];
-                uint32_t incl = mine;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    uint32_t v = __shfl_up(incl, o, OI_WAVE);
-                    if ((int)tid >= o) incl += v;
-                }
-                const unsigned long long ball = __ballot(incl >= kk);
-                const uint32_t owner = ball ? (uint32_t)__builtin_ctzll(ball) : 63u;
-                if (tid == owner) {
-                    uint32_t cum = incl - mine;
-                    int d = 255 - (int)(tid * 4);
-                    for (int i = 0; i < 3; ++i, --d) {
-                        const uint32_t c = hist[d];
-                        if (cum + c >= kk) break;
-                        cum += c;
-                    }
-                    s_prefix = (prefix << 8) | (uint64_t)d;
-                    s_kk = kk - cum;
-                    s_bin_cnt = hist[d];
-                }
-            }
-            __syncthreads();
-            if (s_bin_cnt == 1 || shift == 0) break;
-        }
-        // every key whose top bits are >= prefix is selected: exactly k of them (keys are distinct)
-        const uint64_t prefix = s_prefix;
-        sel_for_each(S, [&](uint64_t key) {
-            if ((key >> shift) >= prefix) {
-                const uint32_t pos = atomicAdd(&s_cnt, 1u);
-                if (pos < SEL_MAX) sel[pos] = key;
-            }
-        });
-        __syncthreads();
-        m = s_cnt < k ? s_cnt : k;
-    }
-    // Sorted output is needed only for a final list; an intermediate compaction just needs the set
-    // and its smallest key (the new threshold).
-    __shared__ unsigned long long s_min;
-    if (out_scores) {
-        uint32_t P = 2;
-        while (P < m) P <<= 1;
-        for (uint32_t i = m + tid; i < P; i += SEL_THREADS) sel[i] = 0; // lowest possible key
-        __syncthreads();
-        bitonic_sort_desc(sel, P);
-        for (uint32_t i = tid; i < m; i += SEL_THREADS) {
-            const uint64_t key = sel[i];
-            out_scores[(uint64_t)q * out_stride + i] = oi_rank_key_score(key);
-            out_docs[(uint64_t)q * out_stride + i] = oi_rank_key_doc(key);
-        }
-        if (tid == 0) { out_counts[q] = m; s_min = m ? sel[m - 1] : 0; }
-    } else {
-        if (tid == 0) s_min = ~0ull;
-        __syncthreads();
-        unsigned long long lo = ~0ull;
-        for (uint32_t i = tid; i < m; i += SEL_THREADS) lo = sel[i] < lo ? sel[i] : lo;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long v = __shfl_xor(lo, o, OI_WAVE);
-            lo = v < lo ? v : lo;
-        }
-        if ((tid & 63) == 0 && lo != ~0ull) atomicMin(&s_min, lo);
-    }
-    __syncthreads();
-    if (compact) {
-        for (uint32_t i = tid; i < m; i += SEL_THREADS) pool[i] = sel[i];
-        for (uint32_t sg = tid; sg < n_segs; sg += SEL_THREADS) segc[sg] = 0;
-        if (tid == 0) {
-            carry_cnt[q] = m;
-            if (m == k && tau_keys) {
-                // k docs at or above this score exist: a valid lower bound for the final
-                // k-th score, so later chunks may drop anything strictly below it.
-                const uint32_t t = (uint32_t)(s_min >> 32);
-                if (t > tau_keys[q]) tau_keys[q] = t;
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// select_flat_kernel: the same selection with the pool seen as ONE flat array.
-//
-// The kernel above walks the pool a segment at a time (one wave per segment: a dependent count -> keys
-// load chain per segment, repeated on every radix pass when the pool does not fit its LDS copy); with the
-// 256 short segments a cosine chunk leaves behind, that chain IS the select (40-120 us per launch, on the
-// critical path between two corpus chunks).  Here
-//   * the segment counts are scanned once into LDS offsets; flat index -> (segment, slot) is one binary
-//     search per lane and then a forward walk, because wave w owns the contiguous flat range
-//     [w*kpt*64, (w+1)*kpt*64) and reads it 64 consecutive keys per load (coalesced, all loads in flight);
-//   * the keys then live in REGISTERS (<= 32 per thread: pools up to 32K keys) for everything that follows;
-//     larger pools re-load through the same flat view on every pass;
-//   * pools above 4K keys are cut down first: the threshold that keeps ~2k keys is read off a 1024-key
-//     sample (radix select over one key per thread), one filter pass moves the survivors to LDS, and the
-//     exact selection runs over those.  A sample that keeps fewer than k or more than 4096 keys falls back
-//     to the exact passes over the whole pool: the RESULT never depends on the sample;
-//   * histogram and append atomics are aggregated per wave first (the leading digits of a pool of
-//     near-threshold scores are nearly all equal, i.e. one LDS address).
 #define SEL_MAX_SEGS 4096
 #define SEL_KPT_MAX 32
 #ifdef OI_ABLATION
@@ -231,22 +69,23 @@ __device__ unsigned long long sel_dbg_t[16];
 
 // Per-row margins of a margin select (the int8 screening tier, cosine_screen_i8.hip): keys are LOWER bounds l_r of rows whose upper
 // bound is l_r + 2 (e_r qn + cq); a key passing the global margin (eps2 = the largest such width) is kept only when its own upper
-// bound reaches the k-th key, less a guard for the f32 rounding of the test.  meta: {scale, e_r} per row (row = doc - base).
+// bound reaches the k-th key, less a guard for the f32 rounding of the test.  meta: {scale, e_r} per row (row = doc - base);
+// null: no row margins.
 struct SelRowMargin {
     const float *meta;
     uint32_t base;
     float qn, cq;
 };
 // (the gather and the test apart: the fast margin path issues a group of gathers before it evaluates any)
-__device__ __forceinline__ float sel_row_e(const SelRowMargin *rm, uint64_t kv) {
-    return rm->meta[2 * (uint64_t)(oi_rank_key_doc(kv) - rm->base) + 1];
+__device__ __forceinline__ float sel_row_e(const SelRowMargin &rm, uint64_t kv) {
+    return rm.meta[2 * (uint64_t)(oi_rank_key_doc(kv) - rm.base) + 1];
 }
-__device__ __forceinline__ bool sel_row_test(const SelRowMargin *rm, uint64_t kv, float e, float edge, float eps2) {
-    const float u = oi_rank_key_score(kv) + 2.002f * (e * rm->qn + rm->cq);
+__device__ __forceinline__ bool sel_row_test(const SelRowMargin &rm, uint64_t kv, float e, float edge, float eps2) {
+    const float u = oi_rank_key_score(kv) + 2.002f * (e * rm.qn + rm.cq);
     return u >= edge - 9.5367431640625e-07f * (fabsf(edge) + eps2);
 }
-__device__ __forceinline__ bool sel_row_keep(const SelRowMargin *rm, uint64_t kv, float edge, float eps2) {
-    if (!rm) return true;
+__device__ __forceinline__ bool sel_row_keep(const SelRowMargin &rm, uint64_t kv, float edge, float eps2) {
+    if (!rm.meta) return true;
     return sel_row_test(rm, kv, sel_row_e(rm, kv), edge, eps2);
 }
 
@@ -262,50 +101,20 @@ __device__ __forceinline__ void sel_spec_words(bool have, uint32_t rth_key, floa
     if (st > tau && st > *spec_max) *spec_max = st;
 }
 
-struct SelShared {
+// The words of a radix select (sel_threshold, sel_rank_bin2k): all select_topk_kernel needs of SelShared.
+struct SelRadix {
     uint32_t hist[256];
-    uint32_t hist2k[2048]; // the margin selects' 11-bit digits (sel_flat_select, fast margin path)
+    uint32_t kk, bin_cnt;
+    uint64_t prefix;
+};
+struct SelShared {
+    SelRadix rx;
+    uint32_t hist2k[2048]; // the margin selects' 11-bit digits (sel_margin_bins, sel_rth_score_key)
     uint32_t seg_off[SEL_MAX_SEGS + 1];
     uint32_t wave_tot[SEL_THREADS / 64];
-    uint32_t cnt, kk, bin_cnt, n_samples;
-    uint64_t prefix;
+    uint32_t cnt, n_samples;
     unsigned long long min_key;
 };
-
-struct SelFlat {
-    const uint64_t *pool;
-    const uint32_t *seg_off; // LDS, n_segs + 1 entries, seg_off[n_segs] = keys in segments
-    uint32_t n, c0, carry_cap, seg_cap, n_segs, steps;
-};
-// A lane's position in the flat view: segment sg holds the segment-relative flat indices [lo, hi).
-struct SelCursor {
-    uint32_t sg, lo, hi;
-};
-// flat index i < n  ->  cursor at its segment (binary search; indices inside the carry region map to e = 0)
-__device__ __forceinline__ SelCursor sel_seek(const SelFlat &K, uint32_t i) {
-    const uint32_t e = i < K.c0 ? 0u : i - K.c0;
-    uint32_t lo = 0, hi = K.n_segs; // seg_off[lo] <= e < seg_off[hi]
-    for (uint32_t s = 0; s < K.steps; ++s) {
-        const uint32_t mid = (lo + hi) >> 1;
-        const bool up = K.seg_off[mid] <= e;
-        lo = up ? mid : lo;
-        hi = up ? hi : mid;
-    }
-    SelCursor c;
-    c.sg = lo; c.lo = K.seg_off[lo]; c.hi = K.seg_off[lo + 1];
-    return c;
-}
-// pool offset of flat index i < n, i >= every index this cursor was used for before (forward walk)
-__device__ __forceinline__ uint64_t sel_at(const SelFlat &K, SelCursor &c, uint32_t i) {
-    if (i < K.c0) return i;
-    const uint32_t e = i - K.c0;
-    while (e >= c.hi) { // e < seg_off[n_segs]: stops at the segment that holds e (skips empty ones)
-        ++c.sg;
-        c.lo = c.hi;
-        c.hi = K.seg_off[c.sg + 1];
-    }
-    return (uint64_t)K.carry_cap + (uint64_t)c.sg * K.seg_cap + (e - c.lo);
-}
 
 // hist[digit] += 1 for the active lanes; the two most common digits of the wave go in as one atomic each
 __device__ __forceinline__ void sel_hist_add(uint32_t *hist, bool active, uint32_t digit) {
@@ -352,27 +161,39 @@ __device__ __forceinline__ void sel_hist_add_w(uint32_t *hist, bool active, uint
     if (active) atomicAdd(&hist[digit], weight);
 }
 
-// Radix select over the keys `for_each` enumerates (f(valid, key), same keys on every call): finds
-// (shift, prefix) such that exactly kk of them have (key >> shift) >= prefix.  Needs kk <= their number,
-// distinct keys; all threads call.
+// The smallest of a[0..m) into *min_key (an LDS word, ~0 or a larger candidate on entry; readable after the next barrier).
+__device__ __forceinline__ void sel_min_key(const uint64_t *a, uint32_t m, unsigned long long *min_key) {
+    unsigned long long lo = ~0ull;
+    for (uint32_t i = threadIdx.x; i < m; i += SEL_THREADS) lo = a[i] < lo ? a[i] : lo;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long v = __shfl_xor(lo, o, OI_WAVE);
+        lo = v < lo ? v : lo;
+    }
+    if ((threadIdx.x & 63) == 0 && lo != ~0ull) atomicMin(min_key, lo);
+}
+
+// Radix select over the keys `for_each` enumerates (f(valid, key), same keys on every call, wave-uniform trip counts: f
+// ballots): finds (shift, prefix) such that exactly kk of them have (key >> shift) >= prefix.  Needs kk <= their number,
+// distinct keys; all threads call.  Reads nothing of rx, leaves nothing in it.
 template <class FE>
-__device__ __forceinline__ void sel_threshold(FE &&for_each, uint32_t kk_in, SelShared &sh, int &shift_out, uint64_t &prefix_out) {
+__device__ __forceinline__ void sel_threshold(FE &&for_each, uint32_t kk_in, SelRadix &rx, int &shift_out, uint64_t &prefix_out) {
     const uint32_t tid = threadIdx.x;
-    if (tid == 0) { sh.prefix = 0; sh.kk = kk_in; }
+    if (tid == 0) { rx.prefix = 0; rx.kk = kk_in; }
     int shift = 56;
     for (;; shift -= 8) {
-        if (tid < 256) sh.hist[tid] = 0;
+        if (tid < 256) rx.hist[tid] = 0;
         __syncthreads();
-        const uint64_t prefix = sh.prefix;
+        const uint64_t prefix = rx.prefix;
         const bool top = shift == 56;
         for_each([&](bool valid, uint64_t kv) {
-            sel_hist_add(sh.hist, valid && (top || (kv >> ((shift + 8) & 63)) == prefix), (uint32_t)(kv >> shift) & 255u);
+            sel_hist_add(rx.hist, valid && (top || (kv >> ((shift + 8) & 63)) == prefix), (uint32_t)(kv >> shift) & 255u);
         });
         __syncthreads();
         if (tid < 64) { // wave 0: the digit holding the kk-th key counted from the top
-            const uint32_t kk = sh.kk;
+            const uint32_t kk = rx.kk;
             uint32_t mine = 0;
-            for (int i = 0; i < 4; ++i) mine += sh.hist[255 - (tid * 4 + i)];
+            for (int i = 0; i < 4; ++i) mine += rx.hist[255 - (tid * 4 + i)];
             uint32_t incl = mine;
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) {
@@ -385,26 +206,26 @@ __device__ __forceinline__ void sel_threshold(FE &&for_each, uint32_t kk_in, Sel
                 uint32_t cum = incl - mine;
                 int d = 255 - (int)(tid * 4);
                 for (int i = 0; i < 3; ++i, --d) {
-                    const uint32_t c = sh.hist[d];
+                    const uint32_t c = rx.hist[d];
                     if (cum + c >= kk) break;
                     cum += c;
                 }
-                sh.prefix = (prefix << 8) | (uint64_t)d;
-                sh.kk = kk - cum;
-                sh.bin_cnt = sh.hist[d];
+                rx.prefix = (prefix << 8) | (uint64_t)d;
+                rx.kk = kk - cum;
+                rx.bin_cnt = rx.hist[d];
             }
         }
         __syncthreads();
-        if (sh.bin_cnt == 1 || shift == 0) break;
+        if (rx.bin_cnt == 1 || shift == 0) break;
     }
     shift_out = shift;
-    prefix_out = sh.prefix;
-    __syncthreads(); // sh.prefix / sh.kk may be rewritten by the next call
+    prefix_out = rx.prefix;
+    __syncthreads(); // rx.prefix / rx.kk may be rewritten by the next call
 }
 
 // sh.hist2k holds a histogram of 2048 digits (filled, barrier passed): which digit holds the kk-th key counted from the top?
-// -> sh.prefix = the digit, sh.kk = the rank inside it, sh.bin_cnt = 1; fewer than kk keys: sh.bin_cnt = 0xFFFFFFFF.  All threads
-// call; the words are readable on return (and rewritten by the next call: a barrier before that).
+// -> sh.rx.prefix = the digit, sh.rx.kk = the rank inside it, sh.rx.bin_cnt = 1; fewer than kk keys: sh.rx.bin_cnt = 0xFFFFFFFF.
+// All threads call; the words are readable on return (and rewritten by the next call: a barrier before that).
 __device__ __forceinline__ void sel_rank_bin2k(SelShared &sh, uint32_t kk, int pass) {
     const uint32_t tid = threadIdx.x;
     { // 64 super-bins of 32 bins: a thread adds two bins, a DPP row (16 lanes) the 32 of a super-bin -- conflict-free reads
@@ -413,15 +234,15 @@ __device__ __forceinline__ void sel_rank_bin2k(SelShared &sh, uint32_t kk, int p
         v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
         v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
         v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
-        if ((tid & 15u) == 15u) sh.hist[tid >> 4] = v; // super-bin s = bins [32 s, 32 s + 32)
+        if ((tid & 15u) == 15u) sh.rx.hist[tid >> 4] = v; // super-bin s = bins [32 s, 32 s + 32)
     }
     __syncthreads();
     if (tid < 64) { // wave 0: the super-bin, then the bin, holding the kk-th key counted from the top -- two scans, no walk
-        const uint32_t x = sh.hist[63u - tid];
+        const uint32_t x = sh.rx.hist[63u - tid];
         const uint32_t incl = oi_wave_incl_scan(x);
         const unsigned long long ball = __ballot(incl >= kk);
         if (!ball) {
-            if (tid == 0) sh.bin_cnt = 0xFFFFFFFFu; // fewer than kk valid keys
+            if (tid == 0) sh.rx.bin_cnt = 0xFFFFFFFFu; // fewer than kk valid keys
         } else {
             const uint32_t l1 = (uint32_t)__builtin_ctzll(ball), sb = 63u - l1;
             const uint32_t kk2 = kk - (uint32_t)__builtin_amdgcn_readlane((int)(incl - x), (int)l1);
@@ -432,16 +253,16 @@ __device__ __forceinline__ void sel_rank_bin2k(SelShared &sh, uint32_t kk, int p
             // (read with every lane active: inside the one-lane branch below hipcc computes incl2 - y for that lane only)
             const uint32_t above = (uint32_t)__builtin_amdgcn_readlane((int)(incl2 - y), (int)l2);
             if (tid == 0) {
-                sh.prefix = (uint64_t)(32u * sb + 31u - l2);
-                sh.kk = kk2 - above;
-                sh.bin_cnt = 1u;
+                sh.rx.prefix = (uint64_t)(32u * sb + 31u - l2);
+                sh.rx.kk = kk2 - above;
+                sh.rx.bin_cnt = 1u;
 #ifdef OI_ABLATION
                 if (sel_dbg_on > 1) { // OI_SELECT_STAMPS=2: self-check against the plain walk from the top
                     uint32_t cum = 0; int dd = 2047;
                     for (; dd >= 0; --dd) { if (cum + sh.hist2k[dd] >= kk) break; cum += sh.hist2k[dd]; }
-                    if ((uint32_t)dd != (uint32_t)sh.prefix || kk - cum != sh.kk)
+                    if ((uint32_t)dd != (uint32_t)sh.rx.prefix || kk - cum != sh.rx.kk)
                         printf("MISMATCH q=%u pass=%d kk=%u: walk (%d, %u) super-bin (%u, %u) sb=%u l1=%u kk2=%u l2=%u\n", blockIdx.x, pass, kk, dd, kk - cum,
-                               (uint32_t)sh.prefix, sh.kk, sb, l1, kk2, l2);
+                               (uint32_t)sh.rx.prefix, sh.rx.kk, sb, l1, kk2, l2);
                 }
 #endif
             }
@@ -450,10 +271,27 @@ __device__ __forceinline__ void sel_rank_bin2k(SelShared &sh, uint32_t kk, int p
     __syncthreads();
 }
 
+// One pass of a thread's keys into sh.hist2k by their leading 11 bits (sign, exponent, two bits of mantissa).  A pool of
+// near-threshold scores takes a handful of such digits: a thread adds its keys up in runs first, and the wave its threads'
+// last runs (one LDS address each).
+template <class FE>
+__device__ __forceinline__ void sel_hist_leading(FE &&for_each, SelShared &sh) {
+    uint32_t run_d = 0, run_c = 0;
+    for_each([&](bool valid, uint64_t kv) {
+        if (valid) {
+            const uint32_t d = (uint32_t)(kv >> 53);
+            if (run_c && d != run_d) { atomicAdd(&sh.hist2k[run_d], run_c); run_c = 0; }
+            run_d = d;
+            ++run_c;
+        }
+    });
+    sel_hist_add_w(sh.hist2k, run_c != 0u, run_d, run_c);
+}
+
 // The r-th largest 32-bit score key of the keys `for_each` enumerates (f(valid, key), the same keys on every call; 1 <= r <= their
 // number): digits of 11, 11 and 10 bits from the top through the same histogram.  This is the key pf_spec_kernel
 // (cosine_prefilter.hip) finds in the carry region -- the r-th largest of a set is unique -- taken from the keys the select
-// already holds.  All threads call; the result is uniform.  sh.hist2k / prefix / kk / bin_cnt are free on entry and on return.
+// already holds.  All threads call; the result is uniform.  sh.hist2k / sh.rx's words are free on entry and on return.
 template <class FE>
 __device__ __forceinline__ uint32_t sel_rth_score_key(FE &&for_each, uint32_t r, SelShared &sh) {
     const uint32_t tid = threadIdx.x;
@@ -464,17 +302,8 @@ __device__ __forceinline__ uint32_t sel_rth_score_key(FE &&for_each, uint32_t r,
         sh.hist2k[tid] = 0;
         sh.hist2k[tid + SEL_THREADS] = 0;
         __syncthreads();
-        if (pass == 0) { // (few leading digits: runs per thread, then per wave, as in the margin select's first pass)
-            uint32_t run_d = 0, run_c = 0;
-            for_each([&](bool valid, uint64_t kv) {
-                if (valid) {
-                    const uint32_t d = (uint32_t)(kv >> 53);
-                    if (run_c && d != run_d) { atomicAdd(&sh.hist2k[run_d], run_c); run_c = 0; }
-                    run_d = d;
-                    ++run_c;
-                }
-            });
-            sel_hist_add_w(sh.hist2k, run_c != 0u, run_d, run_c);
+        if (pass == 0) {
+            sel_hist_leading(for_each, sh);
         } else {
             for_each([&](bool valid, uint64_t kv) {
                 const uint32_t sk = (uint32_t)(kv >> 32);
@@ -483,65 +312,184 @@ __device__ __forceinline__ uint32_t sel_rth_score_key(FE &&for_each, uint32_t r,
         }
         __syncthreads();
         sel_rank_bin2k(sh, kk, 2 + pass);
-        const uint32_t d = sh.bin_cnt != 0xFFFFFFFFu ? (uint32_t)sh.prefix : 0u; // (r <= the number of keys: always found)
-        kk = sh.kk;
+        const uint32_t d = sh.rx.bin_cnt != 0xFFFFFFFFu ? (uint32_t)sh.rx.prefix : 0u; // (r <= the number of keys: always found)
+        kk = sh.rx.kk;
         __syncthreads();
         pfx = (pfx << bits) | d;
     }
     return pfx;
 }
+// ... of the array a[0..m), m >= r
+__device__ __forceinline__ uint32_t sel_rth_score_key_of(const uint64_t *a, uint32_t m, uint32_t r, SelShared &sh) {
+    const uint32_t tid = threadIdx.x;
+    return sel_rth_score_key([&](auto &&f) {
+        for (uint32_t i0 = 0; i0 < m; i0 += SEL_THREADS) f(i0 + tid < m, a[i0 + tid < m ? i0 + tid : 0]);
+    }, r, sh);
+}
 
-// Selects the top min(n, k) keys of K into sel[], returns their number.  KPT > 0: the keys live in registers
-// (n <= KPT * SEL_THREADS); KPT == 0: every pass re-loads them through the flat view.  sh.cnt == 0 on entry.
-//
-// Margin mode (eps2 >= 0; the bf16 screen of cosine_prefilter.hip): the result is not the top k but EVERY key whose
-// score is within eps2 of the k-th largest score -- the set that must survive for the exact top k to be inside
-// it -- left in cand[] (*in_cand = true), at most SEL_CAND keys (more: *margin_overflow = true, the caller opens
-// the exact pipeline), and *margin_tau = the orderable key of (k-th score - eps2), the next chunk's threshold.
-template <int KPT>
-__device__ __forceinline__ uint32_t sel_flat_select(const SelFlat &K, uint32_t k, SelShared &sh, uint64_t *sel,
-                                                    uint64_t *cand, float eps2, bool *in_cand, uint32_t *margin_tau,
-                                                    bool *margin_overflow, const uint32_t *skip, uint32_t skip_base,
-                                                    uint64_t *mc, uint32_t mcap, const SelRowMargin *rm, uint64_t *carry,
-                                                    bool *in_carry, uint32_t spec_rank, uint32_t *spec_key) {
-    // carry (KPT > 0, the fast margin path): this query's carry region.  Every key of the pool is in registers before the first
-    // barrier, so the survivors are written there directly (*in_carry = true) instead of to mc and copied; and with spec_rank
-    // = r, r <= the survivors kept, *spec_key = the r-th largest score key among them (sel_rth_score_key), else left alone.
-    // skip (the screen's two-class margin): keys of docs marked in this bitmap do not take part -- they are scored exactly
-    // whatever happens here, and their screen scores must not move the threshold (cosine_prefilter.hip)
-    auto skipped = [&](uint64_t kv) -> bool {
-        const uint32_t d = oi_rank_key_doc(kv) - skip_base;
-        return (skip[d >> 5] >> (d & 31u)) & 1u;
-    };
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = K.n;
-    *in_cand = false;
-    *margin_overflow = false;
-    if (n == 0) return 0;
-    const uint32_t kpt = (n + SEL_THREADS - 1) / SEL_THREADS; // keys per thread; wave w owns [w*kpt*64, (w+1)*kpt*64)
-    const uint32_t first = wv * kpt * 64 + lane, last = n - 1;
-    constexpr int NR = KPT > 0 ? KPT : 1;
-    uint64_t key[NR];
-    uint32_t dead = 0; // bit j: key[j] is a skipped doc's
-    if constexpr (KPT > 0) {
-        SelCursor cur = sel_seek(K, first < n ? first : last);
-        uint64_t at = sel_at(K, cur, first < n ? first : last);
-#pragma unroll
-        for (int j = 0; j < KPT; ++j) { // loads unpredicated (a slot past the end re-reads the previous key): all in flight
-            const uint32_t i = first + (uint32_t)j * 64;
-            if ((uint32_t)j < kpt && i < n) at = sel_at(K, cur, i); // the cursor only walks forward
-            key[j] = K.pool[at];
+// The tail of both kernels.  Reads sel[0..m), the selected set (LDS, barrier passed), and *min_key (LDS, ~0).  Sorted output is
+// needed only for a final list (a.out_scores); an intermediate compaction just needs the set and its smallest key, left in
+// *min_key.  a.compact: the pool is rewritten as carry = the selected keys, all segments empty, and the threshold raised to the
+// k-th score, so the next corpus chunk appends after them.  All threads call; returns past a barrier.
+__device__ __forceinline__ void sel_finish(const SelArgs &a, uint32_t q, uint64_t *pool, uint32_t *segc, uint64_t *sel, uint32_t m,
+                                           unsigned long long *min_key) {
+    const uint32_t tid = threadIdx.x;
+    if (a.out_scores) {
+        uint32_t P = 2;
+        while (P < m) P <<= 1;
+        for (uint32_t i = m + tid; i < P; i += SEL_THREADS) sel[i] = 0; // lowest possible key
+        __syncthreads();
+        bitonic_sort_desc(sel, P);
+        for (uint32_t i = tid; i < m; i += SEL_THREADS) {
+            const uint64_t key = sel[i];
+            a.out_scores[(uint64_t)q * a.out_stride + i] = oi_rank_key_score(key);
+            a.out_docs[(uint64_t)q * a.out_stride + i] = oi_rank_key_doc(key);
         }
-        if (skip) {
-#pragma unroll
-            for (int j = 0; j < KPT; ++j)
-                if ((uint32_t)j < kpt && first + (uint32_t)j * 64 < n && skipped(key[j])) dead |= 1u << j;
+        if (tid == 0) { a.out_counts[q] = m; *min_key = m ? sel[m - 1] : 0; }
+    } else {
+        sel_min_key(sel, m, min_key);
+    }
+    __syncthreads();
+    if (a.compact) {
+        for (uint32_t i = tid; i < m; i += SEL_THREADS) pool[i] = sel[i];
+        for (uint32_t sg = tid; sg < a.n_segs; sg += SEL_THREADS) segc[sg] = 0;
+        if (tid == 0) {
+            a.carry_cnt[q] = m;
+            if (m == a.k && a.tau_keys && !a.eps2) { // k docs at or above this score exist: a valid lower bound of the final
+                // k-th, so later chunks may drop anything strictly below it (a margin-mode pool of exactly k keys keeps its
+                // threshold: that bound needs the margin)
+                const uint32_t t = (uint32_t)(*min_key >> 32);
+                if (t > a.tau_keys[q]) a.tau_keys[q] = t;
+            }
         }
     }
-    auto for_each = [&](auto &&f) {
+}
+
+// ---------------------------------------------------------------------------------------------------
+// select_flat_kernel: the selection with the pool seen as ONE flat array.
+//
+// select_topk_kernel (below) walks the pool a segment at a time (one wave per segment: a dependent count -> keys
+// load chain per segment, repeated on every radix pass when the pool does not fit its LDS copy); with the
+// 256 short segments a cosine chunk leaves behind, that chain IS the select (40-120 us per launch, on the
+// critical path between two corpus chunks).  Here
+//   * the segment counts are scanned once into LDS offsets; flat index -> (segment, slot) is one binary
+//     search per lane and then a forward walk, because wave w owns the contiguous flat range
+//     [w*kpt*64, (w+1)*kpt*64) and reads it 64 consecutive keys per load (coalesced, all loads in flight);
+//   * the keys then live in REGISTERS (<= 32 per thread: pools up to 32K keys) for everything that follows;
+//     larger pools re-load through the same flat view on every pass;
+//   * pools above 4K keys are cut down first: the threshold that keeps ~2k keys is read off a 1024-key
+//     sample (radix select over one key per thread), one filter pass moves the survivors to LDS, and the
+//     exact selection runs over those.  A sample that keeps fewer than k or more than 4096 keys falls back
+//     to the exact passes over the whole pool: the RESULT never depends on the sample;
+//   * histogram and append atomics are aggregated per wave first (the leading digits of a pool of
+//     near-threshold scores are nearly all equal, i.e. one LDS address).
+struct SelFlat {
+    const uint64_t *pool;
+    const uint32_t *seg_off; // LDS, n_segs + 1 entries, seg_off[n_segs] = keys in segments
+    uint32_t n, c0, carry_cap, seg_cap, n_segs, steps;
+};
+// A lane's position in the flat view: segment sg holds the segment-relative flat indices [lo, hi).
+struct SelCursor {
+    uint32_t sg, lo, hi;
+};
+// flat index i < n  ->  cursor at its segment (binary search; indices inside the carry region map to e = 0)
+__device__ __forceinline__ SelCursor sel_seek(const SelFlat &K, uint32_t i) {
+    const uint32_t e = i < K.c0 ? 0u : i - K.c0;
+    uint32_t lo = 0, hi = K.n_segs; // seg_off[lo] <= e < seg_off[hi]
+    for (uint32_t s = 0; s < K.steps; ++s) {
+        const uint32_t mid = (lo + hi) >> 1;
+        const bool up = K.seg_off[mid] <= e;
+        lo = up ? mid : lo;
+        hi = up ? hi : mid;
+    }
+    SelCursor c;
+    c.sg = lo; c.lo = K.seg_off[lo]; c.hi = K.seg_off[lo + 1];
+    return c;
+}
+// pool offset of flat index i < n, i >= every index this cursor was used for before (forward walk)
+__device__ __forceinline__ uint64_t sel_at(const SelFlat &K, SelCursor &c, uint32_t i) {
+    if (i < K.c0) return i;
+    const uint32_t e = i - K.c0;
+    while (e >= c.hi) { // e < seg_off[n_segs]: stops at the segment that holds e (skips empty ones)
+        ++c.sg;
+        c.lo = c.hi;
+        c.hi = K.seg_off[c.sg + 1];
+    }
+    return (uint64_t)K.carry_cap + (uint64_t)c.sg * K.seg_cap + (e - c.lo);
+}
+
+// Margin mode of one query (eps2 >= 0; the bf16 screen of cosine_prefilter.hip, the int8 tier): the result is not the top k but
+// EVERY key whose score is within eps2 of the k-th largest score -- the set that must survive for the exact top k to be inside it.
+struct SelMargin {
+    float eps2;           // < 0: not a margin select; +inf: a query without a bound (keeps everything, raises nothing)
+    // the screen's two-class margin: keys of docs marked in this bitmap (bit doc - skip_base) do not take part -- they are scored
+    // exactly whatever happens here, and their screen scores must not move the threshold (cosine_prefilter.hip).  Null: none
+    const uint32_t *skip;
+    uint32_t skip_base;
+    uint64_t *cand;       // the survivors' staging buffer (LDS, or the caller's global one) of `cap` keys
+    uint32_t cap;
+    uint64_t *carry;      // this query's carry region: sel_margin_bins with the keys in registers writes the survivors there
+    uint32_t spec_rank;   // r > 0: the prediction, the r-th largest score key among the survivors kept (sel_rth_score_key)
+    SelRowMargin rows;    // meta == nullptr: none (also when eps2 is +inf)
+};
+// What a select leaves: m keys in sel[], or -- in_cand, margin mode -- m survivors (at most M.cap; overflow: there were more,
+// the caller opens the exact pipeline) in M.cand, or in M.carry already (in_carry), tau = the orderable key of (k-th score -
+// eps2), the next chunk's threshold, and spec_key = the prediction where the stage already made it.
+struct SelResult {
+    uint32_t m;
+    bool in_cand, overflow, in_carry;
+    uint32_t tau, spec_key;
+};
+// ... of a margin stage that counted c survivors into a buffer of cap keys
+__device__ __forceinline__ SelResult sel_margin_result(uint32_t c, uint32_t cap, uint32_t tau, bool in_carry) {
+    return SelResult{c > cap ? cap : c, true, c > cap, in_carry, tau, 0u};
+}
+
+// The keys of a thread.  KPT > 0: they live in registers (n <= KPT * SEL_THREADS), key[j] = flat index first + 64 j, dead bit j =
+// key[j] is a skipped doc's; KPT == 0: for_each re-loads them through the flat view on every pass.  kpt = keys per thread; wave
+// w owns [w*kpt*64, (w+1)*kpt*64).  for_each(f) calls f(valid, key) kpt times (wave-uniform; 4-rounded for KPT == 0).
+template <int KPT>
+struct SelKeys {
+    static constexpr int NR = KPT > 0 ? KPT : 1;
+    const SelFlat &K;
+    const uint32_t *const skip;
+    const uint32_t skip_base;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = K.n;
+    const uint32_t kpt = (n + SEL_THREADS - 1) / SEL_THREADS;
+    const uint32_t first = wv * kpt * 64 + lane, last = n - 1;
+    uint64_t key[NR];
+    uint32_t dead = 0;
+
+    __device__ __forceinline__ SelKeys(const SelFlat &K_, const SelMargin &M) : K(K_), skip(M.skip), skip_base(M.skip_base) {}
+    __device__ __forceinline__ bool skipped(uint64_t kv) const {
+        const uint32_t d = oi_rank_key_doc(kv) - skip_base;
+        return (skip[d >> 5] >> (d & 31u)) & 1u;
+    }
+    // key[j] is a key of the pool (j < kpt) and takes part
+    __device__ __forceinline__ bool live(int j) const { return first + (uint32_t)j * 64 < n && !((dead >> j) & 1u); }
+    __device__ __forceinline__ void load() { // n > 0
+        if constexpr (KPT > 0) {
+            SelCursor cur = sel_seek(K, first < n ? first : last);
+            uint64_t at = sel_at(K, cur, first < n ? first : last);
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) { // loads unpredicated (a slot past the end re-reads the previous key): all in flight
+                const uint32_t i = first + (uint32_t)j * 64;
+                if ((uint32_t)j < kpt && i < n) at = sel_at(K, cur, i); // the cursor only walks forward
+                key[j] = K.pool[at];
+            }
+            if (skip) {
+#pragma unroll
+                for (int j = 0; j < KPT; ++j)
+                    if ((uint32_t)j < kpt && first + (uint32_t)j * 64 < n && skipped(key[j])) dead |= 1u << j;
+            }
+        }
+    }
+    template <class F>
+    __device__ __forceinline__ void for_each(F &&f) const {
         if constexpr (KPT > 0) {
 #pragma unroll
             for (int j = 0; j < KPT; ++j)
-                if ((uint32_t)j < kpt) f(first + (uint32_t)j * 64 < n && !((dead >> j) & 1u), key[j]); // uniform guard
+                if ((uint32_t)j < kpt) f(live(j), key[j]); // uniform guard
         } else {
             SelCursor cur = sel_seek(K, first < n ? first : last);
             uint64_t at = sel_at(K, cur, first < n ? first : last);
@@ -559,253 +507,291 @@ __device__ __forceinline__ uint32_t sel_flat_select(const SelFlat &K, uint32_t k
                 for (int u = 0; u < 4; ++u) f(ok[u] && !(skip && skipped(kx[u])), kx[u]);
             }
         }
-    };
-    if (n <= k) {
-        for_each([&](bool valid, uint64_t kv) { sel_append(sel, &sh.cnt, 2 * SEL_MAX, valid, kv); });
+    }
+};
+
+// ---- stage: take-all (n <= k).  Leaves every live key in sel[], sh.cnt = their number (0 on entry); returns it.
+template <int KPT>
+__device__ __forceinline__ uint32_t sel_take_all(const SelKeys<KPT> &H, SelShared &sh, uint64_t *sel) {
+    H.for_each([&](bool valid, uint64_t kv) { sel_append(sel, &sh.cnt, 2 * SEL_MAX, valid, kv); });
+    __syncthreads();
+    return H.skip ? sh.cnt : H.n; // (skipped keys were not appended)
+}
+
+// ---- stage: margin bins, the fast path of margin mode.  What the next chunk and the rescoring need is ANY lower bound tau' of the
+// k-th largest screen score and every key within eps2 of tau' -- not the k-th key itself.  Two passes of 11-bit digits
+// over the valid keys find the 22-bit bin (sign, exponent, 13 bits of mantissa) that holds the k-th largest; its LOWER
+// EDGE is tau': at least k keys are >= it, and it is below the k-th score by < 2^-13 of its size, ~1e-5 where the margin
+// is ~4e-3, so the survivor set grows by a fraction of a percent.  (The exact stages: a 1024-key sample, 4-7 passes of
+// 8-bit digits over the sample, a cut, 4-7 more over the cut, the k-th key, then the margin filter -- 25-30 us per launch
+// between two corpus chunks; this one: two histogram passes and the filter.)
+// Uses sh.hist2k and sh.rx (free on entry and on return); sh.cnt (0 on entry) = the survivors on return.  Fewer than k valid
+// keys: in_cand stays false, nothing but hist2k / rx was touched, and the exact stages follow.
+template <int KPT>
+__device__ __forceinline__ SelResult sel_margin_bins(const SelKeys<KPT> &H, uint32_t k, const SelMargin &M, SelShared &sh) {
+    const uint32_t tid = H.tid, lane = H.lane, kpt = H.kpt;
+    const float eps2 = M.eps2;
+    SelResult R = {};
+    uint32_t kk = k, pfx = 0;
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+        const int shift = 53 - 11 * pass;
+        sh.hist2k[tid] = 0;
+        sh.hist2k[tid + SEL_THREADS] = 0;
         __syncthreads();
-        return skip ? sh.cnt : n; // (skipped keys were not appended)
-    }
-    SEL_STAMP(2);
-    if (eps2 >= 0.f) {
-        // ---- margin mode, the fast path (round 4).  What the next chunk and the rescoring need is ANY lower bound tau' of the
-        // k-th largest screen score and every key within eps2 of tau' -- not the k-th key itself.  Two passes of 11-bit digits
-        // over the valid keys find the 22-bit bin (sign, exponent, 13 bits of mantissa) that holds the k-th largest; its LOWER
-        // EDGE is tau': at least k keys are >= it, and it is below the k-th score by < 2^-13 of its size, ~1e-5 where the margin
-        // is ~4e-3, so the survivor set grows by a fraction of a percent.  (The exact path below: a 1024-key sample, 4-7 passes of
-        // 8-bit digits over the sample, a cut, 4-7 more over the cut, the k-th key, then the margin filter -- 25-30 us per launch
-        // between two corpus chunks; this one: two histogram passes and the filter.)  Fewer than k valid keys: the exact path.
-        uint32_t kk = k;
-        uint32_t pfx = 0;
-        bool enough = true;
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            const int shift = 53 - 11 * pass;
-            sh.hist2k[tid] = 0;
-            sh.hist2k[tid + SEL_THREADS] = 0;
-            __syncthreads();
-            if (pass == 0) {
-                // the leading digit (sign, exponent, two bits of mantissa) of a pool of near-threshold scores takes a handful of
-                // values: a thread adds its keys up in runs first, and the wave its threads' last runs (one LDS address each)
-                uint32_t run_d = 0, run_c = 0;
-                for_each([&](bool valid, uint64_t kv) {
-                    if (valid) {
-                        const uint32_t d = (uint32_t)(kv >> 53);
-                        if (run_c && d != run_d) { atomicAdd(&sh.hist2k[run_d], run_c); run_c = 0; }
-                        run_d = d;
-                        ++run_c;
-                    }
-                });
-                sel_hist_add_w(sh.hist2k, run_c != 0u, run_d, run_c);
-            } else { // 11 bits of mantissa inside one leading bin: spread over the 2048 addresses, plain atomics
-                for_each([&](bool valid, uint64_t kv) {
-                    if (valid && (uint32_t)(kv >> 53) == pfx) atomicAdd(&sh.hist2k[(uint32_t)(kv >> shift) & 2047u], 1u);
-                });
-            }
-            __syncthreads();
-            sel_rank_bin2k(sh, kk, pass);
-            enough = sh.bin_cnt != 0xFFFFFFFFu;
-            const uint32_t d = (uint32_t)sh.prefix;
-            kk = sh.kk;
-            __syncthreads(); // (sh.prefix / sh.kk / sh.bin_cnt are rewritten by the next pass or the exact path)
-            if (!enough) break;
-            if (pass == 0) pfx = d;
-            else pfx = (pfx << 11) | d;
-            SEL_STAMP(3 + pass);
+        if (pass == 0) {
+            sel_hist_leading([&](auto &&f) { H.for_each(f); }, sh);
+        } else { // 11 bits of mantissa inside one leading bin: spread over the 2048 addresses, plain atomics
+            H.for_each([&](bool valid, uint64_t kv) {
+                if (valid && (uint32_t)(kv >> 53) == pfx) atomicAdd(&sh.hist2k[(uint32_t)(kv >> shift) & 2047u], 1u);
+            });
         }
-        if (enough) {
-            uint32_t tkey = pfx << 10; // the bin's lower edge as a 32-bit score key
-            tkey = tkey < 0x007FFFFFu ? 0x007FFFFFu : tkey; // (below key(-inf) the bit pattern is a NaN's: -inf instead)
-            const uint32_t t32 = eps2 < __builtin_inff() ? oi_f32_key(oi_key_f32(tkey) - eps2) : 0u;
-            // the filter: a thread counts its survivors, the wave takes ONE slot range for all of them
-            uint32_t mine = 0;
-            const float edge = oi_key_f32(tkey);
-            auto keep = [&](bool valid, uint64_t kv) { return valid && (uint32_t)(kv >> 32) >= t32 && sel_row_keep(rm, kv, edge, eps2); };
-            uint32_t verdict = 0; // KPT > 0, bit j: key[j] survives -- each key is tested ONCE, the storing pass reads the mask
-            if constexpr (KPT > 0) {
-#pragma unroll
-                for (int j = 0; j < KPT; ++j) // the cheap global test first
-                    if ((uint32_t)j < kpt && first + (uint32_t)j * 64 < n && !((dead >> j) & 1u) && (uint32_t)(key[j] >> 32) >= t32) verdict |= 1u << j;
-                if (rm) { // the row test: the gathers of a group of keys that passed are issued together, then evaluated
-                    constexpr int G = KPT < 8 ? KPT : 8;
-#pragma unroll
-                    for (int j0 = 0; j0 < KPT; j0 += G) {
-                        if ((uint32_t)j0 < kpt) { // (uniform)
-                            float e[G];
-#pragma unroll
-                            for (int u = 0; u < G; ++u) e[u] = (verdict >> (j0 + u)) & 1u ? sel_row_e(rm, key[j0 + u]) : 0.f;
-#pragma unroll
-                            for (int u = 0; u < G; ++u)
-                                if (((verdict >> (j0 + u)) & 1u) && !sel_row_test(rm, key[j0 + u], e[u], edge, eps2)) verdict &= ~(1u << (j0 + u));
-                        }
-                    }
-                }
-                mine = (uint32_t)__popc(verdict);
-            } else {
-                for_each([&](bool valid, uint64_t kv) { mine += keep(valid, kv) ? 1u : 0u; });
-            }
-            const uint32_t incl = oi_wave_incl_scan(mine);
-            const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            uint32_t base = 0;
-            if (lane == 0 && tot) base = atomicAdd(&sh.cnt, tot);
-            uint32_t pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)base) + incl - mine;
-            if constexpr (KPT > 0) {
-                uint32_t stored = 0; // bit j: key[j] went into the carry region (all of verdict unless the survivors overflow it)
-#pragma unroll
-                for (int j = 0; j < KPT; ++j) {
-                    if ((verdict >> j) & 1u) {
-                        if (pos < mcap) { carry[pos] = key[j]; stored |= 1u << j; }
-                        ++pos;
-                    }
-                }
-                *in_carry = true;
-                __syncthreads();
-                const uint32_t c = sh.cnt, kept = c > mcap ? mcap : c;
-                SEL_STAMP(5);
-                if (spec_rank && kept >= spec_rank) // (uniform) the prediction, over the keys that were stored
-                    *spec_key = sel_rth_score_key([&](auto &&f) {
-#pragma unroll
-                        for (int j = 0; j < KPT; ++j)
-                            if ((uint32_t)j < kpt) f((stored >> j) & 1u, key[j]);
-                    }, spec_rank, sh);
-                *in_cand = true;
-                *margin_tau = t32;
-                *margin_overflow = c > mcap;
-                return kept;
-            } else {
-                for_each([&](bool valid, uint64_t kv) {
-                    if (keep(valid, kv)) {
-                        if (pos < mcap) mc[pos] = kv;
-                        ++pos;
-                    }
-                });
-            }
-            __syncthreads();
-            const uint32_t c = sh.cnt;
-            *in_cand = true;
-            *margin_tau = t32;
-            *margin_overflow = c > mcap;
-            SEL_STAMP(5);
-            return c > mcap ? mcap : c;
-        }
+        __syncthreads();
+        sel_rank_bin2k(sh, kk, pass);
+        const bool enough = sh.rx.bin_cnt != 0xFFFFFFFFu;
+        const uint32_t d = (uint32_t)sh.rx.prefix;
+        kk = sh.rx.kk;
+        __syncthreads(); // (sh.rx's words are rewritten by the next pass or the exact stages)
+        if (!enough) return R;
+        if (pass == 0) pfx = d;
+        else pfx = (pfx << 11) | d;
+        SEL_STAMP(3 + pass);
     }
+    uint32_t tkey = pfx << 10; // the bin's lower edge as a 32-bit score key
+    tkey = tkey < 0x007FFFFFu ? 0x007FFFFFu : tkey; // (below key(-inf) the bit pattern is a NaN's: -inf instead)
+    const uint32_t t32 = eps2 < __builtin_inff() ? oi_f32_key(oi_key_f32(tkey) - eps2) : 0u;
+    // the filter: a thread counts its survivors, the wave takes ONE slot range for all of them
+    uint32_t mine = 0;
+    const float edge = oi_key_f32(tkey);
+    auto keep = [&](bool valid, uint64_t kv) { return valid && (uint32_t)(kv >> 32) >= t32 && sel_row_keep(M.rows, kv, edge, eps2); };
+    uint32_t verdict = 0; // KPT > 0, bit j: key[j] survives -- each key is tested ONCE, the storing pass reads the mask
+    if constexpr (KPT > 0) {
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) // the cheap global test first
+            if ((uint32_t)j < kpt && H.live(j) && (uint32_t)(H.key[j] >> 32) >= t32) verdict |= 1u << j;
+        if (M.rows.meta) { // the row test: the gathers of a group of keys that passed are issued together, then evaluated
+            constexpr int G = KPT < 8 ? KPT : 8;
+#pragma unroll
+            for (int j0 = 0; j0 < KPT; j0 += G) {
+                if ((uint32_t)j0 < kpt) { // (uniform)
+                    float e[G];
+#pragma unroll
+                    for (int u = 0; u < G; ++u) e[u] = (verdict >> (j0 + u)) & 1u ? sel_row_e(M.rows, H.key[j0 + u]) : 0.f;
+#pragma unroll
+                    for (int u = 0; u < G; ++u)
+                        if (((verdict >> (j0 + u)) & 1u) && !sel_row_test(M.rows, H.key[j0 + u], e[u], edge, eps2)) verdict &= ~(1u << (j0 + u));
+                }
+            }
+        }
+        mine = (uint32_t)__popc(verdict);
+    } else {
+        H.for_each([&](bool valid, uint64_t kv) { mine += keep(valid, kv) ? 1u : 0u; });
+    }
+    const uint32_t incl = oi_wave_incl_scan(mine);
+    const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    uint32_t base = 0;
+    if (lane == 0 && tot) base = atomicAdd(&sh.cnt, tot);
+    uint32_t pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)base) + incl - mine;
+    uint32_t stored = 0; // KPT > 0, bit j: key[j] went into the carry region (all of verdict unless the survivors overflow it)
+    if constexpr (KPT > 0) { // every key of the pool has been in registers since before the first barrier: straight to the carry region
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {
+            if ((verdict >> j) & 1u) {
+                if (pos < M.cap) { M.carry[pos] = H.key[j]; stored |= 1u << j; }
+                ++pos;
+            }
+        }
+    } else {
+        H.for_each([&](bool valid, uint64_t kv) {
+            if (keep(valid, kv)) {
+                if (pos < M.cap) M.cand[pos] = kv;
+                ++pos;
+            }
+        });
+    }
+    __syncthreads();
+    R = sel_margin_result(sh.cnt, M.cap, t32, KPT > 0);
+    SEL_STAMP(5);
+    if constexpr (KPT > 0) {
+        if (M.spec_rank && R.m >= M.spec_rank) // (uniform) the prediction, over the keys that were stored
+            R.spec_key = sel_rth_score_key([&](auto &&f) {
+#pragma unroll
+                for (int j = 0; j < KPT; ++j)
+                    if ((uint32_t)j < kpt) f((stored >> j) & 1u, H.key[j]);
+            }, M.spec_rank, sh);
+    }
+    return R;
+}
+
+// ---- stage: sampled cut (pools above SEL_CAND keys).  One key per thread, spread over the wave's range, is the sample; the
+// threshold that keeps ~2k keys is read off it and the keys above it go to cand[] (LDS).  True: the cut held between k and
+// SEL_CAND keys and sel[0..k) is the top k, sh.cnt = k.  False: the sample misjudged the pool, sh.cnt = 0 as on entry, cand[]
+// is garbage, and sel_exact follows.  Uses sh.rx and sh.n_samples.
+template <int KPT>
+__device__ __forceinline__ bool sel_sampled_cut(const SelKeys<KPT> &H, uint32_t k, SelShared &sh, uint64_t *sel, uint64_t *cand) {
+    const uint32_t tid = H.tid, lane = H.lane, kpt = H.kpt, first = H.first, last = H.last, n = H.n;
     int shift;
     uint64_t prefix;
-    bool selected = false; // sel[0..k) holds the top k
-    if (KPT != 4 && n > SEL_CAND) {
-        // ---- cut the pool down with a sampled threshold: one key per thread, spread over the wave's range
-        const uint32_t js = lane % kpt, is = first + js * 64;
-        bool sv = is < n;
-        uint64_t sk;
-        if constexpr (KPT > 0) {
-            sk = key[0];
+    const uint32_t js = lane % kpt, is = first + js * 64;
+    bool sv = is < n;
+    uint64_t sk;
+    if constexpr (KPT > 0) {
+        sk = H.key[0];
 #pragma unroll
-            for (int j = 1; j < KPT; ++j) sk = (uint32_t)j == js ? key[j] : sk;
-            sv = sv && !((dead >> js) & 1u);
-        } else {
-            SelCursor cur = sel_seek(K, sv ? is : last);
-            sk = K.pool[sel_at(K, cur, sv ? is : last)];
-            sv = sv && !(skip && skipped(sk));
-        }
-        if (tid == 0) sh.n_samples = 0;
-        __syncthreads();
-        {
-            const unsigned long long m = __ballot(sv);
-            if (lane == 0 && m) atomicAdd(&sh.n_samples, (uint32_t)__popcll(m));
-        }
-        __syncthreads();
-        const uint32_t ns = sh.n_samples;
-        uint32_t r = (uint32_t)(((uint64_t)ns * (2 * k) + n - 1) / n) + 1; // keeps ~2k keys (+1 sample of margin)
-        r = r > ns ? ns : r;
-        sel_threshold([&](auto &&f) { f(sv, sk); }, r, sh, shift, prefix);
-        for_each([&](bool valid, uint64_t kv) { sel_append(cand, &sh.cnt, SEL_CAND, valid && (kv >> shift) >= prefix, kv); });
-        __syncthreads();
-        const uint32_t c = sh.cnt;
-        __syncthreads();
-        if (tid == 0) sh.cnt = 0;
-        __syncthreads();
-        if (c >= k && c <= SEL_CAND) { // the top k of the pool are the top k of cand[0..c)
-            uint64_t ck[SEL_CAND / SEL_THREADS];
-#pragma unroll
-            for (int j = 0; j < SEL_CAND / SEL_THREADS; ++j) {
-                const uint32_t i = (uint32_t)j * SEL_THREADS + tid;
-                ck[j] = cand[i < c ? i : c - 1];
-            }
-            auto cand_each = [&](auto &&f) {
-#pragma unroll
-                for (int j = 0; j < SEL_CAND / SEL_THREADS; ++j)
-                    if ((uint32_t)j * SEL_THREADS < c) f((uint32_t)j * SEL_THREADS + tid < c, ck[j]);
-            };
-            if (c == k) { // nothing to select
-                cand_each([&](bool valid, uint64_t kv) { sel_append(sel, &sh.cnt, SEL_MAX, valid, kv); });
-            } else {
-                sel_threshold(cand_each, k, sh, shift, prefix);
-                cand_each([&](bool valid, uint64_t kv) { sel_append(sel, &sh.cnt, SEL_MAX, valid && (kv >> shift) >= prefix, kv); });
-            }
-            __syncthreads();
-            selected = true;
-        }
-        // else: the sample misjudged the pool -- exact passes over all of it
+        for (int j = 1; j < KPT; ++j) sk = (uint32_t)j == js ? H.key[j] : sk;
+        sv = sv && !((H.dead >> js) & 1u);
+    } else {
+        SelCursor cur = sel_seek(H.K, sv ? is : last);
+        sk = H.K.pool[sel_at(H.K, cur, sv ? is : last)];
+        sv = sv && !(H.skip && H.skipped(sk));
     }
-    if (!selected) {
-        sel_threshold(for_each, k, sh, shift, prefix);
-        // every key whose top bits are >= prefix is selected: exactly k of them (keys are distinct)
-        for_each([&](bool valid, uint64_t kv) { sel_append(sel, &sh.cnt, SEL_MAX, valid && (kv >> shift) >= prefix, kv); });
-        __syncthreads();
+    if (tid == 0) sh.n_samples = 0;
+    __syncthreads();
+    {
+        const unsigned long long m = __ballot(sv);
+        if (lane == 0 && m) atomicAdd(&sh.n_samples, (uint32_t)__popcll(m));
     }
-    const uint32_t m = sh.cnt < k ? sh.cnt : k;
-    if (!(eps2 >= 0.f) || m < k) return m;
-    __syncthreads(); // everyone has read sh.cnt before it is reset below
-    // ---- margin mode: the k-th key is the smallest selected one; keep everything within eps2 of its score
-    unsigned long long lo = ~0ull;
-    for (uint32_t i = tid; i < m; i += SEL_THREADS) lo = sel[i] < lo ? sel[i] : lo;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long v = __shfl_xor(lo, o, OI_WAVE);
-        lo = v < lo ? v : lo;
-    }
-    if (lane == 0 && lo != ~0ull) atomicMin(&sh.min_key, lo);
+    __syncthreads();
+    const uint32_t ns = sh.n_samples;
+    uint32_t r = (uint32_t)(((uint64_t)ns * (2 * k) + n - 1) / n) + 1; // keeps ~2k keys (+1 sample of margin)
+    r = r > ns ? ns : r;
+    sel_threshold([&](auto &&f) { f(sv, sk); }, r, sh.rx, shift, prefix);
+    H.for_each([&](bool valid, uint64_t kv) { sel_append(cand, &sh.cnt, SEL_CAND, valid && (kv >> shift) >= prefix, kv); });
+    __syncthreads();
+    const uint32_t c = sh.cnt;
+    __syncthreads();
     if (tid == 0) sh.cnt = 0;
+    __syncthreads();
+    if (c >= k && c <= SEL_CAND) { // the top k of the pool are the top k of cand[0..c)
+        uint64_t ck[SEL_CAND / SEL_THREADS];
+#pragma unroll
+        for (int j = 0; j < SEL_CAND / SEL_THREADS; ++j) {
+            const uint32_t i = (uint32_t)j * SEL_THREADS + tid;
+            ck[j] = cand[i < c ? i : c - 1];
+        }
+        auto cand_each = [&](auto &&f) {
+#pragma unroll
+            for (int j = 0; j < SEL_CAND / SEL_THREADS; ++j)
+                if ((uint32_t)j * SEL_THREADS < c) f((uint32_t)j * SEL_THREADS + tid < c, ck[j]);
+        };
+        if (c == k) { // nothing to select
+            cand_each([&](bool valid, uint64_t kv) { sel_append(sel, &sh.cnt, SEL_MAX, valid, kv); });
+        } else {
+            sel_threshold(cand_each, k, sh.rx, shift, prefix);
+            cand_each([&](bool valid, uint64_t kv) { sel_append(sel, &sh.cnt, SEL_MAX, valid && (kv >> shift) >= prefix, kv); });
+        }
+        __syncthreads();
+        return true;
+    }
+    return false;
+}
+
+// ---- stage: exact select (n > k).  Radix select over every live key; sel[] takes the keys at or above the k-th, sh.cnt (0 on
+// entry) their number: k, or all of them when fewer than k are live.  Uses sh.rx.
+template <int KPT>
+__device__ __forceinline__ void sel_exact(const SelKeys<KPT> &H, uint32_t k, SelShared &sh, uint64_t *sel) {
+    int shift;
+    uint64_t prefix;
+    sel_threshold([&](auto &&f) { H.for_each(f); }, k, sh.rx, shift, prefix);
+    // every key whose top bits are >= prefix is selected: exactly k of them (keys are distinct)
+    H.for_each([&](bool valid, uint64_t kv) { sel_append(sel, &sh.cnt, SEL_MAX, valid && (kv >> shift) >= prefix, kv); });
+    __syncthreads();
+}
+
+// ---- stage: exact margin filter, margin mode behind an exact select.  sel[0..k) is the top k (barrier passed), sh.min_key is ~0:
+// the k-th key is the smallest selected one; everything within eps2 of its score goes to M.cand, sh.cnt = their number.
+template <int KPT>
+__device__ __forceinline__ SelResult sel_margin_exact(const SelKeys<KPT> &H, uint32_t k, const SelMargin &M, SelShared &sh, const uint64_t *sel) {
+    const float eps2 = M.eps2;
+    __syncthreads(); // everyone has read sh.cnt before it is reset below
+    sel_min_key(sel, k, &sh.min_key);
+    if (H.tid == 0) sh.cnt = 0;
     __syncthreads();
     // an infinite margin (a query without a bound, cosine_prefilter.hip) keeps everything and never raises the threshold
     const uint32_t t32 = eps2 < __builtin_inff() ? oi_f32_key(oi_key_f32((uint32_t)(sh.min_key >> 32)) - eps2) : 0u;
     const float edge = oi_key_f32((uint32_t)(sh.min_key >> 32));
-    for_each([&](bool valid, uint64_t kv) {
-        sel_append(mc, &sh.cnt, mcap, valid && (uint32_t)(kv >> 32) >= t32 && sel_row_keep(rm, kv, edge, eps2), kv);
+    H.for_each([&](bool valid, uint64_t kv) {
+        sel_append(M.cand, &sh.cnt, M.cap, valid && (uint32_t)(kv >> 32) >= t32 && sel_row_keep(M.rows, kv, edge, eps2), kv);
     });
     __syncthreads();
-    const uint32_t c = sh.cnt;
-    *in_cand = true;
-    *margin_tau = t32;
-    *margin_overflow = c > mcap;
-    return c > mcap ? mcap : c;
+    return sel_margin_result(sh.cnt, M.cap, t32, false);
 }
 
-__global__ __launch_bounds__(SEL_THREADS) void select_flat_kernel(
-    uint64_t *pools, uint32_t *carry_cnt, uint32_t *seg_cnt, uint32_t *tau_keys, uint64_t pool_stride,
-    uint32_t carry_cap, uint32_t seg_cap, uint32_t n_segs, uint32_t seg_cnt_stride, uint32_t *overflow,
-    uint32_t k, int compact, float *out_scores, uint32_t *out_docs, uint32_t *out_counts, uint32_t out_stride,
-    const float *eps2, uint32_t *margin_gate, const uint32_t *run_gate, const uint32_t *skip, uint32_t skip_base,
-    uint64_t *cand_g, uint32_t cand_cap, const float *row_meta, uint32_t meta_base, const float *row_qn, const float *row_cq,
-    uint32_t spec_rank, uint32_t *spec_tau, uint32_t *spec_max) {
+// Selects the top min(n, k) keys of K into sel[] (R.m of them), or in margin mode the survivors (R.in_cand, see SelResult).
+// sh.cnt == 0 and sh.min_key == ~0 on entry; cand: SEL_CAND keys of LDS for the sampled cut.
+template <int KPT>
+__device__ __forceinline__ SelResult sel_flat_select(const SelFlat &K, uint32_t k, const SelMargin &M, SelShared &sh, uint64_t *sel, uint64_t *cand) {
+    SelResult R = {};
+    const uint32_t n = K.n;
+    if (n == 0) return R;
+    SelKeys<KPT> H(K, M);
+    H.load();
+    if (n <= k) return SelResult{sel_take_all(H, sh, sel)};
+    SEL_STAMP(2);
+    if (M.eps2 >= 0.f) {
+        R = sel_margin_bins(H, k, M, sh);
+        if (R.in_cand) return R;
+    }
+    bool selected = false; // sel[0..k) holds the top k
+    if (KPT != 4 && n > SEL_CAND) selected = sel_sampled_cut(H, k, sh, sel, cand);
+    if (!selected) sel_exact(H, k, sh, sel);
+    R.m = sh.cnt < k ? sh.cnt : k;
+    if (!(M.eps2 >= 0.f) || R.m < k) return R;
+    return sel_margin_exact(H, k, M, sh, sel);
+}
+
+// The register class of a pool of n keys: f(SelClass<KPT>), KPT = 0 for the re-loading class.
+template <int KPT> struct SelClass { static constexpr int value = KPT; };
+template <class F>
+__device__ __forceinline__ SelResult sel_dispatch(uint32_t n, F &&f) {
+    if (n <= 4 * SEL_THREADS) return f(SelClass<4>{});
+    if (n <= 8 * SEL_THREADS) return f(SelClass<8>{});
+    if (n <= 16 * SEL_THREADS) return f(SelClass<16>{});
+    if (n <= SEL_KPT_MAX * SEL_THREADS) return f(SelClass<SEL_KPT_MAX>{});
+    return f(SelClass<0>{});
+}
+
+// The tail of a margin select: R.m survivors, an unsorted superset of the top k, only ever compacted -- into the carry region
+// (unless the stage wrote them there), all segments empty, the threshold raised to R.tau, the gate opened on overflow, and with
+// a.spec_rank the speculative threshold's words.  All threads call.
+__device__ __forceinline__ void sel_finish_margin(const SelArgs &a, uint32_t q, uint64_t *pool, uint32_t *segc, const SelMargin &M,
+                                                  const SelResult &R, SelShared &sh) {
+    const uint32_t tid = threadIdx.x, m = R.m;
+    if (R.overflow && tid == 0 && a.margin_gate) *a.margin_gate = 1u;
+    if (!R.in_carry)
+        for (uint32_t i = tid; i < m; i += SEL_THREADS) pool[i] = M.cand[i];
+    for (uint32_t sg = tid; sg < a.n_segs; sg += SEL_THREADS) segc[sg] = 0;
+    uint32_t spec_key = R.spec_key;
+    if (a.spec_rank && !R.in_carry && m >= a.spec_rank) spec_key = sel_rth_score_key_of(M.cand, m, a.spec_rank, sh); // (uniform)
+    if (tid == 0) {
+        a.carry_cnt[q] = m;
+        uint32_t tau = a.tau_keys ? a.tau_keys[q] : 0u;
+        if (a.tau_keys && R.tau > tau) a.tau_keys[q] = tau = R.tau;
+        if (a.spec_rank) sel_spec_words(m >= a.spec_rank, spec_key, M.eps2, tau, a.spec_tau + q, a.spec_max + q);
+    }
+}
+
+__global__ __launch_bounds__(SEL_THREADS) void select_flat_kernel(const SelArgs a) {
     // run_gate: this launch belongs to the gated exact pipeline (cosine_prefilter.hip) and only runs when the
-    // screen gave up.  eps2: margin mode (see sel_flat_select); its overflow opens that gate.
-    if (run_gate && *run_gate == 0u) return;
+    // screen gave up.  eps2: margin mode (SelMargin); its overflow opens that gate.
+    if (a.run_gate && *a.run_gate == 0u) return;
     __shared__ SelShared sh;
     __shared__ uint64_t sel[2 * SEL_MAX];
     __shared__ uint64_t cand[SEL_CAND];
-    const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    uint64_t *pool = pools + (uint64_t)q * pool_stride;
-    uint32_t *segc = seg_cnt + (uint64_t)q * seg_cnt_stride;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n_segs = a.n_segs;
+    uint64_t *pool = a.pools + (uint64_t)q * a.pool_stride;
+    uint32_t *segc = a.seg_cnt + (uint64_t)q * a.seg_cnt_stride;
     SEL_STAMP(0);
-    const uint32_t c0_raw = carry_cnt[q];    // (issued beside the segment counts: not a second round trip after the scan)
-    const float e2 = eps2 ? eps2[q] : -1.f;
+    const uint32_t c0_raw = a.carry_cnt[q];    // (issued beside the segment counts: not a second round trip after the scan)
+    SelMargin M;
+    M.eps2 = a.eps2 ? a.eps2[q] : -1.f;
+    M.skip = a.skip; M.skip_base = a.skip_base; M.carry = pool; M.spec_rank = a.spec_rank;
     // margin candidates: LDS (4096 keys), or a global buffer of the caller's (the int8 tier: OI_I8_CARRY keys), copied into the
     // carry region after the pass that reads the pool
-    uint64_t *const mc = cand_g ? cand_g + (uint64_t)q * cand_cap : cand;
-    const uint32_t mcap = cand_g ? cand_cap : SEL_CAND;
-    SelRowMargin rm_v;
-    if (row_meta) rm_v = SelRowMargin{row_meta, meta_base, row_qn[q], row_cq[q]};
-    const SelRowMargin *rm = row_meta && e2 < __builtin_inff() ? &rm_v : nullptr;
+    M.cand = a.cand ? a.cand + (uint64_t)q * a.cand_cap : cand;
+    M.cap = a.cand ? a.cand_cap : SEL_CAND;
+    M.rows = SelRowMargin{a.row_meta && M.eps2 < __builtin_inff() ? a.row_meta : nullptr, a.meta_base, a.row_meta ? a.row_qn[q] : 0.f,
+                          a.row_meta ? a.row_cq[q] : 0.f};
 
     // exclusive scan of the (clamped) segment counts -> sh.seg_off; SEL_MAX_SEGS / SEL_THREADS = 4 per thread
     constexpr int SPT = SEL_MAX_SEGS / SEL_THREADS;
@@ -815,7 +801,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_flat_kernel(
         const uint32_t sg = tid * SPT + u;
         uint32_t v = segc[sg < n_segs ? sg : 0];
         if (sg >= n_segs) v = 0;
-        if (v > seg_cap) { *overflow = 1u; v = seg_cap; }
+        if (v > a.seg_cap) { *a.overflow = 1u; v = a.seg_cap; }
         c[u] = v;
         local += v;
     }
@@ -841,36 +827,17 @@ __global__ __launch_bounds__(SEL_THREADS) void select_flat_kernel(
     __syncthreads();
 
     SelFlat K;
-    K.pool = pool; K.seg_off = sh.seg_off; K.carry_cap = carry_cap; K.seg_cap = seg_cap; K.n_segs = n_segs;
-    K.c0 = c0_raw < carry_cap ? c0_raw : carry_cap;
+    K.pool = pool; K.seg_off = sh.seg_off; K.carry_cap = a.carry_cap; K.seg_cap = a.seg_cap; K.n_segs = n_segs;
+    K.c0 = c0_raw < a.carry_cap ? c0_raw : a.carry_cap;
     K.n = K.c0 + total;
     K.steps = 0;
     while ((1u << K.steps) < n_segs) ++K.steps;
     SEL_STAMP(1);
 
-    uint32_t m, m_tau = 0;
-    bool in_cand = false, m_over = false, in_carry = false;
-    uint32_t spec_key = 0;
-    if (K.n <= 4 * SEL_THREADS) m = sel_flat_select<4>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm, pool, &in_carry, spec_rank, &spec_key);
-    else if (K.n <= 8 * SEL_THREADS) m = sel_flat_select<8>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm, pool, &in_carry, spec_rank, &spec_key);
-    else if (K.n <= 16 * SEL_THREADS) m = sel_flat_select<16>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm, pool, &in_carry, spec_rank, &spec_key);
-    else if (K.n <= SEL_KPT_MAX * SEL_THREADS) m = sel_flat_select<SEL_KPT_MAX>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm, pool, &in_carry, spec_rank, &spec_key);
-    else m = sel_flat_select<0>(K, k, sh, sel, cand, e2, &in_cand, &m_tau, &m_over, skip, skip_base, mc, mcap, rm, pool, &in_carry, spec_rank, &spec_key);
-    if (in_cand) { // margin mode: an unsorted superset of the top k in cand[]; only ever compacted
-        if (m_over && tid == 0 && margin_gate) *margin_gate = 1u;
-        if (!in_carry) // (the fast path with the keys in registers wrote the carry region itself)
-            for (uint32_t i = tid; i < m; i += SEL_THREADS) pool[i] = mc[i];
-        for (uint32_t sg = tid; sg < n_segs; sg += SEL_THREADS) segc[sg] = 0;
-        if (spec_rank && !in_carry && m >= spec_rank) // (uniform) the prediction from the keys just copied
-            spec_key = sel_rth_score_key([&](auto &&f) {
-                for (uint32_t i0 = 0; i0 < m; i0 += SEL_THREADS) f(i0 + tid < m, mc[i0 + tid < m ? i0 + tid : 0]);
-            }, spec_rank, sh);
-        if (tid == 0) {
-            carry_cnt[q] = m;
-            uint32_t tau = tau_keys ? tau_keys[q] : 0u;
-            if (tau_keys && m_tau > tau) tau_keys[q] = tau = m_tau;
-            if (spec_rank) sel_spec_words(m >= spec_rank, spec_key, e2, tau, spec_tau + q, spec_max + q);
-        }
+    const SelResult R = sel_dispatch(K.n, [&](auto cls) { return sel_flat_select<decltype(cls)::value>(K, a.k, M, sh, sel, cand); });
+    const uint32_t m = R.m;
+    if (R.in_cand) {
+        sel_finish_margin(a, q, pool, segc, M, R, sh);
 #ifdef OI_ABLATION
         __syncthreads();
         if (sel_dbg_on && blockIdx.x == 0 && tid == 0) {
@@ -881,52 +848,80 @@ __global__ __launch_bounds__(SEL_THREADS) void select_flat_kernel(
 #endif
         return;
     }
-
-    // Sorted output is needed only for a final list; an intermediate compaction just needs the set
-    // and its smallest key (the new threshold).
-    if (out_scores) {
-        uint32_t P = 2;
-        while (P < m) P <<= 1;
-        for (uint32_t i = m + tid; i < P; i += SEL_THREADS) sel[i] = 0; // lowest possible key
+    sel_finish(a, q, pool, segc, sel, m, &sh.min_key);
+    if (a.compact && a.spec_rank) { // a margin select of a pool of <= k keys (or of fewer than k valid ones): the prediction all the same
         __syncthreads();
-        bitonic_sort_desc(sel, P);
-        for (uint32_t i = tid; i < m; i += SEL_THREADS) {
-            const uint64_t key = sel[i];
-            out_scores[(uint64_t)q * out_stride + i] = oi_rank_key_score(key);
-            out_docs[(uint64_t)q * out_stride + i] = oi_rank_key_doc(key);
+        uint32_t spec_key = 0;
+        if (m >= a.spec_rank) spec_key = sel_rth_score_key_of(sel, m, a.spec_rank, sh); // (uniform)
+        if (tid == 0) sel_spec_words(m >= a.spec_rank, spec_key, M.eps2, a.tau_keys ? a.tau_keys[q] : 0u, a.spec_tau + q, a.spec_max + q);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// select_topk_kernel: the selection a segment at a time, for pools of more than SEL_MAX_SEGS segments (a BM25 shard of more
+// than 134M docs) and for A/B runs (OI_SELECT_V1).  Small pools are gathered into LDS once and the radix select runs out of
+// LDS; large pools are scanned in place, one wave per segment, on every pass.  Plain selects only: a margin or gated launch
+// takes the flat kernel.
+#define SEL_LDS_KEYS 8192
+
+__global__ __launch_bounds__(SEL_THREADS) void select_topk_kernel(const SelArgs a) {
+    __shared__ SelRadix rx;
+    __shared__ uint64_t sel[2 * SEL_MAX];
+    __shared__ uint64_t lds_keys[SEL_LDS_KEYS];
+    __shared__ uint32_t s_cnt, s_total;
+    __shared__ unsigned long long s_min;
+
+    const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, k = a.k;
+    uint64_t *pool = a.pools + (uint64_t)q * a.pool_stride;
+    uint32_t *segc = a.seg_cnt + (uint64_t)q * a.seg_cnt_stride;
+    const uint32_t c0 = a.carry_cnt[q] < a.carry_cap ? a.carry_cnt[q] : a.carry_cap;
+    if (tid == 0) { s_cnt = 0; s_total = 0; s_min = ~0ull; }
+    __syncthreads();
+    {
+        uint32_t local = 0;
+        for (uint32_t sg = tid; sg < a.n_segs; sg += SEL_THREADS) {
+            uint32_t c = segc[sg];
+            if (c > a.seg_cap) { *a.overflow = 1u; c = a.seg_cap; }
+            local += c;
         }
-        if (tid == 0) { out_counts[q] = m; sh.min_key = m ? sel[m - 1] : 0; }
-    } else {
-        unsigned long long lo = ~0ull;
-        for (uint32_t i = tid; i < m; i += SEL_THREADS) lo = sel[i] < lo ? sel[i] : lo;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long v = __shfl_xor(lo, o, OI_WAVE);
-            lo = v < lo ? v : lo;
-        }
-        if (lane == 0 && lo != ~0ull) atomicMin(&sh.min_key, lo);
+        local = oi_wave_sum(local);
+        if ((tid & 63) == 0 && local) atomicAdd(&s_total, local);
     }
     __syncthreads();
-    if (compact) {
-        for (uint32_t i = tid; i < m; i += SEL_THREADS) pool[i] = sel[i];
-        for (uint32_t sg = tid; sg < n_segs; sg += SEL_THREADS) segc[sg] = 0;
-        if (tid == 0) {
-            carry_cnt[q] = m;
-            if (m == k && tau_keys && !eps2) { // k docs at or above this score exist: a valid lower bound of the final
-                // k-th (a margin-mode pool of exactly k keys keeps its threshold: that bound needs the margin)
-                const uint32_t t = (uint32_t)(sh.min_key >> 32);
-                if (t > tau_keys[q]) tau_keys[q] = t;
-            }
+    const uint32_t n = c0 + s_total;
+    bool gathered = false; // everything is in lds_keys[0..n)
+    // f(valid, key) over the pool; trip counts are uniform over a wave (valid = false past the end), as f's ballots need
+    auto for_each = [&](auto &&f) {
+        if (gathered) {
+            for (uint32_t i0 = 0; i0 < n; i0 += SEL_THREADS) f(i0 + tid < n, lds_keys[i0 + tid < n ? i0 + tid : 0]);
+            return;
         }
-        if (spec_rank) { // a margin select of a pool of <= k keys (or of fewer than k valid ones): the prediction all the same
-            __syncthreads();
-            if (m >= spec_rank) // (uniform)
-                spec_key = sel_rth_score_key([&](auto &&f) {
-                    for (uint32_t i0 = 0; i0 < m; i0 += SEL_THREADS) f(i0 + tid < m, sel[i0 + tid < m ? i0 + tid : 0]);
-                }, spec_rank, sh);
-            if (tid == 0) sel_spec_words(m >= spec_rank, spec_key, e2, tau_keys ? tau_keys[q] : 0u, spec_tau + q, spec_max + q);
+        for (uint32_t i0 = 0; i0 < c0; i0 += SEL_THREADS) f(i0 + tid < c0, pool[i0 + tid < c0 ? i0 + tid : 0]);
+        for (uint32_t sg = wv; sg < a.n_segs; sg += SEL_THREADS / 64) {
+            uint32_t c = segc[sg];
+            if (c > a.seg_cap) c = a.seg_cap;
+            const uint64_t *base = pool + a.carry_cap + (uint64_t)sg * a.seg_cap;
+            for (uint32_t i0 = 0; i0 < c; i0 += 64) f(i0 + lane < c, base[i0 + lane < c ? i0 + lane : 0]);
         }
+    };
+    if (n <= SEL_LDS_KEYS) {
+        for_each([&](bool valid, uint64_t key) { sel_append(lds_keys, &s_cnt, SEL_LDS_KEYS, valid, key); });
+        __syncthreads();
+        gathered = true;
+        if (tid == 0) s_cnt = 0;
+        __syncthreads();
     }
+    if (n <= k) {
+        for_each([&](bool valid, uint64_t key) { sel_append(sel, &s_cnt, 2 * SEL_MAX, valid, key); });
+    } else {
+        int shift;
+        uint64_t prefix;
+        sel_threshold(for_each, k, rx, shift, prefix);
+        // every key whose top bits are >= prefix is selected: exactly k of them (keys are distinct)
+        for_each([&](bool valid, uint64_t key) { sel_append(sel, &s_cnt, SEL_MAX, valid && (key >> shift) >= prefix, key); });
+    }
+    __syncthreads();
+    sel_finish(a, q, pool, segc, sel, s_cnt < k ? s_cnt : k, &s_min);
 }
 
 int oi_launch_select(oi_ctx *ctx, const PoolView &pool, uint32_t n_queries, uint32_t k, bool compact,
@@ -954,23 +949,23 @@ int oi_launch_select(oi_ctx *ctx, const PoolView &pool, uint32_t n_queries, uint
     const bool spec = extra && extra->spec_rank;
     OI_REQUIRE(!spec || (extra->eps2 && extra->spec_tau && extra->spec_max && pool.tau_keys),
                "select: a speculative threshold needs margin mode, thresholds and both output arrays");
-    if ((!v1 || special) && pool.n_segs <= SEL_MAX_SEGS) {
-        hipLaunchKernelGGL(select_flat_kernel, dim3(n_queries), dim3(SEL_THREADS), 0, ctx->stream, pool.keys,
-                           pool.carry_cnt, pool.seg_cnt, pool.tau_keys, pool.stride, pool.carry_cap, pool.seg_cap,
-                           pool.n_segs, pool.seg_cnt_stride, pool.overflow, k, compact ? 1 : 0, out_scores, out_docs,
-                           out_counts, out_stride, extra ? extra->eps2 : nullptr, extra ? extra->margin_gate : nullptr,
-                           extra ? extra->run_gate : nullptr, extra && extra->eps2 ? extra->skip_bitmap : nullptr,
-                           extra ? extra->skip_base : 0u, extra && extra->eps2 ? extra->cand : nullptr,
-                           extra && extra->eps2 ? extra->cand_cap : 0u, extra && extra->eps2 ? extra->row_meta : nullptr,
-                           extra ? extra->meta_base : 0u, extra ? extra->row_qn : nullptr, extra ? extra->row_cq : nullptr,
-                           spec ? extra->spec_rank : 0u, spec ? extra->spec_tau : nullptr, spec ? extra->spec_max : nullptr);
-        OI_HIP_CHECK(hipGetLastError());
-        return OI_OK;
-    }
-    hipLaunchKernelGGL(select_topk_kernel, dim3(n_queries), dim3(SEL_THREADS), 0, ctx->stream, pool.keys,
-                       pool.carry_cnt, pool.seg_cnt, pool.tau_keys, pool.stride, pool.carry_cap, pool.seg_cap,
-                       pool.n_segs, pool.seg_cnt_stride, pool.overflow, k, compact ? 1 : 0, out_scores, out_docs,
-                       out_counts, out_stride);
+    const SelectExtra none{}, &x = extra ? *extra : none;
+    const bool margin = x.eps2 != nullptr; // (the members below mean something in margin mode only)
+    SelArgs a;
+    a.pools = pool.keys; a.carry_cnt = pool.carry_cnt; a.seg_cnt = pool.seg_cnt; a.tau_keys = pool.tau_keys;
+    a.pool_stride = pool.stride; a.carry_cap = pool.carry_cap; a.seg_cap = pool.seg_cap; a.n_segs = pool.n_segs;
+    a.seg_cnt_stride = pool.seg_cnt_stride; a.overflow = pool.overflow;
+    a.k = k; a.compact = compact ? 1 : 0;
+    a.out_scores = out_scores; a.out_docs = out_docs; a.out_counts = out_counts; a.out_stride = out_stride;
+    a.eps2 = x.eps2; a.margin_gate = x.margin_gate; a.run_gate = x.run_gate;
+    a.skip = margin ? x.skip_bitmap : nullptr; a.skip_base = x.skip_base;
+    a.cand = margin ? x.cand : nullptr; a.cand_cap = margin ? x.cand_cap : 0u;
+    a.row_meta = margin ? x.row_meta : nullptr; a.meta_base = x.meta_base; a.row_qn = x.row_qn; a.row_cq = x.row_cq;
+    a.spec_rank = x.spec_rank; a.spec_tau = x.spec_tau; a.spec_max = x.spec_max;
+    if ((!v1 || special) && pool.n_segs <= SEL_MAX_SEGS)
+        hipLaunchKernelGGL(select_flat_kernel, dim3(n_queries), dim3(SEL_THREADS), 0, ctx->stream, a);
+    else
+        hipLaunchKernelGGL(select_topk_kernel, dim3(n_queries), dim3(SEL_THREADS), 0, ctx->stream, a);
     OI_HIP_CHECK(hipGetLastError());
     return OI_OK;
 }

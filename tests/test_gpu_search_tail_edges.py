@@ -1027,8 +1027,8 @@ def test_mirror_constants_equal_the_sources():
     assert src.count("(d * %du) >> %d" % (RRF_MULT, 32 - RRF_HASH_BITS)) == 2            # insert and lookup
     assert src.count("1.0f / (%.1ff + (float)" % RRF_K) == 3
     for c in SEL_CLASSES[:3]:
-        assert "K.n <= %d * SEL_THREADS) m = sel_flat_select<%d>" % (c, c) in src
-    assert "K.n <= SEL_KPT_MAX * SEL_THREADS) m = sel_flat_select<SEL_KPT_MAX>" in src and SEL_CLASSES[3] == SEL_KPT_MAX
+        assert "if (n <= %d * SEL_THREADS) return f(SelClass<%d>{});" % (c, c) in src
+    assert "if (n <= SEL_KPT_MAX * SEL_THREADS) return f(SelClass<SEL_KPT_MAX>{});" in src and SEL_CLASSES[3] == SEL_KPT_MAX
     assert "if (KPT != 4 && n > SEL_CAND)" in src and "if (c >= k && c <= SEL_CAND)" in src and "if (c == k)" in src
     assert "const uint32_t js = lane % kpt, is = first + js * 64;" in src
     assert "uint32_t r = (uint32_t)(((uint64_t)ns * (2 * k) + n - 1) / n) + 1;" in src

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """ms per hybrid step (oi_search, device buffers, 4 rotating batches) at the bench shape, for A/B runs of ablation switches:
-    OI_LIB=ablation [OI_NO_LATE_FORK=1 ...] python tools/step_ab.py [n_docs] [steps] [batch] [depth]"""
+    OI_LIB=ablation [OI_NO_LATE_FORK=1 ...] python tools/step_ab.py [n_docs] [steps] [batch] [depth]
+and, from a further untimed pass with the profiler on, the `select` tag's ms per step."""
 import json
 import os
 import sys
@@ -45,4 +46,12 @@ for rep in range(3):
     torch.cuda.synchronize()
     res.append(a.elapsed_time(b) / steps)
 ctx.synchronize()
-print(json.dumps({"docs": n, "batch": B, "depth": DEPTH, "ms_per_step": [round(x, 4) for x in res], "docs_checksum": int(out.docs.sum().item())}))
+# the `select` profile tag per step (HIP events around every tagged launch: after the timed loops, never inside them)
+ctx.profile_reset(True)
+for i in range(steps):
+    idx.search(*batches[i % 4], k=K, depth=DEPTH, out=out)
+ctx.synchronize()
+sel_ms, sel_n = ctx.profile_read("select")
+ctx.profile_reset(False)
+print(json.dumps({"docs": n, "batch": B, "depth": DEPTH, "ms_per_step": [round(x, 4) for x in res], "docs_checksum": int(out.docs.sum().item()),
+                  "select_ms_per_step": round(sel_ms / steps, 5), "select_launches_per_step": sel_n / steps}))
