@@ -320,17 +320,21 @@ int oi_launch_cosine_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, u
 }
 
 // ------------------------------------------------------------------ row normalisation
+// The squares are summed in f64 (as the oracle does): an f32 sum overflows for |row| above 1.8e19 (inv = 0 zeroed the row) and
+// is 0 when every square underflows (|x_k| below 3e-23: the row was left as it came).  Ingest is one pass over HBM: the f64
+// fmas are hidden behind the loads.  ss == 0 (a zero row) leaves the row; an inf gives inv = 0 (NaN there, 0 elsewhere), a NaN
+// a row of NaNs -- the oracle's results.
 __global__ __launch_bounds__(256) void l2_normalize_kernel(float *rows, uint64_t n, uint32_t dim) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
     for (uint64_t r = wave; r < n; r += n_waves) {
         float *x = rows + r * dim;
-        float ss = 0.f;
-        for (uint32_t k = lane; k < dim; k += 64) ss = fmaf(x[k], x[k], ss);
+        double ss = 0.0;
+        for (uint32_t k = lane; k < dim; k += 64) ss = fma((double)x[k], (double)x[k], ss);
         ss = oi_wave_sum(ss);
-        if (ss == 0.f) continue;
-        const float inv = 1.0f / sqrtf(ss);
+        if (ss == 0.0) continue;
+        const float inv = (float)(1.0 / sqrt(ss));
         for (uint32_t k = lane; k < dim; k += 64) x[k] = x[k] * inv;
     }
 }
