@@ -852,6 +852,71 @@ int oi_narratives_fit(oi_index *idx, const float *seeds /* [n_clusters][dim] */,
                       uint32_t *labels_out /* [n_docs] by LOCAL row, or NULL */, oi_narrative_info *info_host);
 
 /* ------------------------------------------------------------------------- */
+/* Mention summary: posts containing a query's terms, per bucket or ticker     */
+/* ------------------------------------------------------------------------- */
+/*
+ * The lexical member of the aggregation family, and the one a host WITHOUT embeddings can use: "how many posts mention gme
+ * and squeeze, hour by hour, and were they bullish?"  oi_similar_volume / _summary / _groups / _share decide a document by
+ * sim(q, d) >= t; this call decides it by the TERMS it contains, read from the postings oi_index_finalize made, and returns
+ * the same social_summary records -- per time bucket (OI_MENTION_AXIS_TIME) or per key of the documents' group attribute
+ * (OI_MENTION_AXIS_KEY).  Nothing per post returns to the host and no list is cut at OI_MAX_DEPTH.  It is the reference's
+ * own question (social_summary over the posts that mention a ticker) asked of the index.
+ *
+ * The definition.
+ *   D_q is the set of DISTINCT term ids in query_terms[q_term_offsets[q] .. q_term_offsets[q+1]).  A repeated term counts
+ *     once -- unlike BM25, where it counts each time.  A term id >= vocab occurs in no document, but it is a member of D_q.
+ *   m(q, d) is the number of t in D_q with a posting for local document d.
+ *   need_q: min_match == NULL gives 1 (ANY); min_match[q] == 0 gives |D_q| (ALL); otherwise it is min_match[q].
+ *   d MATCHES q when |D_q| >= 1 and m(q, d) >= need_q.  An empty query matches nothing; need_q > |D_q| matches nothing.
+ * out[q][c] holds the social_summary raw sums over the local documents d of the handle that match q, pass filters[q] and
+ * fall into cell c:
+ *   - the pass clause is oi_similar_summary's clause 1: d passes filters[q]; filters == NULL means every document passes;
+ *   - on the TIME axis the cell is oi_similar_summary's clause 2: bucket_width == 0 (one cell, c = 0), or stamp_origin <=
+ *     stamp[d] and (stamp[d] - stamp_origin) / bucket_width == c (evaluated in 64 bits);
+ *   - on the KEY axis the cell is oi_similar_groups's key clause: (group[d] & key_mask) >> ctz(key_mask) == c, and a key >=
+ *     n_cells belongs to no cell.
+ * The fields and the integer arithmetic are oi_similar_summary's: total, by_source[2], bullish, bearish, neutral and
+ * spec_count are exact integers, and polarity_sum = (double)(sum of pol_q30) * 2^-30, the sum taken in 64-bit integers.
+ *
+ * The contract that follows from it:
+ *   - the result is deterministic and independent of the order of the atomics, the grid and the batch composition;
+ *   - with one term, no filter and one cell, total equals the term's local df (oi_index_local_stats);
+ *   - with min_match == NULL the matching set of a query equals the set of documents with BM25 score > 0 for it (every idf
+ *     is > 0);
+ *   - records of document shards add.
+ *
+ * Limits.  At most OI_MAX_MENTION_TERMS raw terms per query, duplicates included.  With OI_HOST a longer query is
+ * OI_ERR_INVALID_ARG, naming the query and the count.  With OI_DEVICE the offsets are not host-visible: such a query gets
+ * all-zero records, and nothing is read or written out of bounds for it.  n_queries <= 4096; n_queries * n_cells <=
+ * OI_MAX_GROUP_CELLS; n_queries == 0 is OI_OK.
+ *
+ * Rules.  spec is always a host pointer; location says where the terms, the offsets, min_match, the filters and out live;
+ * OI_DEVICE is asynchronous on the ctx stream; not captured by graph replay.  A finalized index is required (the postings),
+ * and signals (oi_index_set_signals): otherwise OI_ERR_STATE.  Doc attributes are required when bucket_width > 0, when
+ * filters != NULL, or on the KEY axis: otherwise OI_ERR_STATE.  NO embeddings are needed.  It works on a view (views alias
+ * the postings, cell_start, the signals and the attributes).  A null spec, a bad axis, n_cells, bucket_width, key_mask,
+ * n_queries or cell count out of range, a null terms, offsets or out buffer, a bad location -> OI_ERR_INVALID_ARG with the
+ * number in the message; every argument check precedes the first device call.
+ * Workspace per searching context: 64 B per cell and the per-query plan, 272 B per query (oi_workspace_bytes counts both);
+ * with OI_HOST also the staged inputs and records.  Profile tags: "mention_plan" (the distinct terms and need_q of every
+ * query) and "mention" (the match: postings counted in LDS, matches summed).
+ *
+ * NOT covered: oi_search_sharded* and oi_pipeline_*.  A sharded host adds the records of its ranks.
+ */
+#define OI_MAX_MENTION_TERMS 64u
+enum { OI_MENTION_AXIS_TIME = 0, OI_MENTION_AXIS_KEY = 1 };
+typedef struct oi_mention_spec {
+    uint32_t axis;          /* OI_MENTION_AXIS_* */
+    uint32_t stamp_origin;  /* TIME: oi_summary_spec's meaning.             KEY: key_mask (non-zero, one contiguous run of bits) */
+    uint32_t bucket_width;  /* TIME: oi_summary_spec's (0: no axis, 1 cell). KEY: must be 0 */
+    uint32_t n_cells;       /* TIME: 1 .. OI_MAX_VOLUME_BUCKETS.             KEY: 1 .. min(2^popcount(mask), OI_MAX_GROUP_KEYS) */
+} oi_mention_spec;
+int oi_mention_summary(oi_index *idx, const uint32_t *query_terms, const uint32_t *q_term_offsets, uint32_t n_queries,
+                       const oi_mention_spec *spec, const uint32_t *min_match /* [n_queries] where `location` says, or NULL */,
+                       const oi_doc_filter *filters /* or NULL */, int location,
+                       oi_social_counters *out /* [n_queries][n_cells] */);
+
+/* ------------------------------------------------------------------------- */
 /* Text to term ids: the tokeniser and the hashed vocabulary                   */
 /* ------------------------------------------------------------------------- */
 /*

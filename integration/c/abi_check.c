@@ -103,6 +103,27 @@ int main(void) {
             fprintf(stderr, "abi_check: hybrid query returned %u docs, first %u (expected 10, 123)\n", counts[0], docs[0]);
             return 1;
         }
+        { /* the mention summary (oi_mention_summary): the posts that hold BOTH of the query's terms, counted from the postings */
+            double *pol = (double *)malloc(sizeof(double) * N);
+            uint8_t *spec = (uint8_t *)calloc(N, 1);
+            const oi_mention_spec ms = {OI_MENTION_AXIS_TIME, 0, 0, 1};
+            const uint32_t all[1] = {0};
+            oi_social_counters rec;
+            uint64_t want = 0;
+            for (i = 0; i < N; ++i) {
+                const uint32_t *t = terms + 3 * i;
+                pol[i] = 0.5;
+                want += (t[0] == 7 || t[1] == 7 || t[2] == 7) && (t[0] == 9 || t[1] == 9 || t[2] == 9);
+            }
+            if ((rc = oi_index_set_signals(idx, pol, spec, NULL, 0.2, OI_HOST)) != OI_OK) return fail("oi_index_set_signals", rc);
+            if ((rc = oi_mention_summary(idx, qt, qo, 1, &ms, all, NULL, OI_HOST, &rec)) != OI_OK) return fail("oi_mention_summary", rc);
+            if (rec.total != want || rec.bullish != want || rec.polarity_sum != 0.5 * (double)want) {
+                fprintf(stderr, "abi_check: mention summary counted %llu posts (expected %llu)\n", (unsigned long long)rec.total,
+                        (unsigned long long)want);
+                return 1;
+            }
+            free(pol); free(spec);
+        }
         { /* the pipelined query (oi_pipeline_*): the same batch three times through two lanes the library owns; every
            * result must be oi_search's, bit for bit */
             oi_pipeline *pipe = NULL;

@@ -89,6 +89,20 @@ pub struct OiNarrativeInfo {
 }
 pub const OI_MAX_CENTROIDS: u32 = 256;
 
+/// `oi_mention_spec`: axis TIME -- `stamp_origin`, `bucket_width` and `n_cells` are `oi_summary_spec`'s time axis; axis KEY --
+/// `stamp_origin` carries the key_mask (non-zero, one contiguous run of bits), `bucket_width` is 0, `n_cells` the number of keys.
+#[repr(C)]
+#[derive(Debug, Clone, Copy, PartialEq)]
+pub struct OiMentionSpec {
+    pub axis: u32,
+    pub stamp_origin: u32,
+    pub bucket_width: u32,
+    pub n_cells: u32,
+}
+pub const OI_MAX_MENTION_TERMS: u32 = 64;
+pub const OI_MENTION_AXIS_TIME: u32 = 0;
+pub const OI_MENTION_AXIS_KEY: u32 = 1;
+
 /// `oi_groups_spec`: the key of a document is (group & key_mask) >> ctz(key_mask); top == 0 asks for dense records, top >= 1 for
 /// the best `top` keys by `rank_by` among those with total >= max(min_total, 1).
 #[repr(C)]
@@ -275,6 +289,12 @@ extern "C" {
     pub fn oi_similar_share(idx: *mut OiIndex, query_vecs: *const f32, n_queries: u32, spec: *const OiSummarySpec,
                             thresholds: *const f32, filters: *const OiDocFilter, location: c_int,
                             out: *mut OiSocialCounters, labels_out: *mut u32) -> c_int;
+
+    // mention summary: the social_summary sums of the documents that contain at least need_q of a query's distinct terms, per
+    // time bucket or group key; min_match [n_queries] (0: all) and filters may be null; needs postings and signals, no embeddings
+    pub fn oi_mention_summary(idx: *mut OiIndex, query_terms: *const u32, q_term_offsets: *const u32, n_queries: u32,
+                              spec: *const OiMentionSpec, min_match: *const u32, filters: *const OiDocFilter, location: c_int,
+                              out: *mut OiSocialCounters) -> c_int;
 
     // narrative discovery: the update step of a clustering (integer sums per label: exact, shards add), sums -> unit
     // vectors (previous may be null), and the k-means loop over oi_similar_share (filter: ONE, may be null; labels_out may

@@ -397,6 +397,32 @@ impl HipIndex {
         })?;
         Ok((out.chunks(nb.max(1)).map(|c| c.to_vec()).collect(), lab))
     }
+    /// The sentiment of the posts that MENTION a query's terms (`oi_mention_summary`): one record per query and cell -- a time
+    /// bucket (`OI_MENTION_AXIS_TIME`) or a key of the documents' group (`OI_MENTION_AXIS_KEY`).  A document matches a query
+    /// when at least need_q of its DISTINCT terms occur in it: `min_match` None = 1 (any), an entry 0 = all of them.  Reads the
+    /// postings of a finalized index and its signals; no embeddings.  At most 64 terms per query.  Records of shards add.
+    pub fn mention_summary(&self, query_terms: &[u32], q_term_offsets: &[u32], spec: ffi::OiMentionSpec, min_match: Option<&[u32]>,
+                           filters: Option<&[ffi::OiDocFilter]>) -> Result<Vec<Vec<ffi::OiSocialCounters>>, HipError> {
+        assert!(!q_term_offsets.is_empty());
+        let b = q_term_offsets.len() - 1;
+        assert_eq!(*q_term_offsets.last().unwrap() as usize, query_terms.len());
+        if let Some(f) = filters {
+            assert_eq!(f.len(), b);
+        }
+        if let Some(m) = min_match {
+            assert_eq!(m.len(), b);
+        }
+        let nc = spec.n_cells as usize;
+        let mut out = vec![ffi::OiSocialCounters::default(); b * nc];
+        let none = [0u32];
+        let terms = if query_terms.is_empty() { &none[..] } else { query_terms };
+        check(unsafe {
+            ffi::oi_mention_summary(self.idx, terms.as_ptr(), q_term_offsets.as_ptr(), b as u32, &spec,
+                                    min_match.map_or(std::ptr::null(), |m| m.as_ptr()), filters.map_or(std::ptr::null(), |f| f.as_ptr()),
+                                    ffi::OI_HOST, out.as_mut_ptr())
+        })?;
+        Ok(out.chunks(nc.max(1)).map(|c| c.to_vec()).collect())
+    }
     /// The update step of a clustering over the index (`oi_label_sums`): per label c < n_clusters the number of rows that
     /// carry it and the sum of rint(row * 2^30) over them, as 64-bit integers ([n_clusters * dim], [n_clusters]).  Any other
     /// label (0xFFFFFFFF, as `similar_share` writes for unassigned rows) is "no cluster".  Exact: shards of the documents add.

@@ -21,6 +21,8 @@ OI_MAX_SUMMARY_CELLS = 1 << 18
 OI_MAX_GROUP_KEYS = 65536
 OI_MAX_GROUP_CELLS = 1 << 20
 OI_MAX_CENTROIDS = 256
+OI_MAX_MENTION_TERMS = 64
+OI_MENTION_AXIS_TIME, OI_MENTION_AXIS_KEY = 0, 1
 OI_GROUP_RANK_TOTAL, OI_GROUP_RANK_SPEC, OI_GROUP_RANK_BULLISH, OI_GROUP_RANK_BEARISH = 0, 1, 2, 3
 OI_BM25_BLOCK_DOCS = 32768
 OI_N_CATALYST_KEYWORDS = 16
@@ -122,6 +124,17 @@ class GroupsSpec(C.Structure):
     ]
 
 
+class MentionSpec(C.Structure):
+    """oi_mention_spec: axis TIME -- {stamp_origin, bucket_width, n_cells} are oi_summary_spec's time axis; axis KEY -- stamp_origin
+    carries the key_mask, bucket_width is 0 and n_cells the number of keys."""
+    _fields_ = [
+        ("axis", C.c_uint32),
+        ("stamp_origin", C.c_uint32),
+        ("bucket_width", C.c_uint32),
+        ("n_cells", C.c_uint32),
+    ]
+
+
 _P = C.c_void_p
 _U32, _U64, _I = C.c_uint32, C.c_uint64, C.c_int
 
@@ -185,6 +198,7 @@ SIGNATURES = {
     "oi_similar_summary": (_I, [_P, _P, _U32, _P, _P, _P, _I, _P]),
     "oi_similar_groups": (_I, [_P, _P, _U32, _P, _P, _P, _I, _P, _P, _P, _P]),
     "oi_similar_share": (_I, [_P, _P, _U32, _P, _P, _P, _I, _P, _P]),
+    "oi_mention_summary": (_I, [_P, _P, _P, _U32, _P, _P, _P, _I, _P]),
     "oi_label_sums": (_I, [_P, _P, _U32, _I, _P, _P]),
     "oi_centroids_from_sums": (_I, [_P, _P, _P, _P, _U32, _U32, _I, _P]),
     "oi_narratives_fit": (_I, [_P, _P, _U32, _P, _P, _I, _P, _P, _P, _P]),

@@ -10,6 +10,7 @@ Host mirror of the reference's batch tools (paths relative to the openintel repo
     RankBy / CompareArgs / RankedEntry / CompareError / CompareOutput
     rank_metric / sort_ranked / run_compare        src/mcp/tools.rs:227-352
     rank_group_records / compare_index             src/mcp/tools.rs:323-349 over the index's per-ticker sums (oi_similar_groups)
+    compare_mentions                               the same over the posts that CONTAIN a text's terms (oi_mention_summary, key axis)
     VoiceShare / share_of_voice                    builder-defined: the records of oi_similar_share as fractions per bucket
     discover_narratives                            builder-defined: oi_narratives_fit and the share of voice of what it found
     SentimentSummary / sentiment_for (per dip row) src/domain/dip.rs:428-431, src/application/dip.rs:175-194
@@ -342,6 +343,27 @@ def compare_index(index, query_vec, threshold: float, tickers, key_mask: int, ra
     res = index.similar_groups(q, float(threshold), int(key_mask), int(n_keys), top=int(top), rank_by="total",
                                min_total=int(cfg.min_sample if min_total is None else min_total), filters=filters)
     return rank_group_records(res.keys[0], res.records[0], int(res.counts[0]), tickers, rank_by, market_by_ticker, now, cfg)
+
+
+def compare_mentions(index, text: str, tickers, key_mask: int, rank_by: RankBy = RankBy.CROWDING, top: int = 100,
+                     min_total: Optional[int] = None, min_match=None, filters=None, n_keys: Optional[int] = None,
+                     market_by_ticker=None, now: Optional[_dt.datetime] = None, cfg: EngineConfig = EngineConfig()) -> CompareOutput:
+    """compare_tickers answered from the postings: "which tickers do the posts that MENTION this text belong to, and what do
+    they feel?"  ONE dense `mention_groups_text` call for the single query `text` (no embeddings needed); the host keeps the
+    keys with total >= max(min_total, 1) (default `cfg.min_sample`), orders them by (total descending, key ascending), cuts
+    at `top`, then `rank_group_records` -- compare_index with the lexical match in the similarity's place.  n_keys defaults
+    to the number of names (a mapping: its largest key + 1).  The index's signals must have been set with
+    `cfg.bull_bear_threshold`."""
+    from .analyzer import COUNTERS_DTYPE
+    if n_keys is None:
+        n_keys = (max(tickers) + 1) if isinstance(tickers, dict) else len(tickers)
+    rec = index.mention_groups_text([text], int(key_mask), int(n_keys), min_match=min_match, filters=filters)
+    if hasattr(rec, "data_ptr"):
+        rec = rec.cpu().numpy().view(COUNTERS_DTYPE).reshape(rec.shape[0], rec.shape[1])
+    rec = rec[0]
+    bar = max(int(cfg.min_sample if min_total is None else min_total), 1)
+    keys = sorted((k for k in range(len(rec)) if int(rec[k]["total"]) >= bar), key=lambda k: (-int(rec[k]["total"]), k))[:int(top)]
+    return rank_group_records(keys, [rec[k] for k in keys], len(keys), tickers, rank_by, market_by_ticker, now, cfg)
 
 
 # ----------------------------------------------------------------------------- share of voice (oi_similar_share)

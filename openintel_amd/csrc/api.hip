@@ -1731,6 +1731,85 @@ extern "C" int oi_similar_share(oi_index *idx, const float *qv, uint32_t B, cons
                           });
 }
 
+// ---------------------------------------------------------------- mention summary (mention.hip)
+// The family's order of checks: the spec, the numbers, the buffers, then the handle and its state; all of them precede the
+// first HIP call.  Never captured.
+extern "C" int oi_mention_summary(oi_index *idx, const uint32_t *qt, const uint32_t *qo, uint32_t B, const oi_mention_spec *spec,
+                                  const uint32_t *min_match, const oi_doc_filter *filters, int location, oi_social_counters *out) {
+    static_assert(sizeof(oi_doc_filter) == sizeof(uint4), "oi_doc_filter is 16 bytes");
+    OI_REQUIRE(spec, "mention_summary: null spec");
+    OI_REQUIRE(spec->axis == OI_MENTION_AXIS_TIME || spec->axis == OI_MENTION_AXIS_KEY, "mention_summary: axis=%u is not an OI_MENTION_AXIS_* value",
+               spec->axis);
+    const bool key_axis = spec->axis == OI_MENTION_AXIS_KEY;
+    if (key_axis) {
+        const uint32_t mask = spec->stamp_origin, run = mask ? mask >> __builtin_ctz(mask) : 0u;
+        OI_REQUIRE(mask != 0 && (run & (run + 1u)) == 0u, "mention_summary: key_mask=0x%x is not one contiguous run of bits", mask);
+        OI_REQUIRE(spec->bucket_width == 0, "mention_summary: bucket_width=%u on the key axis (must be 0)", spec->bucket_width);
+        const uint64_t key_space = std::min<uint64_t>(1ull << __builtin_popcount(mask), OI_MAX_GROUP_KEYS);
+        OI_REQUIRE(spec->n_cells >= 1 && spec->n_cells <= key_space, "mention_summary: n_cells=%u outside [1,%llu] (key_mask=0x%x)", spec->n_cells,
+                   (unsigned long long)key_space, mask);
+    } else {
+        OI_REQUIRE(spec->n_cells >= 1 && spec->n_cells <= OI_MAX_VOLUME_BUCKETS, "mention_summary: n_cells=%u outside [1,%u]", spec->n_cells,
+                   OI_MAX_VOLUME_BUCKETS);
+        OI_REQUIRE(spec->bucket_width != 0 || spec->n_cells == 1, "mention_summary: bucket_width=0 (no time axis) with n_cells=%u", spec->n_cells);
+    }
+    OI_REQUIRE(B <= 4096, "mention_summary: n_queries=%u outside [0,4096]", B);
+    OI_REQUIRE((uint64_t)B * spec->n_cells <= OI_MAX_GROUP_CELLS, "mention_summary: n_queries * n_cells = %llu cells, more than %u",
+               (unsigned long long)B * spec->n_cells, OI_MAX_GROUP_CELLS);
+    OI_REQUIRE(B == 0 || (qt && qo && out), "mention_summary: null buffer");
+    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "mention_summary: bad location %d", location);
+    uint32_t nt = 0;
+    if (location == OI_HOST && B) { // (device offsets are not host-visible: the plan kernel refuses such a query by itself)
+        for (uint32_t q = 0; q < B; ++q) {
+            OI_REQUIRE(qo[q + 1] >= qo[q], "mention_summary: q_term_offsets decrease at query %u", q);
+            OI_REQUIRE(qo[q + 1] - qo[q] <= OI_MAX_MENTION_TERMS, "mention_summary: query %u has %u terms, more than %u", q, qo[q + 1] - qo[q],
+                       OI_MAX_MENTION_TERMS);
+        }
+        nt = qo[B] - qo[0];
+    }
+    if (!idx) { oi_set_error("mention_summary: null index"); return OI_ERR_INVALID_ARG; }
+    oi_ctx *ctx = idx->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!idx->finalized || !idx->postings.p || !idx->cell_start.p) {
+        oi_set_error("mention_summary: the index is not finalized (oi_index_finalize makes the postings)");
+        return OI_ERR_STATE;
+    }
+    if (!idx->signals.p) { oi_set_error("mention_summary: the index has no signals (oi_index_set_signals)"); return OI_ERR_STATE; }
+    if ((key_axis || filters || spec->bucket_width) && !idx->doc_attrs.p) {
+        oi_set_error("mention_summary: %s the index's doc attributes (oi_index_set_doc_attrs)", key_axis ? "the key axis needs" : SIMILAR_TIME_AXIS);
+        return OI_ERR_STATE;
+    }
+    OI_REQUIRE((uint64_t)idx->n_blocks * B <= 0xFFFFFFFFull, "mention_summary: %llu (query, doc block) tasks, more than 2^32 - 1",
+               (unsigned long long)idx->n_blocks * B);
+    if (B == 0) return OI_OK;
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    const uint4 *filt = reinterpret_cast<const uint4 *>(filters);
+    if (location == OI_DEVICE) return oi_launch_mention_summary(idx, qt, qo, B, *spec, min_match, filt, out);
+    // the host location: [offsets | terms | min_match | filters | records] in the call's workspace, every part 16-byte aligned
+    hipStream_t st = ctx->stream;
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t ob = up16(sizeof(uint32_t) * ((size_t)B + 1)), tb = up16(sizeof(uint32_t) * (size_t)(nt ? nt : 1));
+    const size_t mb = min_match ? up16(sizeof(uint32_t) * (size_t)B) : 0, fb = filters ? sizeof(oi_doc_filter) * (size_t)B : 0;
+    const size_t rb = sizeof(oi_social_counters) * (size_t)B * spec->n_cells;
+    DevBuf &w = ctx->buf("mention_io");
+    OI_CHECK(w.ensure(ob + tb + mb + fb + rb));
+    uint8_t *d = w.as<uint8_t>();
+    std::vector<uint32_t> rel(qo, qo + B + 1); // offsets relative to the first staged term
+    for (uint32_t &o : rel) o -= qo[0];
+    OI_HIP_CHECK(hipMemcpyAsync(d, rel.data(), sizeof(uint32_t) * ((size_t)B + 1), hipMemcpyHostToDevice, st));
+    if (nt) OI_HIP_CHECK(hipMemcpyAsync(d + ob, qt + qo[0], sizeof(uint32_t) * (size_t)nt, hipMemcpyHostToDevice, st));
+    if (min_match) OI_HIP_CHECK(hipMemcpyAsync(d + ob + tb, min_match, sizeof(uint32_t) * (size_t)B, hipMemcpyHostToDevice, st));
+    if (filters) OI_HIP_CHECK(hipMemcpyAsync(d + ob + tb + mb, filters, fb, hipMemcpyHostToDevice, st));
+    OI_HIP_CHECK(hipStreamSynchronize(st)); // (`rel` is pageable and dies with this call)
+    oi_social_counters *d_out = reinterpret_cast<oi_social_counters *>(d + ob + tb + mb + fb);
+    OI_CHECK(oi_launch_mention_summary(idx, reinterpret_cast<const uint32_t *>(d + ob), reinterpret_cast<const uint32_t *>(d), B, *spec,
+                                       min_match ? reinterpret_cast<const uint32_t *>(d + ob + tb) : nullptr,
+                                       filters ? reinterpret_cast<const uint4 *>(d + ob + tb + mb) : nullptr, d_out));
+    OI_HIP_CHECK(hipMemcpyAsync(out, d_out, rb, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipStreamSynchronize(st));
+    return OI_OK;
+}
+
 // ---------------------------------------------------------------- narrative discovery (centroids.hip)
 // The checks keep the family's order: the numbers, the buffers, then the handle; all of them precede the first HIP call.
 

@@ -351,6 +351,10 @@ int oi_launch_similar_groups(oi_index *idx, const float *d_q, uint32_t n_queries
 // (may be null) labels [n_docs] by local row out.  Asynchronous on the ctx stream; d_thresholds and d_filt may be null
 int oi_launch_similar_share(oi_index *idx, const float *d_q, uint32_t n_queries, const oi_summary_spec &spec, const float *d_thresholds,
                             const uint4 *d_filt, oi_social_counters *d_out, uint32_t *d_labels);
+// mention.hip: the mention summary -- device terms / offsets / min_match / filters in, device records
+// [n_queries][n_cells] out, asynchronous on the ctx stream; d_min_match (null: ANY) and d_filt may be null
+int oi_launch_mention_summary(oi_index *idx, const uint32_t *d_terms, const uint32_t *d_offsets, uint32_t n_queries,
+                              const oi_mention_spec &spec, const uint32_t *d_min_match, const uint4 *d_filt, oi_social_counters *d_out);
 // centroids.hip: the update step of a clustering over the index, all asynchronous on the ctx stream -- device
 // labels [n_docs] in, device sums [n_clusters][dim] and counts [n_clusters] out (zeroed by the launch); sums to unit vectors
 // (d_previous may be null or d_out); d_out[0] = rows with d_cur != d_prev, d_out[1] = rows with a label

@@ -645,6 +645,81 @@ class HybridIndex(PostRetriever):
                                              _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(out), _lib.ptr(lab)))
         return (out, lab) if labels else out
 
+    # ---------------------------------------------------------------- mention summary
+    def _mention(self, query_terms, q_term_offsets, spec, min_match, filters):
+        """One oi_mention_summary call: host arrays in, numpy records out; CUDA tensors in, an int64 [B, n, 8] tensor out."""
+        from .analyzer import COUNTERS_DTYPE
+        dev = _is_dev(query_terms) or _is_dev(q_term_offsets)
+        if dev:
+            assert _is_dev(query_terms) and _is_dev(q_term_offsets), "terms and offsets must live in the same place"
+            assert query_terms.is_contiguous() and query_terms.element_size() == 4
+            assert q_term_offsets.is_contiguous() and q_term_offsets.element_size() == 4
+            B = int(q_term_offsets.numel()) - 1
+            if query_terms.numel() == 0:
+                query_terms = self._alloc(True, (1,), np.uint32)
+        else:
+            query_terms, q_term_offsets = _np(query_terms, np.uint32), _np(q_term_offsets, np.uint32)
+            B = int(q_term_offsets.size) - 1
+            if query_terms.size == 0:
+                query_terms = np.zeros(1, dtype=np.uint32)
+        assert B >= 0, "q_term_offsets has n_queries + 1 entries"
+        mm = None
+        if isinstance(min_match, str):
+            assert min_match in ("any", "all"), min_match
+            min_match = None if min_match == "any" else 0
+        if min_match is not None:
+            if not _is_dev(min_match):
+                mm = np.full(B, int(min_match), dtype=np.uint32) if np.ndim(min_match) == 0 else _np(min_match, np.uint32)
+                assert mm.size == B
+                if dev:
+                    import torch
+                    mm = torch.from_numpy(mm.view(np.int32)).to("cuda:%d" % self.ctx.device)
+            else:
+                mm = min_match if dev else _np(min_match.cpu().numpy(), np.uint32)
+                assert (mm.numel() if dev else mm.size) == B and (not dev or (mm.is_contiguous() and mm.element_size() == 4))
+        nc = max(int(spec.n_cells), 0)
+        if dev:
+            import torch
+            out = torch.zeros((B, nc, 8), dtype=torch.int64, device="cuda:%d" % self.ctx.device)
+            self._mention_keep = (query_terms, q_term_offsets, mm)  # (an asynchronous call reads them later)
+        else:
+            out = np.zeros((B, nc), dtype=COUNTERS_DTYPE)
+        f = None if filters is None else self._filters(filters, dev, B)
+        _lib.check(self.lib.oi_mention_summary(self.handle, _lib.ptr(query_terms), _lib.ptr(q_term_offsets), B, C.byref(spec),
+                                               _lib.ptr(mm), _lib.ptr(f), _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(out)))
+        return out
+
+    def mention_summary(self, query_terms, q_term_offsets, min_match=None, n_buckets: int = 1, stamp_origin: int = 0,
+                        bucket_width: int = 0, filters=None):
+        """oi_mention_summary on the time axis: [B, n_buckets] records (analyzer.COUNTERS_DTYPE) of the social_summary sums
+        over this shard's documents that CONTAIN the query's terms, pass filters[q] and fall into bucket
+        (stamp - stamp_origin) // bucket_width (bucket_width = 0: one bucket).  A document matches when at least need_q of
+        the query's DISTINCT terms occur in it: min_match None or "any" -> 1, "all" or 0 -> all of them, an int, or one per
+        query (array).  Needs finalize() and set_signals(); no embeddings.  At most 64 terms per query.  Host arrays in, numpy
+        records out; torch CUDA tensors in, an int64 [B, n_buckets, 8] tensor holding the records' bits out (asynchronous on
+        the ctx stream).  Records of shards add."""
+        spec = _lib.MentionSpec(_lib.OI_MENTION_AXIS_TIME, int(stamp_origin), int(bucket_width), int(n_buckets))
+        return self._mention(query_terms, q_term_offsets, spec, min_match, filters)
+
+    def mention_groups(self, query_terms, q_term_offsets, key_mask: int, n_keys: int, min_match=None, filters=None):
+        """oi_mention_summary on the key axis: [B, n_keys] records, one per key = (group & key_mask) >> ctz(key_mask) of the
+        documents' group attribute (a ticker id, say); a key >= n_keys belongs to no record.  Everything else as
+        mention_summary (filters carry a time window)."""
+        spec = _lib.MentionSpec(_lib.OI_MENTION_AXIS_KEY, int(key_mask), 0, int(n_keys))
+        return self._mention(query_terms, q_term_offsets, spec, min_match, filters)
+
+    def mention_summary_text(self, texts, min_match=None, n_buckets: int = 1, stamp_origin: int = 0, bucket_width: int = 0,
+                             filters=None):
+        """mention_summary with the queries given as text: query_terms(texts), then the call."""
+        qt, qo = self.query_terms(texts)
+        return self.mention_summary(qt, qo, min_match=min_match, n_buckets=n_buckets, stamp_origin=stamp_origin,
+                                    bucket_width=bucket_width, filters=filters)
+
+    def mention_groups_text(self, texts, key_mask: int, n_keys: int, min_match=None, filters=None):
+        """mention_groups with the queries given as text: query_terms(texts), then the call."""
+        qt, qo = self.query_terms(texts)
+        return self.mention_groups(qt, qo, key_mask, n_keys, min_match=min_match, filters=filters)
+
     # ---------------------------------------------------------------- narrative discovery
     def label_sums(self, labels, n_clusters: int):
         """oi_label_sums, the update step of a clustering: (sums int64 [n_clusters, dim], counts uint64 [n_clusters]) over the
