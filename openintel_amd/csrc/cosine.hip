@@ -13,6 +13,7 @@
 
 #include "oi_device.h"
 #include "oi_internal.h"
+#include "oi_ksplit_tile.h" // oi_cosine_ksplit_geometry
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

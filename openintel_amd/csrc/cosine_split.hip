@@ -14,28 +14,22 @@
 // Shape: one workgroup per CU, 4 waves splitting K (wave w owns k in [w D/4, (w+1) D/4)):
 //   * the wave's K-slice of all 64 queries, already split into (H, M, L) bf16 planes by the staging
 //     kernel, lives in registers as MFMA B operands (3 x 96 VGPRs at d = 768);
-//   * the f32 rows stream through the wave's own LDS ring (4 KiB slots of 32 rows x 32 floats; oi_lds_dma.h:
-//     buffer_load ... lds, counted vmcnt waits; the prefetch runs across tiles);
+//   * the f32 rows stream through the wave's own LDS ring (4 KiB slots of 32 rows x 32 floats; oi_ksplit_tile.h: the ring,
+//     the tile ownership and the deferred epilogue are the exact-f32 kernel's, cosine_ksplit.hip);
 //   * per 16 k: two ds_read_b128 (the lane's 8 consecutive floats), ~44 VALU to split and pack them into
 //     the three A operands -- issued in the shadow of the 12 MFMAs (32 cycles each) they feed;
 //   * the big term hH accumulates apart from the five small ones (added at the end), then the four waves'
 //     partial tiles are summed through LDS in a fixed order, filtered against the per-query threshold and
-//     appended to this workgroup's private pool segment.
+//     appended to this workgroup's private pool segment -- inside the next tile's MFMA stream: barrier A before
+//     k-step EPI_G0, the outputs spread over the k-steps from it, barrier B behind the last one.
 #include <cstdlib>
 #include <type_traits>
 
-#include "oi_device.h"
-#include "oi_internal.h"
-#include "oi_lds_dma.h"
+#include "oi_ksplit_tile.h"
 
 typedef float cs_f32x16 __attribute__((ext_vector_type(16)));
 typedef float cs_f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 cs_bf16x8 __attribute__((ext_vector_type(8)));
-
-#define CS_TILE_ROWS 32
-#define CS_SLOT_BYTES 4096 // 32 rows x 128 B (32 floats of K)
-
-__device__ __forceinline__ void cs_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // 8 consecutive floats of a row -> the three bf16x8 A operands (h, m, l), x = h + m + l exactly.
 union CsPack {
@@ -67,20 +61,12 @@ __global__ __launch_bounds__(256, 1) void cosine_split_filter(
     uint32_t n_queries, uint32_t doc_id_base, uint64_t *pools, uint32_t *seg_cnt, uint32_t seg_cnt_stride,
     const uint32_t *tau_keys, uint64_t pool_stride, uint32_t carry_cap, uint32_t seg_cap, uint32_t *overflow) {
     OI_CLAIM_WHOLE_SIMD(); // (MFMA kernel: nothing else may run on this CU -- oi_device.h)
-    constexpr int KS = D / 4;            // K-slice of one wave (floats)
-    constexpr int NKC = KS / 32;         // ring slots per tile and wave
-    constexpr int NBUF = NKC <= 6 ? NKC : NKC / 2;
-    constexpr int P = NBUF - 1;
+    using Tile = OiKsplitTile<D, NQT>;
+    constexpr int KS = Tile::KS, NKC = Tile::NKC, NBUF = Tile::NBUF, P = Tile::P, NG = Tile::NG, N_OUT = Tile::N_OUT;
     constexpr int KSTEPS = KS / 16;      // MFMA groups per tile and wave (two per slot)
-    constexpr int RED = NQT * 16 * 64;   // floats of one wave's partial tile
-    static_assert(KS % 32 == 0 && NKC % NBUF == 0 && P >= 1 && P < NKC, "unsupported D");
     static_assert(3 * NQT * KSTEPS * 4 <= 300, "the split query block must fit the register file");
 
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
-    unsigned char *ring = smem;                                                   // [4][NBUF][4 KiB]
-    float *red = reinterpret_cast<float *>(smem + 4 * NBUF * CS_SLOT_BYTES);      // [4][RED]
-    uint32_t *seg_fill = reinterpret_cast<uint32_t *>(red + 4 * RED);             // [32*NQT]
-
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t li = lane & 31, lh = lane >> 5;
@@ -98,28 +84,10 @@ __global__ __launch_bounds__(256, 1) void cosine_split_filter(
             ql[t][s] = *reinterpret_cast<const cs_bf16x8 *>(qsplit + 2 * PLANE + o);
         }
     uint32_t tau[NQT];
-#pragma unroll
-    for (int t = 0; t < NQT; ++t) {
-        const uint32_t q = 32u * t + li;
-        tau[t] = q < n_queries ? tau_keys[q] : 0xFFFFFFFFu;
-    }
-    if (tid < 32 * NQT) seg_fill[tid] = 0;
+    oi_ks_thresholds<32>(tau, tau_keys, n_queries, li);
 
-    // ---- tiles of this workgroup: blockIdx.x, + gridDim.x, ...
-    const uint64_t n_rows = row_end - row_begin;
-    const uint64_t n_tiles = (n_rows + CS_TILE_ROWS - 1) / CS_TILE_ROWS;
-    const uint64_t my_nt = blockIdx.x < n_tiles ? (n_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
-    if (my_nt == 0) return;
-    uint64_t *my_seg = pools + carry_cap + (uint64_t)blockIdx.x * seg_cap;
-
-    uint32_t voff[4]; // per-lane source of the 4 DMA pieces of a slot (swizzled: 16-B column c of row r at c ^ ((r >> 1) & 7))
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const uint32_t prow = 8 * m + (lane >> 3);
-        voff[m] = prow * (uint32_t)(D * 4) + w * (uint32_t)(KS * 4) + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
-    }
-    const uint32_t ring_w = oi_lds_addr(ring) + w * (NBUF * CS_SLOT_BYTES);
-    const unsigned char *ring_rd = ring + w * (NBUF * CS_SLOT_BYTES);
+    Tile tile;
+    if (!tile.open(smem, w, rows, row_begin, row_end, pools, carry_cap, seg_cap, pool_stride, doc_id_base, overflow)) return;
     // fragment (slot half g in {0,1}): the lane's floats 16 g + 8 lh .. + 8 = logical 16-B columns 4g + 2lh, + 1
     uint32_t frag_off[2][2];
 #pragma unroll
@@ -127,80 +95,56 @@ __global__ __launch_bounds__(256, 1) void cosine_split_filter(
 #pragma unroll
         for (int c = 0; c < 2; ++c) frag_off[g][c] = li * 128 + (((4 * g + 2 * lh + c) ^ ((li >> 1) & 7)) << 4);
 
-    auto tile_row0 = [&](uint64_t ti) { return row_begin + (blockIdx.x + ti * gridDim.x) * (uint64_t)CS_TILE_ROWS; };
-    // Past the workgroup's last tile the descriptor is empty: its loads return zeros, so the tile loop needs no
-    // branch around the prefetch (and no second set of wait counts) -- a branch-free body is also what lets the
-    // scheduler interleave the split arithmetic with the MFMAs.
-    auto tile_srd = [&](uint64_t ti) {
-        const uint64_t r0 = tile_row0(ti < my_nt ? ti : 0);
-        return oi_make_srd(rows + r0 * D, ti < my_nt ? (row_end - r0) * (uint64_t)(D * 4) : 0ull);
-    };
-    oi_u32x4 cur = tile_srd(0), nxt = tile_srd(1);
-    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only: retire every load hipcc knows about, here
-#pragma unroll
-    for (int kc = 0; kc < P; ++kc)
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-            oi_dma_piece(cur, voff[m], kc * 128, ring_w + (kc % NBUF) * CS_SLOT_BYTES + m * 1024, (DBG & 1) != 0);
-    float *my_red = red + w * RED;
+    tile.start_ring(lane, w, (DBG & 1) != 0);
 
-    // ---- deferred epilogue (as in cosine_ksplit.hip).  A tile's partial sums go to LDS right after its last
-    // MFMA; the cross-wave sum + filter of tile t then rides INSIDE tile t+1's MFMA stream (barrier A before
-    // k-step EPI_G0, one output per thread per k-step, barrier B behind the last one), so the DMA ring keeps
-    // being refilled while the epilogue's LDS round trips and stores go out.
-    uint64_t prev_row0 = 0; // first corpus row of the tile whose partials sit in `red`
-    bool have_prev = false;  // false during the first tile: `red` holds nothing yet
+    // element e = tid + 256 i of a partial tile is (t * 16 + r) * 64 + lane with t = i >> 2, r = (e >> 6) & 15: register r
+    // of query tile t, D[row (r&3) + 8 (r>>2) + 4 lh][query 32 t + li]
     auto epi_out = [&](int i) {
-        const uint32_t e = tid + 256u * i; // (t = i>>2, r = (e>>6)&15, lane)
-        const float s = (red[e] + red[RED + e]) + (red[2 * RED + e] + red[3 * RED + e]);
+        const uint32_t e = tid + 256u * i;
+        const float s = tile.sum(e);
         const uint32_t t = i >> 2, r = (e >> 6) & 15u;
-        const uint32_t q = 32u * t + li;
-        const uint64_t row = prev_row0 + (r & 3u) + 8u * (r >> 2) + 4u * lh;
-        if (have_prev && row < row_end && s == s && oi_f32_key(s) >= tau[t]) {
-            const uint32_t pos = atomicAdd(&seg_fill[q], 1u); // LDS
-            if (pos < seg_cap) my_seg[(uint64_t)q * pool_stride + pos] = oi_rank_key(s, doc_id_base + (uint32_t)row);
-            else *overflow = 1u;
-        }
+        OI_KS_OUT(tile, s, 32u * t + li, tile.prev_row0 + (r & 3u) + 8u * (r >> 2) + 4u * lh, tau[t], true);
     };
-    constexpr int NG = NKC * 2;                              // k-steps per tile
     constexpr int EPI_G0 = 1;                                // first k-step with outputs
-    constexpr int EPI_PER = (NQT * 4 + (NG - 2) - 1) / (NG - 2); // outputs per thread and k-step (2 at d = 384)
-    constexpr int EPI_STEPS = (NQT * 4 + EPI_PER - 1) / EPI_PER;
+    constexpr int EPI_PER = (N_OUT + (NG - 2) - 1) / (NG - 2); // outputs per thread and k-step (2 at d = 384)
+    constexpr int EPI_STEPS = (N_OUT + EPI_PER - 1) / EPI_PER;
     constexpr int EPI_GB = EPI_G0 + EPI_STEPS;               // k-step of barrier B
     static_assert(EPI_GB <= NG - 1, "tile too short to host the deferred epilogue");
 
-    for (uint64_t ti = 0; ti < my_nt; ++ti) {
-        have_prev = ti > 0;
+    for (uint64_t ti = 0; ti < tile.my_nt; ++ti) {
+        // (`red` holds the previous tile.  With two query tiles the flag is computed from ti here; with one it is carried from the
+        // end of the first tile, below.  The other form costs <768, 2> 16 register moves inside its MFMA stream and 0.5 % of its
+        // step, and <768, 1> 0.7 % -- DESIGN 4.1b)
+        if constexpr (NQT == 2) tile.begin(ti);
         // hH accumulates apart from the five small terms; with one query tile the small terms use two
         // accumulators so that no MFMA waits for the one issued right before it
-        cs_f32x16 acc[NQT], cor[NQT], cor2[NQT == 1 ? 1 : 1];
+        cs_f32x16 acc[NQT], cor[NQT], cor2; // (cor2: with one query tile only)
 #pragma unroll
         for (int t = 0; t < NQT; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) { acc[t][r] = 0.f; cor[t][r] = 0.f; }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) cor2[0][r] = 0.f;
+        for (int r = 0; r < 16; ++r) cor2[r] = 0.f;
 
         oi_wait_vm<4 * (P - 1)>();
         cs_bf16x8 ah, am, al; // A operands of the current k-step
         {
-            const cs_f32x4 f0 = *reinterpret_cast<const cs_f32x4 *>(ring_rd + frag_off[0][0]);
-            const cs_f32x4 f1 = *reinterpret_cast<const cs_f32x4 *>(ring_rd + frag_off[0][1]);
+            const cs_f32x4 f0 = *reinterpret_cast<const cs_f32x4 *>(tile.ring_rd + frag_off[0][0]);
+            const cs_f32x4 f1 = *reinterpret_cast<const cs_f32x4 *>(tile.ring_rd + frag_off[0][1]);
             if constexpr ((DBG & 4) != 0) { CsPack pk; pk.u[0] = __float_as_uint(f0[0]); pk.u[1] = __float_as_uint(f0[1]); pk.u[2] = __float_as_uint(f1[0]); pk.u[3] = __float_as_uint(f1[1]); ah = am = al = pk.v; }
             else cs_split8(f0, f1, ah, am, al);
         }
         oi_static_for<0, NG>([&](auto gi_) {
             constexpr int gi = decltype(gi_)::value; // k-step of the tile
             constexpr int kc = gi / 2, g = gi % 2;
-            constexpr int sn = kc + P;               // slot refilled during this slot's k-steps
             // The NEXT k-step's floats are read now and split into its three operands WHILE this k-step's MFMAs
             // run: one wave per SIMD issues in order, so the split has to sit between the MFMAs in program order
             // (sched_group_barrier below) to execute in their shadow.
             cs_bf16x8 nh = ah, nm = am, nl = al;
             if constexpr (gi + 1 < NG) {
                 constexpr int nslot = g == 0 ? kc : kc + 1, nhalf = g == 0 ? 1 : 0;
-                const cs_f32x4 f0 = *reinterpret_cast<const cs_f32x4 *>(ring_rd + (nslot % NBUF) * CS_SLOT_BYTES + frag_off[nhalf][0]);
-                const cs_f32x4 f1 = *reinterpret_cast<const cs_f32x4 *>(ring_rd + (nslot % NBUF) * CS_SLOT_BYTES + frag_off[nhalf][1]);
+                const cs_f32x4 f0 = *reinterpret_cast<const cs_f32x4 *>(tile.ring_rd + (nslot % NBUF) * OI_KS_SLOT_BYTES + frag_off[nhalf][0]);
+                const cs_f32x4 f1 = *reinterpret_cast<const cs_f32x4 *>(tile.ring_rd + (nslot % NBUF) * OI_KS_SLOT_BYTES + frag_off[nhalf][1]);
                 if constexpr ((DBG & 4) != 0) { CsPack pk; pk.u[0] = __float_as_uint(f0[0]); pk.u[1] = __float_as_uint(f0[1]); pk.u[2] = __float_as_uint(f1[0]); pk.u[3] = __float_as_uint(f1[1]); nh = nm = nl = pk.v; }
                 else cs_split8(f0, f1, nh, nm, nl);
             }
@@ -223,10 +167,10 @@ __global__ __launch_bounds__(256, 1) void cosine_split_filter(
                 cor[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, qm[1][gi], cor[1], 0, 0, 0);
             } else {
                 cor[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, qh[0][gi], cor[0], 0, 0, 0);
-                cor2[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, ql[0][gi], cor2[0], 0, 0, 0);
+                cor2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, ql[0][gi], cor2, 0, 0, 0);
                 acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, qh[0][gi], acc[0], 0, 0, 0);
                 cor[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, qm[0][gi], cor[0], 0, 0, 0);
-                cor2[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, qh[0][gi], cor2[0], 0, 0, 0);
+                cor2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, qh[0][gi], cor2, 0, 0, 0);
                 cor[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, qm[0][gi], cor[0], 0, 0, 0);
             }
             if constexpr ((DBG & 6) == 0) {
@@ -242,20 +186,14 @@ __global__ __launch_bounds__(256, 1) void cosine_split_filter(
             }
             // two DMA pieces per k-step: slot kc + P goes into the buffer slot kc - 1 has vacated
 #pragma unroll
-            for (int m = 2 * g; m < 2 * g + 2; ++m) {
-                if constexpr (sn < NKC)
-                    oi_dma_piece(cur, voff[m], sn * 128, ring_w + (sn % NBUF) * CS_SLOT_BYTES + m * 1024, (DBG & 1) != 0);
-                else
-                    oi_dma_piece(nxt, voff[m], (sn - NKC) * 128, ring_w + (sn % NBUF) * CS_SLOT_BYTES + m * 1024,
-                                   (DBG & 1) != 0);
-            }
-            if constexpr (gi == EPI_G0 - 1 && !(DBG & 8)) cs_barrier();                        // (A) partials visible
+            for (int m = 2 * g; m < 2 * g + 2; ++m) tile.refill(kc + P, m, (DBG & 1) != 0);
+            if constexpr (gi == EPI_G0 - 1 && !(DBG & 8)) oi_ks_barrier();                        // (A) partials visible
             if constexpr (gi >= EPI_G0 && gi < EPI_GB && !(DBG & 8)) {
 #pragma unroll
                 for (int o = 0; o < EPI_PER; ++o)
-                    if ((gi - EPI_G0) * EPI_PER + o < NQT * 4) epi_out((gi - EPI_G0) * EPI_PER + o);
+                    if ((gi - EPI_G0) * EPI_PER + o < N_OUT) epi_out((gi - EPI_G0) * EPI_PER + o);
             }
-            if constexpr (gi == EPI_GB && !(DBG & 8)) cs_barrier();                            // (B) `red` is free again
+            if constexpr (gi == EPI_GB && !(DBG & 8)) oi_ks_barrier();                            // (B) `red` is free again
             // the next k-step reads slot kc + 1 when this one is the slot's first half: it has to have landed
             // (the two pieces of slot kc + P issued just above may still be in flight with P - 2 younger slots)
             if constexpr (g == 0 && kc + 1 < NKC) oi_wait_vm<4 * (P - 2) + 2>();
@@ -267,20 +205,14 @@ __global__ __launch_bounds__(256, 1) void cosine_split_filter(
         for (int t = 0; t < NQT; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                my_red[(t * 16 + r) * 64 + lane] = acc[t][r] + (NQT == 1 ? cor[t][r] + cor2[0][r] : cor[t][r]);
-        prev_row0 = tile_row0(ti);
-        cur = nxt;
-        nxt = tile_srd(ti + 2);
+                tile.my_red[(t * 16 + r) * 64 + lane] = acc[t][r] + (NQT == 1 ? cor[t][r] + cor2[r] : cor[t][r]);
+        tile.next(ti);
+        if constexpr (NQT == 1) tile.have_prev = true;
     }
-    have_prev = true;
-    cs_barrier(); // the last tile's epilogue has no MFMA stream to hide in
+    tile.last();
 #pragma unroll
-    for (int i = 0; i < NQT * 4; ++i) epi_out(i);
-    cs_barrier();
-    if (tid < 32 * NQT && tid < n_queries) {
-        const uint32_t c = seg_fill[tid];
-        seg_cnt[(uint64_t)tid * seg_cnt_stride + blockIdx.x] = c < seg_cap ? c : seg_cap;
-    }
+    for (int i = 0; i < N_OUT; ++i) epi_out(i);
+    tile.close(n_queries, seg_cnt, seg_cnt_stride);
 }
 
 // ------------------------------------------------------------------ query staging: f32 -> (H, M, L) bf16 planes
@@ -312,18 +244,10 @@ bool oi_cosine_split_supported(uint32_t dim) { return dim == 384 || dim == 768; 
 template <int D, int NQT, int DBG = 0>
 static int launch_split(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end, const uint16_t *q,
                         uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
-    constexpr int KS = D / 4, NKC = KS / 32, NBUF = NKC <= 6 ? NKC : NKC / 2;
-    constexpr size_t smem = 4 * NBUF * CS_SLOT_BYTES + 4 * (NQT * 16 * 64) * 4 + 64 * 4;
-    OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(cosine_split_filter<D, NQT, DBG>), (size_t)(smem)));
-    hipLaunchKernelGGL((cosine_split_filter<D, NQT, DBG>), dim3(p.n_segs), dim3(256), smem, ctx->stream, rows, row_begin,
-                       row_end, q, nq, doc_id_base, p.keys, p.seg_cnt, p.seg_cnt_stride, p.tau_keys, p.stride,
-                       p.carry_cap, p.seg_cap, p.overflow);
-    OI_HIP_CHECK(hipGetLastError());
-    return OI_OK;
+    return oi_ksplit_launch<D, NQT>(ctx, cosine_split_filter<D, NQT, DBG>, rows, row_begin, row_end, q, nq, doc_id_base, p);
 }
 
-// One group of <= 64 queries (f32, device) over rows [row_begin, row_end); same pool geometry as the K-split
-// kernel (one segment per workgroup, oi_cosine_ksplit_geometry).
+// One group of <= 64 queries (f32, device) over rows [row_begin, row_end); the pool has oi_cosine_ksplit_geometry.
 int oi_launch_cosine_split(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end, uint32_t dim,
                            const float *d_queries, uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
     OI_REQUIRE(oi_cosine_split_supported(dim), "cosine (split products): dim %u not instantiated (384, 768)", dim);

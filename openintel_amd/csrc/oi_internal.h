@@ -380,9 +380,8 @@ bool oi_cosine_bf16_supported(uint32_t dim);
 int oi_launch_cosine_bf16_chunk(oi_ctx *ctx, const uint16_t *rows, uint64_t row_begin, uint64_t row_end, uint32_t dim,
                                 const float *d_queries, uint32_t n_queries, uint32_t doc_id_base, PoolView &pool);
 uint32_t oi_cosine_query_padding(uint32_t n_queries);
-// cosine_ksplit.hip
+// cosine_ksplit.hip (the pool geometry of its chunks: oi_cosine_ksplit_geometry, oi_ksplit_tile.h)
 bool oi_cosine_ksplit_supported(uint32_t dim);
-void oi_cosine_ksplit_geometry(const oi_ctx *ctx, uint64_t n_rows, uint32_t *n_segs, uint32_t *seg_cap);
 // cosine_prefilter.hip: the bf16 screen + exact rescoring of an f32 corpus
 bool oi_cosine_screen_supported(uint32_t dim);
 // The bf16 screen (and the screening copies behind it) applies to this index's corpus: f32 rows of a dim the screen kernels are

@@ -1,7 +1,8 @@
 // oi_lds_dma.h -- what the streaming kernels share: the LDS-DMA ring primitives (descriptor, one 1-KiB piece, the counted
 // wait, the compile-time loop the ring schedules are written in) and the per-wave staging ring the survivors leave through.
-// Users: cosine_ksplit, cosine_split, cosine_bf16, cosine_screen_i8 (.hip), and oi_screen_tile.h: the tile pipeline that
-// cosine_prefilter, cosine_screen_copy, cosine_volume and cosine_summary (.hip, the last two through oi_volume.h) are written on.
+// Users: cosine_bf16, cosine_screen_i8 (.hip), oi_ksplit_tile.h: what cosine_ksplit and cosine_split (.hip) are written on, and
+// oi_screen_tile.h: the tile pipeline that cosine_prefilter, cosine_screen_copy, cosine_volume and cosine_summary (.hip, the
+// last two through oi_volume.h) are written on.
 //
 // THE CONTRACT of an LDS-DMA load (`buffer_load_dwordx4 ... lds`: 64 lanes x 16 B from each lane's own source offset into
 // 1 KiB of LDS at M0 + 16 * lane, no register destination):
@@ -78,6 +79,20 @@ template <bool STREAM = true>
 __device__ __forceinline__ void oi_dma_piece(const oi_u32x4 &srd, uint32_t voff, uint32_t soff, uint32_t lds_dst, bool skip) {
     if (skip) return;
     oi_dma_piece<STREAM>(srd, voff, soff, lds_dst);
+}
+// Per-lane source of the 4 pieces of a slot (32 rows x 128 B): piece m covers tile rows 8m..8m+7; lane l -> row 8m + (l>>3),
+// physical 16-B column l&7 holding LOGICAL column (l&7) ^ ((row>>1)&7), so that the ds_read_b128 fragment reads are
+// conflict-free.  ROW_BYTES: 2 D (bf16 rows) or 4 D (f32).  base (wave-uniform bytes): where the wave's K-slice starts in a
+// row; OiKsplitTile (oi_ksplit_tile.h) is its one caller.  cosine_bf16.hip (the kh * KH * 2 half of cosine_bf16_pair among
+// its three sites) and cosine_screen_i8.hip write the same offsets in loops of their own: as a call the arithmetic is
+// canonicalised apart from the kernel's other lane arithmetic and every kernel of those files comes out different.
+template <uint32_t ROW_BYTES>
+__device__ __forceinline__ void oi_tile_voff(uint32_t (&voff)[4], uint32_t lane, uint32_t base = 0) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const uint32_t prow = 8 * m + (lane >> 3);
+        voff[m] = prow * ROW_BYTES + base + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
+    }
 }
 // f(integral_constant<int, I>) for I in [I, N): a ring schedule's slots and waits are compile-time constants.
 template <int I, int N, class F>

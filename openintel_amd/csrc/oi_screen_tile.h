@@ -3,8 +3,8 @@
 // All three run one persistent workgroup of 4 waves per segment; a wave holds the whole query block as bf16 B operands in
 // registers, owns every (4 x grid)-th 32-row tile and streams its tiles through its own LDS ring of 4-KiB slots (32 rows x 128 B)
 // with the LDS-DMA loads of oi_lds_dma.h (read THE CONTRACT there first: everything below is written around it).  Here:
-//   * the query block preload, the wave's tile ownership with its buffer descriptors, the swizzled DMA source offsets, the
-//     retiring wait for the loads hipcc knows about, the score test and the ragged-tile mask        (all three kernels);
+//   * the query block preload, the wave's tile ownership with its buffer descriptors, the retiring wait for the loads
+//     hipcc knows about, the score test and the ragged-tile mask (the swizzled DMA source offsets: oi_lds_dma.h) (all three kernels);
 //   * OiCopyRing: the ring over bf16 rows with a run-time ring offset                    (copy screen and vo_stream_kernel;
 //     cosine_screen_filter keeps its own k-loop: a compile-time ring index, two ds_read_b128 and four conversions per k-step);
 //   * the threshold decode and OiPoolSink, the survivor epilogue into the candidate pool (copy screen and f32 screen;
@@ -46,17 +46,6 @@ __device__ __forceinline__ void oi_tile_load_queries(oi_bf16x8 (&qreg)[NQT][D / 
 // otherwise it re-waits for them inside the tile loop and drains the DMA ring.
 __device__ __forceinline__ void oi_tile_retire_visible_loads() {
     __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only
-}
-
-// Per-lane source of the 4 DMA pieces of a slot: piece m covers tile rows 8m..8m+7; lane l -> row 8m + (l>>3), physical 16-B
-// column l&7 holding LOGICAL column (l&7) ^ ((row>>1)&7).  ROW_BYTES: 2 D (bf16 rows) or 4 D (f32 rows).
-template <uint32_t ROW_BYTES>
-__device__ __forceinline__ void oi_tile_voff(uint32_t (&voff)[4], uint32_t lane) {
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const uint32_t prow = 8 * m + (lane >> 3);
-        voff[m] = prow * ROW_BYTES + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
-    }
 }
 
 // The tiles of this WAVE among rows [row_begin, row_end): (blockIdx.x * 4 + w), + 4 * gridDim.x, ...
