@@ -159,6 +159,11 @@ extern "C" int oi_profile_read(oi_ctx *ctx, const char *kernel_tag, double *tota
         if (launches_out) *launches_out = (uint64_t)ctx->num_cus;
         return OI_OK;
     }
+    if (strcmp(kernel_tag, "screen_sample") == 0) { // diagnostics: rows of the last search's sample pass (search.hip), 0 = it took none
+        if (total_ms_out) *total_ms_out = (double)ctx->last_sample_rows;
+        if (launches_out) *launches_out = 0;
+        return OI_OK;
+    }
     if (strcmp(kernel_tag, "volume_state") == 0 || strcmp(kernel_tag, "summary_state") == 0 || strcmp(kernel_tag, "groups_state") == 0 ||
         strcmp(kernel_tag, "share_state") == 0) {
         // diagnostics of the last oi_similar_volume / oi_similar_summary / oi_similar_groups / oi_similar_share: undecided pairs its stream sent to the band (may exceed

@@ -255,6 +255,11 @@ __device__ __forceinline__ void i8s_issue_meta(const oi_u32x4 &srd, uint32_t vof
 #endif
 }
 
+// The lower bound a pair is keyed by, l = s~ - (e_r |q^| + c_q) with s~ = f32(S) (scale a / 128): ONE body for the screen's
+// survivor path and the sample pass, so both round alike (qa = a / 128).
+__device__ __forceinline__ float i8s_screen_score(int S, float scale, float qa) { return (float)S * (scale * qa); }
+__device__ __forceinline__ float i8s_lower_bound(float sc, float er, float qn, float cq) { return sc - fmaf(er, qn, cq); }
+
 template <int D, int NQT, int NBUF, bool FILT>
 __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
     const uint8_t *__restrict__ rows, const float *__restrict__ meta, uint64_t row_begin, uint64_t row_end,
@@ -538,7 +543,7 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
                         const uint32_t bit = (uint32_t)__builtin_ctz(m), r = bit & 15u;
                         const bool t1 = NQT > 1 && bit >= 16u;
                         const uint32_t rit = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        const float low = cap_sc - fmaf(cap_er, t1 ? qn[NQT - 1] : qn[0], t1 ? cq[NQT - 1] : cq[0]);
+                        const float low = i8s_lower_bound(cap_sc, cap_er, t1 ? qn[NQT - 1] : qn[0], t1 ? cq[NQT - 1] : cq[0]);
                         const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(has >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)has, 0u));
                         const uint32_t idx = (st_head + st_n + below) & (OI_STAGE - 1);
                         stage_keys[idx] = oi_rank_key(low, doc_id_base + ((uint32_t)row0 + rit));
@@ -558,8 +563,8 @@ __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
                     auto lower_key = [&](int t, uint32_t r) -> uint64_t { // (survivors only: the metadata read again)
                         const uint32_t rit = (r & 3) + 8 * (r >> 2) + 4 * lh;
                         const i8s_f32x2 md = *reinterpret_cast<const i8s_f32x2 *>(mt + rit * 8);
-                        const float sc = (float)S[16 * t + r] * (md[0] * qa[t]);
-                        return oi_rank_key(sc - fmaf(md[1], qn[t], cq[t]), doc_id_base + ((uint32_t)row0 + rit));
+                        const float sc = i8s_screen_score(S[16 * t + r], md[0], qa[t]);
+                        return oi_rank_key(i8s_lower_bound(sc, md[1], qn[t], cq[t]), doc_id_base + ((uint32_t)row0 + rit));
                     };
                     if (total <= OI_STAGE - OI_STAGE_FLUSH) {
                         uint32_t idx = st_head + st_n + incl - cnt;
@@ -669,6 +674,152 @@ int oi_launch_cosine_screen_i8_chunk(oi_ctx *ctx, const uint8_t *i8_copy, uint64
         } else {
             if (two) OI_CHECK((launch_i8_screen<384, 2, 6>(ctx, i8_copy, meta, row_begin, row_end, qhi, qlo, qfp, np, nq_here, doc_id_base, p)));
             else OI_CHECK((launch_i8_screen<384, 1, 6>(ctx, i8_copy, meta, row_begin, row_end, qhi, qlo, qfp, np, nq_here, doc_id_base, p)));
+        }
+    }
+    return OI_OK;
+}
+
+// ------------------------------------------------------------------ the sample pass
+// What the first speculative threshold is read from (search.hip, Plan::sample_rows): the lower-bound score keys of
+// rows [0, m) against every query, dense, keys[q][row] of a [padded queries][key_stride] array -- no thresholds, no pools, no
+// survivor path.  One 32-row tile per wave, the row fragments straight from global memory (a lane's KSTEPS 16-byte loads are
+// all in flight before the first MFMA); the hi and lo query fragments go to LDS once per workgroup, fragment-major as the screen
+// keeps its lo parts (a wave with one tile would read 48 KB of hi parts for 24 KB of rows: with the hi parts in registers per
+// wave, as in the screen, the launch took 22 us, most of it the query block's trips from L2).
+// Register r of query tile t is row (r&3) + 8 (r>>2) + 4 lh of the tile: four consecutive rows per r >> 2, one 16-byte store.
+// Key 0 (below every real key) for a row past m, a long row (they must not move a threshold: the margin selects skip them), a
+// padding query and a score that is NaN (the screen's test keeps no such pair either).
+template <int D, int NQT>
+__global__ __launch_bounds__(256, 1) void i8s_sample_kernel(const uint8_t *__restrict__ rows, const float *__restrict__ meta, uint32_t m_rows,
+                                                            const int8_t *__restrict__ qhi, const int8_t *__restrict__ qlo,
+                                                            const float *__restrict__ qf, uint32_t qf_stride, uint32_t n_queries,
+                                                            const uint32_t *__restrict__ long_bitmap, uint32_t *__restrict__ keys,
+                                                            uint32_t key_stride) {
+    constexpr int KSTEPS = D / 32;
+    constexpr uint32_t PART = NQT * KSTEPS * 64; // 16-byte fragments of the hi parts; as many of the lo parts
+    static_assert(D % 32 == 0 && KSTEPS * 4 <= 128, "a tile's row fragments must fit the register file");
+    static_assert(2 * PART * 16 <= 160 * 1024, "LDS");
+    extern __shared__ __attribute__((aligned(1024))) unsigned char smem[]; // [hi, lo][NQT][KSTEPS][64 lanes][16 B]
+    OI_CLAIM_WHOLE_SIMD(); // (MFMA kernel: nothing else may run on this CU -- oi_device.h)
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t li = lane & 31, lh = lane >> 5;
+    const uint32_t row0 = (blockIdx.x * 4u + w) * I8S_TILE_ROWS; // (a wave past the last tile only helps to fill the LDS)
+    const bool has_tile = row0 < m_rows;
+
+    // A[m = li][k = 32 s + 16 lh + 0..15]; a row past the end reads the last row (its keys are 0)
+    const uint32_t arow = has_tile ? (row0 + li < m_rows ? row0 + li : m_rows - 1u) : 0u;
+    i8s_i32x4 a[KSTEPS];
+#pragma unroll
+    for (int s = 0; s < KSTEPS; ++s) a[s] = *reinterpret_cast<const i8s_i32x4 *>(rows + (uint64_t)arow * D + 32 * s + 16 * lh);
+    // B[k = 32 s + 16 (l >> 5) + 0..15][n = l & 31] of query tile t, hi then lo: a thread's NCP fragments are all loaded before the
+    // first goes to LDS (as a loop of load, wait, write the copy was NCP trips to L2 one after the other)
+    constexpr int NCP = 2 * PART / 256;
+    static_assert(NCP * 256 == 2 * PART, "whole trips of the workgroup");
+    i8s_i32x4 qv[NCP];
+#pragma unroll
+    for (int i = 0; i < NCP; ++i) {
+        const uint32_t c = tid + 256u * i, f = c % PART, t = f / (KSTEPS * 64), s = (f / 64) % KSTEPS, l = f % 64;
+        qv[i] = *reinterpret_cast<const i8s_i32x4 *>((c < PART ? qhi : qlo) + (uint64_t)(32 * t + (l & 31)) * D + 32 * s + 16 * (l >> 5));
+    }
+#pragma unroll
+    for (int i = 0; i < NCP; ++i) *reinterpret_cast<i8s_i32x4 *>(smem + (tid + 256u * i) * 16) = qv[i];
+    // {scale, e_r} of this lane's 16 rows: rows 8 j + 4 lh + 0..3 of the tile are 32 contiguous bytes (the copy's metadata is
+    // padded by I8S_PAD_ROWS rows of zeros: a ragged tile reads inside it)
+    float4 md[4][2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float4 *mp = reinterpret_cast<const float4 *>(meta + 2 * (uint64_t)((has_tile ? row0 : 0u) + 8 * j + 4 * lh));
+        md[j][0] = mp[0];
+        md[j][1] = mp[1];
+    }
+    const uint32_t long_word = long_bitmap && has_tile ? long_bitmap[row0 >> 5] : 0u;
+    float qa[NQT], qn[NQT], cq[NQT];
+#pragma unroll
+    for (int t = 0; t < NQT; ++t) {
+        const uint32_t q = 32u * t + li;
+        const bool real = q < n_queries;
+        qa[t] = real ? qf[q] * 0.0078125f : 0.f; // a / 128, as the screen
+        qn[t] = real ? qf[qf_stride + q] : 0.f;
+        cq[t] = real ? qf[2 * qf_stride + q] : 0.f;
+    }
+    __syncthreads(); // the only barrier: the query fragments are in LDS
+    if (!has_tile) return;
+
+    i8s_i32x16 ah[NQT], al[NQT];
+#pragma unroll
+    for (int t = 0; t < NQT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { ah[t][r] = 0; al[t][r] = 0; }
+#pragma unroll
+    for (int s = 0; s < KSTEPS; ++s)
+#pragma unroll
+        for (int t = 0; t < NQT; ++t) {
+            const unsigned char *frag = smem + ((t * KSTEPS + s) * 64 + lane) * 16;
+            const i8s_i32x4 bh = *reinterpret_cast<const i8s_i32x4 *>(frag), bl = *reinterpret_cast<const i8s_i32x4 *>(frag + PART * 16);
+            ah[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], bh, ah[t], 0, 0, 0);
+            al[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], bl, al[t], 0, 0, 0);
+        }
+#pragma unroll
+    for (int t = 0; t < NQT; ++t) {
+        const uint32_t q = 32u * t + li;
+        const bool real = q < n_queries;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float scale[4] = {md[j][0].x, md[j][0].z, md[j][1].x, md[j][1].z};
+            const float er[4] = {md[j][0].y, md[j][0].w, md[j][1].y, md[j][1].w};
+            uint32_t k[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const uint32_t rit = (uint32_t)(c + 8 * j) + 4u * lh;
+                const float sc = i8s_screen_score(ah[t][4 * j + c] * 128 + al[t][4 * j + c], scale[c], qa[t]);
+                const bool keep = real && row0 + rit < m_rows && !((long_word >> rit) & 1u) && sc == sc;
+                k[c] = keep ? oi_f32_key(i8s_lower_bound(sc, er[c], qn[t], cq[t])) : 0u;
+            }
+            // (key_stride is a multiple of 32: the tile's columns are there for every query, 16-byte aligned)
+            *reinterpret_cast<uint4 *>(keys + (uint64_t)q * key_stride + row0 + 8 * j + 4 * lh) = make_uint4(k[0], k[1], k[2], k[3]);
+        }
+    }
+}
+
+template <int D, int NQT>
+static int launch_i8_sample(oi_ctx *ctx, const uint8_t *rows, const float *meta, uint32_t m_rows, const int8_t *qhi, const int8_t *qlo,
+                            const float *qf, uint32_t qf_stride, uint32_t nq, const uint32_t *long_bitmap, uint32_t *keys, uint32_t key_stride) {
+    constexpr size_t smem = 2 * NQT * (D / 32) * 64 * 16;
+    OI_CHECK(oi_dyn_lds(ctx, reinterpret_cast<const void *>(i8s_sample_kernel<D, NQT>), smem));
+    const uint32_t tiles = (m_rows + I8S_TILE_ROWS - 1) / I8S_TILE_ROWS;
+    hipLaunchKernelGGL((i8s_sample_kernel<D, NQT>), dim3((tiles + 3) / 4), dim3(256), smem, ctx->stream, rows, meta, m_rows, qhi, qlo, qf,
+                       qf_stride, nq, long_bitmap, keys, key_stride);
+    OI_HIP_CHECK(hipGetLastError());
+    return OI_OK;
+}
+
+uint32_t oi_screen_i8_sample_stride(uint32_t m_rows) { return (m_rows + 31u) & ~31u; }
+
+// The lower-bound score keys of rows [0, m_rows) of the index's int8 copy against every query of the batch:
+// keys[(padded queries)][oi_screen_i8_sample_stride(m_rows)].  qi8 / qf: staged by oi_launch_screen_stage_i8.
+int oi_launch_screen_i8_sample(oi_ctx *ctx, const uint8_t *i8_copy, uint64_t n_rows_total, uint32_t m_rows, uint32_t dim, const int8_t *qi8,
+                               const float *qf, uint32_t n_queries, const uint32_t *long_bitmap, uint32_t *keys) {
+    OI_REQUIRE(oi_cosine_screen_supported(dim), "cosine screen (int8 sample): dim %u not instantiated (384, 768)", dim);
+    OI_REQUIRE(m_rows <= n_rows_total, "cosine screen (int8 sample): rows past the copy");
+    if (m_rows == 0 || n_queries == 0) return OI_OK;
+    const float *meta = reinterpret_cast<const float *>(i8_copy + oi_screen_i8_meta_offset(n_rows_total, dim));
+    const uint32_t np = (n_queries + 31u) & ~31u, ks = oi_screen_i8_sample_stride(m_rows);
+    // two spans: "sample" is this launch's own tag; "cosine" goes on counting one span per scoring launch of the cosine leg, this
+    // one in the pooled first chunk's place (the schedule checks and the scorer's share of a step read that tag)
+    ProfScope pc(ctx, "cosine");
+    ProfScope ps(ctx, "sample");
+    for (uint32_t q0 = 0; q0 < n_queries; q0 += 64) {
+        const uint32_t nq_here = std::min(64u, n_queries - q0);
+        const int8_t *qhi = qi8 + (uint64_t)q0 * dim, *qlo = qi8 + ((uint64_t)np + q0) * dim;
+        uint32_t *kq = keys + (uint64_t)q0 * ks;
+        const bool two = nq_here > 32;
+        if (dim == 768) {
+            if (two) OI_CHECK((launch_i8_sample<768, 2>(ctx, i8_copy, meta, m_rows, qhi, qlo, qf + q0, np, nq_here, long_bitmap, kq, ks)));
+            else OI_CHECK((launch_i8_sample<768, 1>(ctx, i8_copy, meta, m_rows, qhi, qlo, qf + q0, np, nq_here, long_bitmap, kq, ks)));
+        } else {
+            if (two) OI_CHECK((launch_i8_sample<384, 2>(ctx, i8_copy, meta, m_rows, qhi, qlo, qf + q0, np, nq_here, long_bitmap, kq, ks)));
+            else OI_CHECK((launch_i8_sample<384, 1>(ctx, i8_copy, meta, m_rows, qhi, qlo, qf + q0, np, nq_here, long_bitmap, kq, ks)));
         }
     }
     return OI_OK;

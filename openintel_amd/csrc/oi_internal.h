@@ -138,6 +138,7 @@ struct oi_ctx {
     const uint32_t *run_gate = nullptr;
     const uint32_t *last_screen_gate = nullptr; // the gate word of the last screened search (diagnostics)
     uint32_t last_screen_wgs = 0;               // workgroups of the widest screen launch of the last screened search (diagnostics)
+    uint32_t last_sample_rows = 0;              // rows of the last search's sample pass, 0 = it took none (diagnostics: "screen_sample")
     std::map<std::string, std::vector<ProfSpan>> prof;
     std::vector<hipEvent_t> event_pool;
     bool use_graphs = false;          // oi_set_graph_replay
@@ -412,6 +413,14 @@ int oi_launch_cosine_screen_i8_chunk(oi_ctx *ctx, const uint8_t *i8_copy, uint64
                                      uint32_t dim, const int8_t *qi8, const float *qf, uint32_t n_queries, uint32_t doc_id_base,
                                      PoolView &pool, uint32_t wgs = 0);
 // (wgs: the launch's width in workgroups, 0 = the screens' 7/8 of the CUs)
+// the sample pass (search.hip, Plan::sample_rows): the dense lower-bound score keys of rows [0, m_rows) against every query,
+// keys[padded queries][oi_screen_i8_sample_stride(m_rows)], 0 where a row takes no part (long_bitmap: may be null); then
+// (select.hip) the first speculative threshold from the r-th largest of a query's keys -- the words sel_spec_words writes
+uint32_t oi_screen_i8_sample_stride(uint32_t m_rows);
+int oi_launch_screen_i8_sample(oi_ctx *ctx, const uint8_t *i8_copy, uint64_t n_rows_total, uint32_t m_rows, uint32_t dim, const int8_t *qi8,
+                               const float *qf, uint32_t n_queries, const uint32_t *long_bitmap, uint32_t *keys);
+int oi_launch_sample_rank(oi_ctx *ctx, const uint32_t *keys, uint32_t stride, uint32_t m, uint32_t n_queries, uint32_t r, const float *eps2,
+                          const uint32_t *tau_keys, uint32_t *spec_tau, uint32_t *spec_max);
 // the bf16 rescreen: every key of pool's carry (an int8 survivor) becomes its bf16 screen key, in place
 int oi_launch_rescreen_bf16(oi_ctx *ctx, const uint16_t *copy_rows, uint64_t n_rows, uint32_t dim, uint32_t doc_id_base,
                             const uint16_t *q_bf16, uint32_t n_queries, const PoolView &pool);

@@ -16,6 +16,7 @@ struct Knobs {
     uint32_t bm25_first_div = env_int("OI_BM25_FIRST_DIV", 8, 1);
     bool screen_no_round = env_set("OI_SCREEN_NO_ROUND"), no_spec = env_set("OI_NO_SPEC"), no_overlap = env_set("OI_NO_OVERLAP");
     bool bm25_beside_last = env_set("OI_BM25_BESIDE_LAST"), screen_i8_narrow = env_set("OI_SCREEN_I8_NARROW");
+    bool no_sample_pass = env_set("OI_NO_SAMPLE_PASS");
     bool bm25_early = env_set("OI_BM25_EARLY"), small_gemv = env_set("OI_SMALL_BATCH_GEMV"), bm25_two_phase = env_set("OI_BM25_TWO_PHASE");
     // the first-generation cosine / select kernels have no screen in front of them
     bool exact_only = env_set("OI_COSINE_V1") || env_set("OI_SELECT_V1");
@@ -134,6 +135,10 @@ struct Plan {
     uint32_t pf_carry = 4096;
     bool spec = false; // speculative screen thresholds
     std::vector<Chunk> screen_chunks; // the screen routes' schedule
+    // the int8 route's sample pass: the first speculative threshold comes from the dense score keys of rows [0, sample_rows)
+    // (cosine_screen_i8.hip: i8s_sample_kernel, select.hip: sample_rank_kernel) and the first screen chunk, which starts at row 0
+    // all the same, runs under it; 0 = the first chunk is pooled without a threshold and its margin select makes the prediction
+    uint32_t sample_rows = 0;
     // the BM25 leg on the side stream; late_fork: forked in at the screen's last chunk -- beside it, or (tail_fork, the int8 route)
     // behind it, beside the cosine leg's tail
     bool overlap = false, late_fork = false, tail_fork = false;
@@ -219,6 +224,25 @@ Plan plan_search(const Search &s) {
     }
     // (the threshold-less first chunk is never stretched: it is the sample the thresholds come from)
     if (screened(p.cos)) p.screen_chunks = chunk_schedule(n, first, growth, pool_max, /*stretch_first=*/false);
+    // ---- the sample pass of the int8 route.  Where a prediction follows the threshold-less first chunk, that prediction is the
+    // chunk's only use: T1 = key(r-th largest lower-bound key of its rows) - m2, and the proven threshold of the same select, from
+    // rank k' >= 2 r of the same keys less the same m2, is never the larger one.  So the rows of that chunk are scored into a dense
+    // key array instead (no pool, no survivor path, no margin select), a small kernel takes the r-th largest, and the second chunk
+    // starts at row 0: it screens the sample rows again, under T1 (10M rows: 0.8 % more stream).  The later chunk ends stay, so
+    // every later launch is the same launch.  Only where the merged chunk still fits one launch's pool room; otherwise, and
+    // without speculation (off, backed off, filtered, graph replay, B <= 8), on the bf16 routes and with OI_NO_SAMPLE_PASS=1
+    // (ablation builds), the pooled first chunk as before.
+    if (p.cos == CosRoute::screen_i8 && p.spec && !K.no_sample_pass && p.screen_chunks.size() >= 2) {
+        const uint64_t m = p.screen_chunks[0].e;
+        // (the key array, [B rounded to 32][m rounded to 32] words, lies in the still empty pool buffer: cosine_screen)
+        const uint64_t key_words = (uint64_t)((B + 31u) & ~31u) * ((m + 31) & ~31ull);
+        if (2 * ((3ull * depth * m + n - 1) / n + 12) <= depth && p.screen_chunks[1].e <= pool_max && m <= (32u << 10) &&
+            key_words <= 2 * (uint64_t)B * p.pf_stride) {
+            p.sample_rows = (uint32_t)m;
+            p.screen_chunks.erase(p.screen_chunks.begin());
+            p.screen_chunks[0].r = 0;
+        }
+    }
     // ---- the two legs of a hybrid query are independent until fusion: the BM25 leg (latency-bound, 128 KB of LDS per workgroup)
     // is issued on a side stream and fills the issue slots the MFMA-bound cosine leg leaves, instead of running after it.
     // OI_NO_OVERLAP=1 serialises them (A/B runs).
@@ -503,6 +527,19 @@ int cosine_screen(const Search &s, const Plan &p, const Pools &P, uint32_t *w, c
     // Speculative thresholds (the plan's spec and schedule): the next chunk is screened against the larger of the proven
     // threshold and a prediction from the rows seen so far, checked at the end (a failed check opens the gate).
     bool spec_next = false, spec_any = false;
+    if (p.sample_rows) { // the plan's sample pass: the first prediction before any chunk is pooled (the proven thresholds are still 0)
+        // The dense key array lies at the head of the pool buffer (ctx->buf "pool_cos": 7.3 MB of it at 10M x 768, B = 64): the pool
+        // holds nothing yet -- no carried key, no segment -- and the first chunk, which writes it, starts behind the rank launch.
+        const uint32_t ks = oi_screen_i8_sample_stride(p.sample_rows);
+        OI_REQUIRE(sizeof(uint32_t) * (size_t)n_padded * ks <= sizeof(uint64_t) * (size_t)B * p.pf_stride && pk.p,
+                   "search: the sample pass's keys do not fit the candidate pool");
+        uint32_t *sample_keys = pk.as<uint32_t>();
+        OI_CHECK(oi_launch_screen_i8_sample(ctx, idx->screen_i8.as<uint8_t>(), n, p.sample_rows, dim, qi8, qf8, B,
+                                            idx->n_long ? idx->long_bitmap.as<uint32_t>() : nullptr, sample_keys));
+        const uint64_t rank = (3ull * depth * p.sample_rows + n - 1) / n + 12;
+        OI_CHECK(oi_launch_sample_rank(ctx, sample_keys, ks, p.sample_rows, B, (uint32_t)rank, m8.eps2, pf_tau, spec_tau, spec_max));
+        spec_next = spec_any = true;
+    }
     for (size_t i = 0; i < p.screen_chunks.size(); ++i) {
         const uint64_t r = p.screen_chunks[i].r, e = p.screen_chunks[i].e;
         const bool last = i + 1 == p.screen_chunks.size();
@@ -612,6 +649,7 @@ int search_lists_device(oi_index *idx, const float *d_qv, const uint32_t *d_qt, 
     oi_ctx *ctx = idx->ctx;
     const Search s{idx, ctx, d_qv, d_qt, d_qo, B, depth, cos_s, cos_d, cos_c, bm_s, bm_d, bm_c, d_filt, d_attrs};
     const Plan p = plan_search(s);
+    ctx->last_sample_rows = p.sample_rows;
     Pools P;
     // the bf16 screen's state words (cosine_screen) ride in the same memset; the depth-sized segments of P.bm belong to the
     // workgroup-per-block kernel: no room is set aside for them otherwise

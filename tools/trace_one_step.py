@@ -7,8 +7,11 @@ Prints every launch of the middle step in start order: start (us from the step's
 A step begins at the query staging launch (pf_stage_queries_kernel; on the int8 route of later builds i8s_stage_both_kernel).
 Each select_flat_kernel launch is named by what precedes it on its queue: the margin select of screen chunk i, the bf16 margin
 select after the rescreen, the final sorted select after the rescoring, the gated selects behind the gated exact kernel, the BM25
-leg's select.  --json also writes the table, the per-role medians over all steps but the first three and the last, and the end of
-each leg before the fusion (which leg ends last)."""
+leg's select.  The int8 route's sample pass (i8s_sample_kernel) and its rank launch (sample_rank_kernel) get roles of their own, and
+the HEAD of a step is measured: from the end of the staging launch to the start of the first screen launch that runs under a
+threshold -- screen chunk 2 behind a pooled first chunk, screen chunk 1 behind a sample pass.  --json also writes the table, the
+per-role medians over all steps but the first three and the last, the median head, and the end of each leg before the fusion
+(which leg ends last)."""
 import csv
 import glob
 import json
@@ -46,6 +49,10 @@ def label(step):
         if "screen" in r["name"] and ("i8_screen" in r["name"] or "screen_copy" in r["name"] or "screen_filter" in r["name"]):
             chunk += 1
             role = "screen chunk %d" % chunk
+        elif r["name"] == "i8s_sample_kernel":
+            role = "sample pass"
+        elif r["name"] == "sample_rank_kernel":
+            role = "sample rank"
         elif r["name"] == "select_flat_kernel":
             prev = last.get(r["queue"], "")
             if "screen" in prev and "rescreen" not in prev:
@@ -71,6 +78,14 @@ def table(step):
              "kernel": r["name"], "role": role, "grid": r["grid"]} for r, role in zip(step, label(step))]
 
 
+def head(step):
+    """us from the end of the staging launch to the start of the first thresholded screen launch (None: fewer screen launches)"""
+    roles = label(step)
+    want = "screen chunk 1" if "sample pass" in roles else "screen chunk 2"
+    at = [r for r, role in zip(step, roles) if role == want]
+    return round((at[0]["start"] - step[0]["end"]) / 1e3, 1) if at else None
+
+
 def legs(step):
     """end of the cosine leg (the last launch before rrf on rrf's queue) and of the BM25 leg (the last launch on another queue)"""
     t0 = step[0]["start"]
@@ -92,6 +107,7 @@ def main():
     for e in table(mid):
         print("%9.1f +%8.1f q=%s %s%s grid=%s" % (e["start_us"], e["dur_us"], e["queue"], e["kernel"], "  [%s]" % e["role"] if e["role"] else "", e["grid"]))
     print(legs(mid))
+    print("head: %s us from the end of staging to the first thresholded screen launch" % head(mid))
     if "--json" in sys.argv:
         steady = steps[3:-1] if len(steps) > 6 else steps
         per = {}
@@ -103,7 +119,9 @@ def main():
                 per.setdefault(key if n == 1 else "%s #%d" % (key, n), []).append(e["dur_us"])
         lg = [legs(s) for s in steady]
         lg = [x for x in lg if x and x["bm25_leg_end_us"] is not None]
+        heads = [h for h in (head(s) for s in steady) if h is not None]
         out = {"steps_in_trace": len(steps), "steady_steps": len(steady), "one_step": table(mid), "one_step_legs": legs(mid),
+               "median_head_us": round(statistics.median(heads), 1) if heads else None,
                "median_dur_us": {k: round(statistics.median(v), 1) for k, v in per.items()},
                "launches_per_step": {k: round(len(v) / len(steady), 2) for k, v in per.items()},
                "median_legs": {k: round(statistics.median(x[k] for x in lg), 1) for k in lg[0]} if lg else None,
