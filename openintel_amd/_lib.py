@@ -219,6 +219,13 @@ SIGNATURES = {
     "oi_profile_read": (_I, [_P, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_U64)]),
 }
 
+# exports that are NOT part of the C ABI (no declaration in the header): the switch between the int8 route's two second tiers
+# (A/B runs, tests) and the tests' view of an index's residual plane
+INTERNAL = {
+    "oi_internal_set_rescreen_tier": (_I, [_P, _I]),
+    "oi_internal_residual_plane": (_I, [_P, _I, _P, _P, _P, C.POINTER(_U64)]),
+}
+
 _lib = None
 
 
@@ -241,7 +248,7 @@ def load() -> C.CDLL:
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(INTERNAL.items()):
         fn = getattr(lib, name)  # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args

@@ -59,6 +59,18 @@ class HipContext:
         the end, the exact pipeline behind a failed check.  The lists do not depend on it."""
         _lib.check(self.lib.oi_set_screen_speculation(self.handle, 1 if enable else 0))
 
+    def set_rescreen_tier(self, residual: bool) -> None:
+        """The int8 route's second tier (internal switch, A/B runs and tests): the residual plane's rescreen where the index holds
+        the plane (default), or the bf16 rescreen whatever it holds.  The lists do not depend on it."""
+        _lib.check(self.lib.oi_internal_set_rescreen_tier(self.handle, 1 if residual else 0))
+
+    def rescreen_state(self):
+        """(tier of the last search: 0 bf16, 1 residual, -1 not the int8 route; keys its second margin select kept, summed over
+        the queries; the most for one query)."""
+        tier, _ = self.profile_read("rescreen_tier")
+        total, most = self.profile_read("rescreen_survivors")
+        return int(tier), int(total), int(most)
+
     def speculation_state(self):
         """(failed checks seen, searches that speculated) since the ctx was created."""
         f, n = self.profile_read("spec_state")

@@ -164,6 +164,20 @@ extern "C" int oi_profile_read(oi_ctx *ctx, const char *kernel_tag, double *tota
         if (launches_out) *launches_out = 0;
         return OI_OK;
     }
+    if (strcmp(kernel_tag, "rescreen_tier") == 0) { // diagnostics: the second tier of the last search's int8 route: 0 the bf16 rescreen,
+        if (total_ms_out) *total_ms_out = (double)ctx->last_rescreen_tier; // 1 the residual plane's, -1 the search took another route
+        if (launches_out) *launches_out = 0;
+        return OI_OK;
+    }
+    if (strcmp(kernel_tag, "rescreen_survivors") == 0) { // diagnostics: keys the last int8-route search's second margin select kept,
+        std::vector<uint32_t> c(ctx->last_rescreen_cnt ? ctx->last_rescreen_b : 0); // summed over the queries; the largest of one query
+        if (!c.empty()) OI_HIP_CHECK(hipMemcpy(c.data(), ctx->last_rescreen_cnt, sizeof(uint32_t) * c.size(), hipMemcpyDeviceToHost));
+        uint64_t sum = 0, mx = 0;
+        for (uint32_t v : c) { sum += v; mx = std::max<uint64_t>(mx, v); }
+        if (total_ms_out) *total_ms_out = (double)sum;
+        if (launches_out) *launches_out = mx;
+        return OI_OK;
+    }
     if (strcmp(kernel_tag, "volume_state") == 0 || strcmp(kernel_tag, "summary_state") == 0 || strcmp(kernel_tag, "groups_state") == 0 ||
         strcmp(kernel_tag, "share_state") == 0) {
         // diagnostics of the last oi_similar_volume / oi_similar_summary / oi_similar_groups / oi_similar_share: undecided pairs its stream sent to the band (may exceed
@@ -356,6 +370,7 @@ extern "C" int oi_create_like(oi_ctx *like, oi_ctx **out) {
     (*out)->cosine_mode = like->cosine_mode;
     (*out)->overlap_legs = like->overlap_legs;
     (*out)->speculate = like->speculate;
+    (*out)->rescreen_residual = like->rescreen_residual;
     (*out)->use_graphs = like->use_graphs;
     return OI_OK;
 }
@@ -429,6 +444,18 @@ extern "C" int oi_set_screen_speculation(oi_ctx *ctx, int enable) {
     std::lock_guard<std::mutex> g(ctx->mu);
     ctx->speculate = enable != 0;
     ctx->spec_skip = ctx->spec_backoff = 0;
+    return OI_OK;
+}
+
+// Not part of the C ABI (no declaration in include/openintel_hip.h): the second tier of the int8 route.  tier 1 (default): the
+// residual plane's rescreen where the index holds the plane; tier 0: the bf16 rescreen whatever the index holds -- A/B runs and the
+// tests take both tails over one index in one process.  The lists do not depend on it.
+extern "C" int oi_internal_set_rescreen_tier(oi_ctx *ctx, int tier) {
+    if (!ctx) { oi_set_error("null ctx"); return OI_ERR_INVALID_ARG; }
+    OI_REQUIRE(tier == 0 || tier == 1, "oi_internal_set_rescreen_tier: unknown tier %d", tier);
+    std::lock_guard<std::mutex> g(ctx->mu);
+    g_oi_ws_epoch.fetch_add(1); // (captured query calls hold the other tail's launches)
+    ctx->rescreen_residual = tier == 1;
     return OI_OK;
 }
 
@@ -858,6 +885,7 @@ extern "C" int oi_index_view(oi_index *src, oi_ctx *ctx, oi_index **out) {
     v->avgdl = src->avgdl; v->max_query_terms = src->max_query_terms; v->bm25_mode = src->bm25_mode;
     auto alias = [](DevBuf &dst, const DevBuf &from) { dst.p = from.p; dst.cap = from.cap; dst.borrowed = from.p != nullptr; };
     alias(v->max_row_norm, src->max_row_norm); alias(v->screen_copy, src->screen_copy); alias(v->screen_i8, src->screen_i8);
+    alias(v->screen_i8r, src->screen_i8r);
     alias(v->uniq_keys, src->uniq_keys); alias(v->tf, src->tf); alias(v->doc_len, src->doc_len); alias(v->df_local, src->df_local);
     alias(v->postings, src->postings); alias(v->cell_start, src->cell_start); alias(v->idf, src->idf);
     alias(v->impact_floor, src->impact_floor);
@@ -885,7 +913,7 @@ static void index_release(oi_index *idx) {
         idx->uniq_keys.release(); idx->tf.release(); idx->doc_len.release(); idx->df_local.release();
         idx->postings.release(); idx->cell_start.release(); idx->idf.release();
         idx->fwd_terms.release(); idx->fwd_offsets.release(); idx->max_row_norm.release(); idx->screen_copy.release();
-        idx->screen_i8.release();
+        idx->screen_i8.release(); idx->screen_i8r.release();
     }
     delete idx;
     if (src) index_release(src);
@@ -919,19 +947,21 @@ static int apply_screen_copy_policy(oi_index *idx) {
     if (idx->is_view) return OI_OK;
     const int policy = idx->screen_copy_policy < 0 ? default_screen_copy_policy() : idx->screen_copy_policy;
     if (policy == OI_SCREEN_COPY_NEVER || !oi_index_screenable(idx)) {
-        if (idx->screen_copy.p || idx->screen_i8.p) {
+        if (idx->screen_copy.p || idx->screen_i8.p || idx->screen_i8r.p) {
             OI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
             idx->screen_copy.release();
             idx->screen_i8.release();
+            idx->screen_i8r.release();
         }
         return OI_OK;
     }
     if (idx->screen_copy.p) return OI_OK; // (set_embeddings releases the copies of the previous rows)
     // The bf16 copy and, in front of it, the int8 copy of the first screening tier (cosine_screen_i8.hip): AUTO makes both when
-    // both fit the budget, the bf16 one alone when only it does
+    // both fit the budget, the bf16 one alone when only it does; and behind the int8 copy its residual plane
+    // (screen_i8_residual.hip, the int8 copy's size once more) when all three fit -- the first to be left out
     const size_t bytes = sizeof(uint16_t) * (size_t)idx->n_docs * idx->dim + 64;
     const size_t bytes_i8 = oi_screen_i8_bytes(idx->n_docs, idx->dim);
-    bool with_i8 = true;
+    bool with_i8 = true, with_i8r = true;
     if (policy == OI_SCREEN_COPY_AUTO) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return OI_OK; // no figure, no copy
@@ -942,6 +972,7 @@ static int apply_screen_copy_policy(oi_index *idx) {
         }();
         if ((double)bytes > frac * (double)free_b) return OI_OK;
         with_i8 = (double)(bytes + bytes_i8) <= frac * (double)free_b;
+        with_i8r = (double)(bytes + 2 * bytes_i8) <= frac * (double)free_b;
     }
     OI_CHECK(idx->screen_copy.ensure(bytes));
     OI_CHECK(oi_launch_make_screen_copy(ctx, idx->rows, idx->n_docs, idx->dim, idx->screen_copy.as<uint16_t>()));
@@ -949,8 +980,38 @@ static int apply_screen_copy_policy(oi_index *idx) {
         OI_CHECK(idx->screen_i8.ensure(bytes_i8));
         OI_CHECK(oi_launch_make_screen_i8(ctx, idx->rows, idx->n_docs, idx->dim, idx->n_long ? idx->long_bitmap.as<uint32_t>() : nullptr,
                                           idx->screen_i8.as<uint8_t>()));
+        if (with_i8r) {
+            OI_CHECK(idx->screen_i8r.ensure(bytes_i8));
+            OI_CHECK(oi_launch_make_screen_i8_residual(ctx, idx->rows, idx->n_docs, idx->dim, idx->n_long ? idx->long_bitmap.as<uint32_t>() : nullptr,
+                                                       idx->screen_i8.as<uint8_t>(), idx->screen_i8r.as<uint8_t>()));
+        }
     }
     OI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return OI_OK;
+}
+
+// Not part of the C ABI: the residual plane of an index, for the tests.  drop != 0 frees it (the index is then what the AUTO budget
+// makes when only two copies fit); otherwise the n x dim bytes, the n {t_r, e2_r} pairs and e2_max are copied to the host
+// pointers that are not null.  *bytes_out: the plane's allocation, 0 = the index holds none.
+extern "C" int oi_internal_residual_plane(oi_index *idx, int drop, uint8_t *rows_out, float *meta_out, float *e2max_out, uint64_t *bytes_out) {
+    if (!idx) { oi_set_error("null index"); return OI_ERR_INVALID_ARG; }
+    oi_ctx *ctx = idx->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    OI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (drop) {
+        OI_REQUIRE(!idx->is_view, "index view: read-only");
+        OI_REQUIRE(idx->refs.load() == 1, "residual plane: the index has live views that alias it");
+        g_oi_ws_epoch.fetch_add(1);
+        idx->screen_i8r.release();
+    }
+    if (bytes_out) *bytes_out = idx->screen_i8r.p ? (uint64_t)idx->screen_i8r.cap : 0;
+    if (!idx->screen_i8r.p || drop) return OI_OK;
+    const uint8_t *p = idx->screen_i8r.as<uint8_t>();
+    const size_t n = idx->n_docs, mo = oi_screen_i8_meta_offset(n, idx->dim);
+    if (rows_out && n) OI_HIP_CHECK(hipMemcpy(rows_out, p, n * idx->dim, hipMemcpyDeviceToHost));
+    if (meta_out && n) OI_HIP_CHECK(hipMemcpy(meta_out, p + mo, 8 * n, hipMemcpyDeviceToHost));
+    if (e2max_out) OI_HIP_CHECK(hipMemcpy(e2max_out, p + mo + 8 * (n + 64), 4, hipMemcpyDeviceToHost)); // (behind the 64 padding rows: I8S_PAD_ROWS)
     return OI_OK;
 }
 
@@ -976,7 +1037,8 @@ extern "C" int oi_index_bytes(oi_index *idx, uint64_t *rows_owned, uint64_t *scr
                       (idx->rows_bf16_owned ? sizeof(uint16_t) * (uint64_t)idx->n_docs * idx->dim : 0);
     if (screen_copy)
         *screen_copy = (idx->screen_copy.p && !idx->screen_copy.borrowed ? (uint64_t)idx->screen_copy.cap : 0) +
-                       (idx->screen_i8.p && !idx->screen_i8.borrowed ? (uint64_t)idx->screen_i8.cap : 0);
+                       (idx->screen_i8.p && !idx->screen_i8.borrowed ? (uint64_t)idx->screen_i8.cap : 0) +
+                       (idx->screen_i8r.p && !idx->screen_i8r.borrowed ? (uint64_t)idx->screen_i8r.cap : 0);
     if (bm25) {
         uint64_t b = 0;
         for (const DevBuf *d : {&idx->uniq_keys, &idx->tf, &idx->doc_len, &idx->df_local, &idx->postings, &idx->cell_start, &idx->idf,
@@ -1001,6 +1063,7 @@ extern "C" int oi_index_set_embeddings(oi_index *idx, float *rows, int location,
     idx->rows_bf16 = nullptr; idx->rows_bf16_owned = false;
     idx->screen_copy.release(); // a copy of the previous rows
     idx->screen_i8.release();
+    idx->screen_i8r.release();
     const size_t bytes = (size_t)idx->n_docs * idx->dim * sizeof(float);
     if (location == OI_DEVICE) {
         OI_REQUIRE(((uintptr_t)rows & 15u) == 0, "index: embedding matrix must be 16-byte aligned");
@@ -1067,6 +1130,7 @@ extern "C" int oi_index_set_embeddings_bf16(oi_index *idx, const uint16_t *rows,
     idx->rows = nullptr; idx->rows_owned = false;
     idx->screen_copy.release(); // (a copy of f32 rows that are gone)
     idx->screen_i8.release();
+    idx->screen_i8r.release();
     if (idx->rows_bf16_owned && idx->rows_bf16) (void)hipFree(idx->rows_bf16);
     idx->rows_bf16 = nullptr; idx->rows_bf16_owned = false;
     const size_t bytes = (size_t)idx->n_docs * idx->dim * sizeof(uint16_t);

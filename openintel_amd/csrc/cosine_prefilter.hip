@@ -619,11 +619,11 @@ int oi_launch_cosine_screen_chunk(oi_ctx *ctx, const float *rows, uint64_t row_b
 int oi_launch_rescore(oi_ctx *ctx, const float *rows, uint64_t n_rows, uint32_t dim, uint32_t doc_id_base,
                       const float *d_queries, uint32_t n_queries, const PoolView &in, const PoolView &out,
                       const uint32_t *extra_docs, uint32_t n_extra, const uint32_t *spec_max, const uint32_t *tau_final,
-                      uint32_t *gate, uint32_t *fail_host) {
+                      uint32_t *gate, uint32_t *fail_host, uint32_t wgs_per_query) {
     if (n_queries == 0) return OI_OK;
     OI_REQUIRE(out.carry_cap >= in.carry_cap + n_extra, "rescore: output pool too small");
     ProfScope ps(ctx, "rescore");
-    hipLaunchKernelGGL(pf_rescore_kernel, dim3(64, n_queries), dim3(256), 0, ctx->stream, rows, dim, doc_id_base, n_rows,
+    hipLaunchKernelGGL(pf_rescore_kernel, dim3(wgs_per_query ? wgs_per_query : 64u, n_queries), dim3(256), 0, ctx->stream, rows, dim, doc_id_base, n_rows,
                        d_queries, in.keys, in.carry_cnt, in.stride, in.carry_cap, out.keys, out.carry_cnt, out.stride, extra_docs,
                        n_extra, spec_max, tau_final, gate, fail_host, out.filt, out.attrs);
     OI_HIP_CHECK(hipGetLastError());

@@ -46,6 +46,7 @@
 #include "oi_internal.h"
 #include "oi_screen_stage.h"
 #include "oi_lds_dma.h"
+#include "oi_screen_i8.h"
 
 typedef int i8s_i32x4 __attribute__((ext_vector_type(4)));
 typedef int i8s_i32x16 __attribute__((ext_vector_type(16)));
@@ -58,7 +59,6 @@ struct i8s_ivec {
 #define I8S_TILE_ROWS 32
 #define I8S_SLOT_BYTES (I8S_TILE_ROWS * 128) // 32 rows x 128 i8 of K
 #define I8S_META_BYTES 256                   // 32 rows x {scale, e_r}
-#define I8S_PAD_ROWS 64
 
 // ------------------------------------------------------------------ the copy
 size_t oi_screen_i8_meta_offset(uint64_t n, uint32_t dim) { return ((size_t)n * dim + 255) & ~(size_t)255; }
@@ -143,6 +143,7 @@ int oi_launch_make_screen_i8(oi_ctx *ctx, const float *rows, uint64_t n, uint32_
 // (one query row: all 64 lanes of the wave call)
 __device__ __forceinline__ void i8s_stage_query_row(const float *__restrict__ q, uint32_t row, uint32_t n_queries, uint32_t n_padded, uint32_t dim,
                                                     const uint32_t *__restrict__ max_norm_bits, const uint32_t *__restrict__ emax_bits,
+                                                    const uint32_t *__restrict__ e2max_bits, float *__restrict__ eps2r,
                                                     int8_t *__restrict__ qi8, float *__restrict__ qf, uint32_t *gate) {
     const uint32_t lane = threadIdx.x & 63;
     const bool real = row < n_queries;
@@ -186,15 +187,25 @@ __device__ __forceinline__ void i8s_stage_query_row(const float *__restrict__ q,
         qf[n_padded + row] = ok ? qn : 0.f;
         qf[2 * n_padded + row] = ok ? cq : 0.f;
         qf[3 * n_padded + row] = ok || !real ? m2 : __builtin_inff();
+        // the residual plane's uniform select margin 2 eps2'_q (screen_i8_residual.hip): e2_max in e_max's place and
+        // 2^-21 ((X + e_max) |q^| + m_max) for the recovery of s~ from the key and the roundings of the second product and the sum.
+        // It goes where the bf16 screen's 2 eps would stand (eps2r: [n_queries], the final margin select's array): on that tail
+        // the bf16 margin has no reader, and this body runs after the bf16 one
+        if (e2max_bits && real) {
+            const float rec = 4.76837158203125e-07f * ((X + em) * qn + (em * qn + cq));
+            const float m2r = 2.002f * (__uint_as_float(*e2max_bits) * qn + cq + rec);
+            eps2r[row] = ok ? m2r : __builtin_inff();
+        }
         if (real && !ok) *gate = 1u;
     }
 }
 __global__ __launch_bounds__(256) void i8s_stage_kernel(const float *__restrict__ q, uint32_t n_queries, uint32_t n_padded, uint32_t dim,
                                                         const uint32_t *__restrict__ max_norm_bits, const uint32_t *__restrict__ emax_bits,
+                                                        const uint32_t *__restrict__ e2max_bits, float *__restrict__ eps2r,
                                                         int8_t *__restrict__ qi8, float *__restrict__ qf, uint32_t *gate) {
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
     for (uint32_t row = wave; row < n_padded; row += n_waves) {
-        i8s_stage_query_row(q, row, n_queries, n_padded, dim, max_norm_bits, emax_bits, qi8, qf, gate);
+        i8s_stage_query_row(q, row, n_queries, n_padded, dim, max_norm_bits, emax_bits, e2max_bits, eps2r, qi8, qf, gate);
     }
 }
 
@@ -202,27 +213,31 @@ __global__ __launch_bounds__(256) void i8s_stage_kernel(const float *__restrict_
 // (oi_screen_stage.h: bf16 copy, eps2, gate) -- the words pf_stage_queries_kernel writes, the row read a second time from cache.
 __global__ __launch_bounds__(256) void i8s_stage_both_kernel(const float *__restrict__ q, uint32_t n_queries, uint32_t n_padded, uint32_t dim,
                                                              const uint32_t *__restrict__ max_norm_bits, const uint32_t *__restrict__ emax_bits,
+                                                             const uint32_t *__restrict__ e2max_bits, float *__restrict__ eps2r,
                                                              int8_t *__restrict__ qi8, float *__restrict__ qf, uint16_t *__restrict__ q_bf16,
                                                              float *__restrict__ eps2, uint32_t *gate) {
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
     for (uint32_t row = wave; row < n_padded; row += n_waves) {
-        i8s_stage_query_row(q, row, n_queries, n_padded, dim, max_norm_bits, emax_bits, qi8, qf, gate);
         pf_stage_query_row(q, row, n_queries, dim, max_norm_bits, q_bf16, eps2, gate);
+        i8s_stage_query_row(q, row, n_queries, n_padded, dim, max_norm_bits, emax_bits, e2max_bits, eps2r, qi8, qf, gate);
     }
 }
 
 int oi_launch_screen_stage_i8(oi_ctx *ctx, const float *d_queries, uint32_t n_queries, uint32_t dim, const uint32_t *max_norm_bits,
                               const uint8_t *i8_copy, uint64_t n_rows, int8_t *qi8, float *qf, uint32_t *gate, uint16_t *q_bf16,
-                              float *eps2) {
+                              float *eps2, const uint8_t *residual, float *eps2_residual) {
     const uint32_t n_padded = (n_queries + 31u) & ~31u;
     if (n_padded == 0) return OI_OK;
+    // residual: the index's residual plane (screen_i8_residual.hip, the int8 copy's layout) -- its margin to eps2_residual[q]
+    const uint32_t *e2max = !(residual && eps2_residual) ? nullptr :
+        reinterpret_cast<const uint32_t *>(residual + oi_screen_i8_meta_offset(n_rows, dim)) + 2 * (n_rows + I8S_PAD_ROWS);
     const uint32_t *emax = reinterpret_cast<const uint32_t *>(i8_copy + oi_screen_i8_meta_offset(n_rows, dim)) + 2 * (n_rows + I8S_PAD_ROWS);
     if (q_bf16) // the bf16 screen's block as well (oi_launch_screen_stage's outputs)
         hipLaunchKernelGGL(i8s_stage_both_kernel, dim3((n_padded + 3) / 4), dim3(256), 0, ctx->stream, d_queries, n_queries, n_padded, dim,
-                           max_norm_bits, emax, qi8, qf, q_bf16, eps2, gate);
+                           max_norm_bits, emax, e2max, eps2_residual, qi8, qf, q_bf16, eps2, gate);
     else
         hipLaunchKernelGGL(i8s_stage_kernel, dim3((n_padded + 3) / 4), dim3(256), 0, ctx->stream, d_queries, n_queries, n_padded, dim,
-                           max_norm_bits, emax, qi8, qf, gate);
+                           max_norm_bits, emax, e2max, eps2_residual, qi8, qf, gate);
     OI_HIP_CHECK(hipGetLastError());
     return OI_OK;
 }
@@ -255,10 +270,7 @@ __device__ __forceinline__ void i8s_issue_meta(const oi_u32x4 &srd, uint32_t vof
 #endif
 }
 
-// The lower bound a pair is keyed by, l = s~ - (e_r |q^| + c_q) with s~ = f32(S) (scale a / 128): ONE body for the screen's
-// survivor path and the sample pass, so both round alike (qa = a / 128).
-__device__ __forceinline__ float i8s_screen_score(int S, float scale, float qa) { return (float)S * (scale * qa); }
-__device__ __forceinline__ float i8s_lower_bound(float sc, float er, float qn, float cq) { return sc - fmaf(er, qn, cq); }
+// (the lower bound a pair is keyed by, i8s_screen_score and i8s_lower_bound: oi_screen_i8.h -- the residual rescreen recovers s~ from it)
 
 template <int D, int NQT, int NBUF, bool FILT>
 __global__ __launch_bounds__(256, 1) void cosine_i8_screen(

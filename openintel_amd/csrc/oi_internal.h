@@ -139,6 +139,12 @@ struct oi_ctx {
     const uint32_t *last_screen_gate = nullptr; // the gate word of the last screened search (diagnostics)
     uint32_t last_screen_wgs = 0;               // workgroups of the widest screen launch of the last screened search (diagnostics)
     uint32_t last_sample_rows = 0;              // rows of the last search's sample pass, 0 = it took none (diagnostics: "screen_sample")
+    // the int8 route's second tier: the residual plane's rescreen where the index holds the plane (default), or the bf16 rescreen
+    // whatever it holds (oi_internal_set_rescreen_tier: A/B runs and tests take both tails over one index)
+    bool rescreen_residual = true;
+    int last_rescreen_tier = -1;                // the last search's: 0 bf16, 1 residual, -1 no int8 route (diagnostics: "rescreen_tier")
+    const uint32_t *last_rescreen_cnt = nullptr; // its survivor counts behind the second margin select, [last_rescreen_b] (diagnostics: "rescreen_survivors")
+    uint32_t last_rescreen_b = 0;
     std::map<std::string, std::vector<ProfSpan>> prof;
     std::vector<hipEvent_t> event_pool;
     bool use_graphs = false;          // oi_set_graph_replay
@@ -193,6 +199,10 @@ struct oi_index {
     // per-row absmax scale) then, 256-B aligned, f32 {scale, e_r} per row (+ 64 rows of zero padding) and bits of max e_r over
     // the rows that are not long
     DevBuf screen_i8;
+    // the residual plane of the int8 copy (screen_i8_residual.hip): what the first plane's rounding left over, in the same layout
+    // ({t_r, e2_r} per row, the bits of e2_max).  Made, dropped and aliased with the int8 copy; the first of the three copies the
+    // AUTO budget leaves out -- an index without it takes the bf16 rescreen
+    DevBuf screen_i8r;
     // the doc attributes of filtered searches (oi_index_set_doc_attrs): {group, stamp} per local row, n_docs x 8 B; allocated
     // by the first call, overwritten in place by later ones (never reallocated: views alias it)
     DevBuf doc_attrs;
@@ -407,8 +417,10 @@ int oi_launch_make_screen_i8(oi_ctx *ctx, const float *rows, uint64_t n, uint32_
 // per search: i8 hi / lo query blocks (qi8: [2][n_padded][dim]) and four floats per query in qf: qa, qn, cq, eps2 (the tier's margin)
 int oi_launch_screen_stage_i8(oi_ctx *ctx, const float *d_queries, uint32_t n_queries, uint32_t dim, const uint32_t *max_norm_bits,
                               const uint8_t *i8_copy, uint64_t n_rows, int8_t *qi8, float *qf, uint32_t *gate,
-                              uint16_t *q_bf16 = nullptr, float *eps2 = nullptr);
-// (q_bf16 / eps2 set: the same launch also writes what oi_launch_screen_stage writes -- the int8 route stages once)
+                              uint16_t *q_bf16 = nullptr, float *eps2 = nullptr, const uint8_t *residual = nullptr,
+                              float *eps2_residual = nullptr);
+// (q_bf16 / eps2 set: the same launch also writes what oi_launch_screen_stage writes -- the int8 route stages once;
+// residual / eps2_residual set: eps2_residual[q] = 2 eps2'_q, the residual tier's select margin, written last -- it may be eps2)
 int oi_launch_cosine_screen_i8_chunk(oi_ctx *ctx, const uint8_t *i8_copy, uint64_t n_rows_total, uint64_t row_begin, uint64_t row_end,
                                      uint32_t dim, const int8_t *qi8, const float *qf, uint32_t n_queries, uint32_t doc_id_base,
                                      PoolView &pool, uint32_t wgs = 0);
@@ -424,6 +436,12 @@ int oi_launch_sample_rank(oi_ctx *ctx, const uint32_t *keys, uint32_t stride, ui
 // the bf16 rescreen: every key of pool's carry (an int8 survivor) becomes its bf16 screen key, in place
 int oi_launch_rescreen_bf16(oi_ctx *ctx, const uint16_t *copy_rows, uint64_t n_rows, uint32_t dim, uint32_t doc_id_base,
                             const uint16_t *q_bf16, uint32_t n_queries, const PoolView &pool);
+// screen_i8_residual.hip: the residual plane (out: oi_screen_i8_bytes(n, dim) bytes, i8_copy: the finished first plane) and its
+// rescreen -- every key of pool's carry (an int8 survivor's lower bound) becomes its two-plane score key, in place
+int oi_launch_make_screen_i8_residual(oi_ctx *ctx, const float *rows, uint64_t n, uint32_t dim, const uint32_t *long_bitmap,
+                                      const uint8_t *i8_copy, uint8_t *out);
+int oi_launch_rescreen_residual(oi_ctx *ctx, const uint8_t *residual, const uint8_t *i8_copy, uint64_t n_rows, uint32_t dim,
+                                uint32_t doc_id_base, const int8_t *qi8, const float *qf, uint32_t n_queries, const PoolView &pool);
 // cosine_screen_copy.hip
 int oi_launch_cosine_screen_copy_chunk(oi_ctx *ctx, const uint16_t *copy_rows, uint64_t row_begin, uint64_t row_end, uint32_t dim,
                                        const uint16_t *q_bf16, uint32_t n_queries, uint32_t doc_id_base, PoolView &pool);
@@ -442,7 +460,9 @@ int oi_launch_spec_compare(oi_ctx *ctx, uint32_t n_queries, const uint32_t *tau_
 int oi_launch_rescore(oi_ctx *ctx, const float *rows, uint64_t n_rows, uint32_t dim, uint32_t doc_id_base,
                       const float *d_queries, uint32_t n_queries, const PoolView &in, const PoolView &out,
                       const uint32_t *extra_docs = nullptr, uint32_t n_extra = 0, const uint32_t *spec_max = nullptr,
-                      const uint32_t *tau_final = nullptr, uint32_t *gate = nullptr, uint32_t *fail_host = nullptr);
+                      const uint32_t *tau_final = nullptr, uint32_t *gate = nullptr, uint32_t *fail_host = nullptr,
+                      uint32_t wgs_per_query = 0);
+// (wgs_per_query: the launch's workgroups per query, 16 survivors a trip each; 0 = 64, sized for about 2 200 survivors)
 #define OI_LONG_ROWS_MAX 1024u // rows the two-class margin may set aside (more: one class, the corpus maxima, as before)
 int oi_launch_row_norm_classes(oi_ctx *ctx, const float *rows, uint64_t n, uint32_t dim, float X0, float E0, uint32_t *cls,
                                uint32_t *bitmap, uint32_t *list, uint32_t cap);

@@ -145,6 +145,9 @@ struct Plan {
     // workgroups of an int8 screen launch: every CU when no other kernel runs beside the chunks, 0 = the screens' 7/8 of the
     // CUs (oi_cosine_screen_geometry).  The bf16 copy, f32-stream and threshold-family kernels are HBM-bound at 7/8 and keep it.
     uint32_t screen_wgs = 0;
+    // the int8 route's second tier: the residual plane's rescreen (screen_i8_residual.hip) where the index holds the plane and the
+    // ctx allows it (oi_internal_set_rescreen_tier), the bf16 rescreen otherwise
+    bool rescreen_residual = false;
 };
 bool screened(CosRoute c) { return c == CosRoute::screen_f32 || c == CosRoute::screen_copy || c == CosRoute::screen_i8; }
 
@@ -171,6 +174,7 @@ Plan plan_search(const Search &s) {
     else if (!want_copy) p.cos = s.filt ? CosRoute::exact : CosRoute::screen_f32; // (filtered: the f32-stream screen has no filter)
     else if (B > 8 && idx->screen_copy.p && idx->screen_i8.p) p.cos = CosRoute::screen_i8;
     else p.cos = CosRoute::screen_copy;
+    p.rescreen_residual = p.cos == CosRoute::screen_i8 && idx->screen_i8r.p != nullptr && ctx->rescreen_residual;
     p.bm25 = bm25_mode_of(idx);
     if (p.bm25 == BM25_SCAN && !(idx->fwd_terms.p && idx->total_tokens > 0)) p.bm25 = BM25_STREAM; // (no forward tokens to scan)
     // A filtered search: every BM25 mode runs the stream kernel (the four give bit-identical lists; only it has the filter)
@@ -518,7 +522,9 @@ int cosine_screen(const Search &s, const Plan &p, const Pools &P, uint32_t *w, c
         qi8 = reinterpret_cast<int8_t *>(qs.p);
         qf8 = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(qs.p) + qi8_bytes);
         OI_CHECK(oi_launch_screen_stage_i8(ctx, s.qv, B, dim, idx->max_row_norm.as<uint32_t>(), idx->screen_i8.as<uint8_t>(), n,
-                                           qi8, qf8, gate, stage_split ? nullptr : qb.as<uint16_t>(), stage_split ? nullptr : eps2));
+                                           qi8, qf8, gate, stage_split ? nullptr : qb.as<uint16_t>(), stage_split ? nullptr : eps2,
+                                           // (the residual tier's margin over the bf16 screen's, which has no reader on that tail)
+                                           p.rescreen_residual ? idx->screen_i8r.as<uint8_t>() : nullptr, p.rescreen_residual ? eps2 : nullptr));
         m8.eps2 = qf8 + 3 * (size_t)n_padded; m8.row_qn = qf8 + (size_t)n_padded; m8.row_cq = qf8 + 2 * (size_t)n_padded;
         m8.cand = cb.as<uint64_t>(); m8.cand_cap = OI_I8_CARRY;
         m8.row_meta = reinterpret_cast<const float *>(idx->screen_i8.as<uint8_t>() + oi_screen_i8_meta_offset(n, dim));
@@ -589,18 +595,29 @@ int cosine_screen(const Search &s, const Plan &p, const Pools &P, uint32_t *w, c
     if (spec_any) ++ctx->spec_searches;
     PoolView PR = PF; // what the rescoring reads: the bf16 screen's final survivors (<= 4096 per query)
     if (i8) {
-        // the int8 survivors' bf16 keys (in place), then the bf16 screen's final margin select over them; the int8 tier's
-        // proven thresholds stay (the speculation check and the gated exact pipeline read them)
-        OI_CHECK(oi_launch_rescreen_bf16(ctx, idx->screen_copy.as<uint16_t>(), n, dim, idx->doc_id_base, qb.as<uint16_t>(), B, PF));
+        // the int8 survivors' second-tier keys (in place) -- their two-plane scores from the residual plane, or their bf16 screen
+        // scores from the bf16 copy -- then the bf16 screen's final margin select over them, with that tier's uniform margin (mx.eps2:
+        // staging wrote the residual tier's there); the int8 tier's proven thresholds stay (the speculation check and the gated
+        // exact pipeline read them)
+        if (p.rescreen_residual) {
+            OI_CHECK(oi_launch_rescreen_residual(ctx, idx->screen_i8r.as<uint8_t>(), idx->screen_i8.as<uint8_t>(), n, dim, idx->doc_id_base,
+                                                 qi8, qf8, B, PF));
+        } else {
+            OI_CHECK(oi_launch_rescreen_bf16(ctx, idx->screen_copy.as<uint16_t>(), n, dim, idx->doc_id_base, qb.as<uint16_t>(), B, PF));
+        }
         PoolView PB = PF; PB.tau_keys = nullptr; PB.n_segs = 0;
         OI_CHECK(oi_launch_select(ctx, PB, B, depth, /*compact=*/true, nullptr, nullptr, nullptr, depth, &mx));
         PR.carry_cap = 4096;
+        ctx->last_rescreen_cnt = pf_cnt; ctx->last_rescreen_b = B;
     }
     // (the check of the speculative thresholds against the proven final ones rides in the rescoring launch; the gated exact
     // pipeline is enqueued after it)
     OI_CHECK(oi_launch_rescore(ctx, idx->rows, n, dim, idx->doc_id_base, s.qv, B, PR, RS,
                                idx->n_long ? idx->long_list.as<uint32_t>() : nullptr, idx->n_long,
-                               spec_any ? spec_max : nullptr, pf_tau, gate, ctx->spec_fail_host));
+                               spec_any ? spec_max : nullptr, pf_tau, gate, ctx->spec_fail_host,
+                               // behind the residual tier about k' + 7 % survivors per query (10M x 768, k' = 1000: 1 072, at most
+                               // 1 094): 72 workgroups take 1 152 in ONE trip, 64 send a few waves on a second (48 -> 40 us)
+                               i8 && p.rescreen_residual ? 72u : 0u));
     RS.n_segs = 0;
     OI_CHECK(oi_launch_select(ctx, RS, B, depth, false, s.cos_s, s.cos_d, s.cos_c, depth));
     ctx->run_gate = ctx->last_screen_gate = gate;
@@ -650,6 +667,8 @@ int search_lists_device(oi_index *idx, const float *d_qv, const uint32_t *d_qt, 
     const Search s{idx, ctx, d_qv, d_qt, d_qo, B, depth, cos_s, cos_d, cos_c, bm_s, bm_d, bm_c, d_filt, d_attrs};
     const Plan p = plan_search(s);
     ctx->last_sample_rows = p.sample_rows;
+    ctx->last_rescreen_tier = p.cos == CosRoute::screen_i8 ? (p.rescreen_residual ? 1 : 0) : -1;
+    ctx->last_rescreen_cnt = nullptr;
     Pools P;
     // the bf16 screen's state words (cosine_screen) ride in the same memset; the depth-sized segments of P.bm belong to the
     // workgroup-per-block kernel: no room is set aside for them otherwise

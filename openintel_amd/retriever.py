@@ -266,6 +266,20 @@ class HybridIndex(PostRetriever):
         _lib.check(self.lib.oi_index_bytes(self.handle, C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
 
+    def residual_plane(self, drop: bool = False):
+        """The residual plane of the int8 screening copy (internal, for the tests): None when the index holds none, else
+        (j: int8 [n_docs, dim], {t_r, e2_r}: float32 [n_docs, 2], e2_max, bytes allocated).  drop=True frees it -- the index is
+        then the one the AUTO budget makes when only two copies fit -- and returns None."""
+        nb = C.c_uint64()
+        _lib.check(self.lib.oi_internal_residual_plane(self.handle, 1 if drop else 0, None, None, None, C.byref(nb)))
+        if drop or nb.value == 0:
+            return None
+        j = np.empty((self.n_docs, self.dim), np.int8)
+        meta = np.empty((self.n_docs, 2), np.float32)
+        e2max = np.zeros(1, np.float32)
+        _lib.check(self.lib.oi_internal_residual_plane(self.handle, 0, _lib.ptr(j), _lib.ptr(meta), _lib.ptr(e2max), C.byref(nb)))
+        return j, meta, float(e2max[0]), int(nb.value)
+
     BM25_DEFAULT, BM25_TAAT, BM25_SCAN, BM25_WAVE, BM25_STREAM = 0, 1, 2, 3, 4
 
     def set_bm25_mode(self, mode: int) -> None:
