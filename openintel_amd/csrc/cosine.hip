@@ -248,7 +248,7 @@ uint32_t oi_cosine_query_padding(uint32_t n_queries) {
 
 int oi_launch_cosine_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end,
                            uint32_t dim, const float *d_queries, uint32_t n_queries,
-                           uint32_t n_queries_padded, uint32_t doc_id_base, PoolView &pool) {
+                           uint32_t n_queries_padded, uint32_t doc_id_base, PoolView &pool, const uint32_t *run_gate) {
     static const bool force_v1 = oi_ablation_env("OI_COSINE_V1") != nullptr; // A/B switch for benchmarking
     const bool ksplit = n_queries > 8 && !force_v1 && oi_cosine_ksplit_supported(dim);
     if (ksplit) oi_cosine_ksplit_geometry(ctx, row_end > row_begin ? row_end - row_begin : 0, &pool.n_segs, &pool.seg_cap);
@@ -263,7 +263,7 @@ int oi_launch_cosine_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, u
     OI_REQUIRE(dim % 4 == 0 && dim >= 4 && dim <= OI_MAX_DIM, "cosine: dim=%u must be a multiple of 4 in [4,%u]",
                dim, OI_MAX_DIM);
     const uint64_t n_rows = row_end - row_begin;
-    ProfScope ps(ctx, ctx->run_gate ? "cosine_gated" : "cosine");
+    ProfScope ps(ctx, run_gate ? "cosine_gated" : "cosine");
     if (n_queries <= 8) {
         dim3 g((uint32_t)gemv_blocks(ctx, n_rows)), b(256);
 #define OI_GEMV(NQ)                                                                                     \
@@ -271,12 +271,12 @@ int oi_launch_cosine_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, u
         hipLaunchKernelGGL((cosine_gemv_filter<NQ, true>), g, b, 0, ctx->stream, rows, row_begin, row_end, dim, \
                            d_queries, doc_id_base, pool.keys + pool.carry_cap, pool.seg_cnt,             \
                            pool.seg_cnt_stride, pool.tau_keys, pool.stride, pool.seg_cap, pool.overflow, \
-                           ctx->run_gate, pool.filt, pool.attrs);                                        \
+                           run_gate, pool.filt, pool.attrs);                                             \
     else                                                                                                \
         hipLaunchKernelGGL((cosine_gemv_filter<NQ, false>), g, b, 0, ctx->stream, rows, row_begin, row_end, dim, \
                            d_queries, doc_id_base, pool.keys + pool.carry_cap, pool.seg_cnt,             \
                            pool.seg_cnt_stride, pool.tau_keys, pool.stride, pool.seg_cap, pool.overflow, \
-                           ctx->run_gate, nullptr, nullptr)
+                           run_gate, nullptr, nullptr)
         // queries beyond n_queries are not readable: dispatch on the exact count
         switch (n_queries) {
             case 1: OI_GEMV(1); break;
@@ -306,7 +306,7 @@ int oi_launch_cosine_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, u
             OI_CHECK(oi_launch_cosine_split(ctx, rows, row_begin, row_end, dim, qptr, nq_here, doc_id_base, p));
         } else if (ksplit) {
             OI_CHECK(oi_launch_cosine_ksplit(ctx, rows, row_begin, row_end, dim, qptr, nq_here, left >= 64,
-                                             doc_id_base, p));
+                                             doc_id_base, p, run_gate));
         } else {
             auto kernel = left >= 64 ? (p.filt ? cosine_mfma_filter<2, true> : cosine_mfma_filter<2, false>)
                                      : (p.filt ? cosine_mfma_filter<1, true> : cosine_mfma_filter<1, false>);

@@ -145,20 +145,21 @@ __global__ __launch_bounds__(256, 1) void cosine_ksplit16_filter(
 
 template <int D, int NQT>
 static int launch_ksplit16(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end, const float *q,
-                           uint32_t nq, uint32_t doc_id_base, const PoolView &p) {
+                           uint32_t nq, uint32_t doc_id_base, const PoolView &p, const uint32_t *run_gate) {
     auto kernel = p.filt ? cosine_ksplit16_filter<D, NQT, true> : cosine_ksplit16_filter<D, NQT, false>;
-    return oi_ksplit_launch<D, NQT>(ctx, kernel, rows, row_begin, row_end, q, nq, doc_id_base, p, ctx->run_gate, p.filt, p.attrs);
+    return oi_ksplit_launch<D, NQT>(ctx, kernel, rows, row_begin, row_end, q, nq, doc_id_base, p, run_gate, p.filt, p.attrs);
 }
 
 bool oi_cosine_ksplit_supported(uint32_t dim) { return dim == 384 || dim == 768 || dim == 1024; }
 
 // One group of <= 64 queries (zero padded to 32 or 64 rows at `q`).
 int oi_launch_cosine_ksplit(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end, uint32_t dim,
-                            const float *q, uint32_t nq, bool two_tiles, uint32_t doc_id_base, const PoolView &p) {
-#define OI_KS(DD)                                                                                       \
-    case DD:                                                                                            \
-        return two_tiles ? launch_ksplit16<DD, 2>(ctx, rows, row_begin, row_end, q, nq, doc_id_base, p) \
-                         : launch_ksplit16<DD, 1>(ctx, rows, row_begin, row_end, q, nq, doc_id_base, p);
+                            const float *q, uint32_t nq, bool two_tiles, uint32_t doc_id_base, const PoolView &p,
+                            const uint32_t *run_gate) {
+#define OI_KS(DD)                                                                                                 \
+    case DD:                                                                                                      \
+        return two_tiles ? launch_ksplit16<DD, 2>(ctx, rows, row_begin, row_end, q, nq, doc_id_base, p, run_gate) \
+                         : launch_ksplit16<DD, 1>(ctx, rows, row_begin, row_end, q, nq, doc_id_base, p, run_gate);
     switch (dim) {
         OI_KS(384)
         OI_KS(768)

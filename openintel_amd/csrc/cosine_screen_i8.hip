@@ -199,15 +199,6 @@ __device__ __forceinline__ void i8s_stage_query_row(const float *__restrict__ q,
         if (real && !ok) *gate = 1u;
     }
 }
-__global__ __launch_bounds__(256) void i8s_stage_kernel(const float *__restrict__ q, uint32_t n_queries, uint32_t n_padded, uint32_t dim,
-                                                        const uint32_t *__restrict__ max_norm_bits, const uint32_t *__restrict__ emax_bits,
-                                                        const uint32_t *__restrict__ e2max_bits, float *__restrict__ eps2r,
-                                                        int8_t *__restrict__ qi8, float *__restrict__ qf, uint32_t *gate) {
-    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    for (uint32_t row = wave; row < n_padded; row += n_waves) {
-        i8s_stage_query_row(q, row, n_queries, n_padded, dim, max_norm_bits, emax_bits, e2max_bits, eps2r, qi8, qf, gate);
-    }
-}
 
 // The int8 route stages both tiers' blocks in ONE launch: per query row the int8 body above, then the bf16 screen's
 // (oi_screen_stage.h: bf16 copy, eps2, gate) -- the words pf_stage_queries_kernel writes, the row read a second time from cache.
@@ -232,12 +223,8 @@ int oi_launch_screen_stage_i8(oi_ctx *ctx, const float *d_queries, uint32_t n_qu
     const uint32_t *e2max = !(residual && eps2_residual) ? nullptr :
         reinterpret_cast<const uint32_t *>(residual + oi_screen_i8_meta_offset(n_rows, dim)) + 2 * (n_rows + I8S_PAD_ROWS);
     const uint32_t *emax = reinterpret_cast<const uint32_t *>(i8_copy + oi_screen_i8_meta_offset(n_rows, dim)) + 2 * (n_rows + I8S_PAD_ROWS);
-    if (q_bf16) // the bf16 screen's block as well (oi_launch_screen_stage's outputs)
-        hipLaunchKernelGGL(i8s_stage_both_kernel, dim3((n_padded + 3) / 4), dim3(256), 0, ctx->stream, d_queries, n_queries, n_padded, dim,
-                           max_norm_bits, emax, e2max, eps2_residual, qi8, qf, q_bf16, eps2, gate);
-    else
-        hipLaunchKernelGGL(i8s_stage_kernel, dim3((n_padded + 3) / 4), dim3(256), 0, ctx->stream, d_queries, n_queries, n_padded, dim,
-                           max_norm_bits, emax, e2max, eps2_residual, qi8, qf, gate);
+    hipLaunchKernelGGL(i8s_stage_both_kernel, dim3((n_padded + 3) / 4), dim3(256), 0, ctx->stream, d_queries, n_queries, n_padded, dim,
+                       max_norm_bits, emax, e2max, eps2_residual, qi8, qf, q_bf16, eps2, gate);
     OI_HIP_CHECK(hipGetLastError());
     return OI_OK;
 }
@@ -275,7 +262,7 @@ __device__ __forceinline__ void i8s_issue_meta(const oi_u32x4 &srd, uint32_t vof
 template <int D, int NQT, int NBUF, bool FILT>
 __global__ __launch_bounds__(256, 1) void cosine_i8_screen(
     const uint8_t *__restrict__ rows, const float *__restrict__ meta, uint64_t row_begin, uint64_t row_end,
-    const int8_t *__restrict__ qhi, const int8_t *__restrict__ qlo, // [32*NQT][D] each (i8s_stage_kernel)
+    const int8_t *__restrict__ qhi, const int8_t *__restrict__ qlo, // [32*NQT][D] each (i8s_stage_both_kernel)
     const float *__restrict__ qf, uint32_t qf_stride, uint32_t n_queries, uint32_t doc_id_base, uint64_t *pools, uint32_t *seg_cnt,
     uint32_t seg_cnt_stride, const uint32_t *tau_keys, uint64_t pool_stride, uint32_t carry_cap, uint32_t seg_cap, uint32_t *overflow,
     const uint4 *__restrict__ filt, const uint2 *__restrict__ attrs) { // FILT: the doc filter (oi_filter_tile) after the threshold

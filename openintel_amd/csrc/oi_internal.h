@@ -122,7 +122,7 @@ struct oi_ctx {
     bool side_stream_failed = false;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool overlap_legs = true;              // oi_set_overlap
-    // speculative screen thresholds (cosine_prefilter.hip, pf_spec_kernel): on by default (oi_set_screen_speculation); a batch whose
+    // speculative screen thresholds (oi_select_rank.h: sel_spec_words): on by default (oi_set_screen_speculation); a batch whose
     // speculation failed its check (the device writes *spec_fail_host) switches them off for spec_backoff searches, doubling up to 1024
     bool speculate = true;
     uint32_t spec_skip = 0, spec_backoff = 0;
@@ -133,9 +133,6 @@ struct oi_ctx {
     std::mutex mu;
     std::map<std::string, DevBuf> ws; // named workspaces
     int prof_enabled = 0; // 0 off, 1 every tagged launch, 2 the cosine scorer only
-    // set by search.hip around the gated exact pipeline that follows a bf16 screen (cosine_prefilter.hip): the exact
-    // cosine kernel and the selects launched meanwhile exit at once unless *run_gate is nonzero
-    const uint32_t *run_gate = nullptr;
     const uint32_t *last_screen_gate = nullptr; // the gate word of the last screened search (diagnostics)
     uint32_t last_screen_wgs = 0;               // workgroups of the widest screen launch of the last screened search (diagnostics)
     uint32_t last_sample_rows = 0;              // rows of the last search's sample pass, 0 = it took none (diagnostics: "screen_sample")
@@ -319,7 +316,7 @@ struct SelectExtra {
     const float *row_meta = nullptr;
     uint32_t meta_base = 0;
     const float *row_qn = nullptr, *row_cq = nullptr;
-    // margin mode: the speculative threshold rides in the select (cosine_prefilter.hip: what pf_spec_kernel computes, from the
+    // margin mode: the speculative threshold rides in the select (oi_select_rank.h: sel_spec_words, from the r-th largest of the
     // keys the select holds): spec_rank = r > 0 and both pointers set
     uint32_t spec_rank = 0;
     uint32_t *spec_tau = nullptr, *spec_max = nullptr;
@@ -375,9 +372,11 @@ int oi_launch_centroids_from_sums(oi_ctx *ctx, const int64_t *d_sums, const uint
 int oi_launch_fit_moved(oi_ctx *ctx, const uint32_t *d_cur, const uint32_t *d_prev, uint64_t n, uint64_t *d_out);
 // cosine.hip
 // Sets pool.n_segs / pool.seg_cap for this chunk (the following select must use the same view).
+// run_gate != null: a launch of the gated exact pipeline behind a screen (search.hip: cosine_exact) -- the kernel exits at once
+// unless *run_gate is nonzero, and the launch is profiled as "cosine_gated"; null: ungated, "cosine".
 int oi_launch_cosine_chunk(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end,
                            uint32_t dim, const float *d_queries_padded, uint32_t n_queries,
-                           uint32_t n_queries_padded, uint32_t doc_id_base, PoolView &pool);
+                           uint32_t n_queries_padded, uint32_t doc_id_base, PoolView &pool, const uint32_t *run_gate);
 // Largest chunk (rows) that can never overflow a pool of `stride` entries per query.
 uint64_t oi_cosine_max_chunk_rows(const oi_ctx *ctx, uint32_t dim, uint32_t n_queries, uint64_t stride,
                                   uint32_t carry_cap);
@@ -417,9 +416,8 @@ int oi_launch_make_screen_i8(oi_ctx *ctx, const float *rows, uint64_t n, uint32_
 // per search: i8 hi / lo query blocks (qi8: [2][n_padded][dim]) and four floats per query in qf: qa, qn, cq, eps2 (the tier's margin)
 int oi_launch_screen_stage_i8(oi_ctx *ctx, const float *d_queries, uint32_t n_queries, uint32_t dim, const uint32_t *max_norm_bits,
                               const uint8_t *i8_copy, uint64_t n_rows, int8_t *qi8, float *qf, uint32_t *gate,
-                              uint16_t *q_bf16 = nullptr, float *eps2 = nullptr, const uint8_t *residual = nullptr,
-                              float *eps2_residual = nullptr);
-// (q_bf16 / eps2 set: the same launch also writes what oi_launch_screen_stage writes -- the int8 route stages once;
+                              uint16_t *q_bf16, float *eps2, const uint8_t *residual = nullptr, float *eps2_residual = nullptr);
+// (q_bf16 / eps2: the same launch also writes what oi_launch_screen_stage writes -- the int8 route stages once;
 // residual / eps2_residual set: eps2_residual[q] = 2 eps2'_q, the residual tier's select margin, written last -- it may be eps2)
 int oi_launch_cosine_screen_i8_chunk(oi_ctx *ctx, const uint8_t *i8_copy, uint64_t n_rows_total, uint64_t row_begin, uint64_t row_end,
                                      uint32_t dim, const int8_t *qi8, const float *qf, uint32_t n_queries, uint32_t doc_id_base,
@@ -447,16 +445,10 @@ int oi_launch_cosine_screen_copy_chunk(oi_ctx *ctx, const uint16_t *copy_rows, u
                                        const uint16_t *q_bf16, uint32_t n_queries, uint32_t doc_id_base, PoolView &pool);
 int oi_launch_screen_probe(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint32_t n_rows, uint32_t dim,
                            const uint16_t *q_bf16, uint32_t n_queries, float *d_out);
-// speculative thresholds of the screen (cosine_prefilter.hip): the r-th best screen score so far - 2 eps, if above the proven
-// threshold, for the NEXT chunk (spec_tau), the largest one used per query (spec_max); the check against the final one rides in
+// speculative thresholds of the screen: the r-th best screen score so far - 2 eps, if above the proven threshold, for the NEXT
+// chunk (spec_tau), the largest one used per query (spec_max) -- made inside the margin select that precedes the next chunk
+// (SelectExtra::spec_rank, select.hip) or by the sample pass's rank launch; the check against the final one rides in
 // oi_launch_rescore (spec_max, tau_final, gate, fail_host)
-// (the product computes them inside the margin select that precedes the next chunk -- SelectExtra::spec_rank, select.hip; the
-// separate launch stays for A/B runs of ablation builds, OI_SPEC_KERNEL, and oi_launch_spec_compare reports, from the device, any
-// word of theirs that differs)
-int oi_launch_spec_threshold(oi_ctx *ctx, const PoolView &pool, uint32_t n_queries, uint32_t r, const float *eps2, uint32_t *spec_tau,
-                             uint32_t *spec_max);
-int oi_launch_spec_compare(oi_ctx *ctx, uint32_t n_queries, const uint32_t *tau_a, const uint32_t *max_a, const uint32_t *tau_b,
-                           const uint32_t *max_b);
 int oi_launch_rescore(oi_ctx *ctx, const float *rows, uint64_t n_rows, uint32_t dim, uint32_t doc_id_base,
                       const float *d_queries, uint32_t n_queries, const PoolView &in, const PoolView &out,
                       const uint32_t *extra_docs = nullptr, uint32_t n_extra = 0, const uint32_t *spec_max = nullptr,
@@ -467,7 +459,7 @@ int oi_launch_rescore(oi_ctx *ctx, const float *rows, uint64_t n_rows, uint32_t 
 int oi_launch_row_norm_classes(oi_ctx *ctx, const float *rows, uint64_t n, uint32_t dim, float X0, float E0, uint32_t *cls,
                                uint32_t *bitmap, uint32_t *list, uint32_t cap);
 int oi_launch_cosine_ksplit(oi_ctx *ctx, const float *rows, uint64_t row_begin, uint64_t row_end, uint32_t dim,
-                            const float *q, uint32_t nq, bool two_tiles, uint32_t doc_id_base, const PoolView &p);
+                            const float *q, uint32_t nq, bool two_tiles, uint32_t doc_id_base, const PoolView &p, const uint32_t *run_gate);
 // bm25.hip
 int oi_bm25_stage_forward(oi_index *idx, const uint32_t *d_terms, const uint64_t *d_offsets);
 int oi_bm25_finalize(oi_index *idx, uint64_t global_n, uint64_t global_tokens, const uint32_t *global_df_host);

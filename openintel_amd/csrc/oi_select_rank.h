@@ -14,9 +14,23 @@
 #endif
 static_assert(SEL_THREADS == 1024 && SEL_MAX_SEGS == 4096, "sel_rank_bin2k and SelShared are laid out for 1024 threads and 4096 segments");
 
-// The speculative threshold of a query from the r-th largest score key of its carry region (sel_rth_score_key; have: r keys were
-// there) -- pf_spec_kernel's last step (cosine_prefilter.hip), word for word: lowered by the margin, never below the proven
-// threshold tau, and the largest one used is remembered for the check.  One thread calls.
+// ---------------------------------------------------------------- speculative thresholds of the screen
+// The screen's threshold after m of n rows is PROVEN: tau~_m - 2 eps, tau~_m the k'-th best screen score of those m rows.  It is
+// weak while m << n (k' of 28 672 rows: 3.5 % of the next chunk pass; the final one passes 0.01 %), and every survivor of a weak
+// threshold costs staging, pool traffic and select time.  What the final threshold will be can be PREDICTED from the same m rows:
+// if they are a fair sample, the k'-th best of n sits near the (k' m / n)-th best of m.  The prediction takes the r-th best screen
+// score so far, r = 3 k' m / n + 12 (three times the expected rank plus twelve: for rows in any exchangeable order the chance
+// that fewer than k' of the n rows reach it is < 1e-9 whatever m), lowers it by the same 2 eps, and hands the LARGER of it and the
+// proven threshold to the next chunk.  A prediction is not a bound -- so it is CHECKED: pf_rescore_kernel (cosine_prefilter.hip,
+// first thing) compares the largest speculative threshold used for a query with the proven one at the end, tau~_n - 2 eps.
+// T_spec <= tau~_n - 2 eps means every row the speculation dropped (s~ < T_spec) would have been dropped by the final proven
+// threshold as well: the survivor set still holds every row of the exact list, the lists are the proven screen's.  Otherwise (a
+// corpus whose first rows are not a fair sample: sorted by time or topic) the gate opens and the exact pipeline rescores the batch
+// in the same call, and the host, told through a pinned flag, stops speculating for a while (search.hip: oi_spec_take_failure).
+//
+// The words of a query's speculative threshold from the r-th largest score key of its carry region (sel_rth_score_key; have: r
+// keys were there): the key lowered by the margin, never below the proven threshold tau, and the largest one used is remembered
+// for the check.  One thread calls.
 __device__ __forceinline__ void sel_spec_words(bool have, uint32_t rth_key, float eps2, uint32_t tau, uint32_t *spec_tau, uint32_t *spec_max) {
     if (!have) { *spec_tau = tau; return; } // too few keys kept: the proven threshold as it is
     const float s = oi_key_f32(rth_key) - eps2; // (a query without a bound has eps2 = +inf: -inf, no speculation)
@@ -124,9 +138,8 @@ __device__ __forceinline__ void sel_hist_leading(FE &&for_each, SelShared &sh) {
 }
 
 // The r-th largest 32-bit score key of the keys `for_each` enumerates (f(valid, key), the same keys on every call; 1 <= r <= their
-// number): digits of 11, 11 and 10 bits from the top through the same histogram.  This is the key pf_spec_kernel
-// (cosine_prefilter.hip) finds in the carry region -- the r-th largest of a set is unique -- taken from the keys the select
-// already holds.  All threads call; the result is uniform.  sh.hist2k / sh.rx's words are free on entry and on return.
+// number): digits of 11, 11 and 10 bits from the top through the same histogram.  The r-th largest of a set is unique, so
+// whichever keys of the carry region the select already holds in registers give the prediction's key.  All threads call; the result is uniform.  sh.hist2k / sh.rx's words are free on entry and on return.
 template <class FE>
 __device__ __forceinline__ uint32_t sel_rth_score_key(FE &&for_each, uint32_t r, SelShared &sh) {
     const uint32_t tid = threadIdx.x;

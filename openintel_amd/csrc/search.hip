@@ -1,6 +1,7 @@
 // search.hip -- one hybrid search on the device (search_lists_device): the plan of the call, the chunk schedule of the cosine
 // leg, the cosine routes and the four BM25 modes.  The entry points that stage the queries and copy the results are in api.hip.
 #include <algorithm>
+#include <cassert>
 
 #include "oi_internal.h"
 
@@ -35,8 +36,14 @@ int bm25_mode_of(const oi_index *idx) {
         mode = strcmp(mode_env, "scan") == 0 ? 2 : strcmp(mode_env, "taat") == 0 ? 1 : strcmp(mode_env, "wave") == 0 ? 3 : 4;
     return mode == 0 ? 4 : mode;
 }
-// State of both pools in one block, zeroed with ONE memset per search:
-//   cosine: carry_cnt[B] tau[B] seg_cnt[B][CUs]      BM25: carry_cnt[B] seg_cnt[B][n_blocks]
+// The state words of one pool, carry_cnt[n] tau[n] seg_cnt[n][segs] in memory order: the one place that lays them out.
+struct PoolWords {
+    uint32_t *carry, *tau, *seg;
+    static size_t count(uint32_t n_queries, uint32_t segs) { return (size_t)n_queries * (2 + (size_t)segs); }
+    PoolWords(uint32_t *w, uint32_t n_queries) : carry(w), tau(w + n_queries), seg(w + 2 * (size_t)n_queries) {}
+};
+// State of both pools in one block, zeroed with ONE memset per search: the cosine pool's words (a segment per workgroup), then
+// the BM25 pool's (a segment per doc block).
 // `extra_words` more zeroed words follow them (*extra): the bf16 screen's state, so that one memset kernel does both.
 int prepare_pools(oi_ctx *ctx, uint32_t B, uint64_t cos_alloc_stride, uint64_t cos_stride, uint32_t carry_cap, uint32_t bm_blocks,
                   uint32_t depth, Pools *out, size_t extra_words, uint32_t **extra) {
@@ -47,7 +54,7 @@ int prepare_pools(oi_ctx *ctx, uint32_t B, uint64_t cos_alloc_stride, uint64_t c
     }
     const uint32_t cos_segs = (uint32_t)ctx->num_cus * (B <= 8 ? 8u : 1u); // one per workgroup: GEMV grids are 8 per CU
     const uint32_t bm_segs = bm_blocks ? bm_blocks : 1;
-    const size_t words = (size_t)B * (2 + cos_segs + 2 + bm_segs);
+    const size_t cos_words = PoolWords::count(B, cos_segs), words = cos_words + PoolWords::count(B, bm_segs);
     DevBuf &st = ctx->buf("pool_state");
     OI_CHECK(st.ensure(sizeof(uint32_t) * (words + extra_words)));
     OI_HIP_CHECK(hipMemsetAsync(st.p, 0, sizeof(uint32_t) * (words + extra_words), ctx->stream));
@@ -56,11 +63,9 @@ int prepare_pools(oi_ctx *ctx, uint32_t B, uint64_t cos_alloc_stride, uint64_t c
     DevBuf &pc = ctx->buf("pool_cos"), &pb = ctx->buf("pool_bm");
     OI_CHECK(pc.ensure(sizeof(uint64_t) * (size_t)B * cos_alloc_stride)); // (room for the widest view of it: the screen's)
     OI_CHECK(pb.ensure(sizeof(uint64_t) * (size_t)B * bm_stride));
-    uint32_t *s = st.as<uint32_t>();
-    uint32_t *cos_carry = s, *cos_tau = s + B, *cos_seg = s + 2 * (size_t)B;
-    uint32_t *bm_carry = cos_seg + (size_t)B * cos_segs, *bm_tau = bm_carry + B, *bm_seg = bm_tau + B;
-    out->cos = PoolView{pc.as<uint64_t>(), cos_carry, cos_seg, cos_tau, cos_stride, carry_cap, 0, 0, cos_segs, flag.as<uint32_t>()};
-    out->bm = PoolView{pb.as<uint64_t>(), bm_carry, bm_seg, bm_tau, bm_stride, carry_cap, depth, bm_segs, bm_segs, flag.as<uint32_t>()};
+    const PoolWords cw(st.as<uint32_t>(), B), bw(st.as<uint32_t>() + cos_words, B);
+    out->cos = PoolView{pc.as<uint64_t>(), cw.carry, cw.seg, cw.tau, cos_stride, carry_cap, 0, 0, cos_segs, flag.as<uint32_t>()};
+    out->bm = PoolView{pb.as<uint64_t>(), bw.carry, bw.seg, bw.tau, bm_stride, carry_cap, depth, bm_segs, bm_segs, flag.as<uint32_t>()};
     return OI_OK;
 }
 
@@ -196,7 +201,7 @@ Plan plan_search(const Search &s) {
     p.pf_carry = p.cos == CosRoute::screen_i8 ? OI_I8_CARRY : 4096;
     p.pf_slack = 128ull * ((uint64_t)ctx->num_cus + 1);
     p.pf_stride = std::min<uint64_t>(p.pf_carry + n + p.pf_slack, std::max<uint64_t>(std::min<uint64_t>(1ull << 24, budget), p.pf_carry + 4 * p.pf_slack));
-    // ---- speculative thresholds of the screen (cosine_prefilter.hip, pf_spec_kernel; oi_set_screen_speculation).  Decided here
+    // ---- speculative thresholds of the screen (oi_select_rank.h: sel_spec_words; oi_set_screen_speculation).  Decided here
     // because the chunk schedule depends on it: with a predicted threshold after the first chunk the second can be as large as the
     // pool takes (10M rows 2.64 -> 2.54 ms, a 1.25M-row shard 0.574 -> 0.540 -> 0.523 with the short first chunk;
     // tools/r05_spec_sched.sh), with proven thresholds it must grow slowly (x 8).  Off: oi_set_screen_speculation(ctx, 0); with
@@ -317,14 +322,14 @@ int bm25_stream(const Search &s, const PoolView &bm) {
     pass = std::max<uint64_t>(1, std::min<uint64_t>(pass, std::min<uint32_t>(B, oi_bm25_stream_pass_queries())));
     DevBuf &sp = ctx->buf("pool_bm_stream"), &sc = ctx->buf("pool_bm_stream_state");
     OI_CHECK(sp.ensure(sizeof(uint64_t) * (size_t)pass * sstride));
-    const size_t swords = (size_t)pass * (2 + nb);
+    const size_t swords = PoolWords::count((uint32_t)pass, nb);
     OI_CHECK(sc.ensure(sizeof(uint32_t) * swords));
     for (uint32_t q0 = 0; q0 < B; q0 += (uint32_t)pass) {
         const uint32_t nq = std::min<uint32_t>((uint32_t)pass, B - q0);
-        uint32_t *w = sc.as<uint32_t>();
-        // (the plan launch also zeroes the pass's pool state: carry_cnt[pass] tau[pass] seg_cnt[pass][nb])
-        OI_CHECK(oi_launch_bm25_plan(idx, s.qt, s.qo, q0, nq, w, swords, depth, (uint32_t)pass, (uint32_t)pass, floors));
-        PoolView W1{sp.as<uint64_t>(), w, w + 2 * (size_t)pass, w + pass, sstride, carry_cap, cap1, first, nb, bm.overflow, s.filt, s.attrs};
+        const PoolWords w(sc.as<uint32_t>(), (uint32_t)pass);
+        // (the plan launch also zeroes the pass's pool state, and writes the pass's thresholds)
+        OI_CHECK(oi_launch_bm25_plan(idx, s.qt, s.qo, q0, nq, w.carry, swords, depth, (uint32_t)(w.tau - w.carry), (uint32_t)pass, floors));
+        PoolView W1{sp.as<uint64_t>(), w.carry, w.seg, w.tau, sstride, carry_cap, cap1, first, nb, bm.overflow, s.filt, s.attrs};
         OI_CHECK(oi_launch_bm25_stream(idx, s.qt, s.qo, q0, nq, depth, W1, 0, first));
         PoolView W2 = W1;
         if (first < nb) {
@@ -352,14 +357,14 @@ int bm25_wave(const Search &s, const PoolView &bm) {
     pass = std::max<uint64_t>(1, std::min<uint64_t>(pass, std::min<uint32_t>(B, oi_bm25_wave_pass_queries())));
     DevBuf &wp = ctx->buf("pool_bm_wave"), &wc = ctx->buf("pool_bm_wave_state");
     OI_CHECK(wp.ensure(sizeof(uint64_t) * (size_t)pass * wstride));
-    const size_t wwords = (size_t)pass * (2 + nb);
+    const size_t wwords = PoolWords::count((uint32_t)pass, nb);
     OI_CHECK(wc.ensure(sizeof(uint32_t) * wwords));
     const uint32_t first = nb > 16 ? std::max<uint32_t>(8, nb / 8) : nb;
     for (uint32_t q0 = 0; q0 < B; q0 += (uint32_t)pass) {
         const uint32_t nq = std::min<uint32_t>((uint32_t)pass, B - q0);
         OI_HIP_CHECK(hipMemsetAsync(wc.p, 0, sizeof(uint32_t) * wwords, ctx->stream));
-        uint32_t *w = wc.as<uint32_t>();
-        PoolView W{wp.as<uint64_t>(), w, w + 2 * (size_t)pass, w + pass, wstride, carry_cap, OI_BM25_BLOCK_DOCS, nb, nb, bm.overflow};
+        const PoolWords w(wc.as<uint32_t>(), (uint32_t)pass);
+        PoolView W{wp.as<uint64_t>(), w.carry, w.seg, w.tau, wstride, carry_cap, OI_BM25_BLOCK_DOCS, nb, nb, bm.overflow};
         OI_CHECK(oi_launch_bm25_wave(idx, s.qt, s.qo, q0, nq, W, 0, first));
         if (first < nb) {
             OI_CHECK(oi_launch_select(ctx, W, nq, depth, /*compact=*/true, nullptr, nullptr, nullptr, depth));
@@ -397,11 +402,11 @@ int bm25_scan(const Search &s, const PoolView &bm) {
     if (sstride > sbudget) sstride = std::max<uint64_t>(sbudget, carry_cap + 4 * sslack);
     DevBuf &sp = ctx->buf("pool_bm_scan"), &sc = ctx->buf("pool_bm_scan_state");
     OI_CHECK(sp.ensure(sizeof(uint64_t) * (size_t)B * sstride));
-    const size_t swords = (size_t)B * (2 + segs);
+    const size_t swords = PoolWords::count(B, segs);
     OI_CHECK(sc.ensure(sizeof(uint32_t) * swords));
     OI_HIP_CHECK(hipMemsetAsync(sc.p, 0, sizeof(uint32_t) * swords, ctx->stream));
-    uint32_t *w = sc.as<uint32_t>();
-    PoolView SP{sp.as<uint64_t>(), w, w + 2 * (size_t)B, w + B, sstride, carry_cap, 0, 0, segs, bm.overflow};
+    const PoolWords w(sc.as<uint32_t>(), B);
+    PoolView SP{sp.as<uint64_t>(), w.carry, w.seg, w.tau, sstride, carry_cap, 0, 0, segs, bm.overflow};
     const uint64_t max_chunk = sstride - carry_cap - sslack;
     const uint32_t pass = oi_bm25_scan_pass_queries(idx->max_query_terms);
     for (uint32_t q0 = 0; q0 < B; q0 += pass) {
@@ -472,158 +477,229 @@ int cosine_exact(const Search &s, PoolView X, const float *q, uint32_t Bp, uint6
     X.filt = s.filt; X.attrs = s.attrs;
     const uint64_t first = gate ? max_chunk : oi_first_chunk_rows(s.depth);
     for (const Chunk &c : chunk_schedule(idx->n_docs, first, oi_chunk_growth(s.B), max_chunk, true)) {
-        OI_CHECK(oi_launch_cosine_chunk(s.ctx, idx->rows, c.r, c.e, idx->dim, q, s.B, Bp, idx->doc_id_base, X));
+        OI_CHECK(oi_launch_cosine_chunk(s.ctx, idx->rows, c.r, c.e, idx->dim, q, s.B, Bp, idx->doc_id_base, X, gate));
         const bool last = c.e == idx->n_docs;
         OI_CHECK(oi_launch_select(s.ctx, X, s.B, s.depth, /*compact=*/!last, last ? s.cos_s : nullptr,
                                   last ? s.cos_d : nullptr, last ? s.cos_c : nullptr, s.depth, gate ? &ex : nullptr));
     }
     return OI_OK;
 }
+
+// ---------------------------------------------------------------- the screen routes
 // bf16 screen -> margin selects -> exact rescoring -> sorted selection; then the gated exact pipeline (cosine_prefilter.hip).
 // Its pool keeps up to 4096 keys per query between chunks (OI_I8_CARRY on the int8 route).
-int cosine_screen(const Search &s, const Plan &p, const Pools &P, uint32_t *w, const float *q, uint32_t Bp, uint64_t max_chunk) {
+
+// The screen's state words, zeroed with the pool state (prepare_pools: its extra words), in memory order:
+//   carry_cnt[B] tau[B] rs_cnt[B] eps2[B] gate[4] seg_cnt[B][segs] spec_tau[B] spec_max[B]
+// search_lists_device sizes them with count(), cosine_screen carves them with the constructor: the one place that lays them out.
+uint32_t screen_segs(const oi_ctx *ctx) { return (uint32_t)ctx->num_cus; } // a segment per workgroup of the widest screen launch
+struct ScreenWords {
+    uint32_t *pf_cnt, *pf_tau, *rs_cnt;
+    float *eps2;
+    uint32_t *gate, *pf_seg, *spec_tau, *spec_max;
+    static size_t count(uint32_t B, uint32_t segs) { return (size_t)B * (6 + (size_t)segs) + 4; }
+    ScreenWords(uint32_t *w, uint32_t B, uint32_t segs) {
+        uint32_t *const end = w + count(B, segs);
+        auto take = [&w](size_t words) { uint32_t *at = w; w += words; return at; };
+        pf_cnt = take(B);
+        pf_tau = take(B);
+        rs_cnt = take(B);
+        eps2 = reinterpret_cast<float *>(take(B));
+        gate = take(4);
+        pf_seg = take((size_t)B * segs);
+        spec_tau = take(B);
+        spec_max = take(B);
+        assert(w == end); // a field added here and not to count() (or the reverse) stops the first search
+        (void)end;
+    }
+};
+
+// What the stages of one screened search share, passed by reference (nothing of it lives on the ctx).
+struct ScreenRun {
+    ScreenWords w;
+    PoolView PF{}, RS{}; // the screen's view of the cosine pool buffer; the rescored survivors
+    // the margin selects: mx the bf16 screen's (uniform margin w.eps2: the chunks of the bf16 routes, the final one of the int8
+    // route), m8 the chunks' -- the int8 tier's per-row margins on that route, a copy of mx on the others
+    SelectExtra mx, m8;
+    uint16_t *qb = nullptr; // the staged query blocks: bf16, and the int8 tier's (hi / lo planes, four floats per query)
+    int8_t *qi8 = nullptr;
+    float *qf8 = nullptr;
+    // Speculative thresholds (the plan's spec and schedule): the next chunk is screened against the larger of the proven
+    // threshold and a prediction from the rows seen so far, checked at the end (a failed check opens the gate).
+    bool spec_next = false, spec_any = false;
+    explicit ScreenRun(const ScreenWords &words) : w(words) {}
+};
+
+// The staging launch of a route: the bf16 query block, the margins and the gate; the int8 route stages both tiers' blocks in one.
+int screen_stage(const Search &s, const Plan &p, ScreenRun &R) {
+    oi_index *idx = s.idx;
+    const uint32_t *norms = idx->max_row_norm.as<uint32_t>();
+    switch (p.cos) {
+        case CosRoute::screen_f32:
+        case CosRoute::screen_copy:
+            return oi_launch_screen_stage(s.ctx, s.qv, s.B, idx->dim, norms, R.qb, R.w.eps2, R.w.gate);
+        case CosRoute::screen_i8:
+            return oi_launch_screen_stage_i8(s.ctx, s.qv, s.B, idx->dim, norms, idx->screen_i8.as<uint8_t>(), idx->n_docs, R.qi8, R.qf8,
+                                             R.w.gate, R.qb, R.w.eps2,
+                                             // (the residual tier's margin over the bf16 screen's, which has no reader on that tail)
+                                             p.rescreen_residual ? idx->screen_i8r.as<uint8_t>() : nullptr,
+                                             p.rescreen_residual ? R.w.eps2 : nullptr);
+        default:
+            oi_set_error("search: not a screen route");
+            return OI_ERR_STATE;
+    }
+}
+// The screen launch of one chunk: the same products, the same bound on the two bf16 routes -- only where bf16(x) comes from differs
+// (converted on the fly from the f32 rows, 4 d bytes per row, or read from the copy, 2 d bytes per row); the int8 first tier
+// (cosine_screen_i8.hip) streams the int8 copy against per-row bounds.  Sets R.PF's segments for the chunk's select.
+int screen_launch_chunk(const Search &s, const Plan &p, ScreenRun &R, const Chunk &c) {
+    oi_index *idx = s.idx;
+    switch (p.cos) {
+        case CosRoute::screen_f32:
+            return oi_launch_cosine_screen_chunk(s.ctx, idx->rows, c.r, c.e, idx->dim, R.qb, s.B, idx->doc_id_base, R.PF);
+        case CosRoute::screen_copy:
+            return oi_launch_cosine_screen_copy_chunk(s.ctx, idx->screen_copy.as<uint16_t>(), c.r, c.e, idx->dim, R.qb, s.B, idx->doc_id_base, R.PF);
+        case CosRoute::screen_i8:
+            return oi_launch_cosine_screen_i8_chunk(s.ctx, idx->screen_i8.as<uint8_t>(), idx->n_docs, c.r, c.e, idx->dim, R.qi8, R.qf8, s.B,
+                                                    idx->doc_id_base, R.PF, p.screen_wgs);
+        default:
+            oi_set_error("search: not a screen route");
+            return OI_ERR_STATE;
+    }
+}
+
+// Open: the workspace buffers and the pool views, the route's staging launch, a missing bf16 copy, the margin selects' extras.
+int screen_open(const Search &s, const Plan &p, const Pools &P, ScreenRun &R) {
     oi_index *idx = s.idx; oi_ctx *ctx = s.ctx;
     const uint64_t n = idx->n_docs;
-    const uint32_t B = s.B, depth = s.depth, dim = idx->dim;
-    const bool i8 = p.cos == CosRoute::screen_i8, copy = p.cos != CosRoute::screen_f32;
-    const uint32_t segs = (uint32_t)ctx->num_cus;
+    const uint32_t B = s.B, dim = idx->dim, segs = screen_segs(ctx), n_padded = (B + 31u) & ~31u;
+    const bool i8 = p.cos == CosRoute::screen_i8;
     DevBuf &pk = ctx->buf("pool_cos"), &rk = ctx->buf("screen_rescored"), &qb = ctx->buf("screen_q_bf16");
     const uint32_t rs_cap = p.pf_carry + OI_LONG_ROWS_MAX; // the survivors and the index's long rows (two-class margin)
     OI_CHECK(rk.ensure(sizeof(uint64_t) * (size_t)B * rs_cap));
-    const uint32_t n_padded = (B + 31u) & ~31u;
     OI_CHECK(qb.ensure(sizeof(uint16_t) * (size_t)(n_padded + 64) * dim));
-    // state, zeroed with the pool state (prepare_pools): carry_cnt[B] tau[B] rs_cnt[B] eps2[B] gate[4] seg_cnt[B][segs] spec_tau[B] spec_max[B]
-    uint32_t *pf_cnt = w, *pf_tau = w + B, *rs_cnt = w + 2 * (size_t)B;
-    float *eps2 = reinterpret_cast<float *>(w + 3 * (size_t)B);
-    uint32_t *gate = w + 4 * (size_t)B, *pf_seg = gate + 4;
-    uint32_t *spec_tau = pf_seg + (size_t)B * segs, *spec_max = spec_tau + B;
-    PoolView PF{pk.as<uint64_t>(), pf_cnt, pf_seg, pf_tau, p.pf_stride, p.pf_carry, 0, 0, segs, P.cos.overflow, s.filt, s.attrs};
-    PoolView RS{rk.as<uint64_t>(), rs_cnt, pf_seg, nullptr, rs_cap, rs_cap, 0, 0, segs, P.cos.overflow, s.filt, s.attrs};
-    // (the int8 route stages the bf16 block in its own staging launch, below; OI_STAGE_SPLIT, ablation builds: two launches as before)
-    static const bool stage_split = oi_ablation_env("OI_STAGE_SPLIT") != nullptr;
-    if (!i8 || stage_split) OI_CHECK(oi_launch_screen_stage(ctx, s.qv, B, dim, idx->max_row_norm.as<uint32_t>(), qb.as<uint16_t>(), eps2, gate));
-    SelectExtra mx; mx.eps2 = eps2; mx.margin_gate = gate;
-    if (idx->n_long) { mx.skip_bitmap = idx->long_bitmap.as<uint32_t>(); mx.skip_base = idx->doc_id_base; }
-    if (copy && !idx->screen_copy.p) { // made once, on the first search that asks for it (n x d x 2 B of HBM)
-        OI_CHECK(idx->screen_copy.ensure(sizeof(uint16_t) * (size_t)n * dim + 64));
-        OI_CHECK(oi_launch_make_screen_copy(ctx, idx->rows, n, dim, idx->screen_copy.as<uint16_t>()));
-    }
+    R.qb = qb.as<uint16_t>();
+    R.PF = PoolView{pk.as<uint64_t>(), R.w.pf_cnt, R.w.pf_seg, R.w.pf_tau, p.pf_stride, p.pf_carry, 0, 0, segs, P.cos.overflow, s.filt, s.attrs};
+    R.RS = PoolView{rk.as<uint64_t>(), R.w.rs_cnt, R.w.pf_seg, nullptr, rs_cap, rs_cap, 0, 0, segs, P.cos.overflow, s.filt, s.attrs};
+    R.mx.eps2 = R.w.eps2; R.mx.margin_gate = R.w.gate;
+    if (idx->n_long) { R.mx.skip_bitmap = idx->long_bitmap.as<uint32_t>(); R.mx.skip_base = idx->doc_id_base; }
+    R.m8 = R.mx;
     // The int8 first tier (cosine_screen_i8.hip): the chunks stream the int8 copy against per-row bounds, the
     // margin selects keep up to OI_I8_CARRY lower-bound keys per query (an overflow opens the gate), the speculation works on
-    // those keys; after the last chunk the survivors get their bf16 screen keys from the bf16 copy and the bf16 screen's
-    // final margin select, rescoring and gate follow unchanged.
-    int8_t *qi8 = nullptr; float *qf8 = nullptr;
-    SelectExtra m8 = mx;
+    // those keys; after the last chunk the survivors get their second-tier keys and the bf16 screen's final margin select,
+    // rescoring and gate follow unchanged.
     if (i8) {
         DevBuf &qs = ctx->buf("screen_q_i8"), &cb = ctx->buf("screen_i8_cand");
         const size_t qi8_bytes = ((2 * (size_t)n_padded * dim) + 255) & ~(size_t)255;
         OI_CHECK(qs.ensure(qi8_bytes + sizeof(float) * 4 * (size_t)n_padded));
         OI_CHECK(cb.ensure(sizeof(uint64_t) * (size_t)B * OI_I8_CARRY));
-        qi8 = reinterpret_cast<int8_t *>(qs.p);
-        qf8 = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(qs.p) + qi8_bytes);
-        OI_CHECK(oi_launch_screen_stage_i8(ctx, s.qv, B, dim, idx->max_row_norm.as<uint32_t>(), idx->screen_i8.as<uint8_t>(), n,
-                                           qi8, qf8, gate, stage_split ? nullptr : qb.as<uint16_t>(), stage_split ? nullptr : eps2,
-                                           // (the residual tier's margin over the bf16 screen's, which has no reader on that tail)
-                                           p.rescreen_residual ? idx->screen_i8r.as<uint8_t>() : nullptr, p.rescreen_residual ? eps2 : nullptr));
-        m8.eps2 = qf8 + 3 * (size_t)n_padded; m8.row_qn = qf8 + (size_t)n_padded; m8.row_cq = qf8 + 2 * (size_t)n_padded;
-        m8.cand = cb.as<uint64_t>(); m8.cand_cap = OI_I8_CARRY;
-        m8.row_meta = reinterpret_cast<const float *>(idx->screen_i8.as<uint8_t>() + oi_screen_i8_meta_offset(n, dim));
-        m8.meta_base = idx->doc_id_base;
+        R.qi8 = reinterpret_cast<int8_t *>(qs.p);
+        R.qf8 = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(qs.p) + qi8_bytes);
+        R.m8.eps2 = R.qf8 + 3 * (size_t)n_padded; R.m8.row_qn = R.qf8 + (size_t)n_padded; R.m8.row_cq = R.qf8 + 2 * (size_t)n_padded;
+        R.m8.cand = cb.as<uint64_t>(); R.m8.cand_cap = OI_I8_CARRY;
+        R.m8.row_meta = reinterpret_cast<const float *>(idx->screen_i8.as<uint8_t>() + oi_screen_i8_meta_offset(n, dim));
+        R.m8.meta_base = idx->doc_id_base;
     }
-    // Speculative thresholds (the plan's spec and schedule): the next chunk is screened against the larger of the proven
-    // threshold and a prediction from the rows seen so far, checked at the end (a failed check opens the gate).
-    bool spec_next = false, spec_any = false;
-    if (p.sample_rows) { // the plan's sample pass: the first prediction before any chunk is pooled (the proven thresholds are still 0)
-        // The dense key array lies at the head of the pool buffer (ctx->buf "pool_cos": 7.3 MB of it at 10M x 768, B = 64): the pool
-        // holds nothing yet -- no carried key, no segment -- and the first chunk, which writes it, starts behind the rank launch.
-        const uint32_t ks = oi_screen_i8_sample_stride(p.sample_rows);
-        OI_REQUIRE(sizeof(uint32_t) * (size_t)n_padded * ks <= sizeof(uint64_t) * (size_t)B * p.pf_stride && pk.p,
-                   "search: the sample pass's keys do not fit the candidate pool");
-        uint32_t *sample_keys = pk.as<uint32_t>();
-        OI_CHECK(oi_launch_screen_i8_sample(ctx, idx->screen_i8.as<uint8_t>(), n, p.sample_rows, dim, qi8, qf8, B,
-                                            idx->n_long ? idx->long_bitmap.as<uint32_t>() : nullptr, sample_keys));
-        const uint64_t rank = (3ull * depth * p.sample_rows + n - 1) / n + 12;
-        OI_CHECK(oi_launch_sample_rank(ctx, sample_keys, ks, p.sample_rows, B, (uint32_t)rank, m8.eps2, pf_tau, spec_tau, spec_max));
-        spec_next = spec_any = true;
+    OI_CHECK(screen_stage(s, p, R));
+    if (p.cos == CosRoute::screen_copy && !idx->screen_copy.p) { // made once, on the first search that asks for it (n x d x 2 B of HBM)
+        OI_CHECK(idx->screen_copy.ensure(sizeof(uint16_t) * (size_t)n * dim + 64));
+        OI_CHECK(oi_launch_make_screen_copy(ctx, idx->rows, n, dim, idx->screen_copy.as<uint16_t>()));
     }
-    for (size_t i = 0; i < p.screen_chunks.size(); ++i) {
-        const uint64_t r = p.screen_chunks[i].r, e = p.screen_chunks[i].e;
-        const bool last = i + 1 == p.screen_chunks.size();
-        // the same products, the same bound: only where bf16(x) comes from differs (converted on the fly from the
-        // f32 rows, 4 d bytes per row -- or read from the copy, 2 d bytes per row)
-        if (p.late_fork && !p.tail_fork && last) OI_HIP_CHECK(hipEventRecord(ctx->ev_fork, ctx->stream)); // (before the last chunk's launch)
-        uint32_t *const proven_tau = PF.tau_keys;
-        if (spec_next) PF.tau_keys = spec_tau; // (this launch only: the selects keep the proven thresholds)
-        const int rc_screen = i8 ? oi_launch_cosine_screen_i8_chunk(ctx, idx->screen_i8.as<uint8_t>(), n, r, e, dim, qi8, qf8, B, idx->doc_id_base, PF, p.screen_wgs)
-                              : copy ? oi_launch_cosine_screen_copy_chunk(ctx, idx->screen_copy.as<uint16_t>(), r, e, dim, qb.as<uint16_t>(), B, idx->doc_id_base, PF)
-                                     : oi_launch_cosine_screen_chunk(ctx, idx->rows, r, e, dim, qb.as<uint16_t>(), B, idx->doc_id_base, PF);
-        PF.tau_keys = proven_tau;
-        OI_CHECK(rc_screen);
-        ctx->last_screen_wgs = i ? std::max(ctx->last_screen_wgs, PF.n_segs) : PF.n_segs;
-        // ... enqueued after it: the screen's workgroups get their CUs first.  tail_fork: the event is recorded here, behind the
-        // launch, so the leg starts when the chunk ends and this chunk's margin select is the first kernel it runs beside.
-        if (p.tail_fork && last) OI_HIP_CHECK(hipEventRecord(ctx->ev_fork, ctx->stream));
-        if (p.late_fork && last) OI_CHECK(fork_bm25(s, p, P.bm));
-        // The prediction for the next chunk rides in this chunk's margin select (select.hip), which holds the carried keys in
-        // registers.  expected rank of the final k'-th among the e rows seen: depth e / n; three times that plus twelve
-        // OI_SPEC_KERNEL (ablation builds): 1 = the separate pf_spec_kernel launch as before; 2 = both, compared on the device
-        static const int spec_kernel = oi_ablation_env("OI_SPEC_KERNEL") ? atoi(oi_ablation_env("OI_SPEC_KERNEL")) : 0;
-        const uint64_t rank = (3ull * depth * e + n - 1) / n + 12;
-        const bool spec_here = p.spec && !last && 2 * rank <= depth;
-        SelectExtra sx = i8 ? m8 : mx;
-        if (spec_here && spec_kernel != 1) { sx.spec_rank = (uint32_t)rank; sx.spec_tau = spec_tau; sx.spec_max = spec_max; }
-        uint32_t *chk = nullptr; // OI_SPEC_KERNEL=2: spec_tau'[B] spec_max'[B], spec_max' starting from the words the select starts from
-        if (spec_here && spec_kernel == 2) {
-            DevBuf &cw = ctx->buf("spec_check");
-            OI_CHECK(cw.ensure(sizeof(uint32_t) * 2 * (size_t)B));
-            chk = cw.as<uint32_t>();
-            OI_HIP_CHECK(hipMemcpyAsync(chk + B, spec_max, sizeof(uint32_t) * B, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        OI_CHECK(oi_launch_select(ctx, PF, B, depth, /*compact=*/true, nullptr, nullptr, nullptr, depth, &sx));
-        spec_next = false;
-        if (spec_here) {
-            // (the profile's "spec" spans count the predictions made: an empty one where the select made it)
-            if (spec_kernel != 1) { ProfScope ps(ctx, "spec"); }
-            if (spec_kernel == 1) OI_CHECK(oi_launch_spec_threshold(ctx, PF, B, (uint32_t)rank, sx.eps2, spec_tau, spec_max));
-            if (chk) {
-                OI_CHECK(oi_launch_spec_threshold(ctx, PF, B, (uint32_t)rank, sx.eps2, chk, chk + B));
-                OI_CHECK(oi_launch_spec_compare(ctx, B, spec_tau, spec_max, chk, chk + B));
-            }
-            spec_next = spec_any = true;
-        }
+    return OI_OK;
+}
+// The plan's sample pass (int8 route): the first prediction before any chunk is pooled (the proven thresholds are still 0).
+int screen_sample(const Search &s, const Plan &p, ScreenRun &R) {
+    oi_index *idx = s.idx; oi_ctx *ctx = s.ctx;
+    const uint64_t n = idx->n_docs;
+    const uint32_t B = s.B, n_padded = (B + 31u) & ~31u;
+    // The dense key array lies at the head of the pool buffer (ctx->buf "pool_cos": 7.3 MB of it at 10M x 768, B = 64): the pool
+    // holds nothing yet -- no carried key, no segment -- and the first chunk, which writes it, starts behind the rank launch.
+    const uint32_t ks = oi_screen_i8_sample_stride(p.sample_rows);
+    OI_REQUIRE(sizeof(uint32_t) * (size_t)n_padded * ks <= sizeof(uint64_t) * (size_t)B * p.pf_stride && R.PF.keys,
+               "search: the sample pass's keys do not fit the candidate pool");
+    uint32_t *sample_keys = reinterpret_cast<uint32_t *>(R.PF.keys);
+    OI_CHECK(oi_launch_screen_i8_sample(ctx, idx->screen_i8.as<uint8_t>(), n, p.sample_rows, idx->dim, R.qi8, R.qf8, B,
+                                        idx->n_long ? idx->long_bitmap.as<uint32_t>() : nullptr, sample_keys));
+    const uint64_t rank = (3ull * s.depth * p.sample_rows + n - 1) / n + 12;
+    OI_CHECK(oi_launch_sample_rank(ctx, sample_keys, ks, p.sample_rows, B, (uint32_t)rank, R.m8.eps2, R.w.pf_tau, R.w.spec_tau, R.w.spec_max));
+    R.spec_next = R.spec_any = true;
+    return OI_OK;
+}
+// Chunk i of the plan's schedule: its screen launch, the late or tail fork of the BM25 leg, its margin select with the prediction
+// for the next chunk.
+int screen_chunk(const Search &s, const Plan &p, const Pools &P, ScreenRun &R, size_t i) {
+    oi_ctx *ctx = s.ctx;
+    const uint64_t n = s.idx->n_docs, e = p.screen_chunks[i].e;
+    const bool last = i + 1 == p.screen_chunks.size();
+    if (p.late_fork && !p.tail_fork && last) OI_HIP_CHECK(hipEventRecord(ctx->ev_fork, ctx->stream)); // (before the last chunk's launch)
+    uint32_t *const proven_tau = R.PF.tau_keys;
+    if (R.spec_next) R.PF.tau_keys = R.w.spec_tau; // (this launch only: the selects keep the proven thresholds)
+    const int rc_screen = screen_launch_chunk(s, p, R, p.screen_chunks[i]);
+    R.PF.tau_keys = proven_tau;
+    OI_CHECK(rc_screen);
+    ctx->last_screen_wgs = i ? std::max(ctx->last_screen_wgs, R.PF.n_segs) : R.PF.n_segs;
+    // ... enqueued after it: the screen's workgroups get their CUs first.  tail_fork: the event is recorded here, behind the
+    // launch, so the leg starts when the chunk ends and this chunk's margin select is the first kernel it runs beside.
+    if (p.tail_fork && last) OI_HIP_CHECK(hipEventRecord(ctx->ev_fork, ctx->stream));
+    if (p.late_fork && last) OI_CHECK(fork_bm25(s, p, P.bm));
+    // The prediction for the next chunk rides in this chunk's margin select (select.hip), which holds the carried keys in
+    // registers.  expected rank of the final k'-th among the e rows seen: depth e / n; three times that plus twelve
+    const uint64_t rank = (3ull * s.depth * e + n - 1) / n + 12;
+    const bool spec_here = p.spec && !last && 2 * rank <= s.depth;
+    SelectExtra sx = R.m8;
+    if (spec_here) { sx.spec_rank = (uint32_t)rank; sx.spec_tau = R.w.spec_tau; sx.spec_max = R.w.spec_max; }
+    OI_CHECK(oi_launch_select(ctx, R.PF, s.B, s.depth, /*compact=*/true, nullptr, nullptr, nullptr, s.depth, &sx));
+    R.spec_next = spec_here;
+    if (spec_here) {
+        { ProfScope ps(ctx, "spec"); } // (the profile's "spec" spans count the predictions made: an empty one, the select made it)
+        R.spec_any = true;
     }
-    if (spec_any) ++ctx->spec_searches;
-    PoolView PR = PF; // what the rescoring reads: the bf16 screen's final survivors (<= 4096 per query)
-    if (i8) {
-        // the int8 survivors' second-tier keys (in place) -- their two-plane scores from the residual plane, or their bf16 screen
-        // scores from the bf16 copy -- then the bf16 screen's final margin select over them, with that tier's uniform margin (mx.eps2:
-        // staging wrote the residual tier's there); the int8 tier's proven thresholds stay (the speculation check and the gated
-        // exact pipeline read them)
-        if (p.rescreen_residual) {
-            OI_CHECK(oi_launch_rescreen_residual(ctx, idx->screen_i8r.as<uint8_t>(), idx->screen_i8.as<uint8_t>(), n, dim, idx->doc_id_base,
-                                                 qi8, qf8, B, PF));
-        } else {
-            OI_CHECK(oi_launch_rescreen_bf16(ctx, idx->screen_copy.as<uint16_t>(), n, dim, idx->doc_id_base, qb.as<uint16_t>(), B, PF));
-        }
-        PoolView PB = PF; PB.tau_keys = nullptr; PB.n_segs = 0;
-        OI_CHECK(oi_launch_select(ctx, PB, B, depth, /*compact=*/true, nullptr, nullptr, nullptr, depth, &mx));
-        PR.carry_cap = 4096;
-        ctx->last_rescreen_cnt = pf_cnt; ctx->last_rescreen_b = B;
+    return OI_OK;
+}
+// The int8 route's second tier: the int8 survivors' second-tier keys (in place) -- their two-plane scores from the residual plane,
+// or their bf16 screen scores from the bf16 copy -- then the bf16 screen's final margin select over them, with that tier's uniform
+// margin (mx.eps2: staging wrote the residual tier's there); the int8 tier's proven thresholds stay (the speculation check and the
+// gated exact pipeline read them).
+int screen_second_tier(const Search &s, const Plan &p, ScreenRun &R) {
+    oi_index *idx = s.idx; oi_ctx *ctx = s.ctx;
+    if (p.rescreen_residual) {
+        OI_CHECK(oi_launch_rescreen_residual(ctx, idx->screen_i8r.as<uint8_t>(), idx->screen_i8.as<uint8_t>(), idx->n_docs, idx->dim,
+                                             idx->doc_id_base, R.qi8, R.qf8, s.B, R.PF));
+    } else {
+        OI_CHECK(oi_launch_rescreen_bf16(ctx, idx->screen_copy.as<uint16_t>(), idx->n_docs, idx->dim, idx->doc_id_base, R.qb, s.B, R.PF));
     }
+    PoolView PB = R.PF; PB.tau_keys = nullptr; PB.n_segs = 0;
+    OI_CHECK(oi_launch_select(ctx, PB, s.B, s.depth, /*compact=*/true, nullptr, nullptr, nullptr, s.depth, &R.mx));
+    ctx->last_rescreen_cnt = R.w.pf_cnt; ctx->last_rescreen_b = s.B;
+    return OI_OK;
+}
+// Finish: exact rescoring of the survivors, the final sorted select, then the gated exact pipeline over the pool's own view.
+int screen_finish(const Search &s, const Plan &p, const Pools &P, ScreenRun &R, const float *q, uint32_t Bp, uint64_t max_chunk) {
+    oi_index *idx = s.idx; oi_ctx *ctx = s.ctx;
+    PoolView PR = R.PF; // what the rescoring reads: the bf16 screen's final survivors (<= 4096 per query)
+    if (p.cos == CosRoute::screen_i8) PR.carry_cap = 4096;
     // (the check of the speculative thresholds against the proven final ones rides in the rescoring launch; the gated exact
     // pipeline is enqueued after it)
-    OI_CHECK(oi_launch_rescore(ctx, idx->rows, n, dim, idx->doc_id_base, s.qv, B, PR, RS,
+    OI_CHECK(oi_launch_rescore(ctx, idx->rows, idx->n_docs, idx->dim, idx->doc_id_base, s.qv, s.B, PR, R.RS,
                                idx->n_long ? idx->long_list.as<uint32_t>() : nullptr, idx->n_long,
-                               spec_any ? spec_max : nullptr, pf_tau, gate, ctx->spec_fail_host,
+                               R.spec_any ? R.w.spec_max : nullptr, R.w.pf_tau, R.w.gate, ctx->spec_fail_host,
                                // behind the residual tier about k' + 7 % survivors per query (10M x 768, k' = 1000: 1 072, at most
                                // 1 094): 72 workgroups take 1 152 in ONE trip, 64 send a few waves on a second (48 -> 40 us)
-                               i8 && p.rescreen_residual ? 72u : 0u));
-    RS.n_segs = 0;
-    OI_CHECK(oi_launch_select(ctx, RS, B, depth, false, s.cos_s, s.cos_d, s.cos_c, depth));
-    ctx->run_gate = ctx->last_screen_gate = gate;
-    const int rc = cosine_exact(s, P.cos, q, Bp, max_chunk, gate, pf_tau);
-    ctx->run_gate = nullptr;
-    return rc;
+                               p.rescreen_residual ? 72u : 0u));
+    R.RS.n_segs = 0;
+    OI_CHECK(oi_launch_select(ctx, R.RS, s.B, s.depth, false, s.cos_s, s.cos_d, s.cos_c, s.depth));
+    ctx->last_screen_gate = R.w.gate;
+    return cosine_exact(s, P.cos, q, Bp, max_chunk, R.w.gate, R.w.pf_tau);
+}
+// One screened search, stage by stage; `w`: its zeroed state words (ScreenWords::count of them).
+int cosine_screen(const Search &s, const Plan &p, const Pools &P, uint32_t *w, const float *q, uint32_t Bp, uint64_t max_chunk) {
+    ScreenRun R(ScreenWords(w, s.B, screen_segs(s.ctx)));
+    OI_CHECK(screen_open(s, p, P, R));
+    if (p.sample_rows) OI_CHECK(screen_sample(s, p, R));
+    for (size_t i = 0; i < p.screen_chunks.size(); ++i) OI_CHECK(screen_chunk(s, p, P, R, i));
+    if (R.spec_any) ++s.ctx->spec_searches;
+    if (p.cos == CosRoute::screen_i8) OI_CHECK(screen_second_tier(s, p, R));
+    return screen_finish(s, p, P, R, q, Bp, max_chunk);
 }
 
 int cosine_leg(const Search &s, const Plan &p, const Pools &P, uint32_t *screen_state) {
@@ -672,7 +748,7 @@ int search_lists_device(oi_index *idx, const float *d_qv, const uint32_t *d_qt, 
     Pools P;
     // the bf16 screen's state words (cosine_screen) ride in the same memset; the depth-sized segments of P.bm belong to the
     // workgroup-per-block kernel: no room is set aside for them otherwise
-    const size_t screen_words = (size_t)B * (6 + (size_t)ctx->num_cus) + 4;
+    const size_t screen_words = ScreenWords::count(B, screen_segs(ctx));
     uint32_t *screen_state = nullptr;
     OI_CHECK(prepare_pools(ctx, B, std::max<uint64_t>(p.cos_stride, idx->rows_bf16 ? 0ull : p.pf_stride), p.cos_stride, OI_MAX_DEPTH,
                            p.bm25 == BM25_TAAT ? idx->n_blocks : 0, depth, &P, screen_words, &screen_state));

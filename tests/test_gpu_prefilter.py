@@ -653,7 +653,7 @@ def test_fuzz_small_batches_through_the_screen(ctx, O):
 
 @pytest.mark.parametrize("n,dim,B,depth", [(300_000, 768, 64, 1000), (300_000, 768, 64, 100), (120_001, 384, 40, 10), (700_000, 768, 3, 100)])
 def test_speculative_thresholds_leave_the_lists_alone(ctx, O, n, dim, B, depth):
-    """Round 5: between chunks the screen may use a PREDICTED threshold (cosine_prefilter.hip, pf_spec_kernel), checked at the end
+    """Round 5: between chunks the screen may use a PREDICTED threshold (oi_select_rank.h: sel_spec_words), checked at the end
     against the proven one.  On a corpus in random order the check holds (no fallback) and the lists are those of the
     proven-threshold screen bit for bit -- both survivor sets hold the exact list, the scores are the same exact rescoring."""
     from openintel_amd import synth

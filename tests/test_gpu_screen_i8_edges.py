@@ -269,13 +269,13 @@ PK_F32 = re.compile(r"^\s*v_pk_(fma|mul|add)_f32\b.*$", re.M)
 @pytest.mark.skipif(not os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")), reason="no hipcc")
 def test_isa_rescreen_and_rescore_have_no_packed_f32():
     """pf_rescreen_kernel and pf_rescore_kernel (the non-MFMA kernels the screen runs beside another lane's MFMA stream) hold no
-    v_pk_{fma,mul,add}_f32 at all; i8s_stage_kernel and pf_stage_queries_kernel hold none with an op_sel:[...] operand (the
-    documented failing form; op_sel_hi alone is not it)."""
+    v_pk_{fma,mul,add}_f32 at all; i8s_stage_both_kernel (both staging bodies) and pf_stage_queries_kernel hold none with an
+    op_sel:[...] operand (the documented failing form; op_sel_hi alone is not it)."""
     i8 = _kernel_asm("cosine_screen_i8.hip")
     pf = _kernel_asm("cosine_prefilter.hip")
     for k in (_find(i8, "pf_rescreen_kernel"), _find(pf, "pf_rescore_kernel")):
         assert not PK_F32.findall(k), [m.group(0) for m in PK_F32.finditer(k)]
-    for k in (_find(i8, "i8s_stage_kernel"), _find(pf, "pf_stage_queries_kernel")):
+    for k in (_find(i8, "i8s_stage_both_kernel"), _find(pf, "pf_stage_queries_kernel")):
         bad = [m.group(0).strip() for m in PK_F32.finditer(k) if re.search(r"\bop_sel:\[", m.group(0))]
         assert not bad, bad
 

@@ -21,10 +21,9 @@ from test_gpu_screen_i8_edges import (OI_I8_CARRY, O, _forward, _index, _queries
 
 # Two cases the selects handle cannot be reached through oi_search, and have no test here:
 #  * fewer than r carried keys (sel_spec_words' `have == false`: the proven threshold is handed on as it is).  A prediction is asked
-#    for only when 2 r <= k' (search.hip: cosine_screen); the first chunk holds at least max(8 192, 8 k') rows and no threshold, so all
+#    for only when 2 r <= k' (search.hip: screen_chunk); the first chunk holds at least max(8 192, 8 k') rows and no threshold, so all
 #    its rows are keys; at most 1 024 of them are set aside as long rows and a filtered search, which could pass fewer, never
-#    speculates (plan_search).  So the select sees >= 7 168 valid keys, keeps at least the k' best, and k' >= 2 r > r.  In ablation
-#    builds OI_SPEC_KERNEL=2 runs pf_spec_kernel beside the select and reports, from the device, any word that differs.
+#    speculates (plan_search).  So the select sees >= 7 168 valid keys, keeps at least the k' best, and k' >= 2 r > r.
 #  * fewer than k' keys in play because of long rows: an index sets rows aside only when it has more than 4 096 and at most 1 024
 #    of them, so more than 3 072 >= k' stay in play (test_long_rows_set_aside runs the dead-slot mask at its limit of 1 000 rows).
 pytestmark = pytest.mark.gpu
