@@ -1300,55 +1300,110 @@ int stage_queries(oi_index *idx, const float *qv, const uint32_t *qt, const uint
     oi_ctx *ctx = idx->ctx;
     if (location == OI_DEVICE) { *out = QueryStage{qv, qt, qo, reinterpret_cast<const uint4 *>(filters)}; return OI_OK; }
     hipStream_t st = ctx->stream;
-    // one page-locked staging buffer, one DMA: [vectors | terms | offsets (| filters)], each part 16-byte aligned
     const uint32_t nt = qo[B];
-    const size_t vb = sizeof(float) * (size_t)B * idx->dim, tb = sizeof(uint32_t) * (size_t)(nt ? nt : 1), ob = sizeof(uint32_t) * ((size_t)B + 1);
-    const size_t off_t = (vb + 15) & ~(size_t)15, off_o = off_t + ((tb + 15) & ~(size_t)15);
-    const size_t off_f = off_o + ((ob + 15) & ~(size_t)15), total = filters ? off_f + sizeof(oi_doc_filter) * (size_t)B : off_o + ob;
+    const QueryLayout l(B, idx->dim, nt, filters != nullptr); // one page-locked staging buffer, one DMA
     DevBuf &a = ctx->buf("q_stage");
-    OI_CHECK(a.ensure(total));
-    OI_CHECK(ctx->pin_in.ensure(total));
+    OI_CHECK(a.ensure(l.total));
+    OI_CHECK(ctx->pin_in.ensure(l.total));
     uint8_t *h = ctx->pin_in.as<uint8_t>();
-    memcpy(h, qv, vb);
-    if (nt) memcpy(h + off_t, qt, sizeof(uint32_t) * nt);
-    memcpy(h + off_o, qo, ob);
-    if (filters) memcpy(h + off_f, filters, sizeof(oi_doc_filter) * (size_t)B);
-    OI_HIP_CHECK(hipMemcpyAsync(a.p, h, total, hipMemcpyHostToDevice, st));
+    memcpy(h, qv, l.vb);
+    if (nt) memcpy(h + l.off_t, qt, sizeof(uint32_t) * nt);
+    memcpy(h + l.off_o, qo, l.ob);
+    if (filters) memcpy(h + l.off_f, filters, sizeof(oi_doc_filter) * (size_t)B);
+    OI_HIP_CHECK(hipMemcpyAsync(a.p, h, l.total, hipMemcpyHostToDevice, st));
     uint8_t *d = a.as<uint8_t>();
-    *out = QueryStage{reinterpret_cast<const float *>(d), reinterpret_cast<const uint32_t *>(d + off_t),
-                      reinterpret_cast<const uint32_t *>(d + off_o), filters ? reinterpret_cast<const uint4 *>(d + off_f) : nullptr};
-    return OI_OK;
-}
-// A filtered search needs the index's doc attributes
-int check_filter_state(oi_index *idx, const oi_doc_filter *filters) {
-    if (filters && !idx->doc_attrs.p) { oi_set_error("filtered search: the index has no doc attributes (oi_index_set_doc_attrs)"); return OI_ERR_STATE; }
-    return OI_OK;
-}
-const uint2 *attrs_of(oi_index *idx, const QueryStage &q) { return q.filt ? idx->doc_attrs.as<uint2>() : nullptr; }
-// (graph keys: a filtered call differs from the unfiltered one by the filters pointer, folded into the call-kind word)
-uint64_t call_kind(uint64_t kind, const oi_doc_filter *filters) { return kind | ((uint64_t)(uintptr_t)filters << 8); }
-
-// The fused result block [scores K | docs K | counts B] (contiguous in HBM) to the caller's three host arrays: one DMA into
-// the context's page-locked buffer, the stream synchronised, three host copies.
-int results_to_host(oi_ctx *ctx, const float *d_block, size_t K, uint32_t B, float *scores_out, uint32_t *docs_out,
-                    uint32_t *counts_out) {
-    const size_t bytes = (2 * K + B) * 4;
-    OI_CHECK(ctx->pin_out.ensure(bytes));
-    OI_HIP_CHECK(hipMemcpyAsync(ctx->pin_out.p, d_block, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    OI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    const uint8_t *h = ctx->pin_out.as<uint8_t>();
-    memcpy(scores_out, h, K * 4);
-    memcpy(docs_out, h + K * 4, K * 4);
-    memcpy(counts_out, h + 2 * K * 4, (size_t)B * 4);
+    *out = QueryStage{reinterpret_cast<const float *>(d), reinterpret_cast<const uint32_t *>(d + l.off_t),
+                      reinterpret_cast<const uint32_t *>(d + l.off_o), filters ? reinterpret_cast<const uint4 *>(d + l.off_f) : nullptr};
     return OI_OK;
 }
 
-int check_search_args(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B,
-                      uint32_t depth) {
+int check_search_args(oi_index *idx, const float *qv, const uint32_t *qo, uint32_t B, uint32_t depth) {
     if (!idx) { oi_set_error("null index"); return OI_ERR_INVALID_ARG; }
-    OI_REQUIRE(qv && qo && (qt || true), "search: null query buffer");
+    OI_REQUIRE(qv && qo, "search: null query buffer");
     OI_REQUIRE(B >= 1 && B <= 4096, "search: n_queries=%u outside [1,4096]", B);
     OI_REQUIRE(depth >= 1 && depth <= OI_MAX_DEPTH, "search: depth=%u outside [1,%u]", depth, OI_MAX_DEPTH);
+    return OI_OK;
+}
+
+// What the five search impls open behind their argument checks: the context locked, the filter state checked (a filtered
+// search needs the index's doc attributes), the device set, the queries staged -- in that order.  attrs: the index's doc attributes for a filtered call, null otherwise.
+struct SearchCall {
+    oi_ctx *ctx = nullptr;
+    std::unique_lock<std::mutex> lock;
+    QueryStage q;
+    const uint2 *attrs = nullptr;
+};
+int open_search(SearchCall &c, oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B, int location,
+                const oi_doc_filter *filters) {
+    c.ctx = idx->ctx;
+    c.lock = std::unique_lock<std::mutex>(c.ctx->mu);
+    if (filters && !idx->doc_attrs.p) { oi_set_error("filtered search: the index has no doc attributes (oi_index_set_doc_attrs)"); return OI_ERR_STATE; }
+    OI_HIP_CHECK(hipSetDevice(c.ctx->device));
+    OI_CHECK(stage_queries(idx, qv, qt, qo, B, location, &c.q, filters));
+    c.attrs = c.q.filt ? idx->doc_attrs.as<uint2>() : nullptr;
+    return OI_OK;
+}
+
+// The six arrays of one search's two ranked lists, over either of their two contiguous layouts (L = B * depth); in both the
+// BM25 counts follow the cosine counts.
+struct SearchLists {
+    float *cos_s;
+    uint32_t *cos_d, *cos_c;
+    float *bm_s;
+    uint32_t *bm_d, *bm_c;
+    // [cos scores L | cos docs L | bm25 scores L | bm25 docs L | cos counts B | bm25 counts B]
+    static size_t block_bytes(uint32_t B, uint32_t depth) { return (size_t)B * depth * 16 + (size_t)B * 8; }
+    static SearchLists block(void *p, uint32_t B, uint32_t depth) {
+        const size_t L = (size_t)B * depth;
+        float *s = static_cast<float *>(p);
+        uint32_t *u = static_cast<uint32_t *>(p);
+        return {s, u + L, u + 4 * L, s + 2 * L, u + 3 * L, u + 4 * L + B};
+    }
+    // the exchange format [scores 2L | docs 2L | counts 2B] (cosine first in each): OI_PACKED_WORDS(B, depth) words
+    static size_t packed_bytes(uint32_t B, uint32_t depth) { return (size_t)OI_PACKED_WORDS(B, depth) * 4; }
+    static SearchLists packed(uint32_t *p, uint32_t B, uint32_t depth) {
+        const size_t L = (size_t)B * depth;
+        float *s = reinterpret_cast<float *>(p);
+        return {s, p + 2 * L, p + 4 * L, s + L, p + 3 * L, p + 4 * L + B};
+    }
+    int clear_counts(uint32_t B, hipStream_t st) const {
+        OI_HIP_CHECK(hipMemsetAsync(cos_c, 0, (size_t)B * 8, st));
+        return OI_OK;
+    }
+    int run(oi_index *idx, const SearchCall &c, uint32_t B, uint32_t depth) const {
+        return search_lists_device(idx, c.q.qv, c.q.qt, c.q.qo, B, depth, cos_s, cos_d, cos_c, bm_s, bm_d, bm_c, c.q.filt, c.attrs);
+    }
+};
+
+// The graph key of a captured search call (location == OI_DEVICE: c.q holds the caller's own pointers).  Words 0-6: the index,
+// the call kind with the filters pointer folded in (a filtered call differs from the unfiltered one by it), the query
+// pointers, B | depth, the first output pointer.  Word 7: every context / index setting that changes what the call launches --
+// add a new one HERE -- under the caller's w7_high; words 8 and 9 are the caller's.
+struct SearchKey { uint64_t w[10]; };
+SearchKey search_graph_key(oi_index *idx, const SearchCall &c, uint64_t kind, uint32_t B, uint32_t depth, const void *out0,
+                           uint32_t w7_high, uint64_t w8, uint64_t w9) {
+    const uint64_t mode = ((uint64_t)c.ctx->cosine_mode << 16) | ((uint64_t)idx->bm25_mode << 8) | (c.ctx->overlap_legs ? 1u : 0u);
+    return {{idx->uid, kind | ((uint64_t)(uintptr_t)c.q.filt << 8), (uint64_t)(uintptr_t)c.q.qv, (uint64_t)(uintptr_t)c.q.qt,
+             (uint64_t)(uintptr_t)c.q.qo, ((uint64_t)B << 32) | depth, (uint64_t)(uintptr_t)out0, ((uint64_t)w7_high << 32) | mode, w8, w9}};
+}
+
+// A result block in HBM to the caller's host arrays (null ones skipped): one DMA into the context's page-locked buffer, the
+// stream synchronised, host copies.
+int results_to_host(oi_ctx *ctx, const ResultBlock &r, float *scores_out, uint32_t *docs_out, uint32_t *counts_out,
+                    uint32_t *dup_out = nullptr) {
+    OI_CHECK(ctx->pin_out.ensure(r.bytes()));
+    OI_HIP_CHECK(hipMemcpyAsync(ctx->pin_out.p, r.scores, r.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+    OI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    r.at(ctx->pin_out.p).to_arrays(scores_out, docs_out, counts_out, dup_out);
+    return OI_OK;
+}
+// ... the same straight into the caller's arrays, three DMAs and a synchronise (oi_rrf_fuse, oi_merge_lists, oi_fuse_packed:
+// calls that make no overflow check)
+int results_to_host_direct(oi_ctx *ctx, const ResultBlock &r, float *scores_out, uint32_t *docs_out, uint32_t *counts_out) {
+    OI_HIP_CHECK(hipMemcpyAsync(scores_out, r.scores, r.K * 4, hipMemcpyDeviceToHost, ctx->stream));
+    OI_HIP_CHECK(hipMemcpyAsync(docs_out, r.docs, r.K * 4, hipMemcpyDeviceToHost, ctx->stream));
+    OI_HIP_CHECK(hipMemcpyAsync(counts_out, r.counts, (size_t)r.B * 4, hipMemcpyDeviceToHost, ctx->stream));
+    OI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return OI_OK;
 }
 
@@ -1357,35 +1412,27 @@ int check_search_args(oi_index *idx, const float *qv, const uint32_t *qt, const 
 static int search_lists_impl(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B,
                              uint32_t depth, int location, float *cos_s, uint32_t *cos_d, uint32_t *cos_c,
                              float *bm_s, uint32_t *bm_d, uint32_t *bm_c, const oi_doc_filter *filters) {
-    OI_CHECK(check_search_args(idx, qv, qt, qo, B, depth));
+    OI_CHECK(check_search_args(idx, qv, qo, B, depth));
     OI_REQUIRE(cos_s && cos_d && cos_c && bm_s && bm_d && bm_c, "search_lists: null output buffer");
-    oi_ctx *ctx = idx->ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    OI_CHECK(check_filter_state(idx, filters));
-    OI_HIP_CHECK(hipSetDevice(ctx->device));
-    QueryStage q;
-    OI_CHECK(stage_queries(idx, qv, qt, qo, B, location, &q, filters));
-    if (location == OI_DEVICE)
-        return search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, cos_s, cos_d, cos_c, bm_s, bm_d, bm_c, q.filt, attrs_of(idx, q));
-    hipStream_t st = ctx->stream;
-    const size_t L = (size_t)B * depth;
-    DevBuf &o = ctx->buf("lists_out");
-    OI_CHECK(o.ensure(L * 16 + (size_t)B * 8 + 64));
-    float *d_cs = o.as<float>();
-    uint32_t *d_cd = reinterpret_cast<uint32_t *>(d_cs + L);
-    float *d_bs = reinterpret_cast<float *>(d_cd + L);
-    uint32_t *d_bd = reinterpret_cast<uint32_t *>(d_bs + L);
-    uint32_t *d_cc = d_bd + L, *d_bc = d_cc + B;
-    OI_HIP_CHECK(hipMemsetAsync(o.p, 0, L * 16 + (size_t)B * 8, st));
-    OI_CHECK(search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, d_cs, d_cd, d_cc, d_bs, d_bd, d_bc, q.filt, attrs_of(idx, q)));
-    OI_HIP_CHECK(hipMemcpyAsync(cos_s, d_cs, L * 4, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(cos_d, d_cd, L * 4, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(bm_s, d_bs, L * 4, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(bm_d, d_bd, L * 4, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(cos_c, d_cc, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(bm_c, d_bc, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    SearchCall c;
+    OI_CHECK(open_search(c, idx, qv, qt, qo, B, location, filters));
+    const SearchLists out{cos_s, cos_d, cos_c, bm_s, bm_d, bm_c};
+    if (location == OI_DEVICE) return out.run(idx, c, B, depth);
+    hipStream_t st = c.ctx->stream;
+    const size_t L = (size_t)B * depth, bytes = SearchLists::block_bytes(B, depth);
+    DevBuf &o = c.ctx->buf("lists_out");
+    OI_CHECK(o.ensure(bytes + 64));
+    const SearchLists d = SearchLists::block(o.p, B, depth);
+    OI_HIP_CHECK(hipMemsetAsync(o.p, 0, bytes, st));
+    OI_CHECK(d.run(idx, c, B, depth));
+    OI_HIP_CHECK(hipMemcpyAsync(out.cos_s, d.cos_s, L * 4, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipMemcpyAsync(out.cos_d, d.cos_d, L * 4, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipMemcpyAsync(out.bm_s, d.bm_s, L * 4, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipMemcpyAsync(out.bm_d, d.bm_d, L * 4, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipMemcpyAsync(out.cos_c, d.cos_c, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipMemcpyAsync(out.bm_c, d.bm_c, (size_t)B * 4, hipMemcpyDeviceToHost, st));
     OI_HIP_CHECK(hipStreamSynchronize(st));
-    return check_overflow_locked(ctx);
+    return check_overflow_locked(c.ctx);
 }
 extern "C" int oi_search_lists(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B,
                                uint32_t depth, int location, float *cos_s, uint32_t *cos_d, uint32_t *cos_c,
@@ -1409,23 +1456,18 @@ extern "C" int oi_rrf_fuse(oi_ctx *ctx, const uint32_t *docs_a, const uint32_t *
     if (location == OI_DEVICE)
         return oi_launch_rrf(ctx, docs_a, counts_a, docs_b, counts_b, B, depth, k, scores_out, docs_out, counts_out);
     hipStream_t st = ctx->stream;
-    const size_t L = (size_t)B * depth, K = (size_t)B * k;
+    const size_t L = (size_t)B * depth;
     DevBuf &w = ctx->buf("rrf_io");
-    OI_CHECK(w.ensure((2 * L + 2 * (size_t)B + 2 * K + B) * 4 + 64));
+    OI_CHECK(w.ensure((2 * L + 2 * (size_t)B) * 4 + ResultBlock::bytes(B, k) + 64));
     uint32_t *d_a = w.as<uint32_t>(), *d_b = d_a + L, *d_ca = d_b + L, *d_cb = d_ca + B;
-    float *d_so = reinterpret_cast<float *>(d_cb + B);
-    uint32_t *d_do = reinterpret_cast<uint32_t *>(d_so + K), *d_co = d_do + K;
+    const ResultBlock r(d_cb + B, B, k);
     OI_HIP_CHECK(hipMemcpyAsync(d_a, docs_a, L * 4, hipMemcpyHostToDevice, st));
     OI_HIP_CHECK(hipMemcpyAsync(d_b, docs_b, L * 4, hipMemcpyHostToDevice, st));
     OI_HIP_CHECK(hipMemcpyAsync(d_ca, counts_a, (size_t)B * 4, hipMemcpyHostToDevice, st));
     OI_HIP_CHECK(hipMemcpyAsync(d_cb, counts_b, (size_t)B * 4, hipMemcpyHostToDevice, st));
-    OI_HIP_CHECK(hipMemsetAsync(d_so, 0, (2 * K + B) * 4, st));
-    OI_CHECK(oi_launch_rrf(ctx, d_a, d_ca, d_b, d_cb, B, depth, k, d_so, d_do, d_co));
-    OI_HIP_CHECK(hipMemcpyAsync(scores_out, d_so, K * 4, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(docs_out, d_do, K * 4, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(counts_out, d_co, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipStreamSynchronize(st));
-    return OI_OK;
+    OI_HIP_CHECK(hipMemsetAsync(r.scores, 0, r.bytes(), st));
+    OI_CHECK(oi_launch_rrf(ctx, d_a, d_ca, d_b, d_cb, B, depth, k, r.scores, r.docs, r.counts));
+    return results_to_host_direct(ctx, r, scores_out, docs_out, counts_out);
 }
 
 extern "C" int oi_merge_lists(oi_ctx *ctx, const float *scores, const uint32_t *docs, const uint32_t *counts,
@@ -1451,72 +1493,56 @@ extern "C" int oi_merge_lists(oi_ctx *ctx, const float *scores, const uint32_t *
     OI_CHECK(pc.ensure(sizeof(uint32_t) * (size_t)B * (1 + n_shards)));
     PoolView pool{pk.as<uint64_t>(), pc.as<uint32_t>(), pc.as<uint32_t>() + B, nullptr, mstride, carry_cap,
                   depth, n_shards, n_shards, flag.as<uint32_t>()};
-    const size_t Lin = (size_t)n_shards * B * depth, Cin = (size_t)n_shards * B, L = (size_t)B * depth;
+    const size_t Lin = (size_t)n_shards * B * depth, Cin = (size_t)n_shards * B;
     if (location == OI_DEVICE) {
         OI_CHECK(oi_launch_lists_to_pool(ctx, scores, docs, counts, (uint64_t)B * depth, B, n_shards, B, depth, pool));
         return oi_launch_select(ctx, pool, B, depth, false, scores_out, docs_out, counts_out, depth);
     }
     DevBuf &w = ctx->buf("merge_io");
-    OI_CHECK(w.ensure((2 * Lin + Cin + 2 * L + B) * 4 + 64));
+    OI_CHECK(w.ensure((2 * Lin + Cin) * 4 + ResultBlock::bytes(B, depth) + 64));
     float *d_s = w.as<float>();
     uint32_t *d_d = reinterpret_cast<uint32_t *>(d_s + Lin), *d_c = d_d + Lin;
-    float *d_so = reinterpret_cast<float *>(d_c + Cin);
-    uint32_t *d_do = reinterpret_cast<uint32_t *>(d_so + L), *d_co = d_do + L;
+    const ResultBlock r(d_c + Cin, B, depth);
     OI_HIP_CHECK(hipMemcpyAsync(d_s, scores, Lin * 4, hipMemcpyHostToDevice, st));
     OI_HIP_CHECK(hipMemcpyAsync(d_d, docs, Lin * 4, hipMemcpyHostToDevice, st));
     OI_HIP_CHECK(hipMemcpyAsync(d_c, counts, Cin * 4, hipMemcpyHostToDevice, st));
-    OI_HIP_CHECK(hipMemsetAsync(d_so, 0, (2 * L + B) * 4, st));
+    OI_HIP_CHECK(hipMemsetAsync(r.scores, 0, r.bytes(), st));
     OI_CHECK(oi_launch_lists_to_pool(ctx, d_s, d_d, d_c, (uint64_t)B * depth, B, n_shards, B, depth, pool));
-    OI_CHECK(oi_launch_select(ctx, pool, B, depth, false, d_so, d_do, d_co, depth));
-    OI_HIP_CHECK(hipMemcpyAsync(scores_out, d_so, L * 4, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(docs_out, d_do, L * 4, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(counts_out, d_co, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipStreamSynchronize(st));
-    return OI_OK;
+    OI_CHECK(oi_launch_select(ctx, pool, B, depth, false, r.scores, r.docs, r.counts, depth));
+    return results_to_host_direct(ctx, r, scores_out, docs_out, counts_out);
 }
 
 static int search_impl(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B,
                        uint32_t depth, uint32_t k, int location, float *scores_out, uint32_t *docs_out,
                        uint32_t *counts_out, const oi_doc_filter *filters) {
-    OI_CHECK(check_search_args(idx, qv, qt, qo, B, depth));
+    OI_CHECK(check_search_args(idx, qv, qo, B, depth));
     OI_REQUIRE(k >= 1 && k <= OI_MAX_DEPTH, "search: k=%u outside [1,%u]", k, OI_MAX_DEPTH);
     OI_REQUIRE(scores_out && docs_out && counts_out, "search: null output buffer");
-    oi_ctx *ctx = idx->ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    OI_CHECK(check_filter_state(idx, filters));
-    OI_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    QueryStage q;
-    OI_CHECK(stage_queries(idx, qv, qt, qo, B, location, &q, filters));
-    const uint2 *attrs = attrs_of(idx, q);
-    const size_t L = (size_t)B * depth, K = (size_t)B * k;
+    SearchCall c;
+    OI_CHECK(open_search(c, idx, qv, qt, qo, B, location, filters));
+    oi_ctx *ctx = c.ctx;
     DevBuf &o = ctx->buf("search_lists");
-    OI_CHECK(o.ensure(L * 16 + (size_t)B * 8 + 64));
-    float *d_cs = o.as<float>();
-    uint32_t *d_cd = reinterpret_cast<uint32_t *>(d_cs + L);
-    float *d_bs = reinterpret_cast<float *>(d_cd + L);
-    uint32_t *d_bd = reinterpret_cast<uint32_t *>(d_bs + L);
-    uint32_t *d_cc = d_bd + L, *d_bc = d_cc + B;
+    OI_CHECK(o.ensure(SearchLists::block_bytes(B, depth) + 64));
+    const SearchLists l = SearchLists::block(o.p, B, depth);
+    auto lists = [&]() -> int {
+        OI_CHECK(l.clear_counts(B, ctx->stream));
+        return l.run(idx, c, B, depth);
+    };
     if (location == OI_DEVICE) {
-        const uint64_t key[10] = {idx->uid, call_kind(3, filters), (uint64_t)(uintptr_t)qv, (uint64_t)(uintptr_t)qt, (uint64_t)(uintptr_t)qo,
-                                  ((uint64_t)B << 32) | depth, (uint64_t)(uintptr_t)scores_out,
-                                  ((uint64_t)ctx->cosine_mode << 16) | ((uint64_t)idx->bm25_mode << 8) | (ctx->overlap_legs ? 1u : 0u),
-                                  ((uint64_t)idx->max_query_terms << 32) | k, (uint64_t)(uintptr_t)docs_out ^ ((uint64_t)(uintptr_t)counts_out << 1)};
-        return run_captured(ctx, key, [&]() -> int {
-            OI_HIP_CHECK(hipMemsetAsync(d_cc, 0, (size_t)B * 8, ctx->stream));
-            OI_CHECK(search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, d_cs, d_cd, d_cc, d_bs, d_bd, d_bc, q.filt, attrs));
-            return oi_launch_rrf(ctx, d_cd, d_cc, d_bd, d_bc, B, depth, k, scores_out, docs_out, counts_out);
+        const SearchKey key = search_graph_key(idx, c, 3, B, depth, scores_out, 0, ((uint64_t)idx->max_query_terms << 32) | k,
+                                               (uint64_t)(uintptr_t)docs_out ^ ((uint64_t)(uintptr_t)counts_out << 1));
+        return run_captured(ctx, key.w, [&]() -> int {
+            OI_CHECK(lists());
+            return oi_launch_rrf(ctx, l.cos_d, l.cos_c, l.bm_d, l.bm_c, B, depth, k, scores_out, docs_out, counts_out);
         });
     }
-    OI_HIP_CHECK(hipMemsetAsync(d_cc, 0, (size_t)B * 8, st));
-    OI_CHECK(search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, d_cs, d_cd, d_cc, d_bs, d_bd, d_bc, q.filt, attrs));
+    OI_CHECK(lists());
     DevBuf &f = ctx->buf("search_out");
-    OI_CHECK(f.ensure((2 * K + B) * 4 + 64));
-    float *d_so = f.as<float>();
-    uint32_t *d_do = reinterpret_cast<uint32_t *>(d_so + K), *d_co = d_do + K;
-    OI_HIP_CHECK(hipMemsetAsync(f.p, 0, (2 * K + B) * 4, st));
-    OI_CHECK(oi_launch_rrf(ctx, d_cd, d_cc, d_bd, d_bc, B, depth, k, d_so, d_do, d_co));
-    OI_CHECK(results_to_host(ctx, d_so, K, B, scores_out, docs_out, counts_out));
+    OI_CHECK(f.ensure(ResultBlock::bytes(B, k) + 64));
+    const ResultBlock r(f.p, B, k);
+    OI_HIP_CHECK(hipMemsetAsync(f.p, 0, r.bytes(), ctx->stream));
+    OI_CHECK(oi_launch_rrf(ctx, l.cos_d, l.cos_c, l.bm_d, l.bm_c, B, depth, k, r.scores, r.docs, r.counts));
+    OI_CHECK(results_to_host(ctx, r, scores_out, docs_out, counts_out));
     return check_overflow_locked(ctx);
 }
 extern "C" int oi_search(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo, uint32_t B,
@@ -1543,21 +1569,6 @@ static int check_collapse_state(const char *what, oi_index *idx) {
     if (!idx->rows && !idx->rows_bf16) { oi_set_error("%s: the index has no embeddings (oi_index_set_embeddings)", what); return OI_ERR_STATE; }
     return OI_OK;
 }
-// [scores K | docs K | counts B | dup K] (contiguous in HBM) to the caller's host arrays (scores_out / dup_out may be null)
-static int collapsed_to_host(oi_ctx *ctx, const float *d_block, size_t K, uint32_t B, float *scores_out, uint32_t *docs_out,
-                             uint32_t *counts_out, uint32_t *dup_out) {
-    const size_t bytes = (3 * K + B) * 4;
-    OI_CHECK(ctx->pin_out.ensure(bytes));
-    OI_HIP_CHECK(hipMemcpyAsync(ctx->pin_out.p, d_block, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    OI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    const uint8_t *h = ctx->pin_out.as<uint8_t>();
-    if (scores_out) memcpy(scores_out, h, K * 4);
-    memcpy(docs_out, h + K * 4, K * 4);
-    memcpy(counts_out, h + 2 * K * 4, (size_t)B * 4);
-    if (dup_out) memcpy(dup_out, h + (2 * K + B) * 4, K * 4);
-    return OI_OK;
-}
-
 extern "C" int oi_collapse_lists(oi_index *idx, const float *scores, const uint32_t *docs, const uint32_t *counts, uint32_t B,
                                  uint32_t depth, float threshold, uint32_t k, int location, float *scores_out, uint32_t *docs_out,
                                  uint32_t *counts_out, uint32_t *dup_counts_out) {
@@ -1573,18 +1584,18 @@ extern "C" int oi_collapse_lists(oi_index *idx, const float *scores, const uint3
     if (location == OI_DEVICE)
         return oi_launch_collapse(idx, scores, docs, counts, B, depth, threshold, k, scores_out, docs_out, counts_out, dup_counts_out);
     hipStream_t st = ctx->stream;
-    const size_t L = (size_t)B * depth, K = (size_t)B * k;
+    const size_t L = (size_t)B * depth;
     DevBuf &w = ctx->buf("collapse_io");
-    OI_CHECK(w.ensure((2 * L + B + 3 * K + B) * 4 + 64));
+    OI_CHECK(w.ensure((2 * L + B) * 4 + ResultBlock::bytes(B, k, true) + 64));
     uint32_t *d_d = w.as<uint32_t>(), *d_c = d_d + L;
-    float *d_s = reinterpret_cast<float *>(d_c + B), *d_so = d_s + L;
-    uint32_t *d_do = reinterpret_cast<uint32_t *>(d_so + K), *d_co = d_do + K, *d_dup = d_co + B;
+    float *d_s = reinterpret_cast<float *>(d_c + B);
+    const ResultBlock r(d_s + L, B, k, true);
     OI_HIP_CHECK(hipMemcpyAsync(d_d, docs, L * 4, hipMemcpyHostToDevice, st));
     OI_HIP_CHECK(hipMemcpyAsync(d_c, counts, (size_t)B * 4, hipMemcpyHostToDevice, st));
     if (scores) OI_HIP_CHECK(hipMemcpyAsync(d_s, scores, L * 4, hipMemcpyHostToDevice, st));
-    OI_HIP_CHECK(hipMemsetAsync(d_so, 0, (3 * K + B) * 4, st));
-    OI_CHECK(oi_launch_collapse(idx, scores ? d_s : nullptr, d_d, d_c, B, depth, threshold, k, scores ? d_so : nullptr, d_do, d_co, d_dup));
-    return collapsed_to_host(ctx, d_so, K, B, scores_out, docs_out, counts_out, dup_counts_out);
+    OI_HIP_CHECK(hipMemsetAsync(r.scores, 0, r.bytes(), st));
+    OI_CHECK(oi_launch_collapse(idx, scores ? d_s : nullptr, d_d, d_c, B, depth, threshold, k, scores ? r.scores : nullptr, r.docs, r.counts, r.dup));
+    return results_to_host(ctx, r, scores_out, docs_out, counts_out, dup_counts_out);
 }
 
 // oi_search_filtered(depth, k = pool) into a device buffer, then the collapse of that fused list
@@ -1595,49 +1606,35 @@ extern "C" int oi_search_collapsed(oi_index *idx, const float *qv, const uint32_
     OI_REQUIRE(k <= pool, "search_collapsed: k=%u exceeds pool=%u", k, pool);
     OI_REQUIRE(scores_out && docs_out && counts_out, "search_collapsed: null output buffer");
     OI_CHECK(check_collapse_state("search_collapsed", idx));
-    OI_CHECK(check_search_args(idx, qv, qt, qo, B, depth));
-    oi_ctx *ctx = idx->ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    OI_CHECK(check_filter_state(idx, filters));
-    OI_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    QueryStage q;
-    OI_CHECK(stage_queries(idx, qv, qt, qo, B, location, &q, filters));
-    const uint2 *attrs = attrs_of(idx, q);
-    const size_t L = (size_t)B * depth, P = (size_t)B * pool, K = (size_t)B * k;
+    OI_CHECK(check_search_args(idx, qv, qo, B, depth));
+    SearchCall c;
+    OI_CHECK(open_search(c, idx, qv, qt, qo, B, location, filters));
+    oi_ctx *ctx = c.ctx;
     DevBuf &o = ctx->buf("search_lists"), &pl = ctx->buf("collapse_pool");
-    OI_CHECK(o.ensure(L * 16 + (size_t)B * 8 + 64));
-    OI_CHECK(pl.ensure((2 * P + B) * 4 + 64));
-    float *d_cs = o.as<float>();
-    uint32_t *d_cd = reinterpret_cast<uint32_t *>(d_cs + L);
-    float *d_bs = reinterpret_cast<float *>(d_cd + L);
-    uint32_t *d_bd = reinterpret_cast<uint32_t *>(d_bs + L);
-    uint32_t *d_cc = d_bd + L, *d_bc = d_cc + B;
-    float *d_ps = pl.as<float>(); // the fused pool-list: it never leaves the device
-    uint32_t *d_pd = reinterpret_cast<uint32_t *>(d_ps + P), *d_pc = d_pd + P;
+    OI_CHECK(o.ensure(SearchLists::block_bytes(B, depth) + 64));
+    OI_CHECK(pl.ensure(ResultBlock::bytes(B, pool) + 64));
+    const SearchLists l = SearchLists::block(o.p, B, depth);
+    const ResultBlock fused(pl.p, B, pool); // the fused pool-list: it never leaves the device
     auto body = [&](float *so, uint32_t *dd, uint32_t *co, uint32_t *dup) -> int {
-        OI_HIP_CHECK(hipMemsetAsync(d_cc, 0, (size_t)B * 8, ctx->stream));
-        OI_CHECK(search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, d_cs, d_cd, d_cc, d_bs, d_bd, d_bc, q.filt, attrs));
-        OI_CHECK(oi_launch_rrf(ctx, d_cd, d_cc, d_bd, d_bc, B, depth, pool, d_ps, d_pd, d_pc));
-        return oi_launch_collapse(idx, d_ps, d_pd, d_pc, B, pool, threshold, k, so, dd, co, dup);
+        OI_CHECK(l.clear_counts(B, ctx->stream));
+        OI_CHECK(l.run(idx, c, B, depth));
+        OI_CHECK(oi_launch_rrf(ctx, l.cos_d, l.cos_c, l.bm_d, l.bm_c, B, depth, pool, fused.scores, fused.docs, fused.counts));
+        return oi_launch_collapse(idx, fused.scores, fused.docs, fused.counts, B, pool, threshold, k, so, dd, co, dup);
     };
     if (location == OI_DEVICE) {
         uint32_t tbits;
         memcpy(&tbits, &threshold, 4);
-        const uint64_t key[10] = {idx->uid, call_kind(5, filters), (uint64_t)(uintptr_t)qv, (uint64_t)(uintptr_t)qt, (uint64_t)(uintptr_t)qo,
-                                  ((uint64_t)B << 32) | depth, (uint64_t)(uintptr_t)scores_out,
-                                  ((uint64_t)tbits << 32) | ((uint64_t)ctx->cosine_mode << 16) | ((uint64_t)idx->bm25_mode << 8) | (ctx->overlap_legs ? 1u : 0u),
-                                  ((uint64_t)idx->max_query_terms << 32) | ((uint64_t)pool << 16) | k,
-                                  (uint64_t)(uintptr_t)docs_out ^ ((uint64_t)(uintptr_t)counts_out << 1) ^ ((uint64_t)(uintptr_t)dup_counts_out << 2)};
-        return run_captured(ctx, key, [&]() -> int { return body(scores_out, docs_out, counts_out, dup_counts_out); });
+        const SearchKey key = search_graph_key(
+            idx, c, 5, B, depth, scores_out, tbits, ((uint64_t)idx->max_query_terms << 32) | ((uint64_t)pool << 16) | k,
+            (uint64_t)(uintptr_t)docs_out ^ ((uint64_t)(uintptr_t)counts_out << 1) ^ ((uint64_t)(uintptr_t)dup_counts_out << 2));
+        return run_captured(ctx, key.w, [&]() -> int { return body(scores_out, docs_out, counts_out, dup_counts_out); });
     }
     DevBuf &f = ctx->buf("collapse_out");
-    OI_CHECK(f.ensure((3 * K + B) * 4 + 64));
-    float *d_so = f.as<float>();
-    uint32_t *d_do = reinterpret_cast<uint32_t *>(d_so + K), *d_co = d_do + K, *d_dup = d_co + B;
-    OI_HIP_CHECK(hipMemsetAsync(f.p, 0, (3 * K + B) * 4, st));
-    OI_CHECK(body(d_so, d_do, d_co, d_dup));
-    OI_CHECK(collapsed_to_host(ctx, d_so, K, B, scores_out, docs_out, counts_out, dup_counts_out));
+    OI_CHECK(f.ensure(ResultBlock::bytes(B, k, true) + 64));
+    const ResultBlock r(f.p, B, k, true);
+    OI_HIP_CHECK(hipMemsetAsync(f.p, 0, r.bytes(), ctx->stream));
+    OI_CHECK(body(r.scores, r.docs, r.counts, r.dup));
+    OI_CHECK(results_to_host(ctx, r, scores_out, docs_out, counts_out, dup_counts_out));
     return check_overflow_locked(ctx);
 }
 
@@ -2036,38 +2033,27 @@ extern "C" int oi_screen_probe(oi_index *idx, const float *query_vecs, uint32_t 
 // ---------------------------------------------------------------- packed multi-GPU exchange
 static int search_lists_packed_impl(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo,
                                     uint32_t B, uint32_t depth, int location, uint32_t *packed_out, const oi_doc_filter *filters) {
-    OI_CHECK(check_search_args(idx, qv, qt, qo, B, depth));
+    OI_CHECK(check_search_args(idx, qv, qo, B, depth));
     OI_REQUIRE(packed_out, "search_lists_packed: null output buffer");
-    oi_ctx *ctx = idx->ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    OI_CHECK(check_filter_state(idx, filters));
-    OI_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    QueryStage q;
-    OI_CHECK(stage_queries(idx, qv, qt, qo, B, location, &q, filters));
-    const size_t L = (size_t)B * depth, W = (size_t)OI_PACKED_WORDS(B, depth);
+    SearchCall c;
+    OI_CHECK(open_search(c, idx, qv, qt, qo, B, location, filters));
+    oi_ctx *ctx = c.ctx;
+    const size_t bytes = SearchLists::packed_bytes(B, depth);
     uint32_t *d_out = packed_out;
     if (location != OI_DEVICE) {
         DevBuf &o = ctx->buf("packed_out");
-        OI_CHECK(o.ensure(W * 4));
+        OI_CHECK(o.ensure(bytes));
         d_out = o.as<uint32_t>();
     }
-    float *sc = reinterpret_cast<float *>(d_out);
-    uint32_t *dc = d_out + 2 * L, *cn = d_out + 4 * L;
+    const SearchLists l = SearchLists::packed(d_out, B, depth);
     auto body = [&]() -> int {
-        OI_HIP_CHECK(hipMemsetAsync(d_out + 4 * L, 0, (size_t)B * 8, ctx->stream)); // counts
-        return search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, sc, dc, cn, sc + L, dc + L, cn + B, q.filt, attrs_of(idx, q));
+        OI_CHECK(l.clear_counts(B, ctx->stream));
+        return l.run(idx, c, B, depth);
     };
-    if (location == OI_DEVICE) {
-        const uint64_t key[10] = {idx->uid, call_kind(1, filters), (uint64_t)(uintptr_t)qv, (uint64_t)(uintptr_t)qt, (uint64_t)(uintptr_t)qo,
-                                  ((uint64_t)B << 32) | depth, (uint64_t)(uintptr_t)packed_out,
-                                  ((uint64_t)ctx->cosine_mode << 16) | ((uint64_t)idx->bm25_mode << 8) | (ctx->overlap_legs ? 1u : 0u),
-                                  idx->max_query_terms, 0};
-        return run_captured(ctx, key, body);
-    }
+    if (location == OI_DEVICE) return run_captured(ctx, search_graph_key(idx, c, 1, B, depth, packed_out, 0, idx->max_query_terms, 0).w, body);
     OI_CHECK(body());
-    OI_HIP_CHECK(hipMemcpyAsync(packed_out, d_out, W * 4, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipStreamSynchronize(st));
+    OI_HIP_CHECK(hipMemcpyAsync(packed_out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    OI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return check_overflow_locked(ctx);
 }
 extern "C" int oi_search_lists_packed(oi_index *idx, const float *qv, const uint32_t *qt, const uint32_t *qo,
@@ -2084,7 +2070,7 @@ extern "C" int oi_search_lists_packed_filtered(oi_index *idx, const float *qv, c
 static int fuse_packed_device(oi_ctx *ctx, const uint32_t *d_in, uint32_t n_shards, uint32_t B, uint32_t depth, uint32_t k,
                               float *o_s, uint32_t *o_d, uint32_t *o_c) {
     hipStream_t st = ctx->stream;
-    const size_t L = (size_t)B * depth, W = (size_t)OI_PACKED_WORDS(B, depth);
+    const size_t W = (size_t)OI_PACKED_WORDS(B, depth);
     DevBuf &flag = ctx->buf("state_flag");
     if (!flag.p) {
         OI_CHECK(flag.ensure(16));
@@ -2095,18 +2081,25 @@ static int fuse_packed_device(oi_ctx *ctx, const uint32_t *d_in, uint32_t n_shar
     DevBuf &pk = ctx->buf("merge_pool"), &pc = ctx->buf("merge_counts"), &ml = ctx->buf("merged_lists");
     OI_CHECK(pk.ensure(sizeof(uint64_t) * (size_t)2 * B * mstride));
     OI_CHECK(pc.ensure(sizeof(uint32_t) * (size_t)2 * B * (1 + n_shards)));
-    OI_CHECK(ml.ensure((4 * L + 2 * (size_t)B) * 4));
+    OI_CHECK(ml.ensure(SearchLists::packed_bytes(B, depth)));
     PoolView pool{pk.as<uint64_t>(), pc.as<uint32_t>(), pc.as<uint32_t>() + 2 * (size_t)B, nullptr, mstride,
                   carry_cap, depth, n_shards, n_shards, flag.as<uint32_t>()};
-    float *m_s = ml.as<float>();                       // [2][B][depth]
-    uint32_t *m_d = ml.as<uint32_t>() + 2 * L;          // [2][B][depth]
-    uint32_t *m_c = m_d + 2 * L;                        // [2][B]
-    // scores[2][B][depth] is [2B][depth]: both lists of every query are merged by ONE pair of launches
-    // (2B virtual queries; list 0 = cosine, 1 = BM25)
-    OI_CHECK(oi_launch_lists_to_pool(ctx, reinterpret_cast<const float *>(d_in), d_in + 2 * L, d_in + 4 * L, W, W,
-                                     n_shards, 2 * B, depth, pool));
-    OI_CHECK(oi_launch_select(ctx, pool, 2 * B, depth, false, m_s, m_d, m_c, depth));
-    return oi_launch_rrf(ctx, m_d, m_c, m_d + L, m_c + B, B, depth, k, o_s, o_d, o_c);
+    // the first shard's lists (read only) and the merged lists, both in the packed layout: scores[2][B][depth] is [2B][depth], so
+    // both lists of every query are merged by ONE pair of launches (2B virtual queries; list 0 = cosine, 1 = BM25)
+    const SearchLists in = SearchLists::packed(const_cast<uint32_t *>(d_in), B, depth), m = SearchLists::packed(ml.as<uint32_t>(), B, depth);
+    OI_CHECK(oi_launch_lists_to_pool(ctx, in.cos_s, in.cos_d, in.cos_c, W, W, n_shards, 2 * B, depth, pool));
+    OI_CHECK(oi_launch_select(ctx, pool, 2 * B, depth, false, m.cos_s, m.cos_d, m.cos_c, depth));
+    return oi_launch_rrf(ctx, m.cos_d, m.cos_c, m.bm_d, m.bm_c, B, depth, k, o_s, o_d, o_c);
+}
+// ... into the zeroed result block of the "fuse_out" workspace: what the host tails of oi_fuse_packed and oi_search_sharded share.
+// They part at the copy out (three DMAs and no overflow check / one DMA and the check); oi_pipeline_submit's tail: pipeline.hip.
+static int fuse_packed_to_block(oi_ctx *ctx, const uint32_t *d_in, uint32_t n_shards, uint32_t B, uint32_t depth, uint32_t k,
+                                ResultBlock *out) {
+    DevBuf &fo = ctx->buf("fuse_out");
+    OI_CHECK(fo.ensure(ResultBlock::bytes(B, k) + 64));
+    *out = ResultBlock(fo.p, B, k);
+    OI_HIP_CHECK(hipMemsetAsync(fo.p, 0, out->bytes(), ctx->stream));
+    return fuse_packed_device(ctx, d_in, n_shards, B, depth, k, out->scores, out->docs, out->counts);
 }
 
 extern "C" int oi_fuse_packed(oi_ctx *ctx, const uint32_t *packed_all, uint32_t n_shards, uint32_t B, uint32_t depth,
@@ -2126,21 +2119,13 @@ extern "C" int oi_fuse_packed(oi_ctx *ctx, const uint32_t *packed_all, uint32_t 
             return fuse_packed_device(ctx, packed_all, n_shards, B, depth, k, scores_out, docs_out, counts_out);
         });
     }
-    hipStream_t st = ctx->stream;
-    const size_t W = (size_t)OI_PACKED_WORDS(B, depth), K = (size_t)B * k;
-    DevBuf &in = ctx->buf("packed_in"), &fo = ctx->buf("fuse_out");
-    OI_CHECK(in.ensure(W * 4 * n_shards));
-    OI_CHECK(fo.ensure((2 * K + B) * 4 + 64));
-    OI_HIP_CHECK(hipMemcpyAsync(in.p, packed_all, W * 4 * n_shards, hipMemcpyHostToDevice, st));
-    float *o_s = fo.as<float>();
-    uint32_t *o_d = reinterpret_cast<uint32_t *>(o_s + K), *o_c = o_d + K;
-    OI_HIP_CHECK(hipMemsetAsync(o_s, 0, (2 * K + B) * 4, st));
-    OI_CHECK(fuse_packed_device(ctx, in.as<uint32_t>(), n_shards, B, depth, k, o_s, o_d, o_c));
-    OI_HIP_CHECK(hipMemcpyAsync(scores_out, o_s, K * 4, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(docs_out, o_d, K * 4, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(counts_out, o_c, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipStreamSynchronize(st));
-    return OI_OK;
+    const size_t in_bytes = SearchLists::packed_bytes(B, depth) * n_shards;
+    DevBuf &in = ctx->buf("packed_in");
+    OI_CHECK(in.ensure(in_bytes));
+    OI_HIP_CHECK(hipMemcpyAsync(in.p, packed_all, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    ResultBlock r(nullptr, B, k);
+    OI_CHECK(fuse_packed_to_block(ctx, in.as<uint32_t>(), n_shards, B, depth, k, &r));
+    return results_to_host_direct(ctx, r, scores_out, docs_out, counts_out);
 }
 
 // ---------------------------------------------------------------- the sharded query with RCCL inside (comm.hip)
@@ -2211,38 +2196,28 @@ extern "C" int oi_index_finalize_sharded(oi_index *idx, oi_comm *comm) {
 static int search_sharded_impl(oi_index *idx, oi_comm *comm, const float *qv, const uint32_t *qt, const uint32_t *qo,
                                uint32_t B, uint32_t depth, uint32_t k, int location, float *scores_out,
                                uint32_t *docs_out, uint32_t *counts_out, const oi_doc_filter *filters) {
-    OI_CHECK(check_search_args(idx, qv, qt, qo, B, depth));
+    OI_CHECK(check_search_args(idx, qv, qo, B, depth));
     if (!comm) { oi_set_error("null communicator"); return OI_ERR_INVALID_ARG; }
     OI_REQUIRE(k >= 1 && k <= OI_MAX_DEPTH, "search: k=%u outside [1,%u]", k, OI_MAX_DEPTH);
     OI_REQUIRE(scores_out && docs_out && counts_out, "search: null output buffer");
-    oi_ctx *ctx = idx->ctx;
-    OI_REQUIRE(comm->ctx == ctx, "search_sharded: the communicator belongs to another context");
-    std::lock_guard<std::mutex> g(ctx->mu);
-    OI_CHECK(check_filter_state(idx, filters));
-    OI_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    QueryStage q;
-    OI_CHECK(stage_queries(idx, qv, qt, qo, B, location, &q, filters));
-    const size_t L = (size_t)B * depth, W = (size_t)OI_PACKED_WORDS(B, depth), K = (size_t)B * k;
+    OI_REQUIRE(comm->ctx == idx->ctx, "search_sharded: the communicator belongs to another context");
+    SearchCall c;
+    OI_CHECK(open_search(c, idx, qv, qt, qo, B, location, filters));
+    oi_ctx *ctx = c.ctx;
+    const size_t bytes = SearchLists::packed_bytes(B, depth);
     DevBuf &pk = ctx->buf("sharded_packed"), &fl = ctx->buf("sharded_flat");
-    OI_CHECK(pk.ensure(W * 4));
-    OI_CHECK(fl.ensure(W * 4 * comm->world));
-    uint32_t *d_p = pk.as<uint32_t>();
-    OI_HIP_CHECK(hipMemsetAsync(d_p + 4 * L, 0, (size_t)B * 8, st)); // counts
-    float *sc = reinterpret_cast<float *>(d_p);
-    uint32_t *dc = d_p + 2 * L, *cn = d_p + 4 * L;
-    OI_CHECK(search_lists_device(idx, q.qv, q.qt, q.qo, B, depth, sc, dc, cn, sc + L, dc + L, cn + B, q.filt, attrs_of(idx, q)));
+    OI_CHECK(pk.ensure(bytes));
+    OI_CHECK(fl.ensure(bytes * comm->world));
+    const SearchLists l = SearchLists::packed(pk.as<uint32_t>(), B, depth);
+    OI_CHECK(l.clear_counts(B, ctx->stream));
+    OI_CHECK(l.run(idx, c, B, depth));
     // the ONE exchange per batch: every rank's packed lists to every rank (1 MB per rank at B=64, k'=1000)
-    OI_CHECK(oi_rccl_all_gather_u32(comm->nccl, d_p, fl.as<uint32_t>(), W, st));
+    OI_CHECK(oi_rccl_all_gather_u32(comm->nccl, pk.as<uint32_t>(), fl.as<uint32_t>(), bytes / 4, ctx->stream));
     if (location == OI_DEVICE)
         return fuse_packed_device(ctx, fl.as<uint32_t>(), comm->world, B, depth, k, scores_out, docs_out, counts_out);
-    DevBuf &fo = ctx->buf("fuse_out");
-    OI_CHECK(fo.ensure((2 * K + B) * 4 + 64));
-    float *o_s = fo.as<float>();
-    uint32_t *o_d = reinterpret_cast<uint32_t *>(o_s + K), *o_c = o_d + K;
-    OI_HIP_CHECK(hipMemsetAsync(o_s, 0, (2 * K + B) * 4, st));
-    OI_CHECK(fuse_packed_device(ctx, fl.as<uint32_t>(), comm->world, B, depth, k, o_s, o_d, o_c));
-    OI_CHECK(results_to_host(ctx, o_s, K, B, scores_out, docs_out, counts_out));
+    ResultBlock r(nullptr, B, k);
+    OI_CHECK(fuse_packed_to_block(ctx, fl.as<uint32_t>(), comm->world, B, depth, k, &r));
+    OI_CHECK(results_to_host(ctx, r, scores_out, docs_out, counts_out));
     return check_overflow_locked(ctx);
 }
 extern "C" int oi_search_sharded(oi_index *idx, oi_comm *comm, const float *qv, const uint32_t *qt, const uint32_t *qo,

@@ -244,6 +244,43 @@ int search_lists_device(oi_index *idx, const float *d_qv, const uint32_t *d_qt, 
                         const uint4 *d_filt = nullptr, const uint2 *d_attrs = nullptr);
 void oi_spec_take_failure(oi_ctx *ctx); // a failed speculation check seen since the last look: back off
 
+// The two layouts the search entry points of api.hip share with pipeline.hip, each written once.
+// Staged host queries [vectors | terms | offsets (| filters)], each part 16-byte aligned; nt = the batch's term count (qo[B]).
+struct QueryLayout {
+    size_t vb, ob, off_t, off_o, off_f, total; // bytes of the vectors / offsets, where the later parts start, bytes in all
+    QueryLayout(uint32_t B, uint32_t dim, size_t nt, bool filters) {
+        const auto r16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+        vb = sizeof(float) * (size_t)B * dim;
+        ob = sizeof(uint32_t) * ((size_t)B + 1);
+        off_t = r16(vb);
+        off_o = off_t + r16(sizeof(uint32_t) * (nt ? nt : 1));
+        off_f = off_o + r16(ob);
+        total = filters ? off_f + sizeof(oi_doc_filter) * (size_t)B : off_o + ob;
+    }
+};
+// The fused result block [scores K | docs K | counts B (| dup K)], K = B * k, contiguous in device or page-locked memory.
+struct ResultBlock {
+    float *scores;
+    uint32_t *docs, *counts, *dup; // dup: null without the fourth section
+    size_t K;
+    uint32_t B, k;
+    ResultBlock(void *p, uint32_t B_, uint32_t k_, bool with_dup = false) : scores(static_cast<float *>(p)), K((size_t)B_ * k_), B(B_), k(k_) {
+        docs = reinterpret_cast<uint32_t *>(scores + K);
+        counts = docs + K;
+        dup = with_dup ? counts + B : nullptr;
+    }
+    ResultBlock at(void *p) const { return ResultBlock(p, B, k, dup != nullptr); } // the same sections over another buffer
+    static size_t bytes(uint32_t B, uint32_t k, bool with_dup = false) { return ((with_dup ? 3 : 2) * (size_t)B * k + B) * 4; }
+    size_t bytes() const { return ((dup ? 3 : 2) * K + B) * 4; }
+    // a block in host memory to the caller's arrays (a null array is skipped)
+    void to_arrays(float *scores_out, uint32_t *docs_out, uint32_t *counts_out, uint32_t *dup_out = nullptr) const {
+        if (scores_out) memcpy(scores_out, scores, K * 4);
+        if (docs_out) memcpy(docs_out, docs, K * 4);
+        if (counts_out) memcpy(counts_out, counts, (size_t)B * 4);
+        if (dup && dup_out) memcpy(dup_out, dup, K * 4);
+    }
+};
+
 // ---------------------------------------------------------------- kernels (host launchers)
 // lexicon.hip
 int oi_launch_lexicon(oi_ctx *ctx, const uint8_t *d_blob, const uint64_t *d_offsets, uint64_t n,

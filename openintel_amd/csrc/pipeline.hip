@@ -142,12 +142,7 @@ void free_slot(Slot &s, bool own_flat) {
 int retire(oi_pipeline *p, Slot &s) {
     if (!s.ticket) return OI_OK;
     OI_HIP_CHECK(hipEventSynchronize(s.fused));
-    if (s.location != OI_DEVICE) {
-        const size_t K = (size_t)s.B * p->k;
-        memcpy(s.h_scores, s.out_pin, K * 4);
-        memcpy(s.h_docs, s.out_pin + K * 4, K * 4);
-        memcpy(s.h_counts, s.out_pin + 2 * K * 4, (size_t)s.B * 4);
-    }
+    if (s.location != OI_DEVICE) ResultBlock(s.out_pin, s.B, p->k).to_arrays(s.h_scores, s.h_docs, s.h_counts);
     s.ticket = 0;
     return OI_OK;
 }
@@ -194,10 +189,8 @@ extern "C" int oi_pipeline_create(oi_index *idx, oi_comm *comm, uint32_t lanes, 
     p->k = k;
     p->q_terms_max = max_query_terms;
     p->words = (size_t)OI_PACKED_WORDS(max_queries, depth);
-    const size_t vb = (sizeof(float) * (size_t)max_queries * idx->dim + 15) & ~(size_t)15;
-    const size_t tb = (sizeof(uint32_t) * (size_t)max_queries * max_query_terms + 15) & ~(size_t)15;
-    p->q_bytes = vb + tb + sizeof(uint32_t) * ((size_t)max_queries + 1);
-    p->out_bytes = (2 * (size_t)max_queries * k + max_queries) * 4;
+    p->q_bytes = QueryLayout(max_queries, idx->dim, (size_t)max_queries * max_query_terms, false).total; // the largest batch submit accepts
+    p->out_bytes = ResultBlock::bytes(max_queries, k);
     auto fail = [&](int rc) { destroy(p); return rc; };
 #define PL_HIP(expr)                                                                                            \
     do {                                                                                                        \
@@ -317,18 +310,17 @@ extern "C" int oi_pipeline_submit(oi_pipeline *p, const float *qv, const uint32_
         const uint32_t nt = qo[B];
         OI_REQUIRE(nt <= (uint64_t)p->B_max * p->q_terms_max, "pipeline submit: %u query terms exceed max_queries x max_query_terms", nt);
         OI_REQUIRE(nt == 0 || qt, "pipeline submit: null term buffer");
-        const size_t vb = sizeof(float) * (size_t)B * p->src->dim, tb = sizeof(uint32_t) * (size_t)(nt ? nt : 1), ob = sizeof(uint32_t) * ((size_t)B + 1);
-        const size_t off_t = (vb + 15) & ~(size_t)15, off_o = off_t + ((tb + 15) & ~(size_t)15), total = off_o + ob;
+        const QueryLayout l(B, p->src->dim, nt, false);
         // (the slot's previous batch has been scored long before its fusion finished; a host-input batch is only staged
         // over a slot whose lists are done: wait for that on the host -- n_slots batches back, normally long past)
         if (n >= p->slots.size()) OI_HIP_CHECK(hipEventSynchronize(s.lists_done));
-        memcpy(s.q_pin, qv, vb);
-        if (nt) memcpy(s.q_pin + off_t, qt, sizeof(uint32_t) * nt);
-        memcpy(s.q_pin + off_o, qo, ob);
-        OI_HIP_CHECK(hipMemcpyAsync(s.q_dev, s.q_pin, total, hipMemcpyHostToDevice, lst));
+        memcpy(s.q_pin, qv, l.vb);
+        if (nt) memcpy(s.q_pin + l.off_t, qt, sizeof(uint32_t) * nt);
+        memcpy(s.q_pin + l.off_o, qo, l.ob);
+        OI_HIP_CHECK(hipMemcpyAsync(s.q_dev, s.q_pin, l.total, hipMemcpyHostToDevice, lst));
         d_qv = reinterpret_cast<const float *>(s.q_dev);
-        d_qt = reinterpret_cast<const uint32_t *>(s.q_dev + off_t);
-        d_qo = reinterpret_cast<const uint32_t *>(s.q_dev + off_o);
+        d_qt = reinterpret_cast<const uint32_t *>(s.q_dev + l.off_t);
+        d_qo = reinterpret_cast<const uint32_t *>(s.q_dev + l.off_o);
     }
     // the shard's two lists, packed, on the lane
     const auto t1 = now();
@@ -337,17 +329,17 @@ extern "C" int oi_pipeline_submit(oi_pipeline *p, const float *qv, const uint32_
     OI_HIP_CHECK(hipEventRecord(s.lists_done, lst));
     // exchange + fusion on the fusing stream
     OI_HIP_CHECK(hipStreamWaitEvent(p->fuse_st, s.lists_done, 0));
-    const size_t W = (size_t)OI_PACKED_WORDS(B, p->depth), K = (size_t)B * p->k;
+    const size_t W = (size_t)OI_PACKED_WORDS(B, p->depth);
     if (p->comm) OI_CHECK(oi_rccl_all_gather_u32(p->comm->nccl, s.packed, s.flat, W, p->fuse_st)); // the ONE exchange of the batch
     const auto t3 = now();
     if (location == OI_DEVICE) {
         OI_CHECK(oi_fuse_packed(p->fuse_ctx, s.flat, p->world, B, p->depth, p->k, OI_DEVICE, scores_out, docs_out, counts_out));
     } else {
-        float *o_s = s.out_dev;
-        uint32_t *o_d = reinterpret_cast<uint32_t *>(o_s + K), *o_c = o_d + K;
-        OI_HIP_CHECK(hipMemsetAsync(o_s, 0, (2 * K + B) * 4, p->fuse_st));
-        OI_CHECK(oi_fuse_packed(p->fuse_ctx, s.flat, p->world, B, p->depth, p->k, OI_DEVICE, o_s, o_d, o_c));
-        OI_HIP_CHECK(hipMemcpyAsync(s.out_pin, o_s, (2 * K + B) * 4, hipMemcpyDeviceToHost, p->fuse_st));
+        // (api.hip's host tails fuse eagerly on their context's stream into its pinned buffer and synchronise; this one does not)
+        const ResultBlock r(s.out_dev, B, p->k);
+        OI_HIP_CHECK(hipMemsetAsync(r.scores, 0, r.bytes(), p->fuse_st));
+        OI_CHECK(oi_fuse_packed(p->fuse_ctx, s.flat, p->world, B, p->depth, p->k, OI_DEVICE, r.scores, r.docs, r.counts));
+        OI_HIP_CHECK(hipMemcpyAsync(s.out_pin, r.scores, r.bytes(), hipMemcpyDeviceToHost, p->fuse_st));
     }
     OI_HIP_CHECK(hipEventRecord(s.fused, p->fuse_st));
     if (p->trace) {
