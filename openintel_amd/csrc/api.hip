@@ -1015,6 +1015,35 @@ extern "C" int oi_internal_residual_plane(oi_index *idx, int drop, uint8_t *rows
     return OI_OK;
 }
 
+// Not part of the C ABI: the BM25 structures of a finalized index (or of a view of one), for the tests.  Always: the number of
+// postings, the windows per term and avgdl.  Copied to the host pointers that are not null: the postings as n_postings pairs
+// {u32 doc_in_block, f32 impact}, cell_start [vocab * n_win + 1], idf [vocab], the impact floors [vocab * OI_BM25_FLOOR_RANKS]
+// and doc_len [n_docs].  An index without a posting has no cell table (oi_bm25_stage_forward builds none, no kernel reads
+// one): every run is empty, cell_start is given as zeros.
+extern "C" int oi_internal_bm25_index(oi_index *idx, uint64_t *n_postings_out, uint32_t *n_win_out, float *avgdl_out, void *postings_out,
+                                      uint32_t *cell_start_out, float *idf_out, uint32_t *floors_out, uint32_t *doc_len_out) {
+    if (!idx) { oi_set_error("null index"); return OI_ERR_INVALID_ARG; }
+    oi_ctx *ctx = idx->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!idx->finalized) { oi_set_error("bm25 index: the index is not finalized"); return OI_ERR_STATE; }
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    OI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (n_postings_out) *n_postings_out = idx->n_postings;
+    if (n_win_out) *n_win_out = idx->n_win;
+    if (avgdl_out) *avgdl_out = idx->avgdl;
+    const size_t np = idx->n_postings, cells = (size_t)idx->vocab * idx->n_win + 1;
+    if (postings_out && np) OI_HIP_CHECK(hipMemcpy(postings_out, idx->postings.p, 8 * np, hipMemcpyDeviceToHost));
+    if (cell_start_out) {
+        if (np) OI_HIP_CHECK(hipMemcpy(cell_start_out, idx->cell_start.p, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost));
+        else memset(cell_start_out, 0, sizeof(uint32_t) * cells);
+    }
+    if (idf_out) OI_HIP_CHECK(hipMemcpy(idf_out, idx->idf.p, sizeof(float) * idx->vocab, hipMemcpyDeviceToHost));
+    if (floors_out)
+        OI_HIP_CHECK(hipMemcpy(floors_out, idx->impact_floor.p, sizeof(uint32_t) * (size_t)idx->vocab * OI_BM25_FLOOR_RANKS, hipMemcpyDeviceToHost));
+    if (doc_len_out && idx->n_docs) OI_HIP_CHECK(hipMemcpy(doc_len_out, idx->doc_len.p, sizeof(uint32_t) * (size_t)idx->n_docs, hipMemcpyDeviceToHost));
+    return OI_OK;
+}
+
 extern "C" int oi_index_set_screen_copy(oi_index *idx, int policy) {
     if (!idx) { oi_set_error("null index"); return OI_ERR_INVALID_ARG; }
     if (idx->is_view) { oi_set_error("index view: read-only (set the policy on the index it was taken from)"); return OI_ERR_STATE; }

@@ -280,6 +280,22 @@ class HybridIndex(PostRetriever):
         _lib.check(self.lib.oi_internal_residual_plane(self.handle, 0, _lib.ptr(j), _lib.ptr(meta), _lib.ptr(e2max), C.byref(nb)))
         return j, meta, float(e2max[0]), int(nb.value)
 
+    def bm25_index(self):
+        """The BM25 structures of a finalized index or of a view of one (internal, for the tests): a dict of n_postings, n_win,
+        avgdl (np.float32) and the arrays dib: uint32 [n_postings], impact: float32 [n_postings], cell_start: uint32
+        [vocab * n_win + 1], idf: float32 [vocab], floors: uint32 [vocab, 4], doc_len: uint32 [n_docs]."""
+        n, w, a = C.c_uint64(), C.c_uint32(), C.c_float()
+        _lib.check(self.lib.oi_internal_bm25_index(self.handle, C.byref(n), C.byref(w), C.byref(a), None, None, None, None, None))
+        post = np.zeros((n.value, 2), np.uint32)
+        cell_start = np.zeros(self.vocab * w.value + 1, np.uint32)
+        idf = np.zeros(self.vocab, np.float32)
+        floors = np.zeros((self.vocab, 4), np.uint32)
+        doc_len = np.zeros(self.n_docs, np.uint32)
+        _lib.check(self.lib.oi_internal_bm25_index(self.handle, C.byref(n), C.byref(w), C.byref(a), _lib.ptr(post), _lib.ptr(cell_start),
+                                                   _lib.ptr(idf), _lib.ptr(floors), _lib.ptr(doc_len)))
+        return dict(n_postings=int(n.value), n_win=int(w.value), avgdl=np.float32(a.value), dib=post[:, 0].copy(),
+                    impact=post[:, 1].copy().view(np.float32), cell_start=cell_start, idf=idf, floors=floors, doc_len=doc_len)
+
     BM25_DEFAULT, BM25_TAAT, BM25_SCAN, BM25_WAVE, BM25_STREAM = 0, 1, 2, 3, 4
 
     def set_bm25_mode(self, mode: int) -> None:

@@ -326,6 +326,14 @@ def bm25_idf(n_docs: int, df: int) -> np.float32:
     return np.float32(_L().oio_bm25_idf(n_docs, df))
 
 
+def bm25_doc_norm(doc_len: int, avgdl) -> np.float32:
+    return np.float32(_L().oio_bm25_doc_norm(int(doc_len), float(np.float32(avgdl))))
+
+
+def bm25_impact(tf: int, doc_norm) -> np.float32:
+    return np.float32(_L().oio_bm25_impact(int(tf), float(np.float32(doc_norm))))
+
+
 def bm25_df(term_ids, doc_offsets, vocab: int):
     term_ids = np.ascontiguousarray(term_ids, dtype=np.uint32)
     doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.uint64)
