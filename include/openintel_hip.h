@@ -832,7 +832,8 @@ int oi_similar_share(oi_index *idx, const float *query_vecs, uint32_t n_queries,
  * Profile tags: "label_sums" and "centroids" as above, "fit_moved" (the moved / assigned count of a step), and the share's.
  *
  * NOT covered: a sharded or pipelined form (shards of the documents add their oi_label_sums outputs and call
- * oi_centroids_from_sums on the total); seeding is the caller's; one threshold for all clusters; at most 256 clusters.
+ * oi_centroids_from_sums on the total); the seeds come from the caller or from oi_narratives_seed (below); one threshold
+ * for all clusters; at most 256 clusters.
  */
 #define OI_MAX_CENTROIDS 256u
 int oi_label_sums(oi_index *idx, const uint32_t *labels /* [n_docs] by LOCAL row */, uint32_t n_clusters, int location,
@@ -850,6 +851,82 @@ int oi_narratives_fit(oi_index *idx, const float *seeds /* [n_clusters][dim] */,
                       const oi_narrative_spec *spec, const oi_doc_filter *filter /* ONE, host pointer, or NULL */, int location,
                       float *centroids_out /* [n_clusters][dim] */, oi_social_counters *records_out /* [n_clusters][n_buckets] */,
                       uint32_t *labels_out /* [n_docs] by LOCAL row, or NULL */, oi_narrative_info *info_host);
+
+/* ------------------------------------------------------------------------- */
+/* Narrative seeding: greedy k-means++ over the index on the device            */
+/* ------------------------------------------------------------------------- */
+/*
+ * oi_narratives_fit starts from seed vectors; a host that does not know vectors close to the narratives gets them here,
+ * without a row leaving the device.  oi_narratives_seed chooses n_clusters STORED ROWS of the index as seeds: greedy
+ * k-means++ (D^2 sampling, the best of `trials` candidates per seed) or farthest-first.  Builder-defined like the whole
+ * retrieval path.
+ *
+ * Eligible rows.  A row d is ELIGIBLE when it passes `filter` (if one is given) and bucket_width == 0 or it has a bucket:
+ * stamp_origin <= stamp[d] and (stamp[d] - stamp_origin) / bucket_width < n_buckets (evaluated in 64 bits).  This is the set
+ * oi_narratives_fit assigns from.  E is the number of eligible rows.
+ *
+ * sim and weight.  sim(p, d) is oi_similar_volume's sim with the stored row p as the query: the f32 value of the library's
+ * chain (on a bf16 corpus both rows are widened exactly, so the query rounding is the identity).
+ * weight(s) = (uint32) rintf(min(max(1.0f - s, 0), 2) * 2^20): one rounded f32 subtract, an exact scale; weight(NaN) = 0.
+ * For unit rows the weight is proportional to the squared distance.  Weights are integers <= 2^21 and every sum is a 64-bit
+ * integer, so the result is a function of the inputs alone.
+ *
+ * RNG.  u(i, t) = splitmix64(seed + (8 * i + t + 1) * 0x9E3779B97F4A7C15), where splitmix64(z) is z ^= z >> 30;
+ * z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31, all mod 2^64.  A target below a total W is
+ * r = mulhi64(u, W), the high 64 bits of the 128-bit product (not u mod W: mulhi64 moves continuously with W).
+ *
+ * Seed 0.  p_0 is the mulhi64(u(0, 0), E)-th eligible row in row order.  w_1[d] = weight(sim(p_0, d)) for eligible d != p_0;
+ * w_1[d] = 0 for p_0 and for every ineligible row.
+ *
+ * Seed i >= 1, OI_SEED_KMEANSPP with trials = L in 1 .. 8.  W = sum of w_i; if W == 0, stop with found = i.  For each
+ * t < L: r_t = mulhi64(u(i, t), W), and candidate c_t is the smallest row whose inclusive prefix sum of w_i in row order
+ * exceeds r_t (candidates may repeat).  wc_t[d] = weight(sim(c_t, d)) for eligible d, with wc_t[c_t] = 0 and wc_t[d] = 0 for
+ * ineligible rows.  pot_t = sum over d of min(w_i[d], wc_t[d]).  The step takes t* = argmin pot_t, ties to the smallest t.
+ * p_i = c_t*, w_{i+1} = min(w_i, wc_t*), and the next W is pot_t*.
+ *
+ * Seed i >= 1, OI_SEED_FARTHEST (trials must be 1).  p_i is the row with the largest w_i, ties to the smallest row; if the
+ * maximum is 0, stop with found = i.  The update is the same.  Seed 0 is chosen as above.
+ *
+ * Outputs.  seeds_out[i] is the stored row p_i as f32, bit for bit (a bf16 row widened exactly); rows_out[i] = p_i, the LOCAL
+ * row.  Seeds at and beyond `found` are all-zero vectors with row 0xFFFFFFFF.  info = {found, eligible = E, potential = the
+ * sum of w after the last seed}.  A chosen row has weight 0 from then on, so the seeds are distinct rows.
+ *
+ * Caveats.  Seed 0 is uniform over the eligible rows whatever they hold: if it is a NaN row every weight becomes 0 and
+ * found = 1.  On float embeddings the similarities are only within 1e-5 of f64 (the sentence the share carries): the choice
+ * is deterministic per build and independent of the cosine mode and the copy policy, but it is not pinned against f64.
+ *
+ * Rules.  Embeddings only: no signals, no forward index, no finalize; attributes are required only when a filter or
+ * bucket_width > 0 is given (without them -> OI_ERR_STATE); it works on a view; an f32 corpus of any supported dim and a
+ * bf16 corpus.  n_clusters in [1, OI_MAX_CENTROIDS], trials in [1, OI_MAX_SEED_TRIALS], n_buckets in
+ * [1, OI_MAX_VOLUME_BUCKETS] (1 when bucket_width == 0).  An unknown method, OI_SEED_FARTHEST with trials != 1,
+ * reserved != 0, a number out of range, a null spec, index or seeds_out -> OI_ERR_INVALID_ARG with the number in the
+ * message, before the first device call.  E == 0 is OK with found = 0.  `location` covers seeds_out and rows_out (rows_out
+ * may be NULL); spec, filter and info_host are always host pointers.  The seed loop runs without a host synchronise between
+ * its steps: two launches per seed, and once W == 0 every later launch of the call exits at once.  With info_host != NULL
+ * the call synchronises the ctx stream once at the end to read 24 bytes; with NULL and OI_DEVICE it is fully asynchronous.
+ * Never captured by graph replay.
+ * Workspace "seeds" per searching context, every part rounded up to 256 B (oi_workspace_bytes counts it): 256 B of state;
+ * w, 4 B per local row; cw, 4 * trials B per local row, only when trials > 1; the partial sums, 8 * trials B per range of
+ * 2048 rows; with OI_SEED_FARTHEST 8 B more per range; the candidate vectors, 4 * trials * dim B.  With OI_HOST the seeds
+ * and rows are staged in "seeds_io".
+ * Profile tags: "seed_init" (eligibility), "seed_score" (one stream of the rows per seed), "seed_pick" (one per seed + 1).
+ *
+ * NOT covered: streaming the bf16 screening copy for the passes; a sharded form; k-means|| or other schemes that take more
+ * than one seed per pass.
+ */
+#define OI_SEED_KMEANSPP 0u
+#define OI_SEED_FARTHEST 1u
+#define OI_MAX_SEED_TRIALS 8u
+typedef struct oi_seed_spec {
+    uint32_t method, trials;   /* OI_SEED_*; candidates per seed, 1 .. OI_MAX_SEED_TRIALS (1 with OI_SEED_FARTHEST) */
+    uint64_t seed;             /* of the RNG above */
+    uint32_t stamp_origin, bucket_width, n_buckets, reserved;   /* oi_narrative_spec's time axis; reserved == 0 */
+} oi_seed_spec;
+typedef struct oi_seed_info { uint32_t found, reserved; uint64_t eligible, potential; } oi_seed_info;
+int oi_narratives_seed(oi_index *idx, uint32_t n_clusters, const oi_seed_spec *spec,
+                       const oi_doc_filter *filter /* ONE, host pointer, or NULL */, int location,
+                       float *seeds_out /* [n_clusters][dim] */, uint32_t *rows_out /* [n_clusters], or NULL */,
+                       oi_seed_info *info_host /* or NULL */);
 
 /* ------------------------------------------------------------------------- */
 /* Mention summary: posts containing a query's terms, per bucket or ticker     */

@@ -89,6 +89,32 @@ pub struct OiNarrativeInfo {
 }
 pub const OI_MAX_CENTROIDS: u32 = 256;
 
+/// `oi_seed_spec`: method (`OI_SEED_*`), trials (candidates per seed, 1 ..= 8; 1 with farthest-first), the RNG seed,
+/// `oi_narrative_spec`'s time axis, reserved (0).  32 bytes.
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct OiSeedSpec {
+    pub method: u32,
+    pub trials: u32,
+    pub seed: u64,
+    pub stamp_origin: u32,
+    pub bucket_width: u32,
+    pub n_buckets: u32,
+    pub reserved: u32,
+}
+/// `oi_seed_info`: seeds found, reserved, eligible rows, the sum of the weights after the last seed.  24 bytes.
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
+pub struct OiSeedInfo {
+    pub found: u32,
+    pub reserved: u32,
+    pub eligible: u64,
+    pub potential: u64,
+}
+pub const OI_SEED_KMEANSPP: u32 = 0;
+pub const OI_SEED_FARTHEST: u32 = 1;
+pub const OI_MAX_SEED_TRIALS: u32 = 8;
+
 /// `oi_mention_spec`: axis TIME -- `stamp_origin`, `bucket_width` and `n_cells` are `oi_summary_spec`'s time axis; axis KEY --
 /// `stamp_origin` carries the key_mask (non-zero, one contiguous run of bits), `bucket_width` is 0, `n_cells` the number of keys.
 #[repr(C)]
@@ -306,6 +332,10 @@ extern "C" {
     pub fn oi_narratives_fit(idx: *mut OiIndex, seeds: *const f32, n_clusters: u32, spec: *const OiNarrativeSpec,
                              filter: *const OiDocFilter, location: c_int, centroids_out: *mut f32,
                              records_out: *mut OiSocialCounters, labels_out: *mut u32, info_host: *mut OiNarrativeInfo) -> c_int;
+    // the seeds of that loop, chosen on the device among the stored rows (filter: ONE, may be null; rows_out and info_host may
+    // be null; spec, filter and info_host are host pointers whatever `location`)
+    pub fn oi_narratives_seed(idx: *mut OiIndex, n_clusters: u32, spec: *const OiSeedSpec, filter: *const OiDocFilter,
+                              location: c_int, seeds_out: *mut f32, rows_out: *mut u32, info_host: *mut OiSeedInfo) -> c_int;
 
     pub fn oi_pipeline_create(idx: *mut OiIndex, comm: *mut OiComm, lanes: u32, max_queries: u32, max_query_terms: u32,
                               depth: u32, k: u32, out: *mut *mut OiPipeline) -> c_int;

@@ -452,6 +452,22 @@ impl HipIndex {
         })?;
         Ok((cent, rec.chunks(nb.max(1)).map(|c| c.to_vec()).collect(), lab, info))
     }
+    /// Seeds for `fit_narratives`, chosen on the device (`oi_narratives_seed`): `n_clusters` stored rows of the index by greedy
+    /// k-means++ (the best of `spec.trials` D^2-sampled candidates per seed) or farthest-first, among the rows that pass
+    /// `filter` and have a bucket.  Returns the seed vectors ([n_clusters * dim], zeros at and beyond `info.found`), their local
+    /// rows (`u32::MAX` there) and {found, eligible, potential}.  A function of the arguments alone.
+    pub fn seed_narratives(&self, n_clusters: u32, spec: ffi::OiSeedSpec, filter: Option<ffi::OiDocFilter>)
+                           -> Result<(Vec<f32>, Vec<u32>, ffi::OiSeedInfo), HipError> {
+        let k = n_clusters as usize;
+        let mut seeds = vec![0f32; k.max(1) * self.dim];
+        let mut rows = vec![u32::MAX; k.max(1)];
+        let mut info = ffi::OiSeedInfo::default();
+        check(unsafe {
+            ffi::oi_narratives_seed(self.idx, n_clusters, &spec, filter.as_ref().map_or(std::ptr::null(), |f| f as *const _),
+                                    ffi::OI_HOST, seeds.as_mut_ptr(), rows.as_mut_ptr(), &mut info)
+        })?;
+        Ok((seeds, rows, info))
+    }
     /// Which group keys (tickers) the posts like each query are about, and what those posts feel (`oi_similar_groups`): the
     /// social_summary sums per key = (group & key_mask) >> ctz(key_mask), under `similar_summary`'s clauses.  spec.top == 0: per
     /// query `n_keys` records, keys implied (entry i is (i, record i)).  spec.top >= 1: per query the listed (key, record) pairs,

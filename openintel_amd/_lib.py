@@ -21,6 +21,8 @@ OI_MAX_SUMMARY_CELLS = 1 << 18
 OI_MAX_GROUP_KEYS = 65536
 OI_MAX_GROUP_CELLS = 1 << 20
 OI_MAX_CENTROIDS = 256
+OI_SEED_KMEANSPP, OI_SEED_FARTHEST = 0, 1
+OI_MAX_SEED_TRIALS = 8
 OI_MAX_MENTION_TERMS = 64
 OI_MENTION_AXIS_TIME, OI_MENTION_AXIS_KEY = 0, 1
 OI_GROUP_RANK_TOTAL, OI_GROUP_RANK_SPEC, OI_GROUP_RANK_BULLISH, OI_GROUP_RANK_BEARISH = 0, 1, 2, 3
@@ -108,6 +110,30 @@ class NarrativeInfo(C.Structure):
         ("converged", C.c_uint32),
         ("moved", C.c_uint64),
         ("assigned", C.c_uint64),
+    ]
+
+
+class SeedSpec(C.Structure):
+    """oi_seed_spec: method (OI_SEED_*), trials (candidates per seed, 1 .. 8), the RNG seed, oi_narrative_spec's time axis,
+    reserved (0).  32 bytes."""
+    _fields_ = [
+        ("method", C.c_uint32),
+        ("trials", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("stamp_origin", C.c_uint32),
+        ("bucket_width", C.c_uint32),
+        ("n_buckets", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class SeedInfo(C.Structure):
+    """oi_seed_info: seeds found, reserved, eligible rows, the potential (sum of the weights) after the last seed.  24 bytes."""
+    _fields_ = [
+        ("found", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("eligible", C.c_uint64),
+        ("potential", C.c_uint64),
     ]
 
 
@@ -202,6 +228,7 @@ SIGNATURES = {
     "oi_label_sums": (_I, [_P, _P, _U32, _I, _P, _P]),
     "oi_centroids_from_sums": (_I, [_P, _P, _P, _P, _U32, _U32, _I, _P]),
     "oi_narratives_fit": (_I, [_P, _P, _U32, _P, _P, _I, _P, _P, _P, _P]),
+    "oi_narratives_seed": (_I, [_P, _U32, _P, _P, _I, _P, _P, _P]),
     "oi_text_terms": (_I, [_P, _P, _P, _U64, _U64, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_query_terms": (_I, [_P, _P, _P, _U32, _U32, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_index_set_text": (_I, [_P, _P, _P, _U64, _I]),

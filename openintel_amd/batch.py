@@ -392,8 +392,18 @@ def discover_narratives(index, seeds, threshold, **kw):
     """Which narratives are there: `index.fit_narratives(seeds, threshold, **kw)` (k-means over the index on the device,
     oi_narratives_fit) and the share of voice of what it found -> (NarrativeFit, share_of_voice(fit.records)).  Entry
     [c][b] of the second is narrative c's share of the assigned posts in bucket b.  Records that live on the device
-    (tensor seeds) are read back for it; the fit itself is returned as it came."""
+    (tensor seeds) are read back for it; the fit itself is returned as it came.
+    `seeds` may also be an int: that many seeds are first chosen on the device by `index.seed_narratives` (oi_narratives_seed)
+    among the rows the fit assigns from -- with the fit's `filter`, `n_buckets`, `stamp_origin` and `bucket_width`, and with
+    `method`, `trials` and `seed` taken from kw (they do not reach the fit).  The seed vectors stay on the device when the
+    index's rows were given as device tensors."""
     from .analyzer import COUNTERS_DTYPE
+    import numbers
+    if isinstance(seeds, numbers.Integral) and not isinstance(seeds, bool):
+        skw = {k: kw.pop(k) for k in ("method", "trials", "seed") if k in kw}
+        skw.update({k: kw[k] for k in ("filter", "n_buckets", "stamp_origin", "bucket_width") if k in kw})
+        on_device = any(hasattr(t, "data_ptr") for t in getattr(index, "_keep", []))
+        seeds = index.seed_narratives(int(seeds), device=on_device, **skw).seeds
     fit = index.fit_narratives(seeds, threshold, **kw)
     rec = fit.records
     if hasattr(rec, "data_ptr"):

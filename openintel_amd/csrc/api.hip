@@ -2024,6 +2024,48 @@ extern "C" int oi_narratives_fit(oi_index *idx, const float *seeds, uint32_t K, 
     return OI_OK;
 }
 
+// the seeding (seeds.hip): no host synchronise between the steps; one at the end when the caller reads the info
+extern "C" int oi_narratives_seed(oi_index *idx, uint32_t K, const oi_seed_spec *spec, const oi_doc_filter *filter, int location,
+                                  float *seeds_out, uint32_t *rows_out, oi_seed_info *info_host) {
+    OI_REQUIRE(spec, "narratives_seed: null spec");
+    OI_REQUIRE(K >= 1 && K <= OI_MAX_CENTROIDS, "narratives_seed: n_clusters=%u outside [1,%u]", K, OI_MAX_CENTROIDS);
+    OI_REQUIRE(spec->method == OI_SEED_KMEANSPP || spec->method == OI_SEED_FARTHEST, "narratives_seed: method=%u is not an OI_SEED_* value",
+               spec->method);
+    OI_REQUIRE(spec->trials >= 1 && spec->trials <= OI_MAX_SEED_TRIALS, "narratives_seed: trials=%u outside [1,%u]", spec->trials,
+               OI_MAX_SEED_TRIALS);
+    OI_REQUIRE(spec->method != OI_SEED_FARTHEST || spec->trials == 1, "narratives_seed: trials=%u with OI_SEED_FARTHEST (must be 1)", spec->trials);
+    OI_REQUIRE(spec->reserved == 0, "narratives_seed: reserved=%u (must be 0)", spec->reserved);
+    OI_REQUIRE(spec->n_buckets >= 1 && spec->n_buckets <= OI_MAX_VOLUME_BUCKETS, "narratives_seed: n_buckets=%u outside [1,%u]", spec->n_buckets,
+               OI_MAX_VOLUME_BUCKETS);
+    OI_REQUIRE(spec->bucket_width != 0 || spec->n_buckets == 1, "narratives_seed: bucket_width=0 (no time axis) with n_buckets=%u", spec->n_buckets);
+    OI_REQUIRE(seeds_out, "narratives_seed: null buffer");
+    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "narratives_seed: bad location %d", location);
+    std::unique_lock<std::mutex> g;
+    OI_CHECK(similar_check_state("narratives_seed", idx, false, (filter || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
+    oi_ctx *ctx = idx->ctx;
+    hipStream_t st = ctx->stream;
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    const bool host = location != OI_DEVICE;
+    const size_t vb = sizeof(float) * (size_t)K * idx->dim, rb = sizeof(uint32_t) * (size_t)K;
+    float *d_seeds = seeds_out;
+    uint32_t *d_rows = rows_out;
+    if (host) {
+        DevBuf &io = ctx->buf("seeds_io");
+        OI_CHECK(io.ensure(vb + rb));
+        d_seeds = io.as<float>();
+        d_rows = reinterpret_cast<uint32_t *>(io.as<uint8_t>() + vb);
+    }
+    const void *d_info = nullptr;
+    OI_CHECK(oi_launch_narratives_seed(idx, K, *spec, filter, d_seeds, d_rows, &d_info));
+    if (host) {
+        OI_HIP_CHECK(hipMemcpyAsync(seeds_out, d_seeds, vb, hipMemcpyDeviceToHost, st));
+        if (rows_out) OI_HIP_CHECK(hipMemcpyAsync(rows_out, d_rows, rb, hipMemcpyDeviceToHost, st));
+    }
+    if (info_host) OI_HIP_CHECK(hipMemcpyAsync(info_host, d_info, sizeof(oi_seed_info), hipMemcpyDeviceToHost, st));
+    if (host || info_host) OI_HIP_CHECK(hipStreamSynchronize(st));
+    return OI_OK;
+}
+
 // ---------------------------------------------------------------- diagnostics of the bf16 screen
 extern "C" int oi_screen_probe(oi_index *idx, const float *query_vecs, uint32_t B, uint64_t row_begin, uint32_t n_rows,
                                float *screen_scores_out, float *eps_out) {

@@ -407,6 +407,11 @@ int oi_launch_label_sums(oi_index *idx, const uint32_t *d_labels, uint32_t n_clu
 int oi_launch_centroids_from_sums(oi_ctx *ctx, const int64_t *d_sums, const uint64_t *d_counts, const float *d_previous,
                                   uint32_t n_clusters, uint32_t dim, float *d_out);
 int oi_launch_fit_moved(oi_ctx *ctx, const uint32_t *d_cur, const uint32_t *d_prev, uint64_t n, uint64_t *d_out);
+// seeds.hip: the seeding of that clustering -- device seeds [n_clusters][dim] and rows [n_clusters] (may be null)
+// out, both preset by the launch; *d_info_out = the call's oi_seed_info in its workspace.  filter: a host pointer or null.
+// Asynchronous on the ctx stream
+int oi_launch_narratives_seed(oi_index *idx, uint32_t n_clusters, const oi_seed_spec &spec, const oi_doc_filter *filter, float *d_seeds,
+                              uint32_t *d_rows, const void **d_info_out);
 // cosine.hip
 // Sets pool.n_segs / pool.seg_cap for this chunk (the following select must use the same view).
 // run_gate != null: a launch of the gated exact pipeline behind a screen (search.hip: cosine_exact) -- the kernel exits at once

@@ -66,6 +66,16 @@ class NarrativeFit:
     assigned: int       # rows the last step assigned
 
 
+@dataclass
+class NarrativeSeeds:
+    """Result of HybridIndex.seed_narratives (oi_narratives_seed)."""
+    seeds: object       # [K, dim] f32: the chosen stored rows, bit for bit; zero vectors at and beyond `found`
+    rows: object        # [K] u32 local rows (0xFFFFFFFF at and beyond `found`)
+    found: int          # seeds chosen: K unless the weights ran out (every eligible row coincides with a seed)
+    eligible: int       # rows that pass the filter and have a bucket
+    potential: int      # sum over the eligible rows of rint((1 - sim to the nearest seed) * 2^20), after the last seed
+
+
 GROUP_RANKS = {"total": _lib.OI_GROUP_RANK_TOTAL, "spec": _lib.OI_GROUP_RANK_SPEC, "bullish": _lib.OI_GROUP_RANK_BULLISH,
                "bearish": _lib.OI_GROUP_RANK_BEARISH}
 
@@ -809,6 +819,31 @@ class HybridIndex(PostRetriever):
                                               _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(cent), _lib.ptr(rec), _lib.ptr(lab),
                                               C.byref(info)))
         return NarrativeFit(cent, rec, lab, int(info.iterations), bool(info.converged), int(info.moved), int(info.assigned))
+
+    SEED_METHODS = {"kmeans++": _lib.OI_SEED_KMEANSPP, "farthest": _lib.OI_SEED_FARTHEST}
+
+    def seed_narratives(self, n_clusters: int, method="kmeans++", trials: int = 4, seed: int = 0, n_buckets: int = 1,
+                        stamp_origin: int = 0, bucket_width: int = 0, filter=None, device: bool = False) -> "NarrativeSeeds":
+        """oi_narratives_seed: n_clusters stored rows of the index chosen as seeds for fit_narratives, on the device -- greedy
+        k-means++ (method "kmeans++": D^2 sampling with integer weights rint((1 - sim) * 2^20), the best of `trials` candidates
+        per seed) or farthest-first ("farthest", trials = 1).  Only rows that pass `filter` (ONE {group_mask, group_value,
+        stamp_lo, stamp_hi}) and have a bucket are eligible: the rows fit_narratives assigns from.  The result is a function
+        of the arguments alone (the RNG is splitmix64 of `seed`).  Seeds at and beyond `found` (every eligible row already
+        coincides with a seed) are zero vectors with row 0xFFFFFFFF.  numpy out; torch CUDA tensors when device=True."""
+        K = int(n_clusters)
+        m = self.SEED_METHODS.get(method, method)
+        spec = _lib.SeedSpec(int(m), int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stamp_origin), int(bucket_width), int(n_buckets), 0)
+        shape_k = max(min(K, _lib.OI_MAX_CENTROIDS), 1)            # (a count out of range is refused by the library, not here)
+        seeds = self._alloc(device, (shape_k, self.dim), np.float32)
+        rows = self._alloc(device, (shape_k,), np.uint32)
+        f = None
+        if filter is not None:
+            fa = np.ascontiguousarray(np.asarray(filter.cpu().numpy() if _is_dev(filter) else filter).astype(np.uint32, copy=False).reshape(4))
+            f = _lib.DocFilter(int(fa[0]), int(fa[1]), int(fa[2]), int(fa[3]))
+        info = _lib.SeedInfo()
+        _lib.check(self.lib.oi_narratives_seed(self.handle, K, C.byref(spec), None if f is None else C.byref(f),
+                                               _lib.OI_DEVICE if device else _lib.OI_HOST, _lib.ptr(seeds), _lib.ptr(rows), C.byref(info)))
+        return NarrativeSeeds(seeds, rows, int(info.found), int(info.eligible), int(info.potential))
 
     # ---------------------------------------------------------------- the sharded query with RCCL inside the library
     def finalize_sharded(self, comm: "NativeComm") -> None:
