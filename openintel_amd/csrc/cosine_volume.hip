@@ -46,9 +46,7 @@ struct VoCount {
 // widened back to f32 for the chain.
 __global__ __launch_bounds__(256) void volume_round_queries_kernel(const float *__restrict__ q, uint64_t total, float *__restrict__ out) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t u = __float_as_uint(q[i]);
-        const uint32_t v = (u & 0x7F800000u) == 0x7F800000u ? u >> 16 : (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-        out[i] = __uint_as_float(v << 16);
+        out[i] = __uint_as_float(oi_f32_to_bf16_rne(q[i]) << 16);
     }
 }
 

@@ -100,6 +100,12 @@ __device__ __forceinline__ float oi_mul_unpacked(float x, float y) {
     return r;
 }
 
+// f32 -> bfloat16 bits, round to nearest even; inf / NaN truncate (a NaN stays a NaN, an inf an inf).
+__device__ __forceinline__ uint32_t oi_f32_to_bf16_rne(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x7F800000u) == 0x7F800000u ? u >> 16 : (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
 // Order-preserving map f32 -> u32 (ascending).  -0.0 is folded into +0.0 first so
 // that equal scores compare equal; NaN must be rejected by the caller.
 __device__ __forceinline__ uint32_t oi_f32_key(float s) {

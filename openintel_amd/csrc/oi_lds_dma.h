@@ -1,8 +1,9 @@
 // oi_lds_dma.h -- what the streaming kernels share: the LDS-DMA ring primitives (descriptor, one 1-KiB piece, the counted
 // wait, the compile-time loop the ring schedules are written in) and the per-wave staging ring the survivors leave through.
-// Users: cosine_bf16, cosine_screen_i8 (.hip), oi_ksplit_tile.h: what cosine_ksplit and cosine_split (.hip) are written on, and
-// oi_screen_tile.h: the tile pipeline that cosine_prefilter, cosine_screen_copy, cosine_volume and cosine_summary (.hip, the
-// last two through oi_volume.h) are written on.
+// Users: cosine_screen_i8.hip and cosine_bf16_qsplit's half-tile ring (cosine_bf16.hip) directly; oi_ksplit_tile.h: what
+// cosine_ksplit and cosine_split (.hip) are written on; and oi_screen_tile.h: the tile pipeline that cosine_prefilter,
+// cosine_screen_copy, cosine_bf16 (solo and pair), cosine_volume and cosine_summary (.hip, the last two through oi_volume.h) are
+// written on.
 //
 // THE CONTRACT of an LDS-DMA load (`buffer_load_dwordx4 ... lds`: 64 lanes x 16 B from each lane's own source offset into
 // 1 KiB of LDS at M0 + 16 * lane, no register destination):
@@ -83,9 +84,9 @@ __device__ __forceinline__ void oi_dma_piece(const oi_u32x4 &srd, uint32_t voff,
 // Per-lane source of the 4 pieces of a slot (32 rows x 128 B): piece m covers tile rows 8m..8m+7; lane l -> row 8m + (l>>3),
 // physical 16-B column l&7 holding LOGICAL column (l&7) ^ ((row>>1)&7), so that the ds_read_b128 fragment reads are
 // conflict-free.  ROW_BYTES: 2 D (bf16 rows) or 4 D (f32).  base (wave-uniform bytes): where the wave's K-slice starts in a
-// row; OiKsplitTile (oi_ksplit_tile.h) is its one caller.  cosine_bf16.hip (the kh * KH * 2 half of cosine_bf16_pair among
-// its three sites) and cosine_screen_i8.hip write the same offsets in loops of their own: as a call the arithmetic is
-// canonicalised apart from the kernel's other lane arithmetic and every kernel of those files comes out different.
+// row (OiKsplitTile, oi_ksplit_tile.h; the K half of a cosine_bf16_pair wave through OiCopyRing, oi_screen_tile.h).
+// cosine_screen_i8.hip writes the same offsets in a loop of its own (as a call its kernels come out different, and nothing
+// bit-exact at every edge stands under them to allow that).
 template <uint32_t ROW_BYTES>
 __device__ __forceinline__ void oi_tile_voff(uint32_t (&voff)[4], uint32_t lane, uint32_t base = 0) {
 #pragma unroll
@@ -93,6 +94,11 @@ __device__ __forceinline__ void oi_tile_voff(uint32_t (&voff)[4], uint32_t lane,
         const uint32_t prow = 8 * m + (lane >> 3);
         voff[m] = prow * ROW_BYTES + base + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
     }
+}
+// Where a lane reads its A fragment of MFMA group g inside a slot: row li, bf16 16 g + 8 lh + 0..7 = logical 16-B column 2g + lh.
+__device__ __forceinline__ void oi_tile_frag_off(uint32_t (&frag_off)[4], uint32_t li, uint32_t lh) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) frag_off[g] = li * 128 + (((2 * g + lh) ^ ((li >> 1) & 7)) << 4);
 }
 // f(integral_constant<int, I>) for I in [I, N): a ring schedule's slots and waits are compile-time constants.
 template <int I, int N, class F>

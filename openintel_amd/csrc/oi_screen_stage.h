@@ -31,9 +31,7 @@ __device__ __forceinline__ void pf_stage_query_row(const float *__restrict__ q, 
         uint16_t v = 0;
         if (row < n_queries) {
             const float f = q[(uint64_t)row * dim + k];
-            const uint32_t u = __float_as_uint(f);
-            v = (u & 0x7F800000u) == 0x7F800000u ? (uint16_t)(u >> 16)                        // inf / NaN: truncate
-                                                 : (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); // RNE
+            v = (uint16_t)oi_f32_to_bf16_rne(f);
             const float ft = __uint_as_float((uint32_t)v << 16), e = ft - f; // exact: f rounded to 8 of its 24 bits
             ss = fmaf(f, f, ss);
             st = fmaf(ft, ft, st);

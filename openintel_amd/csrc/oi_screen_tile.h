@@ -7,6 +7,8 @@
 //     hipcc knows about, the score test and the ragged-tile mask (the swizzled DMA source offsets: oi_lds_dma.h) (all three kernels);
 //   * OiCopyRing: the ring over bf16 rows with a run-time ring offset                    (copy screen and vo_stream_kernel;
 //     cosine_screen_filter keeps its own k-loop: a compile-time ring index, two ds_read_b128 and four conversions per k-step);
+//     also the ring of the bf16 corpus scorer's solo and pair kernels (cosine_bf16.hip), the pair over a K-slice of half a
+//     row; that file takes its tile ownership (oi_owner_tiles), query preload and close (oi_pool_close) from here too;
 //   * the threshold decode and OiPoolSink, the survivor epilogue into the candidate pool (copy screen and f32 screen;
 //     vo_stream_kernel's band staging has another payload and another claim).
 // Everything is force-inlined and by value: the compiler sees three kernel families, not one.
@@ -29,17 +31,18 @@ constexpr size_t oi_ring_lds(int nbuf) { return (size_t)4 * nbuf * OI_SLOT_BYTES
 // Register r of query tile t holds D[row (r&3) + 8 (r>>2) + 4 lh][query 32 t + li]: that row of the tile whose first row is row0.
 __device__ __forceinline__ uint32_t oi_tile_row(uint32_t row0, int r, uint32_t lh) { return row0 + (uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * lh; }
 
-// Every query over the whole K, in registers for the whole launch: B[k = 16 s + 8 lh + 0..7][n = li].
-// queries: bf16 [32 * NQT][D], zero padded (pf_stage_queries_kernel).
-template <int D, int NQT>
-__device__ __forceinline__ void oi_tile_load_queries(oi_bf16x8 (&qreg)[NQT][D / 16], const uint16_t *__restrict__ queries, uint32_t li,
-                                                     uint32_t lh) {
-    static_assert(NQT * (D / 16) * 4 <= 400, "the query block must fit the register file");
+// Every query over the wave's K-slice, in registers for the whole launch: B[k = k0 + 16 s + 8 lh + 0..7][n = li].
+// queries: bf16 [32 * NQT][D], zero padded (pf_stage_queries_kernel, cb_stage_queries).  KW, k0: the slice's width and where
+// it starts (the whole K but for a cosine_bf16_pair wave, which holds one half).
+template <int D, int NQT, int KW = D>
+__device__ __forceinline__ void oi_tile_load_queries(oi_bf16x8 (&qreg)[NQT][KW / 16], const uint16_t *__restrict__ queries, uint32_t li,
+                                                     uint32_t lh, uint32_t k0 = 0) {
+    static_assert(NQT * (KW / 16) * 4 <= 400, "the query block must fit the register file");
 #pragma unroll
     for (int t = 0; t < NQT; ++t)
 #pragma unroll
-        for (int s = 0; s < D / 16; ++s)
-            qreg[t][s] = *reinterpret_cast<const oi_bf16x8 *>(queries + (uint64_t)(32 * t + li) * D + 16 * s + 8 * lh);
+        for (int s = 0; s < KW / 16; ++s)
+            qreg[t][s] = *reinterpret_cast<const oi_bf16x8 *>(queries + (uint64_t)(32 * t + li) * D + k0 + 16 * s + 8 * lh);
 }
 
 // Every load hipcc knows about (queries, thresholds, margins) is retired HERE, before the ring starts, with a wait it models:
@@ -48,7 +51,7 @@ __device__ __forceinline__ void oi_tile_retire_visible_loads() {
     __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) only
 }
 
-// The tiles of this WAVE among rows [row_begin, row_end): (blockIdx.x * 4 + w), + 4 * gridDim.x, ...
+// The tiles of one OWNER (a wave, a pair of waves or a workgroup) among rows [row_begin, row_end): first, + stride, ...
 struct OiWaveTiles {
     uint64_t row_begin, row_end, first, stride, my_nt;
     __device__ __forceinline__ uint64_t row0(uint64_t ti) const { return row_begin + (first + ti * stride) * (uint64_t)OI_TILE_ROWS; }
@@ -59,6 +62,19 @@ struct OiWaveTiles {
         return oi_make_srd(reinterpret_cast<const unsigned char *>(rows) + r0 * ROW_BYTES, ti < my_nt ? (row_end - r0) * (uint64_t)ROW_BYTES : 0ull);
     }
 };
+// Owner `owner` of `n_owners` takes every n_owners-th 32-row tile.
+__device__ __forceinline__ OiWaveTiles oi_owner_tiles(uint64_t row_begin, uint64_t row_end, uint64_t owner, uint64_t n_owners) {
+    OiWaveTiles t;
+    t.row_begin = row_begin;
+    t.row_end = row_end;
+    const uint64_t n_tiles = (row_end - row_begin + OI_TILE_ROWS - 1) / OI_TILE_ROWS;
+    t.first = owner;
+    t.stride = n_owners;
+    t.my_nt = t.first < n_tiles ? (n_tiles - t.first + t.stride - 1) / t.stride : 0;
+    return t;
+}
+// The tiles of this WAVE, every wave of the grid an owner: oi_owner_tiles(.., blockIdx.x * 4 + w, 4 * gridDim.x).  Written out:
+// as that call the operands are evaluated ahead of n_tiles, and the register allocation of every screen kernel moves.
 __device__ __forceinline__ OiWaveTiles oi_wave_tiles(uint64_t row_begin, uint64_t row_end, uint32_t w) {
     OiWaveTiles t;
     t.row_begin = row_begin;
@@ -92,8 +108,8 @@ __device__ __forceinline__ uint32_t oi_tile_mask_ragged(uint32_t m, uint64_t row
 }
 
 // ------------------------------------------------------------------ the bf16 copy ring
-// A wave's ring of NBUF slots over bf16 rows of D: a tile is NKC = D / 64 slots, P = NBUF - 1 slots are in flight ahead of the
-// one being consumed.  Per 16 k of a tile: one conflict-free ds_read_b128, NQT MFMAs, one DMA piece of the slot P ahead.
+// A wave's ring of NBUF slots over a K-slice of KW bf16 (the whole row by default) of bf16 rows of D: a tile is NKC = KW / 64
+// slots, P = NBUF - 1 slots are in flight ahead of the one being consumed.  Per 16 k of a tile: one conflict-free ds_read_b128, NQT MFMAs, one DMA piece of the slot P ahead.
 //   * the ring index is a RUN-TIME scalar (one s_add + s_cselect per slot, one v_add per fragment read), so NBUF is free of
 //     the tile's slot count;
 //   * the refill of slot s + P always issues (an empty descriptor past the wave's last tile returns zeros), so every counted
@@ -104,13 +120,13 @@ __device__ __forceinline__ void oi_dma_piece_stream(const oi_u32x4 &srd, uint32_
     oi_dma_piece(srd, voff, soff, lds_dst);
 }
 
-template <int D, int NBUF, oi_piece_fn ISSUE = oi_dma_piece_stream>
+template <int D, int NBUF, oi_piece_fn ISSUE = oi_dma_piece_stream, int KW = D>
 struct OiCopyRing {
-    static constexpr int NKC = D / OI_SLOT_K;     // ring slots per tile
+    static constexpr int NKC = KW / OI_SLOT_K;    // ring slots per tile
     static constexpr int P = NBUF - 1;            // slots in flight ahead of the one being consumed
     static constexpr uint32_t BYTES = NBUF * OI_SLOT_BYTES;
     static constexpr uint32_t ROW_BYTES = D * 2;
-    static_assert(D % OI_SLOT_K == 0 && P >= 1 && P <= 2 * NKC, "unsupported ring depth for this D");
+    static_assert(KW % OI_SLOT_K == 0 && P >= 1 && P <= 2 * NKC, "unsupported ring depth for this K width");
 
     uint32_t voff[4], frag_off[4];
     uint32_t ring_w;              // LDS address of the wave's ring (the DMA's side)
@@ -118,14 +134,15 @@ struct OiCopyRing {
     uint32_t rd_off, wr_off;      // ring offsets (bytes, wave-uniform): the slot being consumed, and the one vacated before it = the refill target
     oi_u32x4 s0, s1, s2;          // descriptors of the tile being consumed and the two after it (P <= 2 NKC: a refill reaches no further)
 
-    // lds: the wave's BYTES of ring.  Retires the compiler-visible loads and issues the prologue: logical slots 0..P-1 (tile
-    // j / NKC, slot j % NKC) into ring slots 0..P-1.
-    __device__ __forceinline__ void begin(const OiWaveTiles &wt, const void *rows, unsigned char *lds, uint32_t lane) {
+    // lds: the wave's BYTES of ring.  k_base (wave-uniform bytes): where the K-slice starts in a row.  Retires the
+    // compiler-visible loads and issues the prologue: logical slots 0..P-1 (tile j / NKC, slot j % NKC) into ring slots 0..P-1.
+    __device__ __forceinline__ void begin(const OiWaveTiles &wt, const void *rows, unsigned char *lds, uint32_t lane, uint32_t k_base = 0) {
         const uint32_t li = lane & 31, lh = lane >> 5;
-        oi_tile_voff<ROW_BYTES>(voff, lane);
+        oi_tile_voff<ROW_BYTES>(voff, lane, k_base);
         ring_w = oi_lds_addr(lds);
         ring_rd = lds;
-        // fragment of MFMA group g of a slot: row li, bf16 16 g + 8 lh + 0..7 = logical 16-B column 2g + lh
+        // fragment of MFMA group g of a slot: row li, bf16 16 g + 8 lh + 0..7 = logical 16-B column 2g + lh (oi_tile_frag_off, written
+        // out: as the call the swizzle's operands come out in another order in every kernel on this ring)
 #pragma unroll
         for (int g = 0; g < 4; ++g) frag_off[g] = li * 128 + (((2 * g + lh) ^ ((li >> 1) & 7)) << 4);
         s0 = wt.srd<ROW_BYTES>(rows, 0), s1 = wt.srd<ROW_BYTES>(rows, 1), s2 = wt.srd<ROW_BYTES>(rows, 2);
@@ -145,7 +162,7 @@ struct OiCopyRing {
     // g == 3 the counted wait retires slot kc + 1 (P - 1 younger slots stay in flight) and the offsets move on.
     // MFMA = false (variant builds): the stream without the matrix instructions; every score 0, results WRONG.
     template <int NQT, bool MFMA = true>
-    __device__ __forceinline__ void tile(oi_f32x16 (&acc)[NQT], const oi_bf16x8 (&qreg)[NQT][D / 16]) {
+    __device__ __forceinline__ void tile(oi_f32x16 (&acc)[NQT], const oi_bf16x8 (&qreg)[NQT][KW / 16]) {
 #pragma unroll
         for (int t = 0; t < NQT; ++t)
 #pragma unroll
@@ -202,6 +219,19 @@ __device__ __forceinline__ void oi_tile_thresholds(float (&tauf)[NQT], const uin
         const uint32_t q = 32u * t + li;
         const uint32_t k = q < n_queries ? tau_keys[q] : 0xFFFFFFFFu;
         tauf[t] = k <= 0x007FFFFFu ? -__builtin_inff() : oi_key_f32(k);
+    }
+}
+
+// The end of a workgroup's launch: every wave's appends are counted (a barrier), then the fill of segment `seg` per query, for the
+// 32 * NQT queries of the launch.  (OiPoolSink::close, and the three kernels of cosine_bf16.hip, which append by other routes.)
+template <int NQT>
+__device__ __forceinline__ void oi_pool_close(const uint32_t *seg_fill, uint32_t seg_cap, uint32_t n_queries, uint32_t *seg_cnt,
+                                              uint32_t seg_cnt_stride, uint32_t seg) {
+    __syncthreads();
+    const uint32_t tid = threadIdx.x;
+    if (tid < (n_queries < 32u * NQT ? n_queries : 32u * NQT)) { // (one compare of its own: the opening one is not kept alive over the tile loop)
+        const uint32_t c = seg_fill[tid];
+        seg_cnt[(uint64_t)tid * seg_cnt_stride + seg] = c < seg_cap ? c : seg_cap;
     }
 }
 
@@ -297,11 +327,6 @@ struct OiPoolSink {
     // Every wave's appends are counted (a barrier), then the segment's fill per query.
     template <int NQT>
     __device__ __forceinline__ void close(uint32_t n_queries, uint32_t *seg_cnt, uint32_t seg_cnt_stride) const {
-        __syncthreads();
-        const uint32_t tid = threadIdx.x;
-        if (tid < (n_queries < 32u * NQT ? n_queries : 32u * NQT)) { // (one compare of its own: open()'s is not kept alive over the tile loop)
-            const uint32_t c = seg_fill[tid];
-            seg_cnt[(uint64_t)tid * seg_cnt_stride + blockIdx.x] = c < seg_cap ? c : seg_cap;
-        }
+        oi_pool_close<NQT>(seg_fill, seg_cap, n_queries, seg_cnt, seg_cnt_stride, blockIdx.x);
     }
 };

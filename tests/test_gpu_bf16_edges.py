@@ -15,7 +15,13 @@ into a one-chunk case.
 
 Data: rows and queries are integers in [-3, 3], so every product and partial sum is exact in f32 in any order (|dot| <=
 9 x 1024 < 2^24): cosine, BM25 and fused lists must equal the oracle's bit for bit, ties broken towards the lower doc id.
-Cosine reference scores come from one float64 matmul (exact for these integers; test_int_matmul_equals_oracle_dot_scores)."""
+Cosine reference scores come from one float64 matmul (exact for these integers; test_int_matmul_equals_oracle_dot_scores).
+
+Data "order": exact in any order means blind to the order.  The "order" cases carry products of +-2^24 beside small integers, at
+most one non-zero product per (row, query) and 16-wide k-step (one MFMA adds one exact product to its accumulator), so a score
+depends on the order of its sum: 2^24 + 1 = 2^24 in f32.  Their reference is an f32 chain in numpy, per query the one of the kernel
+the mirror names for it: ascending K for the solo and query-split kernels, two ascending half chains summed as (half 0) +
+(half 1) for the pair kernel.  A CPU test holds every such case to telling the two apart in at least one query's list."""
 import os
 from concurrent.futures import ThreadPoolExecutor
 from typing import NamedTuple, Tuple, Union
@@ -87,6 +93,11 @@ def bf16_geometry(n_rows: int, num_cus: int, siblings: bool) -> Tuple[int, int]:
 
 def chunk_kernels(dim: int, B: int, n_rows: int, siblings: bool):
     """cosine_bf16.hip: oi_launch_cosine_bf16_chunk -- the kernel of every group of queries, in launch order."""
+    return [k for k, _ in chunk_groups(dim, B, n_rows, siblings)]
+
+
+def chunk_groups(dim: int, B: int, n_rows: int, siblings: bool):
+    """The same, with each group's size: [(kernel, queries)] in launch order."""
     out, q0 = [], 0
     while q0 < B:
         left = B - q0
@@ -95,17 +106,18 @@ def chunk_kernels(dim: int, B: int, n_rows: int, siblings: bool):
         nqt = (nq + 31) // 32
         if dim == 1024:
             if nq > 128:
-                out.append("qsplit<2>")
+                kernel = "qsplit<2>"
             elif nq > 96:
-                out.append("qsplit<0>")
+                kernel = "qsplit<0>"
             elif nq <= 32:
-                out.append("solo<1024,1>")
+                kernel = "solo<1024,1>"
             else:
-                out.append("pair<1024,%d>" % nqt)
+                kernel = "pair<1024,%d>" % nqt
         elif nq > 64:
-            out.append("pair<%d,3>" % dim)
+            kernel = "pair<%d,3>" % dim
         else:
-            out.append("solo<%d,%d>" % (dim, nqt))
+            kernel = "solo<%d,%d>" % (dim, nqt)
+        out.append((kernel, nq))
         q0 += nq
     return out
 
@@ -162,7 +174,7 @@ class Case(NamedTuple):
     depth: int
     k: int
     base: int
-    data: str             # "rand": i.i.d. integers; "ties": a few distinct rows repeated (many ties at every cut)
+    data: str             # "rand": i.i.d. integers; "ties": a few distinct rows repeated (many ties at every cut); "order": see above
     kernels: frozenset    # every kernel the case runs on an MI355X (the mirror, checked on the CPU)
     chunks: int           # corpus chunks on an MI355X (the mirror on the CPU, the profiler on the GPU)
 
@@ -240,7 +252,16 @@ CASES = [
     Case("ragged-n1-d1024", 1024, 256, 1, 100, 100, MAX_BASE, "rand", _k("qsplit<0>"), 1),
     Case("ragged-n1-d384", 384, 5, 1, 1024, 1024, 7, "rand", _k("solo<384,1>"), 1),
     Case("ragged-n31-d1024", 1024, 97, 31, 2, 1, 0, "ties", _k("qsplit<0>"), 1),
+    # ---- the order of a score's sum, one case per tile loop and K split (scores that depend on it: "order" data)
+    Case("order-d384-B64", 384, 64, N2, 100, 10, 0, "order", _k("solo<384,2>"), 2),
+    Case("order-d768-B96", 768, 96, N2, 100, 100, 7, "order", _k("pair<768,3>"), 2),
+    Case("order-d1024-B32", 1024, 32, N2, 100, 10, 1000, "order", _k("solo<1024,1>"), 2),
+    Case("order-d1024-B64", 1024, 64, N2, 100, 100, 0, "order", _k("pair<1024,2>"), 2),
+    Case("order-d1024-B96", 1024, 96, N2, 100, 10, MAX_BASE, "order", _k("pair<1024,3>"), 2),
+    Case("order-d1024-B128", 1024, 128, N2, 100, 100, 0, "order", _k("qsplit<0>"), 2),
+    Case("order-d1024-B256-sib", 1024, 256, TRows(1, 0), 100, 10, 5, "order", _k("qsplit<2>"), 1),
 ]
+ORDER_CASES = [c for c in CASES if c.data == "order"]
 
 
 @pytest.fixture(scope="module")
@@ -373,8 +394,74 @@ def _int_data(case: Case, n: int, chunks, seed: int):
 
 
 def _int_bits(rows):
-    """bf16 bit patterns of small integers (exact)."""
+    """bf16 bit patterns of small integers and of +-2^24 (exact)."""
     return (rows.astype(np.float32).view(np.uint32) >> 16).astype(np.uint16)
+
+
+BIG = np.float32(2.0 ** 24)
+
+
+def _order_data(case: Case, n: int, seed: int):
+    """Rows and queries (f32, every value exact in bf16) whose scores depend on the order of the sum, and what the reference needs:
+    * one seeded position in every 16-wide k-step; rows are zero elsewhere, queries are 1 or 0 there: a (row, query) pair has at
+      most one non-zero product per k-step, the row's value;
+    * the values vals[row, step]: half of them zero, the rest integers in [-3, 3]; three rows in four also carry +2^24 at one
+      step and -2^24 at another, in either order;
+    * sel[query, step]: every second query takes every step, the others drop one step in ten (a dropped +-2^24 leaves its
+      partner standing: scores near +-2^24 as well as near 0)."""
+    rng = np.random.default_rng(seed)
+    dim, B, ks = case.dim, case.B, case.dim // 16
+    pos = 16 * np.arange(ks) + rng.integers(0, 16, size=ks)
+    vals = rng.integers(-3, 4, size=(n, ks)).astype(np.float32)
+    vals[rng.random((n, ks)) < 0.5] = 0.0
+    big = np.nonzero(rng.random(n) < 0.75)[0]
+    a = rng.integers(0, ks, size=big.size)
+    b = (a + rng.integers(1, ks, size=big.size)) % ks
+    sign = rng.choice(np.array([-1.0, 1.0], dtype=np.float32), size=big.size)
+    vals[big, a] = sign * BIG
+    vals[big, b] = -sign * BIG
+    sel = rng.random((B, ks)) < 0.9
+    sel[::2] = True
+    rows = np.zeros((n, dim), dtype=np.float32)
+    rows[:, pos] = vals
+    q = np.zeros((B, dim), dtype=np.float32)
+    q[:, pos] = sel
+    return rows, q, vals, sel
+
+
+def _f32_chain(M):
+    """((0 + M[:, 0]) + M[:, 1]) + ... in f32, round to nearest even: an MFMA accumulation chain with one product per step."""
+    acc = np.zeros(M.shape[0], dtype=np.float32)
+    for s in range(M.shape[1]):
+        acc = acc + M[:, s]
+    return acc
+
+
+def _order_scores(vals, sel):
+    """([B, n] f32 scores as ONE chain in ascending K, the same as TWO half chains summed as (half 0) + (half 1))."""
+    B, (n, ks) = sel.shape[0], vals.shape
+    one, two = np.empty((B, n), dtype=np.float32), np.empty((B, n), dtype=np.float32)
+    for b in range(B):
+        M = vals * sel[b].astype(np.float32)
+        one[b] = _f32_chain(M)
+        two[b] = _f32_chain(M[:, :ks // 2]) + _f32_chain(M[:, ks // 2:])
+    return one, two
+
+
+def _order_reference(case: Case, chunks, vals, sel):
+    """[B, n] f32 scores of an "order" case: per chunk and query, the sum order of the kernel the mirror names for them."""
+    one, two = _order_scores(vals, sel)
+    S = one.copy()
+    for ch in chunks:
+        q0 = 0
+        for kernel, nq in chunk_groups(case.dim, case.B, ch.rows, ch.siblings):
+            if kernel.startswith("pair<"):
+                S[q0:q0 + nq, ch.begin:ch.end] = two[q0:q0 + nq, ch.begin:ch.end]
+            else:
+                assert kernel.startswith(("solo<", "qsplit<")), kernel
+            q0 += nq
+        assert q0 == case.B
+    return S, one, two
 
 
 # ==================================================================== CPU: the table and the oracle shortcut
@@ -436,6 +523,31 @@ def test_int_matmul_equals_oracle_dot_scores():
         assert np.array_equal(S[b].view(np.uint32), O.dot_scores(rows.astype(np.float32), q[b]).view(np.uint32))
 
 
+def test_order_cases_tell_one_chain_from_two_half_chains():
+    """Every "order" case: its data is what the reference assumes (exact in bf16, at most one non-zero product per k-step and
+    (row, query) pair), and the case can see what it is there for -- the lists of at least one of its queries differ between
+    the two sum orders, so a tile loop that sums a score in the other kernel's order fails the case."""
+    from oracle import lib as O
+    assert [(c.dim, c.B) for c in ORDER_CASES] == [(384, 64), (768, 96), (1024, 32), (1024, 64), (1024, 96), (1024, 128), (1024, 256)]
+    assert ORDER_CASES[-1].n == TRows(1, 0)
+    for c in ORDER_CASES:
+        n, base = c.n_rows(MI355X_CUS), c.doc_base(MI355X_CUS)
+        chunks = schedule(n, c.dim, c.B, c.depth, MI355X_CUS)
+        rows, q, vals, sel = _order_data(c, n, 1009 * c.dim + 31 * c.B + n)
+        assert np.array_equal(from_bf16_bits(_int_bits(rows)), rows) and np.array_equal(from_bf16_bits(to_bf16_bits(q)), q), c.name
+        assert (np.count_nonzero(rows.reshape(n, -1, 16), axis=2) <= 1).all() and np.isin(q, (0.0, 1.0)).all(), c.name
+        assert np.array_equal(rows[:, np.nonzero(q.any(axis=0))[0]] != 0, vals != 0), c.name     # the products ARE vals x sel
+        S, one, two = _order_reference(c, chunks, vals, sel)
+        pair = all(k.startswith("pair<") for k in c.kernels)
+        assert np.array_equal(S.view(np.uint32), (two if pair else one).view(np.uint32)), c.name
+        differ = 0
+        for b in range(c.B):
+            (s1, d1), (s2, d2) = O.topk(one[b], c.depth, False, base), O.topk(two[b], c.depth, False, base)
+            differ += not (np.array_equal(d1, d2) and np.array_equal(s1.view(np.uint32), s2.view(np.uint32)))
+        print("%s: the lists of %d of %d queries differ between the two sum orders" % (c.name, differ, c.B))
+        assert differ >= 1, c.name
+
+
 # ==================================================================== GPU: the table, bit for bit
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", CASES, ids=[c.name for c in CASES])
@@ -443,7 +555,12 @@ def test_bf16_case_bit_exact(ctx, O, num_cus, case):
     n, base = case.n_rows(num_cus), case.doc_base(num_cus)
     chunks = schedule(n, case.dim, case.B, case.depth, num_cus)
     seed = 1009 * case.dim + 31 * case.B + n
-    rows, q = _int_data(case, n, chunks, seed)
+    if case.data == "order":
+        rows, q, vals, sel = _order_data(case, n, seed)
+        S = _order_reference(case, chunks, vals, sel)[0]
+    else:
+        rows, q = _int_data(case, n, chunks, seed)
+        S = _scores_f64(rows, q)
     rng = np.random.default_rng(seed + 1)
     terms, offs = _forward(rng, n)
     qt, qo = _query_terms(rng, case.B)
@@ -455,7 +572,7 @@ def test_bf16_case_bit_exact(ctx, O, num_cus, case):
     assert launches == len(chunks), (case.name, launches, [(c.begin, c.end) for c in chunks])
     R = idx.search(q, qt, qo, k=case.k, depth=case.depth)
     idx.close()
-    ref = _oracle_lists(O, _scores_f64(rows, q), terms, offs, qt, qo, case.depth, case.k, base)
+    ref = _oracle_lists(O, S, terms, offs, qt, qo, case.depth, case.k, base)
     _assert_lists(L, R, ref, case.name)
 
 
