@@ -1044,6 +1044,69 @@ extern "C" int oi_internal_bm25_index(oi_index *idx, uint64_t *n_postings_out, u
     return OI_OK;
 }
 
+// Not part of the C ABI: the int8 route's query staging and its residual rescreen over the caller's keys, for the tests
+// (tests/test_gpu_residual_rescreen_edges.py).  An index that holds both int8 planes, or a view of one.  The two product launchers
+// run unchanged on the ctx stream, in workspaces of this call's own ("rescreen_probe_*": none of a search's): oi_launch_screen_stage_i8
+// over the B host queries [B, dim] with the index's max_row_norm, int8 copy and residual plane, then oi_launch_rescreen_residual
+// over a pool whose keys [B, stride] and counts [B] are the caller's and whose carry_cap is `cap` (<= stride: the kernel clamps a
+// count to it).  Copied back to the host pointers that are not null: the WHOLE key block (in place), the staged qi8 block
+// [2][n_padded][dim] (h then l, n_padded = B rounded up to 32), qf [4][n_padded] (a, |q^|, c_q, m2), eps2_residual [B], the gate
+// word, and the three scalars the staging read: {X = max_row_norm[0], e_max, e2_max}.
+extern "C" int oi_internal_residual_rescreen(oi_index *idx, const float *queries, uint32_t B, uint64_t *keys, const uint32_t *counts,
+                                             uint64_t stride, uint32_t cap, int8_t *qi8_out, float *qf_out, float *eps2r_out,
+                                             uint32_t *gate_out, float *scalars_out) {
+    if (!idx || !queries || !keys || !counts) { oi_set_error("null argument"); return OI_ERR_INVALID_ARG; }
+    OI_REQUIRE(B >= 1 && B <= 4096, "residual rescreen probe: n_queries=%u outside [1,4096]", B);
+    OI_REQUIRE(stride >= 1 && (uint64_t)B * stride <= (1u << 24) && cap >= 1 && cap <= stride,
+               "residual rescreen probe: stride %llu (at most 2^24 keys in all) or cap %u outside [1, stride]", (unsigned long long)stride, cap);
+    OI_REQUIRE(idx->dim == 384 || idx->dim == 768, "residual rescreen probe: dim %u not instantiated (384, 768)", idx->dim);
+    oi_ctx *ctx = idx->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    OI_REQUIRE(idx->n_docs >= 1 && idx->max_row_norm.p && idx->screen_i8.p && idx->screen_i8r.p,
+               "residual rescreen probe: the index does not hold both int8 planes");
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint32_t dim = idx->dim, n_padded = (B + 31u) & ~31u;
+    const uint64_t n = idx->n_docs;
+    const size_t q_bytes = sizeof(float) * (size_t)B * dim, key_bytes = sizeof(uint64_t) * (size_t)B * stride;
+    const size_t qi8_bytes = ((2 * (size_t)n_padded * dim) + 255) & ~(size_t)255, qf_bytes = sizeof(float) * 4 * (size_t)n_padded;
+    DevBuf &qv = ctx->buf("rescreen_probe_q"), &qb = ctx->buf("rescreen_probe_q_bf16"), &qs = ctx->buf("rescreen_probe_q_i8"),
+           &ws = ctx->buf("rescreen_probe_state"), &pk = ctx->buf("rescreen_probe_keys");
+    OI_CHECK(qv.ensure(q_bytes));
+    OI_CHECK(qb.ensure(sizeof(uint16_t) * (size_t)(n_padded + 64) * dim));
+    OI_CHECK(qs.ensure(qi8_bytes + qf_bytes));
+    OI_CHECK(ws.ensure(sizeof(uint32_t) * (2 * (size_t)B + 4))); // counts[B] eps2[B] gate[4]
+    OI_CHECK(pk.ensure(key_bytes));
+    uint32_t *d_cnt = ws.as<uint32_t>();
+    float *d_eps2 = reinterpret_cast<float *>(d_cnt + B);
+    uint32_t *d_gate = d_cnt + 2 * (size_t)B;
+    int8_t *d_qi8 = qs.as<int8_t>();
+    float *d_qf = reinterpret_cast<float *>(qs.as<unsigned char>() + qi8_bytes);
+    OI_HIP_CHECK(hipMemcpyAsync(qv.p, queries, q_bytes, hipMemcpyHostToDevice, st));
+    OI_HIP_CHECK(hipMemcpyAsync(pk.p, keys, key_bytes, hipMemcpyHostToDevice, st));
+    OI_HIP_CHECK(hipMemsetAsync(ws.p, 0, sizeof(uint32_t) * (2 * (size_t)B + 4), st));
+    OI_HIP_CHECK(hipMemcpyAsync(d_cnt, counts, sizeof(uint32_t) * (size_t)B, hipMemcpyHostToDevice, st));
+    // (as search.hip stages the residual tail: the residual tier's margin over the bf16 screen's, in one array)
+    OI_CHECK(oi_launch_screen_stage_i8(ctx, qv.as<float>(), B, dim, idx->max_row_norm.as<uint32_t>(), idx->screen_i8.as<uint8_t>(), n, d_qi8, d_qf,
+                                       d_gate, qb.as<uint16_t>(), d_eps2, idx->screen_i8r.as<uint8_t>(), d_eps2));
+    PoolView P{};
+    P.keys = pk.as<uint64_t>(); P.carry_cnt = d_cnt; P.stride = stride; P.carry_cap = cap;
+    OI_CHECK(oi_launch_rescreen_residual(ctx, idx->screen_i8r.as<uint8_t>(), idx->screen_i8.as<uint8_t>(), n, dim, idx->doc_id_base, d_qi8, d_qf, B, P));
+    OI_HIP_CHECK(hipMemcpyAsync(keys, pk.p, key_bytes, hipMemcpyDeviceToHost, st));
+    if (qi8_out) OI_HIP_CHECK(hipMemcpyAsync(qi8_out, d_qi8, 2 * (size_t)n_padded * dim, hipMemcpyDeviceToHost, st));
+    if (qf_out) OI_HIP_CHECK(hipMemcpyAsync(qf_out, d_qf, qf_bytes, hipMemcpyDeviceToHost, st));
+    if (eps2r_out) OI_HIP_CHECK(hipMemcpyAsync(eps2r_out, d_eps2, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, st));
+    if (gate_out) OI_HIP_CHECK(hipMemcpyAsync(gate_out, d_gate, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (scalars_out) {
+        const size_t emax_at = oi_screen_i8_meta_offset(n, dim) + 8 * ((size_t)n + 64); // (behind the 64 padding rows: I8S_PAD_ROWS)
+        OI_HIP_CHECK(hipMemcpyAsync(scalars_out, idx->max_row_norm.p, 4, hipMemcpyDeviceToHost, st));
+        OI_HIP_CHECK(hipMemcpyAsync(scalars_out + 1, idx->screen_i8.as<uint8_t>() + emax_at, 4, hipMemcpyDeviceToHost, st));
+        OI_HIP_CHECK(hipMemcpyAsync(scalars_out + 2, idx->screen_i8r.as<uint8_t>() + emax_at, 4, hipMemcpyDeviceToHost, st));
+    }
+    OI_HIP_CHECK(hipStreamSynchronize(st));
+    return OI_OK;
+}
+
 extern "C" int oi_index_set_screen_copy(oi_index *idx, int policy) {
     if (!idx) { oi_set_error("null index"); return OI_ERR_INVALID_ARG; }
     if (idx->is_view) { oi_set_error("index view: read-only (set the policy on the index it was taken from)"); return OI_ERR_STATE; }

@@ -290,6 +290,32 @@ class HybridIndex(PostRetriever):
         _lib.check(self.lib.oi_internal_residual_plane(self.handle, 0, _lib.ptr(j), _lib.ptr(meta), _lib.ptr(e2max), C.byref(nb)))
         return j, meta, float(e2max[0]), int(nb.value)
 
+    def residual_rescreen(self, queries, keys, counts, cap: Optional[int] = None):
+        """The int8 route's query staging and its residual rescreen over the caller's keys (internal, for the tests): the
+        two product launches, in workspaces of their own.  queries: float32 [B, dim]; keys: uint64 [B, stride] rank keys
+        (lower-bound score over ~doc); counts: uint32 [B]; cap: the pool's carry_cap (default: stride).  Needs an index (or a
+        view of one) that holds both int8 planes.  Returns a dict: keys (the whole block after the launch; the caller's array is
+        not written), h and l: int8 [n_padded, dim], qf: float32 [4, n_padded] (a, |q^|, c_q, m2), eps2r: float32 [B] (2 eps2'),
+        gate (int) and X, e_max, e2_max (np.float32: the three scalars the staging read)."""
+        q = _np(queries, np.float32)
+        B = q.shape[0]
+        assert q.shape == (B, self.dim)
+        k = np.array(keys, dtype=np.uint64, order="C")
+        assert k.ndim == 2 and k.shape[0] == B
+        stride = k.shape[1]
+        cnt = _np(counts, np.uint32)
+        assert cnt.shape == (B,)
+        n_padded = (B + 31) & ~31
+        qi8 = np.empty((2, n_padded, self.dim), np.int8)
+        qf = np.empty((4, n_padded), np.float32)
+        eps2r = np.empty(B, np.float32)
+        gate = np.zeros(1, np.uint32)
+        sc = np.zeros(3, np.float32)
+        _lib.check(self.lib.oi_internal_residual_rescreen(self.handle, _lib.ptr(q), B, _lib.ptr(k), _lib.ptr(cnt), stride,
+                                                          stride if cap is None else int(cap), _lib.ptr(qi8), _lib.ptr(qf),
+                                                          _lib.ptr(eps2r), _lib.ptr(gate), _lib.ptr(sc)))
+        return dict(keys=k, h=qi8[0], l=qi8[1], qf=qf, eps2r=eps2r, gate=int(gate[0]), X=sc[0], e_max=sc[1], e2_max=sc[2])
+
     def bm25_index(self):
         """The BM25 structures of a finalized index or of a view of one (internal, for the tests): a dict of n_postings, n_win,
         avgdl (np.float32) and the arrays dib: uint32 [n_postings], impact: float32 [n_postings], cell_start: uint32

@@ -63,8 +63,17 @@ def stage(q, X, e_max, e2_max):
 
 
 def fma32(x, y, z):
-    """f32(x y + z) with one rounding (x y is exact in f64; the f64 sum's own rounding is 2^-29 of an f32 ulp)."""
-    return (x.astype(F64) * y.astype(F64) + z.astype(F64)).astype(F32)
+    """f32(x y + z) with ONE rounding, as v_fma_f32 gives it (finite operands).  x y is exact in f64; the f64 sum is taken with
+    its exact error (two-sum) and rounded to odd, so that the rounding to f32 behind it cannot land on a tie the exact sum is not
+    on -- a plain f64 sum rounds twice and is off by an f32 ulp about once in 2^30 operations, which a bit-for-bit comparison
+    with the device over millions of products meets (tests/test_gpu_residual_rescreen_edges.py)."""
+    p, z = x.astype(F64) * y.astype(F64), np.asarray(z).astype(F64)
+    s = p + z
+    v = s - p
+    e = (p - (s - v)) + (z - v)          # s + e = p + z exactly
+    even = (np.ascontiguousarray(s).view(np.int64) & 1) == 0
+    odd = np.where((e != 0) & even, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
+    return odd.astype(F32)
 
 
 def rescreen(i, s, er, j, t, h, l, a, qn, cq):
