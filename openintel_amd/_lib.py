@@ -247,13 +247,14 @@ SIGNATURES = {
 }
 
 # exports that are NOT part of the C ABI (no declaration in the header): the switch between the int8 route's two second tiers
-# (A/B runs, tests) and the tests' views of an index's residual plane, of its BM25 structures and of the residual tier's staging
-# and rescreen launches
+# (A/B runs, tests) and the tests' views of an index's residual plane, of its BM25 structures, of its long rows in the order the
+# rescoring reads them, and of the residual tier's staging and rescreen launches
 INTERNAL = {
     "oi_internal_residual_rescreen": (_I, [_P, _P, _U32, _P, _P, _U64, _U32, _P, _P, _P, _P, _P]),
     "oi_internal_set_rescreen_tier": (_I, [_P, _I]),
     "oi_internal_residual_plane": (_I, [_P, _I, _P, _P, _P, C.POINTER(_U64)]),
     "oi_internal_bm25_index": (_I, [_P, C.POINTER(_U64), C.POINTER(_U32), C.POINTER(C.c_float), _P, _P, _P, _P, _P]),
+    "oi_internal_long_list": (_I, [_P, C.POINTER(_U32), _P]),
 }
 
 _lib = None

@@ -1015,6 +1015,21 @@ extern "C" int oi_internal_residual_plane(oi_index *idx, int drop, uint8_t *rows
     return OI_OK;
 }
 
+// Not part of the C ABI: the long rows of an index (local row numbers) in the order of its long_list, for the tests -- the order
+// is that of pf_row_norm_class_kernel's atomics, and pf_rescore_kernel packs the passing long rows of a filtered search by their
+// position in it.  *n_out: idx->n_long; rows_out (may be null): room for OI_LONG_ROWS_MAX words, n_long of them written.
+extern "C" int oi_internal_long_list(oi_index *idx, uint32_t *n_out, uint32_t *rows_out) {
+    if (!idx || !n_out) { oi_set_error("null argument"); return OI_ERR_INVALID_ARG; }
+    oi_ctx *ctx = idx->ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    OI_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    *n_out = idx->n_long;
+    if (rows_out && idx->n_long && idx->long_list.p)
+        OI_HIP_CHECK(hipMemcpy(rows_out, idx->long_list.p, sizeof(uint32_t) * idx->n_long, hipMemcpyDeviceToHost));
+    return OI_OK;
+}
+
 // Not part of the C ABI: the BM25 structures of a finalized index (or of a view of one), for the tests.  Always: the number of
 // postings, the windows per term and avgdl.  Copied to the host pointers that are not null: the postings as n_postings pairs
 // {u32 doc_in_block, f32 impact}, cell_start [vocab * n_win + 1], idf [vocab], the impact floors [vocab * OI_BM25_FLOOR_RANKS]

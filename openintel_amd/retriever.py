@@ -262,7 +262,15 @@ class HybridIndex(PostRetriever):
         _lib.check(self.lib.oi_index_long_rows(self.handle, C.byref(n)))
         return int(n.value)
 
-    SCREEN_COPY_AUTO, SCREEN_COPY_NEVER, SCREEN_COPY_ALWAYS = _lib.OI_SCREEN_COPY_AUTO, _lib.OI_SCREEN_COPY_NEVER, _lib.OI_SCREEN_COPY_ALWAYS
+    def long_list(self) -> np.ndarray:
+        """The long rows (local row numbers) in the order the rescoring reads them (internal, for the tests): a filtered search
+        packs the passing ones by their position in this list."""
+        n = C.c_uint32()
+        rows = np.zeros(1024, np.uint32)            # OI_LONG_ROWS_MAX
+        _lib.check(self.lib.oi_internal_long_list(self.handle, C.byref(n), _lib.ptr(rows)))
+        return rows[:int(n.value)].copy()
+
+    SCREEN_COPY_AUTO,SCREEN_COPY_NEVER, SCREEN_COPY_ALWAYS = _lib.OI_SCREEN_COPY_AUTO, _lib.OI_SCREEN_COPY_NEVER, _lib.OI_SCREEN_COPY_ALWAYS
 
     def set_screen_copy(self, policy: int) -> None:
         """The bf16 screening copy of an f32 corpus (oi_index_set_screen_copy): SCREEN_COPY_AUTO (default: made at finalize

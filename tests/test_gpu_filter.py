@@ -2,7 +2,8 @@
 passing documents and cut at depth.  Small-integer embeddings make every dot product exact, so each cosine route (the int8
 tier, the copy screen, the f32-stream screen's route, exact and split at B = 1, 9, 64, the generic dim, a bf16 corpus) and
 every BM25 mode must give exactly that, bit for bit, RRF included.  Larger corpora check the screen's chunk edges and both
-phases of the BM25 stream schedule against the CPU oracle."""
+phases of the BM25 stream schedule against the CPU oracle.  The chunk, query-group, long-row and gate edges of the filtered
+int8, copy-screen and bf16-corpus kernels live in test_gpu_filter_edges.py, bit for bit."""
 import numpy as np
 import pytest
 
