@@ -3,7 +3,7 @@
 // Users: cosine_screen_i8.hip and cosine_bf16_qsplit's half-tile ring (cosine_bf16.hip) directly; oi_ksplit_tile.h: what
 // cosine_ksplit and cosine_split (.hip) are written on; and oi_screen_tile.h: the tile pipeline that cosine_prefilter,
 // cosine_screen_copy, cosine_bf16 (solo and pair), cosine_volume and cosine_summary (.hip, the last two through oi_volume.h) are
-// written on.
+// written on.  bm25_stream.hip takes the address form (oi_dma_lane_word, oi_dma_global_piece) and the runtime-count wait.
 //
 // THE CONTRACT of an LDS-DMA load (`buffer_load_dwordx4 ... lds`: 64 lanes x 16 B from each lane's own source offset into
 // 1 KiB of LDS at M0 + 16 * lane, no register destination):
@@ -24,6 +24,11 @@
 //     before the ring starts (__builtin_amdgcn_s_waitcnt), or hipcc re-waits for them with vmcnt(0) inside the tile loop and
 //     drains the ring; and survivors leave 64 at a time through the staging ring below, not one store each.
 //   * Before the LDS goes back (kernel end) every DMA has landed: oi_wait_vm<0>().
+//   * The `global_load_lds_*` form (bm25_stream.hip: oi_dma_lane_word, oi_dma_global_piece) takes an ADDRESS, not a
+//     descriptor: nothing checks a range and no lane reads zeros, so every lane's address must be readable.  That is why
+//     the postings array is padded (a chunk may run 1 KiB past its run) and why a lane without a run points at some valid
+//     word.  M0 is handled exactly as above (saved, set from a readfirstlane, an s_nop in front of the load, restored), the
+//     loads sit in the same in-order queue and are waited for with the same counted waits.
 #pragma once
 
 #include <type_traits>
@@ -112,6 +117,56 @@ __device__ __forceinline__ void oi_static_for(F &&f) {
 template <int N>
 __device__ __forceinline__ void oi_wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// The same with a wave-uniform RUNTIME count y ("the y issued after the one I need" may stay in flight; the instruction
+// takes an immediate, hence the switch).  A smaller y than the truth only waits longer: 12 stands for every y above it.
+__device__ __forceinline__ void oi_wait_vm_count(uint32_t y) {
+    switch (__builtin_amdgcn_readfirstlane(y)) {
+    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
+    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
+    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
+    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
+    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
+    case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
+    default: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
+    }
+}
+
+// ---- the address form (no descriptor: see the contract).
+// One dword per lane from each lane's OWN address into lds_dst + 4 * lane (256 B of LDS).
+__device__ __forceinline__ void oi_dma_lane_word(const uint32_t *gptr, uint32_t lds_dst) {
+    uint32_t keep;
+    const uint32_t d = __builtin_amdgcn_readfirstlane(lds_dst);
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %2\n\t"
+        "s_nop 4\n\t"
+        "global_load_lds_dword %1, off\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(gptr), "s"(d)
+        : "memory");
+}
+// One 1-KiB piece from a WAVE-UNIFORM base (an SGPR pair) plus a per-lane byte offset (16 * lane for a contiguous KiB):
+// lane l loads 16 B from base + voff into lds_dst + 16 l.
+__device__ __forceinline__ void oi_dma_global_piece(const void *base, uint32_t voff, uint32_t lds_dst) {
+    uint32_t keep;
+    const uint32_t d = __builtin_amdgcn_readfirstlane(lds_dst);
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %3\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dwordx4 %1, %2\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(voff), "s"(base), "s"(d)
+        : "memory");
 }
 
 // ---- survivor staging of the screens and of cosine_bf16_qsplit: OI_STAGE entries per wave (a power of two) in LDS, flushed
