@@ -994,6 +994,76 @@ int oi_mention_summary(oi_index *idx, const uint32_t *query_terms, const uint32_
                        oi_social_counters *out /* [n_queries][n_cells] */);
 
 /* ------------------------------------------------------------------------- */
+/* Narrative terms: the distinguishing terms of each cluster of posts          */
+/* ------------------------------------------------------------------------- */
+/*
+ * oi_narratives_fit and oi_similar_share say which narratives there are, how big they are and which post belongs to which;
+ * these calls say what a narrative is ABOUT: for every cluster of a labelling, the terms its posts hold more often than the
+ * assigned posts at large (the step a host otherwise takes with c-TF-IDF on the CPU, after pulling the labels and the forward
+ * index off the device).  They read the postings oi_index_finalize made and the labels where they are.  The lexical
+ * counterpart of oi_label_sums, as oi_mention_summary is of oi_similar_summary.  The term ids they return are valid
+ * query_terms of oi_mention_summary and of every oi_search* call.  Builder-defined like the whole retrieval path.
+ *
+ * The table.  labels[d] is a u32 per LOCAL row.  A label >= n_clusters (0xFFFFFFFF included) is "no cluster", as in
+ * oi_label_sums: the row counts nowhere, and there is no error for it.
+ *   sizes[c]     = the number of local rows with labels[d] == c; it equals the counts of oi_label_sums for the same labels.
+ *   counts[t][c] = the number of local documents d with labels[d] == c that have a posting for term t.  A term counts once
+ *                  per document, however often it occurs.  The layout is [vocab][n_clusters] u32, term-major like the postings.
+ * All of these are exact integers: the table does not depend on the grid, the order of any atomics or the run, and the tables
+ * and sizes of document shards ADD.
+ *
+ * The ranked cut is a function of a table, sizes and a spec only.
+ *   A = sum_c sizes[c] and dfA[t] = sum_c counts[t][c], taken in 64 bits.
+ *   Term t is ELIGIBLE for cluster c when counts[t][c] >= max(min_df, 1).
+ *   excess(c, t) = (int64)counts[t][c] * A - (int64)sizes[c] * dfA[t]: A times (observed minus expected documents of c
+ *     holding t).  A term spread evenly over the clusters scores about 0 whatever its frequency, a frequent term concentrated
+ *     in c scores high, a rare term scores low even at high lift.
+ *   The order within a cluster is excess descending, then counts[t][c] descending, then t ascending: a total order, so the
+ *     lists are unique.  With n_clusters == 1 every excess is 0 and the list holds the cluster's most frequent terms.
+ *   Cluster c returns n[c] = min(top, number of eligible terms) records {term, df_cluster = counts[t][c], df_assigned =
+ *     dfA[t] (its low 32 bits), reserved = 0, excess}; entries at and beyond n[c] are all-zero records with term = 0xFFFFFFFF.
+ *   With df_cluster, df_assigned, sizes[c] and A the host has every integer it needs to re-rank by lift, PMI or c-TF-IDF.
+ * Overflow is ruled out by a check, not by saturation: A <= 2^31 - 1 is required, and then every product is below 2^62 for a
+ * consistent table (dfA[t] <= A).  An inconsistent caller-made table wraps in two's complement; nothing is read or written
+ * out of bounds for it.
+ *
+ * oi_label_term_counts -- labels to the table and the sizes.  oi_label_terms_rank -- a table and sizes to the lists; a call
+ * of its own for the reason oi_centroids_from_sums is one: a sharded host adds the per-rank tables and sizes with its own
+ * all-reduce and ranks the total.  oi_label_terms -- their composition for a single-GPU host: the table never leaves the ctx
+ * workspace; sizes_out may be NULL.
+ *
+ * Rules.  oi_label_term_counts and oi_label_terms need a FINALIZED index (the postings): otherwise OI_ERR_STATE.  They need
+ * NO embeddings, signals or attributes, and they work on a view.  n_clusters in [1, OI_MAX_CENTROIDS]; vocab * n_clusters <=
+ * OI_MAX_LABEL_TERM_CELLS; top in [1, OI_MAX_LABEL_TERMS]; reserved == 0; min_df is any value (0 means 1).  oi_label_terms
+ * additionally requires n_docs <= 2^31 - 1 (so A is in range without reading the sizes back).  sizes_host and spec are always
+ * host pointers (the sizes are at most 2 KB, the A check runs on them, and they are read before the call returns); location
+ * covers the labels, the tables, the records, n_out, and sizes_out of oi_label_term_counts and oi_label_terms.  With OI_DEVICE
+ * the calls are asynchronous on the ctx stream.  Not captured by graph replay.  A null handle, spec or buffer, a number out of
+ * range, A > 2^31 - 1, a bad location -> OI_ERR_INVALID_ARG with the offending number in the message; every argument check
+ * precedes the first device call.
+ * Workspace per searching context (oi_workspace_bytes counts it): "label_terms" holds the table of the composite call
+ * (4 B x vocab x n_clusters), the sizes, and the rank's partial lists (16 B x top x n_clusters per slice of 1024 terms, and
+ * 1/64 of that again); "label_terms_plan" holds 4 B per 16384 postings.  With OI_HOST the staged labels, table and records
+ * are held in "label_terms_io".
+ * Profile tags: "label_term_counts" (the pass over the postings and the pass over the labels) and "label_terms_rank".
+ *
+ * NOT covered: a time axis (one list per cluster and bucket); a background other than the assigned posts, such as the whole
+ * index's df; oi_search_sharded* / oi_pipeline_* forms; mapping ids back to words inside the library (the vocabulary is
+ * hashed: a host names the ids by hashing the tokens of a sample of posts with oi_text_terms).
+ */
+#define OI_MAX_LABEL_TERMS 64u             /* `top` per cluster */
+#define OI_MAX_LABEL_TERM_CELLS (1u << 28) /* vocab * n_clusters: 1 GiB of u32 at most */
+typedef struct oi_label_terms_spec { uint32_t top, min_df, reserved[2]; } oi_label_terms_spec;
+typedef struct oi_label_term { uint32_t term, df_cluster, df_assigned, reserved; int64_t excess; } oi_label_term;
+int oi_label_term_counts(oi_index *idx, const uint32_t *labels /* [n_docs] by LOCAL row */, uint32_t n_clusters, int location,
+                         uint32_t *counts_out /* [vocab][n_clusters] */, uint64_t *sizes_out /* [n_clusters] */);
+int oi_label_terms_rank(oi_ctx *ctx, const uint32_t *counts, const uint64_t *sizes_host, uint32_t vocab, uint32_t n_clusters,
+                        const oi_label_terms_spec *spec, int location,
+                        oi_label_term *terms_out /* [n_clusters][top] */, uint32_t *n_out /* [n_clusters] */);
+int oi_label_terms(oi_index *idx, const uint32_t *labels, uint32_t n_clusters, const oi_label_terms_spec *spec, int location,
+                   oi_label_term *terms_out, uint32_t *n_out, uint64_t *sizes_out /* or NULL */);
+
+/* ------------------------------------------------------------------------- */
 /* Text to term ids: the tokeniser and the hashed vocabulary                   */
 /* ------------------------------------------------------------------------- */
 /*

@@ -29,6 +29,9 @@ int main(void) {
         offsetof(oi_groups_spec, n_keys) != 8 || offsetof(oi_groups_spec, top) != 12 || offsetof(oi_groups_spec, rank_by) != 16 ||
         offsetof(oi_groups_spec, min_total) != 20 || sizeof(oi_social_counters) != 64)
         return fail("oi_groups_spec layout", (int)sizeof(oi_groups_spec));
+    /* the narrative-terms records as the bindings lay them out: 16-byte spec, 24-byte record with the excess at 16 */
+    if (sizeof(oi_label_terms_spec) != 16 || sizeof(oi_label_term) != 24 || offsetof(oi_label_term, excess) != 16)
+        return fail("oi_label_term layout", (int)sizeof(oi_label_term));
     rc = oi_create(0, &ctx);
     if (rc == OI_ERR_NO_DEVICE) {
         if (ctx != NULL || oi_last_error()[0] == '\0') return fail("no-device contract", rc);

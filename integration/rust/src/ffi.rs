@@ -89,6 +89,28 @@ pub struct OiNarrativeInfo {
 }
 pub const OI_MAX_CENTROIDS: u32 = 256;
 
+/// `oi_label_terms_spec`: records per cluster (1 ..= 64), the smallest df_cluster of an eligible term (0 means 1), reserved (0).
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
+pub struct OiLabelTermsSpec {
+    pub top: u32,
+    pub min_df: u32,
+    pub reserved: [u32; 2],
+}
+/// `oi_label_term`: one distinguishing term of a cluster -- the term id (`u32::MAX`: no entry), the cluster's documents that hold
+/// it, the assigned documents that hold it, reserved (0), excess = df_cluster * A - sizes[c] * df_assigned.  24 bytes.
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default, PartialEq)]
+pub struct OiLabelTerm {
+    pub term: u32,
+    pub df_cluster: u32,
+    pub df_assigned: u32,
+    pub reserved: u32,
+    pub excess: i64,
+}
+pub const OI_MAX_LABEL_TERMS: u32 = 64;
+pub const OI_MAX_LABEL_TERM_CELLS: u32 = 1 << 28;
+
 /// `oi_seed_spec`: method (`OI_SEED_*`), trials (candidates per seed, 1 ..= 8; 1 with farthest-first), the RNG seed,
 /// `oi_narrative_spec`'s time axis, reserved (0).  32 bytes.
 #[repr(C)]
@@ -336,6 +358,16 @@ extern "C" {
     // be null; spec, filter and info_host are host pointers whatever `location`)
     pub fn oi_narratives_seed(idx: *mut OiIndex, n_clusters: u32, spec: *const OiSeedSpec, filter: *const OiDocFilter,
                               location: c_int, seeds_out: *mut f32, rows_out: *mut u32, info_host: *mut OiSeedInfo) -> c_int;
+
+    // narrative terms: labels -> the [vocab][n_clusters] table of documents per (term, cluster) and the cluster sizes (exact,
+    // shards add); a table and sizes -> the ranked lists; their composition (sizes_out may be null; spec and sizes_host are
+    // host pointers whatever `location`)
+    pub fn oi_label_term_counts(idx: *mut OiIndex, labels: *const u32, n_clusters: u32, location: c_int, counts_out: *mut u32,
+                                sizes_out: *mut u64) -> c_int;
+    pub fn oi_label_terms_rank(ctx: *mut OiCtx, counts: *const u32, sizes_host: *const u64, vocab: u32, n_clusters: u32,
+                               spec: *const OiLabelTermsSpec, location: c_int, terms_out: *mut OiLabelTerm, n_out: *mut u32) -> c_int;
+    pub fn oi_label_terms(idx: *mut OiIndex, labels: *const u32, n_clusters: u32, spec: *const OiLabelTermsSpec, location: c_int,
+                          terms_out: *mut OiLabelTerm, n_out: *mut u32, sizes_out: *mut u64) -> c_int;
 
     pub fn oi_pipeline_create(idx: *mut OiIndex, comm: *mut OiComm, lanes: u32, max_queries: u32, max_query_terms: u32,
                               depth: u32, k: u32, out: *mut *mut OiPipeline) -> c_int;

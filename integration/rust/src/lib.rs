@@ -67,6 +67,23 @@ pub fn centroids_from_sums(ctx: &HipCtx, sums: &[i64], counts: &[u64], previous:
     Ok(out)
 }
 
+/// A table and sizes (`HipIndex::label_term_counts`, or the total over the shards of the documents) to the ranked lists
+/// (`oi_label_terms_rank`): per cluster its eligible terms (df_cluster >= max(min_df, 1)), best first by excess, then
+/// df_cluster, then the smaller id.  The sum of the sizes must not exceed 2^31 - 1.
+pub fn rank_label_terms(ctx: &HipCtx, counts: &[u32], sizes: &[u64], top: u32, min_df: u32) -> Result<Vec<Vec<ffi::OiLabelTerm>>, HipError> {
+    let k = sizes.len();
+    assert!(k > 0 && counts.len() % k == 0);
+    let spec = ffi::OiLabelTermsSpec { top, min_df, reserved: [0, 0] };
+    let width = top.clamp(1, ffi::OI_MAX_LABEL_TERMS) as usize;
+    let mut rec = vec![ffi::OiLabelTerm::default(); k * width];
+    let mut n = vec![0u32; k];
+    check(unsafe {
+        ffi::oi_label_terms_rank(ctx.raw(), counts.as_ptr(), sizes.as_ptr(), (counts.len() / k) as u32, k as u32, &spec, ffi::OI_HOST,
+                                 rec.as_mut_ptr(), n.as_mut_ptr())
+    })?;
+    Ok((0..k).map(|c| rec[c * width..c * width + n[c] as usize].to_vec()).collect())
+}
+
 /// Gather strings into the FFI layout: one UTF-8 blob + (n + 1) u64 offsets.  In the reference every post owns
 /// its text as a separate heap `String` (social_post.rs:25-27).
 pub fn gather<'a, I: IntoIterator<Item = &'a str>>(texts: I) -> (Vec<u8>, Vec<u64>) {
@@ -432,6 +449,30 @@ impl HipIndex {
         let (mut sums, mut counts) = (vec![0i64; k * self.dim], vec![0u64; k]);
         check(unsafe { ffi::oi_label_sums(self.idx, labels.as_ptr(), n_clusters, ffi::OI_HOST, sums.as_mut_ptr(), counts.as_mut_ptr()) })?;
         Ok((sums, counts))
+    }
+    /// The documents per (term, cluster) of a labelling (`oi_label_term_counts`): ([vocab * n_clusters] term-major, sizes
+    /// [n_clusters]) over the postings of a finalized index; a term counts once per document, any label >= n_clusters is "no
+    /// cluster".  Exact: shards of the documents add.  `vocab` is the index's.
+    pub fn label_term_counts(&self, labels: &[u32], n_clusters: u32, vocab: u32) -> Result<(Vec<u32>, Vec<u64>), HipError> {
+        assert_eq!(labels.len(), self.n_docs);
+        let k = n_clusters as usize;
+        let (mut counts, mut sizes) = (vec![0u32; k.max(1) * vocab as usize], vec![0u64; k.max(1)]);
+        check(unsafe { ffi::oi_label_term_counts(self.idx, labels.as_ptr(), n_clusters, ffi::OI_HOST, counts.as_mut_ptr(), sizes.as_mut_ptr()) })?;
+        Ok((counts, sizes))
+    }
+    /// What each cluster of a labelling is about (`oi_label_terms`): per cluster its distinguishing terms, best first, and the
+    /// cluster sizes.  The ids are valid query terms of `mention_summary` and of every search.
+    pub fn label_terms(&self, labels: &[u32], n_clusters: u32, top: u32, min_df: u32) -> Result<(Vec<Vec<ffi::OiLabelTerm>>, Vec<u64>), HipError> {
+        assert_eq!(labels.len(), self.n_docs);
+        let k = n_clusters as usize;
+        let spec = ffi::OiLabelTermsSpec { top, min_df, reserved: [0, 0] };
+        let width = top.clamp(1, ffi::OI_MAX_LABEL_TERMS) as usize;
+        let mut rec = vec![ffi::OiLabelTerm::default(); k.max(1) * width];
+        let (mut n, mut sizes) = (vec![0u32; k.max(1)], vec![0u64; k.max(1)]);
+        check(unsafe {
+            ffi::oi_label_terms(self.idx, labels.as_ptr(), n_clusters, &spec, ffi::OI_HOST, rec.as_mut_ptr(), n.as_mut_ptr(), sizes.as_mut_ptr())
+        })?;
+        Ok(((0..k).map(|c| rec[c * width..c * width + n[c] as usize].to_vec()).collect(), sizes))
     }
     /// Which narratives are there (`oi_narratives_fit`): k-means over the index on the device, from `seeds` ([k * dim]).
     /// Returns the centroids, records and (with `labels`) labels of the LAST assignment step and what the loop did;

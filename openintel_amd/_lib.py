@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libopenintel_hip.so")
 # (No environment override here: tests/ and bench.py always load THIS file.  The tools that time -DOI_ABLATION builds set
@@ -24,6 +26,8 @@ OI_MAX_CENTROIDS = 256
 OI_SEED_KMEANSPP, OI_SEED_FARTHEST = 0, 1
 OI_MAX_SEED_TRIALS = 8
 OI_MAX_MENTION_TERMS = 64
+OI_MAX_LABEL_TERMS = 64
+OI_MAX_LABEL_TERM_CELLS = 1 << 28
 OI_MENTION_AXIS_TIME, OI_MENTION_AXIS_KEY = 0, 1
 OI_GROUP_RANK_TOTAL, OI_GROUP_RANK_SPEC, OI_GROUP_RANK_BULLISH, OI_GROUP_RANK_BEARISH = 0, 1, 2, 3
 OI_BM25_BLOCK_DOCS = 32768
@@ -161,6 +165,21 @@ class MentionSpec(C.Structure):
     ]
 
 
+class LabelTermsSpec(C.Structure):
+    """oi_label_terms_spec: records per cluster (1 .. OI_MAX_LABEL_TERMS), the smallest counts[t][c] of an eligible term (0 means
+    1), reserved (0).  16 bytes."""
+    _fields_ = [
+        ("top", C.c_uint32),
+        ("min_df", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+# oi_label_term: 24 bytes
+LABEL_TERM_DTYPE = np.dtype([("term", "<u4"), ("df_cluster", "<u4"), ("df_assigned", "<u4"), ("reserved", "<u4"), ("excess", "<i8")])
+assert LABEL_TERM_DTYPE.itemsize == 24
+
+
 _P = C.c_void_p
 _U32, _U64, _I = C.c_uint32, C.c_uint64, C.c_int
 
@@ -229,6 +248,9 @@ SIGNATURES = {
     "oi_centroids_from_sums": (_I, [_P, _P, _P, _P, _U32, _U32, _I, _P]),
     "oi_narratives_fit": (_I, [_P, _P, _U32, _P, _P, _I, _P, _P, _P, _P]),
     "oi_narratives_seed": (_I, [_P, _U32, _P, _P, _I, _P, _P, _P]),
+    "oi_label_term_counts": (_I, [_P, _P, _U32, _I, _P, _P]),
+    "oi_label_terms_rank": (_I, [_P, _P, _P, _U32, _U32, _P, _I, _P, _P]),
+    "oi_label_terms": (_I, [_P, _P, _U32, _P, _I, _P, _P, _P]),
     "oi_text_terms": (_I, [_P, _P, _P, _U64, _U64, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_query_terms": (_I, [_P, _P, _P, _U32, _U32, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_index_set_text": (_I, [_P, _P, _P, _U64, _I]),

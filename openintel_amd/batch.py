@@ -396,7 +396,8 @@ def discover_narratives(index, seeds, threshold, **kw):
     `seeds` may also be an int: that many seeds are first chosen on the device by `index.seed_narratives` (oi_narratives_seed)
     among the rows the fit assigns from -- with the fit's `filter`, `n_buckets`, `stamp_origin` and `bucket_width`, and with
     `method`, `trials` and `seed` taken from kw (they do not reach the fit).  The seed vectors stay on the device when the
-    index's rows were given as device tensors."""
+    index's rows were given as device tensors.
+    What each narrative is ABOUT -- its distinguishing terms -- comes from `describe_narratives(index, fit)` (fit with labels=True)."""
     from .analyzer import COUNTERS_DTYPE
     import numbers
     if isinstance(seeds, numbers.Integral) and not isinstance(seeds, bool):
@@ -409,6 +410,78 @@ def discover_narratives(index, seeds, threshold, **kw):
     if hasattr(rec, "data_ptr"):
         rec = rec.cpu().numpy().view(COUNTERS_DTYPE).reshape(rec.shape[0], rec.shape[1])
     return fit, share_of_voice(rec)
+
+
+@dataclass
+class NarrativeTerm:
+    """One distinguishing term of a narrative: the term id (valid in query_terms of mention_summary and every search), the word
+    a text sample names it with (None without a sample), df = the narrative's posts that hold it, df_assigned = the assigned
+    posts that hold it, lift = (df / size of the narrative) / (df_assigned / assigned posts)."""
+    term: int
+    word: Optional[str]
+    df: int
+    df_assigned: int
+    lift: float
+
+
+def _term_words(index, texts):
+    """id -> the most frequent token of `texts` that the library's own hash sends to it (ties: the smaller token)."""
+    import collections
+    import re
+    import numpy as np
+    from . import retriever
+    freq = collections.Counter()
+    for t in texts:
+        freq.update(re.findall(r"[0-9a-z]+", t.lower()))
+    tokens = sorted(freq)
+    if not tokens:
+        return {}
+    ids, offs = retriever.text_terms(index.ctx, tokens, index.vocab)
+    ids, offs = np.asarray(ids), np.asarray(offs)
+    words = {}
+    for i, tok in enumerate(tokens):
+        if int(offs[i + 1]) - int(offs[i]) != 1:     # (the tokeniser cut it differently or dropped it: it names no single id)
+            continue
+        tid = int(ids[int(offs[i])])
+        best = words.get(tid)
+        if best is None or freq[tok] > freq[best]:   # (a collision is not an error: the more frequent token names the id)
+            words[tid] = tok
+    return words
+
+
+def describe_narratives(index, fit_or_labels, n_clusters=None, top=10, min_df=1, texts=None):
+    """What every narrative is about: per cluster, the list of its distinguishing terms as NarrativeTerm, best first
+    (`index.label_terms`, oi_label_terms: one pass over the BM25 postings on the device, ranked by excess = A * (observed -
+    expected posts of the cluster holding the term); the index must be finalized).
+    fit_or_labels: a NarrativeFit made with labels=True (n_clusters is then its number of centroids), or a label array
+    [n_docs] by local row (numpy or torch CUDA tensor) with n_clusters given.  texts: any sample of posts, or the corpus
+    itself, to name the hashed ids with: it is lowercased and split into maximal [0-9a-z] runs, the distinct tokens go through
+    retriever.text_terms with the index's vocab, and an id is named by the most frequent token that hashes to it."""
+    from . import retriever
+    labels = fit_or_labels
+    if hasattr(fit_or_labels, "centroids") and hasattr(fit_or_labels, "labels"):
+        labels = fit_or_labels.labels
+        if labels is None:
+            raise ValueError("describe_narratives: the fit carries no labels (fit_narratives(..., labels=True))")
+        if n_clusters is None:
+            n_clusters = int(fit_or_labels.centroids.shape[0])
+    if n_clusters is None:
+        raise ValueError("describe_narratives: n_clusters is required with a label array")
+    rec, n, sizes = index.label_terms(labels, int(n_clusters), top=top, min_df=min_df)
+    rec = retriever.label_term_records(rec)
+    if hasattr(n, "data_ptr"):
+        n, sizes = n.cpu().numpy(), sizes.cpu().numpy()
+    words = _term_words(index, texts) if texts is not None else {}
+    assigned = int(sum(int(x) for x in sizes))
+    out = []
+    for c in range(int(n_clusters)):
+        terms = []
+        for r in rec[c][:int(n[c])]:
+            df, dfa = int(r["df_cluster"]), int(r["df_assigned"])
+            lift = (df / int(sizes[c])) / (dfa / assigned) if int(sizes[c]) and dfa and assigned else 0.0
+            terms.append(NarrativeTerm(int(r["term"]), words.get(int(r["term"])), df, dfa, lift))
+        out.append(terms)
+    return out
 
 
 # ----------------------------------------------------------------------------- wire format (#[derive(Serialize)])

@@ -2144,6 +2144,140 @@ extern "C" int oi_narratives_seed(oi_index *idx, uint32_t K, const oi_seed_spec 
     return OI_OK;
 }
 
+// ---------------------------------------------------------------- narrative terms (label_terms.hip)
+// The family's order of checks: the spec, the numbers, the buffers, the location, then the handle and its state; all of them
+// precede the first HIP call.  Never captured.
+static int label_terms_check_spec(const char *call, const oi_label_terms_spec *spec) {
+    if (!spec) { oi_set_error("%s: null spec", call); return OI_ERR_INVALID_ARG; }
+    OI_REQUIRE(spec->top >= 1 && spec->top <= OI_MAX_LABEL_TERMS, "%s: top=%u outside [1,%u]", call, spec->top, OI_MAX_LABEL_TERMS);
+    OI_REQUIRE(spec->reserved[0] == 0 && spec->reserved[1] == 0, "%s: reserved=%u (must be 0)", call,
+               spec->reserved[0] ? spec->reserved[0] : spec->reserved[1]);
+    return OI_OK;
+}
+static int label_terms_check_clusters(const char *call, uint32_t K) {
+    OI_REQUIRE(K >= 1 && K <= OI_MAX_CENTROIDS, "%s: n_clusters=%u outside [1,%u]", call, K, OI_MAX_CENTROIDS);
+    return OI_OK;
+}
+static int label_terms_check_cells(const char *call, uint32_t vocab, uint32_t K) {
+    OI_REQUIRE(vocab >= 1, "%s: vocab=%u", call, vocab);
+    OI_REQUIRE((uint64_t)vocab * K <= OI_MAX_LABEL_TERM_CELLS, "%s: vocab * n_clusters = %llu cells, more than %u", call,
+               (unsigned long long)vocab * K, OI_MAX_LABEL_TERM_CELLS);
+    return OI_OK;
+}
+// the handle and its state; takes the ctx lock
+static int label_terms_check_index(const char *call, oi_index *idx, uint32_t K, std::unique_lock<std::mutex> &g) {
+    if (!idx) { oi_set_error("%s: null index", call); return OI_ERR_INVALID_ARG; }
+    OI_CHECK(label_terms_check_cells(call, idx->vocab, K));
+    g = std::unique_lock<std::mutex>(idx->ctx->mu);
+    if (!idx->finalized || !idx->cell_start.p || (idx->n_postings && !idx->postings.p)) {
+        oi_set_error("%s: the index is not finalized (oi_index_finalize makes the postings)", call);
+        return OI_ERR_STATE;
+    }
+    return OI_OK;
+}
+static size_t lt_up(size_t b) { return (b + 255) & ~(size_t)255; }
+
+extern "C" int oi_label_term_counts(oi_index *idx, const uint32_t *labels, uint32_t K, int location, uint32_t *counts_out, uint64_t *sizes_out) {
+    OI_CHECK(label_terms_check_clusters("label_term_counts", K));
+    OI_REQUIRE(labels && counts_out && sizes_out, "label_term_counts: null buffer");
+    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "label_term_counts: bad location %d", location);
+    std::unique_lock<std::mutex> g;
+    OI_CHECK(label_terms_check_index("label_term_counts", idx, K, g));
+    oi_ctx *ctx = idx->ctx;
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    if (location == OI_DEVICE) return oi_launch_label_term_counts(idx, labels, K, counts_out, sizes_out);
+    hipStream_t st = ctx->stream;
+    const size_t lb = lt_up(sizeof(uint32_t) * (size_t)idx->n_docs), tb = sizeof(uint32_t) * (size_t)idx->vocab * K, sb = sizeof(uint64_t) * (size_t)K;
+    DevBuf &w = ctx->buf("label_terms_io");
+    OI_CHECK(w.ensure(lb + lt_up(tb) + sb));
+    uint8_t *d = w.as<uint8_t>();
+    if (idx->n_docs) OI_HIP_CHECK(hipMemcpyAsync(d, labels, sizeof(uint32_t) * (size_t)idx->n_docs, hipMemcpyHostToDevice, st));
+    OI_CHECK(oi_launch_label_term_counts(idx, reinterpret_cast<const uint32_t *>(d), K, reinterpret_cast<uint32_t *>(d + lb),
+                                         reinterpret_cast<uint64_t *>(d + lb + lt_up(tb))));
+    OI_HIP_CHECK(hipMemcpyAsync(counts_out, d + lb, tb, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipMemcpyAsync(sizes_out, d + lb + lt_up(tb), sb, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipStreamSynchronize(st));
+    return OI_OK;
+}
+
+extern "C" int oi_label_terms_rank(oi_ctx *ctx, const uint32_t *counts, const uint64_t *sizes_host, uint32_t vocab, uint32_t K,
+                                   const oi_label_terms_spec *spec, int location, oi_label_term *terms_out, uint32_t *n_out) {
+    static_assert(sizeof(oi_label_term) == 24 && sizeof(oi_label_terms_spec) == 16, "the records are 24 bytes, the spec 16");
+    OI_CHECK(label_terms_check_spec("label_terms_rank", spec));
+    OI_CHECK(label_terms_check_clusters("label_terms_rank", K));
+    OI_CHECK(label_terms_check_cells("label_terms_rank", vocab, K));
+    OI_REQUIRE(counts && sizes_host && terms_out && n_out, "label_terms_rank: null buffer");
+    unsigned long long A = 0; // (saturating: 256 sizes of 2^64 - 1 must not wrap past the check)
+    for (uint32_t c = 0; c < K; ++c) A = A + sizes_host[c] < A ? ~0ull : A + sizes_host[c];
+    OI_REQUIRE(A <= 0x7FFFFFFFull, "label_terms_rank: A = %llu assigned rows, more than 2^31 - 1", A);
+    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "label_terms_rank: bad location %d", location);
+    OI_REQUIRE(ctx, "label_terms_rank: null ctx");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    const size_t scratch = oi_label_terms_rank_scratch(vocab, K, spec->top);
+    DevBuf &ws = ctx->buf("label_terms");
+    OI_CHECK(ws.ensure(scratch));
+    if (location == OI_DEVICE)
+        return oi_launch_label_terms_rank(ctx, counts, sizes_host, nullptr, vocab, K, spec->top, spec->min_df, ws.p, terms_out, n_out);
+    hipStream_t st = ctx->stream;
+    const size_t tb = lt_up(sizeof(uint32_t) * (size_t)vocab * K), rb = sizeof(oi_label_term) * (size_t)K * spec->top, nb = sizeof(uint32_t) * (size_t)K;
+    DevBuf &w = ctx->buf("label_terms_io");
+    OI_CHECK(w.ensure(tb + lt_up(rb) + nb));
+    uint8_t *d = w.as<uint8_t>();
+    OI_HIP_CHECK(hipMemcpyAsync(d, counts, sizeof(uint32_t) * (size_t)vocab * K, hipMemcpyHostToDevice, st));
+    OI_CHECK(oi_launch_label_terms_rank(ctx, reinterpret_cast<const uint32_t *>(d), sizes_host, nullptr, vocab, K, spec->top, spec->min_df, ws.p,
+                                        reinterpret_cast<oi_label_term *>(d + tb), reinterpret_cast<uint32_t *>(d + tb + lt_up(rb))));
+    OI_HIP_CHECK(hipMemcpyAsync(terms_out, d + tb, rb, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipMemcpyAsync(n_out, d + tb + lt_up(rb), nb, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipStreamSynchronize(st));
+    return OI_OK;
+}
+
+extern "C" int oi_label_terms(oi_index *idx, const uint32_t *labels, uint32_t K, const oi_label_terms_spec *spec, int location,
+                              oi_label_term *terms_out, uint32_t *n_out, uint64_t *sizes_out) {
+    OI_CHECK(label_terms_check_spec("label_terms", spec));
+    OI_CHECK(label_terms_check_clusters("label_terms", K));
+    OI_REQUIRE(labels && terms_out && n_out, "label_terms: null buffer");
+    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "label_terms: bad location %d", location);
+    std::unique_lock<std::mutex> g;
+    OI_CHECK(label_terms_check_index("label_terms", idx, K, g));
+    OI_REQUIRE(idx->n_docs <= 0x7FFFFFFFull, "label_terms: n_docs=%llu, more than 2^31 - 1", (unsigned long long)idx->n_docs);
+    oi_ctx *ctx = idx->ctx;
+    hipStream_t st = ctx->stream;
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    const bool host = location != OI_DEVICE;
+    const uint32_t vocab = idx->vocab, top = spec->top;
+    const size_t tb = lt_up(sizeof(uint32_t) * (size_t)vocab * K), sb = lt_up(sizeof(uint64_t) * (size_t)K);
+    DevBuf &ws = ctx->buf("label_terms"); // [table | sizes | the rank's scratch]
+    OI_CHECK(ws.ensure(tb + sb + oi_label_terms_rank_scratch(vocab, K, top)));
+    uint8_t *d = ws.as<uint8_t>();
+    uint32_t *d_counts = reinterpret_cast<uint32_t *>(d);
+    uint64_t *d_sizes = reinterpret_cast<uint64_t *>(d + tb);
+    const uint32_t *d_labels = labels;
+    oi_label_term *d_terms = terms_out;
+    uint32_t *d_n = n_out;
+    const size_t lb = lt_up(sizeof(uint32_t) * (size_t)idx->n_docs), rb = sizeof(oi_label_term) * (size_t)K * top, nb = sizeof(uint32_t) * (size_t)K;
+    if (host) {
+        DevBuf &w = ctx->buf("label_terms_io");
+        OI_CHECK(w.ensure(lb + lt_up(rb) + nb));
+        uint8_t *io = w.as<uint8_t>();
+        if (idx->n_docs) OI_HIP_CHECK(hipMemcpyAsync(io, labels, sizeof(uint32_t) * (size_t)idx->n_docs, hipMemcpyHostToDevice, st));
+        d_labels = reinterpret_cast<const uint32_t *>(io);
+        d_terms = reinterpret_cast<oi_label_term *>(io + lb);
+        d_n = reinterpret_cast<uint32_t *>(io + lb + lt_up(rb));
+    }
+    OI_CHECK(oi_launch_label_term_counts(idx, d_labels, K, d_counts, d_sizes));
+    OI_CHECK(oi_launch_label_terms_rank(ctx, d_counts, nullptr, d_sizes, vocab, K, top, spec->min_df, d + tb + sb, d_terms, d_n));
+    if (sizes_out)
+        OI_HIP_CHECK(hipMemcpyAsync(sizes_out, d_sizes, sizeof(uint64_t) * (size_t)K, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    if (host) {
+        OI_HIP_CHECK(hipMemcpyAsync(terms_out, d_terms, rb, hipMemcpyDeviceToHost, st));
+        OI_HIP_CHECK(hipMemcpyAsync(n_out, d_n, nb, hipMemcpyDeviceToHost, st));
+        OI_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    return OI_OK;
+}
+
 // ---------------------------------------------------------------- diagnostics of the bf16 screen
 extern "C" int oi_screen_probe(oi_index *idx, const float *query_vecs, uint32_t B, uint64_t row_begin, uint32_t n_rows,
                                float *screen_scores_out, float *eps_out) {

@@ -310,6 +310,7 @@ int oi_bm25_finalize(oi_index *idx, uint64_t global_n, uint64_t global_tokens, c
         OI_CHECK(idx->postings.ensure(sizeof(Posting) * idx->n_postings + 1024));
         uint64_t blocks = (idx->n_postings + 255) / 256;
         if (blocks > 65535) blocks = 65535;
+        ProfScope ps(ctx, "bm25_impact"); // (the yardstick of the passes that read one 8-byte record per posting: tools/label_terms_bench.py)
         hipLaunchKernelGGL(bm_impact_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, idx->uniq_keys.as<uint64_t>(),
                            idx->tf.as<uint32_t>(), idx->n_postings, idx->doc_len.as<uint32_t>(), avgdl,
                            idx->postings.as<Posting>());

@@ -412,6 +412,14 @@ int oi_launch_fit_moved(oi_ctx *ctx, const uint32_t *d_cur, const uint32_t *d_pr
 // Asynchronous on the ctx stream
 int oi_launch_narratives_seed(oi_index *idx, uint32_t n_clusters, const oi_seed_spec &spec, const oi_doc_filter *filter, float *d_seeds,
                               uint32_t *d_rows, const void **d_info_out);
+// label_terms.hip: the distinguishing terms of each cluster, all asynchronous on the ctx stream -- device labels
+// [n_docs] in, device table [vocab][n_clusters] and sizes [n_clusters] out (zeroed by the launch); a device table and the sizes
+// (the host's, passed by value, or with sizes_host == null the device's) to device records [n_clusters][top] and n [n_clusters],
+// with oi_label_terms_rank_scratch() bytes of the caller's workspace behind `scratch`
+int oi_launch_label_term_counts(oi_index *idx, const uint32_t *d_labels, uint32_t n_clusters, uint32_t *d_counts, uint64_t *d_sizes);
+size_t oi_label_terms_rank_scratch(uint32_t vocab, uint32_t n_clusters, uint32_t top);
+int oi_launch_label_terms_rank(oi_ctx *ctx, const uint32_t *d_counts, const uint64_t *sizes_host, const uint64_t *d_sizes, uint32_t vocab,
+                               uint32_t n_clusters, uint32_t top, uint32_t min_df, void *scratch, oi_label_term *d_terms, uint32_t *d_n);
 // cosine.hip
 // Sets pool.n_segs / pool.seg_cap for this chunk (the following select must use the same view).
 // run_gate != null: a launch of the gated exact pipeline behind a screen (search.hip: cosine_exact) -- the kernel exits at once

@@ -818,6 +818,58 @@ class HybridIndex(PostRetriever):
                                           _lib.ptr(sums), _lib.ptr(counts)))
         return sums, counts
 
+    def label_term_counts(self, labels, n_clusters: int):
+        """oi_label_term_counts: (counts uint32 [vocab, n_clusters], sizes uint64 [n_clusters]) -- counts[t, c] = local documents
+        with labels[d] == c that hold term t (once per document), sizes[c] = rows with labels[d] == c.  Any label >=
+        n_clusters, 0xFFFFFFFF included, is "no cluster".  Exact integers: the same bits on every run, and the tables and sizes
+        of document shards add (then rank_label_terms the total).  Needs a finalized index, no embeddings.  labels as in
+        label_sums; numpy in, numpy out; torch CUDA tensor in, tensors out (counts int32 holding the u32 bits, sizes int64;
+        asynchronous)."""
+        K = int(n_clusters)
+        dev = _is_dev(labels)
+        cols = max(min(K, _lib.OI_MAX_CENTROIDS), 1)                # (a count out of range is refused by the library, not here)
+        if dev:
+            import torch
+            assert labels.is_contiguous() and labels.numel() == self.n_docs and labels.element_size() == 4
+            counts = torch.zeros((self.vocab, cols), dtype=torch.int32, device="cuda:%d" % self.ctx.device)
+            sizes = torch.zeros((cols,), dtype=torch.int64, device="cuda:%d" % self.ctx.device)
+        else:
+            labels = _np(labels, np.uint32)
+            assert labels.size == self.n_docs
+            counts = np.zeros((self.vocab, cols), dtype=np.uint32)
+            sizes = np.zeros((cols,), dtype=np.uint64)
+        _lib.check(self.lib.oi_label_term_counts(self.handle, _lib.ptr(labels), K, _lib.OI_DEVICE if dev else _lib.OI_HOST,
+                                                 _lib.ptr(counts), _lib.ptr(sizes)))
+        return counts, sizes
+
+    def label_terms(self, labels, n_clusters: int, top: int = 10, min_df: int = 1):
+        """oi_label_terms: the distinguishing terms of every cluster of a labelling -> (records [n_clusters, top], n
+        [n_clusters], sizes [n_clusters]).  Per cluster the eligible terms (counts[t, c] >= max(min_df, 1)) in the order
+        excess descending, counts descending, term ascending, where excess = counts[t, c] * A - sizes[c] * dfA[t] (A times
+        observed minus expected); records beyond n[c] have term 0xFFFFFFFF.  The table stays in the ctx workspace.  numpy
+        labels: records as _lib.LABEL_TERM_DTYPE, n uint32, sizes uint64; torch CUDA labels: records as an int64 tensor
+        [n_clusters, top, 3] (label_term_records views it), n int32, sizes int64; asynchronous."""
+        K = int(n_clusters)
+        dev = _is_dev(labels)
+        spec = _lib.LabelTermsSpec(int(top), int(min_df), (C.c_uint32 * 2)(0, 0))
+        rows, cols = max(min(K, _lib.OI_MAX_CENTROIDS), 1), max(min(int(top), _lib.OI_MAX_LABEL_TERMS), 1)
+        if dev:
+            import torch
+            assert labels.is_contiguous() and labels.numel() == self.n_docs and labels.element_size() == 4
+            where = "cuda:%d" % self.ctx.device
+            rec = torch.zeros((rows, cols, 3), dtype=torch.int64, device=where)
+            n = torch.zeros((rows,), dtype=torch.int32, device=where)
+            sizes = torch.zeros((rows,), dtype=torch.int64, device=where)
+        else:
+            labels = _np(labels, np.uint32)
+            assert labels.size == self.n_docs
+            rec = np.zeros((rows, cols), dtype=_lib.LABEL_TERM_DTYPE)
+            n = np.zeros((rows,), dtype=np.uint32)
+            sizes = np.zeros((rows,), dtype=np.uint64)
+        _lib.check(self.lib.oi_label_terms(self.handle, _lib.ptr(labels), K, C.byref(spec), _lib.OI_DEVICE if dev else _lib.OI_HOST,
+                                           _lib.ptr(rec), _lib.ptr(n), _lib.ptr(sizes)))
+        return rec, n, sizes
+
     def fit_narratives(self, seeds, threshold: float, max_iters: int = 20, n_buckets: int = 1, stamp_origin: int = 0,
                        bucket_width: int = 0, filter=None, labels: bool = False) -> "NarrativeFit":
         """oi_narratives_fit: k-means over the index on the device.  Starting from seeds [K, dim], similar_share (one
@@ -1080,6 +1132,40 @@ def centroids_from_sums(ctx: HipContext, sums, counts, previous=None):
     _lib.check(ctx.lib.oi_centroids_from_sums(ctx.handle, _lib.ptr(sums), _lib.ptr(counts), _lib.ptr(previous), K, dim,
                                               _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(out)))
     return out
+
+
+def rank_label_terms(ctx: HipContext, counts, sizes, top: int = 10, min_df: int = 1):
+    """oi_label_terms_rank: a table [vocab, n_clusters] and sizes [n_clusters] (HybridIndex.label_term_counts's, or the total
+    of several shards') -> (records [n_clusters, top], n [n_clusters]) as HybridIndex.label_terms returns them.  The sizes go
+    to the host (at most 2 KB; their sum A must be <= 2^31 - 1).  numpy table in, numpy out; torch CUDA table in, tensors
+    out."""
+    dev = _is_dev(counts)
+    sizes_h = _np(sizes.cpu().numpy() if _is_dev(sizes) else sizes, np.uint64)
+    vocab, K = int(counts.shape[0]), int(counts.shape[1])
+    assert sizes_h.size == K
+    spec = _lib.LabelTermsSpec(int(top), int(min_df), (C.c_uint32 * 2)(0, 0))
+    cols = max(min(int(top), _lib.OI_MAX_LABEL_TERMS), 1)
+    if dev:
+        import torch
+        assert counts.is_contiguous() and counts.element_size() == 4
+        rec = torch.zeros((K, cols, 3), dtype=torch.int64, device=counts.device)
+        n = torch.zeros((K,), dtype=torch.int32, device=counts.device)
+    else:
+        counts = _np(counts, np.uint32)
+        rec = np.zeros((K, cols), dtype=_lib.LABEL_TERM_DTYPE)
+        n = np.zeros((K,), dtype=np.uint32)
+    _lib.check(ctx.lib.oi_label_terms_rank(ctx.handle, _lib.ptr(counts), _lib.ptr(sizes_h), vocab, K, C.byref(spec),
+                                           _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(rec), _lib.ptr(n)))
+    return rec, n
+
+
+def label_term_records(records) -> np.ndarray:
+    """The records of label_terms / rank_label_terms as a _lib.LABEL_TERM_DTYPE array [n_clusters, top] on the host (a torch
+    int64 tensor [n_clusters, top, 3] is copied off the device; a numpy array is returned as it is)."""
+    if _is_dev(records):
+        a = records.cpu().numpy()
+        return a.view(_lib.LABEL_TERM_DTYPE).reshape(a.shape[0], a.shape[1])
+    return records
 
 
 def rrf_fuse(ctx: HipContext, docs_a, counts_a, docs_b, counts_b, k: int) -> SearchResult:
