@@ -1064,6 +1064,58 @@ int oi_label_terms(oi_index *idx, const uint32_t *labels, uint32_t n_clusters, c
                    oi_label_term *terms_out, uint32_t *n_out, uint64_t *sizes_out /* or NULL */);
 
 /* ------------------------------------------------------------------------- */
+/* Narrative exemplars: the most central posts of each cluster                */
+/* ------------------------------------------------------------------------- */
+/*
+ * oi_narratives_fit says which narratives there are and which post belongs to which, oi_label_terms what each is about; this
+ * call returns THE POSTS TO QUOTE: for every cluster of a labelling, the stored posts closest to the cluster's centroid, among
+ * the posts the labelling gave it.  (A search with the centroids as queries returns each centroid's nearest posts in the whole
+ * index -- under the share's tie and exclusivity rules a different set -- and a filter tests group and stamp, not a label.)
+ * Builder-defined like the whole retrieval path.
+ *
+ * The lists.  labels[d] is a u32 per LOCAL row.  Row d is a MEMBER of cluster c when
+ *   labels[d] == c < n_clusters   (any other label, 0xFFFFFFFF included, is "no cluster", as in oi_label_sums: the row is not
+ *                                  read), and
+ *   d passes `filter`, when one is given, and
+ *   s = sim(centroids[c], d) is not NaN.
+ * sim is oi_similar_volume's sim with the centroid as the query: on an f32 corpus the f32 chain; on a bf16 corpus the row is
+ * widened exactly and the vector is rounded to bf16 the way that corpus's scorer rounds it.  The list of cluster c is its
+ * members in descending order of oi_rank_key(s, doc) -- score descending with -0 and +0 as one key, ties to the smaller doc id:
+ * the order of every ranked list of the library -- cut at `top`.  docs_out holds GLOBAL doc ids (doc_id_base + local row),
+ * counts_out[c] the number of valid entries; entries beyond it are score 0 and doc 0xFFFFFFFF.  An empty cluster has count 0.
+ *
+ * The result is a function of the inputs alone: it does not depend on the grid, the order of any atomics, the cosine mode, the
+ * screening-copy policy or the run, and ties at the cut are resolved by the rule above, not by arrival.  The score of an entry
+ * is bit for bit the sim oi_similar_share compared against the threshold for that pair (a -0 is returned as +0, as by every
+ * ranked list).  The lists are valid input of oi_collapse_lists (row stride `top`) -- retweets are what fills the top of a
+ * narrative -- and of oi_merge_lists: document shards hold disjoint rows, so a sharded host calls per rank and merges.
+ *
+ * Rules.  Embeddings only (otherwise OI_ERR_STATE): no signals, no forward index, no finalize; attributes only when a filter
+ * is given (otherwise OI_ERR_STATE); it works on a view, on an f32 corpus of any supported dim and on a bf16 corpus.
+ * n_clusters in [1, OI_MAX_CENTROIDS]; top in [1, OI_MAX_DEPTH]; reserved == 0.  location covers labels, centroids and the
+ * three outputs; spec and filter are host pointers, read before the call returns.  With OI_DEVICE the call is asynchronous on
+ * the ctx stream, with no host synchronise anywhere in it.  Not captured by graph replay.  A null index, spec or buffer, top or
+ * n_clusters out of range, reserved != 0, a bad location -> OI_ERR_INVALID_ARG with the offending number in the message; every
+ * argument check precedes the first device call.
+ * Workspace per searching context (oi_workspace_bytes counts it): "exemplars" holds one 4-byte score key per local row, the
+ * select's histograms (1 KB per cluster) and states, 8 B x top x n_clusters of list slots and, for a bf16 corpus, the rounded
+ * centroids.  With OI_HOST the staged labels, centroids and outputs are held in "exemplars_io".
+ * Profile tags: "exemplar_score" (the stream of the member rows), "exemplar_select" (the segmented radix select: at most
+ * 4 + ceil(log256 n_docs) passes of 8 B per row), "exemplar_emit" (collect, sort, write).
+ *
+ * NOT covered: a screened route over the bf16 copy (every member row is read in full); a time axis (one list per cluster and
+ * bucket); oi_search_sharded* / oi_pipeline_* forms (a sharded host merges per-rank lists with oi_merge_lists); more than
+ * OI_MAX_DEPTH posts per cluster.
+ */
+typedef struct oi_exemplar_spec { uint32_t top, reserved[3]; } oi_exemplar_spec;   /* top in 1 .. OI_MAX_DEPTH; reserved == 0 */
+int oi_label_exemplars(oi_index *idx, const uint32_t *labels /* [n_docs] by LOCAL row */,
+                       const float *centroids /* [n_clusters][dim] */, uint32_t n_clusters,
+                       const oi_exemplar_spec *spec, const oi_doc_filter *filter /* ONE, host pointer, or NULL */,
+                       int location,
+                       float *scores_out /* [n_clusters][top] */, uint32_t *docs_out /* [n_clusters][top] */,
+                       uint32_t *counts_out /* [n_clusters] */);
+
+/* ------------------------------------------------------------------------- */
 /* Text to term ids: the tokeniser and the hashed vocabulary                   */
 /* ------------------------------------------------------------------------- */
 /*

@@ -32,6 +32,9 @@ int main(void) {
     /* the narrative-terms records as the bindings lay them out: 16-byte spec, 24-byte record with the excess at 16 */
     if (sizeof(oi_label_terms_spec) != 16 || sizeof(oi_label_term) != 24 || offsetof(oi_label_term, excess) != 16)
         return fail("oi_label_term layout", (int)sizeof(oi_label_term));
+    /* the narrative-exemplars spec as the bindings lay it out: 16 bytes, top first */
+    if (sizeof(oi_exemplar_spec) != 16 || offsetof(oi_exemplar_spec, top) != 0 || offsetof(oi_exemplar_spec, reserved) != 4)
+        return fail("oi_exemplar_spec layout", (int)sizeof(oi_exemplar_spec));
     rc = oi_create(0, &ctx);
     if (rc == OI_ERR_NO_DEVICE) {
         if (ctx != NULL || oi_last_error()[0] == '\0') return fail("no-device contract", rc);

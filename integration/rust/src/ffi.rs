@@ -111,6 +111,14 @@ pub struct OiLabelTerm {
 pub const OI_MAX_LABEL_TERMS: u32 = 64;
 pub const OI_MAX_LABEL_TERM_CELLS: u32 = 1 << 28;
 
+/// `oi_exemplar_spec`: posts per cluster (1 ..= `OI_MAX_DEPTH`), reserved (0).  16 bytes.
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
+pub struct OiExemplarSpec {
+    pub top: u32,
+    pub reserved: [u32; 3],
+}
+
 /// `oi_seed_spec`: method (`OI_SEED_*`), trials (candidates per seed, 1 ..= 8; 1 with farthest-first), the RNG seed,
 /// `oi_narrative_spec`'s time axis, reserved (0).  32 bytes.
 #[repr(C)]
@@ -368,6 +376,12 @@ extern "C" {
                                spec: *const OiLabelTermsSpec, location: c_int, terms_out: *mut OiLabelTerm, n_out: *mut u32) -> c_int;
     pub fn oi_label_terms(idx: *mut OiIndex, labels: *const u32, n_clusters: u32, spec: *const OiLabelTermsSpec, location: c_int,
                           terms_out: *mut OiLabelTerm, n_out: *mut u32, sizes_out: *mut u64) -> c_int;
+
+    // narrative exemplars: per cluster of a labelling, its member rows closest to its centroid as ranked lists [n_clusters][top]
+    // (global doc ids; score 0 / doc u32::MAX beyond counts_out[c]); spec and filter (one, or null) are host pointers
+    pub fn oi_label_exemplars(idx: *mut OiIndex, labels: *const u32, centroids: *const f32, n_clusters: u32, spec: *const OiExemplarSpec,
+                              filter: *const OiDocFilter, location: c_int, scores_out: *mut f32, docs_out: *mut u32,
+                              counts_out: *mut u32) -> c_int;
 
     pub fn oi_pipeline_create(idx: *mut OiIndex, comm: *mut OiComm, lanes: u32, max_queries: u32, max_query_terms: u32,
                               depth: u32, k: u32, out: *mut *mut OiPipeline) -> c_int;

@@ -474,6 +474,24 @@ impl HipIndex {
         })?;
         Ok(((0..k).map(|c| rec[c * width..c * width + n[c] as usize].to_vec()).collect(), sizes))
     }
+    /// The posts to quote (`oi_label_exemplars`): per cluster of a labelling, its member rows closest to its centroid, best
+    /// first, as (global doc id, score) -- score descending, ties to the smaller doc id, at most `top` per cluster.  A member
+    /// has `labels[d] == c < n_clusters`, passes `filter` when one is given, and a sim that is not NaN.  `centroids` is
+    /// [n_clusters * dim].  The lists of document shards merge with `oi_merge_lists`.
+    pub fn label_exemplars(&self, labels: &[u32], centroids: &[f32], n_clusters: u32, top: u32,
+                           filter: Option<&ffi::OiDocFilter>) -> Result<Vec<Vec<(u32, f32)>>, HipError> {
+        assert_eq!(labels.len(), self.n_docs);
+        let k = n_clusters as usize;
+        let spec = ffi::OiExemplarSpec { top, reserved: [0, 0, 0] };
+        let width = top.clamp(1, 1024) as usize;
+        let (mut scores, mut docs, mut counts) = (vec![0f32; k.max(1) * width], vec![0u32; k.max(1) * width], vec![0u32; k.max(1)]);
+        check(unsafe {
+            ffi::oi_label_exemplars(self.idx, labels.as_ptr(), centroids.as_ptr(), n_clusters, &spec,
+                                    filter.map_or(std::ptr::null(), |f| f as *const ffi::OiDocFilter), ffi::OI_HOST, scores.as_mut_ptr(),
+                                    docs.as_mut_ptr(), counts.as_mut_ptr())
+        })?;
+        Ok((0..k).map(|c| (0..counts[c] as usize).map(|i| (docs[c * width + i], scores[c * width + i])).collect()).collect())
+    }
     /// Which narratives are there (`oi_narratives_fit`): k-means over the index on the device, from `seeds` ([k * dim]).
     /// Returns the centroids, records and (with `labels`) labels of the LAST assignment step and what the loop did;
     /// `similar_share` with the centroids as queries reproduces records and labels bit for bit.

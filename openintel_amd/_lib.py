@@ -175,6 +175,14 @@ class LabelTermsSpec(C.Structure):
     ]
 
 
+class ExemplarSpec(C.Structure):
+    """oi_exemplar_spec: posts per cluster (1 .. OI_MAX_DEPTH), reserved (0).  16 bytes."""
+    _fields_ = [
+        ("top", C.c_uint32),
+        ("reserved", C.c_uint32 * 3),
+    ]
+
+
 # oi_label_term: 24 bytes
 LABEL_TERM_DTYPE = np.dtype([("term", "<u4"), ("df_cluster", "<u4"), ("df_assigned", "<u4"), ("reserved", "<u4"), ("excess", "<i8")])
 assert LABEL_TERM_DTYPE.itemsize == 24
@@ -251,6 +259,7 @@ SIGNATURES = {
     "oi_label_term_counts": (_I, [_P, _P, _U32, _I, _P, _P]),
     "oi_label_terms_rank": (_I, [_P, _P, _P, _U32, _U32, _P, _I, _P, _P]),
     "oi_label_terms": (_I, [_P, _P, _U32, _P, _I, _P, _P, _P]),
+    "oi_label_exemplars": (_I, [_P, _P, _P, _U32, _P, _P, _I, _P, _P, _P]),
     "oi_text_terms": (_I, [_P, _P, _P, _U64, _U64, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_query_terms": (_I, [_P, _P, _P, _U32, _U32, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_index_set_text": (_I, [_P, _P, _P, _U64, _I]),

@@ -484,6 +484,50 @@ def describe_narratives(index, fit_or_labels, n_clusters=None, top=10, min_df=1,
     return out
 
 
+def narrative_exemplars(index, fit_or_labels, centroids=None, top=5, pool=64, collapse=None, texts=None):
+    """The posts to quote for every narrative: per cluster a list of (doc, score, stands_for, text-or-None), best first -- the
+    cluster's own posts closest to its centroid (`index.label_exemplars`, oi_label_exemplars).
+    fit_or_labels: a NarrativeFit made with labels=True (the centroids are then the fit's), or a label array [n_docs] by local
+    row (numpy or torch CUDA tensor) with `centroids` [n_clusters, dim] given.
+    collapse=t: by definition label_exemplars(.., top=pool) followed by index.collapse_lists(.., threshold=t, k=top) -- retweets
+    and copies of a post fold into its best-ranked copy, and stands_for is how many pool entries the kept post stands for.
+    Without collapse: label_exemplars(.., top=top), stands_for = 1.  texts: the corpus's texts by GLOBAL doc id (a sequence
+    or a mapping); None leaves the text None."""
+    labels = fit_or_labels
+    if hasattr(fit_or_labels, "centroids") and hasattr(fit_or_labels, "labels"):
+        labels = fit_or_labels.labels
+        if labels is None:
+            raise ValueError("narrative_exemplars: the fit carries no labels (fit_narratives(..., labels=True))")
+        if centroids is None:
+            centroids = fit_or_labels.centroids
+    if centroids is None:
+        raise ValueError("narrative_exemplars: centroids are required with a label array")
+    if collapse is None:
+        lists = index.label_exemplars(labels, centroids, top=top)
+        scores, docs, counts, dups = lists.cos_scores, lists.cos_docs, lists.cos_counts, None
+    else:
+        lists = index.label_exemplars(labels, centroids, top=pool)
+        res = index.collapse_lists(lists.cos_scores, lists.cos_docs, lists.cos_counts, threshold=collapse, k=top)
+        scores, docs, counts, dups = res.scores, res.docs, res.counts, res.dup_counts
+    if hasattr(docs, "data_ptr"):
+        import numpy as np
+        scores, docs, counts = scores.cpu().numpy(), docs.cpu().numpy().view(np.uint32), counts.cpu().numpy().view(np.uint32)
+        dups = None if dups is None else dups.cpu().numpy().view(np.uint32)
+
+    def text_of(doc):
+        if texts is None:
+            return None
+        if hasattr(texts, "get"):
+            return texts.get(doc)
+        return texts[doc] if 0 <= doc < len(texts) else None
+
+    out = []
+    for c in range(int(docs.shape[0])):
+        out.append([(int(docs[c, i]), float(scores[c, i]), 1 if dups is None else int(dups[c, i]), text_of(int(docs[c, i])))
+                    for i in range(int(counts[c]))])
+    return out
+
+
 # ----------------------------------------------------------------------------- wire format (#[derive(Serialize)])
 def scan_output_to_json(out: ScanOutput) -> str:
     """serde_json::to_string_pretty(&ScanOutput): `report` / `error` are skipped when None (tools.rs:180-183)."""

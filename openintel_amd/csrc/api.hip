@@ -2278,6 +2278,45 @@ extern "C" int oi_label_terms(oi_index *idx, const uint32_t *labels, uint32_t K,
     return OI_OK;
 }
 
+// ---------------------------------------------------------------- narrative exemplars (label_exemplars.hip)
+// The family's order of checks: the spec, the numbers, the buffers, the location, then the handle and its state; all of them
+// precede the first HIP call.  OI_DEVICE: no host synchronise anywhere.  Never captured.
+extern "C" int oi_label_exemplars(oi_index *idx, const uint32_t *labels, const float *centroids, uint32_t K, const oi_exemplar_spec *spec,
+                                  const oi_doc_filter *filter, int location, float *scores_out, uint32_t *docs_out, uint32_t *counts_out) {
+    static_assert(sizeof(oi_exemplar_spec) == 16, "the spec is 16 bytes");
+    if (!spec) { oi_set_error("label_exemplars: null spec"); return OI_ERR_INVALID_ARG; }
+    OI_REQUIRE(spec->top >= 1 && spec->top <= OI_MAX_DEPTH, "label_exemplars: top=%u outside [1,%u]", spec->top, OI_MAX_DEPTH);
+    OI_REQUIRE(spec->reserved[0] == 0 && spec->reserved[1] == 0 && spec->reserved[2] == 0, "label_exemplars: reserved=%u (must be 0)",
+               spec->reserved[0] ? spec->reserved[0] : spec->reserved[1] ? spec->reserved[1] : spec->reserved[2]);
+    OI_REQUIRE(K >= 1 && K <= OI_MAX_CENTROIDS, "label_exemplars: n_clusters=%u outside [1,%u]", K, OI_MAX_CENTROIDS);
+    OI_REQUIRE(labels && centroids && scores_out && docs_out && counts_out, "label_exemplars: null buffer");
+    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "label_exemplars: bad location %d", location);
+    std::unique_lock<std::mutex> g;
+    OI_CHECK(similar_check_state("label_exemplars", idx, false, filter ? "a filter needs" : nullptr, g));
+    oi_ctx *ctx = idx->ctx;
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    const uint32_t top = spec->top;
+    if (location == OI_DEVICE) return oi_launch_label_exemplars(idx, labels, centroids, K, top, filter, scores_out, docs_out, counts_out);
+    hipStream_t st = ctx->stream;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t lb = up(sizeof(uint32_t) * (size_t)idx->n_docs), vb = up(sizeof(float) * (size_t)K * idx->dim),
+                 ob = up(sizeof(uint32_t) * (size_t)K * top), cb = sizeof(uint32_t) * (size_t)K;
+    DevBuf &w = ctx->buf("exemplars_io");
+    OI_CHECK(w.ensure(lb + vb + 2 * ob + cb));
+    uint8_t *d = w.as<uint8_t>();
+    if (idx->n_docs) OI_HIP_CHECK(hipMemcpyAsync(d, labels, sizeof(uint32_t) * (size_t)idx->n_docs, hipMemcpyHostToDevice, st));
+    OI_HIP_CHECK(hipMemcpyAsync(d + lb, centroids, sizeof(float) * (size_t)K * idx->dim, hipMemcpyHostToDevice, st));
+    float *d_scores = reinterpret_cast<float *>(d + lb + vb);
+    uint32_t *d_docs = reinterpret_cast<uint32_t *>(d + lb + vb + ob), *d_counts = reinterpret_cast<uint32_t *>(d + lb + vb + 2 * ob);
+    OI_CHECK(oi_launch_label_exemplars(idx, reinterpret_cast<const uint32_t *>(d), reinterpret_cast<const float *>(d + lb), K, top, filter, d_scores,
+                                       d_docs, d_counts));
+    OI_HIP_CHECK(hipMemcpyAsync(scores_out, d_scores, sizeof(float) * (size_t)K * top, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipMemcpyAsync(docs_out, d_docs, sizeof(uint32_t) * (size_t)K * top, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, cb, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipStreamSynchronize(st));
+    return OI_OK;
+}
+
 // ---------------------------------------------------------------- diagnostics of the bf16 screen
 extern "C" int oi_screen_probe(oi_index *idx, const float *query_vecs, uint32_t B, uint64_t row_begin, uint32_t n_rows,
                                float *screen_scores_out, float *eps_out) {

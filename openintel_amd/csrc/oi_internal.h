@@ -420,6 +420,11 @@ int oi_launch_label_term_counts(oi_index *idx, const uint32_t *d_labels, uint32_
 size_t oi_label_terms_rank_scratch(uint32_t vocab, uint32_t n_clusters, uint32_t top);
 int oi_launch_label_terms_rank(oi_ctx *ctx, const uint32_t *d_counts, const uint64_t *sizes_host, const uint64_t *d_sizes, uint32_t vocab,
                                uint32_t n_clusters, uint32_t top, uint32_t min_df, void *scratch, oi_label_term *d_terms, uint32_t *d_n);
+// label_exemplars.hip: the most central posts of each cluster -- device labels [n_docs] and centroids
+// [n_clusters][dim] in, device scores / docs [n_clusters][top] and counts [n_clusters] out; `filter` is the host's (by value into
+// the launch) or null.  Asynchronous on the ctx stream; its workspace is "exemplars".
+int oi_launch_label_exemplars(oi_index *idx, const uint32_t *d_labels, const float *d_centroids, uint32_t n_clusters, uint32_t top,
+                              const oi_doc_filter *filter, float *d_scores, uint32_t *d_docs, uint32_t *d_counts);
 // cosine.hip
 // Sets pool.n_segs / pool.seg_cap for this chunk (the following select must use the same view).
 // run_gate != null: a launch of the gated exact pipeline behind a screen (search.hip: cosine_exact) -- the kernel exits at once

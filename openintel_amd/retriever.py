@@ -870,6 +870,42 @@ class HybridIndex(PostRetriever):
                                            _lib.ptr(rec), _lib.ptr(n), _lib.ptr(sizes)))
         return rec, n, sizes
 
+    def label_exemplars(self, labels, centroids, top: int = 10, filter=None) -> "RankedLists":
+        """oi_label_exemplars: the posts to quote -- per cluster of a labelling, its member rows closest to its centroid, as
+        ranked lists [n_clusters, top] in cos_scores / cos_docs / cos_counts of a RankedLists (the bm25 fields are None).  A
+        member of cluster c has labels[d] == c < n_clusters, passes `filter` (ONE {group_mask, group_value, stamp_lo,
+        stamp_hi}, or None) and has a sim to centroids[c] that is not NaN; the order is score descending, then the smaller
+        doc id; docs are global ids; entries beyond cos_counts[c] are score 0, doc 0xFFFFFFFF.  The scores are the sims
+        similar_share compares, bit for bit.  The lists feed collapse_lists and merge_lists as they are.  labels as in
+        label_sums; numpy labels in, numpy out; torch CUDA labels in (centroids are moved to the device if they are not
+        there), tensors out, asynchronous."""
+        dev = _is_dev(labels)
+        K = int(centroids.shape[0])
+        assert K == 0 or int(centroids.shape[1]) == self.dim
+        spec = _lib.ExemplarSpec(int(top), (C.c_uint32 * 3)(0, 0, 0))
+        rows, cols = max(min(K, _lib.OI_MAX_CENTROIDS), 1), max(min(int(top), _lib.OI_MAX_DEPTH), 1)   # (refused by the library, not here)
+        if dev:
+            import torch
+            assert labels.is_contiguous() and labels.numel() == self.n_docs and labels.element_size() == 4
+            if not _is_dev(centroids):
+                centroids = torch.from_numpy(_np(centroids, np.float32)).to("cuda:%d" % self.ctx.device)
+            assert centroids.is_contiguous() and centroids.element_size() == 4
+            self._exemplar_keep = centroids  # (an asynchronous call reads it later)
+        else:
+            labels = _np(labels, np.uint32)
+            assert labels.size == self.n_docs
+            centroids = _np(centroids.cpu().numpy() if _is_dev(centroids) else centroids, np.float32)
+        f = None
+        if filter is not None:
+            fa = np.ascontiguousarray(np.asarray(filter.cpu().numpy() if _is_dev(filter) else filter).astype(np.uint32, copy=False).reshape(4))
+            f = _lib.DocFilter(int(fa[0]), int(fa[1]), int(fa[2]), int(fa[3]))
+        out = RankedLists(self._alloc(dev, (rows, cols), np.float32), self._alloc(dev, (rows, cols), np.uint32),
+                          self._alloc(dev, (rows,), np.uint32), None, None, None)
+        _lib.check(self.lib.oi_label_exemplars(self.handle, _lib.ptr(labels), _lib.ptr(centroids), K, C.byref(spec),
+                                               None if f is None else C.byref(f), _lib.OI_DEVICE if dev else _lib.OI_HOST,
+                                               _lib.ptr(out.cos_scores), _lib.ptr(out.cos_docs), _lib.ptr(out.cos_counts)))
+        return out
+
     def fit_narratives(self, seeds, threshold: float, max_iters: int = 20, n_buckets: int = 1, stamp_origin: int = 0,
                        bucket_width: int = 0, filter=None, labels: bool = False) -> "NarrativeFit":
         """oi_narratives_fit: k-means over the index on the device.  Starting from seeds [K, dim], similar_share (one
