@@ -1116,6 +1116,78 @@ int oi_label_exemplars(oi_index *idx, const uint32_t *labels /* [n_docs] by LOCA
                        uint32_t *counts_out /* [n_clusters] */);
 
 /* ------------------------------------------------------------------------- */
+/* Narrative breakdown: per-cluster records by time bucket or ticker           */
+/* ------------------------------------------------------------------------- */
+/*
+ * oi_narratives_fit says which narratives there are, oi_label_terms what each is about, oi_label_exemplars which posts to
+ * quote; this call answers the two questions the reference's own reports are built around (social_summary per ticker,
+ * run_compare across tickers) for a NARRATIVE: how did each cluster develop over time (OI_LABEL_AXIS_TIME), and which tickers
+ * is it about and how do its posts feel per ticker (OI_LABEL_AXIS_KEY)?  It is the member of the summing tallies that decides
+ * a document by a LABEL: oi_similar_summary / _groups decide it by similarity, oi_mention_summary by terms.  It reads the
+ * labels where they are, 4 bytes per row, and the attributes and signals of the labelled rows: no embeddings, no corpus stream,
+ * and nothing per post returns to the host.  Builder-defined like the whole retrieval path.
+ *
+ * The definition.  labels[d] is a u32 per LOCAL row.  Row d is in cell (c, x) when
+ *   labels[d] == c < n_clusters   (any other label, 0xFFFFFFFF included, is "no cluster", as in oi_label_sums: it is no error,
+ *                                  and the row's attributes and signals are not read), and
+ *   d passes `filter`, when one is given, and
+ *   on the TIME axis oi_similar_summary's clause 2 gives x: bucket_width == 0 (one cell, x = 0), or stamp_origin <= stamp[d]
+ *     and (stamp[d] - stamp_origin) / bucket_width == x < n_cells;
+ *   on the KEY axis oi_similar_groups's key clause gives x: (group[d] & key_mask) >> ctz(key_mask) == x, and a key >= n_cells
+ *     belongs to no cell.
+ * The record of a cell is oi_similar_summary's, word for word: total, by_source[2], bullish, bearish, neutral and spec_count
+ * are exact integers, and polarity_sum = (double)(sum of pol_q30) * 2^-30, the sum taken in 64-bit integers.
+ *
+ * The contract that follows from it:
+ *   - the result is a function of the inputs alone: grid, route, order of atomics and run do not matter;
+ *   - records of document shards add;
+ *   - with no filter, the sum over x of total[c][x] on a one-cell TIME axis equals oi_label_sums' counts[c];
+ *   - with labels_out of an oi_similar_share or oi_narratives_fit call, and that call's time axis and filter used for every
+ *     query, the dense TIME records equal that call's out bit for bit;
+ *   - summed over the keys, a KEY-axis call equals the one-cell TIME call when every document has a key.
+ *
+ * Dense output (top == 0): records_out[c][x], row stride n_cells; keys_out, counts_out and qualified_out may be NULL and are
+ * not written.  Ranked output (top >= 1, KEY axis only) is exactly oi_similar_groups' ranked output with "query" replaced by
+ * "cluster": the keys of cluster c with total >= max(min_total, 1) are ordered by the rank key v << 32 | ~key descending (v =
+ * the record's total / spec_count / bullish / bearish as rank_by says; ties go to the smaller key) and cut at `top`;
+ * records_out and keys_out have row stride `top`; counts_out[c] is the number of listed keys; entries beyond it are key
+ * 0xFFFFFFFF and an all-zero record; qualified_out[c], when given, is the number of keys that met the bar before the cut.
+ *
+ * Rules.  Signals are required (oi_index_set_signals): otherwise OI_ERR_STATE.  Doc attributes are required on the KEY axis,
+ * with bucket_width > 0, or with a filter: otherwise OI_ERR_STATE.  NO embeddings, forward index or finalize are needed, and
+ * it works on a view.  n_clusters in [1, OI_MAX_CENTROIDS]; n_clusters * n_cells <= OI_MAX_GROUP_CELLS.  spec and filter are
+ * host pointers, read before the call returns; location covers the labels and the four outputs.  With OI_DEVICE the call is
+ * asynchronous on the ctx stream, with no host synchronise anywhere in it.  Not captured by graph replay.  A null index, spec
+ * or required buffer, a bad axis, n_clusters, n_cells or the cell count out of range, top > 0 on the TIME axis, top >
+ * OI_MAX_DEPTH, rank_by out of range or non-zero with top == 0, reserved != 0, bucket_width != 0 on the KEY axis, a key_mask
+ * that is zero or not one contiguous run of bits, a bad location -> OI_ERR_INVALID_ARG with the offending number in the
+ * message; every argument check precedes the first device call.
+ * Workspace per searching context (oi_workspace_bytes counts it): "label_summary" holds 64 B per cell and, for ranked output,
+ * 8 B more per cell; with OI_HOST the staged labels and outputs are held in "label_summary_io".
+ * Profile tags: "label_summary" (the pass over labels, attributes and signals) and "label_summary_rank" (the ranked finish).
+ *
+ * NOT covered: oi_search_sharded* / oi_pipeline_* forms (a sharded host adds the dense records of its ranks); both axes at
+ * once (one record per cluster, bucket and key).
+ */
+enum { OI_LABEL_AXIS_TIME = 0, OI_LABEL_AXIS_KEY = 1 };
+typedef struct oi_label_summary_spec {
+    uint32_t axis;          /* OI_LABEL_AXIS_* */
+    uint32_t stamp_origin;  /* TIME: oi_summary_spec's meaning.              KEY: key_mask (non-zero, one contiguous run of bits) */
+    uint32_t bucket_width;  /* TIME: oi_summary_spec's (0: no axis, 1 cell).  KEY: must be 0 */
+    uint32_t n_cells;       /* TIME: 1 .. OI_MAX_VOLUME_BUCKETS (1 when bucket_width == 0).  KEY: 1 .. min(2^popcount(mask), OI_MAX_GROUP_KEYS) */
+    uint32_t top;           /* 0: dense output;  1 .. OI_MAX_DEPTH: ranked output, KEY axis only */
+    uint32_t rank_by;       /* OI_GROUP_RANK_*; must be 0 when top == 0 */
+    uint32_t min_total;     /* ranked output lists a key only when its total >= max(min_total, 1) */
+    uint32_t reserved;      /* 0 */
+} oi_label_summary_spec;    /* 32 bytes */
+int oi_label_summary(oi_index *idx, const uint32_t *labels /* [n_docs] by LOCAL row */, uint32_t n_clusters,
+                     const oi_label_summary_spec *spec, const oi_doc_filter *filter /* ONE, host pointer, or NULL */,
+                     int location,
+                     oi_social_counters *records_out /* [n_clusters][n_cells], or [n_clusters][top] */,
+                     uint32_t *keys_out /* [n_clusters][top] */, uint32_t *counts_out /* [n_clusters] */,
+                     uint32_t *qualified_out /* [n_clusters], may be NULL */);
+
+/* ------------------------------------------------------------------------- */
 /* Text to term ids: the tokeniser and the hashed vocabulary                   */
 /* ------------------------------------------------------------------------- */
 /*

@@ -35,6 +35,10 @@ int main(void) {
     /* the narrative-exemplars spec as the bindings lay it out: 16 bytes, top first */
     if (sizeof(oi_exemplar_spec) != 16 || offsetof(oi_exemplar_spec, top) != 0 || offsetof(oi_exemplar_spec, reserved) != 4)
         return fail("oi_exemplar_spec layout", (int)sizeof(oi_exemplar_spec));
+    /* the narrative-breakdown spec as the bindings lay it out: eight 4-byte fields, no padding */
+    if (sizeof(oi_label_summary_spec) != 32 || offsetof(oi_label_summary_spec, axis) != 0 || offsetof(oi_label_summary_spec, n_cells) != 12 ||
+        offsetof(oi_label_summary_spec, top) != 16 || offsetof(oi_label_summary_spec, reserved) != 28)
+        return fail("oi_label_summary_spec layout", (int)sizeof(oi_label_summary_spec));
     rc = oi_create(0, &ctx);
     if (rc == OI_ERR_NO_DEVICE) {
         if (ctx != NULL || oi_last_error()[0] == '\0') return fail("no-device contract", rc);

@@ -159,6 +159,24 @@ pub const OI_MAX_MENTION_TERMS: u32 = 64;
 pub const OI_MENTION_AXIS_TIME: u32 = 0;
 pub const OI_MENTION_AXIS_KEY: u32 = 1;
 
+/// `oi_label_summary_spec`: axis TIME -- `stamp_origin`, `bucket_width` and `n_cells` are `oi_summary_spec`'s time axis and `top`
+/// is 0; axis KEY -- `stamp_origin` carries the key_mask, `bucket_width` is 0, `n_cells` the number of keys, and `top` >= 1 asks
+/// for the best `top` keys by `rank_by` among those with total >= max(min_total, 1).  `reserved` is 0.  32 bytes.
+#[repr(C)]
+#[derive(Debug, Clone, Copy, PartialEq)]
+pub struct OiLabelSummarySpec {
+    pub axis: u32,
+    pub stamp_origin: u32,
+    pub bucket_width: u32,
+    pub n_cells: u32,
+    pub top: u32,
+    pub rank_by: u32,
+    pub min_total: u32,
+    pub reserved: u32,
+}
+pub const OI_LABEL_AXIS_TIME: u32 = 0;
+pub const OI_LABEL_AXIS_KEY: u32 = 1;
+
 /// `oi_groups_spec`: the key of a document is (group & key_mask) >> ctz(key_mask); top == 0 asks for dense records, top >= 1 for
 /// the best `top` keys by `rank_by` among those with total >= max(min_total, 1).
 #[repr(C)]
@@ -382,6 +400,12 @@ extern "C" {
     pub fn oi_label_exemplars(idx: *mut OiIndex, labels: *const u32, centroids: *const f32, n_clusters: u32, spec: *const OiExemplarSpec,
                               filter: *const OiDocFilter, location: c_int, scores_out: *mut f32, docs_out: *mut u32,
                               counts_out: *mut u32) -> c_int;
+
+    // narrative breakdown: per cluster of a labelling the social_summary records per time bucket or key; dense (spec.top == 0:
+    // [n_clusters][n_cells], keys / counts / qualified may be null) or ranked ([n_clusters][top]); spec and filter are host pointers
+    pub fn oi_label_summary(idx: *mut OiIndex, labels: *const u32, n_clusters: u32, spec: *const OiLabelSummarySpec,
+                            filter: *const OiDocFilter, location: c_int, records_out: *mut OiSocialCounters, keys_out: *mut u32,
+                            counts_out: *mut u32, qualified_out: *mut u32) -> c_int;
 
     pub fn oi_pipeline_create(idx: *mut OiIndex, comm: *mut OiComm, lanes: u32, max_queries: u32, max_query_terms: u32,
                               depth: u32, k: u32, out: *mut *mut OiPipeline) -> c_int;

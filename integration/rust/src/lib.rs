@@ -492,6 +492,32 @@ impl HipIndex {
         })?;
         Ok((0..k).map(|c| (0..counts[c] as usize).map(|i| (docs[c * width + i], scores[c * width + i])).collect()).collect())
     }
+    /// The narrative breakdown (`oi_label_summary`): the social_summary sums of the posts of each cluster of a labelling, one
+    /// record per cluster and cell -- a time bucket (`OI_LABEL_AXIS_TIME`) or a key of the documents' group
+    /// (`OI_LABEL_AXIS_KEY`).  `spec.top == 0`: dense records [n_clusters][n_cells], no keys.  `spec.top >= 1` (KEY axis): per
+    /// cluster the listed (key, record) pairs, best first, as `similar_groups` ranks them.  Reads labels, attributes and
+    /// signals only; any label >= n_clusters is "no cluster".  Dense records of shards add.
+    pub fn label_summary(&self, labels: &[u32], n_clusters: u32, spec: ffi::OiLabelSummarySpec, filter: Option<&ffi::OiDocFilter>)
+                         -> Result<Vec<Vec<(u32, ffi::OiSocialCounters)>>, HipError> {
+        assert_eq!(labels.len(), self.n_docs);
+        let k = (n_clusters as usize).max(1);
+        let ranked = spec.top != 0;
+        let width = if ranked { spec.top.clamp(1, 1024) as usize } else { (spec.n_cells as usize).clamp(1, (1usize << 20) / k) };
+        let mut rec = vec![ffi::OiSocialCounters::default(); k * width];
+        let (mut keys, mut counts) = (vec![u32::MAX; if ranked { k * width } else { 0 }], vec![0u32; if ranked { k } else { 0 }]);
+        check(unsafe {
+            ffi::oi_label_summary(self.idx, labels.as_ptr(), n_clusters, &spec,
+                                  filter.map_or(std::ptr::null(), |f| f as *const ffi::OiDocFilter), ffi::OI_HOST, rec.as_mut_ptr(),
+                                  if ranked { keys.as_mut_ptr() } else { std::ptr::null_mut() },
+                                  if ranked { counts.as_mut_ptr() } else { std::ptr::null_mut() }, std::ptr::null_mut())
+        })?;
+        Ok((0..n_clusters as usize)
+            .map(|c| {
+                let n = if ranked { counts[c] as usize } else { width };
+                (0..n).map(|i| (if ranked { keys[c * width + i] } else { i as u32 }, rec[c * width + i])).collect()
+            })
+            .collect())
+    }
     /// Which narratives are there (`oi_narratives_fit`): k-means over the index on the device, from `seeds` ([k * dim]).
     /// Returns the centroids, records and (with `labels`) labels of the LAST assignment step and what the loop did;
     /// `similar_share` with the centroids as queries reproduces records and labels bit for bit.

@@ -29,6 +29,7 @@ OI_MAX_MENTION_TERMS = 64
 OI_MAX_LABEL_TERMS = 64
 OI_MAX_LABEL_TERM_CELLS = 1 << 28
 OI_MENTION_AXIS_TIME, OI_MENTION_AXIS_KEY = 0, 1
+OI_LABEL_AXIS_TIME, OI_LABEL_AXIS_KEY = 0, 1
 OI_GROUP_RANK_TOTAL, OI_GROUP_RANK_SPEC, OI_GROUP_RANK_BULLISH, OI_GROUP_RANK_BEARISH = 0, 1, 2, 3
 OI_BM25_BLOCK_DOCS = 32768
 OI_N_CATALYST_KEYWORDS = 16
@@ -183,6 +184,22 @@ class ExemplarSpec(C.Structure):
     ]
 
 
+class LabelSummarySpec(C.Structure):
+    """oi_label_summary_spec: axis TIME -- {stamp_origin, bucket_width, n_cells} are oi_summary_spec's time axis, top is 0; axis
+    KEY -- stamp_origin carries the key_mask, bucket_width is 0, n_cells the number of keys, and top >= 1 asks for the best `top`
+    keys by rank_by among those with total >= max(min_total, 1).  reserved is 0.  32 bytes."""
+    _fields_ = [
+        ("axis", C.c_uint32),
+        ("stamp_origin", C.c_uint32),
+        ("bucket_width", C.c_uint32),
+        ("n_cells", C.c_uint32),
+        ("top", C.c_uint32),
+        ("rank_by", C.c_uint32),
+        ("min_total", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 # oi_label_term: 24 bytes
 LABEL_TERM_DTYPE = np.dtype([("term", "<u4"), ("df_cluster", "<u4"), ("df_assigned", "<u4"), ("reserved", "<u4"), ("excess", "<i8")])
 assert LABEL_TERM_DTYPE.itemsize == 24
@@ -260,6 +277,7 @@ SIGNATURES = {
     "oi_label_terms_rank": (_I, [_P, _P, _P, _U32, _U32, _P, _I, _P, _P]),
     "oi_label_terms": (_I, [_P, _P, _U32, _P, _I, _P, _P, _P]),
     "oi_label_exemplars": (_I, [_P, _P, _P, _U32, _P, _P, _I, _P, _P, _P]),
+    "oi_label_summary": (_I, [_P, _P, _U32, _P, _P, _I, _P, _P, _P, _P]),
     "oi_text_terms": (_I, [_P, _P, _P, _U64, _U64, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_query_terms": (_I, [_P, _P, _P, _U32, _U32, _U32, _I, _P, _U64, _P, C.POINTER(_U64)]),
     "oi_index_set_text": (_I, [_P, _P, _P, _U64, _I]),

@@ -528,6 +528,75 @@ def narrative_exemplars(index, fit_or_labels, centroids=None, top=5, pool=64, co
     return out
 
 
+def _narrative_labels(who, fit_or_labels, n_clusters):
+    """(labels, n_clusters) of a NarrativeFit made with labels=True, or of a label array with n_clusters given."""
+    labels = fit_or_labels
+    if hasattr(fit_or_labels, "centroids") and hasattr(fit_or_labels, "labels"):
+        labels = fit_or_labels.labels
+        if labels is None:
+            raise ValueError("%s: the fit carries no labels (fit_narratives(..., labels=True))" % who)
+        if n_clusters is None:
+            n_clusters = int(fit_or_labels.centroids.shape[0])
+    if n_clusters is None:
+        raise ValueError("%s: n_clusters is required with a label array" % who)
+    return labels, int(n_clusters)
+
+
+def _host_records(rec):
+    """Records as an analyzer.COUNTERS_DTYPE array [., .] on the host (a torch int64 tensor [., ., 8] is copied off the device)."""
+    from .analyzer import COUNTERS_DTYPE
+    if hasattr(rec, "data_ptr"):
+        rec = rec.cpu().numpy().view(COUNTERS_DTYPE).reshape(rec.shape[0], rec.shape[1])
+    return rec
+
+
+def narrative_timeline(index, fit_or_labels, stamp_origin, bucket_width, n_buckets, n_clusters=None, filter=None):
+    """How every narrative developed over time: `share_of_voice` of `index.label_summary` (oi_label_summary on the time axis,
+    one pass over labels, stamps and signals -- no corpus stream, whatever the bucket width or window asked for).  Entry [c][b]
+    holds narrative c's total in bucket b, its fraction of the bucket's labelled posts and the SocialSummary of its posts.
+    fit_or_labels: a NarrativeFit made with labels=True (n_clusters is then its number of centroids), or a label array
+    [n_docs] by local row (numpy or torch CUDA tensor) with n_clusters given."""
+    labels, K = _narrative_labels("narrative_timeline", fit_or_labels, n_clusters)
+    rec = index.label_summary(labels, K, n_buckets=int(n_buckets), stamp_origin=int(stamp_origin), bucket_width=int(bucket_width),
+                              filter=filter)
+    return share_of_voice(_host_records(rec))
+
+
+def narrative_tickers(index, fit_or_labels, tickers, key_mask: int, n_clusters=None, top: int = 10, rank_by: RankBy = RankBy.CROWDING,
+                      min_total: Optional[int] = None, n_keys: Optional[int] = None, filter=None, market_by_ticker=None,
+                      now: Optional[_dt.datetime] = None, cfg: EngineConfig = EngineConfig(), distinctive: bool = False) -> List[CompareOutput]:
+    """Which tickers every narrative is about, and what its posts feel per ticker: per cluster a CompareOutput -- compare_index
+    with the label in the similarity's place.  ONE ranked `index.label_groups` call by total (oi_label_summary on the key axis:
+    per cluster the `top` most-mentioned tickers with at least `min_total` posts, default `cfg.min_sample`), then
+    `rank_group_records` per cluster.  n_keys defaults to the number of names (a mapping: its largest key + 1).
+    distinctive=True lists instead the tickers a narrative holds MORE of than the labelled posts at large: the dense totals,
+    transposed to [n_keys, n_clusters], go through `retriever.rank_label_terms` with the per-cluster sums as the sizes -- its
+    order (excess = total[c][k] * A - size[c] * total[.][k] descending, then total descending, then key ascending, among the
+    keys with total >= max(min_total, 1)) is the rule wanted; top is then at most 64.
+    fit_or_labels as in narrative_timeline.  The index's signals must have been set with `cfg.bull_bear_threshold`."""
+    import numpy as np
+    from . import retriever
+    labels, K = _narrative_labels("narrative_tickers", fit_or_labels, n_clusters)
+    if n_keys is None:
+        n_keys = (max(tickers) + 1) if isinstance(tickers, dict) else len(tickers)
+    bar = int(cfg.min_sample if min_total is None else min_total)
+    if not distinctive:
+        res = index.label_groups(labels, K, int(key_mask), int(n_keys), top=int(top), rank_by="total", min_total=bar, filter=filter)
+        keys, counts, rec = res.keys, res.counts, _host_records(res.records)
+        if hasattr(keys, "data_ptr"):
+            keys, counts = keys.cpu().numpy().view(np.uint32), counts.cpu().numpy().view(np.uint32)
+        return [rank_group_records(keys[c], rec[c], int(counts[c]), tickers, rank_by, market_by_ticker, now, cfg) for c in range(K)]
+    rec = _host_records(index.label_groups(labels, K, int(key_mask), int(n_keys), filter=filter))
+    totals = np.ascontiguousarray(rec["total"].astype(np.uint32).T)            # [n_keys][n_clusters]
+    sizes = rec["total"].sum(axis=1, dtype=np.uint64)
+    terms, n = retriever.rank_label_terms(index.ctx, totals, sizes, top=int(top), min_df=max(bar, 1))
+    out = []
+    for c in range(K):
+        keys = [int(t) for t in terms[c]["term"][:int(n[c])]]
+        out.append(rank_group_records(keys, [rec[c][k] for k in keys], len(keys), tickers, rank_by, market_by_ticker, now, cfg))
+    return out
+
+
 # ----------------------------------------------------------------------------- wire format (#[derive(Serialize)])
 def scan_output_to_json(out: ScanOutput) -> str:
     """serde_json::to_string_pretty(&ScanOutput): `report` / `error` are skipped when None (tools.rs:180-183)."""

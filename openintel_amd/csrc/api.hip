@@ -1764,10 +1764,11 @@ static int similar_check_spec(const char *call, float threshold, const float *th
 }
 
 // The index and its state.  g takes the context's lock where every call took it: behind the embeddings check.  attrs_for: who
-// needs the doc attributes ("... need" / "... needs"), or null when this call does not.
-static int similar_check_state(const char *call, oi_index *idx, bool signals, const char *attrs_for, std::unique_lock<std::mutex> &g) {
+// needs the doc attributes ("... need" / "... needs"), or null when this call does not.  need_rows: the call reads the embeddings.
+static int similar_check_state(const char *call, oi_index *idx, bool signals, const char *attrs_for, std::unique_lock<std::mutex> &g,
+                               bool need_rows = true) {
     if (!idx) { oi_set_error("%s: null index", call); return OI_ERR_INVALID_ARG; }
-    if (!idx->rows && !idx->rows_bf16) { oi_set_error("%s: the index has no embeddings (oi_index_set_embeddings)", call); return OI_ERR_STATE; }
+    if (need_rows && !idx->rows && !idx->rows_bf16) { oi_set_error("%s: the index has no embeddings (oi_index_set_embeddings)", call); return OI_ERR_STATE; }
     g = std::unique_lock<std::mutex>(idx->ctx->mu);
     if (signals && !idx->signals.p) { oi_set_error("%s: the index has no signals (oi_index_set_signals)", call); return OI_ERR_STATE; }
     if (attrs_for && !idx->doc_attrs.p) {
@@ -2313,6 +2314,74 @@ extern "C" int oi_label_exemplars(oi_index *idx, const uint32_t *labels, const f
     OI_HIP_CHECK(hipMemcpyAsync(scores_out, d_scores, sizeof(float) * (size_t)K * top, hipMemcpyDeviceToHost, st));
     OI_HIP_CHECK(hipMemcpyAsync(docs_out, d_docs, sizeof(uint32_t) * (size_t)K * top, hipMemcpyDeviceToHost, st));
     OI_HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, cb, hipMemcpyDeviceToHost, st));
+    OI_HIP_CHECK(hipStreamSynchronize(st));
+    return OI_OK;
+}
+
+// ---------------------------------------------------------------- narrative breakdown (label_summary.hip)
+// The family's order of checks: the spec, the numbers, the buffers, the location, then the handle and its state; all of them
+// precede the first HIP call.  OI_DEVICE: no host synchronise anywhere.  Never captured.
+extern "C" int oi_label_summary(oi_index *idx, const uint32_t *labels, uint32_t K, const oi_label_summary_spec *spec, const oi_doc_filter *filter,
+                                int location, oi_social_counters *records_out, uint32_t *keys_out, uint32_t *counts_out,
+                                uint32_t *qualified_out) {
+    static_assert(sizeof(oi_label_summary_spec) == 32, "the spec is 32 bytes");
+    if (!spec) { oi_set_error("label_summary: null spec"); return OI_ERR_INVALID_ARG; }
+    OI_REQUIRE(spec->axis == OI_LABEL_AXIS_TIME || spec->axis == OI_LABEL_AXIS_KEY, "label_summary: axis=%u is not an OI_LABEL_AXIS_* value",
+               spec->axis);
+    const bool key_axis = spec->axis == OI_LABEL_AXIS_KEY;
+    OI_REQUIRE(spec->reserved == 0, "label_summary: reserved=%u (must be 0)", spec->reserved);
+    if (key_axis) {
+        const uint32_t mask = spec->stamp_origin, run = mask ? mask >> __builtin_ctz(mask) : 0u;
+        OI_REQUIRE(mask != 0 && (run & (run + 1u)) == 0u, "label_summary: key_mask=0x%x is not one contiguous run of bits", mask);
+        OI_REQUIRE(spec->bucket_width == 0, "label_summary: bucket_width=%u on the key axis (must be 0)", spec->bucket_width);
+        const uint64_t key_space = std::min<uint64_t>(1ull << __builtin_popcount(mask), OI_MAX_GROUP_KEYS);
+        OI_REQUIRE(spec->n_cells >= 1 && spec->n_cells <= key_space, "label_summary: n_cells=%u outside [1,%llu] (key_mask=0x%x)", spec->n_cells,
+                   (unsigned long long)key_space, mask);
+        OI_REQUIRE(spec->top <= OI_MAX_DEPTH, "label_summary: top=%u outside [0,%u]", spec->top, OI_MAX_DEPTH);
+    } else {
+        OI_REQUIRE(spec->n_cells >= 1 && spec->n_cells <= OI_MAX_VOLUME_BUCKETS, "label_summary: n_cells=%u outside [1,%u]", spec->n_cells,
+                   OI_MAX_VOLUME_BUCKETS);
+        OI_REQUIRE(spec->bucket_width != 0 || spec->n_cells == 1, "label_summary: bucket_width=0 (no time axis) with n_cells=%u", spec->n_cells);
+        OI_REQUIRE(spec->top == 0, "label_summary: top=%u on the time axis (ranked output is the key axis's)", spec->top);
+    }
+    OI_REQUIRE(spec->rank_by <= OI_GROUP_RANK_BEARISH, "label_summary: rank_by=%u is not an OI_GROUP_RANK_* value", spec->rank_by);
+    OI_REQUIRE(spec->top != 0 || spec->rank_by == 0, "label_summary: rank_by=%u with top=0 (must be 0)", spec->rank_by);
+    OI_REQUIRE(K >= 1 && K <= OI_MAX_CENTROIDS, "label_summary: n_clusters=%u outside [1,%u]", K, OI_MAX_CENTROIDS);
+    OI_REQUIRE((uint64_t)K * spec->n_cells <= OI_MAX_GROUP_CELLS, "label_summary: n_clusters * n_cells = %llu cells, more than %u",
+               (unsigned long long)K * spec->n_cells, OI_MAX_GROUP_CELLS);
+    OI_REQUIRE(labels && records_out, "label_summary: null buffer");
+    OI_REQUIRE(spec->top == 0 || (keys_out && counts_out), "label_summary: null buffer (keys_out / counts_out with top=%u)", spec->top);
+    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "label_summary: bad location %d", location);
+    std::unique_lock<std::mutex> g;
+    OI_CHECK(similar_check_state("label_summary", idx, true,
+                                 key_axis ? "the key axis needs" : (filter || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g, false));
+    oi_ctx *ctx = idx->ctx;
+    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    const uint32_t top = spec->top;
+    if (location == OI_DEVICE)
+        return oi_launch_label_summary(idx, labels, K, *spec, filter, records_out, top ? keys_out : nullptr, top ? counts_out : nullptr,
+                                       top ? qualified_out : nullptr);
+    // the host location: [labels | records | keys | counts | qualified] in the call's workspace, every part 256-byte aligned
+    hipStream_t st = ctx->stream;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t per_c = top ? top : spec->n_cells; // records (and, ranked, keys) per cluster
+    const size_t lb = up(sizeof(uint32_t) * (size_t)idx->n_docs), rb = sizeof(oi_social_counters) * (size_t)K * per_c;
+    const size_t kb = top ? up(sizeof(uint32_t) * (size_t)K * per_c) : 0, cb = top ? up(sizeof(uint32_t) * (size_t)K) : 0;
+    DevBuf &w = ctx->buf("label_summary_io");
+    OI_CHECK(w.ensure(lb + up(rb) + kb + 2 * cb));
+    uint8_t *d = w.as<uint8_t>();
+    if (idx->n_docs) OI_HIP_CHECK(hipMemcpyAsync(d, labels, sizeof(uint32_t) * (size_t)idx->n_docs, hipMemcpyHostToDevice, st));
+    oi_social_counters *d_records = reinterpret_cast<oi_social_counters *>(d + lb);
+    uint32_t *d_keys = reinterpret_cast<uint32_t *>(d + lb + up(rb)), *d_counts = reinterpret_cast<uint32_t *>(d + lb + up(rb) + kb),
+             *d_qual = reinterpret_cast<uint32_t *>(d + lb + up(rb) + kb + cb);
+    OI_CHECK(oi_launch_label_summary(idx, reinterpret_cast<const uint32_t *>(d), K, *spec, filter, d_records, top ? d_keys : nullptr,
+                                     top ? d_counts : nullptr, top && qualified_out ? d_qual : nullptr));
+    OI_HIP_CHECK(hipMemcpyAsync(records_out, d_records, rb, hipMemcpyDeviceToHost, st));
+    if (top) {
+        OI_HIP_CHECK(hipMemcpyAsync(keys_out, d_keys, sizeof(uint32_t) * (size_t)K * per_c, hipMemcpyDeviceToHost, st));
+        OI_HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, sizeof(uint32_t) * (size_t)K, hipMemcpyDeviceToHost, st));
+        if (qualified_out) OI_HIP_CHECK(hipMemcpyAsync(qualified_out, d_qual, sizeof(uint32_t) * (size_t)K, hipMemcpyDeviceToHost, st));
+    }
     OI_HIP_CHECK(hipStreamSynchronize(st));
     return OI_OK;
 }

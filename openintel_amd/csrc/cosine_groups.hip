@@ -193,6 +193,29 @@ __global__ __launch_bounds__(GR_THREADS) void groups_rank_kernel(const uint64_t 
     }
 }
 
+// ------------------------------------------------------------------ the finish of a key-axis tally, on the ctx stream
+// cells [n_cells / n_keys][n_keys] -> the caller's arrays.  top == 0: dense records, nothing else is written.  top >= 1: the
+// ranked output, with n_cells u64 of the caller's workspace behind rank_keys, timed under `rank_tag`.  (oi_similar_groups and
+// oi_label_summary share it: one ranking.)
+int oi_launch_groups_finish(oi_ctx *ctx, const uint32_t *cells, uint64_t n_cells, uint32_t n_keys, uint32_t top, uint32_t rank_by,
+                            uint32_t min_total, uint64_t *rank_keys, const char *rank_tag, oi_social_counters *d_records, uint32_t *d_keys,
+                            uint32_t *d_counts, uint32_t *d_qualified) {
+    const dim3 grid((uint32_t)std::min<uint64_t>((n_cells + 255) / 256, 1024));
+    if (top == 0) {
+        hipLaunchKernelGGL(groups_finish_kernel, grid, dim3(256), 0, ctx->stream, cells, n_cells, n_keys, 0u, 0u, d_records, (uint64_t *)nullptr);
+        OI_HIP_CHECK(hipGetLastError());
+        return OI_OK;
+    }
+    ProfScope ps(ctx, rank_tag);
+    hipLaunchKernelGGL(groups_finish_kernel, grid, dim3(256), 0, ctx->stream, cells, n_cells, n_keys, rank_by, std::max(min_total, 1u),
+                       (oi_social_counters *)nullptr, rank_keys);
+    OI_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(groups_rank_kernel, dim3((uint32_t)(n_cells / n_keys)), dim3(GR_THREADS), 0, ctx->stream, rank_keys, cells, n_keys, top,
+                       d_records, d_keys, d_counts, d_qualified);
+    OI_HIP_CHECK(hipGetLastError());
+    return OI_OK;
+}
+
 // ------------------------------------------------------------------ the key-axis tally
 // SmSum's cell and thresholds (cosine_summary.hip) with clause 2 on the key; the host part carries what the finish needs.
 struct GrOut {
@@ -216,23 +239,14 @@ struct GrSum {
                                       "groups", "groups_band", "groups_exact", "groups_fallback"};
     static const float *thr_block(const float *thr_q, uint32_t q0) { return thr_q ? thr_q + q0 : nullptr; }
     int finish(oi_ctx *ctx, uint64_t n_cells, const GrOut *out) const {
-        const dim3 grid((uint32_t)std::min<uint64_t>((n_cells + 255) / 256, 1024));
-        if (top == 0) {
-            hipLaunchKernelGGL(groups_finish_kernel, grid, dim3(256), 0, ctx->stream, cells, n_cells, n_keys, 0u, 0u, out->records,
-                               (uint64_t *)nullptr);
-            OI_HIP_CHECK(hipGetLastError());
-            return OI_OK;
+        uint64_t *rank_keys = nullptr;
+        if (top != 0) {
+            DevBuf &kb = ctx->buf("groups_keys");
+            OI_CHECK(kb.ensure(n_cells * sizeof(uint64_t)));
+            rank_keys = kb.as<uint64_t>();
         }
-        DevBuf &kb = ctx->buf("groups_keys");
-        OI_CHECK(kb.ensure(n_cells * sizeof(uint64_t)));
-        ProfScope ps(ctx, "groups_rank");
-        hipLaunchKernelGGL(groups_finish_kernel, grid, dim3(256), 0, ctx->stream, cells, n_cells, n_keys, rank_by, std::max(min_total, 1u),
-                           (oi_social_counters *)nullptr, kb.as<uint64_t>());
-        OI_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(groups_rank_kernel, dim3((uint32_t)(n_cells / n_keys)), dim3(GR_THREADS), 0, ctx->stream, kb.as<uint64_t>(), cells,
-                           n_keys, top, out->records, out->keys, out->counts, out->qualified);
-        OI_HIP_CHECK(hipGetLastError());
-        return OI_OK;
+        return oi_launch_groups_finish(ctx, cells, n_cells, n_keys, top, rank_by, min_total, rank_keys, "groups_rank", out->records, out->keys,
+                                       out->counts, out->qualified);
     }
 };
 

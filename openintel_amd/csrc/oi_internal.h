@@ -425,6 +425,17 @@ int oi_launch_label_terms_rank(oi_ctx *ctx, const uint32_t *d_counts, const uint
 // the launch) or null.  Asynchronous on the ctx stream; its workspace is "exemplars".
 int oi_launch_label_exemplars(oi_index *idx, const uint32_t *d_labels, const float *d_centroids, uint32_t n_clusters, uint32_t top,
                               const oi_doc_filter *filter, float *d_scores, uint32_t *d_docs, uint32_t *d_counts);
+// cosine_groups.hip: the finish of a key-axis tally -- cells [n_cells / n_keys][n_keys] to dense records (top == 0) or to the
+// ranked output (rank_keys: n_cells u64 of the caller's workspace; rank_tag: its profile tag).  Asynchronous on the ctx stream.
+int oi_launch_groups_finish(oi_ctx *ctx, const uint32_t *cells, uint64_t n_cells, uint32_t n_keys, uint32_t top, uint32_t rank_by,
+                            uint32_t min_total, uint64_t *rank_keys, const char *rank_tag, oi_social_counters *d_records, uint32_t *d_keys,
+                            uint32_t *d_counts, uint32_t *d_qualified);
+// label_summary.hip: the narrative breakdown -- device labels [n_docs] in; dense (spec.top == 0): device records
+// [n_clusters][n_cells] out; ranked: records and keys [n_clusters][top], counts and (may be null) qualified [n_clusters] out;
+// `filter` is the host's (by value into the launch) or null.  Asynchronous on the ctx stream; its workspace is "label_summary".
+int oi_launch_label_summary(oi_index *idx, const uint32_t *d_labels, uint32_t n_clusters, const oi_label_summary_spec &spec,
+                            const oi_doc_filter *filter, oi_social_counters *d_records, uint32_t *d_keys, uint32_t *d_counts,
+                            uint32_t *d_qualified);
 // cosine.hip
 // Sets pool.n_segs / pool.seg_cap for this chunk (the following select must use the same view).
 // run_gate != null: a launch of the gated exact pipeline behind a screen (search.hip: cosine_exact) -- the kernel exits at once

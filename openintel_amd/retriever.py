@@ -906,6 +906,61 @@ class HybridIndex(PostRetriever):
                                                _lib.ptr(out.cos_scores), _lib.ptr(out.cos_docs), _lib.ptr(out.cos_counts)))
         return out
 
+    def _label_summary(self, labels, n_clusters, spec, filter):
+        """One oi_label_summary call: numpy labels in, numpy out; torch CUDA labels in, tensors out (asynchronous)."""
+        from .analyzer import COUNTERS_DTYPE
+        K = int(n_clusters)
+        dev = _is_dev(labels)
+        top = int(spec.top)
+        rows = max(min(K, _lib.OI_MAX_CENTROIDS), 1)                # (a count out of range is refused by the library, not here)
+        per_c = max(min(top, _lib.OI_MAX_DEPTH) if top else min(int(spec.n_cells), _lib.OI_MAX_GROUP_CELLS // rows), 1)
+        if dev:
+            import torch
+            assert labels.is_contiguous() and labels.numel() == self.n_docs and labels.element_size() == 4
+            self._label_summary_keep = labels  # (an asynchronous call reads it later)
+            records = torch.zeros((rows, per_c, 8), dtype=torch.int64, device="cuda:%d" % self.ctx.device)
+        else:
+            labels = _np(labels, np.uint32)
+            assert labels.size == self.n_docs
+            records = np.zeros((rows, per_c), dtype=COUNTERS_DTYPE)
+        f = None
+        if filter is not None:
+            fa = np.ascontiguousarray(np.asarray(filter.cpu().numpy() if _is_dev(filter) else filter).astype(np.uint32, copy=False).reshape(4))
+            f = _lib.DocFilter(int(fa[0]), int(fa[1]), int(fa[2]), int(fa[3]))
+        keys = counts = qualified = None
+        if top:
+            keys, counts, qualified = (self._alloc(dev, (rows, per_c), np.uint32), self._alloc(dev, (rows,), np.uint32),
+                                       self._alloc(dev, (rows,), np.uint32))
+        _lib.check(self.lib.oi_label_summary(self.handle, _lib.ptr(labels), K, C.byref(spec), None if f is None else C.byref(f),
+                                             _lib.OI_DEVICE if dev else _lib.OI_HOST, _lib.ptr(records), _lib.ptr(keys),
+                                             _lib.ptr(counts), _lib.ptr(qualified)))
+        return GroupRanking(keys, records, counts, qualified) if top else records
+
+    def label_summary(self, labels, n_clusters: int, n_buckets: int = 1, stamp_origin: int = 0, bucket_width: int = 0, filter=None):
+        """oi_label_summary on the time axis: how each cluster of a labelling developed over time -- [n_clusters, n_buckets]
+        records (analyzer.COUNTERS_DTYPE) of the social_summary sums over the rows d with labels[d] == c < n_clusters that pass
+        `filter` (ONE {group_mask, group_value, stamp_lo, stamp_hi}, or None) and fall into bucket (stamp - stamp_origin) //
+        bucket_width (bucket_width = 0: one bucket).  Any other label, 0xFFFFFFFF included, is "no cluster".  Needs
+        set_signals(), and set_doc_attrs() with a time axis or a filter; no embeddings.  With the labels, axis and filter of a
+        similar_share or fit_narratives call the records are that call's, bit for bit.  Exact integers; records of shards add.
+        labels as in label_sums; numpy labels in, numpy out; torch CUDA labels in, an int64 [n_clusters, n_buckets, 8] tensor
+        holding the records' bits out (asynchronous on the ctx stream)."""
+        spec = _lib.LabelSummarySpec(_lib.OI_LABEL_AXIS_TIME, int(stamp_origin), int(bucket_width), int(n_buckets), 0, 0, 0, 0)
+        return self._label_summary(labels, n_clusters, spec, filter)
+
+    def label_groups(self, labels, n_clusters: int, key_mask: int, n_keys: int, top: int = 0, rank_by="total", min_total: int = 0,
+                     filter=None):
+        """oi_label_summary on the key axis: which tickers each cluster of a labelling is about -- one record per key =
+        (group & key_mask) >> ctz(key_mask) of the documents' group attribute; a key >= n_keys belongs to no record.  top == 0:
+        [n_clusters, n_keys] records, what shards add.  top >= 1: a GroupRanking as similar_groups returns it, with "query"
+        replaced by "cluster": the best `top` keys per cluster by rank_by ("total", "spec", "bullish", "bearish", or an
+        OI_GROUP_RANK_* value; ties by key ascending) among the keys with total >= max(min_total, 1).  Everything else as
+        label_summary (the filter carries a time window)."""
+        by = GROUP_RANKS[rank_by] if isinstance(rank_by, str) else int(rank_by)
+        spec = _lib.LabelSummarySpec(_lib.OI_LABEL_AXIS_KEY, int(key_mask), 0, int(n_keys), int(top), by if int(top) else 0,   # (dense: no ranking)
+                                     int(min_total), 0)
+        return self._label_summary(labels, n_clusters, spec, filter)
+
     def fit_narratives(self, seeds, threshold: float, max_iters: int = 20, n_buckets: int = 1, stamp_origin: int = 0,
                        bucket_width: int = 0, filter=None, labels: bool = False) -> "NarrativeFit":
         """oi_narratives_fit: k-means over the index on the device.  Starting from seeds [K, dim], similar_share (one
