@@ -1745,32 +1745,70 @@ extern "C" int oi_search_collapsed(oi_index *idx, const float *qv, const uint32_
     return check_overflow_locked(ctx);
 }
 
-// ---------------------------------------------------------------- the threshold family's entry points (oi_volume.h)
-// What oi_similar_volume / _summary / _groups / _share check and stage alike, written once; `call` is the entry point's name in
-// the messages.  In every call the checks keep their order -- the spec first (it can be judged without a handle), then the
-// buffers, the index, its state -- and all of them precede the first HIP call.  None of the four is ever captured.
+// ---------------------------------------------------------------- the analytics family's entry points
+// The threshold family (oi_volume.h), the mention summary (mention.hip), narrative discovery (centroids.hip, 4.14),
+// its seeding (seeds.hip, 4.16), narrative terms (label_terms.hip, 4.17), exemplars (label_exemplars.hip, 4.18) and the
+// breakdown (label_summary.hip, 4.19).  What they check and stage alike is written once; `call` is the entry point's name in
+// the messages.
+// The family's order of checks: the spec first (it can be judged without a handle), the numbers, the buffers, the location
+// (in the calls that check it), then the handle and its state, which takes the context's lock; all of them precede the first
+// HIP call.  OI_DEVICE: oi_label_terms, oi_label_exemplars and oi_label_summary make no host synchronise anywhere.  None of
+// the calls is ever captured.
 
-// The spec of the three calls with a time axis.  per_query: the call takes a thresholds array; max_cells: its cap on
+// One axis of cells.  The key axis: `mask` is one contiguous run of bits, there is no bucket width, n_cells lies within the key
+// space.  The time axis: the bucket rules (mask is not looked at).  cells_name: what the call's spec calls n_cells.
+static int check_axis(const char *call, bool key_axis, uint32_t mask, uint32_t bucket_width, uint32_t n_cells, const char *cells_name) {
+    if (key_axis) {
+        const uint32_t run = mask ? mask >> __builtin_ctz(mask) : 0u;
+        OI_REQUIRE(mask != 0 && (run & (run + 1u)) == 0u, "%s: key_mask=0x%x is not one contiguous run of bits", call, mask);
+        OI_REQUIRE(bucket_width == 0, "%s: bucket_width=%u on the key axis (must be 0)", call, bucket_width);
+        const uint64_t key_space = std::min<uint64_t>(1ull << __builtin_popcount(mask), OI_MAX_GROUP_KEYS);
+        OI_REQUIRE(n_cells >= 1 && n_cells <= key_space, "%s: %s=%u outside [1,%llu] (key_mask=0x%x)", call, cells_name, n_cells,
+                   (unsigned long long)key_space, mask);
+        return OI_OK;
+    }
+    OI_REQUIRE(n_cells >= 1 && n_cells <= OI_MAX_VOLUME_BUCKETS, "%s: %s=%u outside [1,%u]", call, cells_name, n_cells, OI_MAX_VOLUME_BUCKETS);
+    OI_REQUIRE(bucket_width != 0 || n_cells == 1, "%s: bucket_width=0 (no time axis) with %s=%u", call, cells_name, n_cells);
+    return OI_OK;
+}
+static int check_clusters(const char *call, uint32_t K) {
+    OI_REQUIRE(K >= 1 && K <= OI_MAX_CENTROIDS, "%s: n_clusters=%u outside [1,%u]", call, K, OI_MAX_CENTROIDS);
+    return OI_OK;
+}
+static int check_location(const char *call, int location) {
+    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "%s: bad location %d", call, location);
+    return OI_OK;
+}
+// every_list: the postings buffer must exist even where the index holds no posting (the mention summary's rule)
+static int check_finalized(const char *call, const oi_index *idx, bool every_list) {
+    if (!idx->finalized || !idx->cell_start.p || ((every_list || idx->n_postings) && !idx->postings.p)) {
+        oi_set_error("%s: the index is not finalized (oi_index_finalize makes the postings)", call);
+        return OI_ERR_STATE;
+    }
+    return OI_OK;
+}
+
+// The spec of the calls with a threshold and a time axis.  per_query: the call takes a thresholds array; max_cells: its cap on
 // n_queries * n_buckets (0: none).
 static int similar_check_spec(const char *call, float threshold, const float *thresholds, bool per_query, uint32_t n_buckets,
                               uint32_t bucket_width, uint32_t B, uint32_t max_cells) {
     OI_REQUIRE(thresholds || threshold == threshold, "%s: threshold is NaN%s", call, per_query ? " (and no thresholds array)" : "");
-    OI_REQUIRE(n_buckets >= 1 && n_buckets <= OI_MAX_VOLUME_BUCKETS, "%s: n_buckets=%u outside [1,%u]", call, n_buckets, OI_MAX_VOLUME_BUCKETS);
-    OI_REQUIRE(bucket_width != 0 || n_buckets == 1, "%s: bucket_width=0 (no time axis) with n_buckets=%u", call, n_buckets);
+    OI_CHECK(check_axis(call, false, 0, bucket_width, n_buckets, "n_buckets"));
     OI_REQUIRE(B <= 4096, "%s: n_queries=%u outside [0,4096]", call, B);
     OI_REQUIRE(!max_cells || (uint64_t)B * n_buckets <= max_cells, "%s: n_queries * n_buckets = %llu cells, more than %u", call,
                (unsigned long long)B * n_buckets, max_cells);
     return OI_OK;
 }
 
-// The index and its state.  g takes the context's lock where every call took it: behind the embeddings check.  attrs_for: who
-// needs the doc attributes ("... need" / "... needs"), or null when this call does not.  need_rows: the call reads the embeddings.
-static int similar_check_state(const char *call, oi_index *idx, bool signals, const char *attrs_for, std::unique_lock<std::mutex> &g,
-                               bool need_rows = true) {
+// The index and what of its state the call needs.  g takes the context's lock where every call took it: behind the embeddings
+// check.  attrs_for: who needs the doc attributes ("... need" / "... needs"), or null when this call does not.
+enum : unsigned { NEED_ROWS = 1, NEED_SIGNALS = 2, NEED_POSTINGS = 4 };
+static int check_index_state(const char *call, oi_index *idx, unsigned needs, const char *attrs_for, std::unique_lock<std::mutex> &g) {
     if (!idx) { oi_set_error("%s: null index", call); return OI_ERR_INVALID_ARG; }
-    if (need_rows && !idx->rows && !idx->rows_bf16) { oi_set_error("%s: the index has no embeddings (oi_index_set_embeddings)", call); return OI_ERR_STATE; }
+    if ((needs & NEED_ROWS) && !idx->rows && !idx->rows_bf16) { oi_set_error("%s: the index has no embeddings (oi_index_set_embeddings)", call); return OI_ERR_STATE; }
     g = std::unique_lock<std::mutex>(idx->ctx->mu);
-    if (signals && !idx->signals.p) { oi_set_error("%s: the index has no signals (oi_index_set_signals)", call); return OI_ERR_STATE; }
+    if (needs & NEED_POSTINGS) OI_CHECK(check_finalized(call, idx, true));
+    if ((needs & NEED_SIGNALS) && !idx->signals.p) { oi_set_error("%s: the index has no signals (oi_index_set_signals)", call); return OI_ERR_STATE; }
     if (attrs_for && !idx->doc_attrs.p) {
         oi_set_error("%s: %s the index's doc attributes (oi_index_set_doc_attrs)", call, attrs_for);
         return OI_ERR_STATE;
@@ -1779,35 +1817,38 @@ static int similar_check_state(const char *call, oi_index *idx, bool signals, co
 }
 #define SIMILAR_TIME_AXIS "filters / time buckets need"
 
-// The host location: [vectors | filters | thresholds | outputs ...] in the call's workspace `io`, copied in; launch(vectors,
-// thresholds, filters, first output) on the device; then every output with a host pointer copied back, and the stream awaited.
-// An output without one (null) still has its room: the launch may write it.
-struct SimilarOut { void *host; size_t bytes; };
-template <class Launch>
-static int similar_staged(oi_index *idx, const char *io, const float *qv, uint32_t B, const float *thresholds, const oi_doc_filter *filters,
-                          std::initializer_list<SimilarOut> outs, Launch launch) {
+// The host location of every call of the family: [inputs ... | outputs ...] in the call's workspace `io`, each part aligned to
+// `granule`.  The inputs are copied in; launch(in, out) gets the parts' device pointers; then every output with a host pointer
+// is copied back and the stream awaited.  An input without a host pointer is absent: no room, in[i] null.  An output of 0 bytes
+// is absent: out[i] null; one without a host pointer still has its room, the launch may write it.
+struct StageIn { const void *host; size_t bytes; };
+struct StageOut { void *host; size_t bytes; };
+template <size_t NI, size_t NO, class Launch>
+static int staged_call(oi_ctx *ctx, const char *io, size_t granule, const StageIn (&ins)[NI], const StageOut (&outs)[NO], Launch launch) {
     static_assert(sizeof(oi_doc_filter) == sizeof(uint4), "oi_doc_filter is 16 bytes");
-    oi_ctx *ctx = idx->ctx;
     hipStream_t st = ctx->stream;
-    const size_t vb = (sizeof(float) * (size_t)B * idx->dim + 15) & ~(size_t)15, fb = filters ? sizeof(oi_doc_filter) * (size_t)B : 0;
-    const size_t tb = thresholds ? (sizeof(float) * (size_t)B + 15) & ~(size_t)15 : 0;
-    size_t ob = 0;
-    for (const SimilarOut &o : outs) ob += o.bytes;
+    StageLayout lay(granule);
+    size_t in_at[NI], out_at[NO];
+    for (size_t i = 0; i < NI; ++i) in_at[i] = lay.add(ins[i].host ? ins[i].bytes : 0);
+    for (size_t i = 0; i < NO; ++i) out_at[i] = lay.add(outs[i].bytes);
     DevBuf &w = ctx->buf(io);
-    OI_CHECK(w.ensure(vb + fb + tb + ob + 64));
-    uint8_t *d = w.as<uint8_t>(), *d_out = d + vb + fb + tb;
-    OI_HIP_CHECK(hipMemcpyAsync(d, qv, sizeof(float) * (size_t)B * idx->dim, hipMemcpyHostToDevice, st));
-    if (filters) OI_HIP_CHECK(hipMemcpyAsync(d + vb, filters, fb, hipMemcpyHostToDevice, st));
-    if (thresholds) OI_HIP_CHECK(hipMemcpyAsync(d + vb + fb, thresholds, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, st));
-    OI_CHECK(launch(reinterpret_cast<const float *>(d), thresholds ? reinterpret_cast<const float *>(d + vb + fb) : nullptr,
-                    filters ? reinterpret_cast<const uint4 *>(d + vb) : nullptr, d_out));
-    for (const SimilarOut &o : outs) {
-        if (o.host && o.bytes) OI_HIP_CHECK(hipMemcpyAsync(o.host, d_out, o.bytes, hipMemcpyDeviceToHost, st));
-        d_out += o.bytes;
+    OI_CHECK(w.ensure(lay.total()));
+    void *in[NI], *out[NO];
+    for (size_t i = 0; i < NI; ++i) {
+        in[i] = ins[i].host ? lay.at<void>(w.p, in_at[i]) : nullptr;
+        if (ins[i].host && ins[i].bytes) OI_HIP_CHECK(hipMemcpyAsync(in[i], ins[i].host, ins[i].bytes, hipMemcpyHostToDevice, st));
     }
+    for (size_t i = 0; i < NO; ++i) out[i] = outs[i].bytes ? lay.at<void>(w.p, out_at[i]) : nullptr;
+    OI_CHECK(launch(in, out));
+    for (size_t i = 0; i < NO; ++i)
+        if (outs[i].host && outs[i].bytes) OI_HIP_CHECK(hipMemcpyAsync(outs[i].host, out[i], outs[i].bytes, hipMemcpyDeviceToHost, st));
     OI_HIP_CHECK(hipStreamSynchronize(st));
     return OI_OK;
 }
+template <class T> static T *part(void *const *parts, size_t i) { return static_cast<T *>(parts[i]); }
+// the staged inputs of the threshold family: the query vectors, the filters, the thresholds (the last two may be null)
+#define SIMILAR_INPUTS(thresholds) \
+    {{qv, sizeof(float) * (size_t)B * idx->dim}, {filters, sizeof(oi_doc_filter) * (size_t)B}, {thresholds, sizeof(float) * (size_t)B}}
 
 // similarity volume (cosine_volume.hip)
 extern "C" int oi_similar_volume(oi_index *idx, const float *qv, uint32_t B, const oi_volume_spec *spec, const oi_doc_filter *filters,
@@ -1816,14 +1857,14 @@ extern "C" int oi_similar_volume(oi_index *idx, const float *qv, uint32_t B, con
     OI_CHECK(similar_check_spec("similar_volume", spec->threshold, nullptr, false, spec->n_buckets, spec->bucket_width, B, 0));
     OI_REQUIRE(B == 0 || (qv && counts_out), "similar_volume: null buffer");
     std::unique_lock<std::mutex> g;
-    OI_CHECK(similar_check_state("similar_volume", idx, false, (filters || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
+    OI_CHECK(check_index_state("similar_volume", idx, NEED_ROWS, (filters || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
     if (B == 0) return OI_OK;
     OI_HIP_CHECK(hipSetDevice(idx->ctx->device));
     if (location == OI_DEVICE) return oi_launch_similar_volume(idx, qv, B, *spec, reinterpret_cast<const uint4 *>(filters), counts_out);
-    return similar_staged(idx, "volume_io", qv, B, nullptr, filters, {{counts_out, sizeof(uint32_t) * (size_t)B * spec->n_buckets}},
-                          [&](const float *q, const float *, const uint4 *f, uint8_t *o) {
-                              return oi_launch_similar_volume(idx, q, B, *spec, f, reinterpret_cast<uint32_t *>(o));
-                          });
+    return staged_call(idx->ctx, "volume_io", 16, SIMILAR_INPUTS(nullptr), {{counts_out, sizeof(uint32_t) * (size_t)B * spec->n_buckets}},
+                       [&](void *const *in, void *const *out) {
+                           return oi_launch_similar_volume(idx, part<const float>(in, 0), B, *spec, part<const uint4>(in, 1), part<uint32_t>(out, 0));
+                       });
 }
 
 // similarity summary (cosine_summary.hip)
@@ -1833,15 +1874,16 @@ extern "C" int oi_similar_summary(oi_index *idx, const float *qv, uint32_t B, co
     OI_CHECK(similar_check_spec("similar_summary", spec->threshold, thresholds, true, spec->n_buckets, spec->bucket_width, B, OI_MAX_SUMMARY_CELLS));
     OI_REQUIRE(B == 0 || (qv && out), "similar_summary: null buffer");
     std::unique_lock<std::mutex> g;
-    OI_CHECK(similar_check_state("similar_summary", idx, true, (filters || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
+    OI_CHECK(check_index_state("similar_summary", idx, NEED_ROWS | NEED_SIGNALS, (filters || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
     if (B == 0) return OI_OK;
     OI_HIP_CHECK(hipSetDevice(idx->ctx->device));
     if (location == OI_DEVICE)
         return oi_launch_similar_summary(idx, qv, B, *spec, thresholds, reinterpret_cast<const uint4 *>(filters), out);
-    return similar_staged(idx, "summary_io", qv, B, thresholds, filters, {{out, sizeof(oi_social_counters) * (size_t)B * spec->n_buckets}},
-                          [&](const float *q, const float *t, const uint4 *f, uint8_t *o) {
-                              return oi_launch_similar_summary(idx, q, B, *spec, t, f, reinterpret_cast<oi_social_counters *>(o));
-                          });
+    return staged_call(idx->ctx, "summary_io", 16, SIMILAR_INPUTS(thresholds), {{out, sizeof(oi_social_counters) * (size_t)B * spec->n_buckets}},
+                       [&](void *const *in, void *const *o) {
+                           return oi_launch_similar_summary(idx, part<const float>(in, 0), B, *spec, part<const float>(in, 2), part<const uint4>(in, 1),
+                                                            part<oi_social_counters>(o, 0));
+                       });
 }
 
 // similarity leaderboard (cosine_groups.hip): its spec is its own, the rest as above
@@ -1850,11 +1892,7 @@ extern "C" int oi_similar_groups(oi_index *idx, const float *qv, uint32_t B, con
                                  uint32_t *counts_out, uint32_t *qualified_out) {
     OI_REQUIRE(spec, "similar_groups: null spec");
     OI_REQUIRE(thresholds || spec->threshold == spec->threshold, "similar_groups: threshold is NaN (and no thresholds array)");
-    const uint32_t mask = spec->key_mask, run = mask ? mask >> __builtin_ctz(mask) : 0u;
-    OI_REQUIRE(mask != 0 && (run & (run + 1u)) == 0u, "similar_groups: key_mask=0x%x is not one contiguous run of bits", mask);
-    const uint64_t key_space = std::min<uint64_t>(1ull << __builtin_popcount(mask), OI_MAX_GROUP_KEYS);
-    OI_REQUIRE(spec->n_keys >= 1 && spec->n_keys <= key_space, "similar_groups: n_keys=%u outside [1,%llu] (key_mask=0x%x)", spec->n_keys,
-               (unsigned long long)key_space, mask);
+    OI_CHECK(check_axis("similar_groups", true, spec->key_mask, 0, spec->n_keys, "n_keys"));
     OI_REQUIRE(spec->top <= OI_MAX_DEPTH, "similar_groups: top=%u outside [0,%u]", spec->top, OI_MAX_DEPTH);
     OI_REQUIRE(spec->rank_by <= OI_GROUP_RANK_BEARISH, "similar_groups: rank_by=%u is not an OI_GROUP_RANK_* value", spec->rank_by);
     OI_REQUIRE(B <= 4096, "similar_groups: n_queries=%u outside [0,4096]", B);
@@ -1863,21 +1901,21 @@ extern "C" int oi_similar_groups(oi_index *idx, const float *qv, uint32_t B, con
     OI_REQUIRE(B == 0 || (qv && records_out), "similar_groups: null buffer");
     OI_REQUIRE(B == 0 || spec->top == 0 || (keys_out && counts_out), "similar_groups: null buffer (keys_out / counts_out with top=%u)", spec->top);
     std::unique_lock<std::mutex> g;
-    OI_CHECK(similar_check_state("similar_groups", idx, true, "the key axis needs", g));
+    OI_CHECK(check_index_state("similar_groups", idx, NEED_ROWS | NEED_SIGNALS, "the key axis needs", g));
     if (B == 0) return OI_OK;
     OI_HIP_CHECK(hipSetDevice(idx->ctx->device));
     if (location == OI_DEVICE)
         return oi_launch_similar_groups(idx, qv, B, *spec, thresholds, reinterpret_cast<const uint4 *>(filters), records_out, keys_out,
                                         counts_out, qualified_out);
     const size_t per_q = spec->top ? spec->top : spec->n_keys; // records (and, ranked, keys) per query
-    const size_t rb = sizeof(oi_social_counters) * (size_t)B * per_q;
     const size_t kb = spec->top ? sizeof(uint32_t) * (size_t)B * per_q : 0, cb = spec->top ? sizeof(uint32_t) * (size_t)B : 0;
-    return similar_staged(idx, "groups_io", qv, B, thresholds, filters, {{records_out, rb}, {keys_out, kb}, {counts_out, cb}, {qualified_out, cb}},
-                          [&](const float *q, const float *t, const uint4 *f, uint8_t *o) {
-                              uint32_t *d_keys = reinterpret_cast<uint32_t *>(o + rb), *d_counts = d_keys + (size_t)B * per_q, *d_qual = d_counts + B;
-                              return oi_launch_similar_groups(idx, q, B, *spec, t, f, reinterpret_cast<oi_social_counters *>(o),
-                                                              spec->top ? d_keys : nullptr, spec->top ? d_counts : nullptr, spec->top ? d_qual : nullptr);
-                          });
+    return staged_call(idx->ctx, "groups_io", 16, SIMILAR_INPUTS(thresholds),
+                       {{records_out, sizeof(oi_social_counters) * (size_t)B * per_q}, {keys_out, kb}, {counts_out, cb}, {qualified_out, cb}},
+                       [&](void *const *in, void *const *out) { // (dense: keys, counts and qualified are absent)
+                           return oi_launch_similar_groups(idx, part<const float>(in, 0), B, *spec, part<const float>(in, 2), part<const uint4>(in, 1),
+                                                           part<oi_social_counters>(out, 0), part<uint32_t>(out, 1), part<uint32_t>(out, 2),
+                                                           part<uint32_t>(out, 3));
+                       });
 }
 
 // similarity share (cosine_share.hip).  labels_out may be null.
@@ -1887,7 +1925,7 @@ extern "C" int oi_similar_share(oi_index *idx, const float *qv, uint32_t B, cons
     OI_CHECK(similar_check_spec("similar_share", spec->threshold, thresholds, true, spec->n_buckets, spec->bucket_width, B, OI_MAX_SUMMARY_CELLS));
     OI_REQUIRE(B == 0 || (qv && out), "similar_share: null buffer");
     std::unique_lock<std::mutex> g;
-    OI_CHECK(similar_check_state("similar_share", idx, true, (filters || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
+    OI_CHECK(check_index_state("similar_share", idx, NEED_ROWS | NEED_SIGNALS, (filters || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
     OI_HIP_CHECK(hipSetDevice(idx->ctx->device));
     const size_t lb = labels_out ? sizeof(uint32_t) * (size_t)idx->n_docs : 0;
     if (B == 0) { // no query: no row has a candidate
@@ -1897,41 +1935,26 @@ extern "C" int oi_similar_share(oi_index *idx, const float *qv, uint32_t B, cons
     }
     if (location == OI_DEVICE)
         return oi_launch_similar_share(idx, qv, B, *spec, thresholds, reinterpret_cast<const uint4 *>(filters), out, labels_out);
-    const size_t ob = sizeof(oi_social_counters) * (size_t)B * spec->n_buckets;
-    return similar_staged(idx, "share_io", qv, B, thresholds, filters, {{out, ob}, {labels_out, lb}},
-                          [&](const float *q, const float *t, const uint4 *f, uint8_t *o) {
-                              return oi_launch_similar_share(idx, q, B, *spec, t, f, reinterpret_cast<oi_social_counters *>(o),
-                                                             lb ? reinterpret_cast<uint32_t *>(o + ob) : nullptr);
-                          });
+    return staged_call(idx->ctx, "share_io", 16, SIMILAR_INPUTS(thresholds),
+                       {{out, sizeof(oi_social_counters) * (size_t)B * spec->n_buckets}, {labels_out, lb}}, [&](void *const *in, void *const *o) {
+                           return oi_launch_similar_share(idx, part<const float>(in, 0), B, *spec, part<const float>(in, 2), part<const uint4>(in, 1),
+                                                          part<oi_social_counters>(o, 0), part<uint32_t>(o, 1));
+                       });
 }
 
-// ---------------------------------------------------------------- mention summary (mention.hip)
-// The family's order of checks: the spec, the numbers, the buffers, then the handle and its state; all of them precede the
-// first HIP call.  Never captured.
+// mention summary (mention.hip)
 extern "C" int oi_mention_summary(oi_index *idx, const uint32_t *qt, const uint32_t *qo, uint32_t B, const oi_mention_spec *spec,
                                   const uint32_t *min_match, const oi_doc_filter *filters, int location, oi_social_counters *out) {
-    static_assert(sizeof(oi_doc_filter) == sizeof(uint4), "oi_doc_filter is 16 bytes");
     OI_REQUIRE(spec, "mention_summary: null spec");
     OI_REQUIRE(spec->axis == OI_MENTION_AXIS_TIME || spec->axis == OI_MENTION_AXIS_KEY, "mention_summary: axis=%u is not an OI_MENTION_AXIS_* value",
                spec->axis);
     const bool key_axis = spec->axis == OI_MENTION_AXIS_KEY;
-    if (key_axis) {
-        const uint32_t mask = spec->stamp_origin, run = mask ? mask >> __builtin_ctz(mask) : 0u;
-        OI_REQUIRE(mask != 0 && (run & (run + 1u)) == 0u, "mention_summary: key_mask=0x%x is not one contiguous run of bits", mask);
-        OI_REQUIRE(spec->bucket_width == 0, "mention_summary: bucket_width=%u on the key axis (must be 0)", spec->bucket_width);
-        const uint64_t key_space = std::min<uint64_t>(1ull << __builtin_popcount(mask), OI_MAX_GROUP_KEYS);
-        OI_REQUIRE(spec->n_cells >= 1 && spec->n_cells <= key_space, "mention_summary: n_cells=%u outside [1,%llu] (key_mask=0x%x)", spec->n_cells,
-                   (unsigned long long)key_space, mask);
-    } else {
-        OI_REQUIRE(spec->n_cells >= 1 && spec->n_cells <= OI_MAX_VOLUME_BUCKETS, "mention_summary: n_cells=%u outside [1,%u]", spec->n_cells,
-                   OI_MAX_VOLUME_BUCKETS);
-        OI_REQUIRE(spec->bucket_width != 0 || spec->n_cells == 1, "mention_summary: bucket_width=0 (no time axis) with n_cells=%u", spec->n_cells);
-    }
+    OI_CHECK(check_axis("mention_summary", key_axis, spec->stamp_origin, spec->bucket_width, spec->n_cells, "n_cells"));
     OI_REQUIRE(B <= 4096, "mention_summary: n_queries=%u outside [0,4096]", B);
     OI_REQUIRE((uint64_t)B * spec->n_cells <= OI_MAX_GROUP_CELLS, "mention_summary: n_queries * n_cells = %llu cells, more than %u",
                (unsigned long long)B * spec->n_cells, OI_MAX_GROUP_CELLS);
     OI_REQUIRE(B == 0 || (qt && qo && out), "mention_summary: null buffer");
-    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "mention_summary: bad location %d", location);
+    OI_CHECK(check_location("mention_summary", location));
     uint32_t nt = 0;
     if (location == OI_HOST && B) { // (device offsets are not host-visible: the plan kernel refuses such a query by itself)
         for (uint32_t q = 0; q < B; ++q) {
@@ -1941,100 +1964,61 @@ extern "C" int oi_mention_summary(oi_index *idx, const uint32_t *qt, const uint3
         }
         nt = qo[B] - qo[0];
     }
-    if (!idx) { oi_set_error("mention_summary: null index"); return OI_ERR_INVALID_ARG; }
-    oi_ctx *ctx = idx->ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (!idx->finalized || !idx->postings.p || !idx->cell_start.p) {
-        oi_set_error("mention_summary: the index is not finalized (oi_index_finalize makes the postings)");
-        return OI_ERR_STATE;
-    }
-    if (!idx->signals.p) { oi_set_error("mention_summary: the index has no signals (oi_index_set_signals)"); return OI_ERR_STATE; }
-    if ((key_axis || filters || spec->bucket_width) && !idx->doc_attrs.p) {
-        oi_set_error("mention_summary: %s the index's doc attributes (oi_index_set_doc_attrs)", key_axis ? "the key axis needs" : SIMILAR_TIME_AXIS);
-        return OI_ERR_STATE;
-    }
+    std::unique_lock<std::mutex> g;
+    OI_CHECK(check_index_state("mention_summary", idx, NEED_SIGNALS | NEED_POSTINGS,
+                               key_axis ? "the key axis needs" : (filters || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
     OI_REQUIRE((uint64_t)idx->n_blocks * B <= 0xFFFFFFFFull, "mention_summary: %llu (query, doc block) tasks, more than 2^32 - 1",
                (unsigned long long)idx->n_blocks * B);
     if (B == 0) return OI_OK;
-    OI_HIP_CHECK(hipSetDevice(ctx->device));
-    const uint4 *filt = reinterpret_cast<const uint4 *>(filters);
-    if (location == OI_DEVICE) return oi_launch_mention_summary(idx, qt, qo, B, *spec, min_match, filt, out);
-    // the host location: [offsets | terms | min_match | filters | records] in the call's workspace, every part 16-byte aligned
-    hipStream_t st = ctx->stream;
-    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t ob = up16(sizeof(uint32_t) * ((size_t)B + 1)), tb = up16(sizeof(uint32_t) * (size_t)(nt ? nt : 1));
-    const size_t mb = min_match ? up16(sizeof(uint32_t) * (size_t)B) : 0, fb = filters ? sizeof(oi_doc_filter) * (size_t)B : 0;
-    const size_t rb = sizeof(oi_social_counters) * (size_t)B * spec->n_cells;
-    DevBuf &w = ctx->buf("mention_io");
-    OI_CHECK(w.ensure(ob + tb + mb + fb + rb));
-    uint8_t *d = w.as<uint8_t>();
-    std::vector<uint32_t> rel(qo, qo + B + 1); // offsets relative to the first staged term
-    for (uint32_t &o : rel) o -= qo[0];
-    OI_HIP_CHECK(hipMemcpyAsync(d, rel.data(), sizeof(uint32_t) * ((size_t)B + 1), hipMemcpyHostToDevice, st));
-    if (nt) OI_HIP_CHECK(hipMemcpyAsync(d + ob, qt + qo[0], sizeof(uint32_t) * (size_t)nt, hipMemcpyHostToDevice, st));
-    if (min_match) OI_HIP_CHECK(hipMemcpyAsync(d + ob + tb, min_match, sizeof(uint32_t) * (size_t)B, hipMemcpyHostToDevice, st));
-    if (filters) OI_HIP_CHECK(hipMemcpyAsync(d + ob + tb + mb, filters, fb, hipMemcpyHostToDevice, st));
-    OI_HIP_CHECK(hipStreamSynchronize(st)); // (`rel` is pageable and dies with this call)
-    oi_social_counters *d_out = reinterpret_cast<oi_social_counters *>(d + ob + tb + mb + fb);
-    OI_CHECK(oi_launch_mention_summary(idx, reinterpret_cast<const uint32_t *>(d + ob), reinterpret_cast<const uint32_t *>(d), B, *spec,
-                                       min_match ? reinterpret_cast<const uint32_t *>(d + ob + tb) : nullptr,
-                                       filters ? reinterpret_cast<const uint4 *>(d + ob + tb + mb) : nullptr, d_out));
-    OI_HIP_CHECK(hipMemcpyAsync(out, d_out, rb, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipStreamSynchronize(st));
-    return OI_OK;
-}
-
-// ---------------------------------------------------------------- narrative discovery (centroids.hip)
-// The checks keep the family's order: the numbers, the buffers, then the handle; all of them precede the first HIP call.
-
-// the update step's reduction: labels -> integer sums and counts per cluster
-extern "C" int oi_label_sums(oi_index *idx, const uint32_t *labels, uint32_t K, int location, int64_t *sums_out, uint64_t *counts_out) {
-    OI_REQUIRE(K >= 1 && K <= OI_MAX_CENTROIDS, "label_sums: n_clusters=%u outside [1,%u]", K, OI_MAX_CENTROIDS);
-    OI_REQUIRE(labels && sums_out && counts_out, "label_sums: null buffer");
-    std::unique_lock<std::mutex> g;
-    OI_CHECK(similar_check_state("label_sums", idx, false, nullptr, g));
     oi_ctx *ctx = idx->ctx;
     OI_HIP_CHECK(hipSetDevice(ctx->device));
+    if (location == OI_DEVICE) return oi_launch_mention_summary(idx, qt, qo, B, *spec, min_match, reinterpret_cast<const uint4 *>(filters), out);
+    std::vector<uint32_t> rel(qo, qo + B + 1); // offsets relative to the first staged term
+    for (uint32_t &o : rel) o -= qo[0];
+    return staged_call(ctx, "mention_io", 16,
+                       {{rel.data(), sizeof(uint32_t) * ((size_t)B + 1)}, {qt + qo[0], sizeof(uint32_t) * (size_t)nt},
+                        {min_match, sizeof(uint32_t) * (size_t)B}, {filters, sizeof(oi_doc_filter) * (size_t)B}},
+                       {{out, sizeof(oi_social_counters) * (size_t)B * spec->n_cells}}, [&](void *const *in, void *const *o) -> int {
+                           OI_HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (`rel` is pageable and dies with this call)
+                           return oi_launch_mention_summary(idx, part<const uint32_t>(in, 1), part<const uint32_t>(in, 0), B, *spec,
+                                                            part<const uint32_t>(in, 2), part<const uint4>(in, 3), part<oi_social_counters>(o, 0));
+                       });
+}
+
+// ---- narrative discovery (centroids.hip)
+// the update step's reduction: labels -> integer sums and counts per cluster
+extern "C" int oi_label_sums(oi_index *idx, const uint32_t *labels, uint32_t K, int location, int64_t *sums_out, uint64_t *counts_out) {
+    OI_CHECK(check_clusters("label_sums", K));
+    OI_REQUIRE(labels && sums_out && counts_out, "label_sums: null buffer");
+    std::unique_lock<std::mutex> g;
+    OI_CHECK(check_index_state("label_sums", idx, NEED_ROWS, nullptr, g));
+    OI_HIP_CHECK(hipSetDevice(idx->ctx->device));
     if (location == OI_DEVICE) return oi_launch_label_sums(idx, labels, K, sums_out, counts_out);
-    hipStream_t st = ctx->stream;
-    const size_t lb = (sizeof(uint32_t) * (size_t)idx->n_docs + 15) & ~(size_t)15, sb = sizeof(int64_t) * (size_t)K * idx->dim,
-                 cb = sizeof(uint64_t) * (size_t)K;
-    DevBuf &w = ctx->buf("label_sums_io");
-    OI_CHECK(w.ensure(lb + sb + cb));
-    uint8_t *d = w.as<uint8_t>();
-    if (idx->n_docs) OI_HIP_CHECK(hipMemcpyAsync(d, labels, sizeof(uint32_t) * (size_t)idx->n_docs, hipMemcpyHostToDevice, st));
-    OI_CHECK(oi_launch_label_sums(idx, reinterpret_cast<const uint32_t *>(d), K, reinterpret_cast<int64_t *>(d + lb),
-                                  reinterpret_cast<uint64_t *>(d + lb + sb)));
-    OI_HIP_CHECK(hipMemcpyAsync(sums_out, d + lb, sb, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(counts_out, d + lb + sb, cb, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipStreamSynchronize(st));
-    return OI_OK;
+    return staged_call(idx->ctx, "label_sums_io", 16, {{labels, sizeof(uint32_t) * (size_t)idx->n_docs}},
+                       {{sums_out, sizeof(int64_t) * (size_t)K * idx->dim}, {counts_out, sizeof(uint64_t) * (size_t)K}},
+                       [&](void *const *in, void *const *out) {
+                           return oi_launch_label_sums(idx, part<const uint32_t>(in, 0), K, part<int64_t>(out, 0), part<uint64_t>(out, 1));
+                       });
 }
 
 // sums -> unit vectors
 extern "C" int oi_centroids_from_sums(oi_ctx *ctx, const int64_t *sums, const uint64_t *counts, const float *previous, uint32_t K,
                                       uint32_t dim, int location, float *out) {
-    OI_REQUIRE(K >= 1 && K <= OI_MAX_CENTROIDS, "centroids_from_sums: n_clusters=%u outside [1,%u]", K, OI_MAX_CENTROIDS);
+    OI_CHECK(check_clusters("centroids_from_sums", K));
     OI_REQUIRE(dim >= 4 && dim <= OI_MAX_DIM && dim % 4 == 0, "centroids_from_sums: dim=%u is not a multiple of 4 in [4,%u]", dim, OI_MAX_DIM);
     OI_REQUIRE(sums && counts && out, "centroids_from_sums: null buffer");
     OI_REQUIRE(ctx, "centroids_from_sums: null ctx");
     std::lock_guard<std::mutex> g(ctx->mu);
     OI_HIP_CHECK(hipSetDevice(ctx->device));
     if (location == OI_DEVICE) return oi_launch_centroids_from_sums(ctx, sums, counts, previous, K, dim, out);
-    hipStream_t st = ctx->stream;
-    const size_t sb = sizeof(int64_t) * (size_t)K * dim, cb = sizeof(uint64_t) * (size_t)K, vb = sizeof(float) * (size_t)K * dim;
-    DevBuf &w = ctx->buf("centroids_io");
-    OI_CHECK(w.ensure(sb + cb + vb));
-    uint8_t *d = w.as<uint8_t>();
-    float *d_v = reinterpret_cast<float *>(d + sb + cb);
-    OI_HIP_CHECK(hipMemcpyAsync(d, sums, sb, hipMemcpyHostToDevice, st));
-    OI_HIP_CHECK(hipMemcpyAsync(d + sb, counts, cb, hipMemcpyHostToDevice, st));
-    if (previous) OI_HIP_CHECK(hipMemcpyAsync(d_v, previous, vb, hipMemcpyHostToDevice, st));
-    OI_CHECK(oi_launch_centroids_from_sums(ctx, reinterpret_cast<const int64_t *>(d), reinterpret_cast<const uint64_t *>(d + sb),
-                                           previous ? d_v : nullptr, K, dim, d_v)); // (in place: the aliasing form)
-    OI_HIP_CHECK(hipMemcpyAsync(out, d_v, vb, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipStreamSynchronize(st));
-    return OI_OK;
+    const size_t vb = sizeof(float) * (size_t)K * dim;
+    return staged_call(ctx, "centroids_io", 16, {{sums, sizeof(int64_t) * (size_t)K * dim}, {counts, sizeof(uint64_t) * (size_t)K}}, {{out, vb}},
+                       [&](void *const *in, void *const *o) -> int { // (in place: `previous` is staged where the output goes, the aliasing form)
+                           float *d_v = part<float>(o, 0);
+                           if (previous) OI_HIP_CHECK(hipMemcpyAsync(d_v, previous, vb, hipMemcpyHostToDevice, ctx->stream));
+                           return oi_launch_centroids_from_sums(ctx, part<const int64_t>(in, 0), part<const uint64_t>(in, 1), previous ? d_v : nullptr,
+                                                                K, dim, d_v);
+                       });
 }
 
 // the loop: assignment (oi_launch_similar_share) and update alternate on the device; the host reads `moved` once per step
@@ -2042,12 +2026,12 @@ extern "C" int oi_narratives_fit(oi_index *idx, const float *seeds, uint32_t K, 
                                  int location, float *centroids_out, oi_social_counters *records_out, uint32_t *labels_out,
                                  oi_narrative_info *info_host) {
     OI_REQUIRE(spec, "narratives_fit: null spec");
-    OI_REQUIRE(K >= 1 && K <= OI_MAX_CENTROIDS, "narratives_fit: n_clusters=%u outside [1,%u]", K, OI_MAX_CENTROIDS);
+    OI_CHECK(check_clusters("narratives_fit", K));
     OI_REQUIRE(spec->max_iters >= 1 && spec->max_iters <= 64, "narratives_fit: max_iters=%u outside [1,64]", spec->max_iters);
     OI_CHECK(similar_check_spec("narratives_fit", spec->threshold, nullptr, false, spec->n_buckets, spec->bucket_width, K, OI_MAX_SUMMARY_CELLS));
     OI_REQUIRE(seeds && centroids_out && records_out && info_host, "narratives_fit: null buffer");
     std::unique_lock<std::mutex> g;
-    OI_CHECK(similar_check_state("narratives_fit", idx, true, (filter || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
+    OI_CHECK(check_index_state("narratives_fit", idx, NEED_ROWS | NEED_SIGNALS, (filter || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
     oi_ctx *ctx = idx->ctx;
     hipStream_t st = ctx->stream;
     OI_HIP_CHECK(hipSetDevice(ctx->device));
@@ -2055,28 +2039,28 @@ extern "C" int oi_narratives_fit(oi_index *idx, const float *seeds, uint32_t K, 
     const uint64_t n = idx->n_docs;
     const uint32_t dim = idx->dim;
     const bool host = location != OI_DEVICE;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t lb = up(sizeof(uint32_t) * (size_t)n), sb = up(sizeof(int64_t) * (size_t)K * dim), cb = up(sizeof(uint64_t) * (size_t)K),
-                 vb = up(sizeof(float) * (size_t)K * dim), fb = up(sizeof(oi_doc_filter) * (size_t)K),
-                 rbytes = sizeof(oi_social_counters) * (size_t)K * spec->n_buckets, rb = host ? up(rbytes) : 0;
+    const size_t lb = sizeof(uint32_t) * (size_t)n, vb = sizeof(float) * (size_t)K * dim, rb = sizeof(oi_social_counters) * (size_t)K * spec->n_buckets;
+    // the workspace: two label arrays | sums | counts | two centroid sets | the filter, K times | moved | the records (OI_HOST)
+    StageLayout lay(256);
+    const size_t at_lab[2] = {lay.add(lb), lay.add(lb)}, at_sums = lay.add(sizeof(int64_t) * (size_t)K * dim), at_counts = lay.add(sizeof(uint64_t) * (size_t)K);
+    const size_t at_c[2] = {lay.add(vb), lay.add(vb)}, at_filt = lay.add(sizeof(oi_doc_filter) * (size_t)K), at_moved = lay.add(256);
+    const size_t at_rec = lay.add(host ? rb : 0);
     DevBuf &w = ctx->buf("narratives");
-    OI_CHECK(w.ensure(2 * lb + sb + cb + 2 * vb + fb + 256 + rb));
-    uint8_t *d = w.as<uint8_t>();
-    uint32_t *d_lab[2] = {reinterpret_cast<uint32_t *>(d), reinterpret_cast<uint32_t *>(d + lb)};
-    int64_t *d_sums = reinterpret_cast<int64_t *>(d + 2 * lb);
-    uint64_t *d_counts = reinterpret_cast<uint64_t *>(d + 2 * lb + sb);
-    float *d_c[2] = {reinterpret_cast<float *>(d + 2 * lb + sb + cb), reinterpret_cast<float *>(d + 2 * lb + sb + cb + vb)};
-    uint4 *d_filt = reinterpret_cast<uint4 *>(d + 2 * lb + sb + cb + 2 * vb);
-    uint64_t *d_moved = reinterpret_cast<uint64_t *>(d + 2 * lb + sb + cb + 2 * vb + fb);
-    oi_social_counters *d_rec = host ? reinterpret_cast<oi_social_counters *>(d + 2 * lb + sb + cb + 2 * vb + fb + 256) : records_out;
+    OI_CHECK(w.ensure(lay.total()));
+    uint32_t *d_lab[2] = {lay.at<uint32_t>(w.p, at_lab[0]), lay.at<uint32_t>(w.p, at_lab[1])};
+    int64_t *d_sums = lay.at<int64_t>(w.p, at_sums);
+    uint64_t *d_counts = lay.at<uint64_t>(w.p, at_counts), *d_moved = lay.at<uint64_t>(w.p, at_moved);
+    float *d_c[2] = {lay.at<float>(w.p, at_c[0]), lay.at<float>(w.p, at_c[1])};
+    uint4 *d_filt = lay.at<uint4>(w.p, at_filt);
+    oi_social_counters *d_rec = host ? lay.at<oi_social_counters>(w.p, at_rec) : records_out;
 
-    OI_HIP_CHECK(hipMemcpyAsync(d_c[0], seeds, sizeof(float) * (size_t)K * dim, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+    OI_HIP_CHECK(hipMemcpyAsync(d_c[0], seeds, vb, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
     if (filter) {
         std::vector<oi_doc_filter> rep(K, *filter);
         OI_HIP_CHECK(hipMemcpyAsync(d_filt, rep.data(), sizeof(oi_doc_filter) * (size_t)K, hipMemcpyHostToDevice, st));
         OI_HIP_CHECK(hipStreamSynchronize(st)); // (rep leaves scope)
     }
-    if (n) OI_HIP_CHECK(hipMemsetAsync(d_lab[1], 0xFF, sizeof(uint32_t) * (size_t)n, st)); // labels_0: nobody is assigned
+    if (n) OI_HIP_CHECK(hipMemsetAsync(d_lab[1], 0xFF, lb, st)); // labels_0: nobody is assigned
     oi_narrative_info info = {0, 0, 0, 0};
     int cur = 0;
     for (uint32_t i = 1;; ++i) {
@@ -2095,32 +2079,31 @@ extern "C" int oi_narratives_fit(oi_index *idx, const float *seeds, uint32_t K, 
         cur ^= 1; // (centroid set and label array swap together: d_lab[cur ^ 1] is now the previous step's)
     }
     const hipMemcpyKind out_kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    OI_HIP_CHECK(hipMemcpyAsync(centroids_out, d_c[cur], sizeof(float) * (size_t)K * dim, out_kind, st));
-    if (host) OI_HIP_CHECK(hipMemcpyAsync(records_out, d_rec, rbytes, hipMemcpyDeviceToHost, st));
-    if (labels_out && n) OI_HIP_CHECK(hipMemcpyAsync(labels_out, d_lab[cur], sizeof(uint32_t) * (size_t)n, out_kind, st));
+    OI_HIP_CHECK(hipMemcpyAsync(centroids_out, d_c[cur], vb, out_kind, st));
+    if (host) OI_HIP_CHECK(hipMemcpyAsync(records_out, d_rec, rb, hipMemcpyDeviceToHost, st));
+    if (labels_out && n) OI_HIP_CHECK(hipMemcpyAsync(labels_out, d_lab[cur], lb, out_kind, st));
     OI_HIP_CHECK(hipStreamSynchronize(st));
     *info_host = info;
     return OI_OK;
 }
 
-// the seeding (seeds.hip): no host synchronise between the steps; one at the end when the caller reads the info
+// the seeding (seeds.hip): no host synchronise between the steps; one at the end when the caller reads the info, which comes
+// from the launcher's own workspace
 extern "C" int oi_narratives_seed(oi_index *idx, uint32_t K, const oi_seed_spec *spec, const oi_doc_filter *filter, int location,
                                   float *seeds_out, uint32_t *rows_out, oi_seed_info *info_host) {
     OI_REQUIRE(spec, "narratives_seed: null spec");
-    OI_REQUIRE(K >= 1 && K <= OI_MAX_CENTROIDS, "narratives_seed: n_clusters=%u outside [1,%u]", K, OI_MAX_CENTROIDS);
+    OI_CHECK(check_clusters("narratives_seed", K));
     OI_REQUIRE(spec->method == OI_SEED_KMEANSPP || spec->method == OI_SEED_FARTHEST, "narratives_seed: method=%u is not an OI_SEED_* value",
                spec->method);
     OI_REQUIRE(spec->trials >= 1 && spec->trials <= OI_MAX_SEED_TRIALS, "narratives_seed: trials=%u outside [1,%u]", spec->trials,
                OI_MAX_SEED_TRIALS);
     OI_REQUIRE(spec->method != OI_SEED_FARTHEST || spec->trials == 1, "narratives_seed: trials=%u with OI_SEED_FARTHEST (must be 1)", spec->trials);
     OI_REQUIRE(spec->reserved == 0, "narratives_seed: reserved=%u (must be 0)", spec->reserved);
-    OI_REQUIRE(spec->n_buckets >= 1 && spec->n_buckets <= OI_MAX_VOLUME_BUCKETS, "narratives_seed: n_buckets=%u outside [1,%u]", spec->n_buckets,
-               OI_MAX_VOLUME_BUCKETS);
-    OI_REQUIRE(spec->bucket_width != 0 || spec->n_buckets == 1, "narratives_seed: bucket_width=0 (no time axis) with n_buckets=%u", spec->n_buckets);
+    OI_CHECK(check_axis("narratives_seed", false, 0, spec->bucket_width, spec->n_buckets, "n_buckets"));
     OI_REQUIRE(seeds_out, "narratives_seed: null buffer");
-    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "narratives_seed: bad location %d", location);
+    OI_CHECK(check_location("narratives_seed", location));
     std::unique_lock<std::mutex> g;
-    OI_CHECK(similar_check_state("narratives_seed", idx, false, (filter || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
+    OI_CHECK(check_index_state("narratives_seed", idx, NEED_ROWS, (filter || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
     oi_ctx *ctx = idx->ctx;
     hipStream_t st = ctx->stream;
     OI_HIP_CHECK(hipSetDevice(ctx->device));
@@ -2128,11 +2111,13 @@ extern "C" int oi_narratives_seed(oi_index *idx, uint32_t K, const oi_seed_spec 
     const size_t vb = sizeof(float) * (size_t)K * idx->dim, rb = sizeof(uint32_t) * (size_t)K;
     float *d_seeds = seeds_out;
     uint32_t *d_rows = rows_out;
-    if (host) {
+    if (host) { // [seeds | rows]: the rows have their room whether or not the caller takes them
+        StageLayout lay(16);
+        const size_t at_seeds = lay.add(vb), at_rows = lay.add(rb);
         DevBuf &io = ctx->buf("seeds_io");
-        OI_CHECK(io.ensure(vb + rb));
-        d_seeds = io.as<float>();
-        d_rows = reinterpret_cast<uint32_t *>(io.as<uint8_t>() + vb);
+        OI_CHECK(io.ensure(lay.total()));
+        d_seeds = lay.at<float>(io.p, at_seeds);
+        d_rows = lay.at<uint32_t>(io.p, at_rows);
     }
     const void *d_info = nullptr;
     OI_CHECK(oi_launch_narratives_seed(idx, K, *spec, filter, d_seeds, d_rows, &d_info));
@@ -2145,18 +2130,12 @@ extern "C" int oi_narratives_seed(oi_index *idx, uint32_t K, const oi_seed_spec 
     return OI_OK;
 }
 
-// ---------------------------------------------------------------- narrative terms (label_terms.hip)
-// The family's order of checks: the spec, the numbers, the buffers, the location, then the handle and its state; all of them
-// precede the first HIP call.  Never captured.
+// ---- narrative terms (label_terms.hip)
 static int label_terms_check_spec(const char *call, const oi_label_terms_spec *spec) {
     if (!spec) { oi_set_error("%s: null spec", call); return OI_ERR_INVALID_ARG; }
     OI_REQUIRE(spec->top >= 1 && spec->top <= OI_MAX_LABEL_TERMS, "%s: top=%u outside [1,%u]", call, spec->top, OI_MAX_LABEL_TERMS);
     OI_REQUIRE(spec->reserved[0] == 0 && spec->reserved[1] == 0, "%s: reserved=%u (must be 0)", call,
                spec->reserved[0] ? spec->reserved[0] : spec->reserved[1]);
-    return OI_OK;
-}
-static int label_terms_check_clusters(const char *call, uint32_t K) {
-    OI_REQUIRE(K >= 1 && K <= OI_MAX_CENTROIDS, "%s: n_clusters=%u outside [1,%u]", call, K, OI_MAX_CENTROIDS);
     return OI_OK;
 }
 static int label_terms_check_cells(const char *call, uint32_t vocab, uint32_t K) {
@@ -2170,118 +2149,85 @@ static int label_terms_check_index(const char *call, oi_index *idx, uint32_t K, 
     if (!idx) { oi_set_error("%s: null index", call); return OI_ERR_INVALID_ARG; }
     OI_CHECK(label_terms_check_cells(call, idx->vocab, K));
     g = std::unique_lock<std::mutex>(idx->ctx->mu);
-    if (!idx->finalized || !idx->cell_start.p || (idx->n_postings && !idx->postings.p)) {
-        oi_set_error("%s: the index is not finalized (oi_index_finalize makes the postings)", call);
-        return OI_ERR_STATE;
-    }
-    return OI_OK;
+    return check_finalized(call, idx, false);
 }
-static size_t lt_up(size_t b) { return (b + 255) & ~(size_t)255; }
 
 extern "C" int oi_label_term_counts(oi_index *idx, const uint32_t *labels, uint32_t K, int location, uint32_t *counts_out, uint64_t *sizes_out) {
-    OI_CHECK(label_terms_check_clusters("label_term_counts", K));
+    OI_CHECK(check_clusters("label_term_counts", K));
     OI_REQUIRE(labels && counts_out && sizes_out, "label_term_counts: null buffer");
-    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "label_term_counts: bad location %d", location);
+    OI_CHECK(check_location("label_term_counts", location));
     std::unique_lock<std::mutex> g;
     OI_CHECK(label_terms_check_index("label_term_counts", idx, K, g));
-    oi_ctx *ctx = idx->ctx;
-    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    OI_HIP_CHECK(hipSetDevice(idx->ctx->device));
     if (location == OI_DEVICE) return oi_launch_label_term_counts(idx, labels, K, counts_out, sizes_out);
-    hipStream_t st = ctx->stream;
-    const size_t lb = lt_up(sizeof(uint32_t) * (size_t)idx->n_docs), tb = sizeof(uint32_t) * (size_t)idx->vocab * K, sb = sizeof(uint64_t) * (size_t)K;
-    DevBuf &w = ctx->buf("label_terms_io");
-    OI_CHECK(w.ensure(lb + lt_up(tb) + sb));
-    uint8_t *d = w.as<uint8_t>();
-    if (idx->n_docs) OI_HIP_CHECK(hipMemcpyAsync(d, labels, sizeof(uint32_t) * (size_t)idx->n_docs, hipMemcpyHostToDevice, st));
-    OI_CHECK(oi_launch_label_term_counts(idx, reinterpret_cast<const uint32_t *>(d), K, reinterpret_cast<uint32_t *>(d + lb),
-                                         reinterpret_cast<uint64_t *>(d + lb + lt_up(tb))));
-    OI_HIP_CHECK(hipMemcpyAsync(counts_out, d + lb, tb, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(sizes_out, d + lb + lt_up(tb), sb, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipStreamSynchronize(st));
-    return OI_OK;
+    return staged_call(idx->ctx, "label_terms_io", 256, {{labels, sizeof(uint32_t) * (size_t)idx->n_docs}},
+                       {{counts_out, sizeof(uint32_t) * (size_t)idx->vocab * K}, {sizes_out, sizeof(uint64_t) * (size_t)K}},
+                       [&](void *const *in, void *const *out) {
+                           return oi_launch_label_term_counts(idx, part<const uint32_t>(in, 0), K, part<uint32_t>(out, 0), part<uint64_t>(out, 1));
+                       });
 }
 
 extern "C" int oi_label_terms_rank(oi_ctx *ctx, const uint32_t *counts, const uint64_t *sizes_host, uint32_t vocab, uint32_t K,
                                    const oi_label_terms_spec *spec, int location, oi_label_term *terms_out, uint32_t *n_out) {
     static_assert(sizeof(oi_label_term) == 24 && sizeof(oi_label_terms_spec) == 16, "the records are 24 bytes, the spec 16");
     OI_CHECK(label_terms_check_spec("label_terms_rank", spec));
-    OI_CHECK(label_terms_check_clusters("label_terms_rank", K));
+    OI_CHECK(check_clusters("label_terms_rank", K));
     OI_CHECK(label_terms_check_cells("label_terms_rank", vocab, K));
     OI_REQUIRE(counts && sizes_host && terms_out && n_out, "label_terms_rank: null buffer");
     unsigned long long A = 0; // (saturating: 256 sizes of 2^64 - 1 must not wrap past the check)
     for (uint32_t c = 0; c < K; ++c) A = A + sizes_host[c] < A ? ~0ull : A + sizes_host[c];
     OI_REQUIRE(A <= 0x7FFFFFFFull, "label_terms_rank: A = %llu assigned rows, more than 2^31 - 1", A);
-    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "label_terms_rank: bad location %d", location);
+    OI_CHECK(check_location("label_terms_rank", location));
     OI_REQUIRE(ctx, "label_terms_rank: null ctx");
     std::lock_guard<std::mutex> g(ctx->mu);
     OI_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t scratch = oi_label_terms_rank_scratch(vocab, K, spec->top);
     DevBuf &ws = ctx->buf("label_terms");
-    OI_CHECK(ws.ensure(scratch));
+    OI_CHECK(ws.ensure(oi_label_terms_rank_scratch(vocab, K, spec->top)));
     if (location == OI_DEVICE)
         return oi_launch_label_terms_rank(ctx, counts, sizes_host, nullptr, vocab, K, spec->top, spec->min_df, ws.p, terms_out, n_out);
-    hipStream_t st = ctx->stream;
-    const size_t tb = lt_up(sizeof(uint32_t) * (size_t)vocab * K), rb = sizeof(oi_label_term) * (size_t)K * spec->top, nb = sizeof(uint32_t) * (size_t)K;
-    DevBuf &w = ctx->buf("label_terms_io");
-    OI_CHECK(w.ensure(tb + lt_up(rb) + nb));
-    uint8_t *d = w.as<uint8_t>();
-    OI_HIP_CHECK(hipMemcpyAsync(d, counts, sizeof(uint32_t) * (size_t)vocab * K, hipMemcpyHostToDevice, st));
-    OI_CHECK(oi_launch_label_terms_rank(ctx, reinterpret_cast<const uint32_t *>(d), sizes_host, nullptr, vocab, K, spec->top, spec->min_df, ws.p,
-                                        reinterpret_cast<oi_label_term *>(d + tb), reinterpret_cast<uint32_t *>(d + tb + lt_up(rb))));
-    OI_HIP_CHECK(hipMemcpyAsync(terms_out, d + tb, rb, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(n_out, d + tb + lt_up(rb), nb, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipStreamSynchronize(st));
-    return OI_OK;
+    return staged_call(ctx, "label_terms_io", 256, {{counts, sizeof(uint32_t) * (size_t)vocab * K}},
+                       {{terms_out, sizeof(oi_label_term) * (size_t)K * spec->top}, {n_out, sizeof(uint32_t) * (size_t)K}},
+                       [&](void *const *in, void *const *out) {
+                           return oi_launch_label_terms_rank(ctx, part<const uint32_t>(in, 0), sizes_host, nullptr, vocab, K, spec->top, spec->min_df,
+                                                             ws.p, part<oi_label_term>(out, 0), part<uint32_t>(out, 1));
+                       });
 }
 
 extern "C" int oi_label_terms(oi_index *idx, const uint32_t *labels, uint32_t K, const oi_label_terms_spec *spec, int location,
                               oi_label_term *terms_out, uint32_t *n_out, uint64_t *sizes_out) {
     OI_CHECK(label_terms_check_spec("label_terms", spec));
-    OI_CHECK(label_terms_check_clusters("label_terms", K));
+    OI_CHECK(check_clusters("label_terms", K));
     OI_REQUIRE(labels && terms_out && n_out, "label_terms: null buffer");
-    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "label_terms: bad location %d", location);
+    OI_CHECK(check_location("label_terms", location));
     std::unique_lock<std::mutex> g;
     OI_CHECK(label_terms_check_index("label_terms", idx, K, g));
     OI_REQUIRE(idx->n_docs <= 0x7FFFFFFFull, "label_terms: n_docs=%llu, more than 2^31 - 1", (unsigned long long)idx->n_docs);
     oi_ctx *ctx = idx->ctx;
-    hipStream_t st = ctx->stream;
     OI_HIP_CHECK(hipSetDevice(ctx->device));
-    const bool host = location != OI_DEVICE;
     const uint32_t vocab = idx->vocab, top = spec->top;
-    const size_t tb = lt_up(sizeof(uint32_t) * (size_t)vocab * K), sb = lt_up(sizeof(uint64_t) * (size_t)K);
-    DevBuf &ws = ctx->buf("label_terms"); // [table | sizes | the rank's scratch]
-    OI_CHECK(ws.ensure(tb + sb + oi_label_terms_rank_scratch(vocab, K, top)));
-    uint8_t *d = ws.as<uint8_t>();
-    uint32_t *d_counts = reinterpret_cast<uint32_t *>(d);
-    uint64_t *d_sizes = reinterpret_cast<uint64_t *>(d + tb);
-    const uint32_t *d_labels = labels;
-    oi_label_term *d_terms = terms_out;
-    uint32_t *d_n = n_out;
-    const size_t lb = lt_up(sizeof(uint32_t) * (size_t)idx->n_docs), rb = sizeof(oi_label_term) * (size_t)K * top, nb = sizeof(uint32_t) * (size_t)K;
-    if (host) {
-        DevBuf &w = ctx->buf("label_terms_io");
-        OI_CHECK(w.ensure(lb + lt_up(rb) + nb));
-        uint8_t *io = w.as<uint8_t>();
-        if (idx->n_docs) OI_HIP_CHECK(hipMemcpyAsync(io, labels, sizeof(uint32_t) * (size_t)idx->n_docs, hipMemcpyHostToDevice, st));
-        d_labels = reinterpret_cast<const uint32_t *>(io);
-        d_terms = reinterpret_cast<oi_label_term *>(io + lb);
-        d_n = reinterpret_cast<uint32_t *>(io + lb + lt_up(rb));
-    }
-    OI_CHECK(oi_launch_label_term_counts(idx, d_labels, K, d_counts, d_sizes));
-    OI_CHECK(oi_launch_label_terms_rank(ctx, d_counts, nullptr, d_sizes, vocab, K, top, spec->min_df, d + tb + sb, d_terms, d_n));
-    if (sizes_out)
-        OI_HIP_CHECK(hipMemcpyAsync(sizes_out, d_sizes, sizeof(uint64_t) * (size_t)K, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
-    if (host) {
-        OI_HIP_CHECK(hipMemcpyAsync(terms_out, d_terms, rb, hipMemcpyDeviceToHost, st));
-        OI_HIP_CHECK(hipMemcpyAsync(n_out, d_n, nb, hipMemcpyDeviceToHost, st));
-        OI_HIP_CHECK(hipStreamSynchronize(st));
-    }
-    return OI_OK;
+    StageLayout lay(256); // [table | sizes | the rank's scratch]
+    const size_t at_table = lay.add(sizeof(uint32_t) * (size_t)vocab * K), at_sizes = lay.add(sizeof(uint64_t) * (size_t)K),
+                 at_scratch = lay.add(oi_label_terms_rank_scratch(vocab, K, top));
+    DevBuf &ws = ctx->buf("label_terms");
+    OI_CHECK(ws.ensure(lay.total()));
+    // counts, rank, then the sizes to the caller (the table and the sizes never leave the device)
+    auto run = [&](const uint32_t *d_labels, oi_label_term *d_terms, uint32_t *d_n, hipMemcpyKind sizes_kind) -> int {
+        uint32_t *d_counts = lay.at<uint32_t>(ws.p, at_table);
+        uint64_t *d_sizes = lay.at<uint64_t>(ws.p, at_sizes);
+        OI_CHECK(oi_launch_label_term_counts(idx, d_labels, K, d_counts, d_sizes));
+        OI_CHECK(oi_launch_label_terms_rank(ctx, d_counts, nullptr, d_sizes, vocab, K, top, spec->min_df, lay.at<void>(ws.p, at_scratch), d_terms, d_n));
+        if (sizes_out) OI_HIP_CHECK(hipMemcpyAsync(sizes_out, d_sizes, sizeof(uint64_t) * (size_t)K, sizes_kind, ctx->stream));
+        return OI_OK;
+    };
+    if (location == OI_DEVICE) return run(labels, terms_out, n_out, hipMemcpyDeviceToDevice);
+    return staged_call(ctx, "label_terms_io", 256, {{labels, sizeof(uint32_t) * (size_t)idx->n_docs}},
+                       {{terms_out, sizeof(oi_label_term) * (size_t)K * top}, {n_out, sizeof(uint32_t) * (size_t)K}},
+                       [&](void *const *in, void *const *out) {
+                           return run(part<const uint32_t>(in, 0), part<oi_label_term>(out, 0), part<uint32_t>(out, 1), hipMemcpyDeviceToHost);
+                       });
 }
 
-// ---------------------------------------------------------------- narrative exemplars (label_exemplars.hip)
-// The family's order of checks: the spec, the numbers, the buffers, the location, then the handle and its state; all of them
-// precede the first HIP call.  OI_DEVICE: no host synchronise anywhere.  Never captured.
+// narrative exemplars (label_exemplars.hip)
 extern "C" int oi_label_exemplars(oi_index *idx, const uint32_t *labels, const float *centroids, uint32_t K, const oi_exemplar_spec *spec,
                                   const oi_doc_filter *filter, int location, float *scores_out, uint32_t *docs_out, uint32_t *counts_out) {
     static_assert(sizeof(oi_exemplar_spec) == 16, "the spec is 16 bytes");
@@ -2289,38 +2235,24 @@ extern "C" int oi_label_exemplars(oi_index *idx, const uint32_t *labels, const f
     OI_REQUIRE(spec->top >= 1 && spec->top <= OI_MAX_DEPTH, "label_exemplars: top=%u outside [1,%u]", spec->top, OI_MAX_DEPTH);
     OI_REQUIRE(spec->reserved[0] == 0 && spec->reserved[1] == 0 && spec->reserved[2] == 0, "label_exemplars: reserved=%u (must be 0)",
                spec->reserved[0] ? spec->reserved[0] : spec->reserved[1] ? spec->reserved[1] : spec->reserved[2]);
-    OI_REQUIRE(K >= 1 && K <= OI_MAX_CENTROIDS, "label_exemplars: n_clusters=%u outside [1,%u]", K, OI_MAX_CENTROIDS);
+    OI_CHECK(check_clusters("label_exemplars", K));
     OI_REQUIRE(labels && centroids && scores_out && docs_out && counts_out, "label_exemplars: null buffer");
-    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "label_exemplars: bad location %d", location);
+    OI_CHECK(check_location("label_exemplars", location));
     std::unique_lock<std::mutex> g;
-    OI_CHECK(similar_check_state("label_exemplars", idx, false, filter ? "a filter needs" : nullptr, g));
-    oi_ctx *ctx = idx->ctx;
-    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    OI_CHECK(check_index_state("label_exemplars", idx, NEED_ROWS, filter ? "a filter needs" : nullptr, g));
+    OI_HIP_CHECK(hipSetDevice(idx->ctx->device));
     const uint32_t top = spec->top;
     if (location == OI_DEVICE) return oi_launch_label_exemplars(idx, labels, centroids, K, top, filter, scores_out, docs_out, counts_out);
-    hipStream_t st = ctx->stream;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t lb = up(sizeof(uint32_t) * (size_t)idx->n_docs), vb = up(sizeof(float) * (size_t)K * idx->dim),
-                 ob = up(sizeof(uint32_t) * (size_t)K * top), cb = sizeof(uint32_t) * (size_t)K;
-    DevBuf &w = ctx->buf("exemplars_io");
-    OI_CHECK(w.ensure(lb + vb + 2 * ob + cb));
-    uint8_t *d = w.as<uint8_t>();
-    if (idx->n_docs) OI_HIP_CHECK(hipMemcpyAsync(d, labels, sizeof(uint32_t) * (size_t)idx->n_docs, hipMemcpyHostToDevice, st));
-    OI_HIP_CHECK(hipMemcpyAsync(d + lb, centroids, sizeof(float) * (size_t)K * idx->dim, hipMemcpyHostToDevice, st));
-    float *d_scores = reinterpret_cast<float *>(d + lb + vb);
-    uint32_t *d_docs = reinterpret_cast<uint32_t *>(d + lb + vb + ob), *d_counts = reinterpret_cast<uint32_t *>(d + lb + vb + 2 * ob);
-    OI_CHECK(oi_launch_label_exemplars(idx, reinterpret_cast<const uint32_t *>(d), reinterpret_cast<const float *>(d + lb), K, top, filter, d_scores,
-                                       d_docs, d_counts));
-    OI_HIP_CHECK(hipMemcpyAsync(scores_out, d_scores, sizeof(float) * (size_t)K * top, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(docs_out, d_docs, sizeof(uint32_t) * (size_t)K * top, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, cb, hipMemcpyDeviceToHost, st));
-    OI_HIP_CHECK(hipStreamSynchronize(st));
-    return OI_OK;
+    return staged_call(idx->ctx, "exemplars_io", 256,
+                       {{labels, sizeof(uint32_t) * (size_t)idx->n_docs}, {centroids, sizeof(float) * (size_t)K * idx->dim}},
+                       {{scores_out, sizeof(float) * (size_t)K * top}, {docs_out, sizeof(uint32_t) * (size_t)K * top}, {counts_out, sizeof(uint32_t) * (size_t)K}},
+                       [&](void *const *in, void *const *out) {
+                           return oi_launch_label_exemplars(idx, part<const uint32_t>(in, 0), part<const float>(in, 1), K, top, filter,
+                                                            part<float>(out, 0), part<uint32_t>(out, 1), part<uint32_t>(out, 2));
+                       });
 }
 
-// ---------------------------------------------------------------- narrative breakdown (label_summary.hip)
-// The family's order of checks: the spec, the numbers, the buffers, the location, then the handle and its state; all of them
-// precede the first HIP call.  OI_DEVICE: no host synchronise anywhere.  Never captured.
+// narrative breakdown (label_summary.hip)
 extern "C" int oi_label_summary(oi_index *idx, const uint32_t *labels, uint32_t K, const oi_label_summary_spec *spec, const oi_doc_filter *filter,
                                 int location, oi_social_counters *records_out, uint32_t *keys_out, uint32_t *counts_out,
                                 uint32_t *qualified_out) {
@@ -2330,60 +2262,33 @@ extern "C" int oi_label_summary(oi_index *idx, const uint32_t *labels, uint32_t 
                spec->axis);
     const bool key_axis = spec->axis == OI_LABEL_AXIS_KEY;
     OI_REQUIRE(spec->reserved == 0, "label_summary: reserved=%u (must be 0)", spec->reserved);
-    if (key_axis) {
-        const uint32_t mask = spec->stamp_origin, run = mask ? mask >> __builtin_ctz(mask) : 0u;
-        OI_REQUIRE(mask != 0 && (run & (run + 1u)) == 0u, "label_summary: key_mask=0x%x is not one contiguous run of bits", mask);
-        OI_REQUIRE(spec->bucket_width == 0, "label_summary: bucket_width=%u on the key axis (must be 0)", spec->bucket_width);
-        const uint64_t key_space = std::min<uint64_t>(1ull << __builtin_popcount(mask), OI_MAX_GROUP_KEYS);
-        OI_REQUIRE(spec->n_cells >= 1 && spec->n_cells <= key_space, "label_summary: n_cells=%u outside [1,%llu] (key_mask=0x%x)", spec->n_cells,
-                   (unsigned long long)key_space, mask);
-        OI_REQUIRE(spec->top <= OI_MAX_DEPTH, "label_summary: top=%u outside [0,%u]", spec->top, OI_MAX_DEPTH);
-    } else {
-        OI_REQUIRE(spec->n_cells >= 1 && spec->n_cells <= OI_MAX_VOLUME_BUCKETS, "label_summary: n_cells=%u outside [1,%u]", spec->n_cells,
-                   OI_MAX_VOLUME_BUCKETS);
-        OI_REQUIRE(spec->bucket_width != 0 || spec->n_cells == 1, "label_summary: bucket_width=0 (no time axis) with n_cells=%u", spec->n_cells);
-        OI_REQUIRE(spec->top == 0, "label_summary: top=%u on the time axis (ranked output is the key axis's)", spec->top);
-    }
+    OI_CHECK(check_axis("label_summary", key_axis, spec->stamp_origin, spec->bucket_width, spec->n_cells, "n_cells"));
+    if (key_axis) OI_REQUIRE(spec->top <= OI_MAX_DEPTH, "label_summary: top=%u outside [0,%u]", spec->top, OI_MAX_DEPTH);
+    else OI_REQUIRE(spec->top == 0, "label_summary: top=%u on the time axis (ranked output is the key axis's)", spec->top);
     OI_REQUIRE(spec->rank_by <= OI_GROUP_RANK_BEARISH, "label_summary: rank_by=%u is not an OI_GROUP_RANK_* value", spec->rank_by);
     OI_REQUIRE(spec->top != 0 || spec->rank_by == 0, "label_summary: rank_by=%u with top=0 (must be 0)", spec->rank_by);
-    OI_REQUIRE(K >= 1 && K <= OI_MAX_CENTROIDS, "label_summary: n_clusters=%u outside [1,%u]", K, OI_MAX_CENTROIDS);
+    OI_CHECK(check_clusters("label_summary", K));
     OI_REQUIRE((uint64_t)K * spec->n_cells <= OI_MAX_GROUP_CELLS, "label_summary: n_clusters * n_cells = %llu cells, more than %u",
                (unsigned long long)K * spec->n_cells, OI_MAX_GROUP_CELLS);
     OI_REQUIRE(labels && records_out, "label_summary: null buffer");
     OI_REQUIRE(spec->top == 0 || (keys_out && counts_out), "label_summary: null buffer (keys_out / counts_out with top=%u)", spec->top);
-    OI_REQUIRE(location == OI_HOST || location == OI_DEVICE, "label_summary: bad location %d", location);
+    OI_CHECK(check_location("label_summary", location));
     std::unique_lock<std::mutex> g;
-    OI_CHECK(similar_check_state("label_summary", idx, true,
-                                 key_axis ? "the key axis needs" : (filter || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g, false));
-    oi_ctx *ctx = idx->ctx;
-    OI_HIP_CHECK(hipSetDevice(ctx->device));
+    OI_CHECK(check_index_state("label_summary", idx, NEED_SIGNALS,
+                               key_axis ? "the key axis needs" : (filter || spec->bucket_width) ? SIMILAR_TIME_AXIS : nullptr, g));
+    OI_HIP_CHECK(hipSetDevice(idx->ctx->device));
     const uint32_t top = spec->top;
     if (location == OI_DEVICE)
         return oi_launch_label_summary(idx, labels, K, *spec, filter, records_out, top ? keys_out : nullptr, top ? counts_out : nullptr,
                                        top ? qualified_out : nullptr);
-    // the host location: [labels | records | keys | counts | qualified] in the call's workspace, every part 256-byte aligned
-    hipStream_t st = ctx->stream;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t per_c = top ? top : spec->n_cells; // records (and, ranked, keys) per cluster
-    const size_t lb = up(sizeof(uint32_t) * (size_t)idx->n_docs), rb = sizeof(oi_social_counters) * (size_t)K * per_c;
-    const size_t kb = top ? up(sizeof(uint32_t) * (size_t)K * per_c) : 0, cb = top ? up(sizeof(uint32_t) * (size_t)K) : 0;
-    DevBuf &w = ctx->buf("label_summary_io");
-    OI_CHECK(w.ensure(lb + up(rb) + kb + 2 * cb));
-    uint8_t *d = w.as<uint8_t>();
-    if (idx->n_docs) OI_HIP_CHECK(hipMemcpyAsync(d, labels, sizeof(uint32_t) * (size_t)idx->n_docs, hipMemcpyHostToDevice, st));
-    oi_social_counters *d_records = reinterpret_cast<oi_social_counters *>(d + lb);
-    uint32_t *d_keys = reinterpret_cast<uint32_t *>(d + lb + up(rb)), *d_counts = reinterpret_cast<uint32_t *>(d + lb + up(rb) + kb),
-             *d_qual = reinterpret_cast<uint32_t *>(d + lb + up(rb) + kb + cb);
-    OI_CHECK(oi_launch_label_summary(idx, reinterpret_cast<const uint32_t *>(d), K, *spec, filter, d_records, top ? d_keys : nullptr,
-                                     top ? d_counts : nullptr, top && qualified_out ? d_qual : nullptr));
-    OI_HIP_CHECK(hipMemcpyAsync(records_out, d_records, rb, hipMemcpyDeviceToHost, st));
-    if (top) {
-        OI_HIP_CHECK(hipMemcpyAsync(keys_out, d_keys, sizeof(uint32_t) * (size_t)K * per_c, hipMemcpyDeviceToHost, st));
-        OI_HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, sizeof(uint32_t) * (size_t)K, hipMemcpyDeviceToHost, st));
-        if (qualified_out) OI_HIP_CHECK(hipMemcpyAsync(qualified_out, d_qual, sizeof(uint32_t) * (size_t)K, hipMemcpyDeviceToHost, st));
-    }
-    OI_HIP_CHECK(hipStreamSynchronize(st));
-    return OI_OK;
+    const size_t kb = top ? sizeof(uint32_t) * (size_t)K * per_c : 0, cb = top ? sizeof(uint32_t) * (size_t)K : 0;
+    return staged_call(idx->ctx, "label_summary_io", 256, {{labels, sizeof(uint32_t) * (size_t)idx->n_docs}},
+                       {{records_out, sizeof(oi_social_counters) * (size_t)K * per_c}, {keys_out, kb}, {counts_out, cb}, {qualified_out, cb}},
+                       [&](void *const *in, void *const *out) { // (dense: keys, counts and qualified are absent)
+                           return oi_launch_label_summary(idx, part<const uint32_t>(in, 0), K, *spec, filter, part<oi_social_counters>(out, 0),
+                                                          part<uint32_t>(out, 1), part<uint32_t>(out, 2), top && qualified_out ? part<uint32_t>(out, 3) : nullptr);
+                       });
 }
 
 // ---------------------------------------------------------------- diagnostics of the bf16 screen

@@ -297,11 +297,19 @@ __global__ __launch_bounds__(LE_SORT_THREADS) void le_sort_kernel(const LeCluste
 }
 
 // ------------------------------------------------------------------ host
-static size_t le_scratch(uint64_t n, uint32_t K, uint32_t dim, uint32_t top, bool bf16) {
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    return 256 + up(sizeof(LeCluster) * (size_t)K) + up(sizeof(uint32_t) * (size_t)K * LE_BINS) + up(sizeof(uint32_t) * (size_t)n) +
-           up(sizeof(uint64_t) * (size_t)K * top) + (bf16 ? up(sizeof(float) * (size_t)K * dim) : 0);
-}
+// the workspace "exemplars": open words | cluster states | hist | keys | slots | rounded centroids (bf16 corpus)
+struct LeWorkspace {
+    StageLayout lay{256};
+    size_t open, clusters, hist, keys, slots, rounded;
+    LeWorkspace(uint64_t n, uint32_t K, uint32_t dim, uint32_t top, bool bf16) {
+        open = lay.add(256);
+        clusters = lay.add(sizeof(LeCluster) * (size_t)K);
+        hist = lay.add(sizeof(uint32_t) * (size_t)K * LE_BINS);
+        keys = lay.add(sizeof(uint32_t) * (size_t)n);
+        slots = lay.add(sizeof(uint64_t) * (size_t)K * top);
+        rounded = lay.add(bf16 ? sizeof(float) * (size_t)K * dim : 0);
+    }
+};
 
 template <int NV, bool BF16>
 static void le_launch_score(oi_ctx *ctx, uint32_t grid, const void *rows, const uint32_t *labels, const uint2 *attrs, uint4 filt, bool has_filt,
@@ -325,19 +333,14 @@ int oi_launch_label_exemplars(oi_index *idx, const uint32_t *d_labels, const flo
     const uint64_t n = idx->n_docs;
     const uint32_t dim = idx->dim;
     const bool bf16 = idx->rows_bf16 != nullptr;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // the workspace: open words | cluster states | hist | keys | slots | rounded centroids (bf16 corpus)
-    const size_t cb = up(sizeof(LeCluster) * (size_t)K), hb = up(sizeof(uint32_t) * (size_t)K * LE_BINS), kb = up(sizeof(uint32_t) * (size_t)n),
-                 sb = up(sizeof(uint64_t) * (size_t)K * top);
+    const LeWorkspace L(n, K, dim, top, bf16);
     DevBuf &ws = ctx->buf("exemplars");
-    OI_CHECK(ws.ensure(le_scratch(n, K, dim, top, bf16)));
-    uint8_t *d = ws.as<uint8_t>();
-    uint32_t *open = reinterpret_cast<uint32_t *>(d); // open[p]: clusters open before pass p (open[0] = 1)
-    LeCluster *cl = reinterpret_cast<LeCluster *>(d + 256);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(d + 256 + cb);
-    uint32_t *keys = reinterpret_cast<uint32_t *>(d + 256 + cb + hb);
-    unsigned long long *slots = reinterpret_cast<unsigned long long *>(d + 256 + cb + hb + kb);
-    float *rounded = reinterpret_cast<float *>(d + 256 + cb + hb + kb + sb);
+    OI_CHECK(ws.ensure(L.lay.total()));
+    uint32_t *open = L.lay.at<uint32_t>(ws.p, L.open); // open[p]: clusters open before pass p (open[0] = 1)
+    LeCluster *cl = L.lay.at<LeCluster>(ws.p, L.clusters);
+    uint32_t *hist = L.lay.at<uint32_t>(ws.p, L.hist), *keys = L.lay.at<uint32_t>(ws.p, L.keys);
+    unsigned long long *slots = L.lay.at<unsigned long long>(ws.p, L.slots);
+    float *rounded = L.lay.at<float>(ws.p, L.rounded);
 
     // the composite's row bits, in whole digits, and the passes of the select
     uint32_t rb = 0;
@@ -345,7 +348,7 @@ int oi_launch_label_exemplars(oi_index *idx, const uint32_t *d_labels, const flo
     const uint32_t passes = (32u + rb) / LE_RADIX_BITS; // 4 .. 8
     static_assert(256 >= sizeof(uint32_t) * (64 / LE_RADIX_BITS + 1), "the open words fit the head of the workspace");
 
-    OI_HIP_CHECK(hipMemsetAsync(d, 0, 256 + cb + hb, st));
+    OI_HIP_CHECK(hipMemsetAsync(ws.p, 0, L.keys, st)); // the open words, the cluster states and the histograms
     const float *cent = d_centroids;
     if (bf16) {
         OI_CHECK(oi_launch_volume_round_queries(ctx, d_centroids, (uint64_t)K * dim, rounded));
@@ -353,7 +356,7 @@ int oi_launch_label_exemplars(oi_index *idx, const uint32_t *d_labels, const flo
     }
     const void *rows = bf16 ? (const void *)idx->rows_bf16 : (const void *)idx->rows;
     const uint2 *attrs = filter ? idx->doc_attrs.as<uint2>() : nullptr;
-    const uint4 filt = filter ? make_uint4(filter->group_mask, filter->group_value, filter->stamp_lo, filter->stamp_hi) : make_uint4(0u, 0u, 0u, 0u);
+    const uint4 filt = oi_filter_words(filter);
     const uint64_t n_ranges = (n + LE_RANGE_ROWS - 1) / LE_RANGE_ROWS;
     if (n) {
         ProfScope ps(ctx, "exemplar_score");

@@ -182,7 +182,7 @@ int oi_launch_label_summary(oi_index *idx, const uint32_t *d_labels, uint32_t K,
         a.attrs = (key_axis || filter || sp.bucket_width) ? idx->doc_attrs.as<uint2>() : nullptr;
         a.sig = idx->signals.as<uint2>();
         a.cells = cells;
-        a.filt = filter ? make_uint4(filter->group_mask, filter->group_value, filter->stamp_lo, filter->stamp_hi) : make_uint4(0u, 0u, 0u, 0u);
+        a.filt = oi_filter_words(filter);
         a.n = n;
         a.n_ranges = (n + LS_RANGE_ROWS - 1) / LS_RANGE_ROWS;
         a.K = K;

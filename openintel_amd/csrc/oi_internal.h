@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "openintel_hip.h"
+#include "oi_stage_layout.h"
 
 // ---------------------------------------------------------------- errors
 void oi_set_error(const char *fmt, ...);
@@ -280,6 +281,11 @@ struct ResultBlock {
         if (dup && dup_out) memcpy(dup_out, dup, K * 4);
     }
 };
+
+// a launch's filter argument: the host's filter by value, zeros without one (the kernels' filtered instantiations read it)
+inline uint4 oi_filter_words(const oi_doc_filter *f) {
+    return f ? make_uint4(f->group_mask, f->group_value, f->stamp_lo, f->stamp_hi) : make_uint4(0u, 0u, 0u, 0u);
+}
 
 // ---------------------------------------------------------------- kernels (host launchers)
 // lexicon.hip

@@ -428,19 +428,18 @@ int oi_launch_narratives_seed(oi_index *idx, uint32_t K, const oi_seed_spec &sp,
     const uint32_t dim = idx->dim, L = sp.trials;
     const bool far = sp.method == OI_SEED_FARTHEST, bf16 = idx->rows_bf16 != nullptr;
     const uint64_t n_ranges = (n + NS_RANGE_ROWS - 1) / NS_RANGE_ROWS;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     // the workspace: state | w | cw (L > 1) | part | far keys (farthest-first) | candidate vectors
-    const size_t wb = up(sizeof(uint32_t) * (size_t)n), cb = L > 1 ? up(sizeof(uint32_t) * (size_t)L * n) : 0,
-                 pb = up(sizeof(uint64_t) * (size_t)L * n_ranges), kb = far ? up(sizeof(uint64_t) * (size_t)n_ranges) : 0,
-                 vb = up(sizeof(float) * (size_t)L * dim);
+    StageLayout lay(256);
+    const size_t at_state = lay.add(256), at_w = lay.add(sizeof(uint32_t) * (size_t)n), at_cw = lay.add(L > 1 ? sizeof(uint32_t) * (size_t)L * n : 0),
+                 at_part = lay.add(sizeof(uint64_t) * (size_t)L * n_ranges), at_far = lay.add(far ? sizeof(uint64_t) * (size_t)n_ranges : 0),
+                 at_cand = lay.add(sizeof(float) * (size_t)L * dim);
     DevBuf &ws = ctx->buf("seeds");
-    OI_CHECK(ws.ensure(256 + wb + cb + pb + kb + vb));
-    uint8_t *d = ws.as<uint8_t>();
-    NsState *state = reinterpret_cast<NsState *>(d);
-    uint32_t *w = reinterpret_cast<uint32_t *>(d + 256), *cw = L > 1 ? reinterpret_cast<uint32_t *>(d + 256 + wb) : nullptr;
-    unsigned long long *part = reinterpret_cast<unsigned long long *>(d + 256 + wb + cb);
-    unsigned long long *far_key = far ? reinterpret_cast<unsigned long long *>(d + 256 + wb + cb + pb) : nullptr;
-    float *cand = reinterpret_cast<float *>(d + 256 + wb + cb + pb + kb);
+    OI_CHECK(ws.ensure(lay.total()));
+    NsState *state = lay.at<NsState>(ws.p, at_state);
+    uint32_t *w = lay.at<uint32_t>(ws.p, at_w), *cw = L > 1 ? lay.at<uint32_t>(ws.p, at_cw) : nullptr;
+    unsigned long long *part = lay.at<unsigned long long>(ws.p, at_part);
+    unsigned long long *far_key = far ? lay.at<unsigned long long>(ws.p, at_far) : nullptr;
+    float *cand = lay.at<float>(ws.p, at_cand);
     *d_info_out = state;
 
     OI_HIP_CHECK(hipMemsetAsync(state, 0, sizeof(NsState), st));
@@ -449,7 +448,7 @@ int oi_launch_narratives_seed(oi_index *idx, uint32_t K, const oi_seed_spec &sp,
     if (n == 0) return OI_OK; // found = 0, eligible = 0
     const void *rows = bf16 ? (const void *)idx->rows_bf16 : (const void *)idx->rows;
     const uint2 *attrs = (filter || sp.bucket_width) ? idx->doc_attrs.as<uint2>() : nullptr;
-    const uint4 filt = filter ? make_uint4(filter->group_mask, filter->group_value, filter->stamp_lo, filter->stamp_hi) : make_uint4(0u, 0u, 0u, 0u);
+    const uint4 filt = oi_filter_words(filter);
     // four workgroups of four waves per CU, each with NS_UNROLL rows in flight; a workgroup holds at most 32 KB of LDS
     const uint32_t grid = (uint32_t)std::min<uint64_t>(n_ranges, (uint64_t)ctx->num_cus * 4);
     {

@@ -549,3 +549,35 @@ def test_the_reference_fixture_as_one_ticker_among_others(dim):
     assert sorted(r.ticker for r in everyone.ranked) == sorted(names)
     vals = [r.rank_metric for r in everyone.ranked]
     assert vals == sorted(vals, reverse=True)
+
+
+# ------------------------------------------------------------------ the host location, dense and ranked, with and without qualified
+def test_host_location_is_the_device_location_bit_for_bit_dense_and_ranked():
+    """300 rows (a ragged last block of 64), dim 64, 2 queries, 4 keys.  Dense (top == 0: no keys, counts or qualified) and ranked:
+    OI_HOST gives OI_DEVICE's bytes; ranked without qualified_out: records, keys and counts are as they were."""
+    import ctypes as C
+    import torch
+    from openintel_amd import _lib
+    ctx = _ctx()
+    n, dim, B, mask, nk, t, top = 300, 64, 2, 0xFF00, 4, 0.5, 3
+    rows, q = _ints(n, dim, B, seed=92)
+    sig, group = _signals(n, 92), _groups(n, 6, mask, 92)          # keys 4 and 5 belong to no cell
+    idx = _index(ctx, rows, sig, group)
+    dq = torch.from_numpy(q).cuda()
+    host = idx.similar_groups(q, t, mask, nk)
+    dev = idx.similar_groups(dq, t, mask, nk)
+    ctx.synchronize()
+    _same(host, _ref(_exact_scores(rows, q), t, sig, group, mask, nk))
+    assert (host["total"] > 0).all()
+    assert np.ascontiguousarray(_host(dev)).tobytes() == host.tobytes()
+    ranked = idx.similar_groups(q, t, mask, nk, top=top)
+    d_ranked = idx.similar_groups(dq, t, mask, nk, top=top)
+    ctx.synchronize()
+    _same_ranking(ranked, host, top, "total", 0)
+    for f in ("keys", "records", "counts", "qualified"):
+        assert np.ascontiguousarray(_host(getattr(d_ranked, f))).tobytes() == getattr(ranked, f).tobytes(), f
+    spec = _lib.GroupsSpec(t, mask, nk, top, 0, 0)
+    rec, keys, counts = np.zeros((B, top), _dtype()), np.zeros((B, top), np.uint32), np.zeros(B, np.uint32)
+    _lib.check(idx.lib.oi_similar_groups(idx.handle, _lib.ptr(q), B, C.byref(spec), None, None, _lib.OI_HOST, _lib.ptr(rec), _lib.ptr(keys),
+                                         _lib.ptr(counts), None))
+    assert rec.tobytes() == ranked.records.tobytes() and keys.tobytes() == ranked.keys.tobytes() and counts.tobytes() == ranked.counts.tobytes()

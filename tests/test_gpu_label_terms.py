@@ -400,3 +400,23 @@ def test_an_unfinalized_index_is_a_state_error_and_the_ctx_stays_usable():
     counts, sizes = idx.label_term_counts(lab, 4)
     assert _same(counts, ref_counts) and _same(sizes, ref_sizes)
     idx.close()
+
+
+def test_host_location_without_sizes_out_is_the_device_location_bit_for_bit():
+    """300 documents, vocab 50, 3 clusters: OI_HOST gives OI_DEVICE's bytes, and with sizes_out NULL the records and n are as
+    they were."""
+    import ctypes as C
+    from openintel_amd import _lib
+    n, vocab, K, top = 300, 50, 3, 10
+    corp, idx = _built(n, vocab)
+    lab = _labels(n, K, seed=9)
+    rec, cnt, sizes = idx.label_terms(lab, K, top=top)
+    d_rec, d_cnt, d_sizes = _host_terms(*idx.label_terms(_dev(lab), K, top=top))
+    ref_counts, ref_sizes = _ref_table(corp, lab, K)
+    ref_rec, ref_n = _ref_rank(ref_counts, ref_sizes, top, 1)
+    assert _same(rec, ref_rec) and _same(cnt, ref_n) and _same(sizes, ref_sizes) and int(cnt.sum()) > 0
+    assert _same(d_rec, rec) and _same(d_cnt, cnt) and _same(d_sizes, sizes)
+    spec = _lib.LabelTermsSpec(top, 1, (C.c_uint32 * 2)(0, 0))
+    rec2, cnt2 = np.zeros((K, top), _dtype()), np.zeros(K, np.uint32)
+    _lib.check(idx.lib.oi_label_terms(idx.handle, _lib.ptr(lab), K, C.byref(spec), _lib.OI_HOST, _lib.ptr(rec2), _lib.ptr(cnt2), None))
+    assert _same(rec2, rec) and _same(cnt2, cnt)

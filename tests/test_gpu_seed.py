@@ -507,3 +507,23 @@ def test_argument_errors_name_the_number_and_launch_nothing():
     ran = {t: ctx.profile_read(t)[1] for t in ("seed_init", "seed_score", "seed_pick")}
     ctx.profile_reset(False)
     assert ran == {"seed_init": 1, "seed_score": 4, "seed_pick": 5}, ran
+
+
+def test_host_location_without_rows_and_info_is_the_device_location_bit_for_bit():
+    """300 rows (a ragged last block of 64), dim 64, 3 clusters: OI_HOST gives OI_DEVICE's bytes, and with rows_out and
+    info_host both NULL the seeds are as they were."""
+    import ctypes as C
+    from openintel_amd import _lib
+    rows, _ = _exact(64, 300, C=3, rs=12)
+    ctx = _ctx()
+    idx = _index(ctx, rows)
+    full = idx.seed_narratives(3, trials=2, seed=5)
+    dev = idx.seed_narratives(3, trials=2, seed=5, device=True)
+    ctx.synchronize()
+    _check(full, _emulate(rows, 3, KMEANSPP, 2, 5), "host")
+    assert _host(dev.seeds, np.float32).tobytes() == full.seeds.tobytes() and _host(dev.rows, np.uint32).tobytes() == full.rows.tobytes()
+    assert (dev.found, dev.eligible, dev.potential) == (full.found, full.eligible, full.potential) and full.found == 3
+    spec = _lib.SeedSpec(_lib.OI_SEED_KMEANSPP, 2, 5, 0, 0, 1, 0)
+    seeds = np.full((3, 64), 7.0, np.float32)
+    _lib.check(idx.lib.oi_narratives_seed(idx.handle, 3, C.byref(spec), None, _lib.OI_HOST, _lib.ptr(seeds), None, None))
+    assert seeds.tobytes() == full.seeds.tobytes()

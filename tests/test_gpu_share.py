@@ -699,3 +699,28 @@ def test_the_gated_fallback_without_labels_then_a_screened_call():
     got, ran, _ = _ran(ctx, lambda: idx.similar_share(q, t, labels=True))
     _same_both(got, _ref(_exact_scores(rows, q), t, sig))
     assert "share" in ran and "share_exact" not in ran, ran
+
+
+# ------------------------------------------------------------------ the host location, with and without its optional output
+def test_host_location_with_and_without_labels_is_the_device_location_bit_for_bit():
+    """300 rows (a ragged last block of 64), dim 64, 2 queries, 4 buckets: OI_HOST gives OI_DEVICE's bytes, and leaving
+    labels_out out leaves the records as they are, in both locations."""
+    import torch
+    ctx = _ctx()
+    n, dim, B, t = 300, 64, 2, 0.5
+    rows, q = _ints(n, dim, B, seed=91)
+    sig = _signals(n, 91)
+    stamp = (1000 + np.arange(n) % 50).astype(np.uint32)           # buckets of 10 from 1000: a fifth of the rows has none
+    idx = _index(ctx, rows, sig, np.zeros(n, np.uint32), stamp)
+    kw = dict(n_buckets=4, stamp_origin=1000, bucket_width=10)
+    dq = torch.from_numpy(q).cuda()
+    h_rec, h_lab = idx.similar_share(q, t, labels=True, **kw)
+    d_rec, d_lab = idx.similar_share(dq, t, labels=True, **kw)
+    ctx.synchronize()
+    _same_both((h_rec, h_lab), _ref(_exact_scores(rows, q), t, sig, 4, 1000, 10, stamp))
+    assert int(h_rec["total"].sum()) > 0 and (h_lab == NO_LABEL).any()
+    assert _host(d_rec).tobytes() == h_rec.tobytes() and _host_labels(d_lab).tobytes() == h_lab.tobytes()
+    h_only = idx.similar_share(q, t, **kw)
+    d_only = idx.similar_share(dq, t, **kw)
+    ctx.synchronize()
+    assert h_only.tobytes() == h_rec.tobytes() and _host(d_only).tobytes() == h_rec.tobytes()
